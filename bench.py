@@ -8,6 +8,10 @@ HERA-350 x 1024-channel x 1e4-source workload (SURVEY.md 8(d) config 3, fp32 wit
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W        (the driver's launcher: only its RANK / WORLD_SIZE are used)
 
+--dump-outputs DIR writes, after the timed steps, the visibilities the last step computed as DIR/vis_real.npy and DIR/vis_imag.npy
+(with --want-grad also grad_real / grad_imag): global baseline order, float32 for fp32 and float64 for fp64, all baselines or a fixed
+seeded sample of them within 48 MiB.  The inputs are seeded, so two builds run with the same arguments can be compared array for array.
+
 A "step" is one snapshot: one pass of the hot path (prep + pack + sky-sum kernel) over the whole
 sky with all inputs already resident in HBM.  With N > 1 the baselines are sharded (one process per GPU, the reference's pp.key='bl'
 model, scripts/run_prisim.py:1775-1791; groups of 256 baselines dealt round-robin so that every rank gets its share of the long ones),
@@ -29,7 +33,7 @@ Rank 0 prints ONE JSON line.  Beside the contract's keys it carries (N = 1 only,
   cpu_baseline_ref_xN       the reference's parallel model: N such processes side by side over baseline chunks (mpirun, run_prisim.py:1749-1791)
   e2e                       the same snapshots through InterferometerArray.observe(), host geometry and sky staging included
   e2e_host                  the same with every snapshot landing in (pinned) HOST memory: downloads overlapped with the next sky-sum
-  delay_ps                  delay power spectra of the K resident snapshots (interferometry.py:8114-8134 + delay_spectrum.py:3992):
+  delay_ps                  delay power spectra of the resident snapshots (interferometry.py:8114-8134 + delay_spectrum.py:3992):
                             device time, FFT count, achieved algorithmic GB/s against the 8 TB/s HBM roofline
   other_kernels             min / median of 5 timed launches each of the fp64 kernel (headline sky), the fused gradient kernels, and -- on config 3
                             with its nside-128 diffuse half -- the packed fp32 taper kernel and the grouped fp64 taper kernel: the kernels the
@@ -854,6 +858,60 @@ def gather_rehearsal(cfg, zen, prec, device, nsnap=12):
     return res
 
 
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs writes at most this much (the contract allows 64 MB)
+DUMP_SEED = 20240607              # fixes the baseline rows sampled when the whole last snapshot does not fit the budget
+CUBE_BUDGET_BYTES = 32 << 30      # one rank's resident snapshot cube; at N = 1 the timed steps cycle through a ring this size
+
+
+def dump_rows(nbl, nchan, itemsize, ncube):
+    """Global baseline rows --dump-outputs writes: all of them when they fit the budget, else a fixed seeded sample (increasing)."""
+    per_row = nchan * 2 * itemsize * ncube
+    n = max(1, min(nbl, DUMP_BUDGET_BYTES // per_row))
+    if n == nbl:
+        return NP.arange(nbl, dtype=NP.int64)
+    return NP.sort(NP.random.default_rng(DUMP_SEED).choice(nbl, size=n, replace=False)).astype(NP.int64)
+
+
+def dump_outputs(path, ctx, slot, c64, want_grad, nbl_total, world, rank, rdzv):
+    """What the timed path computed in its last step, in the global baseline order a caller receives (the gathered cube at N > 1):
+    vis_real / vis_imag (rows, nchan) and, with --want-grad, grad_real / grad_imag (3, rows, nchan) -- float32 for fp32, float64 for fp64.
+    At N > 1 every rank sends the sampled rows of its own shard to rank 0 (the rows the gathered cube holds: gather_ok checks that)."""
+    import io
+    got = ctx.get_vis(slot=slot, want_grad=want_grad, complex64=c64)
+    vis, grad = got if want_grad else (got, None)
+    ftype = NP.float32 if c64 else NP.float64
+    rows = dump_rows(nbl_total, vis.shape[1], NP.dtype(ftype).itemsize, 4 if want_grad else 1)
+    idx_mine = sharding.shard_index(nbl_total, world, rank)
+    pos = NP.flatnonzero(NP.isin(idx_mine, rows))
+    part = {'idx': idx_mine[pos], 'vis': vis[pos]}
+    if want_grad:
+        part['grad'] = grad[:, pos]
+    if world > 1:
+        buf = io.BytesIO()
+        NP.savez(buf, **part)
+        parts = [dict(NP.load(io.BytesIO(b))) for b in rdzv.allgather_bytes(buf.getvalue())]
+    else:
+        parts = [part]
+    if rank != 0:
+        return None
+    idx = NP.concatenate([p['idx'] for p in parts])
+    order = NP.argsort(idx)
+    if not NP.array_equal(idx[order], rows):
+        raise RuntimeError('--dump-outputs: the ranks do not hold the sampled baselines')
+    arrays = {'vis': NP.concatenate([p['vis'] for p in parts])[order]}
+    if want_grad:
+        arrays['grad'] = NP.concatenate([p['grad'] for p in parts], axis=1)[:, order]
+    os.makedirs(path, exist_ok=True)
+    names = []
+    for key, a in arrays.items():
+        for part_name, comp in (('real', a.real), ('imag', a.imag)):
+            name = '%s_%s' % (key, part_name)
+            NP.save(os.path.join(path, name + '.npy'), NP.ascontiguousarray(comp, dtype=ftype))
+            names.append(name)
+    return {'dir': path, 'arrays': names, 'dtype': NP.dtype(ftype).name, 'baselines': int(rows.size), 'of_baselines': int(nbl_total),
+            'sample_seed': DUMP_SEED if rows.size < nbl_total else None}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -872,7 +930,14 @@ def main():
                          "(kept under profiles/ once per round: they add a minute)")
     ap.add_argument('--chan-tile', type=int, default=0, help='A/B hook: force the channel tile of the recurrence kernels (0 = planned)')
     ap.add_argument('--want-grad', action='store_true', help='profiling hook: every step also computes the baseline gradient (fused kernel)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (a seeded sample of baselines beyond %d MB)'
+                         % (DUMP_BUDGET_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # launched bare: become the launcher.  N rank processes are started BEFORE anything here touches the GPU (this process never
@@ -906,13 +971,19 @@ def main():
     bl_mine, n_real = shard_baselines(bl_all, world, rank)
     prec = _abi.PRISIM_FP32 if args.precision == 'fp32' else _abi.PRISIM_FP64
     dtype = 'f32' if args.precision == 'fp32' else 'f64'
-    K, Wm = max(1, args.steps), max(0, args.warmup)
+    K, Wm = args.steps, args.warmup
+    # Snapshot t lands in slot t % R of the resident cube.  At N = 1 the cube is a ring bounded by CUBE_BUDGET_BYTES, so that --steps sets
+    # the number of timed steps however large it is; at N > 1 every step keeps its own slot (a slot's all-gather may still be in
+    # flight on the communication stream when a later step would reuse it).
+    slot_bytes = bl_mine.shape[0] * nchan * 16 * (4 if args.want_grad else 1)
+    R = K if world > 1 else max(1, min(K, CUBE_BUDGET_BYTES // slot_bytes))
+    last = (K - 1) % R
     zen = NP.array([0.0, 0.0, 1.0])
 
     # PRISIM_BENCH_DEVICE: rehearsal hook (several ranks on one GPU to exercise the multi-process flow on a 1-GPU box)
     device = int(os.environ.get('PRISIM_BENCH_DEVICE', local_rank))
     ctx = _abi.Context(device)
-    ctx.set_array(bl_mine, ch, nt_max=K)
+    ctx.set_array(bl_mine, ch, nt_max=R)
     if args.chan_tile:
         ctx.set_tuning(args.chan_tile, 0, 0)
     # inputs resident in HBM before the timed region: directions, reference fluxes, spectral indices;
@@ -969,9 +1040,9 @@ def main():
 
     wg = bool(args.want_grad)
     for i in range(Wm):
-        ctx.compute(precision=prec, slot=i % K, want_grad=wg)
+        ctx.compute(precision=prec, slot=i % R, want_grad=wg)
         if world > 1:
-            ctx.allgather_slot_async(i % K, complex64=c64)
+            ctx.allgather_slot_async(i % R, complex64=c64)
     ctx.sync()
     ctx.timing(reset=True)
     if world > 1:
@@ -981,7 +1052,7 @@ def main():
     ctx.sync()
     t0 = time.perf_counter()
     for t in range(K):
-        ctx.compute(precision=prec, slot=t, want_grad=wg)
+        ctx.compute(precision=prec, slot=t % R, want_grad=wg)
         if world > 1:
             # RCCL all-gather of snapshot t on the communication stream, overlapped with the sky-sum of snapshot t+1;
             # only the last snapshot's exchange is exposed.  Still inside the timed region.
@@ -1032,6 +1103,9 @@ def main():
         idx_mine = sharding.shard_index(nbl_total, world, rank)
         gather_ok = gather_ok and g.shape[0] == nbl_total
         gather_ok = gather_ok and bool(all(rdzv.allgather(bool(NP.array_equal(g[idx_mine], mine[:n_real])))))
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, ctx, last, c64, wg, nbl_total, world, rank, rdzv)
 
     if rank == 0:
         terms_total = float(nbl_total) * nchan * nsrc * K
@@ -1077,6 +1151,8 @@ def main():
                                             'ratio update 2)')
         out['kernel_ms_per_rank'] = {'min': min(rank_kern_ms), 'max': max(rank_kern_ms), 'all': rank_kern_ms}
         out['plan_per_rank'] = rank_plan
+        if dumped is not None:
+            out['dump_outputs'] = dumped
         out['value_n1_equiv'] = value / world           # whole-job rate per GPU: what to hold against the N = 1 line
         if world > 1:
             out['gather'] = gstats
@@ -1103,7 +1179,7 @@ def main():
                 state['pb_host'] = ctx.get_pbflux()
                 cb, bls, ref, stride = cpu_baseline(cfg, lambda: state['pb_host'])
                 # parity spot-check of the timed GPU result against the checker on the same sample
-                vis = ctx.get_vis(slot=K - 1)
+                vis = ctx.get_vis(slot=last)
                 gpu = vis[::stride][:bls.shape[0]]
                 scale = NP.sum(NP.abs(state['pb_host']), axis=0)[None, :]
                 out['parity_max_err_rel_sumflux'] = float(NP.max(NP.abs(gpu - ref) / scale))
@@ -1112,7 +1188,7 @@ def main():
 
             def x_cpu_ref():
                 cbr, sel, ref2 = cpu_baseline_reference_formulation(cfg, state['pb_host'])
-                cbr['parity_of_gpu_vs_this_max_err_rel_sumflux'] = float(NP.max(NP.abs(ctx.get_vis(slot=K - 1)[sel] - ref2)
+                cbr['parity_of_gpu_vs_this_max_err_rel_sumflux'] = float(NP.max(NP.abs(ctx.get_vis(slot=last)[sel] - ref2)
                                                                                 / NP.sum(NP.abs(state['pb_host']), axis=0)[None, :]))
                 state['t_one'] = cbr.pop('seconds_per_baseline')
                 return cbr
@@ -1122,14 +1198,14 @@ def main():
                 if state['t_one'] is None:
                     raise RuntimeError('the one-process leg failed')
                 cbx, selx, refx = cpu_baseline_ref_xn(cfg, state['pb_host'], state['t_one'])
-                cbx['parity_of_gpu_vs_this_max_err_rel_sumflux'] = float(NP.max(NP.abs(ctx.get_vis(slot=K - 1)[selx] - refx)
+                cbx['parity_of_gpu_vs_this_max_err_rel_sumflux'] = float(NP.max(NP.abs(ctx.get_vis(slot=last)[selx] - refx)
                                                                                 / NP.sum(NP.abs(state['pb_host']), axis=0)[None, :]))
                 return cbx
             if full:
                 extra('cpu_baseline_ref_xN', x_cpu_ref_xn, {'value': None, 'unit': 'terms/s', 'cores': 0, 'kind': 'reference-formulation x N', 'sample': 'failed'})
 
             def x_delay_ps():
-                # delay power spectra of the K resident snapshots, one window for all baselines, pad = 1 (run_prisim.py:954, 2284)
+                # delay power spectra of the R resident snapshots, one window for all baselines, pad = 1 (run_prisim.py:954, 2284)
                 # in K^2 (Mpc/h)^3: abs(.)^2 * jacobian1 * jacobian2 * Jy2K^2 (delay_spectrum.py:3659-3663, 3992) -- redshift, comoving
                 # distances, and the beam volume of the Airy pattern on a HEALPix nside-32 grid (evaluated on the device) on the host
                 from prisim_amd import delay_spectrum as DSM
@@ -1137,13 +1213,13 @@ def main():
                 pconst = DSM.power_constants(ch, {'id': 'hera'}, freq_wts=win, device=device)
                 ms = []
                 for rep in range(4):
-                    ctx.delay_transform_device(K, bpwts=win, pad=1.0, want_lag=False, want_power=True, power_scale=pconst['factor'])
+                    ctx.delay_transform_device(R, bpwts=win, pad=1.0, want_lag=False, want_power=True, power_scale=pconst['factor'])
                     ctx.sync()
                     if rep:
                         ms.append(ctx.timing()['last_delay_ms'])
                 tmd = ctx.timing()
                 med = float(NP.median(ms))
-                nrow = K * bl_mine.shape[0]
+                nrow = R * bl_mine.shape[0]
                 dbytes = float(nrow) * nchan * (16 + 8)            # each visibility read once, each power sample written once
                 gbs = dbytes / (med * 1e-3) / 1e9
                 return {'device_ms': med, 'device_ms_spread': spread(ms), 'ffts': nrow, 'fft_length_kept': nchan, 'pad': 1.0,

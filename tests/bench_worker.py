@@ -3,6 +3,7 @@ socket rendezvous, the hand-over of the communicator id, the timed loop with its
 JSON line of the contract -- with a stand-in for the GPU context that has no kernels behind it: compute() writes a pattern that is a
 function of the rank's own baseline shard, and the exchange goes through files in a directory every rank can see.  What this does not
 cover is exactly what needs the hardware: the HIP kernels (tests -m gpu) and RCCL itself."""
+import json
 import os
 import sys
 import time
@@ -33,9 +34,12 @@ class PatternContext(object):
         self.device = device
         self._n = 0
         self._gathered = {}
+        self._timed_slots = []
 
     def close(self):
-        pass
+        # the slots written since the last timing(reset=True), i.e. by the timed steps: tests/test_distributed_cpu.py counts them
+        with open(os.path.join(XDIR, 'timed_slots_%d.json' % getattr(self, 'rank', 0)), 'w') as f:
+            json.dump({'nt_max': self.nt_max, 'slots': self._timed_slots}, f)
 
     def set_array(self, baselines, freqs_hz, nt_max=1):
         self.bl = NP.asarray(baselines, dtype=NP.float64)                        # every baseline (the shard map speaks of rows), a thinned
@@ -66,6 +70,7 @@ class PatternContext(object):
 
     def compute(self, precision=0, kernel=0, want_grad=False, slot=0):
         self._n += 1
+        self._timed_slots.append(int(slot))
         self.cube[slot] = (self.bl[:, 0:1] * (1 + slot) + 1j * (self.bl[:, 1:2] + self.ch[None, :] * 1e-9)).astype(NP.complex64)
 
     def allgather_slot_async(self, slot, complex64=False):
@@ -98,6 +103,8 @@ class PatternContext(object):
         pass
 
     def timing(self, reset=False):
+        if reset:
+            self._timed_slots = []
         return {'sum_kernel_ms': 1.0 * self._n, 'n_kernel': self._n, 'last_chan_tile': 64, 'last_nsplit': 1, 'last_kernel_ms': 1.0,
                 'last_terms': 0, 'last_taper_group': 0, 'last_delay_ms': 0.0, 'last_delay_fused': 0}
 

@@ -139,3 +139,44 @@ def test_bench_main_reports_a_gather_that_differs_between_ranks(tmp_path):
     codes, lines, errs, json = _bench_ranks(tmp_path, 2, mode='rank1_differs')
     assert codes == [0, 0], errs
     assert json.loads(lines[0][0])['gather_ok'] is False
+
+
+def test_bench_dump_outputs_hold_the_last_step_whatever_the_world_size(tmp_path):
+    """--dump-outputs: the last timed snapshot in the global baseline order a caller receives (the gathered cube at N > 1): the same
+    arrays at world size 1 and 3, and what the stand-in wrote into the last slot, row for row."""
+    import json
+    import numpy as NP
+    sys.path.insert(0, ROOT)
+    from prisim_amd import workloads as W
+    got = {}
+    for n in (1, 3):
+        sub = tmp_path / ('n%d' % n)
+        sub.mkdir()
+        codes, lines, errs, _ = _bench_ranks(sub, n, extra=('--dump-outputs', str(sub / 'out')))
+        assert codes == [0] * n, errs
+        d = json.loads(lines[0][0])['dump_outputs']
+        assert d['arrays'] == ['vis_real', 'vis_imag'] and d['dtype'] == 'float32' and d['baselines'] == d['of_baselines'] == 61075
+        assert sorted(os.listdir(str(sub / 'out'))) == ['vis_imag.npy', 'vis_real.npy']
+        got[n] = [NP.load(str(sub / 'out' / (k + '.npy'))) for k in d['arrays']]
+    cfg = W.config3(nsrc=16)
+    bl, ch = cfg['baselines'], cfg['channels'][::64]
+    want = (bl[:, 0:1] * 2 + 1j * (bl[:, 1:2] + ch[None, :] * 1e-9)).astype(NP.complex64)       # the stand-in's pattern for slot 1
+    for n in (1, 3):
+        assert got[n][0].dtype == NP.float32 and NP.array_equal(got[n][0], want.real) and NP.array_equal(got[n][1], want.imag)
+
+
+def test_bench_steps_sets_the_timed_steps(tmp_path):
+    """--steps K runs K timed steps however many snapshots the resident cube holds (one GPU: a ring of slots), and K < 1 is refused."""
+    import json
+    codes, lines, errs, _ = _bench_ranks(tmp_path, 1, extra=('--steps', '40'))
+    assert codes == [0], errs
+    d = json.loads(lines[0][0])
+    assert d['steps'] == 40 and d['config']['nt'] == 40 and d['ms_per_step'] > 0
+    with open(str(tmp_path / 'timed_slots_0.json')) as f:
+        rec = json.load(f)
+    assert 2 <= rec['nt_max'] < 40 and len(rec['slots']) == 40                 # 40 computes, into a ring of slots (1 GB each here)
+    assert rec['slots'] == [t % rec['nt_max'] for t in range(40)]
+    sub = tmp_path / 'zero'
+    sub.mkdir()
+    codes, lines, errs, _ = _bench_ranks(sub, 1, extra=('--steps', '0'))
+    assert codes == [2] and lines == [[]] and '--steps' in errs[0]

@@ -187,16 +187,14 @@ def test_shipped_yaml_files_describe_the_baseline_configs():
 def test_stock_partition_keys_run_on_baseline_shards(monkeypatch):
     """defaultparms.yaml:939 ships pp.key 'freq' (loop at run_prisim.py:1858-1995; 'src' :1996-2080).  The key only chooses how the sum is
     cut: the run proceeds on baseline shards with a warning naming the substitution, and gives the visibilities of pp.key 'bl' exactly.
-    When the reference tree is at hand (the build container; never on the GPU box) its own defaultparms.yaml is what gets loaded."""
+    The reference's stock defaultparms.yaml is loaded from its values stored in tests/golden (tests/golden/make_defaultparms.py)."""
     import warnings
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import fake_context
     from prisim_amd import _abi
     monkeypatch.setattr(_abi, 'Context', fake_context.OracleContext)
-    stock = '/root/reference/prisim/examples/simparms/defaultparms.yaml'
-    if os.path.exists(stock):
-        ref = driver.load_parms(stock)
-        assert ref['pp']['key'] == 'freq'
+    ref = driver.load_parms(os.path.join(ROOT, 'tests', 'golden', 'defaultparms.yaml'))
+    assert ref['pp']['key'] == 'freq'
     base = driver.load_parms(os.path.join(EX, 'config1.yaml'))
     base['array']['file'] = os.path.join(EX, 'config1_layout.txt')
     base['catalog']['custom_file'] = os.path.join(EX, 'config1_catalog.txt')

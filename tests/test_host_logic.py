@@ -798,3 +798,15 @@ def test_frozen_sky_model_is_recognised_by_identity_and_edits_are_still_seen(mon
     assert ia._catalog_key == ia._catalog_fingerprint(sm)
     v = NP.array(ia.skyvis_freq)
     assert v.shape == (2, 8, 2) and NP.all(NP.isfinite(v))
+
+
+def test_bench_dump_sample_is_fixed_and_inside_the_budget():
+    """bench.py --dump-outputs: the whole snapshot when it fits, else the same seeded, increasing set of distinct baselines on every call,
+    and never more than 64 MB of arrays (fp32 and fp64 headline cubes, with and without the three gradient components)."""
+    assert NP.array_equal(bench.dump_rows(300, 16, 4, 1), NP.arange(300))
+    for itemsize in (4, 8):
+        for ncube in (1, 4):
+            rows = bench.dump_rows(61075, 1024, itemsize, ncube)
+            assert 0 < rows.size < 61075 and rows.size * 1024 * 2 * itemsize * ncube <= 64e6
+            assert NP.all(NP.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 61075
+            assert NP.array_equal(rows, bench.dump_rows(61075, 1024, itemsize, ncube))
