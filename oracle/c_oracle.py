@@ -37,6 +37,9 @@ def _declare(lib):
     lib.oracle_skyvis_f64.restype = C.c_int
     lib.oracle_skyvis_f64.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.oracle_skyvis_grad_f64.restype = C.c_int
+    lib.oracle_skyvis_grad_f64.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.oracle_max_threads.restype = C.c_int
 
 
@@ -55,7 +58,9 @@ def max_threads():
     return _load().oracle_max_threads()
 
 
-def skyvis(baselines, channels, dircos, pbfluxes, pc_dircos, fwhm_deg=None, nthreads=0):
+def skyvis(baselines, channels, dircos, pbfluxes, pc_dircos, fwhm_deg=None, nthreads=0, gradient=False):
+    """fp64 V (nbl, nchan); with gradient=True (vis, grad) where grad (3, nbl, nchan) holds the baseline-gradient sums, as
+    skyvis_oracle.skyvis(..., gradient=True) returns them."""
     lib = _load()
     bl = NP.ascontiguousarray(baselines, dtype=NP.float64).reshape(-1, 3)
     fr = NP.ascontiguousarray(channels, dtype=NP.float64).ravel()
@@ -65,6 +70,13 @@ def skyvis(baselines, channels, dircos, pbfluxes, pc_dircos, fwhm_deg=None, nthr
     fw = None if fwhm_deg is None else NP.ascontiguousarray(fwhm_deg, dtype=NP.float64).ravel()
     out = NP.empty((bl.shape[0], fr.size), dtype=NP.complex128)
     p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    if gradient:
+        grad = NP.empty((3, bl.shape[0], fr.size), dtype=NP.complex128)
+        rc = lib.oracle_skyvis_grad_f64(p(bl), bl.shape[0], p(fr), fr.size, p(dc), p(pb), dc.shape[0], p(pc), p(fw), p(out), p(grad),
+                                        int(nthreads))
+        if rc != 0:
+            raise ValueError('oracle_skyvis_grad_f64 rejected its arguments')
+        return out, grad
     rc = lib.oracle_skyvis_f64(p(bl), bl.shape[0], p(fr), fr.size, p(dc), p(pb), dc.shape[0], p(pc), p(fw), p(out),
                                int(nthreads))
     if rc != 0:

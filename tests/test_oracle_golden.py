@@ -184,3 +184,34 @@ def test_external_beam_normalisation_matches_reference_statements():
     assert NP.array_equal(pb, g['pbeam'], equal_nan=True) and NP.isnan(pb[5, 6]) and NP.sum(NP.isnan(pb)) == 1
     assert g['pbeam_f32'].dtype == NP.float32 and NP.array_equal(pb32, g['pbeam_f32'].astype(NP.float64), equal_nan=True)
     assert NP.max(pb[:, 3]) < 1.0 and abs(NP.nanmax(NP.delete(pb, 3, axis=1)) - 1.0) < 1e-15       # the clamp of :2100
+
+
+def test_c_oracle_baseline_gradient(golden_skyvis):
+    """oracle_skyvis_grad_f64 (the full-size fp64 gradient checker): V and the three baseline-gradient sums (interferometry.py:6330,
+    6338, 6343) against the golden vectors with and without the taper, and against the numpy oracle's gradient on a seeded ragged case
+    with a mixed taper (point sources, sizes that vary source by source)."""
+    g = golden_skyvis
+    s = _scale(g)
+    for fw, vkey, gkey in ((None, 'skyvis_f64', 'grad_f64'), (_fwhm(g), 'skyvis_f64_taper', 'grad_f64_taper')):
+        v, gr = CO.skyvis(g['baselines'], g['channels'], g['dircos'], g['pbfluxes'], g['pc_dircos'], fwhm_deg=fw, gradient=True, nthreads=3)
+        assert v.shape == g[vkey].shape and gr.shape == g[gkey].shape and gr.dtype == NP.complex128
+        assert NP.max(NP.abs(v - g[vkey]) / s) <= 1e-12, vkey
+        assert NP.max(NP.abs(gr - g[gkey]) / s[None]) <= 1e-12, gkey
+        v1 = CO.skyvis(g['baselines'], g['channels'], g['dircos'], g['pbfluxes'], g['pc_dircos'], fwhm_deg=fw)
+        assert NP.max(NP.abs(v - v1) / s) <= 1e-12, vkey                     # (not bit-equal: the compiler contracts the two loops apart)
+    rng = NP.random.default_rng(37)
+    nbl, nchan, nsrc = 37, 29, 101
+    bl = rng.uniform(-900.0, 900.0, size=(nbl, 3)); bl[:, 2] *= 0.01
+    ch = 185e6 - NP.arange(nchan) * 123e3
+    alt = NP.degrees(NP.arcsin(rng.uniform(0.05, 1.0, nsrc)))
+    dc = O.altaz2dircos(NP.stack((alt, rng.uniform(0, 360, nsrc)), axis=1))
+    pb = rng.uniform(0.5, 10.0, size=(nsrc, 1)) * rng.uniform(-0.2, 1.0, size=(nsrc, nchan))
+    pc = O.altaz2dircos(NP.array([[80.0, 120.0]]))[0]
+    fw = NP.where(NP.arange(nsrc) % 4 == 0, 0.0, rng.uniform(0.1, 1.5, nsrc))
+    ref, gref = O.skyvis(bl, ch, dc, pb, pc, fwhm_deg=fw, gradient=True)
+    v, (g0, g1, g2) = CO.skyvis(bl, ch, dc, pb, pc, fwhm_deg=fw, gradient=True)
+    s = O.abs_flux_sum(pb)[None, :]
+    assert NP.max(NP.abs(v - ref) / s) <= 1e-12
+    for k, gk in enumerate((g0, g1, g2)):
+        assert NP.max(NP.abs(gk - gref[k]) / s) <= 1e-12, k
+    assert NP.max(NP.abs(g2)) > 0.1 * NP.max(NP.abs(v))          # the z sums are not trivially zero
