@@ -29,6 +29,7 @@ Out of scope here: gain tables, FITS persistence, uvfits / uvh5.
 """
 import os
 import warnings
+import weakref
 
 import numpy as NP
 
@@ -40,6 +41,7 @@ from . import primary_beams as PB
 
 C_LIGHT = 299792458.0
 SIDEREAL_RATE = 1.00273790935    # sidereal seconds per solar second
+_CATALOG_OOM = 'device memory exhausted on the resident-catalogue path; this sky model continues on the per-snapshot upload path'
 
 
 class _DeviceSlot(object):
@@ -94,10 +96,6 @@ class _OnesStack(_LayerStack):
     @property
     def layers(self):
         return [self._ONE] * len(self.parent.layers)
-
-    @layers.setter
-    def layers(self, value):          # (the rollback of observe_batch restores lists: nothing to restore here)
-        pass
 
     def append(self, layer):
         raise TypeError('bp_wts follows the bandpass stack; assign an array to replace it')
@@ -774,8 +772,8 @@ class InterferometerArray(object):
         raise TypeError('{0} values of interferometers must be provided as a scalar, list, tuple or numpy array.'.format(what))
 
     # ------------------------------------------------------------------------------------------
-    def _stack_bandpass(self, bandpass):
-        """interferometry.py:5993-6024."""
+    def _bandpass_layer(self, bandpass):
+        """The bandpass layer of one snapshot, checked (interferometry.py:5993-6018)."""
         bandpass = NP.asarray(bandpass)
         nbl, nchan = self.baselines.shape[0], self.channels.size
         if bandpass.ndim == 1:
@@ -798,17 +796,10 @@ class InterferometerArray(object):
             layer = bandpass
         else:
             raise ValueError('Specified bandpass has too many dimensions')
-        self._append_layer('bp', layer)                                      # :6019-6022
-        if self._stacks.get('bp') is not None:
-            cur = self._stacks.get('bp_wts')
-            if not (isinstance(cur, _OnesStack) and cur.parent is self._stacks['bp']):
-                self._stacks['bp_wts'] = self._stacks['bp'].ones_like()      # :6024
-            self._dense.pop('bp_wts', None)
-        else:
-            self.bp_wts = NP.ones_like(self.bp)
+        return layer
 
-    def _stack_tsys(self, Tsysinfo, bpcorrect):
-        """interferometry.py:6026-6086."""
+    def _tsys_layer(self, Tsysinfo, bpcorrect):
+        """The system-temperature layer of one snapshot, checked (interferometry.py:6026-6081)."""
         nbl, nchan = self.baselines.shape[0], self.channels.size
         if not isinstance(Tsysinfo, dict):
             raise TypeError('Input Tsysinfo must be a dictionary')
@@ -821,7 +812,6 @@ class InterferometerArray(object):
             except KeyError:
                 raise KeyError('One or more keys not found in input Tsysinfo')
             Tsys = Tsys.reshape(1, -1)                                     # one row for every baseline (:6046; dense on read)
-        self.Tsysinfo += [Tsysinfo]
         if bpcorrect is not None:
             if not isinstance(bpcorrect, NP.ndarray):
                 raise TypeError('Input specifying bandpass correction must be a numpy array')
@@ -856,7 +846,7 @@ class InterferometerArray(object):
                 raise ValueError('Specified Tsys has incompatible dimensions with the number of baselines and/or number of frequency channels.')
         else:
             raise TypeError('Tsys should be a scalar, list, tuple, or numpy array')
-        self._append_layer('Tsys', layer)                                    # :6082-6086
+        return layer
 
     # ------------------------------------------------------------------------------------------
     # ------------------------------------------------------------------------------------------
@@ -919,9 +909,20 @@ class InterferometerArray(object):
 
     def invalidate_catalog(self):
         """Forget the sky model resident on the device: the next observe() uploads it again (for edits the fingerprint cannot see,
-        e.g. a custom generate_spectrum whose parameters changed)."""
+        e.g. a custom generate_spectrum whose parameters changed), and try again one that was refused for want of device memory."""
         self._materialise_catalog_state()
         self._catalog_key = None
+        self._catalog_refused = None
+
+    def _refuse_catalog(self, skymodel, message):
+        """`skymodel` does not fit on the device as a resident catalogue: it takes the per-snapshot upload path (ROI rows only) until
+        invalidate_catalog() or until it is collected.  (An object that cannot be referenced weakly is tried again at its next call.)"""
+        warnings.warn(message)
+        try:
+            self._catalog_refused = weakref.ref(skymodel)
+        except TypeError:
+            self._catalog_refused = None
+        self._materialise_catalog_state()
 
     def _catalog_ready(self, skymodel):
         """True when `skymodel` is (now) the catalogue resident on the device.  PRISIM_CATALOG=0 switches the path off (A/B: every
@@ -931,8 +932,9 @@ class InterferometerArray(object):
         key = self._catalog_fingerprint(skymodel)
         if getattr(self, '_catalog_key', None) == key:
             return True
-        if getattr(self, '_catalog_refused', None) == id(skymodel):
-            return False                               # this sky model ran out of device memory on the resident path (observe())
+        refused = getattr(self, '_catalog_refused', None)
+        if refused is not None and refused() is skymodel:
+            return False                               # this sky model ran out of device memory on the resident path
         self._materialise_catalog_state()              # lazy class state of the previous catalogue is fetched while it is still there
         location = NP.asarray(skymodel.location, dtype=NP.float64).reshape(-1, 2)
         nsrc, nchan = location.shape[0], self.channels.size
@@ -953,8 +955,8 @@ class InterferometerArray(object):
                                      dtype=NP.float64).reshape(-1, nchan)              # :6249, once for the whole catalogue
                 self._ctx.set_catalog(location, self.skycoords, flux_spectrum=spectra, fwhm_deg=fwhm)
         except MemoryError:
-            warnings.warn('the sky model does not fit on the device as a resident catalogue; it takes the per-snapshot upload path')
-            self._catalog_refused = id(skymodel)
+            self._refuse_catalog(skymodel, 'the sky model does not fit on the device as a resident catalogue; it takes the per-snapshot '
+                                           'upload path')
             return False
         self._catalog_key = key
         self._catalog_obs_cache = None
@@ -1011,7 +1013,8 @@ class InterferometerArray(object):
             self._frame_cache = cache
         return cache[1]
 
-    def _check_gradient_mode(self, gradient_mode):
+    @staticmethod
+    def _check_gradient_mode(gradient_mode):
         if gradient_mode is not None:                                                 # :6306-6311
             if not isinstance(gradient_mode, str):
                 raise TypeError('Input gradient_mode must be a string')
@@ -1019,43 +1022,95 @@ class InterferometerArray(object):
                 raise ValueError('Invalid value specified in input gradient_mode')
             if gradient_mode.lower() != 'baseline':
                 raise NotImplementedError('only gradient_mode="baseline" is computed (as in the reference)')
-            if self.gradient_mode is None:
-                self.gradient_mode = gradient_mode
         return gradient_mode is not None
 
-    def _append_pointing(self, pointing_center, lst):
-        """Pointing = phase centre of one more snapshot (:6103-6108, 6155-6164): (alt-az degrees, ENU direction cosines)."""
-        pc = NP.asarray(pointing_center, dtype=NP.float64).reshape(1, -1)
+    @staticmethod
+    def _check_skymodel(skymodel):
+        for attr in ('location', 'generate_spectrum'):                                 # :6171 (duck-typed SkyModel)
+            if not hasattr(skymodel, attr):
+                raise TypeError('skymodel should be an instance of class SkyModel.')
+
+    def _pointing(self, pointing_center, lst):
+        """Pointing = phase centre of one snapshot (:6103-6108, 6155-6164): (its row of pointing_center, alt-az degrees, ENU direction
+        cosines)."""
+        pc = NP.asarray(pointing_center, dtype=NP.float64).reshape(-1)
         if pc.size != 2:
             raise ValueError('pointing_center must be a 2-element vector')
-        # pointing_center / phase_center are (n_acc, 2) arrays like the reference's (:6103-6108, grown there by NP.vstack: O(n) per
-        # snapshot); here both are views of buffers that grow by doubling
-        n = len(self.timestamp)
-        for name in ('pointing_center', 'phase_center'):
-            cur = getattr(self, name)
-            buf = self.__dict__.get('_buf_' + name)
-            if n == 0 or buf is None or cur.base is not buf or cur.shape[0] != n or buf.shape[0] <= n:
-                newbuf = NP.empty((max(16, 2 * (n + 1)), 2))
-                if n > 0:
-                    newbuf[:n] = NP.asarray(cur, dtype=NP.float64).reshape(-1, 2)[:n]
-                buf = self.__dict__['_buf_' + name] = newbuf
-            buf[n] = pc[0]
-            setattr(self, name, buf[:n + 1])
         # (a drift scan points at one (HA, Dec) for hours: the conversion of the previous snapshot is kept while nothing it depends on changes)
-        key = (self.pointing_coords, float(pc[0, 0]), float(pc[0, 1]), lst if self.pointing_coords == 'radec' else None, self.latitude)
+        key = (self.pointing_coords, float(pc[0]), float(pc[1]), lst if self.pointing_coords == 'radec' else None, self.latitude)
         cache = getattr(self, '_pointing_cache', None)
         if cache is not None and cache[0] == key:
-            return cache[1], cache[2]
-        pc_altaz = self.pointing_center[-1, :]                                        # :6155-6162
+            return pc, cache[1], cache[2]
+        pc_altaz = pc                                                                 # :6155-6162
         if self.pointing_coords == 'hadec':
-            pc_altaz = GEOM.hadec2altaz(self.pointing_center[-1, :], self.latitude, units='degrees')
+            pc_altaz = GEOM.hadec2altaz(pc, self.latitude, units='degrees')
         elif self.pointing_coords == 'radec':
-            pc_altaz = GEOM.hadec2altaz(NP.asarray([lst - self.pointing_center[-1, 0], self.pointing_center[-1, 1]]),
-                                        self.latitude, units='degrees')
+            pc_altaz = GEOM.hadec2altaz(NP.asarray([lst - pc[0], pc[1]]), self.latitude, units='degrees')
         pc_altaz = NP.array(pc_altaz, dtype=NP.float64)
         pc_dircos = GEOM.altaz2dircos(pc_altaz, 'degrees').ravel()                    # :6164
         self._pointing_cache = (key, pc_altaz, pc_dircos)
-        return pc_altaz, pc_dircos
+        return pc, pc_altaz, pc_dircos
+
+    def _snapshot_inputs(self, timeobj, Tsysinfo, bandpass, pointing_center, bpcorrect, lst=None):
+        """One snapshot's inputs, checked in the reference's order and appended nowhere: (bandpass layer, Tsysinfo, Tsys layer, jd, lst,
+        pointing row, pointing alt-az, pointing direction cosines)."""
+        bp = self._bandpass_layer(bandpass)
+        tsys = self._tsys_layer(Tsysinfo, bpcorrect)
+        jd, lst = _lst_and_jd(timeobj, lst)                                           # :6113
+        return (bp, Tsysinfo, tsys, jd, lst) + self._pointing(pointing_center, lst)
+
+    def _commit(self, snaps, t_acc, sels, vis, grads, slot0, gradient_mode, memsave):
+        """Append observed snapshots to every per-snapshot attribute -- the only place observe() and observe_batch() change them, after
+        the device has answered, so that a call that fails leaves the instance as it was.  snaps: _snapshot_inputs() of each; sels: the
+        (index list, direction cosines) of each snapshot's region of interest, or None when it was empty on the upload path (the
+        reference then appends no index list and no delays, :6377-6382); vis / grads: host arrays or _DeviceSlot; slot0: the device
+        slot of the first."""
+        for sel in sels:
+            if sel is None or len(sel[0]) == 0:                                      # :6378-6382 (the device slot holds zeros)
+                warnings.warn('No sources found in the catalog within matching radius. Simply populating the observed visibilities and/or gradients with noise.')
+        n, k = self.n_acc, len(snaps)
+        self._device_in_step = slot0 == n and (n == 0 or getattr(self, '_device_in_step', False))
+        base_bl = self._baselines_local()
+        for (bp, tsysinfo, tsys, jd, lst, _, _, _), tacc, sel in zip(snaps, t_acc, sels):
+            self._append_layer('bp', bp)                                              # :6019-6022
+            self._append_layer('Tsys', tsys)                                          # :6082-6086
+            self.Tsysinfo.append(tsysinfo)
+            if sel is not None:
+                self.geometric_delays.append(LazyGeometricDelays(base_bl, sel[1], NP.float32 if memsave else NP.float64))   # :6287-6291
+                self.obs_catalog_indices.append(sel[0])                               # :6377
+            self.timestamp.append(jd)                                                 # :6395-6399
+            self.t_acc.append(tacc)
+            self.t_obs += tacc
+            self.lst.append(lst)
+        if self._stacks.get('bp') is not None:                                        # :6024
+            cur = self._stacks.get('bp_wts')
+            if not (isinstance(cur, _OnesStack) and cur.parent is self._stacks['bp']):
+                self._stacks['bp_wts'] = self._stacks['bp'].ones_like()
+            self._dense.pop('bp_wts', None)
+        else:
+            self.bp_wts = NP.ones_like(self.bp)
+        # pointing_center / phase_center are (n_acc, 2) arrays like the reference's (:6103-6108, grown there by NP.vstack: O(n) per
+        # snapshot); here both are views of buffers that grow by doubling
+        for name in ('pointing_center', 'phase_center'):
+            cur = getattr(self, name)
+            buf = self.__dict__.get('_buf_' + name)
+            if n == 0 or buf is None or cur.base is not buf or cur.shape[0] != n or buf.shape[0] < n + k:
+                newbuf = NP.empty((max(16, 2 * (n + k)), 2))
+                if n > 0:
+                    newbuf[:n] = NP.asarray(cur, dtype=NP.float64).reshape(-1, 2)[:n]
+                buf = self.__dict__['_buf_' + name] = newbuf
+            buf[n:n + k] = [s[5] for s in snaps]
+            setattr(self, name, buf[:n + k])
+        self._cube.extend(vis)                                                        # :6384-6393
+        self._skyvis_cache = None
+        if gradient_mode is not None:
+            self._grad.extend(grads)
+            if self.gradient_mode is None:
+                self.gradient_mode = gradient_mode
+            if not isinstance(self.gradient, _LazyGradients):
+                self.gradient = _LazyGradients(self)
+            self.gradient.invalidate(gradient_mode)                                   # stacked again when it is next read
+        self.n_acc += k
 
     def _unpark(self, slot):
         """Fetch whatever snapshot (and gradient block) still lives only in device slot `slot` before the slot is overwritten."""
@@ -1087,21 +1142,23 @@ class InterferometerArray(object):
         is not re-derived) is accepted too: what it buys is had without a file -- the sky model handed in stays resident on the GPU
         from the first call that sees it, and every later snapshot's geometry, region of interest and beam x flux are formed there
         (prisim_hip_set_catalog / prisim_hip_observe_catalog)."""
-        self._stack_bandpass(bandpass)
-        self._stack_tsys(Tsysinfo, bpcorrect)
-        jd, lst = _lst_and_jd(timeobj, lst)                                           # :6113
-        pc_altaz, pc_dircos = self._append_pointing(pointing_center, lst)             # :6103-6108, 6155-6164
+        snap = self._snapshot_inputs(timeobj, Tsysinfo, bandpass, pointing_center, bpcorrect, lst)
+        self._check_skymodel(skymodel)
+        self._check_gradient_mode(gradient_mode)
+        self._observe_snapshot(snap, skymodel, t_acc, pb_info, roi_info, roi_radius, roi_center, gradient_mode, memsave)
 
-        for attr in ('location', 'generate_spectrum'):                                 # :6171 (duck-typed SkyModel)
-            if not hasattr(skymodel, attr):
-                raise TypeError('skymodel should be an instance of class SkyModel.')
+    def _observe_snapshot(self, snap, skymodel, t_acc, pb_info, roi_info, roi_radius, roi_center, gradient_mode, memsave):
+        """One snapshot of checked inputs through the device -- from the resident catalogue, else formed on the host and uploaded --
+        and committed."""
+        jd, lst, pc_altaz, pc_dircos = snap[3], snap[4], snap[6], snap[7]
         nbl, nchan = self.baselines.shape[0], self.channels.size
         datatype = NP.complex64 if memsave else NP.complex128                         # :6182-6185
-        want_grad = self._check_gradient_mode(gradient_mode)
+        want_grad = gradient_mode is not None
         prec = _abi.PRISIM_FP32 if memsave else _abi.PRISIM_FP64
         slot = self.n_acc if self.n_acc < self._reserved else 0
 
         frame = self._snapshot_frame(jd, lst, skymodel)                               # :6174-6180 as one rotation + aberration vector
+        sel = None
         if roi_info is None and self._catalog_ready(skymodel):
             # ---- the sky model is resident on the device: geometry, ROI, spectra, beam x flux and the sky-sum in ONE call ----
             roi_radius, roi_center = self._roi_defaults(roi_radius, roi_center)
@@ -1114,61 +1171,32 @@ class InterferometerArray(object):
             except MemoryError:
                 # the resident path sizes its beam x flux for a whole chunk of snapshots; a catalogue that ran through the per-snapshot
                 # upload before must still run: drop the resident copy and take that path (ROI rows only)
-                warnings.warn('device memory exhausted on the resident-catalogue path; this sky model continues on the per-snapshot upload path')
-                self._catalog_refused = id(skymodel)
-                self._materialise_catalog_state()
-                nroi = None
-            roi = None if nroi is None else _CatalogROI(self, obs, lst, pc_dircos, nroi, frame)
-        else:
-            roi = None
-        if roi is not None:
-            if nroi == 0:                                                             # :6378-6382 (the device slot holds zeros)
-                warnings.warn('No sources found in the catalog within matching radius. Simply populating the observed visibilities and/or gradients with noise.')
-            self.geometric_delays = self.geometric_delays + [LazyGeometricDelays(self._baselines_local(), roi,
-                                                                                 NP.float32 if memsave else NP.float64)]   # :6287-6291
-            self.obs_catalog_indices = self.obs_catalog_indices + [roi]               # :6377
-            have_sky = True
-        else:
-            have_sky = self._upload_snapshot_sky(skymodel, frame, pc_altaz, pc_dircos, pb_info, roi_info, roi_radius, roi_center, memsave)
-            if have_sky:
+                self._refuse_catalog(skymodel, _CATALOG_OOM)
+            else:
+                roi = _CatalogROI(self, obs, lst, pc_dircos, nroi, frame)
+                sel = (roi, roi)
+        if sel is None:
+            sel = self._upload_snapshot_sky(skymodel, frame, pc_altaz, pc_dircos, pb_info, roi_info, roi_radius, roi_center)
+            if sel is not None:
                 if slot != self.n_acc:                                   # (a fresh reserved slot holds nothing: no O(n_acc) scan per snapshot)
                     self._unpark(slot)
                 self._ctx.compute(precision=prec, want_grad=want_grad, slot=slot)
 
-        if have_sky:
-            self._device_in_step = slot == self.n_acc and (self.n_acc == 0 or getattr(self, '_device_in_step', False))
-            if slot == self.n_acc:
-                # the snapshot stays in its own slot of the device cube: no synchronous download (1 GB and 20 ms per HERA-350
-                # snapshot; 4 GB with the gradient blocks); with host staging its copy to the pinned host cube is queued behind the
-                # sky-sum, on the copy stream.  The gradient blocks stay in the device gradient cube until `gradient` is read.
-                skyvis, skyvis_gradient = _DeviceSlot(slot, datatype), (_DeviceSlot(slot, datatype) if want_grad else None)
-                skyvis.staged = self._stage_download(slot, datatype)
-            else:
-                res = self._ctx.get_vis(slot=slot, want_grad=want_grad, complex64=memsave)
-                skyvis, skyvis_gradient = res if want_grad else (res, None)
-        else:                                                                         # :6378-6382
-            warnings.warn('No sources found in the catalog within matching radius. Simply populating the observed visibilities and/or gradients with noise.')
+        if sel is None:                                                               # :6378-6382
             skyvis = NP.zeros((nbl, nchan), dtype=datatype)
             skyvis_gradient = NP.zeros((3, nbl, nchan), dtype=datatype) if want_grad else None
-            if self.n_acc < self._reserved:                                            # the snapshot's device slot says the same
-                self._ctx.set_vis(NP.zeros((nbl, nchan), dtype=NP.complex128), slot=self.n_acc)
-                self._device_in_step = self.n_acc == 0 or getattr(self, '_device_in_step', False)
-            else:
-                self._device_in_step = False
-
-        self._cube.append(skyvis)                                                     # :6384-6393
-        self._skyvis_cache = None
-        if want_grad:
-            self._grad.append(skyvis_gradient)
-            if not isinstance(self.gradient, _LazyGradients):
-                self.gradient = _LazyGradients(self)
-            self.gradient.invalidate(gradient_mode)                                   # stacked again when it is next read
-
-        self.timestamp = self.timestamp + [jd]                                        # :6395-6399
-        self.t_acc = self.t_acc + [t_acc]
-        self.t_obs += t_acc
-        self.n_acc += 1
-        self.lst = self.lst + [lst]
+            if slot == self.n_acc:                                                    # the snapshot's device slot says the same
+                self._ctx.set_vis(NP.zeros((nbl, nchan), dtype=NP.complex128), slot=slot)
+        elif slot == self.n_acc:
+            # the snapshot stays in its own slot of the device cube: no synchronous download (1 GB and 20 ms per HERA-350
+            # snapshot; 4 GB with the gradient blocks); with host staging its copy to the pinned host cube is queued behind the
+            # sky-sum, on the copy stream.  The gradient blocks stay in the device gradient cube until `gradient` is read.
+            skyvis = _DeviceSlot(slot, datatype, staged=self._stage_download(slot, datatype))
+            skyvis_gradient = _DeviceSlot(slot, datatype) if want_grad else None
+        else:
+            res = self._ctx.get_vis(slot=slot, want_grad=want_grad, complex64=memsave)
+            skyvis, skyvis_gradient = res if want_grad else (res, None)
+        self._commit([snap], [t_acc], [sel], [skyvis], [skyvis_gradient], slot, gradient_mode, memsave)
 
     def observe_batch(self, timeobjs, Tsysinfo, bandpass, pointing_centers, skymodel, t_acc, pb_info=None, bpcorrect=None,
                       roi_radius=None, roi_center=None, gradient_mode=None, memsave=False):
@@ -1183,98 +1211,54 @@ class InterferometerArray(object):
         bandpass          (nchan,) / (nbl, nchan) for every snapshot, or a list of K
         pointing_centers  (2,) for every snapshot or (K, 2)
         t_acc             scalar or K values
-        Falls back to K calls of observe() when the catalogue path is not available (PRISIM_CATALOG=0, no free device slots)."""
+        The inputs of all K snapshots are checked before anything runs.  Falls back to one snapshot after the other, as observe() runs
+        them, when the catalogue path is not available (PRISIM_CATALOG=0, no free device slots)."""
         k = len(timeobjs)
         if k == 0:
             return
         tsys_l = Tsysinfo if isinstance(Tsysinfo, (list, tuple)) else [Tsysinfo] * k
         bp_l = bandpass if isinstance(bandpass, (list, tuple)) else [bandpass] * k
         pcs = NP.broadcast_to(NP.asarray(pointing_centers, dtype=NP.float64).reshape(-1, 2), (k, 2))
-        tacc_l = list(NP.broadcast_to(NP.asarray(t_acc, dtype=NP.float64).ravel(), (k,)))
+        tacc_l = [float(v) for v in NP.broadcast_to(NP.asarray(t_acc, dtype=NP.float64).ravel(), (k,))]
         if len(tsys_l) != k or len(bp_l) != k:
             raise ValueError('Tsysinfo / bandpass lists must have one entry per snapshot')
-        for attr in ('location', 'generate_spectrum'):
-            if not hasattr(skymodel, attr):
-                raise TypeError('skymodel should be an instance of class SkyModel.')
+        self._check_skymodel(skymodel)
+        snaps = [self._snapshot_inputs(timeobjs[t], tsys_l[t], bp_l[t], pcs[t], bpcorrect) for t in range(k)]
+        want_grad = self._check_gradient_mode(gradient_mode)
         if self.n_acc == 0 and self._reserved < k:
             self.reserve(k, host_staging=getattr(self, '_stage', False))
-        batched = self.n_acc + k <= self._reserved and (pb_info is None) and self._catalog_ready(skymodel)
-        if not batched:
-            for t in range(k):
-                self.observe(timeobjs[t], tsys_l[t], bp_l[t], pcs[t], skymodel, float(tacc_l[t]), pb_info=pb_info, bpcorrect=bpcorrect,
-                             roi_radius=roi_radius, roi_center=roi_center, gradient_mode=gradient_mode, memsave=memsave)
-            return
-        want_grad = self._check_gradient_mode(gradient_mode)
-        roi_radius, roi_center = self._roi_defaults(roi_radius, roi_center)
-        datatype = NP.complex64 if memsave else NP.complex128
-        prec = _abi.PRISIM_FP32 if memsave else _abi.PRISIM_FP64
-        # The per-snapshot class state grown before the device call (timestamp, pointing / phase centre rows, bandpass and Tsys layers) is
-        # rolled back if anything fails -- a changed beam specification, a device error -- so that the instance stays aligned with n_acc.
-        state0 = (self.pointing_center, self.phase_center, getattr(self, '_pointing_cache', None), self.timestamp, list(self.Tsysinfo),
-                  dict(self._stacks), {n: (None if st is None else list(st.layers)) for n, st in self._stacks.items()}, dict(self._dense))
-        jds, lsts, pc_dcs, bpcs, frames, obs = [], [], [], [], [], None
-        try:
-            for t in range(k):
-                self._stack_bandpass(bp_l[t])
-                self._stack_tsys(tsys_l[t], bpcorrect)
-                jd, lst = _lst_and_jd(timeobjs[t], None)
-                pc_altaz, pc_dircos = self._append_pointing(pcs[t], lst)
-                self.timestamp = self.timestamp + [jd]                                # (_append_pointing starts a fresh array on an empty list)
-                o, bpc = self._catalog_obs(None, pc_altaz, roi_radius, roi_center)
+        if self.n_acc + k <= self._reserved and (pb_info is None) and self._catalog_ready(skymodel):
+            roi_radius, roi_center = self._roi_defaults(roi_radius, roi_center)
+            datatype = NP.complex64 if memsave else NP.complex128
+            bpcs, frames, obs = [], [], None
+            for s in snaps:
+                o, bpc = self._catalog_obs(None, s[6], roi_radius, roi_center)
                 obs = o if obs is None else obs
                 if o is not obs:
                     raise RuntimeError('the beam specification changed inside a batch')
-                jds.append(jd); lsts.append(lst); pc_dcs.append(pc_dircos); bpcs.append(pc_dircos if bpc is None else bpc)
-                frames.append(self._snapshot_frame(jd, lst, skymodel))
+                bpcs.append(s[7] if bpc is None else bpc)
+                frames.append(self._snapshot_frame(s[3], s[4], skymodel))
             slot0 = self.n_acc
             host_cube = self._ensure_host_cube(datatype) if getattr(self, '_stage', False) else None
-            counts = self._ctx.observe_catalog(obs, lsts, NP.asarray(pc_dcs), NP.asarray(bpcs), precision=prec, want_grad=want_grad, slot0=slot0,
-                                               host_cube=host_cube, frames=frames)
-        except Exception as exc:
-            self.pointing_center, self.phase_center, self._pointing_cache, self.timestamp, self.Tsysinfo, stacks, layers, dense = state0
-            self._stacks = stacks
-            for n, st in stacks.items():
-                if st is not None:
-                    st.layers = layers[n]
-            self._dense = dense
-            if not isinstance(exc, MemoryError):
-                raise
-            # the resident path ran out of device memory: this sky model continues on the per-snapshot upload path (ROI rows only)
-            warnings.warn('device memory exhausted on the resident-catalogue path; this sky model continues on the per-snapshot upload path')
-            self._catalog_refused = id(skymodel)
-            self._materialise_catalog_state()
-            for t in range(k):
-                self.observe(timeobjs[t], tsys_l[t], bp_l[t], pcs[t], skymodel, float(tacc_l[t]), pb_info=pb_info, bpcorrect=bpcorrect,
-                             roi_radius=roi_radius, roi_center=roi_center, gradient_mode=gradient_mode, memsave=memsave)
-            return
-        base_bl = self._baselines_local()
+            try:
+                counts = self._ctx.observe_catalog(obs, [s[4] for s in snaps], NP.asarray([s[7] for s in snaps]), NP.asarray(bpcs),
+                                                   precision=_abi.PRISIM_FP32 if memsave else _abi.PRISIM_FP64, want_grad=want_grad,
+                                                   slot0=slot0, host_cube=host_cube, frames=frames)
+            except MemoryError:
+                self._refuse_catalog(skymodel, _CATALOG_OOM)      # the snapshots below take the per-snapshot upload path (ROI rows only)
+            else:
+                rois = [_CatalogROI(self, obs, s[4], s[7], int(c), f) for s, c, f in zip(snaps, counts, frames)]
+                self._commit(snaps, tacc_l, [(r, r) for r in rois], [_DeviceSlot(slot0 + t, datatype, host_cube is not None) for t in range(k)],
+                             [_DeviceSlot(slot0 + t, datatype) for t in range(k)], slot0, gradient_mode, memsave)
+                return
         for t in range(k):
-            roi = _CatalogROI(self, obs, lsts[t], pc_dcs[t], int(counts[t]), frames[t])
-            if counts[t] == 0:
-                warnings.warn('No sources found in the catalog within matching radius. Simply populating the observed visibilities and/or gradients with noise.')
-            self.geometric_delays = self.geometric_delays + [LazyGeometricDelays(base_bl, roi, NP.float32 if memsave else NP.float64)]
-            self.obs_catalog_indices = self.obs_catalog_indices + [roi]
-            snap = _DeviceSlot(slot0 + t, datatype)
-            snap.staged = host_cube is not None
-            self._cube.append(snap)
-            if want_grad:
-                self._grad.append(_DeviceSlot(slot0 + t, datatype))
-            self.t_acc = self.t_acc + [float(tacc_l[t])]
-            self.t_obs += float(tacc_l[t])
-            self.lst = self.lst + [lsts[t]]
-        self._device_in_step = slot0 == 0 or getattr(self, '_device_in_step', False)
-        self.n_acc += k
-        self._skyvis_cache = None
-        if want_grad:
-            if not isinstance(self.gradient, _LazyGradients):
-                self.gradient = _LazyGradients(self)
-            self.gradient.invalidate(gradient_mode)
+            self._observe_snapshot(snaps[t], skymodel, tacc_l[t], pb_info, None, roi_radius, roi_center, gradient_mode, memsave)
 
-    def _upload_snapshot_sky(self, skymodel, frame, pc_altaz, pc_dircos, pb_info, roi_info, roi_radius, roi_center, memsave):
+    def _upload_snapshot_sky(self, skymodel, frame, pc_altaz, pc_dircos, pb_info, roi_info, roi_radius, roi_center):
         """The snapshot's sky formed on the HOST and uploaded (roi_info given, PRISIM_CATALOG=0, or a spectrum table too large to keep
         resident): interferometry.py:6171-6283 statement by statement, with the astropy / GEOM coordinate chain of :6174-6180 as the
-        snapshot's frame (R, beta) applied by geometry.frame_dircos -- the host statement of the device's cat_source().  Returns False when
-        the region of interest is empty."""
+        snapshot's frame (R, beta) applied by geometry.frame_dircos -- the host statement of the device's cat_source().  Returns the region
+        of interest as (catalogue indices, direction cosines), or None when it is empty."""
         nchan = self.channels.size
         location = NP.asarray(skymodel.location, dtype=NP.float64).reshape(-1, 2)
         dc_all = GEOM.frame_dircos(GEOM.catalog_unitvec(location, self.skycoords), frame[0], frame[1])     # :6174-6180, 6263
@@ -1296,7 +1280,7 @@ class InterferometerArray(object):
             roi_radius, roi_center = self._roi_defaults(roi_radius, roi_center)
             m2 = GEOM.roi_select(dc_all, roi_center, roi_radius, pc_dircos)       # :6210-6216 on the direction cosines
         if len(m2) == 0:
-            return False
+            return None
         dircos_roi = dc_all[m2, :]                                                # :6219, 6263 (unconditional, Q4)
         # flux spectra (:6249).  A power-law sky model (spec_type 'func') is described to the device by its nsrc-sized
         # flux_ref / spindex vectors and S = flux_ref (f / ref_freq)^spindex is formed there; anything else goes through
@@ -1339,10 +1323,7 @@ class InterferometerArray(object):
                                                       first_frequency_hz=float(self.channels[0]))                   # :6252
             self._ctx.set_sky_analytic(dircos_up, flux_ref, spindex, ref_freq, kind, dia, bpc, pc_dircos, fwhm_deg=fwhm,
                                        flux_spectrum=fluxes, ext=ext)
-        self.geometric_delays = self.geometric_delays + [LazyGeometricDelays(self._baselines_local(), dircos_roi,
-                                                                             NP.float32 if memsave else NP.float64)]   # :6287-6291
-        self.obs_catalog_indices = self.obs_catalog_indices + [m2]                # :6377
-        return True
+        return m2, dircos_roi
 
     # skyvis_freq: (nbl, nchan, n_acc), time fastest, like the reference (:6385-6390)
     @property

@@ -640,8 +640,10 @@ def test_out_of_device_memory_on_the_resident_path_falls_back_to_the_upload_path
 
     class Tight(fake_context.OracleContext):
         refuse = 'observe'
+        uploads = 0
 
         def set_catalog(self, *a, **k):
+            Tight.uploads += 1
             if Tight.refuse == 'catalog':
                 raise MemoryError('hipMalloc: out of memory (stand-in)')
             return fake_context.OracleContext.set_catalog(self, *a, **k)
@@ -674,6 +676,72 @@ def test_out_of_device_memory_on_the_resident_path_falls_back_to_the_upload_path
         for t in range(3):
             assert NP.array_equal(NP.asarray(ia.obs_catalog_indices[t]), NP.asarray(want.obs_catalog_indices[t]))
         assert NP.max(NP.abs(ia.skyvis_freq - want.skyvis_freq)) <= 1e-12 * NP.max(NP.abs(want.skyvis_freq))
+        # the refusal holds until invalidate_catalog(): only then is the resident catalogue tried again
+        Tight.refuse, Tight.uploads = None, 0
+        ia.observe(times[0], {'Tnet': 100.0}, NP.ones(ch.size), [0.0, lat], skymod, 10.0)
+        assert Tight.uploads == 0 and isinstance(ia.obs_catalog_indices[-1], NP.ndarray)
+        ia.invalidate_catalog()
+        ia.observe(times[1], {'Tnet': 100.0}, NP.ones(ch.size), [0.0, lat], skymod, 10.0)
+        assert Tight.uploads == 1 and type(ia.obs_catalog_indices[-1]).__name__ == '_CatalogROI'
+        assert NP.max(NP.abs(ia.skyvis_freq[:, :, 4] - want.skyvis_freq[:, :, 1])) <= 1e-12 * NP.max(NP.abs(want.skyvis_freq))
+
+
+@pytest.mark.parametrize('path', ['resident', 'upload'])
+def test_failed_calls_leave_the_instance_aligned_and_lists_grow_in_place(monkeypatch, path):
+    """observe() and observe_batch() check every input before they change anything: a call that raises -- a bad sky model, an
+    unsupported gradient_mode, a bandpass of the wrong length, a negative Tsys (in observe_batch: in its last snapshot) -- leaves every
+    per-snapshot attribute as it was, and the visibilities of the calls that succeed are those of an instance that never saw the failures.
+    A good call grows the per-snapshot lists in place."""
+    if path == 'upload':
+        monkeypatch.setenv('PRISIM_CATALOG', '0')
+    ia, skymod, ch, lat = _radec_case(monkeypatch)
+    clean, _, _, _ = _radec_case(monkeypatch)
+    nbl = ia.baselines.shape[0]
+    for x in (ia, clean):
+        x.reserve(8)
+    times = [(2461041.5 + 0.001 * t, 40.0 + 2.0 * t) for t in range(4)]
+    good = {'Tsysinfo': {'Tnet': 100.0}, 'bandpass': NP.ones(ch.size), 'skymodel': skymod}
+    bad = [({'skymodel': object()}, TypeError), ({'gradient_mode': 'skypos'}, NotImplementedError),
+           ({'bandpass': NP.ones(ch.size + 1)}, ValueError), ({'Tsysinfo': {'Tnet': -5.0}}, ValueError)]
+    lists = ('timestamp', 't_acc', 'lst', 'geometric_delays', 'obs_catalog_indices')
+
+    def observe(x, t, **kw):
+        a = dict(good, **kw)
+        x.observe(t, a['Tsysinfo'], a['bandpass'], [0.0, lat], a['skymodel'], 10.0, gradient_mode=a.get('gradient_mode'))
+
+    def batch(x, tt, **kw):
+        a = dict(good, **kw)
+        bp = [NP.ones(ch.size)] * (len(tt) - 1) + [a['bandpass']]
+        tsys = [{'Tnet': 100.0}] * (len(tt) - 1) + [a['Tsysinfo']]
+        x.observe_batch(tt, tsys, bp, [0.0, lat], a['skymodel'], 10.0, gradient_mode=a.get('gradient_mode'))
+
+    def aligned(n):
+        sizes = [ia.n_acc, len(ia.timestamp), len(ia.t_acc), len(ia.lst), len(ia.Tsysinfo), len(ia.obs_catalog_indices),
+                 len(ia.geometric_delays), ia.pointing_center.shape[0], ia.phase_center.shape[0]]
+        assert sizes == [n] * len(sizes)
+        for name in ('bp', 'bp_wts', 'Tsys'):
+            assert getattr(ia, name).shape == (nbl, ch.size, n)
+
+    observe(ia, times[0])
+    aligned(1)
+    for kw, exc in bad:
+        with pytest.raises(exc):
+            observe(ia, times[1], **kw)
+        aligned(1)
+        with pytest.raises(exc):
+            batch(ia, times[1:3], **kw)
+        aligned(1)
+    before = [getattr(ia, name) for name in lists]
+    observe(ia, times[1])
+    aligned(2)
+    batch(ia, times[2:4])
+    aligned(4)
+    assert all(getattr(ia, name) is b for name, b in zip(lists, before))
+    observe(clean, times[0])
+    observe(clean, times[1])
+    batch(clean, times[2:4])
+    assert NP.array_equal(ia.skyvis_freq, clean.skyvis_freq)
+    assert ia.lst == clean.lst and ia.timestamp == clean.timestamp and NP.array_equal(ia.pointing_center, clean.pointing_center)
 
 
 def test_in_place_edits_of_the_sky_model_and_epoch_of_date(monkeypatch):
