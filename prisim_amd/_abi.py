@@ -37,6 +37,11 @@ EXPORTS = (
     'prisim_hip_comm_version',
 )
 
+# every symbol include/prisim_clean.h declares: delay CLEAN (prisim_amd/csrc_clean/), linked into the same library
+CLEAN_EXPORTS = ('prisim_clean_rows', 'prisim_clean_delay')
+PRISIM_CLEAN_MAX_LEN = 4096
+PRISIM_CLEAN_THRESHOLD, PRISIM_CLEAN_MAXITER, PRISIM_CLEAN_INRMS, PRISIM_CLEAN_NO_OUTRMS, PRISIM_CLEAN_BAD_THRESHOLD = 1, 2, 4, 8, 16
+
 
 class PrisimSky(C.Structure):
     _fields_ = [('nsrc', C.c_int64), ('dircos', C.c_void_p), ('pbflux', C.c_void_p),
@@ -151,6 +156,11 @@ class PrisimCommStats(C.Structure):
                 ('last_undeal_ms', C.c_double)]
 
 
+class PrisimCleanStats(C.Structure):
+    _fields_ = [('device_ms', C.c_double), ('clean_ms', C.c_double), ('sum_iter', C.c_int64), ('rows', C.c_int64),
+                ('waves_per_block', C.c_int32), ('kernel_in_lds', C.c_int32), ('lds_bytes', C.c_int64)]
+
+
 class PrisimHipError(RuntimeError):
     """Raised when libprisim_hip.so is missing/unloadable or no GPU is usable."""
 
@@ -228,6 +238,12 @@ def load_library():
     lib.prisim_hip_set_sky_from_catalog.argtypes = [vp, C.POINTER(PrisimObs), C.POINTER(PrisimSnapshot), C.POINTER(i64)]
     lib.prisim_hip_catalog_roi.argtypes = [vp, C.POINTER(PrisimObs), C.POINTER(PrisimSnapshot), C.POINTER(i64), vp, vp, i64]
     lib.prisim_hip_observe_catalog.argtypes = [vp, C.POINTER(PrisimObs), C.POINTER(PrisimSnapshot), i64, i32, i32, i64, vp, C.POINTER(PrisimPost)]
+    lib.prisim_clean_rows.argtypes = [vp, i64, i64, vp, i64, vp, vp, vp, dbl, i64, dbl, C.c_int32, vp, vp, vp, vp, vp,
+                                      C.POINTER(PrisimCleanStats)]
+    lib.prisim_clean_delay.argtypes = [vp, C.c_int32, i64, i64, i64, vp, i64, vp, vp, vp, dbl, dbl, dbl, dbl, i64, dbl, C.c_int32, vp, vp,
+                                       vp, vp, vp, vp, vp, vp, vp, C.POINTER(PrisimCleanStats)]
+    for name in CLEAN_EXPORTS:
+        getattr(lib, name).restype = C.c_int
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ('prisim_hip_destroy', 'prisim_hip_last_error', 'prisim_hip_version'):
@@ -705,6 +721,62 @@ class Context(object):
             return out
         self._check(self._lib.prisim_hip_noise(self._h, r.shape[0], _ptr(r), int(seed) & 0xFFFFFFFFFFFFFFFF, int(bl_offset), _ptr(out)),
                     'prisim_hip_noise')
+        return out
+
+    # ---- delay CLEAN (include/prisim_clean.h) ----
+    @staticmethod
+    def _clean_stats(st):
+        return {'device_ms': st.device_ms, 'clean_ms': st.clean_ms, 'sum_iter': int(st.sum_iter), 'rows': int(st.rows),
+                'waves_per_block': int(st.waves_per_block), 'kernel_in_lds': bool(st.kernel_in_lds), 'lds_bytes': int(st.lds_bytes)}
+
+    @staticmethod
+    def _clean_kernels(kern, kidx, nrows, n):
+        k = NP.ascontiguousarray(kern, dtype=NP.complex128).reshape(-1, n)
+        if kidx is None:
+            if k.shape[0] != 1:
+                raise ValueError('kidx is required with more than one kernel')
+            return k, None
+        ix = NP.ascontiguousarray(kidx, dtype=NP.int32).ravel()
+        if ix.size != nrows:
+            raise ValueError('kidx must have one entry per row')
+        return k, ix
+
+    def clean_rows(self, inp, kern, cbox, gain, maxiter, threshold, absolute=False, kidx=None):
+        """Hogbom CLEAN of every row of inp (nrows, m) on the device (prisim_clean_rows).  kern: (nkern, m) kernels, row r uses
+        kern[kidx[r]] (kidx None: one kernel).  Returns cc, res (nrows, m), iters, flags (nrows,), rms (nrows, 2), stats."""
+        x = NP.ascontiguousarray(inp, dtype=NP.complex128)
+        nrows, m = x.shape
+        k, ix = self._clean_kernels(kern, kidx, nrows, m)
+        box = NP.ascontiguousarray(cbox, dtype=NP.uint8).reshape(nrows, m)
+        cc, res = NP.empty_like(x), NP.empty_like(x)
+        iters, flags = NP.empty(nrows, dtype=NP.int32), NP.empty(nrows, dtype=NP.int32)
+        rms = NP.empty((nrows, 2))
+        st = PrisimCleanStats()
+        self._check(self._lib.prisim_clean_rows(self._h, nrows, m, _ptr(x), k.shape[0], _ptr(k), _ptr(ix), _ptr(box), float(gain),
+                                                int(maxiter), float(threshold), int(bool(absolute)), _ptr(cc), _ptr(res), _ptr(iters),
+                                                _ptr(flags), _ptr(rms), C.byref(st)), 'prisim_clean_rows')
+        return cc, res, iters, flags, rms, self._clean_stats(st)
+
+    def clean_delay(self, win, kwin, cbox, m, lag_scale, freq_scale1, freq_scale2, gain, maxiter, threshold, absolute=False, kidx=None):
+        """The delayClean chain (prisim_clean_delay) for win (ncubes, nrows, nchan) windowed rows zero-padded to m lags, kernels
+        kwin (nkern, nchan), boxes cbox (nrows, m).  Returns a dict of lag, kern_lag, cc, res, cc_freq, res_freq (unshifted),
+        iters, flags, rms and stats."""
+        w = NP.ascontiguousarray(win, dtype=NP.complex128)
+        ncubes, nrows, nchan = w.shape
+        k, ix = self._clean_kernels(kwin, kidx, nrows, nchan)
+        box = NP.ascontiguousarray(cbox, dtype=NP.uint8).reshape(nrows, m)
+        out = {name: NP.empty((ncubes, nrows, m), dtype=NP.complex128) for name in ('lag', 'cc', 'res', 'cc_freq', 'res_freq')}
+        out['kern_lag'] = NP.empty((k.shape[0], m), dtype=NP.complex128)
+        out['iters'] = NP.empty((ncubes, nrows), dtype=NP.int32)
+        out['flags'] = NP.empty((ncubes, nrows), dtype=NP.int32)
+        out['rms'] = NP.empty((ncubes, nrows, 2))
+        st = PrisimCleanStats()
+        self._check(self._lib.prisim_clean_delay(self._h, ncubes, nrows, nchan, int(m), _ptr(w), k.shape[0], _ptr(k), _ptr(ix), _ptr(box),
+                                                 float(lag_scale), float(freq_scale1), float(freq_scale2), float(gain), int(maxiter),
+                                                 float(threshold), int(bool(absolute)), _ptr(out['lag']), _ptr(out['kern_lag']),
+                                                 _ptr(out['cc']), _ptr(out['res']), _ptr(out['cc_freq']), _ptr(out['res_freq']),
+                                                 _ptr(out['iters']), _ptr(out['flags']), _ptr(out['rms']), C.byref(st)), 'prisim_clean_delay')
+        out['stats'] = self._clean_stats(st)
         return out
 
     # ---- multi-GPU ----

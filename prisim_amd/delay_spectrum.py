@@ -6,7 +6,13 @@ keywords, attributes and exception types.  The transform itself (window, zero-pa
 ``abs(.)**2 * jacobian1 * jacobian2 * Jy2K**2`` run in libprisim_hip.so (prisim_hip_delay_transform*, one HBM-bound kernel for
 power-of-two channel counts); the host computes the scalars: redshift, comoving distances, the beam volume, the Jy -> K factor.
 
-Not here (out of scope): delay CLEAN, sub-band transforms, closure-phase spectra, FITS persistence.
+Delay CLEAN: ``complex1dClean`` (:133-352) and ``DelaySpectrum.delayClean`` (:1622-1838) run on the GPU (include/prisim_clean.h,
+prisim_amd/csrc_clean/clean.hip): one wave64 per (baseline, snapshot) row CLEANs all rows of a chunk in one launch, between rocFFT's
+padded inverse transform to lags and the forward transforms of the clean components and residuals; DelayPowerSpectrum then forms the
+dps['cc_*'] spectra (:3996-4002).  Departures from the reference are listed in each docstring.
+
+Not here (out of scope): sub-band transforms (they need astroutils' DSP windows), closure-phase spectra, FITS
+persistence.
 
 Cosmology.  The reference takes ``astropy.cosmology.Planck15.clone(H0=100)`` (:34-35); astropy is not in this image, so ``cosmo100`` here
 is this module's own flat LambdaCDM with Planck15's Om0 = 0.3075, Tcmb0 = 2.7255 K, Neff = 3.046 (photons + massless neutrinos in the
@@ -189,6 +195,102 @@ def power_constants(channels, telescope, freq_wts=None, cosmo=cosmo100, nside=32
             'cosmology': getattr(cosmo, 'name', None) or type(cosmo).__name__}
 
 
+def _check_clean_args(threshold_type, threshold, gain, maxiter):
+    """The argument checks of complex1dClean that do not depend on the rows (:195-203, 246-256), with the reference's exception types and
+    messages; returns threshold as a float."""
+    if threshold_type not in ['relative', 'absolute']:
+        raise ValueError('invalid specification for threshold_type')
+    if not isinstance(threshold, (int, float)):
+        raise TypeError('input threshold must be a scalar')
+    threshold = float(threshold)
+    if threshold <= 0.0:
+        raise ValueError('input threshold must be positive')
+    if threshold_type == 'relative' and threshold >= 1.0:
+        raise ValueError('incompatible value specified for threshold')
+    return threshold
+
+
+def _check_gain_maxiter(gain, maxiter):
+    if not isinstance(gain, float):
+        raise TypeError('gain must be a floating point number')
+    if (gain <= 0.0) or (gain >= 1.0):
+        raise TypeError('gain must lie between 0 and 1')
+    if not isinstance(maxiter, int):
+        raise TypeError('maxiter must be an integer')
+    if maxiter <= 0:
+        raise ValueError('maxiter must be positive')
+
+
+def complex1dClean(inp, kernel, cbox=None, gain=0.1, maxiter=10000, threshold=5e-3, threshold_type='relative', verbose=False,
+                   progressbar=False, pid=None, progressbar_yloc=0, device=0):
+    """Hogbom CLEAN of a complex 1-D array on the GPU (prisim/delay_spectrum.py:133-352, prisim_clean_rows).
+
+    As the reference: the kernel is divided by its max modulus; each iteration takes the first argmax of |res * cbox|, adds
+    gain * res there to the clean components and subtracts that times the kernel rolled onto it; it stops when |maxres| <=
+    lolim * max|inp| (cond1), after maxiter iterations (cond2), or when the median absolute deviation of the residuals inside the
+    box is <= that outside it (cond3).  Returns {'termination': {'threshold', 'maxiter', 'inrms<outrms'}, 'iter', 'rms', 'inrms',
+    'outrms', 'res', 'cc'}.
+
+    Extension: a 2-D ``inp`` (nrows, m) cleans every row in one launch (kernel (m,) or (nrows, m), cbox (m,) or (nrows, m)); the
+    entries are then arrays over the rows (outrms NaN where undefined) and 'stats' holds the device timing and iteration sum.
+    Departures (one test each in tests/test_delay_clean.py):
+      - with <= 2 entries outside the box the reference raises UnboundLocalError (cond3 is never assigned): here cond3 is False and
+        outrms None;
+      - 'inrms' / 'outrms' are the final values, not per-iteration histories; 'rms' (the MAD of the whole array) decides nothing and
+        is None.
+    verbose, progressbar, pid and progressbar_yloc are accepted and ignored.  Rows are complex128 on the device; up to 4096 entries."""
+    if not isinstance(inp, NP.ndarray):
+        raise TypeError('inp must be a numpy array')
+    if not isinstance(kernel, NP.ndarray):
+        raise TypeError('kernel must be a numpy array')
+    if threshold_type not in ['relative', 'absolute']:
+        raise ValueError('invalid specification for threshold_type')
+    if not isinstance(threshold, (int, float)):
+        raise TypeError('input threshold must be a scalar')
+    threshold = float(threshold)
+    if threshold <= 0.0:
+        raise ValueError('input threshold must be positive')
+    rows = inp.ndim == 2
+    x = NP.ascontiguousarray(inp if rows else inp.reshape(1, -1), dtype=NP.complex128)
+    nrows, m = x.shape
+    k = NP.asarray(kernel, dtype=NP.complex128)
+    if rows and k.ndim == 2 and k.shape[0] == nrows and k.shape[0] > 1:
+        kidx = NP.arange(nrows, dtype=NP.int32)
+    else:
+        k, kidx = k.reshape(1, -1), None
+    if k.shape[1] != m:
+        raise ValueError('inp and kernel must have same size')
+    if cbox is None:
+        box = NP.ones((nrows, m), dtype=bool)
+    elif isinstance(cbox, NP.ndarray):
+        if cbox.size not in (m, nrows * m):
+            raise ValueError('Clean box must be of same size as input')
+        box = NP.broadcast_to(NP.where(cbox > 0.0, True, False).reshape(-1, m), (nrows, m))
+    else:
+        raise TypeError('cbox must be a numpy array')
+    if threshold_type == 'relative':
+        lolim = NP.full(nrows, threshold)
+    else:
+        with NP.errstate(divide='ignore'):
+            lolim = threshold / NP.abs(x).max(axis=1)
+    if NP.any(lolim >= 1.0):
+        raise ValueError('incompatible value specified for threshold')
+    _check_gain_maxiter(gain, maxiter)
+    with _abi.Context(device) as ctx:
+        cc, res, iters, flags, rms, stats = ctx.clean_rows(x, k, box, gain, maxiter, threshold, absolute=threshold_type == 'absolute',
+                                                           kidx=kidx)
+    if NP.any(flags & _abi.PRISIM_CLEAN_BAD_THRESHOLD):
+        raise ValueError('incompatible value specified for threshold')
+    term = {'threshold': (flags & _abi.PRISIM_CLEAN_THRESHOLD) != 0, 'maxiter': (flags & _abi.PRISIM_CLEAN_MAXITER) != 0,
+            'inrms<outrms': (flags & _abi.PRISIM_CLEAN_INRMS) != 0}
+    if rows:
+        return {'termination': term, 'iter': iters, 'rms': None, 'inrms': rms[:, 0], 'outrms': rms[:, 1], 'cc': cc, 'res': res,
+                'stats': stats}
+    no_out = bool(flags[0] & _abi.PRISIM_CLEAN_NO_OUTRMS)
+    return {'termination': {key: bool(v[0]) for key, v in term.items()}, 'iter': int(iters[0]), 'rms': None, 'inrms': float(rms[0, 0]),
+            'outrms': None if no_out else float(rms[0, 1]), 'cc': cc[0], 'res': res[0]}
+
+
 class DelaySpectrum(object):
     """Delay spectra of an InterferometerArray's visibilities (prisim/delay_spectrum.py:493-1342, the argument path of __init__ and
     delay_transform()).  Attributes as in the reference: ia, f, df, n_acc, bp, bp_wts, pad, lags, lag_kernel, skyvis_lag, vis_lag,
@@ -293,10 +395,9 @@ class DelaySpectrum(object):
         self.horizon_delay_limits = self.get_horizon_delay_limits()
 
     # ------------------------------------------------------------------------------------------
-    def _window_source(self, freq_wts):
-        """Per-snapshot windows bp * freq_wts in the most compact form available: (layers, same) with layers[t] of shape
-        (1 | nbl, nchan) and same = every snapshot carries the same window; plus the freq_wts to report (a zero-copy broadcast
-        view when one window serves every baseline and snapshot)."""
+    def _window_factors(self, freq_wts):
+        """Per-snapshot bandpass and window layers, each of shape (1 | nbl, nchan), as two lists of n_acc entries; plus the freq_wts
+        to report (a zero-copy broadcast view when one window serves every baseline and snapshot)."""
         ia = self.ia
         nbl, nchan, nt = ia.baselines.shape[0], self.f.size, self.n_acc
         stacks = getattr(ia, '_stacks', {})
@@ -337,7 +438,13 @@ class DelaySpectrum(object):
                 w_layers = layers_of('bp_wts')
                 report = None                                                            # the array's own (dense on read)
         n = min(len(bp_layers), len(w_layers))
-        layers = [NP.asarray(bp_layers[t]) * NP.asarray(w_layers[t]) for t in range(n)]
+        return [NP.asarray(l) for l in bp_layers[:n]], [NP.asarray(l) for l in w_layers[:n]], report
+
+    def _window_source(self, freq_wts):
+        """Per-snapshot windows bp * freq_wts in the most compact form available: (layers, same) with layers[t] of shape
+        (1 | nbl, nchan) and same = every snapshot carries the same window; plus the freq_wts to report."""
+        bp_layers, w_layers, report = self._window_factors(freq_wts)
+        layers = [bp_layers[t] * w_layers[t] for t in range(len(bp_layers))]
         same = all(l.shape == layers[0].shape and NP.array_equal(l, layers[0]) for l in layers[1:])
         return layers, same, report
 
@@ -462,6 +569,123 @@ class DelaySpectrum(object):
         result['vis_noise_lag'] = vis_noise_lag
         result['lag_kernel'] = _Deferred(make_kernel) if action == 'store' else make_kernel()
         return _LazyDict(result)
+
+
+    def delayClean(self, pad=1.0, freq_wts=None, clean_window_buffer=1.0, gain=0.1, maxiter=10000, threshold=5e-3,
+                   threshold_type='relative', parallel=False, nproc=None, verbose=True):
+        """Delay transform and CLEAN of the sky and noisy visibilities on the GPU (:1622-1838, prisim_clean_delay): the windowed rows
+        vis * bp * bp_wts are zero-padded to M = nchan + int(nchan * pad) lags and inverse-transformed (M df ifft, :1738-1740), every
+        (baseline, snapshot) row is CLEANed with the lag kernel of bp * bp_wts inside the box of lags within the horizon limits widened by
+        clean_window_buffer / bw (:1764), and the clean components and residuals are transformed back, times deta * pad_factor
+        (:1808-1815).  Assigns lags (unshifted), skyvis_lag, vis_lag, lag_kernel, cc_lag_kernel (full length, shifted), cc_lags (shifted)
+        and the cc_skyvis_* / cc_vis_* lag and frequency products (:1816-1838); bp_wts when freq_wts is given.  The whole call is
+        validated and computed before any attribute changes.
+
+        Departures (one test each in tests/test_delay_clean.py):
+          - the box is made per (baseline, snapshot) whatever ``parallel`` says (the parallel branch, :1763-1764; the serial branch
+            never resets its box, so each row would get the union of all earlier rows' boxes); ``parallel`` and ``nproc`` have no effect;
+          - with <= 2 lags outside the box cond3 is False (the reference raises UnboundLocalError);
+          - on a noiseless array (vis_freq None) vis_lag and the cc_vis_* attributes stay None (SURVEY Q20);
+          - a one-row horizon_delay_limits serves every snapshot (the reference indexes it by snapshot and raises IndexError);
+          - complex1dClean's per-iteration rms histories are not formed."""
+        if not isinstance(pad, (int, float)):
+            raise TypeError('pad fraction must be a scalar value.')
+        if pad < 0.0:
+            pad = 0.0
+            if verbose:
+                print('\tPad fraction found to be negative. Resetting to 0.0 (no padding will be applied).')
+        if freq_wts is not None:
+            freq_wts = NP.asarray(freq_wts)
+        bp_layers, w_layers, report = self._window_factors(freq_wts)
+        threshold = _check_clean_args(threshold_type, threshold, gain, maxiter)
+        _check_gain_maxiter(gain, maxiter)
+        ia = self.ia
+        nbl, nchan, nt = ia.baselines.shape[0], self.f.size, self.n_acc
+        if nt == 0:
+            raise ValueError('no visibilities to clean: call observe() first')
+        hdl = NP.asarray(self.horizon_delay_limits, dtype=NP.float64)
+        if hdl.ndim != 3 or hdl.shape[1:] != (nbl, 2) or hdl.shape[0] not in (1, nt):
+            raise ValueError('horizon_delay_limits must have shape (1 or n_acc, n_baselines, 2)')
+        bw = self.df * nchan
+        npad = int(nchan * pad)
+        m = nchan + npad
+        lags = NP.fft.fftfreq(m, self.df)                                               # DSP.spectral_axis(..., shift=False), :1736
+        # :1764, one box per (baseline, snapshot)
+        boxes = NP.logical_and(lags <= hdl[:, :, 1:2] + clean_window_buffer / bw, lags >= hdl[:, :, 0:1] - clean_window_buffer / bw)
+        deta = lags[1] - lags[0]
+        pad_factor = (1.0 + 1.0 * npad / nchan)
+        cubes = [NP.asarray(ia.skyvis_freq, dtype=NP.complex128)]
+        if ia.vis_freq is not None:
+            cubes.append(NP.asarray(ia.vis_freq, dtype=NP.complex128))
+        ncubes = len(cubes)
+        wins = [bp_layers[t] * w_layers[t] for t in range(nt)]                          # self.bp * self.bp_wts (:1740)
+        ctx = ia._ctx
+        chunk = max(1, min(nt, (1 << 30) // max(1, ncubes * nbl * m * 16)))
+        names = ('lag', 'cc', 'res', 'cc_freq', 'res_freq')
+        full = {name: NP.empty((ncubes, nt, nbl, m), dtype=NP.complex128) for name in names}
+        kern_full = NP.empty((nt, nbl, m), dtype=NP.complex128)
+        iters = NP.empty((ncubes, nt, nbl), dtype=NP.int32)
+        flags = NP.empty((ncubes, nt, nbl), dtype=NP.int32)
+        stats = []
+        for t0 in range(0, nt, chunk):
+            t1 = min(nt, t0 + chunk)
+            # the distinct windows of the chunk and every row's index into them
+            kern_rows, kidx = [], NP.empty((t1 - t0, nbl), dtype=NP.int32)
+            for t in range(t0, t1):
+                w = wins[t]
+                hit = next((i for i, (tt, kw) in enumerate(kern_rows) if kw.shape == w.shape and NP.array_equal(kw, w)), None)
+                if hit is None:
+                    hit = len(kern_rows)
+                    kern_rows.append((t, w))
+                base = sum(kw.shape[0] for _, kw in kern_rows[:hit])
+                kidx[t - t0] = base + (NP.arange(nbl) if w.shape[0] == nbl else 0)
+            kwin = NP.concatenate([kw for _, kw in kern_rows], axis=0).astype(NP.complex128)
+            win = NP.empty((ncubes, t1 - t0, nbl, nchan), dtype=NP.complex128)
+            for c, cube in enumerate(cubes):
+                for t in range(t0, t1):
+                    win[c, t - t0] = (cube[:, :, t] * bp_layers[t]) * w_layers[t]         # skyvis_freq * bp * bp_wts (:1738-1739)
+            box = boxes[NP.arange(t0, t1) if hdl.shape[0] > 1 else NP.zeros(t1 - t0, dtype=int)]
+            out = ctx.clean_delay(win.reshape(ncubes, -1, nchan), kwin, box.reshape(-1, m), m, self.df, deta, pad_factor, gain, maxiter,
+                                  threshold, absolute=threshold_type == 'absolute', kidx=None if kwin.shape[0] == 1 else kidx.ravel())
+            for name in names:
+                full[name][:, t0:t1] = out[name].reshape(ncubes, t1 - t0, nbl, m)
+            kern_full[t0:t1] = out['kern_lag'][kidx.ravel()].reshape(t1 - t0, nbl, m) if kwin.shape[0] > 1 else out['kern_lag'][0]
+            iters[:, t0:t1] = out['iters'].reshape(ncubes, t1 - t0, nbl)
+            flags[:, t0:t1] = out['flags'].reshape(ncubes, t1 - t0, nbl)
+            stats.append(out['stats'])
+        if NP.any(flags & _abi.PRISIM_CLEAN_BAD_THRESHOLD):
+            raise ValueError('incompatible value specified for threshold')
+
+        def cube(c, name, shift):
+            x = NP.transpose(full[name][c], (1, 2, 0))                                  # (nt, nbl, M) -> (nbl, M, nt)
+            return NP.fft.fftshift(x, axes=1) if shift else NP.ascontiguousarray(x)
+
+        # commit (:1816-1838)
+        if report is not None:
+            self._bp_wts_override = report
+        self.lags = lags
+        self.skyvis_lag = cube(0, 'lag', True)
+        self.vis_lag = cube(1, 'lag', True) if ncubes > 1 else None
+        self.lag_kernel = NP.fft.fftshift(NP.transpose(kern_full, (1, 2, 0)), axes=1)
+        self.cc_lag_kernel = self.lag_kernel
+        for c, name in enumerate(('skyvis', 'vis')):
+            have = c < ncubes
+            lag_cc, lag_res = (cube(c, 'cc', True), cube(c, 'res', True)) if have else (None, None)
+            f_cc, f_res = (cube(c, 'cc_freq', False), cube(c, 'res_freq', False)) if have else (None, None)
+            setattr(self, 'cc_%s_lag' % name, lag_cc)
+            setattr(self, 'cc_%s_res_lag' % name, lag_res)
+            setattr(self, 'cc_%s_net_lag' % name, lag_cc + lag_res if have else None)
+            setattr(self, 'cc_%s_freq' % name, f_cc)
+            setattr(self, 'cc_%s_res_freq' % name, f_res)
+            setattr(self, 'cc_%s_net_freq' % name, f_cc + f_res if have else None)
+        self.cc_lags = NP.fft.fftshift(lags)
+        self.clean_window_buffer = clean_window_buffer
+        self._clean_iters = NP.transpose(iters, (0, 2, 1))                               # (cube, baseline, snapshot)
+        self._clean_stats = {'device_ms': sum(s['device_ms'] for s in stats), 'clean_ms': sum(s['clean_ms'] for s in stats),
+                             'sum_iter': int(sum(s['sum_iter'] for s in stats)), 'rows': int(sum(s['rows'] for s in stats)),
+                             'calls': len(stats)}
+        if verbose:
+            print('delayClean() completed: {0} rows, {1} iterations'.format(self._clean_stats['rows'], self._clean_stats['sum_iter']))
 
 
 class _Deferred(object):
@@ -593,7 +817,8 @@ class DelayPowerSpectrum(object):
         return float(NP.ravel(self.jacobian1 * self.jacobian2 * self.Jy2K ** 2)[0])
 
     def compute_power_spectrum(self):
-        """dps['skyvis' | 'vis' | 'noise'] = abs(lag spectrum)**2 * jacobian1 * jacobian2 * Jy2K**2 (:3982-3995).  When the delay
+        """dps['skyvis' | 'vis' | 'noise'] = abs(lag spectrum)**2 * jacobian1 * jacobian2 * Jy2K**2 (:3982-3995), and after
+        DelaySpectrum.delayClean the six dps['cc_*'] of the clean components, residuals and their sums (:3996-4002).  When the delay
         spectra are resident on the device the product is formed there (prisim_hip_delay_transform_device with power_scale = the factor)
         and fetched when dps['skyvis'] is read."""
         ds = self.ds
@@ -615,6 +840,11 @@ class DelayPowerSpectrum(object):
             dps['vis'] = NP.abs(ds.vis_lag) ** 2 * factor
         if ds.vis_noise_lag is not None:
             dps['noise'] = NP.abs(ds.vis_noise_lag) ** 2 * factor
+        if ds.cc_lags is not None:                                                       # :3996-4002
+            for key in ('cc_skyvis', 'cc_vis', 'cc_skyvis_res', 'cc_vis_res', 'cc_skyvis_net', 'cc_vis_net'):
+                lag = getattr(ds, key + '_lag')
+                if lag is not None:
+                    dps[key] = NP.abs(lag) ** 2 * factor
         self.dps = dps
         if ds.subband_delay_spectra or ds.subband_delay_spectra_resampled:
             warnings.warn('sub-band delay power spectra are not on the accelerated path')

@@ -1,0 +1,172 @@
+"""GPU: delay CLEAN (include/prisim_clean.h) against the reference's fixtures (tests/golden/golden_clean.npz), against the numpy checker
+(tests/clean_checker.py) on a seeded sweep of row lengths and kernels, and DelaySpectrum.delayClean at BASELINE config-2 size against the
+whole chain restated on the host."""
+import os
+import sys
+
+import numpy as NP
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import clean_checker as CK  # noqa: E402
+
+from prisim_amd import _abi, delay_spectrum as DS, skymodel as SM, workloads as W  # noqa: E402
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLD = os.path.join(HERE, 'golden', 'golden_clean.npz')
+pytestmark = pytest.mark.gpu
+
+
+def _flags(c1, c2, c3, no_out=False):
+    return int(c1) * _abi.PRISIM_CLEAN_THRESHOLD | int(c2) * _abi.PRISIM_CLEAN_MAXITER | int(c3) * _abi.PRISIM_CLEAN_INRMS | \
+        int(no_out) * _abi.PRISIM_CLEAN_NO_OUTRMS
+
+
+def test_fixtures_through_the_device():
+    g = NP.load(GOLD)
+    with _abi.Context(0) as ctx:
+        for i in range(int(g['n'])):
+            inp, kern, box = g['inp_%d' % i], g['kernel_%d' % i], g['cbox_%d' % i]
+            gain, maxiter, thr, absolute = g['params_%d' % i]
+            cc, res, it, fl, rms, st = ctx.clean_rows(inp[None], kern[None], box[None], gain, int(maxiter), thr, absolute=bool(absolute))
+            cond = g['cond_%d' % i]
+            assert it[0] == int(g['iter_%d' % i]), i
+            assert fl[0] == _flags(*cond), i
+            scale = max(NP.abs(inp).max(), 1e-300)
+            assert NP.max(NP.abs(cc[0] - g['cc_%d' % i])) <= 1e-12 * scale, i
+            assert NP.max(NP.abs(res[0] - g['res_%d' % i])) <= 1e-12 * scale, i
+            assert st['rows'] == 1 and st['sum_iter'] == it[0]
+
+
+def _sweep_rows(rng, nrows, m, per_row_kernels):
+    """Lag-like rows: a few tones plus noise under a tapered window of nchan = m // 2 (+1) channels, zero-padded to m."""
+    nchan = m // 2 + (m % 2)
+    f = NP.arange(nchan)
+    x = NP.zeros((nrows, m), dtype=complex)
+    nk = nrows if per_row_kernels else 1
+    wins = NP.empty((nk, nchan))
+    for k in range(nk):
+        p = rng.uniform(0.5, 3.0) if per_row_kernels else 2.0
+        wins[k] = NP.sin(NP.pi * (f + 0.5) / nchan) ** p
+    for r in range(nrows):
+        tau = rng.uniform(-0.15, 0.15, 5)
+        amp = rng.uniform(0.2, 5.0, 5) * NP.exp(2j * NP.pi * rng.uniform(size=5))
+        v = (amp[:, None] * NP.exp(-2j * NP.pi * f[None, :] * tau[:, None])).sum(axis=0)
+        v += rng.uniform(0.0, 0.3) * (rng.standard_normal(nchan) + 1j * rng.standard_normal(nchan))
+        x[r, :nchan] = v * wins[r if per_row_kernels else 0]
+    kz = NP.zeros((nk, m), dtype=complex)
+    kz[:, :nchan] = wins
+    lag = NP.fft.ifft(x, axis=1) * m
+    kern = NP.fft.ifft(kz, axis=1) * m
+    half = rng.integers(1, max(2, m // 10), size=nrows)
+    box = NP.zeros((nrows, m), dtype=NP.uint8)
+    for r in range(nrows):
+        box[r, :half[r] + 1] = 1
+        box[r, m - half[r] - (r % 2):] = 1
+    return lag, kern, box
+
+
+def test_seeded_sweep_against_the_checker():
+    rng = NP.random.default_rng(99)
+    plan = [(36, 500, False, 0.1), (36, 300, True, 0.5), (37, 500, True, 0.1), (37, 300, False, 0.5), (512, 240, False, 0.5),
+            (512, 60, True, 0.5), (1536, 40, False, 0.5), (2048, 40, True, 0.5), (4096, 24, False, 0.5)]
+    total = tolerated = 0
+    with _abi.Context(0) as ctx:
+        for m, nrows, per_row, gain in plan:
+            lag, kern, box = _sweep_rows(rng, nrows, m, per_row)
+            absolute = m % 2 == 1
+            thr = 1e-3 * float(NP.median(NP.abs(lag).max(axis=1))) if absolute else 2e-3
+            kidx = NP.arange(nrows) if per_row else None
+            cc, res, it, fl, rms, st = ctx.clean_rows(lag, kern, box, gain, 3000, thr, absolute=absolute, kidx=kidx)
+            for r in range(nrows):
+                o = CK.clean_row(lag[r], kern[r if per_row else 0], box[r], gain, 3000, thr, 'absolute' if absolute else 'relative')
+                want = _flags(o['cond1'], o['cond2'], o['cond3'], o['outrms'] is None)
+                if it[r] != o['iter'] or fl[r] != want:
+                    assert o['margin'] <= 4 * CK.ULP, (m, r, it[r], o['iter'], fl[r], want, o['margin'])
+                    print('tolerated: M %d row %d, the checker decided within %.2g (<= 4 ulp)' % (m, r, o['margin']))
+                    tolerated += 1
+                    continue
+                scale = NP.abs(lag[r]).max()
+                assert NP.max(NP.abs(cc[r] - o['cc'])) <= 1e-12 * scale, (m, r)
+                assert NP.max(NP.abs(res[r] - o['res'])) <= 1e-12 * scale, (m, r)
+            assert st['sum_iter'] == int(it.sum())
+            total += nrows
+    assert total >= 2000 and tolerated <= total // 100
+
+
+def test_row_length_limit_is_a_clear_error():
+    m = _abi.PRISIM_CLEAN_MAX_LEN + 2
+    with _abi.Context(0) as ctx:
+        with pytest.raises(ValueError, match='4096'):
+            ctx.clean_rows(NP.ones((1, m), dtype=complex), NP.ones((1, m), dtype=complex), NP.ones((1, m), dtype=NP.uint8), 0.1, 10, 5e-3)
+    with pytest.raises(ValueError, match='4096'):
+        DS.complex1dClean(NP.ones(m, dtype=complex), NP.ones(m, dtype=complex))
+
+
+def _config2_array(reserve, nt=4):
+    from prisim_amd import interferometry as RI
+    cfg = W.config2()
+    bl, ch, sky = cfg['baselines'], cfg['channels'], cfg['sky']
+    skymod = SM.SkyModel(location=sky['altaz'], flux_ref=sky['flux_ref'], spindex=sky['spindex'], ref_freq=sky['ref_freq'],
+                         src_shape=NP.stack((sky['fwhm_deg'], sky['fwhm_deg'], NP.zeros_like(sky['fwhm_deg'])), axis=1))
+    ia = RI.InterferometerArray(['b%d' % i for i in range(bl.shape[0])], bl, ch, telescope={'id': 'hera'}, latitude=-30.7224,
+                                skycoords='altaz', pointing_coords='altaz')
+    if reserve:
+        ia.reserve(nt)
+    bpass = 0.6 + 0.4 * NP.hanning(ch.size + 2)[1:-1]
+    for j in range(nt):
+        ia.observe((2457000.5 + j, 30.0 + 2.0 * j), {'Tnet': 200.0}, bpass, [90.0, 270.0], skymod, 10.7)
+    ia.generate_noise(seed=11)
+    ia.add_noise()
+    return ia
+
+
+@pytest.mark.parametrize('reserve', [True, False])
+def test_delay_clean_at_config2_size_against_the_host_chain(reserve):
+    ia = _config2_array(reserve)
+    nbl, nchan, nt = ia.baselines.shape[0], ia.channels.size, ia.n_acc
+    rng = NP.random.default_rng(7)
+    for pad, fw in ((1.0, None), (0.5, NP.blackman(nchan) + 0.02)) if reserve else ((0.5, None), (1.0, NP.blackman(nchan) + 0.02)):
+        ds = DS.DelaySpectrum(ia)
+        ds.delayClean(pad=pad, freq_wts=fw, verbose=False)
+        sky, vis = NP.asarray(ia.skyvis_freq), NP.asarray(ia.vis_freq)
+        bp = NP.asarray(ia.bp)
+        w = NP.ones_like(bp) if fw is None else NP.broadcast_to(fw.reshape(1, -1, 1), bp.shape)
+        npad = int(nchan * pad)
+        m = nchan + npad
+        lags = NP.fft.fftfreq(m, ds.df)
+        assert NP.array_equal(ds.lags, lags) and NP.array_equal(ds.cc_lags, NP.fft.fftshift(lags))
+
+        def to_lag(x):
+            return (npad + nchan) * ds.df * NP.fft.ifft(NP.pad(x, ((0, 0), (0, npad), (0, 0)), mode='constant'), axis=1)
+
+        for got, want in ((ds.skyvis_lag, NP.fft.fftshift(to_lag(sky * bp * w), axes=1)),
+                          (ds.vis_lag, NP.fft.fftshift(to_lag(vis * bp * w), axes=1)),
+                          (ds.lag_kernel, NP.fft.fftshift(to_lag(bp * w), axes=1))):
+            assert got.shape == (nbl, m, nt)
+            assert NP.max(NP.abs(got - want)) <= 1e-10 * NP.max(NP.abs(want))
+        # every cc_* product of a sample of rows, through the whole chain on the host
+        kern = to_lag(bp * w)
+        bw = ds.df * nchan
+        deta, pf = lags[1] - lags[0], 1.0 + 1.0 * npad / nchan
+        rows = [(int(b), int(t)) for b, t in zip(rng.integers(0, nbl, 6), rng.integers(0, nt, 6))]
+        for name, cube in (('skyvis', sky), ('vis', vis)):
+            lag = to_lag(cube * bp * w)
+            scale = {k: NP.max(NP.abs(getattr(ds, 'cc_%s_%s' % (name, k)))) for k in ('lag', 'res_lag', 'net_lag', 'freq', 'res_freq', 'net_freq')}
+            for b, t in rows:
+                hdl = ds.horizon_delay_limits
+                box = CK.clean_box(lags, hdl[t if hdl.shape[0] > 1 else 0, b], 1.0, bw)
+                o = CK.clean_row(lag[b, :, t], kern[b, :, t], box)
+                assert ds._clean_iters[0 if name == 'skyvis' else 1, b, t] == o['iter'], (name, b, t)
+                want = {'lag': NP.fft.fftshift(o['cc']), 'res_lag': NP.fft.fftshift(o['res']),
+                        'freq': NP.fft.fft(o['cc']) * deta * pf, 'res_freq': NP.fft.fft(o['res']) * deta * pf}
+                want['net_lag'] = want['lag'] + want['res_lag']
+                want['net_freq'] = want['freq'] + want['res_freq']
+                for k, v in want.items():
+                    got = getattr(ds, 'cc_%s_%s' % (name, k))[b, :, t]
+                    assert NP.max(NP.abs(got - v)) <= 1e-10 * scale[k], (name, k, b, t)
+        assert NP.array_equal(ds.cc_lag_kernel, ds.lag_kernel)
+        dps = DS.DelayPowerSpectrum(ds)
+        dps.compute_power_spectrum()
+        assert NP.allclose(dps.dps['cc_vis_net'], NP.abs(ds.cc_vis_net_lag) ** 2 * dps.jacobian1 * dps.jacobian2 * dps.Jy2K ** 2,
+                           rtol=1e-14, atol=0)
