@@ -8,6 +8,8 @@ import os
 
 import numpy as NP
 
+from . import dsp_readings
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PRISIM_HIP_LIB') or os.path.join(_HERE, 'lib', 'libprisim_hip.so')      # PRISIM_HIP_LIB: A/B another build of the same ABI
 ABI_VERSION = 'prisim_hip 0.5 gfx950'       # prisim_hip_version(): bumped whenever a struct or a signature of include/prisim_hip.h changes
@@ -41,6 +43,13 @@ EXPORTS = (
 CLEAN_EXPORTS = ('prisim_clean_rows', 'prisim_clean_delay')
 PRISIM_CLEAN_MAX_LEN = 4096
 PRISIM_CLEAN_THRESHOLD, PRISIM_CLEAN_MAXITER, PRISIM_CLEAN_INRMS, PRISIM_CLEAN_NO_OUTRMS, PRISIM_CLEAN_BAD_THRESHOLD = 1, 2, 4, 8, 16
+
+# every symbol include/prisim_subband.h declares: sub-band delay spectra (prisim_amd/csrc_subband/), linked into the same library
+SUBBAND_EXPORTS = ('prisim_subband_transform',)
+PRISIM_SUBBAND_MAX_LEN = 4096
+PRISIM_SUBBAND_OVER, PRISIM_SUBBAND_OVER_POWER, PRISIM_SUBBAND_RES, PRISIM_SUBBAND_RES_POWER = 1, 2, 4, 8
+PRISIM_SUBBAND_AUTO, PRISIM_SUBBAND_FUSED, PRISIM_SUBBAND_ROCFFT = -1, 0, 1
+SUBBAND_ROUTES = {PRISIM_SUBBAND_FUSED: 'fused', PRISIM_SUBBAND_ROCFFT: 'rocfft'}
 
 
 class PrisimSky(C.Structure):
@@ -161,6 +170,11 @@ class PrisimCleanStats(C.Structure):
                 ('waves_per_block', C.c_int32), ('kernel_in_lds', C.c_int32), ('lds_bytes', C.c_int64)]
 
 
+class PrisimSubbandStats(C.Structure):
+    _fields_ = [('device_ms', C.c_double), ('kernel_ms', C.c_double), ('rows', C.c_int64), ('route', C.c_int32),
+                ('lds_bytes', C.c_int32)]
+
+
 class PrisimHipError(RuntimeError):
     """Raised when libprisim_hip.so is missing/unloadable or no GPU is usable."""
 
@@ -244,6 +258,9 @@ def load_library():
                                        vp, vp, vp, vp, vp, vp, vp, C.POINTER(PrisimCleanStats)]
     for name in CLEAN_EXPORTS:
         getattr(lib, name).restype = C.c_int
+    lib.prisim_subband_transform.argtypes = [vp, C.c_int32, i64, i64, i64, vp, i64, vp, i64, C.c_int32, vp, i64, dbl, i64, i64, vp, vp, vp,
+                                             vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.POINTER(PrisimSubbandStats)]
+    lib.prisim_subband_transform.restype = C.c_int
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ('prisim_hip_destroy', 'prisim_hip_last_error', 'prisim_hip_version'):
@@ -778,6 +795,62 @@ class Context(object):
                                                  _ptr(out['iters']), _ptr(out['flags']), _ptr(out['rms']), C.byref(st)), 'prisim_clean_delay')
         out['stats'] = self._clean_stats(st)
         return out
+
+    # ---- sub-band delay spectra (include/prisim_subband.h) ----
+    def subband_transform(self, cubes, bp, wts, m, df, nres=0, pscale=None, want=('over', 'res'), route='auto', nbl=None, t0=0, nt=None):
+        """Sub-band delay spectra on the device (prisim_subband_transform).  cubes: (ncubes, nt, nbl, nchan) complex128 on the host, or
+        None for the resident visibility slots [t0, t0 + nt) of this context; bp: (nbp, nchan) bandpass rows, nbp in (1, nbl, nt nbl);
+        wts: (nwin, nchan) windows; m lags (zero padding), nres resampled lags; pscale (nwin,) for the power products.  want: any of
+        'over', 'over_power', 'res', 'res_power'.  Returns a dict of the wanted outputs, shaped (ncubes, nt, nbl, nwin, m | nres), and
+        'stats' (device_ms, kernel_ms, rows, route 'fused' | 'rocfft', lds_bytes)."""
+        w = NP.ascontiguousarray(wts, dtype=NP.float64)
+        w = w.reshape(-1, w.shape[-1])
+        nwin, nchan = w.shape
+        if cubes is None:
+            x, ncubes, nbl = None, 1, self.nbl if nbl is None else int(nbl)
+            if nt is None:
+                raise ValueError('nt is required with resident input')
+        else:
+            x = NP.ascontiguousarray(cubes, dtype=NP.complex128)
+            ncubes, nt, nbl = x.shape[0], x.shape[1], x.shape[2]
+            if x.shape[3] != nchan:
+                raise ValueError('cubes and wts must have the same channel count')
+        b = NP.ascontiguousarray(bp, dtype=NP.float64).reshape(-1, nchan)
+        bits = {'over': PRISIM_SUBBAND_OVER, 'over_power': PRISIM_SUBBAND_OVER_POWER, 'res': PRISIM_SUBBAND_RES,
+                'res_power': PRISIM_SUBBAND_RES_POWER}
+        flag = 0
+        for name in want:
+            flag |= bits[name]
+        ps = None if pscale is None else NP.ascontiguousarray(NP.broadcast_to(NP.asarray(pscale, dtype=NP.float64).ravel(), (nwin,)))
+        out = {}
+        for name in want:
+            n = m if name.startswith('over') else max(int(nres), 1)
+            out[name] = NP.empty((ncubes, nt, nbl, nwin, n), dtype=NP.complex128 if name in ('over', 'res') else NP.float64)
+        mo = mi = mw = None
+        if flag & (PRISIM_SUBBAND_RES | PRISIM_SUBBAND_RES_POWER) and 1 <= int(nres) <= PRISIM_SUBBAND_MAX_LEN:
+            mo, mi, mw = (NP.ascontiguousarray(a) for a in dsp_readings.resample_map(m, nres))    # the one reading of the resampling
+        st = PrisimSubbandStats()
+        r = {'auto': PRISIM_SUBBAND_AUTO, 'fused': PRISIM_SUBBAND_FUSED, 'rocfft': PRISIM_SUBBAND_ROCFFT}[route]
+        self._check(self._lib.prisim_subband_transform(self._h, ncubes, int(nt), int(nbl), nchan, _ptr(x), int(t0), _ptr(b), b.shape[0],
+                                                       nwin, _ptr(w), int(m), float(df), int(nres), 0 if mo is None else mo.size,
+                                                       _ptr(mo), _ptr(mi), _ptr(mw), _ptr(ps), flag, r,
+                                                       _ptr(out.get('over')), _ptr(out.get('over_power')), _ptr(out.get('res')),
+                                                       _ptr(out.get('res_power')), C.byref(st)), 'prisim_subband_transform')
+        out['stats'] = self._subband_stats(st)
+        return out
+
+    def subband_power_resident(self, t0, nt, bp, wts, m, df, pscale, nres=0, route='auto'):
+        """Power-only sub-band spectra of the resident snapshots [t0, t0 + nt): |.|^2 * pscale[w] of the oversampled (and, with nres > 0,
+        the resampled) spectra of the visibilities already in HBM.  No complex spectrum leaves the device and no visibility is uploaded.
+        Returns (over_power (nt, nbl, nwin, m), res_power (nt, nbl, nwin, nres) or None, stats)."""
+        want = ('over_power', 'res_power') if nres > 0 else ('over_power',)
+        out = self.subband_transform(None, bp, wts, m, df, nres=nres, pscale=pscale, want=want, route=route, t0=t0, nt=nt)
+        return out['over_power'][0], (out['res_power'][0] if nres > 0 else None), out['stats']
+
+    @staticmethod
+    def _subband_stats(st):
+        return {'device_ms': st.device_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows), 'route': SUBBAND_ROUTES.get(st.route, st.route),
+                'lds_bytes': int(st.lds_bytes)}
 
     # ---- multi-GPU ----
     @staticmethod

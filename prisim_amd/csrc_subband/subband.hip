@@ -1,0 +1,461 @@
+// subband.hip -- sub-band delay spectra for gfx950 (include/prisim_subband.h): prisim/delay_spectrum.py:subband_delay_transform
+// (:2196-2236) for every (snapshot, baseline) row of one or more cubes, every frequency window, and the FFT resampling of the spectra.
+//
+// Fused route (m a power of two, LDS permitting): one workgroup per row.  Per cube the row times its bandpass is read once into LDS;
+// then for every window w
+//   oversampled: x[n] = row[n] bp[n] wts[w][n] on the window's nonzero channel span [lo, hi), zero elsewhere up to m.  With even m,
+//     m df fftshift(ifft(x))[j] = df sum_n x[n] (-1)^n e^{+2 pi i j n / m}: the sign and df are folded into the load (bit-reversed
+//     into LDS) and a radix-2 in-place transform with an LDS twiddle table gives the shifted spectrum in natural order;
+//   resampled: the FFT of the oversampled series is m df e^{-2 pi i k floor(m/2) / m} x[k], so scipy.signal.resample's spectrum
+//     Y[k_out] = sum of at most two weighted bins x[k_in] (the caller's selection map, prisim_amd/dsp_readings.py:resample_map)
+//     follows from the row in LDS without the m lags: the nonzero Y[k_out] are compacted and
+//     y[q] = (1 / m) sum_k_out Y[k_out] e^{+2 pi i k_out q / nres} is summed directly (the kept bins are the lowest and highest
+//     ~nres/2 channels, so a window away from channel 0 has none and writes zeros).
+// Each output element is written once.
+// rocFFT route (any other m): k_sb_prepare writes the windowed padded rows [cube][row][window][m] (and the resampled spectra, as above)
+// -> batched inverse rocFFT in place -> k_sb_finish shifts, scales by df and forms the power.
+// fp64 throughout, built with -ffp-contract=off (the products round as numpy's).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../csrc/ctx_internal.h"
+#include "../../include/prisim_subband.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int64_t kMaxGridRows = int64_t(1) << 22;     // rows per launch: grid x threads stays far inside 32 bits
+
+__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ double2 rmul(double2 a, double s) { return make_double2(a.x * s, a.y * s); }
+
+struct SbParams {
+  const double2* src;       // row r of cube c: src + c * cube_stride + r * nchan
+  int64_t cube_stride;
+  const double* bp;         // [nbp][nchan]
+  int bp_mode;              // 0: one row; 1: r % nbl; 2: row r
+  int64_t nbl, nrows;
+  const double* wts;        // [nwin][nchan]
+  const int32_t* span;      // [nwin][2] nonzero channel span [lo, hi)
+  int ncubes, nwin, nchan, m, logm, nres;
+  double df;
+  const int32_t* rs_in;     // [2][nres] bins of the resampled spectrum (-1: none)
+  const double2* rs_c;      // [2][nres] their coefficients, weight df e^{-2 pi i k_in floor(m/2) / m}
+  const double2* rtw;       // [nres] e^{+2 pi i q / nres}
+  const double* pscale;     // [nwin]
+  double2* over;            // [ncubes][nrows][nwin][m]
+  double* over_pow;
+  double2* res;             // [ncubes][nrows][nwin][nres]
+  double* res_pow;
+  double2* fbuf;            // rocFFT route: [ncubes][nrows][nwin][m]
+  int64_t row0;             // first row of this launch (launches cover at most kMaxGridRows rows)
+};
+
+__device__ __forceinline__ const double* bp_row(const SbParams& P, int64_t r) {
+  return P.bp + (P.bp_mode == 0 ? 0 : (P.bp_mode == 1 ? r % P.nbl : r)) * (int64_t)P.nchan;
+}
+
+// xs[n] = row[n] * bp[n] for one cube
+__device__ __forceinline__ void load_row(const SbParams& P, int c, int64_t r, double2* xs) {
+  const double2* row = P.src + (int64_t)c * P.cube_stride + r * (int64_t)P.nchan;
+  const double* b = bp_row(P, r);
+  for (int n = threadIdx.x; n < P.nchan; n += kThreads) xs[n] = rmul(row[n], b[n]);
+}
+
+// resampled spectrum of window w (and its power) from xs; z: [nres] double2, zi: [nres] int, cnt: one int of LDS
+__device__ void resample_window(const SbParams& P, const double2* xs, int c, int64_t r, int w, int lo, int hi, double2* z, int* zi,
+                                int* cnt) {
+  const double* wt = P.wts + (int64_t)w * P.nchan;
+  const int nres = P.nres;
+  for (int k = threadIdx.x; k < nres; k += kThreads) {
+    double2 v = make_double2(0.0, 0.0);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int i = P.rs_in[s * nres + k];
+      if (i >= lo && i < hi) v = cadd(v, cmul(rmul(xs[i], wt[i]), P.rs_c[s * nres + k]));
+    }
+    z[k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {                       // wave 0 compacts the nonzero bins in increasing order
+    const int lane = threadIdx.x;
+    int total = 0;
+    for (int base = 0; base < nres; base += 64) {
+      const int k = base + lane;
+      const bool nz = k < nres && (z[k].x != 0.0 || z[k].y != 0.0);
+      const uint64_t mask = __ballot(nz);
+      if (nz) zi[total + __popcll(mask & ((1ull << lane) - 1ull))] = k;
+      total += __popcll(mask);
+    }
+    if (lane == 0) *cnt = total;
+  }
+  __syncthreads();
+  const int nz = *cnt;
+  const int64_t o = (((int64_t)c * P.nrows + r) * P.nwin + w) * nres;
+  const double ps = P.pscale ? P.pscale[w] : 0.0;
+  for (int q = threadIdx.x; q < nres; q += kThreads) {
+    double2 acc = make_double2(0.0, 0.0);
+    for (int i = 0; i < nz; ++i) {
+      const int k = zi[i];
+      acc = cadd(acc, cmul(z[k], P.rtw[(int)(((int64_t)k * q) % nres)]));
+    }
+    if (P.res) P.res[o + q] = acc;
+    if (P.res_pow) P.res_pow[o + q] = (acc.x * acc.x + acc.y * acc.y) * ps;
+  }
+  __syncthreads();
+}
+
+// fused route.  LDS: xs [nchan] | buf [m] | tw [m/2] | z [nres] | zi [nres] int | cnt
+__global__ void __launch_bounds__(kThreads) k_sb_fused(SbParams P) {
+  extern __shared__ double2 lds[];
+  const int m = P.m, nchan = P.nchan;
+  double2* xs = lds;
+  double2* buf = xs + nchan;
+  double2* tw = buf + m;
+  double2* z = tw + (m / 2 > 0 ? m / 2 : 1);
+  int* zi = reinterpret_cast<int*>(z + P.nres);
+  int* cnt = zi + P.nres;
+  const int64_t r = P.row0 + blockIdx.x;
+  const bool want_over = P.over || P.over_pow, want_res = P.res || P.res_pow;
+  for (int k = threadIdx.x; k < m / 2; k += kThreads) {
+    double s, co;
+    sincospi(2.0 * (double)k / (double)m, &s, &co);
+    tw[k] = make_double2(co, s);
+  }
+  for (int c = 0; c < P.ncubes; ++c) {
+    load_row(P, c, r, xs);
+    __syncthreads();
+    for (int w = 0; w < P.nwin; ++w) {
+      const int lo = P.span[2 * w], hi = P.span[2 * w + 1];
+      if (want_over) {
+        const double* wt = P.wts + (int64_t)w * nchan;
+        for (int n = threadIdx.x; n < m; n += kThreads) {
+          const int j = P.logm ? (int)(__brev((unsigned)n) >> (32 - P.logm)) : 0;
+          double2 v = make_double2(0.0, 0.0);
+          if (n >= lo && n < hi) v = rmul(rmul(xs[n], wt[n]), (m > 1 && (n & 1)) ? -P.df : P.df);
+          buf[j] = v;
+        }
+        __syncthreads();
+        for (int h = 1; h < m; h <<= 1) {             // butterflies of span 2h; twiddle W_{2h}^pos = tw[pos * m / (2h)]
+          const int step = m / (2 * h);
+          for (int i = threadIdx.x; i < m / 2; i += kThreads) {
+            const int pos = i & (h - 1);
+            const int a = ((i - pos) << 1) + pos, b = a + h;
+            const double2 u = buf[a], v = cmul(buf[b], tw[pos * step]);
+            buf[a] = cadd(u, v);
+            buf[b] = csub(u, v);
+          }
+          __syncthreads();
+        }
+        const int64_t o = (((int64_t)c * P.nrows + r) * P.nwin + w) * m;
+        const double ps = P.pscale ? P.pscale[w] : 0.0;
+        for (int j = threadIdx.x; j < m; j += kThreads) {
+          const double2 v = buf[j];
+          if (P.over) P.over[o + j] = v;
+          if (P.over_pow) P.over_pow[o + j] = (v.x * v.x + v.y * v.y) * ps;
+        }
+        __syncthreads();
+      }
+      if (want_res) resample_window(P, xs, c, r, w, lo, hi, z, zi, cnt);
+    }
+    __syncthreads();
+  }
+}
+
+// rocFFT route, before the transform.  LDS: xs [nchan] | z [nres] | zi [nres] int | cnt
+__global__ void __launch_bounds__(kThreads) k_sb_prepare(SbParams P) {
+  extern __shared__ double2 lds[];
+  double2* xs = lds;
+  double2* z = xs + P.nchan;
+  int* zi = reinterpret_cast<int*>(z + P.nres);
+  int* cnt = zi + P.nres;
+  const int64_t r = P.row0 + blockIdx.x;
+  const bool want_over = P.over || P.over_pow, want_res = P.res || P.res_pow;
+  for (int c = 0; c < P.ncubes; ++c) {
+    load_row(P, c, r, xs);
+    __syncthreads();
+    for (int w = 0; w < P.nwin; ++w) {
+      const int lo = P.span[2 * w], hi = P.span[2 * w + 1];
+      if (want_over) {
+        const double* wt = P.wts + (int64_t)w * P.nchan;
+        double2* dst = P.fbuf + (((int64_t)c * P.nrows + r) * P.nwin + w) * P.m;
+        for (int n = threadIdx.x; n < P.m; n += kThreads)
+          dst[n] = (n >= lo && n < hi) ? rmul(xs[n], wt[n]) : make_double2(0.0, 0.0);
+      }
+      if (want_res) resample_window(P, xs, c, r, w, lo, hi, z, zi, cnt);
+    }
+    __syncthreads();
+  }
+}
+
+// rocFFT route, after the unnormalised inverse transform F: oversampled[j] = df F[(j - floor(m/2)) mod m]
+__global__ void __launch_bounds__(kThreads) k_sb_finish(SbParams P, int64_t nlines) {
+  const int m = P.m, half = m / 2;
+  const int64_t total = nlines * m;
+  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
+    const int64_t line = e / m;
+    const int j = (int)(e - line * m);
+    const double2 v = rmul(P.fbuf[line * m + (j + m - half) % m], P.df);
+    if (P.over) P.over[e] = v;
+    if (P.over_pow) P.over_pow[e] = (v.x * v.x + v.y * v.y) * P.pscale[line % P.nwin];
+  }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+
+struct Dev {
+  std::vector<void*> ptrs;
+  ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
+};
+
+#define SB_ALLOC(ctx, dev, ptr, bytes)                                                                 \
+  do {                                                                                                 \
+    void* p_ = nullptr;                                                                                \
+    HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
+    (dev).ptrs.push_back(p_);                                                                          \
+    (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
+  } while (0)
+
+struct Events {
+  hipEvent_t e[4] = {};
+  ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+struct FftPlan {
+  rocfft_plan p = nullptr;
+  rocfft_execution_info i = nullptr;
+  ~FftPlan() {
+    if (p) g_rocfft.plan_destroy(p);
+    if (i) g_rocfft.execution_info_destroy(i);
+  }
+};
+
+int lds_fused(int64_t nchan, int64_t m, int64_t nres) {
+  return (int)(16 * (nchan + m + std::max<int64_t>(m / 2, 1) + nres) + 4 * nres + 16);
+}
+int lds_prepare(int64_t nchan, int64_t nres) { return (int)(16 * (nchan + nres) + 4 * nres + 16); }
+
+}  // namespace
+
+extern "C" {
+
+int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_t nbl, int64_t nchan, const double* cubes, int64_t t0,
+                             const double* bp, int64_t nbp, int32_t nwin, const double* wts, int64_t m, double df, int64_t nres,
+                             int64_t nmap, const int64_t* map_out, const int64_t* map_in, const double* map_w, const double* pscale,
+                             int32_t want, int32_t route, double* over, double* over_pow, double* res, double* res_pow,
+                             prisim_subband_stats* stats) {
+  return guarded(ctx, [&]() -> int {
+  if (!ctx) return PRISIM_EINVAL;
+  if (m < 1 || m > PRISIM_SUBBAND_MAX_LEN)
+    return fail(ctx, PRISIM_EINVAL, "sub-band spectra take 1 to " + std::to_string(PRISIM_SUBBAND_MAX_LEN) +
+                                        " lags (PRISIM_SUBBAND_MAX_LEN); got m = " + std::to_string(m));
+  const bool w_over = want & PRISIM_SUBBAND_OVER, w_opow = want & PRISIM_SUBBAND_OVER_POWER;
+  const bool w_res = want & PRISIM_SUBBAND_RES, w_rpow = want & PRISIM_SUBBAND_RES_POWER;
+  if ((w_res || w_rpow) && (nres < 1 || nres > PRISIM_SUBBAND_MAX_LEN))
+    return fail(ctx, PRISIM_EINVAL, "resampled sub-band spectra take 1 to " + std::to_string(PRISIM_SUBBAND_MAX_LEN) +
+                                        " lags (PRISIM_SUBBAND_MAX_LEN); got nres = " + std::to_string(nres));
+  if (!(w_res || w_rpow)) nres = 0;
+  if (ncubes < 1 || nt < 0 || nbl < 1 || nchan < 1 || nchan > m || nwin < 1)
+    return fail(ctx, PRISIM_EINVAL, "need ncubes >= 1, nt >= 0, nbl >= 1, nwin >= 1 and 1 <= nchan <= m");
+  if (!(w_over || w_opow || w_res || w_rpow)) return fail(ctx, PRISIM_EINVAL, "nothing requested (want)");
+  if (!bp || !wts || (w_over && !over) || (w_opow && !over_pow) || (w_res && !res) || (w_rpow && !res_pow) ||
+      ((w_opow || w_rpow) && !pscale))
+    return fail(ctx, PRISIM_EINVAL, "null array");
+  const int64_t nrows = nt * nbl;
+  int bp_mode;
+  if (nbp == 1) bp_mode = 0;
+  else if (nbp == nbl) bp_mode = 1;
+  else if (nbp == nrows) bp_mode = 2;
+  else return fail(ctx, PRISIM_EINVAL, "nbp must be 1, nbl or nt * nbl");
+  if (!cubes) {
+    if (!ctx->array_set) return fail(ctx, PRISIM_ESTATE, "resident input needs set_array first");
+    if (ncubes != 1 || nbl != ctx->nbl || nchan != ctx->nchan) return fail(ctx, PRISIM_EINVAL, "resident input is one cube of the array's shape");
+    if (t0 < 0 || t0 + nt > ctx->nt_max) return fail(ctx, PRISIM_EINVAL, "resident slots out of range");
+  }
+  if (route < PRISIM_SUBBAND_AUTO || route > PRISIM_SUBBAND_ROCFFT) return fail(ctx, PRISIM_EINVAL, "unknown route");
+  int logm = 0;
+  while ((int64_t(1) << logm) < m) ++logm;
+  const bool pow2 = (int64_t(1) << logm) == m;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int lds_max = 0;
+  HIPCHK(ctx, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  const int lf = lds_fused(nchan, m, nres), lp = lds_prepare(nchan, nres);
+  const bool fused_ok = pow2 && lf <= lds_max;
+  if (route == PRISIM_SUBBAND_FUSED && !fused_ok)
+    return fail(ctx, PRISIM_EINVAL, "the fused sub-band kernel takes power-of-two m whose rows fit in LDS (" + std::to_string(lf) +
+                                        " B needed, " + std::to_string(lds_max) + " B per workgroup)");
+  const bool fused = route == PRISIM_SUBBAND_FUSED || (route == PRISIM_SUBBAND_AUTO && fused_ok);
+  if (!fused && lp > lds_max) return fail(ctx, PRISIM_EINVAL, "sub-band rows do not fit in LDS");
+  const bool want_over = w_over || w_opow;
+  if (!fused && want_over) {
+    std::string lerr;
+    if (!load_rocfft(lerr)) return fail(ctx, PRISIM_ELIB, lerr);
+    if (!g_rocfft.setup_done) {
+      if (g_rocfft.setup() != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_setup failed");
+      g_rocfft.setup_done = true;
+    }
+  }
+
+  // window spans and the resampling tables
+  std::vector<int32_t> span(2 * (size_t)nwin);
+  for (int w = 0; w < nwin; ++w) {
+    int64_t lo = nchan, hi = 0;
+    for (int64_t n = 0; n < nchan; ++n)
+      if (wts[w * nchan + n] != 0.0) { lo = std::min(lo, n); hi = n + 1; }
+    span[2 * w] = (int32_t)(lo < hi ? lo : 0);
+    span[2 * w + 1] = (int32_t)(lo < hi ? hi : 0);
+  }
+  const int64_t nr = std::max<int64_t>(nres, 1);
+  std::vector<int32_t> rs_in(2 * (size_t)nr, -1);
+  std::vector<double> rs_c(4 * (size_t)nr, 0.0), rtw(2 * (size_t)nr, 0.0);
+  if (nres > 0) {
+    if (nmap < 1 || !map_out || !map_in || !map_w) return fail(ctx, PRISIM_EINVAL, "the resampled spectra need the selection map");
+    std::vector<int> used((size_t)nres, 0);
+    const int64_t half = m / 2;
+    for (int64_t e = 0; e < nmap; ++e) {
+      const int64_t k = map_out[e], kin = map_in[e];
+      if (k < 0 || k >= nres || kin < 0 || kin >= m) return fail(ctx, PRISIM_EINVAL, "selection map entry out of range");
+      if (used[(size_t)k] == 2) return fail(ctx, PRISIM_EINVAL, "selection map: more than two entries for one output bin");
+      const int s = used[(size_t)k]++;
+      if (kin >= nchan) continue;                    // a bin of the zero padding
+      const int64_t red = (kin * half) % m;          // e^{-2 pi i k_in floor(m/2) / m}
+      const double a = -2.0 * M_PI * (double)red / (double)m;
+      const double sc = map_w[e] * df;               // weight * (m df) * (1 / m): the ifft's 1 / nres times resample's nres / m
+      rs_in[(size_t)s * nr + k] = (int32_t)kin;
+      rs_c[2 * ((size_t)s * nr + k)] = sc * std::cos(a);
+      rs_c[2 * ((size_t)s * nr + k) + 1] = sc * std::sin(a);
+    }
+    for (int64_t q = 0; q < nres; ++q) {
+      const double a = 2.0 * M_PI * (double)q / (double)nres;
+      rtw[2 * q] = std::cos(a);
+      rtw[2 * q + 1] = std::sin(a);
+    }
+  }
+
+  Dev dev;
+  Events ev;
+  for (hipEvent_t& e : ev.e) HIPCHK(ctx, hipEventCreate(&e));
+  const size_t in_bytes = (size_t)ncubes * nrows * nchan * 16;
+  const size_t bp_bytes = (size_t)nbp * nchan * 8, w_bytes = (size_t)nwin * nchan * 8;
+  const int64_t nlines = (int64_t)ncubes * nrows * nwin;
+  const size_t over_n = (size_t)nlines * m, res_n = (size_t)nlines * std::max<int64_t>(nres, 0);
+  double2* d_in = nullptr;
+  double *d_bp, *d_wts, *d_ps;
+  int32_t *d_span, *d_rsin;
+  double2 *d_rsc, *d_rtw, *d_over = nullptr, *d_res = nullptr, *d_fbuf = nullptr;
+  double *d_opow = nullptr, *d_rpow = nullptr;
+  if (cubes) SB_ALLOC(ctx, dev, d_in, in_bytes);
+  SB_ALLOC(ctx, dev, d_bp, bp_bytes);
+  SB_ALLOC(ctx, dev, d_wts, w_bytes);
+  SB_ALLOC(ctx, dev, d_ps, (size_t)nwin * 8);
+  SB_ALLOC(ctx, dev, d_span, span.size() * 4);
+  SB_ALLOC(ctx, dev, d_rsin, rs_in.size() * 4);
+  SB_ALLOC(ctx, dev, d_rsc, rs_c.size() * 8);
+  SB_ALLOC(ctx, dev, d_rtw, rtw.size() * 8);
+  if (w_over) SB_ALLOC(ctx, dev, d_over, over_n * 16);
+  if (w_opow) SB_ALLOC(ctx, dev, d_opow, over_n * 8);
+  if (w_res) SB_ALLOC(ctx, dev, d_res, res_n * 16);
+  if (w_rpow) SB_ALLOC(ctx, dev, d_rpow, res_n * 8);
+  if (!fused && want_over) SB_ALLOC(ctx, dev, d_fbuf, over_n * 16);
+  FftPlan plan;
+  if (!fused && want_over && nlines > 0) {
+    size_t len = (size_t)m;
+    RocfftApi& F = g_rocfft;
+    if (F.plan_create(&plan.p, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, rocfft_precision_double, 1, &len,
+                      (size_t)nlines, nullptr) != rocfft_status_success) {
+      plan.p = nullptr;
+      return fail(ctx, PRISIM_ELIB, "rocfft_plan_create failed");
+    }
+    if (F.execution_info_create(&plan.i) != rocfft_status_success) {
+      plan.i = nullptr;
+      return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_create failed");
+    }
+    if (F.execution_info_set_stream(plan.i, ctx->stream) != rocfft_status_success)
+      return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_stream failed");
+    size_t wbytes = 0;
+    F.plan_get_work_buffer_size(plan.p, &wbytes);
+    if (wbytes) {
+      void* wb;
+      SB_ALLOC(ctx, dev, wb, wbytes);
+      if (F.execution_info_set_work_buffer(plan.i, wb, wbytes) != rocfft_status_success)
+        return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_work_buffer failed");
+    }
+  }
+
+  HIPCHK(ctx, hipEventRecord(ev.e[0], ctx->stream));
+  if (cubes && in_bytes) HIPCHK(ctx, hipMemcpyAsync(d_in, cubes, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_bp, bp, bp_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_wts, wts, w_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (pscale) HIPCHK(ctx, hipMemcpyAsync(d_ps, pscale, (size_t)nwin * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_span, span.data(), span.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_rsin, rs_in.data(), rs_in.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_rsc, rs_c.data(), rs_c.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_rtw, rtw.data(), rtw.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+
+  SbParams P;
+  P.src = cubes ? d_in : (const double2*)ctx->cube.p + t0 * nbl * nchan;
+  P.cube_stride = nrows * nchan;
+  P.bp = d_bp; P.bp_mode = bp_mode; P.nbl = nbl; P.nrows = nrows;
+  P.wts = d_wts; P.span = d_span;
+  P.ncubes = ncubes; P.nwin = nwin; P.nchan = (int)nchan; P.m = (int)m; P.logm = logm; P.nres = (int)nres;
+  P.df = df;
+  P.rs_in = d_rsin; P.rs_c = d_rsc; P.rtw = d_rtw;
+  P.pscale = pscale ? d_ps : nullptr;
+  P.over = d_over; P.over_pow = d_opow; P.res = d_res; P.res_pow = d_rpow; P.fbuf = d_fbuf; P.row0 = 0;
+  const int lds = fused ? lf : lp;
+  HIPCHK(ctx, hipEventRecord(ev.e[1], ctx->stream));
+  if (nrows > 0) {
+    if (fused) {
+      if (lds > 65536) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_sb_fused, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      for (int64_t r0 = 0; r0 < nrows; r0 += kMaxGridRows) {
+        P.row0 = r0;
+        hipLaunchKernelGGL(k_sb_fused, dim3((unsigned)std::min(kMaxGridRows, nrows - r0)), dim3(kThreads), (size_t)lds, ctx->stream, P);
+        HIPCHK(ctx, hipGetLastError());
+      }
+    } else {
+      if (lds > 65536) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_sb_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      for (int64_t r0 = 0; r0 < nrows; r0 += kMaxGridRows) {
+        P.row0 = r0;
+        hipLaunchKernelGGL(k_sb_prepare, dim3((unsigned)std::min(kMaxGridRows, nrows - r0)), dim3(kThreads), (size_t)lds, ctx->stream, P);
+        HIPCHK(ctx, hipGetLastError());
+      }
+      if (want_over) {
+        void* b[1] = {d_fbuf};
+        if (g_rocfft.execute(plan.p, b, nullptr, plan.i) != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
+        const int64_t blocks = std::min<int64_t>((int64_t)over_n / kThreads + 1, (int64_t)std::max(ctx->cu_count, 1) * 16);
+        hipLaunchKernelGGL(k_sb_finish, dim3((unsigned)blocks), dim3(kThreads), 0, ctx->stream, P, nlines);
+        HIPCHK(ctx, hipGetLastError());
+      }
+    }
+  }
+  HIPCHK(ctx, hipEventRecord(ev.e[2], ctx->stream));
+  if (nlines > 0) {
+    if (w_over) HIPCHK(ctx, hipMemcpyAsync(over, d_over, over_n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (w_opow) HIPCHK(ctx, hipMemcpyAsync(over_pow, d_opow, over_n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (w_res) HIPCHK(ctx, hipMemcpyAsync(res, d_res, res_n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (w_rpow) HIPCHK(ctx, hipMemcpyAsync(res_pow, d_rpow, res_n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(ctx, hipEventRecord(ev.e[3], ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats) {
+    float ms = 0.0f, kms = 0.0f;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, ev.e[0], ev.e[3]));
+    HIPCHK(ctx, hipEventElapsedTime(&kms, ev.e[1], ev.e[2]));
+    stats->device_ms = ms;
+    stats->kernel_ms = kms;
+    stats->rows = (int64_t)ncubes * nrows;
+    stats->route = fused ? PRISIM_SUBBAND_FUSED : PRISIM_SUBBAND_ROCFFT;
+    stats->lds_bytes = lds;
+  }
+  return PRISIM_OK;
+  });
+}
+
+}  // extern "C"

@@ -11,8 +11,12 @@ prisim_amd/csrc_clean/clean.hip): one wave64 per (baseline, snapshot) row CLEANs
 padded inverse transform to lags and the forward transforms of the clean components and residuals; DelayPowerSpectrum then forms the
 dps['cc_*'] spectra (:3996-4002).  Departures from the reference are listed in each docstring.
 
-Not here (out of scope): sub-band transforms (they need astroutils' DSP windows), closure-phase spectra, FITS
-persistence.
+Sub-band delay spectra: ``DelaySpectrum.subband_delay_transform`` (:1842-2250) windows the band around one or more centre frequencies and
+transforms every window of every (baseline, snapshot) row in one device call (include/prisim_subband.h, prisim_amd/csrc_subband/);
+the astroutils functions it calls are read once in prisim_amd/dsp_readings.py.  ``compute_power_spectrum`` fills the sub-band power
+spectra (:4004-4063).
+
+Not here (out of scope): subband_delay_transform_allruns, closure-phase spectra, FITS persistence.
 
 Cosmology.  The reference takes ``astropy.cosmology.Planck15.clone(H0=100)`` (:34-35); astropy is not in this image, so ``cosmo100`` here
 is this module's own flat LambdaCDM with Planck15's Om0 = 0.3075, Tcmb0 = 2.7255 K, Neff = 3.046 (photons + massless neutrinos in the
@@ -20,12 +24,12 @@ radiation term; Planck15's single 0.06 eV neutrino is not modelled: E(z) differs
 Any object with astropy's interface (``H0.value``, ``efunc(z)``, ``comoving_distance(z).to('Mpc').value``,
 ``comoving_transverse_distance(z)``) is accepted in its place.
 """
-import warnings
 
 import numpy as NP
 import scipy.constants as FCNST
 
 from . import _abi
+from . import dsp_readings as DSP
 from . import geometry as GEOM
 from . import primary_beams as PB
 
@@ -294,7 +298,7 @@ def complex1dClean(inp, kernel, cbox=None, gain=0.1, maxiter=10000, threshold=5e
 class DelaySpectrum(object):
     """Delay spectra of an InterferometerArray's visibilities (prisim/delay_spectrum.py:493-1342, the argument path of __init__ and
     delay_transform()).  Attributes as in the reference: ia, f, df, n_acc, bp, bp_wts, pad, lags, lag_kernel, skyvis_lag, vis_lag,
-    vis_noise_lag, horizon_delay_limits; the CLEAN / sub-band attributes exist and stay None / empty."""
+    vis_noise_lag, horizon_delay_limits; the CLEAN attributes after delayClean(), the sub-band ones after subband_delay_transform()."""
 
     def __init__(self, interferometer_array=None, init_file=None):
         if init_file is not None:
@@ -687,6 +691,230 @@ class DelaySpectrum(object):
         if verbose:
             print('delayClean() completed: {0} rows, {1} iterations'.format(self._clean_stats['rows'], self._clean_stats['sum_iter']))
 
+    def subband_delay_transform(self, bw_eff, freq_center=None, shape=None, fftpow=None, pad=None, bpcorrect=False, action=None,
+                                verbose=True):
+        """Delay spectra of frequency sub-bands on the GPU (:1842-2250, prisim_subband_transform).  For key 'sim' the cubes skyvis_freq,
+        vis_freq and vis_noise_freq, for key 'cc' (only after delayClean) cc_{skyvis,vis}{,_res,_net}_freq[:, :nchan, :], times self.bp
+        times every window of subband_freq_wts, zero-padded to M = nchan + int(nchan pad) and transformed, M df fftshift(ifft(.))
+        (:2196-2206).  subband_delay_spectra[key] holds freq_center, shape, freq_wts, bw_eff, npad, lags, lag_kernel, lag_corr_length and
+        the spectra, each (nbl, n_win, M, n_acc); subband_delay_spectra_resampled[key] the same FFT-resampled (DSP.downsampler, read in
+        prisim_amd/dsp_readings.py) to round(M / factor) lags, lags and lag_kernel linearly interpolated (:2220-2236).  action None,
+        'return_oversampled' or 'return_resampled'; the attributes are always updated, and only after the whole call succeeded.
+
+        Reproduced literally: windows sorted by channel while freq_center / bw_eff keep the given order; windows truncated at the band
+        edges; the resampling factor of every key uses the npad of the last key processed (:2225); 'interp' lags (ceil(M / factor)) and
+        'FFT' spectra (round(M / factor)) may differ in length; bpcorrect is recorded and has no effect (:2190 computes the factor and
+        never applies it).
+        Departures (one test each in tests/test_subband.py): the default freq_center is f[int(nchan / 2)]; on a noiseless array vis_lag /
+        vis_noise_lag (and the cc_vis_* spectra) are None; fftpow other than 1 raises NotImplementedError
+        (dsp_readings.window_fftpow); the caller's dictionaries are not modified."""
+        f, df, ia = self.f, self.df, self.ia
+        nchan = f.size
+        bw_eff, freq_center, shape, fftpow, pad = _check_subband_args(f, df, bw_eff, freq_center, shape, fftpow, pad, bpcorrect, verbose)
+        nbl, nt = ia.baselines.shape[0], self.n_acc
+        keys = [key for key in SUBBAND_KEYS if key == 'sim' or self.cc_lags is not None]
+        if nt == 0:
+            raise ValueError('no visibilities to transform: call observe() first')
+        # the inputs of every key, checked before anything is computed
+        plan = {}
+        for key in keys:
+            freq_wts = subband_freq_wts(f, df, bw_eff[key], freq_center[key], shape[key], fftpow[key])
+            npad = int(nchan * pad[key])
+            m = nchan + npad
+            if m > _abi.PRISIM_SUBBAND_MAX_LEN:
+                raise ValueError('sub-band spectra of %d lags exceed PRISIM_SUBBAND_MAX_LEN = %d' % (m, _abi.PRISIM_SUBBAND_MAX_LEN))
+            if key == 'cc':
+                names = ('skyvis', 'vis', 'skyvis_res', 'vis_res', 'skyvis_net', 'vis_net')
+                srcs = [getattr(self, 'cc_%s_freq' % name) for name in names]
+                srcs = [None if x is None else x[:, :nchan, :] for x in srcs]
+            else:
+                names = ('skyvis', 'vis', 'vis_noise')
+                srcs = [ia.skyvis_freq, ia.vis_freq, ia.vis_noise_freq]
+            plan[key] = {'freq_wts': freq_wts, 'npad': npad, 'm': m, 'names': names, 'srcs': srcs}
+        # :2225 -- the factor of every key takes the npad left over from the last key of the loop above
+        last_npad = plan[keys[-1]]['npad']
+        for key in keys:
+            p = plan[key]
+            p['factor'] = NP.min((nchan + last_npad) * df / bw_eff[key])
+            p['nres'] = DSP.fft_downsample_length(p['m'], p['factor'])
+            if p['nres'] > _abi.PRISIM_SUBBAND_MAX_LEN:
+                raise ValueError('resampled sub-band spectra of %d lags exceed PRISIM_SUBBAND_MAX_LEN = %d'
+                                 % (p['nres'], _abi.PRISIM_SUBBAND_MAX_LEN))
+        bp_layers, _, _ = self._window_factors(None)
+        bp_same = all(l.shape == bp_layers[0].shape and NP.array_equal(l, bp_layers[0]) for l in bp_layers[1:])
+        ctx = ia._ctx
+
+        result, result_resampled, stats = {}, {}, []
+        for key in keys:
+            p = plan[key]
+            m, nres, nwin = p['m'], p['nres'], p['freq_wts'].shape[0]
+            have = [i for i, x in enumerate(p['srcs']) if x is not None]
+            cubes = [NP.asarray(p['srcs'][i]) for i in have]
+            over = [NP.empty((nbl, nwin, m, nt), dtype=NP.complex128) for _ in have]
+            res = [NP.empty((nbl, nwin, nres, nt), dtype=NP.complex128) for _ in have]
+            chunk = max(1, min(nt, (1 << 30) // max(1, len(have) * nbl * nwin * (m + nres) * 16)))
+            for t0 in range(0, nt, chunk):
+                t1 = min(nt, t0 + chunk)
+                x = NP.empty((len(have), t1 - t0, nbl, nchan), dtype=NP.complex128)
+                for c, cube in enumerate(cubes):
+                    x[c] = NP.transpose(cube[:, :, t0:t1], (2, 0, 1))
+                if bp_same:
+                    bp = bp_layers[0]
+                else:
+                    bp = NP.concatenate([NP.broadcast_to(bp_layers[t], (nbl, nchan)) for t in range(t0, t1)], axis=0)
+                out = ctx.subband_transform(x, bp, p['freq_wts'], m, df, nres=nres, want=('over', 'res'))
+                stats.append(out['stats'])
+                for c in range(len(have)):
+                    over[c][..., t0:t1] = NP.transpose(out['over'][c], (1, 2, 3, 0))
+                    res[c][..., t0:t1] = NP.transpose(out['res'][c], (1, 2, 3, 0))
+            # the lag kernel: one transform per row of each distinct bandpass layer, gathered to (nbl, n_win, M, n_acc)
+            distinct, kidx = [], NP.empty((nt, nbl), dtype=NP.int64)
+            for t, l in enumerate(bp_layers[:nt]):
+                hit = next((i for i, d in enumerate(distinct) if d.shape == l.shape and NP.array_equal(d, l)), None)
+                if hit is None:
+                    hit = len(distinct)
+                    distinct.append(l)
+                base = sum(d.shape[0] for d in distinct[:hit])
+                kidx[t] = base + (NP.arange(nbl) if l.shape[0] == nbl else 0)
+            kern_rows = NP.concatenate(distinct, axis=0).astype(NP.complex128)
+            k = ctx.subband_transform(kern_rows.reshape(1, 1, -1, nchan), NP.ones((1, nchan)), p['freq_wts'], m, df, want=('over',))
+            k = k['over'][0, 0]                                                              # (distinct rows, n_win, M)
+            lag_kernel = NP.ascontiguousarray(NP.transpose(k[kidx], (1, 2, 3, 0)))
+            lags = DSP.spectral_axis(m, delx=df, use_real=False, shift=True)
+            r = {'freq_center': freq_center[key], 'shape': shape[key], 'freq_wts': p['freq_wts'], 'bw_eff': bw_eff[key], 'npad': p['npad'],
+                 'lags': lags, 'lag_kernel': lag_kernel, 'lag_corr_length': nchan / NP.sum(p['freq_wts'], axis=1)}
+            rr = {'freq_center': freq_center[key], 'bw_eff': bw_eff[key]}
+            rr['lags'] = DSP.downsampler(lags, p['factor'], axis=-1, method='interp', kind='linear')
+            rr['lag_kernel'] = DSP.downsampler(lag_kernel, p['factor'], axis=2, method='interp', kind='linear')
+            for i, name in enumerate(p['names']):
+                c = have.index(i) if i in have else None
+                r[name + '_lag'] = over[c] if c is not None else None
+                rr[name + '_lag'] = res[c] if c is not None else None
+            dlag = rr['lags'][1] - rr['lags'][0]
+            rr['lag_corr_length'] = (1 / bw_eff[key]) / dlag
+            if key == 'cc':
+                r['bpcorrect'] = bpcorrect
+            result[key], result_resampled[key] = r, rr
+        if verbose:
+            print('\tSub-band(s) delay transform computed')
+            print('\tDownsampled Sub-band(s) delay transform computed')
+        # commit
+        self.subband_delay_spectra = result
+        self.subband_delay_spectra_resampled = result_resampled
+        self._subband_stats = {'device_ms': sum(st['device_ms'] for st in stats), 'kernel_ms': sum(st['kernel_ms'] for st in stats),
+                               'rows': sum(st['rows'] for st in stats), 'routes': sorted(set(st['route'] for st in stats)),
+                               'calls': len(stats)}
+        if action == 'return_oversampled':
+            return result
+        if action == 'return_resampled':
+            return result_resampled
+
+
+
+SUBBAND_KEYS = ('cc', 'sim')
+
+
+def subband_freq_wts(f, df, bw_eff, freq_center, shape, fftpow):
+    """The (n_win, nchan) windows of subband_delay_transform (:2159-2177): a window of n_window = round(bw_eff / df / frac_width) channels
+    scaled by sqrt(frac_width n_window), its peak on the channel nearest each centre, truncated at the band edges; rows in channel order
+    (sortind), not in the order the centres were given."""
+    f = NP.asarray(f, dtype=NP.float64)
+    nchan = f.size
+    frac_width = DSP.window_N2width(n_window=None, shape=shape, fftpow=fftpow, area_normalize=False, power_normalize=True)
+    window_loss_factor = 1 / frac_width
+    n_window = NP.round(window_loss_factor * bw_eff / df).astype(int)
+    ind_freq_center, ind_channels, dfrequency = DSP.find_1NN(f.reshape(-1, 1), freq_center.reshape(-1, 1), distance_ULIM=0.5 * df,
+                                                             remove_oob=True)
+    sortind = NP.argsort(ind_channels)
+    ind_channels = ind_channels[sortind]
+    n_window = n_window[sortind]
+    freq_wts = NP.empty((bw_eff.size, nchan), dtype=NP.float64)
+    for i, ind_chan in enumerate(ind_channels):
+        window = NP.sqrt(frac_width * n_window[i]) * DSP.window_fftpow(n_window[i], shape=shape, fftpow=fftpow, centering=True, peak=None,
+                                                                       area_normalize=False, power_normalize=True)
+        window_chans = f[ind_chan] + df * (NP.arange(n_window[i]) - int(n_window[i] / 2))
+        ind_window_chans, ind_chans, dfreq = DSP.find_1NN(f.reshape(-1, 1), window_chans.reshape(-1, 1), distance_ULIM=0.5 * df,
+                                                          remove_oob=True)
+        sind = NP.argsort(ind_window_chans)
+        ind_window_chans = ind_window_chans[sind]
+        ind_chans = ind_chans[sind]
+        window = window[ind_window_chans]
+        window = NP.pad(window, ((ind_chans.min(), nchan - 1 - ind_chans.max())), mode='constant', constant_values=((0.0, 0.0)))
+        freq_wts[i, :] = window
+    return freq_wts
+
+
+def _check_subband_args(f, df, bw_eff, freq_center, shape, fftpow, pad, bpcorrect, verbose):
+    """The argument checks of :2073-2147 with the reference's exception types, on copies of the caller's dictionaries (the reference
+    writes its normalised values back into them).  Returns the normalised (bw_eff, freq_center, shape, fftpow, pad)."""
+    if not isinstance(bw_eff, dict):
+        raise TypeError('Effective bandwidth must be specified as a dictionary')
+    bw_eff = dict(bw_eff)
+    for key in SUBBAND_KEYS:
+        if key in bw_eff:
+            if not isinstance(bw_eff[key], (int, float, list, NP.ndarray)):
+                raise TypeError('Value of effective bandwidth must be a scalar, list or numpy array')
+            bw_eff[key] = NP.asarray(bw_eff[key]).reshape(-1)
+            if NP.any(bw_eff[key] <= 0.0):
+                raise ValueError('All values in effective bandwidth must be strictly positive')
+    if freq_center is None:
+        # the reference's self.f[self.f.size/2] is a float index under `from __future__ import division` (departure: int(nchan / 2))
+        freq_center = {key: NP.asarray(f[int(f.size / 2)]).reshape(-1) for key in SUBBAND_KEYS}
+    elif isinstance(freq_center, dict):
+        freq_center = dict(freq_center)
+        for key in SUBBAND_KEYS:
+            if isinstance(freq_center[key], (int, float, list, NP.ndarray)):
+                freq_center[key] = NP.asarray(freq_center[key]).reshape(-1)
+                if NP.any((freq_center[key] <= f.min()) | (freq_center[key] >= f.max())):
+                    raise ValueError('Value(s) of frequency center(s) must lie strictly inside the observing band')
+            else:
+                raise TypeError('Values(s) of frequency center must be scalar, list or numpy array')
+    else:
+        raise TypeError('Input frequency center must be specified as a dictionary')
+    for key in SUBBAND_KEYS:
+        if (bw_eff[key].size == 1) and (freq_center[key].size > 1):
+            bw_eff[key] = NP.repeat(bw_eff[key], freq_center[key].size)
+        elif (bw_eff[key].size > 1) and (freq_center[key].size == 1):
+            freq_center[key] = NP.repeat(freq_center[key], bw_eff[key].size)
+        elif bw_eff[key].size != freq_center[key].size:
+            raise ValueError('Effective bandwidth(s) and frequency center(s) must have same number of elements')
+    if shape is not None:
+        if not isinstance(shape, dict):
+            raise TypeError('Window shape must be specified as a dictionary')
+        for key in SUBBAND_KEYS:
+            if not isinstance(shape[key], str):
+                raise TypeError('Window shape must be a string')
+            if shape[key] not in ['rect', 'bhw', 'bnw', 'RECT', 'BHW', 'BNW']:
+                raise ValueError('Invalid value for window shape specified.')
+    else:
+        shape = {key: 'rect' for key in SUBBAND_KEYS}
+    if fftpow is None:
+        fftpow = {key: 1.0 for key in SUBBAND_KEYS}
+    else:
+        if not isinstance(fftpow, dict):
+            raise TypeError('Power to raise FFT of window by must be specified as a dictionary')
+        for key in SUBBAND_KEYS:
+            if not isinstance(fftpow[key], (int, float)):
+                raise TypeError('Power to raise window FFT by must be a scalar value.')
+            if fftpow[key] < 0.0:
+                raise ValueError('Power for raising FFT of window by must be positive.')
+    if pad is None:
+        pad = {key: 1.0 for key in SUBBAND_KEYS}
+    else:
+        if not isinstance(pad, dict):
+            raise TypeError('Padding for delay transform must be specified as a dictionary')
+        pad = dict(pad)
+        for key in SUBBAND_KEYS:
+            if not isinstance(pad[key], (int, float)):
+                raise TypeError('pad fraction must be a scalar value.')
+            if pad[key] < 0.0:
+                pad[key] = 0.0
+                if verbose:
+                    print('\tPad fraction found to be negative. Resetting to 0.0 (no padding will be applied).')
+    if not isinstance(bpcorrect, bool):
+        raise TypeError('Input keyword bpcorrect must be of boolean type')
+    return bw_eff, freq_center, shape, fftpow, pad
+
 
 class _Deferred(object):
     def __init__(self, fn):
@@ -820,7 +1048,10 @@ class DelayPowerSpectrum(object):
         """dps['skyvis' | 'vis' | 'noise'] = abs(lag spectrum)**2 * jacobian1 * jacobian2 * Jy2K**2 (:3982-3995), and after
         DelaySpectrum.delayClean the six dps['cc_*'] of the clean components, residuals and their sums (:3996-4002).  When the delay
         spectra are resident on the device the product is formed there (prisim_hip_delay_transform_device with power_scale = the factor)
-        and fetched when dps['skyvis'] is read."""
+        and fetched when dps['skyvis'] is read.  After DelaySpectrum.subband_delay_transform it fills subband_delay_power_spectra[key]
+        (z, dz, kprll, kperp, horizon_kprll_limits, rz_los, rz_transverse, drz_los, jacobian1 = 1 / beam3Dvol(freq_wts), jacobian2,
+        Jy2K, factor per window, and abs(spectrum)**2 * factor of every product) and subband_delay_power_spectra_resampled[key] (kprll,
+        kperp, horizon_kprll_limits, the resampled products times the same factor), as :4004-4063."""
         ds = self.ds
         factor = self.jacobian1 * self.jacobian2 * self.Jy2K ** 2
         dps = _LazyDict()
@@ -846,5 +1077,44 @@ class DelayPowerSpectrum(object):
                 if lag is not None:
                     dps[key] = NP.abs(lag) ** 2 * factor
         self.dps = dps
-        if ds.subband_delay_spectra or ds.subband_delay_spectra_resampled:
-            warnings.warn('sub-band delay power spectra are not on the accelerated path')
+        if ds.subband_delay_spectra:                                                     # :4004-4040
+            for key in ds.subband_delay_spectra:
+                sb = ds.subband_delay_spectra[key]
+                out = self.subband_delay_power_spectra[key] = {}
+                wl = FCNST.c / sb['freq_center']
+                out['z'] = REST_FREQ_HI / sb['freq_center'] - 1
+                out['dz'] = REST_FREQ_HI / sb['freq_center'] ** 2 * sb['bw_eff']
+                out['kprll'], out['kperp'], out['horizon_kprll_limits'] = self._subband_k(sb['lags'], out['z'])
+                out['rz_los'] = self.cosmo.comoving_distance(out['z']).to('Mpc').value
+                out['rz_transverse'] = self.comoving_transverse_distance(out['z'], action='return')
+                out['drz_los'] = self.comoving_los_depth(sb['bw_eff'], out['z'], action='return')
+                omega_bw = self.beam3Dvol(freq_wts=sb['freq_wts'])
+                out['jacobian1'] = 1 / omega_bw
+                out['jacobian2'] = out['rz_los'] ** 2 * out['drz_los'] / sb['bw_eff']
+                out['Jy2K'] = wl ** 2 * JY / (2 * FCNST.k)
+                out['factor'] = out['jacobian1'] * out['jacobian2'] * out['Jy2K'] ** 2
+                self._subband_power(sb, out, out['factor'].reshape(1, -1, 1, 1))
+        if ds.subband_delay_spectra_resampled:                                           # :4042-4063
+            for key in ds.subband_delay_spectra_resampled:
+                sb = ds.subband_delay_spectra_resampled[key]
+                out = self.subband_delay_power_spectra_resampled[key] = {}
+                out['kprll'], out['kperp'], out['horizon_kprll_limits'] = self._subband_k(sb['lags'], self.subband_delay_power_spectra[key]['z'])
+                self._subband_power(sb, out, self.subband_delay_power_spectra[key]['factor'].reshape(1, -1, 1, 1))
+
+    def _subband_k(self, lags, zs):
+        """kprll (n_win, nlags), kperp (n_win, nbl) and horizon_kprll_limits (n_acc, n_win, nbl, 2) at the redshifts zs (:4011-4018)."""
+        kprll = NP.empty((zs.size, lags.size))
+        kperp = NP.empty((zs.size, self.bl_length.size))
+        horizon_kprll_limits = NP.empty((self.ds.n_acc, zs.size, self.bl_length.size, 2))
+        for zind, z in enumerate(zs):
+            kprll[zind, :] = self.k_parallel(lags, z, action='return')
+            kperp[zind, :] = self.k_perp(self.bl_length, z, action='return')
+            horizon_kprll_limits[:, zind, :, :] = self.k_parallel(self.ds.horizon_delay_limits, z, action='return')
+        return kprll, kperp, horizon_kprll_limits
+
+    @staticmethod
+    def _subband_power(sb, out, conversion_factor):
+        """abs(spectrum)**2 * factor of every product the sub-band dictionary holds (:4031-4040); None where the spectrum is None."""
+        for name in ('skyvis_lag', 'vis_lag', 'vis_noise_lag', 'skyvis_res_lag', 'vis_res_lag', 'skyvis_net_lag', 'vis_net_lag'):
+            if name in sb:
+                out[name] = None if sb[name] is None else NP.abs(sb[name]) ** 2 * conversion_factor
