@@ -31,6 +31,7 @@ import scipy.constants as FCNST
 from . import _abi
 from . import dsp_readings as DSP
 from . import geometry as GEOM
+from . import interferometry as RI
 from . import primary_beams as PB
 
 REST_FREQ_HI = 1420405751.77      # Hz (astroutils.constants.rest_freq_HI, used at :3642, 3707)
@@ -303,8 +304,7 @@ class DelaySpectrum(object):
     def __init__(self, interferometer_array=None, init_file=None):
         if init_file is not None:
             raise NotImplementedError('DelaySpectrum(init_file=...): FITS persistence is out of scope (SURVEY.md 2.1 row 17)')
-        from .interferometry import InterferometerArray
-        if not isinstance(interferometer_array, InterferometerArray):
+        if not isinstance(interferometer_array, RI.InterferometerArray):
             raise TypeError('Input interferometer_array must be an instance of class InterferometerArray')
         self.ia = interferometer_array
         self.f = interferometer_array.channels
@@ -340,23 +340,11 @@ class DelaySpectrum(object):
     def bp_wts(self, value):
         self._bp_wts_override = value
 
-    def _refresh_resident(self):
-        """The stored delay spectra live in the context's single resident buffer and are fetched when read.  Any later transform on that
-        context (another window or pad without action='store', InterferometerArray.delay_transform, a power-spectrum fetch) overwrites the
-        buffer: the transform is then simply run again (milliseconds) before the read -- a stored result never changes, as in the
-        reference, whose store is a host copy."""
-        ctx = self.ia._ctx
-        if getattr(ctx, '_dt_generation', None) != getattr(self, '_lag_gen', None):
-            nt, w0, pad = self._resident_args
-            ctx.delay_transform_device(nt, bpwts=w0, pad=pad, want_lag=True)
-            self._lag_gen = getattr(ctx, '_dt_generation', None)
-
+    # skyvis_lag: a stored result the transform left resident on the device (an interferometry._ResidentLags) is fetched when read
     @property
     def skyvis_lag(self):
         if self._lag_resident is not None and self._skyvis_lag is None:
-            nt, _ = self._lag_resident
-            self._refresh_resident()
-            self._skyvis_lag = NP.transpose(self.ia._ctx.get_lags(0, nt), (1, 2, 0))
+            self._skyvis_lag = self._lag_resident.spectra()
         return self._skyvis_lag
 
     @skyvis_lag.setter
@@ -444,27 +432,6 @@ class DelaySpectrum(object):
         n = min(len(bp_layers), len(w_layers))
         return [NP.asarray(l) for l in bp_layers[:n]], [NP.asarray(l) for l in w_layers[:n]], report
 
-    def _window_source(self, freq_wts):
-        """Per-snapshot windows bp * freq_wts in the most compact form available: (layers, same) with layers[t] of shape
-        (1 | nbl, nchan) and same = every snapshot carries the same window; plus the freq_wts to report."""
-        bp_layers, w_layers, report = self._window_factors(freq_wts)
-        layers = [bp_layers[t] * w_layers[t] for t in range(len(bp_layers))]
-        same = all(l.shape == layers[0].shape and NP.array_equal(l, layers[0]) for l in layers[1:])
-        return layers, same, report
-
-    def _transform_full(self, cube_t, window_t, pad):
-        """One snapshot without the final decimation: the zero-padded product is uploaded as the single snapshot of a temporary context
-        whose channel grid is the padded one, and transformed there with pad = 0 -- same FFT length, same (npad + N) df scale (:1316-1321)."""
-        nbl, nchan = cube_t.shape
-        npad = int(nchan * pad)
-        x = NP.zeros((nbl, nchan + npad), dtype=NP.complex128)
-        x[:, :nchan] = cube_t * window_t
-        grid = self.f[0] + self.df * NP.arange(nchan + npad)
-        with _abi.Context(getattr(self.ia._ctx, 'device', 0)) as tmp:
-            tmp.set_array(NP.asarray(self.ia.baselines, dtype=NP.float64), grid, nt_max=1)
-            out, _, _ = tmp.delay_transform_host(x, None, 0.0)
-        return out
-
     def delay_transform(self, pad=1.0, freq_wts=None, downsample=True, action=None, verbose=True):
         """IFFT of visibilities * bandpass * window along frequency on the GPU (:1224-1342): skyvis_lag, vis_lag, vis_noise_lag (for
         the cubes that exist), lag_kernel, lags, freq_wts, pad.  With the visibility cube resident in HBM (InterferometerArray.reserve)
@@ -479,72 +446,20 @@ class DelaySpectrum(object):
                 print('\tPad fraction found to be negative. Resetting to 0.0 (no padding will be applied).')
         if freq_wts is not None:
             freq_wts = NP.asarray(freq_wts)
-        layers, same, report = self._window_source(freq_wts)
+        bp_layers, w_layers, report = self._window_factors(freq_wts)
         if verbose:
             print('\tFrequency window weights assigned.')
         if not isinstance(downsample, bool):
             raise TypeError('Input downsample must be of boolean type')
-        ia = self.ia
-        nbl, nchan, nt = ia.baselines.shape[0], self.f.size, self.n_acc
-        if nt == 0:
+        nchan = self.f.size
+        if self.n_acc == 0:
             raise ValueError('no visibilities to transform: call observe() first')
-        ctx = ia._ctx
         result = {'freq_wts': report if report is not None else self.bp_wts, 'pad': pad}
         nfft = int(nchan * (1 + pad))
         result['lags'] = NP.fft.fftshift(NP.fft.fftfreq(nfft, self.df))                 # :1303
         decimate = downsample or pad == 0.0
-
-        def window(t):
-            return NP.broadcast_to(layers[t if (not same and t < len(layers)) else 0], (nbl, nchan))
-
-        def transform(cube):
-            outs = []
-            for t in range(cube.shape[2]):
-                if decimate:
-                    out, _, _ = ctx.delay_transform_host(cube[:, :, t], window(t), pad)
-                else:
-                    out = self._transform_full(cube[:, :, t], window(t), pad)
-                outs.append(out)
-            return NP.stack(outs, axis=2)
-
-        # the sky visibilities: on the device where they already are, when they are
-        if hasattr(ia, '_cube') and bool(ia._cube) and ia._reserved >= nt and not getattr(ia, '_device_in_step', False) \
-                and not any(type(sn).__name__ == '_DeviceSlot' for sn in ia._cube):
-            ia._upload_cube()
-        resident = bool(getattr(ia, '_cube', None)) and ia._reserved >= nt and getattr(ia, '_device_in_step', False)
-        lag_resident, skyvis_lag, resident_args = None, None, None
-        if resident and same and decimate:
-            w0 = layers[0][0] if layers[0].shape[0] == 1 else layers[0]
-            _, nout = ctx.delay_transform_device(nt, bpwts=w0, pad=pad, want_lag=True)
-            lag_resident = (nt, nout)
-            resident_args = (nt, NP.array(w0, dtype=NP.float64), pad)
-        else:
-            saved0 = ctx.get_vis(slot=0) if resident else None                          # the host-side transforms run through slot 0
-            skyvis_lag = transform(NP.asarray(ia.skyvis_freq, dtype=NP.complex128))
-            if saved0 is not None:
-                ctx.set_vis(saved0, slot=0)
-
-        def through_slot0(fn):
-            saved = ctx.get_vis(slot=0) if resident else None
-            try:
-                return fn()
-            finally:
-                if saved is not None:
-                    ctx.set_vis(saved, slot=0)
-
-        # (the reference multiplies vis_freq / vis_noise_freq unconditionally and fails on a noiseless object, SURVEY Q20: here the
-        # cubes that exist are transformed)
-        vis_lag = vis_noise_lag = None
-        if ia.vis_freq is not None:
-            vis_lag = through_slot0(lambda: transform(NP.asarray(ia.vis_freq, dtype=NP.complex128)))
-        if ia.vis_noise_freq is not None:
-            vis_noise_lag = through_slot0(lambda: transform(NP.asarray(ia.vis_noise_freq, dtype=NP.complex128)))
-
-        def make_kernel():
-            if same:
-                kern = through_slot0(lambda: transform(NP.ones((nbl, nchan, 1), dtype=NP.complex128)))
-                return NP.repeat(kern, nt, axis=2)
-            return through_slot0(lambda: transform(NP.ones((nbl, nchan, nt), dtype=NP.complex128)))
+        sky, _, vis_lag, vis_noise_lag, make_kernel = self.ia._transform_cubes([b * w for b, w in zip(bp_layers, w_layers)], pad, decimate)
+        resident = isinstance(sky, RI._ResidentLags)
 
         if decimate and pad > 0.0:
             result['lags'] = result['lags'][NP.arange(0, nfft, 1 + pad).astype(int)] if float(1 + pad).is_integer() else \
@@ -559,16 +474,14 @@ class DelaySpectrum(object):
             self.lags = result['lags']
             if report is not None:
                 self._bp_wts_override = report
-            self._skyvis_lag, self._lag_resident = skyvis_lag, lag_resident
-            if lag_resident is not None:               # (only a STORED result keeps a claim on the resident buffer)
-                self._resident_args, self._lag_gen = resident_args, getattr(ctx, '_dt_generation', None)
+            self._skyvis_lag, self._lag_resident = (None, sky) if resident else (sky, None)   # (only a STORED result keeps resident spectra)
             self.vis_lag = vis_lag
             self.vis_noise_lag = vis_noise_lag
             self._lag_kernel, self._lag_kernel_maker = None, make_kernel
-        if lag_resident is not None:
-            result['skyvis_lag'] = NP.transpose(ctx.get_lags(0, nt), (1, 2, 0)) if action != 'store' else _Deferred(lambda: self.skyvis_lag)
+        if resident:
+            result['skyvis_lag'] = sky.spectra() if action != 'store' else _Deferred(lambda: self.skyvis_lag)
         else:
-            result['skyvis_lag'] = skyvis_lag
+            result['skyvis_lag'] = sky
         result['vis_lag'] = vis_lag
         result['vis_noise_lag'] = vis_noise_lag
         result['lag_kernel'] = _Deferred(make_kernel) if action == 'store' else make_kernel()
@@ -633,17 +546,7 @@ class DelaySpectrum(object):
         stats = []
         for t0 in range(0, nt, chunk):
             t1 = min(nt, t0 + chunk)
-            # the distinct windows of the chunk and every row's index into them
-            kern_rows, kidx = [], NP.empty((t1 - t0, nbl), dtype=NP.int32)
-            for t in range(t0, t1):
-                w = wins[t]
-                hit = next((i for i, (tt, kw) in enumerate(kern_rows) if kw.shape == w.shape and NP.array_equal(kw, w)), None)
-                if hit is None:
-                    hit = len(kern_rows)
-                    kern_rows.append((t, w))
-                base = sum(kw.shape[0] for _, kw in kern_rows[:hit])
-                kidx[t - t0] = base + (NP.arange(nbl) if w.shape[0] == nbl else 0)
-            kwin = NP.concatenate([kw for _, kw in kern_rows], axis=0).astype(NP.complex128)
+            kwin, kidx = RI._distinct_layers(wins[t0:t1], nbl)                         # the distinct windows of the chunk, rows' indices
             win = NP.empty((ncubes, t1 - t0, nbl, nchan), dtype=NP.complex128)
             for c, cube in enumerate(cubes):
                 for t in range(t0, t1):
@@ -741,7 +644,9 @@ class DelaySpectrum(object):
                 raise ValueError('resampled sub-band spectra of %d lags exceed PRISIM_SUBBAND_MAX_LEN = %d'
                                  % (p['nres'], _abi.PRISIM_SUBBAND_MAX_LEN))
         bp_layers, _, _ = self._window_factors(None)
-        bp_same = all(l.shape == bp_layers[0].shape and NP.array_equal(l, bp_layers[0]) for l in bp_layers[1:])
+        bp_same = RI._all_same(bp_layers)
+        # the lag kernel: one transform per row of each distinct bandpass layer, gathered to (nbl, n_win, M, n_acc)
+        kern_rows, kidx = RI._distinct_layers(bp_layers[:nt], nbl)
         ctx = ia._ctx
 
         result, result_resampled, stats = {}, {}, []
@@ -767,16 +672,6 @@ class DelaySpectrum(object):
                 for c in range(len(have)):
                     over[c][..., t0:t1] = NP.transpose(out['over'][c], (1, 2, 3, 0))
                     res[c][..., t0:t1] = NP.transpose(out['res'][c], (1, 2, 3, 0))
-            # the lag kernel: one transform per row of each distinct bandpass layer, gathered to (nbl, n_win, M, n_acc)
-            distinct, kidx = [], NP.empty((nt, nbl), dtype=NP.int64)
-            for t, l in enumerate(bp_layers[:nt]):
-                hit = next((i for i, d in enumerate(distinct) if d.shape == l.shape and NP.array_equal(d, l)), None)
-                if hit is None:
-                    hit = len(distinct)
-                    distinct.append(l)
-                base = sum(d.shape[0] for d in distinct[:hit])
-                kidx[t] = base + (NP.arange(nbl) if l.shape[0] == nbl else 0)
-            kern_rows = NP.concatenate(distinct, axis=0).astype(NP.complex128)
             k = ctx.subband_transform(kern_rows.reshape(1, 1, -1, nchan), NP.ones((1, nchan)), p['freq_wts'], m, df, want=('over',))
             k = k['over'][0, 0]                                                              # (distinct rows, n_win, M)
             lag_kernel = NP.ascontiguousarray(NP.transpose(k[kidx], (1, 2, 3, 0)))
@@ -1056,15 +951,8 @@ class DelayPowerSpectrum(object):
         factor = self.jacobian1 * self.jacobian2 * self.Jy2K ** 2
         dps = _LazyDict()
         if ds._lag_resident is not None and ds._skyvis_lag is None:
-            nt, w0, pad = ds._resident_args
-            ctx = ds.ia._ctx
-            k = self.power_scale()
-
-            def fetch():
-                ctx.delay_transform_device(nt, bpwts=w0, pad=pad, want_lag=True, want_power=True, power_scale=k)
-                ds._lag_gen = getattr(ctx, '_dt_generation', None)       # (the same spectra again, with their power beside them)
-                return NP.transpose(ctx.get_delay_power(0, nt), (1, 2, 0))
-            dps['skyvis'] = _Deferred(fetch)
+            resident, k = ds._lag_resident, self.power_scale()
+            dps['skyvis'] = _Deferred(lambda: resident.power(k))
         elif ds.skyvis_lag is not None:
             dps['skyvis'] = NP.abs(ds.skyvis_lag) ** 2 * factor
         if ds.vis_lag is not None:

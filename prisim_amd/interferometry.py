@@ -27,6 +27,7 @@ Differences kept on purpose:
       ``frame_provider`` and reproduces the reference's frame exactly.
 Out of scope here: gain tables, FITS persistence, uvfits / uvh5.
 """
+import contextlib
 import os
 import warnings
 import weakref
@@ -52,6 +53,72 @@ class _DeviceSlot(object):
     def __init__(self, slot, dtype, staged=False):
         self.slot, self.dtype = slot, NP.dtype(dtype)
         self.staged = staged           # an asynchronous download into the pinned host cube is in flight or done (reserve(host_staging=True))
+
+
+class _ResidentLags(object):
+    """Delay spectra of slots [0, nt) that one delay_transform_device call left in the context's single resident buffer, fetched when
+    read (config 5: 120 GB that a sharded run exchanges GPU -> GPU instead).  Any later transform on that context (another window or pad,
+    the other class's delay_transform, a power-spectrum fetch) overwrites the buffer: the transform is then simply run again
+    (milliseconds) before the read -- a stored result never changes, as in the reference, whose store is a host copy."""
+    __slots__ = ('ctx', 'nt', 'nout', 'window', 'pad', 'lags', 'generation')
+
+    def __init__(self, ctx, nt, window, pad):
+        self.ctx, self.nt, self.window, self.pad = ctx, nt, NP.array(window, dtype=NP.float64), pad
+        self.lags, self.nout = ctx.delay_transform_device(nt, bpwts=self.window, pad=pad, want_lag=True)
+        self.generation = getattr(ctx, '_dt_generation', None)
+
+    def _refresh(self):
+        if getattr(self.ctx, '_dt_generation', None) != self.generation:
+            self.ctx.delay_transform_device(self.nt, bpwts=self.window, pad=self.pad, want_lag=True)
+            self.generation = getattr(self.ctx, '_dt_generation', None)
+
+    def spectra(self, rows=None):
+        """(nbl | len(rows), nout, nt) lag spectra."""
+        self._refresh()
+        lags = self.ctx.get_lags(0, self.nt) if rows is None else self.ctx.get_lags(0, self.nt, rows=rows)
+        return NP.transpose(lags, (1, 2, 0))
+
+    def power(self, power_scale):
+        """(nbl, nout, nt) abs(spectra)**2 * power_scale: the same spectra transformed again, with their power beside them."""
+        self.ctx.delay_transform_device(self.nt, bpwts=self.window, pad=self.pad, want_lag=True, want_power=True, power_scale=power_scale)
+        self.generation = getattr(self.ctx, '_dt_generation', None)
+        return NP.transpose(self.ctx.get_delay_power(0, self.nt), (1, 2, 0))
+
+    def allgather(self, nranks, download=True):
+        """RCCL all-gather of the spectra, GPU -> GPU; the gathered [t][rank][b][lag] | [t][bl][lag] cube, or None with download=False."""
+        self._refresh()
+        self.ctx.allgather_lags(self.nt)
+        return self.ctx.get_gathered(self.nt, nranks, row=self.nout) if download else None
+
+
+@contextlib.contextmanager
+def _through_slot0(ctx, keep):
+    """Host-side transforms run through device slot 0; with keep (the slot holds a resident snapshot) it is saved and put back."""
+    saved = ctx.get_vis(slot=0) if keep else None
+    try:
+        yield
+    finally:
+        if saved is not None:
+            ctx.set_vis(saved, slot=0)
+
+
+def _all_same(layers):
+    """Whether every (1 | nbl, nchan) layer of a list equals the first, in shape and values."""
+    return all(l.shape == layers[0].shape and NP.array_equal(l, layers[0]) for l in layers[1:])
+
+
+def _distinct_layers(layers, nbl):
+    """The distinct (1 | nbl, nchan) layers of a list concatenated along the rows (complex128), and each (layer, baseline)'s row index
+    into them, (len(layers), nbl) int64."""
+    distinct, idx = [], NP.empty((len(layers), nbl), dtype=NP.int64)
+    for t, l in enumerate(layers):
+        hit = next((i for i, d in enumerate(distinct) if d.shape == l.shape and NP.array_equal(d, l)), None)
+        if hit is None:
+            hit = len(distinct)
+            distinct.append(l)
+        base = sum(d.shape[0] for d in distinct[:hit])
+        idx[t] = base + (NP.arange(nbl) if l.shape[0] == nbl else 0)
+    return NP.concatenate(distinct, axis=0).astype(NP.complex128), idx
 
 
 class _LayerStack(object):
@@ -698,12 +765,8 @@ class InterferometerArray(object):
         if not getattr(self, '_comm_ready', False):
             raise RuntimeError('allgather() must be called first (it sets up the communicator)')
         if getattr(self, '_lag_resident', None) is not None:
-            nt, nout = self._lag_resident
-            self._refresh_resident_lags()
-            self._ctx.allgather_lags(nt)
-            if not download:
-                return None
-            return self._gathered_cube(self._ctx.get_gathered(nt, nranks, row=nout), nranks, nout)             # [t][rank][b][lag] | [t][bl][lag]
+            g = self._lag_resident.allgather(nranks, download)
+            return None if g is None else self._gathered_cube(g, nranks, self._lag_resident.nout)
         if self.skyvis_lag is None:
             raise RuntimeError('delay_transform() must be called first')
         if self.skyvis_lag.shape != (self.baselines.shape[0], self.channels.size, self.n_acc):
@@ -1403,28 +1466,20 @@ class InterferometerArray(object):
         self._dense[name] = layer if cur.ndim == 2 else NP.dstack((cur, layer))
 
     def _window_layers(self):
-        """bp * bp_wts per snapshot in compact form: a list of (1 | nbl, nchan) arrays, or None when only dense arrays exist."""
+        """bp * bp_wts (:8116) per snapshot as a list of (1 | nbl, nchan) arrays: compact layers while both attributes are layer stacks,
+        else the snapshots of the dense product."""
         a, b = self._stacks.get('bp'), self._stacks.get('bp_wts')
-        if a is None or b is None or len(a.layers) != len(b.layers) or not a.layers:
-            return None
-        return [x * y for x, y in zip(a.layers, b.layers)]
+        if a is not None and b is not None and len(a.layers) == len(b.layers) and a.layers:
+            return [x * y for x, y in zip(a.layers, b.layers)]
+        wall = (self.bp * self.bp_wts).reshape(self.baselines.shape[0], self.channels.size, -1)
+        return [wall[:, :, t] for t in range(wall.shape[2])]
 
     # skyvis_lag / lag_kernel: computed on the GPU by delay_transform(); when the visibility cube is resident on the device the
-    # spectra stay there too and are fetched on first read (config 5: 120 GB that a sharded run exchanges GPU -> GPU instead)
-    def _refresh_resident_lags(self):
-        """The context holds ONE resident spectrum buffer; when another transform (a DelaySpectrum of this array, a power-spectrum
-        fetch) has overwritten it since delay_transform(), the transform is run again before the spectra are read or exchanged."""
-        if getattr(self._ctx, '_dt_generation', None) != getattr(self, '_lag_gen', None) and getattr(self, '_lag_args', None) is not None:
-            nt, w, pad = self._lag_args
-            self._ctx.delay_transform_device(nt, bpwts=w, pad=pad, want_lag=True)
-            self._lag_gen = getattr(self._ctx, '_dt_generation', None)
-
+    # spectra stay there too (a _ResidentLags) and are fetched on first read
     @property
     def skyvis_lag(self):
         if getattr(self, '_lag_resident', None) is not None and getattr(self, '_skyvis_lag', None) is None:
-            nt, nout = self._lag_resident
-            self._refresh_resident_lags()
-            self._skyvis_lag = NP.transpose(self._ctx.get_lags(0, nt), (1, 2, 0))
+            self._skyvis_lag = self._lag_resident.spectra()
         return getattr(self, '_skyvis_lag', None)
 
     @skyvis_lag.setter
@@ -1435,9 +1490,7 @@ class InterferometerArray(object):
     def skyvis_lag_rows(self, rows):
         """Delay spectra (len(rows), nlag, n_acc) of selected baselines without fetching the whole cube from the device."""
         if getattr(self, '_lag_resident', None) is not None and getattr(self, '_skyvis_lag', None) is None:
-            nt, nout = self._lag_resident
-            self._refresh_resident_lags()
-            return NP.transpose(self._ctx.get_lags(0, nt, rows=rows), (1, 2, 0))
+            return self._lag_resident.spectra(rows)
         if self.skyvis_lag is None:
             raise RuntimeError('delay_transform() must be called first')
         return self.skyvis_lag[NP.asarray(rows), :, :]
@@ -2044,71 +2097,77 @@ class InterferometerArray(object):
                 self.bp_wts = freq_wts
         if not self._cube and self._skyvis_override is None:
             raise ValueError('no visibilities to transform: call observe() first')
+        sky, lags, vis_lag, vis_noise_lag, make_kernel = self._transform_cubes(self._window_layers(), pad)
+        self._skyvis_lag, self._lag_resident = (None, sky) if isinstance(sky, _ResidentLags) else (sky, None)
+        self.lags = lags
+        if vis_lag is not None:
+            self.vis_lag = vis_lag
+        if vis_noise_lag is not None:
+            self.vis_noise_lag = vis_noise_lag
+        self._lag_kernel, self._lag_kernel_maker = None, make_kernel      # formed on first read of lag_kernel
 
-        # bp * bp_wts (:8116): compact per-snapshot layers when the attributes still are layer stacks, else the dense product
-        wlayers = self._window_layers()
-        if wlayers is not None:
-            same_wts = all(l.shape == wlayers[0].shape and NP.array_equal(l, wlayers[0]) for l in wlayers[1:])
-            def window(t):
-                return NP.broadcast_to(wlayers[t if t < len(wlayers) else 0], (nbl, nchan))
-            w_first = wlayers[0][0] if wlayers[0].shape[0] == 1 else wlayers[0]      # (nchan,): one window for every baseline
-        else:
-            wall = (self.bp * self.bp_wts).reshape(nbl, nchan, -1)
-            same_wts = wall.shape[2] == 1 or bool(NP.all(wall == wall[:, :, [0]]))
-            def window(t):
-                return wall[:, :, t if t < wall.shape[2] else 0]
-            w_first = wall[:, :, 0]
+    def _transform_cubes(self, layers, pad, decimate=True):
+        """The delay transform of the visibility cubes that exist, for delay_transform() and DelaySpectrum.delay_transform().  layers:
+        the per-snapshot windows bp * bp_wts, each (1 | nbl, nchan).  Returns (sky, lags, vis_lag, vis_noise_lag, make_kernel): sky is a
+        _ResidentLags when the cube is resident on the device (reserve()) and one window serves every snapshot -- all snapshots are
+        transformed where they are and the spectra stay in HBM until read (the device cube is complex128 for memsave runs too: nothing is
+        rounded on the way) --, else the host array (nbl, nlag, nt), transformed snapshot by snapshot through device slot 0; lags are the
+        context's; vis_lag / vis_noise_lag are None where the cube does not exist; make_kernel() forms lag_kernel.
+        decimate=False (DelaySpectrum's downsample=False with pad > 0): every snapshot goes through the host, the zero-padded product
+        uploaded as the single snapshot of a temporary context whose channel grid is the padded one and transformed there with pad = 0 --
+        same FFT length, same (npad + N) df scale (:1316-1321)."""
+        ctx, nbl, nchan = self._ctx, self.baselines.shape[0], self.channels.size
+        same = _all_same(layers)
 
         def transform(cube):
-            # cube (nbl, nchan, nt) times bp*bp_wts, one snapshot at a time through the device cube slot 0
-            nt = cube.shape[2]
-            outs = []
-            for t in range(nt):
-                out, lags, _ = self._ctx.delay_transform_host(cube[:, :, t], window(t if not same_wts else 0), pad)
+            outs, lags = [], None
+            for t in range(cube.shape[2]):
+                window = NP.broadcast_to(layers[t if (not same and t < len(layers)) else 0], (nbl, nchan))
+                if decimate:
+                    out, lags, _ = ctx.delay_transform_host(cube[:, :, t], window, pad)
+                else:
+                    npad = int(nchan * pad)
+                    x = NP.zeros((nbl, nchan + npad), dtype=NP.complex128)
+                    x[:, :nchan] = cube[:, :, t] * window
+                    grid = self.channels[0] + self.freq_resolution * NP.arange(nchan + npad)
+                    with _abi.Context(getattr(ctx, 'device', 0)) as tmp:
+                        tmp.set_array(NP.asarray(self.baselines, dtype=NP.float64), grid, nt_max=1)
+                        out, lags, _ = tmp.delay_transform_host(x, None, 0.0)
                 outs.append(out)
             return NP.stack(outs, axis=2), lags
 
         # number of snapshots without forcing device-resident ones onto the host (_DeviceSlot placeholders)
-        nt_all = len(self._cube) if self._cube else self._skyvis_override.shape[2]
+        nt = len(self._cube) if self._cube else self._skyvis_override.shape[2]
         # Are the device slots holding THIS cube?  observe() into reserved slots leaves them in step; assigning skyvis_freq (the setter,
         # adopt_observation + assignment, assemble_full_array) does not -- then the cube is uploaded first when the slots exist,
         # otherwise the transform goes snapshot by snapshot through slot 0.
-        if bool(self._cube) and self._reserved >= nt_all and self.n_acc == nt_all and not getattr(self, '_device_in_step', False) \
+        if bool(self._cube) and self._reserved >= nt and self.n_acc == nt and not getattr(self, '_device_in_step', False) \
                 and not any(isinstance(sn, _DeviceSlot) for sn in self._cube):
             self._upload_cube()
         resident = self._reserved >= self.n_acc and bool(self._cube) and getattr(self, '_device_in_step', False)   # slot 0 must survive
-        self._skyvis_lag, self._lag_resident = None, None
-        if resident and self._reserved >= nt_all and self.n_acc == nt_all and same_wts:
-            # the cube is resident on the GPU (reserve()): all snapshots are transformed where they are and the spectra stay in HBM
-            # until skyvis_lag is read (the device cube is complex128 for memsave runs too: nothing is rounded on the way)
-            self.lags, nout = self._ctx.delay_transform_device(nt_all, bpwts=w_first, pad=pad, want_lag=True)
-            self._lag_resident = (nt_all, nout)
-            self._lag_args = (nt_all, None if w_first is None else NP.array(w_first, dtype=NP.float64), pad)
-            self._lag_gen = getattr(self._ctx, '_dt_generation', None)
+        if resident and self._reserved >= nt and self.n_acc == nt and same and decimate:
+            w0 = layers[0][0] if layers[0].shape[0] == 1 else layers[0]          # (nchan,): one window for every baseline
+            sky = _ResidentLags(ctx, nt, w0, pad)
+            lags = sky.lags
         else:
-            host_cube = NP.asarray(self.skyvis_freq, dtype=NP.complex128)
-            saved0 = self._ctx.get_vis(slot=0) if resident else None       # the host-side transforms run through slot 0
-            self._skyvis_lag, self.lags = transform(host_cube)
-            if saved0 is not None:
-                self._ctx.set_vis(saved0, slot=0)
+            cube = NP.asarray(self.skyvis_freq, dtype=NP.complex128)
+            with _through_slot0(ctx, resident):
+                sky, lags = transform(cube)
 
-        def through_slot0(fn):
-            saved = self._ctx.get_vis(slot=0) if resident else None
-            try:
-                return fn()
-            finally:
-                if saved is not None:
-                    self._ctx.set_vis(saved, slot=0)                   # put the resident snapshot back
-
+        # (the reference multiplies vis_freq / vis_noise_freq unconditionally and fails on a noiseless object, SURVEY Q20: here the
+        # cubes that exist are transformed)
+        vis_lag = vis_noise_lag = None
         if self.vis_freq is not None:
-            self.vis_lag = through_slot0(lambda: transform(NP.asarray(self.vis_freq, dtype=NP.complex128))[0])
+            with _through_slot0(ctx, resident):
+                vis_lag = transform(NP.asarray(self.vis_freq, dtype=NP.complex128))[0]
         if self.vis_noise_freq is not None:
-            self.vis_noise_lag = through_slot0(lambda: transform(NP.asarray(self.vis_noise_freq, dtype=NP.complex128))[0])
+            with _through_slot0(ctx, resident):
+                vis_noise_lag = transform(NP.asarray(self.vis_noise_freq, dtype=NP.complex128))[0]
 
         def make_kernel():
-            if same_wts:
-                # the transform of bp * bp_wts (:8119 / :8127) is the same for every snapshot then: one FFT batch, repeated
-                kern = through_slot0(lambda: transform(NP.ones((nbl, nchan, 1), dtype=NP.complex128))[0])
-                return NP.repeat(kern, nt_all, axis=2)
-            return through_slot0(lambda: transform(NP.ones((nbl, nchan, nt_all), dtype=NP.complex128))[0])
-        self._lag_kernel, self._lag_kernel_maker = None, make_kernel      # formed on first read of lag_kernel
+            with _through_slot0(ctx, resident):
+                if same:
+                    # the transform of bp * bp_wts (:8119 / :8127) is the same for every snapshot then: one FFT batch, repeated
+                    return NP.repeat(transform(NP.ones((nbl, nchan, 1), dtype=NP.complex128))[0], nt, axis=2)
+                return transform(NP.ones((nbl, nchan, nt), dtype=NP.complex128))[0]
+        return sky, lags, vis_lag, vis_noise_lag, make_kernel

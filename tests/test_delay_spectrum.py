@@ -202,6 +202,39 @@ def test_stored_spectra_survive_later_transforms_on_the_same_context(monkeypatch
     assert NP.max(NP.abs(ia.skyvis_lag - other)) <= 1e-12 * NP.max(NP.abs(other))
 
 
+def test_array_and_delay_spectrum_entries_agree(monkeypatch):
+    """InterferometerArray.delay_transform and DelaySpectrum.delay_transform(action='store') of the same window give identical skyvis_lag,
+    lag_kernel and lags from the same number of device and host transforms, with the cube resident on the device (reserve()) and without."""
+    import fake_context
+    calls = {'device': 0, 'host': 0}
+
+    class Spy(fake_context.OracleContext):
+        def delay_transform_device(self, nt, **kw):
+            calls['device'] += 1
+            return fake_context.OracleContext.delay_transform_device(self, nt, **kw)
+
+        def delay_transform_host(self, vis, bpwts, pad):
+            calls['host'] += 1
+            return fake_context.OracleContext.delay_transform_host(self, vis, bpwts, pad)
+
+    for reserve in (True, False):
+        ia, _ = _observed_array(monkeypatch, reserve=reserve, ctxcls=Spy)
+        w = NP.blackman(ia.channels.size) + 0.05
+        got = []
+        for entry in ('array', 'delay_spectrum'):
+            calls.update(device=0, host=0)
+            if entry == 'array':
+                ia.delay_transform(pad=1.0, freq_wts=w, verbose=False)
+                obj = ia
+            else:
+                obj = DS.DelaySpectrum(ia)
+                obj.delay_transform(pad=1.0, freq_wts=w, action='store', verbose=False)
+            got.append((NP.array(obj.skyvis_lag), NP.array(obj.lag_kernel), NP.array(obj.lags), dict(calls)))
+        (sky_a, kern_a, lags_a, calls_a), (sky_d, kern_d, lags_d, calls_d) = got
+        assert NP.array_equal(sky_a, sky_d) and NP.array_equal(kern_a, kern_d) and NP.array_equal(lags_a, lags_d)
+        assert calls_a == calls_d == ({'device': 1, 'host': 1} if reserve else {'device': 0, 'host': ia.n_acc + 1})
+
+
 @pytest.mark.gpu
 def test_delay_power_spectrum_on_the_gpu_at_config2_size():
     """BASELINE config 2 (HERA-19, 256 channels, nside-16 diffuse, Airy 14 m) through observe() -> DelaySpectrum.delay_transform ->
