@@ -26,13 +26,20 @@ rank's pattern, the run FAILS before the timed region (exit 3, RCCL's own warnin
 At N > 1 the line also carries `gather` (bytes per peer, per-snapshot ms on the communication stream, the exposed tail after the last
 sky-sum, GB/s per xGMI link against 153), the slowest / fastest rank's kernel ms and `value_n1_equiv` = value / N.
 
-Rank 0 prints ONE JSON line.  Beside the contract's keys it carries (N = 1 only, all outside the timed region):
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: it sets up, warms up, times the steps, writes
+--dump-outputs if asked, and prints.  Beside the contract's keys the line carries what the timed steps themselves yield:
   roofline / roofline_hbm   the dominant kernel against the VALU issue roofline (the binding one) and the HBM figure BASELINE words
+                            (kernel time of the timed steps by hipEvents; `traffic` from a committed profile of the same sources)
+With --full (N = 1 only; all of it after the timed steps, none of it inside them; --extras picks which) it also carries:
   cpu_baseline              C/OpenMP port of interferometry.py:6332-6340 on this box's host cores (bounded sample) + parity check
   cpu_baseline_ref          the reference FORMULATION itself: numpy restatement, one process, slabbed like :6348-6376 (bounded sample)
   cpu_baseline_ref_xN       the reference's parallel model: N such processes side by side over baseline chunks (mpirun, run_prisim.py:1749-1791)
   e2e                       the same snapshots through InterferometerArray.observe(), host geometry and sky staging included
+  e2e_batch                 the same through observe_batch(): all snapshots in one call
   e2e_host                  the same with every snapshot landing in (pinned) HOST memory: downloads overlapped with the next sky-sum
+  e2e_shard_estimate        rank 0's share of BASELINE config 4 at N = 1 and 8 through the product loop, against compute() alone
+  gather_rehearsal          a 1-rank RCCL communicator: gathers of a 1/8 shard on the priority stream under the next sky-sum
+  power_clock               sclk and package power under the dominant kernel, on the workload's sky and on constant operands
   delay_ps                  delay power spectra of the resident snapshots (interferometry.py:8114-8134 + delay_spectrum.py:3992):
                             device time, FFT count, achieved algorithmic GB/s against the 8 TB/s HBM roofline
   other_kernels             min / median of 5 timed launches each of the fp64 kernel (headline sky), the fused gradient kernels, and -- on config 3
@@ -922,9 +929,13 @@ def main():
     ap.add_argument('--workload', choices=('cfg3', 'cfg3d', 'cfg5'), default='cfg3',
                     help='cfg3: the headline workload (BASELINE config 3, 1e4 point sources); cfg3d: config 3 with its nside=128 diffuse half '
                          '(source-shape taper on); cfg5: one LST of config 5 (nside=256 diffuse sky, taper on)')
-    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the CPU baselines, the e2e and the delay-stage extras (profiling runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='N = 1 only: after the headline, also measure and check everything else the documents quote (the extras --extras '
+                         'names: CPU baselines and their parity against the GPU result, other configurations and kernels, the product loop); '
+                         'off by default, so that a plain run only sets up, warms up, times the steps, dumps and prints')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the extras even with --full (profiling runs; a plain run has none)')
     ap.add_argument('--extras', choices=('core', 'all'), default='core',
-                    help="N = 1 only.  core (default): the CPU baselines and the extras the documents quote -- config 2, the config-4 shard through the "
+                    help="with --full.  core (default): the CPU baselines and the extras the documents quote -- config 2, the config-4 shard through the "
                          "product loop, the 1-rank RCCL rehearsal, the delay stage, observe() end to end -- each a median of 3 passes; all: also "
                          "the reference formulation x N ranks, the power / clock probe, the other kernels and the kernel-only shard estimate "
                          "(kept under profiles/ once per round: they add a minute)")
@@ -1158,10 +1169,10 @@ def main():
             out['gather'] = gstats
             out['gather_ok'] = gather_ok
             out['launcher'] = 'torch.distributed.run env' if 'TORCHELASTIC_RUN_ID' in os.environ else 'prisim_amd.launch'
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # Everything below is reported beside the contract line, never instead of it: an extra that raises is named in `extras_failed`
             # (and keeps its {'error': ...} entry), so a regression in one of them is visible in the record; `extras_seconds` says what each
-            # cost.  --extras core (the default) keeps the whole run inside ~90 s of driver time; --extras all is the once-per-round record.
+            # cost.  --full with --extras core (the default) adds about 45 s; --extras all is the once-per-round record.
             failed, seconds = [], {}
 
             def extra(key, fn, on_error=None):

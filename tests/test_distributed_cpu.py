@@ -180,3 +180,24 @@ def test_bench_steps_sets_the_timed_steps(tmp_path):
     sub.mkdir()
     codes, lines, errs, _ = _bench_ranks(sub, 1, extra=('--steps', '0'))
     assert codes == [2] and lines == [[]] and '--steps' in errs[0]
+
+
+def test_bench_plain_run_does_only_the_headline(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (no --full, no --no-cpu-baseline): the warm-up and the K timed steps are the
+    only computes, nothing runs after them, and the line carries none of the extras --full adds."""
+    import json
+    env = dict(os.environ, OMP_NUM_THREADS='1', BENCH_REHEARSAL_DIR=str(tmp_path), BENCH_REHEARSAL_MODE='ok')
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'PRISIM_RDZV_FILE', 'MASTER_PORT'):
+        env.pop(k, None)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'bench_worker.py'), '--gpus', '1', '--steps', '3', '--warmup', '2',
+                          '--nsrc', '16'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, res.stdout
+    d = json.loads(lines[0])
+    assert d['metric'] == 'visibility-terms/sec' and d['n_gpus'] == 1 and d['steps'] == 3 and d['warmup'] == 2 and d['ms_per_step'] > 0
+    for key in ('extras', 'extras_failed', 'extras_seconds', 'parity_max_err_rel_sumflux', 'cpu_baseline', 'cpu_baseline_ref', 'delay_ps',
+                'config2', 'gather_rehearsal', 'e2e_shard_estimate', 'e2e', 'e2e_batch', 'e2e_host'):
+        assert key not in d, key
+    with open(str(tmp_path / 'timed_slots_0.json')) as f:
+        assert json.load(f)['slots'] == [0, 1, 2]                               # the timed steps, and no compute after them
