@@ -106,7 +106,7 @@ __device__ __forceinline__ void sincos_cycles_hw(double a, float& c, float& s) {
 }
 
 // sin(2 pi y) for |y| <= 1/8 cycle: y * (2pi_hi + (2pi_lo + y^2 P(y^2))), P = degree-2 minimax fit (1.8e-9 abs), so the
-// result is within ~1 ulp in 6 instructions.  This is the lifting step's s = sin(alpha): its error is multiplied by the chain length.
+// result is within ~1 ulp in 6 instructions.  This is the step rotation's s = sin(alpha) (lifting and leapfrog forms): its error is multiplied by the chain length.
 __device__ __forceinline__ float sin_2pi_y(float y) {
   const float y2 = y * y;
   float ps = -75.36964416503906f;
@@ -1089,12 +1089,15 @@ void k_skyvis_grad_f64(const SkyvisParams p) {
 //   middle:           wait (second half row)                             ->  request first half row + direction of s+1
 //                     pairs HC/2..HC-1
 //
-// LIFT: the step rotation uses the lifting (three-shear) form
-//     x1 = x - t y,  y1 = y + s x1,  x2 = x1 - t y1,   t = tan(alpha/2), s = sin(alpha)
-// = 3 dependent packed FMAs instead of 2 mul + 2 fma, i.e. 5 instead of 6 packed instructions per pair of terms
-// (tools/microbench_inner.hip: 12.5e12 vs 11.1e12 terms/s for the bare loop).  With inexact (t, s) the map is still
-// area-preserving and advances the phase by beta with cos(beta) = 1 - t s, so the angle error per step is ~ alpha * eps:
-// it is only used where |alpha| <= pi/4 is GUARANTEED for every source (the host sets lift_flags[bg] when
+// LIFT: the step rotation is the leapfrog (two-term) recurrence of a unit step r = e^{i alpha}
+//     z_{k+1} = z_{k-1} + (r - conj r) z_k:   x_{k+1} = x_{k-1} - 2 s y_k,  y_{k+1} = y_{k-1} + 2 s x_k,   s = sin(alpha)
+// = 2 packed FMAs (leapfrog_step) instead of 2 mul + 2 fma, i.e. 4 instead of 6 packed instructions per pair of terms.  It replaced
+// the lifting (three-shear) form x1 = x - t y, y1 = y + s x1, x2 = x1 - t y1 (t = tan(alpha/2): 3 FMAs, 5 per pair), which the
+// generic k_skyvis_rec keeps.  Its roots are e^{i alpha} and the parasitic -e^{-i alpha}, both of modulus 1, so rounding errors add
+// up linearly; the split between the two modes is conditioned by 1 / cos(alpha) and s keeps full relative precision as alpha -> 0
+// (unlike the 2 cos(alpha) of a Chebyshev recurrence), so the angle error per step is ~ alpha * eps.  The previous value of each
+// chain is the other chain's seed (z_{-1} of the up chain is channel HC - 1), so the seed pair, swapped, starts the recurrence.
+// It is only used where |alpha| <= pi/4 is GUARANTEED for every source (the host sets lift_flags[bg] when
 // max|b| * max_s|s - s_pc| * |df| / c <= 1/8 cycle for the baseline group), all other groups take the 4-instruction rotation.
 // ------------------------------------------------------------------------------------------
 // waves per SIMD the packed kernels are built for: at 3 (168 VGPRs) the compiler spills around the flush (and, with the taper,
@@ -1106,6 +1109,16 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 
 __device__ __forceinline__ f32x2 pkfma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+
+// One leapfrog step of an (up, down) chain pair (LIFT bodies): z_{k+1} = z_{k-1} + (r - conj r) z_k = z_{k-1} + 2 i sigma z_k, exact for
+// a unit step r whatever the chain, so 2 packed FMAs instead of the lifting form's 3.  S2 = (2 sigma_up, 2 sigma_down) = (2 sin alpha,
+// -2 sin alpha); the first FMA's -S2 is a neg modifier.  (zp_re, zp_im) holds z_{k-1}; the caller's unrolled loop renames, no moves.
+__device__ __forceinline__ void leapfrog_step(f32x2& zre, f32x2& zim, f32x2& zp_re, f32x2& zp_im, f32x2 S2) {
+  const f32x2 nre = pkfma(-S2, zim, zp_re);
+  const f32x2 nim = pkfma(S2, zre, zp_im);
+  zp_re = zre; zp_im = zim;
+  zre = nre; zim = nim;
+}
 
 typedef const __attribute__((address_space(4))) float* cfloat_p;
 typedef const __attribute__((address_space(4))) double* cdouble_p;
@@ -1154,7 +1167,7 @@ __device__ __forceinline__ float exp2m1_small(float D) {
 //   GPK (GRAD bodies without the taper): the rows arrive PRE-MULTIPLIED by the gradient coefficients -- k_pack_grad writes, per source and
 //   16-channel tile, the four operand rows p, p l, p m, p n interleaved per pair as (set, up / down), 64 floats = one 256-byte row like a
 //   64-channel tile's -- so every accumulator set takes its own SGPR-pair operand straight into v_pk_fma_f32: 8 accumulate FMAs + the
-//   3-instruction lifting rotation = 11 packed instructions per pair of terms instead of 13 (term = p zeta first, then four adds / FMAs), and
+//   2-instruction leapfrog rotation (LIFT groups) = 10 packed instructions per pair of terms instead of 13 (term = p zeta first, then four adds / FMAs), and
 //   the per-source coefficient load disappears.
 template <int CT, bool TAPER, bool LIFT, int TGROUP = 0, int REANCHOR = 0, bool GRAD = false, bool GPK = false>
 __device__ __forceinline__ void skyvis_rec_f32pk_body(const SkyvisParams& p, unsigned char* flush_lds) {
@@ -1354,32 +1367,25 @@ __device__ __forceinline__ void skyvis_rec_f32pk_body(const SkyvisParams& p, uns
       float zc, zs;
       sincos_cycles_hw(d * fc_hz, zc, zs);
       const float ur0 = zc, ui0 = -zs;
-      float rr = 1.f, ri, tpy = 0.f, dr0, di0;
-      if (LIFT) {
+      float rr, ri;
+      if (LIFT || (TAPER && REANCHOR != 2)) {
+        // LIFT and the taper bodies of baseline groups whose |theta| <= 1/8 cycle is guaranteed (the host's lift flag): no quadrant logic
         const float yth = (float)(d * p.df);
+        rr = cos_2pi_y(yth);
         ri = -sin_2pi_y(yth);
-        tpy = tan_pi_y(yth);
-        const float x1 = __builtin_fmaf(-tpy, ui0, ur0);
-        di0 = __builtin_fmaf(-ri, x1, ui0);
-        dr0 = __builtin_fmaf(-tpy, di0, x1);
       } else {
-        if (TAPER && REANCHOR != 2) {
-          // taper bodies of baseline groups whose |theta| <= 1/8 cycle is guaranteed (the host's lift flag): no quadrant logic
-          const float yth = (float)(d * p.df);
-          rr = cos_2pi_y(yth);
-          ri = -sin_2pi_y(yth);
-        } else {
-          float rc, rs;
-          sincos_qcycles(d * df4, rc, rs);
-          rr = rc; ri = -rs;
-        }
-        dr0 = __builtin_fmaf(ur0, rr, ui0 * ri);
-        di0 = __builtin_fmaf(ui0, rr, -(ur0 * ri));
+        float rc, rs;
+        sincos_qcycles(d * df4, rc, rs);
+        rr = rc; ri = -rs;
       }
-      const f32x2 NT = {tpy, -tpy};                    // (-t_up, -t_down)
-      const f32x2 SS = {ri, -ri};                      // (sin alpha_up, sin alpha_down)
+      const float dr0 = __builtin_fmaf(ur0, rr, ui0 * ri);
+      const float di0 = __builtin_fmaf(ui0, rr, -(ur0 * ri));
       f32x2 zre = {ur0, dr0};
       f32x2 zim = {ui0, di0};
+      // LIFT: leapfrog state.  The up chain's z_{-1} (channel HC - 1) is the down chain's seed and the reverse, so the previous pair is
+      // the seed pair swapped; 2 sigma = 2 sin alpha is formed once here (the down chain steps by conj r: -sigma)
+      const f32x2 S2 = {2.f * ri, -2.f * ri};
+      f32x2 zp_re = __builtin_shufflevector(zre, zre, 1, 0), zp_im = __builtin_shufflevector(zim, zim, 1, 0);
       const f32x2 RR = {rr, rr};
       const f32x2 RI = {-ri, ri};                      // re' = re*rr + im*RI ;  im' = im*rr - re*RI
       // Source-shape taper folded into the recurrence.  log2 w at channel HC+j is L(j) = A + B j + C j^2 with
@@ -1452,10 +1458,7 @@ __device__ __forceinline__ void skyvis_rec_f32pk_body(const SkyvisParams& p, uns
               acc_im[rs][j] = pkfma(pr, zim, acc_im[rs][j]);
             }
             if (LIFT) {
-              const f32x2 x1 = pkfma(NT, zim, zre);
-              const f32x2 y1 = pkfma(SS, x1, zim);
-              zre = pkfma(NT, y1, x1);
-              zim = y1;
+              leapfrog_step(zre, zim, zp_re, zp_im, S2);
             } else {
               const f32x2 t0 = zim * RI;
               const f32x2 t1 = zre * RI;
@@ -1503,11 +1506,7 @@ __device__ __forceinline__ void skyvis_rec_f32pk_body(const SkyvisParams& p, uns
             acc_im[0][j] = pkfma(pp, zim, acc_im[0][j]);
           }
           if (LIFT) {
-            // x1 = x - t y, y1 = y + s x1, x2 = x1 - t y1
-            const f32x2 x1 = pkfma(NT, zim, zre);
-            const f32x2 y1 = pkfma(SS, x1, zim);
-            zre = pkfma(NT, y1, x1);
-            zim = y1;
+            leapfrog_step(zre, zim, zp_re, zp_im, S2);
           } else if (!TAPER) {
             const f32x2 t0 = zim * RI;
             const f32x2 t1 = zre * RI;
