@@ -51,6 +51,12 @@ PRISIM_SUBBAND_OVER, PRISIM_SUBBAND_OVER_POWER, PRISIM_SUBBAND_RES, PRISIM_SUBBA
 PRISIM_SUBBAND_AUTO, PRISIM_SUBBAND_FUSED, PRISIM_SUBBAND_ROCFFT = -1, 0, 1
 SUBBAND_ROUTES = {PRISIM_SUBBAND_FUSED: 'fused', PRISIM_SUBBAND_ROCFFT: 'rocfft'}
 
+# every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
+GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
+                 'prisim_gains_table_free', 'prisim_gains_apply')
+PRISIM_GAINS_MAX_DEGREE = 5
+PRISIM_GAINS_ANTENNA, PRISIM_GAINS_BASELINE = 0, 1
+
 
 class PrisimSky(C.Structure):
     _fields_ = [('nsrc', C.c_int64), ('dircos', C.c_void_p), ('pbflux', C.c_void_p),
@@ -175,6 +181,10 @@ class PrisimSubbandStats(C.Structure):
                 ('lds_bytes', C.c_int32)]
 
 
+class PrisimGainsStats(C.Structure):
+    _fields_ = [('device_ms', C.c_double), ('kernel_ms', C.c_double), ('elements', C.c_int64)]
+
+
 class PrisimHipError(RuntimeError):
     """Raised when libprisim_hip.so is missing/unloadable or no GPU is usable."""
 
@@ -261,6 +271,19 @@ def load_library():
     lib.prisim_subband_transform.argtypes = [vp, C.c_int32, i64, i64, i64, vp, i64, vp, i64, C.c_int32, vp, i64, dbl, i64, i64, vp, vp, vp,
                                              vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.POINTER(PrisimSubbandStats)]
     lib.prisim_subband_transform.restype = C.c_int
+    pst = C.POINTER(PrisimGainsStats)
+    lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
+                                             C.POINTER(vp), pst]
+    lib.prisim_gains_gather.argtypes = [vp, i64, i64, i64, vp, i64, vp, i64, vp, C.POINTER(vp), pst]
+    lib.prisim_gains_table_shape.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    lib.prisim_gains_table_get.argtypes = [vp, vp, vp]
+    lib.prisim_gains_table_free.argtypes = [vp]
+    lib.prisim_gains_table_free.restype = None
+    lib.prisim_gains_apply.argtypes = [vp, i64, i64, i64, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, i64, C.c_int32, vp, C.c_int32,
+                                       vp, pst]
+    for name in GAINS_EXPORTS:
+        if name != 'prisim_gains_table_free':
+            getattr(lib, name).restype = C.c_int
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ('prisim_hip_destroy', 'prisim_hip_last_error', 'prisim_hip_version'):
@@ -852,6 +875,66 @@ class Context(object):
         return {'device_ms': st.device_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows), 'route': SUBBAND_ROUTES.get(st.route, st.route),
                 'lds_bytes': int(st.lds_bytes)}
 
+    # ---- instrument gain tables (include/prisim_gains.h) ----
+    @staticmethod
+    def _gains_stats(st):
+        return {'device_ms': st.device_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements)}
+
+    def gains_eval_spline(self, packed, times, freqs):
+        """Evaluate a packed spline table (prisim_amd/gains.py:pack_splines) at every (time, channel) on the device: a GainTable
+        [nt][nrows][nchan] and the stats."""
+        t = NP.ascontiguousarray(NP.asarray(times, dtype=NP.float64).ravel())
+        f = NP.ascontiguousarray(NP.asarray(freqs, dtype=NP.float64).ravel())
+        arr = {k: NP.ascontiguousarray(packed[k], dtype=NP.int64) for k in ('nx', 'ny', 'kx_off', 'ky_off', 'c_off')}
+        kn = NP.ascontiguousarray(packed['knots'], dtype=NP.float64)
+        co = NP.ascontiguousarray(packed['coefs'], dtype=NP.float64)
+        nrows = arr['nx'].size // 2
+        h, st = C.c_void_p(), PrisimGainsStats()
+        self._check(self._lib.prisim_gains_eval_spline(self._h, nrows, int(packed['kx']), int(packed['ky']), _ptr(arr['nx']), _ptr(arr['ny']),
+                                                       _ptr(arr['kx_off']), _ptr(arr['ky_off']), _ptr(arr['c_off']), kn.size, _ptr(kn),
+                                                       co.size, _ptr(co), t.size, _ptr(t), f.size, _ptr(f), C.byref(h), C.byref(st)),
+                    'prisim_gains_eval_spline')
+        return GainTable(self, h), self._gains_stats(st)
+
+    def gains_gather(self, gains, fidx, tidx):
+        """Nearest-neighbour table on the device: table[t][r][f] = gains[r][fidx[f]][tidx[t]] for gains (nrows, ngf, ngt)."""
+        g = NP.ascontiguousarray(gains, dtype=NP.complex128)
+        if g.ndim != 3:
+            raise ValueError('gains must be (nrows, nfreq, ntime)')
+        fi = NP.ascontiguousarray(NP.asarray(fidx).ravel(), dtype=NP.int64)
+        ti = NP.ascontiguousarray(NP.asarray(tidx).ravel(), dtype=NP.int64)
+        h, st = C.c_void_p(), PrisimGainsStats()
+        self._check(self._lib.prisim_gains_gather(self._h, g.shape[0], g.shape[1], g.shape[2], _ptr(g), fi.size, _ptr(fi), ti.size, _ptr(ti),
+                                                  C.byref(h), C.byref(st)), 'prisim_gains_gather')
+        return GainTable(self, h), self._gains_stats(st)
+
+    def gains_apply(self, nt, nbl, nchan, fa=None, fb=None, sky=None, t0=0, sky_c64=False, noise=None, want_gain=False):
+        """vis [nt][nbl][nchan] = (fa * fb) * sky + noise on the device (prisim_gains_apply).  fa / fb: None or (GainTable, mode, a, c)
+        with mode PRISIM_GAINS_ANTENNA | PRISIM_GAINS_BASELINE and a, c (nbl,) rows; sky: (nt, nbl, nchan) complex128 or None for the
+        resident slots [t0, t0 + nt); want_gain: the gain cube itself.  Returns (vis, stats)."""
+        def fac(x):
+            if x is None:
+                return None, 0, None, None
+            tab, mode, a, c = x
+            return (tab._h, int(mode), NP.ascontiguousarray(NP.asarray(a).ravel(), dtype=NP.int64),
+                    NP.ascontiguousarray(NP.asarray(c).ravel(), dtype=NP.int64))
+        ta, ma, aa, ca = fac(fa)
+        tb, mb, ab, cb = fac(fb)
+        for arr in (aa, ca, ab, cb):
+            if arr is not None and arr.size != nbl:
+                raise ValueError('factor rows must have one entry per baseline')
+        s = None if (sky is None or want_gain) else NP.ascontiguousarray(sky, dtype=NP.complex128)
+        n = None if (noise is None or want_gain) else NP.ascontiguousarray(noise, dtype=NP.complex128)
+        for arr in (s, n):
+            if arr is not None and arr.shape != (nt, nbl, nchan):
+                raise ValueError('sky and noise must be (nt, nbl, nchan)')
+        out = NP.empty((nt, nbl, nchan), dtype=NP.complex128)
+        st = PrisimGainsStats()
+        self._check(self._lib.prisim_gains_apply(self._h, int(nt), int(nbl), int(nchan), ta, ma, _ptr(aa), _ptr(ca), tb, mb, _ptr(ab), _ptr(cb),
+                                                 _ptr(s), int(t0), int(bool(sky_c64)), _ptr(n), int(bool(want_gain)), _ptr(out), C.byref(st)),
+                    'prisim_gains_apply')
+        return out, self._gains_stats(st)
+
     # ---- multi-GPU ----
     @staticmethod
     def comm_unique_id():
@@ -996,3 +1079,30 @@ class Context(object):
     def set_tuning(self, chan_tile=0, src_chunk=0, nsplit=0):
         self._check(self._lib.prisim_hip_set_tuning(self._h, int(chan_tile), int(src_chunk), int(nsplit)),
                     'prisim_hip_set_tuning')
+
+
+class GainTable(object):
+    """A gain table on the device ([nt][nrows][nchan] complex128, include/prisim_gains.h), freed with close() or when collected.
+    It keeps its context alive."""
+
+    def __init__(self, ctx, handle):
+        self._ctx, self._h = ctx, handle
+        nt, nr, nf = C.c_int64(), C.c_int64(), C.c_int64()
+        ctx._lib.prisim_gains_table_shape(handle, C.byref(nt), C.byref(nr), C.byref(nf))
+        self.shape = (int(nt.value), int(nr.value), int(nf.value))
+
+    def get(self):
+        out = NP.empty(self.shape, dtype=NP.complex128)
+        self._ctx._check(self._ctx._lib.prisim_gains_table_get(self._ctx._h, self._h, _ptr(out)), 'prisim_gains_table_get')
+        return out
+
+    def close(self):
+        if getattr(self, '_h', None) and getattr(self._ctx, '_h', None):
+            self._ctx._lib.prisim_gains_table_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

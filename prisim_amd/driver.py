@@ -12,8 +12,12 @@ Replaced: `mpirun` ranks + per-rank part files + rank-0 concatenate become one p
 itself through prisim_amd.launch; any launcher that sets RANK / WORLD_SIZE / LOCAL_RANK works too) and a single RCCL all-gather of the
 visibility cube;
 the rank-0 ROI/beam precompute through FITS files disappears (beams are fused on the device).
+Instrument gains (gains.file, run_prisim.py:177-187): a GainInfo of the file -- filepathtype 'custom' takes the path as given, 'default'
+(prisim/data/gains, absent) raises NotImplementedError -- is handed to the array and applied in add_noise (only there, as in the
+reference: a run that skips the noise applies no gains and says so); in a sharded run every rank applies them to its own shard before
+the exchange, its padding rows with unity gains, and the noisy cube vis_freq is gathered.
 Not offered (out of scope): survey catalogs (SUMSS/NVSS/GLEAM/GSM need prisim/data, absent),
-gains, uvfits/uvh5 writers, plots, resource monitor (`pp.key: 'freq' | 'src'` are accepted and run on baseline shards).  After the snapshots: thermal noise, re-centring on
+uvfits/uvh5 writers, plots, resource monitor (`pp.key: 'freq' | 'src'` are accepted and run on baseline shards).  After the snapshots: thermal noise, re-centring on
 phasing.center, delay transform and the npz / HDF5 files, in the reference's order (:2278-2286); in a sharded run every rank does the
 per-baseline steps on its own shard and rank 0 puts the whole array together from the gathered cubes (assemble_full_array).  Two synthetic sky models
 are added because the reference's catalogs are not available offline: skyparm.model 'ptsrc_random' and 'healpix_synthetic'.
@@ -62,6 +66,7 @@ DEFAULTS = {
     'skyparm': {'model': 'custom', 'epoch': '2000', 'nside': 16, 'flux_unit': 'Jy', 'custom_reffreq': 0.150, 'flux_min': 0.0,
                 'flux_max': None, 'fluxcut_reffreq': None, 'spindex': -0.83, 'roi_radius': None, 'n_src': 100, 'seed': 1},
     'catalog': {'custom_file': 'custom_catalog.txt'},
+    'gains': {'file': None, 'filepathtype': 'default'},
     'processing': {'gradient_mode': None, 'f_pad': 1.0, 'bpass_shape': 'bhw', 'delay_transform': False, 'memsave': False,
                    'add_noise': None, 'noise_seed': None},
     'phasing': {'center': [90.0, 270.0], 'coords': 'altaz'},
@@ -157,6 +162,22 @@ def baseline_info(parms):
     labels = all_labels[first].tolist()
     groups = {labels[i]: all_labels[NP.asarray(occ[i])].tolist() for i in range(len(labels))}
     return ubl, labels, pos, groups
+
+
+def build_gaininfo(parms):
+    """run_prisim.py:177-187: None without gains.file, else GainInfo(init_file=..., axes_order=['label', 'frequency', 'time'])."""
+    gp = parms.get('gains') or {}
+    if gp.get('file') is None:
+        return None
+    if not isinstance(gp['file'], str):
+        raise TypeError('Filename of instrument gains must be a string')
+    kind = gp.get('filepathtype', 'default')
+    if kind == 'default':
+        raise NotImplementedError('gains.filepathtype default reads prisim/data/gains/{0}, which this build does not carry; give the '
+                                  'file with gains.filepathtype: custom'.format(gp['file']))
+    if kind != 'custom':
+        raise ValueError("gains.filepathtype must be 'default' or 'custom'")
+    return RI.GainInfo(init_file=gp['file'], axes_order=['label', 'frequency', 'time'])
 
 
 def read_custom_catalog(path):
@@ -370,8 +391,12 @@ def run(parms, infile_dir='.', rank=0, world=1, device=0, comm_uid=None, verbose
     proc = parms['processing']
     ia_kwargs = dict(telescope=tel, eff_Q=parms['telescope']['eff_Q'], latitude=tel['latitude'], longitude=tel['longitude'],
                      altitude=tel['altitude'], skycoords='radec', A_eff=parms['telescope']['A_eff'], pointing_coords='hadec', device=device,
-                     blgroupinfo={'groups': blgroups, 'reversemap': {m: k for k, v in blgroups.items() for m in v}})
+                     blgroupinfo={'groups': blgroups, 'reversemap': {m: k for k, v in blgroups.items() for m in v}},
+                     gaininfo=build_gaininfo(parms))
     ia = RI.InterferometerArray(labels_mine, bl_mine, chans, **ia_kwargs)
+    if per > n_real:
+        # the padding rows of the last shard are no baselines: unity gains, and never the table's "antenna not found" path
+        ia.gain_padding = NP.arange(per) >= n_real
     # unsharded runs hand the cube to the host (files, the caller): each snapshot's download is queued under the next one's sky-sum;
     # sharded runs gather on the device and never copy their own shard
     ia.reserve(n_acc, host_staging=(world == 1))
@@ -453,6 +478,8 @@ def run(parms, infile_dir='.', rank=0, world=1, device=0, comm_uid=None, verbose
         ia.generate_noise(seed=seed, bl_index=idx_padded)
         ia.add_noise()
         noise_done = True
+    elif ia.gaininfo is not None and verbose and rank == 0:
+        print('instrument gains not applied: the reference applies them in add_noise only, and the noise step is skipped')
     ph = parms.get('phasing') or {}
     if ph.get('center') is not None:
         ref_point = {'coords': ph.get('coords', 'altaz'), 'location': NP.asarray(ph['center'], dtype=float).reshape(1, -1)}
@@ -468,9 +495,11 @@ def run(parms, infile_dir='.', rank=0, world=1, device=0, comm_uid=None, verbose
             download = rank == 0
         cube = unshard(ia.allgather(comm_uid, world, rank, download=download, root=(0 if gather == 'root' else None)))
         labels_all, bl_all = labels, bl
-        noise_all = None
+        noise_all = vis_all = None
         if noise_done:
             noise_all = unshard(ia.allgather_cube(ia.vis_noise_freq, world, download=download))
+            if ia.gaininfo is not None:      # gains * skyvis + noise was formed on every shard: gather it as it stands
+                vis_all = unshard(ia.allgather_cube(ia.vis_freq, world, download=download))
         grad_all = None
         if ia.gradient_mode is not None:
             # the gradient cubes are per baseline too: gathered like the visibilities (interferometry.py:8349-8350 concatenates them)
@@ -488,7 +517,10 @@ def run(parms, infile_dir='.', rank=0, world=1, device=0, comm_uid=None, verbose
         out['vis_freq'], out['vis_noise_freq'] = ia.vis_freq[:nbl_total], ia.vis_noise_freq[:nbl_total]
     elif noise_done:
         out['vis_noise_freq'] = noise_all
-        out['vis_freq'] = (cube + noise_all) if (cube is not None and noise_all is not None) else None
+        if ia.gaininfo is not None:
+            out['vis_freq'] = vis_all
+        else:
+            out['vis_freq'] = (cube + noise_all) if (cube is not None and noise_all is not None) else None
     if proc.get('delay_transform'):
         # every rank transforms its own shard on its GPU (the FFT runs along frequency); sharded runs then exchange the spectra
         ia.delay_transform(pad=float(proc.get('f_pad', 1.0)), freq_wts=window(chans.size, proc.get('bpass_shape', 'bhw')), verbose=False)

@@ -1,6 +1,7 @@
 """Readings of the astroutils functions that prisim/delay_spectrum.py:subband_delay_transform (:2073-2250) calls and that have no
 source and no fixtures here: ``DSP.windowing`` / ``DSP.window_fftpow``, ``DSP.window_N2width``, ``LKP.find_1NN`` and
-``DSP.downsampler``.  Each function below is ONE explicit reading of its name -- PARITY UNPINNED against astroutils --
+``DSP.downsampler``; and ``NMO.find_list_in_list``, which the gain tables of prisim/interferometry.py (read_gaintable, extract_gains,
+GainInfo) use to match axis names and antenna / baseline labels.  Each function below is ONE explicit reading of its name -- PARITY UNPINNED against astroutils --
 pinned by known answers in tests/test_subband.py, and the only place the reading lives: the host chain, the device call and the
 fixtures' stand-in modules all use these functions.
 
@@ -172,3 +173,29 @@ def spectral_axis(length, delx=1.0, shift=False, use_real=False):
 def fft_downsample_length(n, factor):
     """Samples of downsampler(x of n samples, factor, method='FFT'): round(n / factor) (Python's rounding, halves to even)."""
     return int(round(n / float(factor)))
+
+
+def _key(x):
+    """Hashable form of one element: structured records and array rows become tuples, bytes become str."""
+    if isinstance(x, NP.void) or isinstance(x, (tuple, list, NP.ndarray)):
+        return tuple(_key(v) for v in (x.tolist() if isinstance(x, (NP.void, NP.ndarray)) else x))
+    if isinstance(x, bytes):
+        return x.decode()
+    if isinstance(x, NP.generic):
+        return x.item()
+    return x
+
+
+def find_list_in_list(reference_array, inp):
+    """READING of NMO.find_list_in_list: for every element of `inp` (the rows of a structured array, the items of a list) the index of
+    its FIRST equal element in `reference_array`.  Returns a masked int64 array of inp's length; the mask marks the elements that are
+    not in the reference (their data is -1).  Strings and bytes compare by text; records compare field by field."""
+    if not isinstance(reference_array, (list, tuple, NP.ndarray)):
+        raise TypeError('reference_array must be a list or numpy array')
+    if not isinstance(inp, (list, tuple, NP.ndarray)):
+        raise TypeError('inp must be a list or numpy array')
+    first = {}
+    for i, x in enumerate(reference_array):
+        first.setdefault(_key(x), i)
+    ind = NP.asarray([first.get(_key(x), -1) for x in inp], dtype=NP.int64).reshape(-1)
+    return NP.ma.masked_array(ind, mask=ind < 0)

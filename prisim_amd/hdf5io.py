@@ -29,6 +29,7 @@ H5T_INTEGER, H5T_FLOAT, H5T_STRING, H5T_COMPOUND = 0, 1, 3, 6
 H5T_VARIABLE = C.c_size_t(-1).value
 H5T_CSET_UTF8 = 1
 H5T_STR_NULLPAD = 1
+H5Z_FILTER_DEFLATE = 1
 
 
 class HDF5Unavailable(RuntimeError):
@@ -84,6 +85,9 @@ def _declare(lib):
         'H5Lexists': (i, [hid_t, cs, hid_t]), 'H5Eset_auto2': (i, [hid_t, p, p]),
         'H5Gopen2': (hid_t, [hid_t, cs, hid_t]), 'H5Gget_info': (i, [hid_t, p]),
         'H5Lget_name_by_idx': (C.c_ssize_t, [hid_t, cs, i, i, hsize_t, p, sz, hid_t]),
+        'H5Pcreate': (hid_t, [hid_t]), 'H5Pclose': (i, [hid_t]), 'H5Pset_chunk': (i, [hid_t, i, C.POINTER(hsize_t)]),
+        'H5Pset_deflate': (i, [hid_t, C.c_uint]), 'H5Zfilter_avail': (i, [i]), 'H5Dget_create_plist': (hid_t, [hid_t]),
+        'H5Pget_nfilters': (i, [hid_t]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -189,6 +193,13 @@ class File(object):
         arr = NP.asarray(value)
         if arr.dtype.kind == 'U':
             arr = NP.char.encode(arr, 'utf-8')
+        if arr.dtype.names and any(arr.dtype[n].kind == 'U' for n in arr.dtype.names):     # text fields -> fixed-length UTF-8 strings
+            enc = {n: NP.char.encode(arr[n], 'utf-8') if arr.dtype[n].kind == 'U' else arr[n] for n in arr.dtype.names}
+            fields = [(n, 'S%d' % max(enc[n].dtype.itemsize, 1) if arr.dtype[n].kind == 'U' else arr.dtype[n]) for n in arr.dtype.names]
+            out = NP.empty(arr.shape, dtype=fields)
+            for n in arr.dtype.names:
+                out[n] = enc[n]
+            arr = out
         if arr.dtype.kind == 'O':
             raise TypeError('object arrays cannot be written')
         if arr.dtype.kind == 'b':
@@ -205,14 +216,36 @@ class File(object):
         dims = (hsize_t * len(shape))(*shape)
         return lib.H5Screate_simple(len(shape), dims, None)
 
-    def write(self, path, value, attrs=None):
+    def deflate_available(self):
+        """Whether this HDF5 library has the gzip (deflate) filter for encoding and decoding."""
+        return self._lib.H5Zfilter_avail(H5Z_FILTER_DEFLATE) > 0
+
+    def write(self, path, value, attrs=None, chunks=None, gzip=None):
+        """chunks: a chunk shape (h5py's create_dataset(chunks=...)); gzip: a deflate level 0-9 (compression='gzip',
+        compression_opts=level), which needs chunks.  Without a deflate filter in the library the dataset is written
+        uncompressed (still chunked) with a warning."""
         lib = self._lib
         parent = '/'.join(path.split('/')[:-1])
         if parent:
             self.create_group(parent)
         buf, tid, owned, shape, keep = self._prepare(value)
+        dcpl = H5P_DEFAULT
+        if chunks is not None or gzip is not None:
+            if shape is None or chunks is None or len(chunks) != len(shape) or any(int(c) < 1 for c in chunks):
+                raise ValueError('a chunked / compressed dataset needs one positive chunk length per axis')
+            dcpl = _check(lib.H5Pcreate(hid_t.in_dll(lib, 'H5P_CLS_DATASET_CREATE_ID_g').value), 'H5Pcreate')
+            cdims = (hsize_t * len(chunks))(*[int(c) for c in chunks])
+            _check(lib.H5Pset_chunk(dcpl, len(chunks), cdims), 'H5Pset_chunk ' + path)
+            if gzip is not None:
+                if self.deflate_available():
+                    _check(lib.H5Pset_deflate(dcpl, int(min(max(int(gzip), 0), 9))), 'H5Pset_deflate ' + path)
+                else:
+                    import warnings
+                    warnings.warn('the HDF5 library has no deflate filter: {0} is written uncompressed'.format(path))
         sid = self._space(shape)
-        did = lib.H5Dcreate2(self._fid, path.encode(), tid, sid, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT)
+        did = lib.H5Dcreate2(self._fid, path.encode(), tid, sid, H5P_DEFAULT, dcpl, H5P_DEFAULT)
+        if dcpl != H5P_DEFAULT:
+            lib.H5Pclose(dcpl)
         if did < 0:
             raise IOError('cannot create dataset ' + path)
         try:
@@ -311,6 +344,20 @@ class File(object):
         finally:
             lib.H5Tclose(tid)
             lib.H5Aclose(aid)
+            lib.H5Dclose(did)
+
+    def nfilters(self, path):
+        """Number of filters (compression ...) in the pipeline of a dataset."""
+        lib = self._lib
+        did = lib.H5Dopen2(self._fid, path.encode(), H5P_DEFAULT)
+        if did < 0:
+            raise KeyError(path)
+        try:
+            pid = _check(lib.H5Dget_create_plist(did), 'H5Dget_create_plist ' + path)
+            n = lib.H5Pget_nfilters(pid)
+            lib.H5Pclose(pid)
+            return int(n)
+        finally:
             lib.H5Dclose(did)
 
     def exists(self, path):

@@ -38,6 +38,7 @@ from . import _abi
 from . import baseline_delay_horizon as DLY
 from . import frames as FRAMES
 from . import geometry as GEOM
+from .gains import GainInfo, extract_gains, read_gaintable  # noqa: F401  (the reference's names in prisim.interferometry)
 from . import primary_beams as PB
 
 C_LIGHT = 299792458.0
@@ -354,8 +355,8 @@ class InterferometerArray(object):
             except (IOError, OSError) as exc:
                 warnings.warn('\tinit_file provided but could not open the initialization file ({0}). Attempting to initialize '
                               'with input parameters...'.format(exc))
-        if gaininfo is not None:
-            raise NotImplementedError('gaininfo (instrument gains) is outside the sky-sum path')
+        if gaininfo is not None and not isinstance(gaininfo, GainInfo):                 # :5773-5777
+            raise TypeError('Input gaininfo must be an instance of class GainInfo')
 
         self.baselines = NP.asarray(baselines, dtype=NP.float64)                      # :5668-5682
         if self.baselines.ndim == 1:
@@ -408,7 +409,8 @@ class InterferometerArray(object):
         self.vis_noise_freq = None
         self.gradient_mode = None
         self.gradient = {}
-        self.gaininfo = None
+        self.gaininfo = gaininfo
+        self.gain_padding = None      # bool (nbl,): rows that get unity gains whatever the table holds (the padding rows of a shard)
 
         ch = NP.asarray(channels, dtype=NP.float64).ravel()                           # :5779-5788
         if (freq_scale is None) or (freq_scale in ('Hz', 'hz')):
@@ -566,7 +568,9 @@ class InterferometerArray(object):
             if f.exists('gradients/baseline'):
                 self.gradient_mode = 'baseline'
                 self.gradient = {'baseline': f.read('gradients/baseline')}
-        self.gaininfo = None
+            gainsfile = get('gaininfo/gainsfile')                                      # :5387-5389
+        self.gaininfo = None if gainsfile is None else GainInfo(init_file=text(gainsfile))
+        self.gain_padding = None
         self.blgroups = None
         self.bl_reversemap = None
         self.lag_kernel = None
@@ -1629,12 +1633,89 @@ class InterferometerArray(object):
         self.noise_seed = seed
 
     def add_noise(self):
-        """vis_freq = gains * skyvis_freq + vis_noise_freq with unity gains (interferometry.py:6697-6722; gain tables are out of scope)."""
+        """vis_freq = gains * skyvis_freq + vis_noise_freq (interferometry.py:6697-6722).  With a GainInfo the gains come from
+        spline_gains at (channels, timestamps); on IndexError from spline_gains at timestamps - timestamps[0]; on IndexError again
+        from nearest_gains; if that fails too, unity gains with a warning.  The gains are applied on the device from their per-kind
+        tables (prisim_amd/gains.py) -- no gain cube is formed.  The sky is the device-resident cube when it is in step with
+        skyvis_freq, otherwise skyvis_freq itself; the noise is vis_noise_freq as it stands."""
         if self.vis_noise_freq is None:
             raise ValueError('generate_noise() must be called first')
-        if self.gaininfo is None:
+        plan = None
+        if self.gaininfo is not None:
+            labels = self.gain_labels()[self._gain_rows()]
+            times = NP.asarray(self.timestamp)
+            try:
+                plan = self.gaininfo.spline_plan(labels, freqs=self.channels, times=times)
+            except IndexError:
+                try:
+                    plan = self.gaininfo.spline_plan(labels, freqs=self.channels, times=times - self.timestamp[0])
+                except IndexError:
+                    try:
+                        plan = self.gaininfo.nearest_plan(labels, freqs=self.channels, times=times)
+                    except Exception:
+                        warnings.warn('Interpolation and nearest neighbour logic failed. Proceeding with default unity gains')
+        else:
             warnings.warn('Gain table absent. Proceeding with default unity gains')
-        self.vis_freq = self.skyvis_freq + self.vis_noise_freq
+        if plan is None:
+            self.vis_freq = self.skyvis_freq + self.vis_noise_freq
+            return
+        self.vis_freq = self._apply_gains(plan)
+
+    def gain_labels(self):
+        """The baselines' labels as the reference's gain methods take them: a structured array with fields 'A2', 'A1' (from (A2, A1)
+        tuples, such a structured array, or the driver's '{prefix}{A2}-{prefix}{A1}' strings).  Rows marked in gain_padding get an
+        empty label: they take no part in the gain evaluation."""
+        from .gains import bl_label_array
+        keep = self._gain_rows()
+        labels = bl_label_array([self.labels[i] if keep[i] else ('', '') for i in range(len(self.labels))])
+        return labels
+
+    def _gain_rows(self):
+        """bool (nbl,): the rows whose gains come from the gain table (every row but those of gain_padding)."""
+        nbl = self.baselines.shape[0]
+        if self.gain_padding is None:
+            return NP.ones(nbl, dtype=bool)
+        pad = NP.asarray(self.gain_padding, dtype=bool).ravel()
+        if pad.size != nbl:
+            raise ValueError('gain_padding must have one entry per baseline')
+        return ~pad
+
+    def _apply_gains(self, plan):
+        """gains * skyvis_freq + vis_noise_freq on the device for a GainPlan, with numpy's broadcasting of the three shapes."""
+        nbl, nchan, nt = self.baselines.shape[0], self.channels.size, len(self.timestamp)
+        keep = self._gain_rows()
+        nval = int(NP.sum(keep))
+        gshape = tuple(plan.shape[p] for p in plan.perm)
+        noise = NP.asarray(self.vis_noise_freq)
+        out_shape = tuple(int(n) for n in NP.broadcast_shapes(gshape, (nval, nchan, nt), noise[keep].shape))   # numpy's ValueError
+        if out_shape != (nval, nchan, nt) or noise.shape != (nbl, nchan, nt) or (plan.perm != [0, 1, 2] and gshape != (1, 1, 1)):
+            raise NotImplementedError('gains of shape {0} (axes {1}) against visibilities {2} and noise {3}: only gains that broadcast '
+                                      'along (label, frequency, time) are applied'.format(gshape, plan.perm, (nbl, nchan, nt), noise.shape))
+        cube = getattr(self, '_cube', None) or []
+        resident = bool(getattr(self, '_device_in_step', False)) and len(cube) == nt and \
+            all(isinstance(sn, _DeviceSlot) and sn.slot == i for i, sn in enumerate(cube))
+        sky, c64 = None, False
+        if resident:
+            c64 = any(sn.dtype == NP.complex64 for sn in cube)
+            if not all((sn.dtype == NP.complex64) == c64 for sn in cube):
+                resident = False
+        if not resident:
+            sky = NP.ascontiguousarray(NP.moveaxis(NP.asarray(self.skyvis_freq), 2, 0), dtype=NP.complex128)     # complex64 promoted
+            c64 = False
+        noise_tbf = NP.ascontiguousarray(NP.moveaxis(noise, 2, 0), dtype=NP.complex128)
+        facs, tabs = plan.device_factors(self._ctx, nval)
+        full = []
+        for tab, mode, a, c in facs:                  # rows of gain_padding: row -1, unity gains
+            fa, fc = NP.full(nbl, -1, dtype=NP.int64), NP.zeros(nbl, dtype=NP.int64)
+            fa[keep], fc[keep] = a, c
+            full.append((tab, mode, fa, fc))
+        try:
+            vis, _ = self._ctx.gains_apply(nt, nbl, nchan, fa=full[0] if full else None, fb=full[1] if len(full) > 1 else None,
+                                           sky=sky, t0=0, sky_c64=c64, noise=noise_tbf)
+        finally:
+            for tab in tabs:
+                tab.close()
+        return NP.ascontiguousarray(NP.moveaxis(vis, 0, 2))
 
     # ------------------------------------------------------------------------------------------
     def _pc_dircos(self, pc, coords):
@@ -1992,6 +2073,9 @@ class InterferometerArray(object):
             if self.gradient_mode is not None:
                 for key, arr in self.gradient.items():
                     f.write('gradients/' + str(key), arr)
+            if self.gaininfo is not None:                                                       # :8843-8846
+                f.write('gaininfo/gainsfile', outfile + '.gains.hdf5')
+                self.gaininfo.write_gaintable(outfile + '.gains.hdf5')
             if self.blgroups is not None:
                 f.create_group('blgroupinfo/groups')
                 f.create_group('blgroupinfo/reversemap')
