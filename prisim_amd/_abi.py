@@ -51,6 +51,14 @@ PRISIM_SUBBAND_OVER, PRISIM_SUBBAND_OVER_POWER, PRISIM_SUBBAND_RES, PRISIM_SUBBA
 PRISIM_SUBBAND_AUTO, PRISIM_SUBBAND_FUSED, PRISIM_SUBBAND_ROCFFT = -1, 0, 1
 SUBBAND_ROUTES = {PRISIM_SUBBAND_FUSED: 'fused', PRISIM_SUBBAND_ROCFFT: 'rocfft'}
 
+# every symbol include/prisim_runs.h declares: delay spectra and power spectra of runs (prisim_amd/csrc_runs/), linked into the same library
+RUNS_EXPORTS = ('prisim_runs_transform', 'prisim_runs_power')
+PRISIM_RUNS_MAX_LEN = PRISIM_SUBBAND_MAX_LEN
+PRISIM_RUNS_ALL, PRISIM_RUNS_INTERP, PRISIM_RUNS_RESAMPLE = 1, 2, 3
+PRISIM_RUNS_AUTO, PRISIM_RUNS_FUSED, PRISIM_RUNS_ROCFFT, PRISIM_RUNS_DIRECT = -1, 0, 1, 2
+RUNS_ROUTES = {PRISIM_RUNS_FUSED: 'fused', PRISIM_RUNS_ROCFFT: 'rocfft', PRISIM_RUNS_DIRECT: 'direct'}
+RUNS_BUDGET = 1 << 30               # device bytes one call of the runs entries streams through by default
+
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
                  'prisim_gains_table_free', 'prisim_gains_apply')
@@ -181,6 +189,22 @@ class PrisimSubbandStats(C.Structure):
                 ('lds_bytes', C.c_int32)]
 
 
+class PrisimRunsStats(C.Structure):
+    _fields_ = [('wall_ms', C.c_double), ('pairs', C.c_int64), ('chunks', C.c_int64), ('chunk_pairs', C.c_int64), ('route', C.c_int32),
+                ('streams', C.c_int32), ('tile', C.c_int32), ('lds_bytes', C.c_int32)]
+
+
+def numpy_fuses_complex_product(dtype):
+    """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
+    ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
+    in fp64, (1 + 2^-12)^2 in fp32 -- that the tiny ai bi breaks only when the sum is fused)."""
+    dtype = NP.dtype(dtype)
+    e1, e2, g = (2.0 ** -26, 2.0 ** -27, 2.0 ** -60) if dtype == NP.complex128 else (2.0 ** -12, 2.0 ** -12, 2.0 ** -30)
+    a = NP.full(64, complex(1.0 + e1, g), dtype=dtype)
+    b = NP.full(64, complex(1.0 + e2, g), dtype=dtype)
+    return bool(NP.all((a * b.conj()).real != (a.real * b.real + a.imag * b.imag)))
+
+
 class PrisimGainsStats(C.Structure):
     _fields_ = [('device_ms', C.c_double), ('kernel_ms', C.c_double), ('elements', C.c_int64)]
 
@@ -271,6 +295,11 @@ def load_library():
     lib.prisim_subband_transform.argtypes = [vp, C.c_int32, i64, i64, i64, vp, i64, vp, i64, C.c_int32, vp, i64, dbl, i64, i64, vp, vp, vp,
                                              vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.POINTER(PrisimSubbandStats)]
     lib.prisim_subband_transform.restype = C.c_int
+    lib.prisim_runs_transform.argtypes = [vp, i64, i64, i64, i64, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, i64, dbl, C.c_int32, i64,
+                                          dbl, i64, vp, vp, vp, C.c_int32, i64, vp, C.POINTER(PrisimRunsStats)]
+    lib.prisim_runs_power.argtypes = [vp, i64, i64, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, i64, vp, C.POINTER(PrisimRunsStats)]
+    for name in RUNS_EXPORTS:
+        getattr(lib, name).restype = C.c_int
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
                                              C.POINTER(vp), pst]
@@ -874,6 +903,93 @@ class Context(object):
     def _subband_stats(st):
         return {'device_ms': st.device_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows), 'route': SUBBAND_ROUTES.get(st.route, st.route),
                 'lds_bytes': int(st.lds_bytes)}
+
+    # ---- delay spectra and power spectra of runs (include/prisim_runs.h) ----
+    def runs_transform(self, vis, nbl, nchan, nt, bp=None, wts=None, win=None, m=None, scale=1.0, mode='all', nout=None, factor=1.0,
+                       route='auto', budget_bytes=RUNS_BUDGET):
+        """Delay spectra of a stack of runs on the device (prisim_runs_transform).  vis: (R, nbl, nchan, nt) complex128 or complex64 on
+        the host (any leading shape whose product is R; not copied when C-contiguous), or None for unit visibilities (R = 1, the lag
+        kernel); bp, wts: None or float64 arrays broadcastable to (nbl, nchan, nt), passed with their broadcast strides (nothing dense
+        is formed); win: None or (nwin, nchan) windows.  spectrum = scale fftshift(ifft(((vis bp) wts) win, m)); mode 'all' (m lags),
+        'interp' (nout positions j * factor, linearly interpolated) or 'resample' (scipy.signal.resample to nout lags).  The call is
+        streamed in chunks of (run, baseline) pairs within budget_bytes of device memory.  Returns (out (nwin, R, nbl, nout, nt)
+        complex128, stats)."""
+        nbl, nchan, nt = int(nbl), int(nchan), int(nt)
+        m = nchan if m is None else int(m)
+        if vis is None:
+            x, R, c64 = None, 1, 0
+        else:
+            x = NP.asarray(vis)
+            if x.dtype not in (NP.complex128, NP.complex64):
+                x = x.astype(NP.complex128)
+            x = NP.ascontiguousarray(x)
+            if x.ndim < 3 or x.shape[-3:] != (nbl, nchan, nt):
+                raise ValueError('vis must be (..., nbl, nchan, nt) = (..., %d, %d, %d)' % (nbl, nchan, nt))
+            R, c64 = int(NP.prod(x.shape[:-3], dtype=NP.int64)), int(x.dtype == NP.complex64)
+        weights = []
+        for w in (bp, wts):                     # the broadcast view's strides over the contiguous array's own memory (0: broadcast)
+            if w is None:
+                weights.append((None, None))
+                continue
+            src = NP.ascontiguousarray(w, dtype=NP.float64)
+            if src.ndim > 3:
+                raise ValueError('weights broadcast over (nbl, nchan, nt) only')
+            view = NP.broadcast_to(src, (nbl, nchan, nt))
+            weights.append((src, NP.array([s // 8 for s in view.strides], dtype=NP.int64)))
+        if win is not None:
+            wn = NP.ascontiguousarray(win, dtype=NP.float64).reshape(-1, nchan)
+            nwin = wn.shape[0]
+        else:
+            wn, nwin = None, 1
+        modes = {'all': PRISIM_RUNS_ALL, 'interp': PRISIM_RUNS_INTERP, 'resample': PRISIM_RUNS_RESAMPLE}
+        md = modes[mode]
+        nout = m if md == PRISIM_RUNS_ALL else int(nout)
+        mo = mi = mw = None
+        if md == PRISIM_RUNS_RESAMPLE and 1 <= nout <= PRISIM_RUNS_MAX_LEN and 1 <= m <= PRISIM_RUNS_MAX_LEN:
+            mo, mi, mw = (NP.ascontiguousarray(a) for a in dsp_readings.resample_map(m, nout))    # the one reading of the resampling
+        out = NP.empty((nwin, R, nbl, max(nout, 1), nt), dtype=NP.complex128)
+        st = PrisimRunsStats()
+        r = {'auto': PRISIM_RUNS_AUTO, 'fused': PRISIM_RUNS_FUSED, 'rocfft': PRISIM_RUNS_ROCFFT}[route]
+        (bpa, bps), (wa, wss) = weights
+        self._check(self._lib.prisim_runs_transform(self._h, R, nbl, nchan, nt, _ptr(x), c64, _ptr(bpa), _ptr(bps), _ptr(wa), _ptr(wss),
+                                                    nwin, _ptr(wn), m, float(scale), md, nout, float(factor),
+                                                    0 if mo is None else mo.size, _ptr(mo), _ptr(mi), _ptr(mw), r, int(budget_bytes),
+                                                    _ptr(out), C.byref(st)), 'prisim_runs_transform')
+        return out, self._runs_stats(st)
+
+    def runs_power(self, vislag1, vislag2=None, factor=1.0, cross=False, budget_bytes=RUNS_BUDGET):
+        """(vislag1 * vislag2.conj() * factor).real (* 2 when cross) on the device (prisim_runs_power), rounded as numpy rounds it on
+        this host.  vislag1 / vislag2: same-shape complex128 or complex64 host arrays (vislag2 None: vislag1); factor: a scalar or one
+        value per index of the leading axis.  Returns (power float64 of vislag1's shape, stats)."""
+        v1 = NP.asarray(vislag1)
+        dt = NP.result_type(v1, NP.asarray(vislag2) if vislag2 is not None else v1)
+        if dt not in (NP.complex128, NP.complex64):
+            dt = NP.complex128
+        v1 = NP.ascontiguousarray(v1, dtype=dt)
+        v2 = None if vislag2 is None else NP.ascontiguousarray(vislag2, dtype=dt)
+        if v2 is not None and v2.shape != v1.shape:
+            raise ValueError('vislag1 and vislag2 must have the same shape')
+        f = NP.ascontiguousarray(NP.asarray(factor, dtype=NP.float64).ravel())
+        n = int(v1.size)
+        if f.size == 1:
+            nf, inner = 1, max(n, 1)
+        elif v1.ndim >= 1 and f.size == v1.shape[0]:
+            nf, inner = f.size, max(n // max(f.size, 1), 1)
+        else:
+            raise ValueError('factor must be a scalar or have one value per index of the leading axis')
+        out = NP.empty(v1.shape, dtype=NP.float64)
+        st = PrisimRunsStats()
+        if n == 0:
+            return out, self._runs_stats(st)
+        self._check(self._lib.prisim_runs_power(self._h, nf, inner, _ptr(v1), _ptr(v2), int(dt == NP.complex64), _ptr(f), int(bool(cross)),
+                                                int(numpy_fuses_complex_product(dt)), int(budget_bytes), _ptr(out), C.byref(st)),
+                    'prisim_runs_power')
+        return out, self._runs_stats(st)
+
+    @staticmethod
+    def _runs_stats(st):
+        return {'wall_ms': st.wall_ms, 'pairs': int(st.pairs), 'chunks': int(st.chunks), 'chunk_pairs': int(st.chunk_pairs),
+                'route': RUNS_ROUTES.get(st.route, st.route), 'streams': int(st.streams), 'tile': int(st.tile), 'lds_bytes': int(st.lds_bytes)}
 
     # ---- instrument gain tables (include/prisim_gains.h) ----
     @staticmethod

@@ -1,0 +1,590 @@
+// runs.hip -- delay spectra and delay power spectra of stacks of runs for gfx950 (include/prisim_runs.h):
+// prisim/delay_spectrum.py:delay_transform_allruns (:1475-1618), subband_delay_transform_allruns (:2252-2513) and the product of
+// compute_power_spectrum_allruns (:4067-4195), on the caller's arrays in the reference's layout.
+//
+// A row is one (run, baseline, snapshot): channel n of row (p, t) sits at vis[(p nchan + n) nt + t], p = run * nbl + baseline.  Every
+// kernel maps consecutive lanes to consecutive snapshots of one channel, so that the [nchan][nt] block of a pair is read, and the
+// [nout][nt] block of the spectra written, in contiguous runs of nt elements.
+//
+// Fused route (m a power of two): one workgroup per (pair, window, tile of TT snapshots).  The tile's windowed rows x[n] times
+// (scale / m) (-1)^n are loaded bit-reversed into LDS (with even m, scale fftshift(ifft(x))[j] = (scale / m) sum_n x[n] (-1)^n
+// e^{+2 pi i j n / m}), a radix-2 in-place transform with an LDS twiddle table gives the shifted spectra in natural order, and the
+// selected lags are written.
+// rocFFT route (any other m): k_runs_prepare writes the windowed padded rows [w][pair][t][m] -> batched inverse rocFFT in place ->
+// k_runs_finish shifts, scales, selects and writes [w][pair][j][t].
+// Resampling (out_mode PRISIM_RUNS_RESAMPLE, any m): k_runs_resample forms scipy.signal.resample's spectrum Y[k] (at most two weighted
+// bins of x per output bin) in LDS and sums y[q] = sum_k Y[k] e^{+2 pi i k q / nout} over the bins that the window can make nonzero;
+// the m-lag spectra never exist.
+// The power kernel forms Re(v1 conj(v2)) * factor (* 2) as numpy rounds it.
+// Chunks of pairs are spread over two streams with their own buffers: the copies of one chunk overlap the kernels of the other.
+// fp64 throughout (complex64 input is widened on load), built with -ffp-contract=off; the one fused product is an explicit fma().
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../csrc/ctx_internal.h"
+#include "../../include/prisim_runs.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxStreams = 2;
+constexpr int kMaxTile = 64;
+constexpr int kTileLds = 65536;                       // LDS the snapshot tile may fill (the fused kernel of m = 4096 takes 96 KiB)
+constexpr int64_t kDefaultBudget = int64_t(1) << 30;  // device bytes of a call when the caller gives none
+
+__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ double2 rmul(double2 a, double s) { return make_double2(a.x * s, a.y * s); }
+
+struct RunParams {
+  const void* vis;          // this chunk's [pc][nchan][nt] (complex128 or complex64), or null: ones
+  int c64;
+  const double* bp;         // weights over (baseline, channel, snapshot), or null
+  int64_t bs0, bs1, bs2;
+  const double* wts;
+  int64_t ws0, ws1, ws2;
+  const double* win;        // [nwin][nchan], or null
+  int nwin, nchan, nt, m, logm, nout, mode, tile, ntiles;
+  int64_t nbl, p0, pc;      // first global pair of the chunk, pairs in the chunk
+  double s;                 // scale / m
+  double factor;            // PRISIM_RUNS_INTERP: lag position step
+  const int32_t* rs_in;     // [2][nout] input bins of the resampled spectrum (-1: none)
+  const double2* rs_c;      // [2][nout] their coefficients map_w (scale / m) e^{-2 pi i k_in floor(m/2) / m}
+  const double2* rtw;       // [nout] e^{+2 pi i q / nout}
+  const int32_t* klist;     // bins each window can make nonzero: klist[kofs[w] .. kofs[w + 1])
+  const int32_t* kofs;
+  double2* out;             // this chunk's [nwin][pc][nout][nt]
+  double2* fbuf;            // rocFFT route: [nwin][pc][nt][m]
+};
+
+// x[n] of row (local pair pl, snapshot t) under window w: ((vis * bp) * wts) * win, as numpy multiplies a complex array by real ones
+__device__ __forceinline__ double2 row_value(const RunParams& P, int64_t pl, int n, int t, int w) {
+  double2 v = make_double2(1.0, 0.0);
+  const int64_t i = (pl * P.nchan + n) * (int64_t)P.nt + t;
+  if (P.vis) {
+    if (P.c64) {
+      const float2 f = reinterpret_cast<const float2*>(P.vis)[i];
+      v = make_double2((double)f.x, (double)f.y);
+    } else {
+      v = reinterpret_cast<const double2*>(P.vis)[i];
+    }
+  }
+  const int64_t b = (P.p0 + pl) % P.nbl;
+  if (P.bp) v = rmul(v, P.bp[b * P.bs0 + n * P.bs1 + t * P.bs2]);
+  if (P.wts) v = rmul(v, P.wts[b * P.ws0 + n * P.ws1 + t * P.ws2]);
+  if (P.win) v = rmul(v, P.win[(int64_t)w * P.nchan + n]);
+  return v;
+}
+
+// output lag j of a shifted spectrum row: the lag itself, or dsp_readings.downsampler's linear interpolation at j * factor
+template <typename Get>
+__device__ __forceinline__ double2 select_lag(const RunParams& P, int j, Get get) {
+  if (P.mode != PRISIM_RUNS_INTERP) return get(j);
+  const double pos = (double)j * P.factor;
+  int i0 = (int)floor(pos);
+  const double frac = pos - (double)i0;
+  i0 = min(i0, P.m - 1);
+  const int i1 = min(i0 + 1, P.m - 1);
+  const double2 x0 = get(i0), x1 = get(i1);
+  return cadd(x0, rmul(csub(x1, x0), frac));
+}
+
+// fused route.  LDS: buf [tile][m] | tw [m/2]
+__global__ void __launch_bounds__(kThreads) k_runs_fused(RunParams P) {
+  extern __shared__ double2 lds[];
+  const int m = P.m, tile = P.tile;
+  double2* buf = lds;
+  double2* tw = buf + (int64_t)tile * m;
+  const int64_t pl = blockIdx.x / P.ntiles;
+  const int t0 = (int)(blockIdx.x % P.ntiles) * tile;
+  const int w = blockIdx.y;
+  const int tcount = min(tile, P.nt - t0);
+  for (int k = threadIdx.x; k < m / 2; k += kThreads) {
+    double sn, cs;
+    sincospi(2.0 * (double)k / (double)m, &sn, &cs);
+    tw[k] = make_double2(cs, sn);
+  }
+  for (int e = threadIdx.x; e < m * tile; e += kThreads) {
+    const int n = e / tile, tt = e - n * tile;
+    const int j = P.logm ? (int)(__brev((unsigned)n) >> (32 - P.logm)) : 0;
+    double2 v = make_double2(0.0, 0.0);
+    if (n < P.nchan && tt < tcount) v = rmul(row_value(P, pl, n, t0 + tt, w), (m > 1 && (n & 1)) ? -P.s : P.s);
+    buf[tt * m + j] = v;
+  }
+  __syncthreads();
+  const int half = m / 2;
+  for (int h = 1; h < m; h <<= 1) {               // butterflies of span 2h; twiddle W_{2h}^pos = tw[pos * m / (2h)]
+    const int step = m / (2 * h);
+    for (int i = threadIdx.x; i < tile * half; i += kThreads) {
+      const int tt = i / half, ii = i - tt * half;
+      const int pos = ii & (h - 1);
+      const int a = tt * m + ((ii - pos) << 1) + pos, b = a + h;
+      const double2 u = buf[a], v = cmul(buf[b], tw[pos * step]);
+      buf[a] = cadd(u, v);
+      buf[b] = csub(u, v);
+    }
+    __syncthreads();
+  }
+  double2* dst = P.out + ((int64_t)w * P.pc + pl) * P.nout * P.nt + t0;
+  for (int e = threadIdx.x; e < P.nout * tile; e += kThreads) {
+    const int j = e / tile, tt = e - j * tile;
+    if (tt >= tcount) continue;
+    const double2* row = buf + tt * m;
+    dst[(int64_t)j * P.nt + tt] = select_lag(P, j, [&](int i) { return row[i]; });
+  }
+}
+
+// rocFFT route, before the transform: fbuf[w][pl][t][n] = x[n] (zero for n >= nchan)
+__global__ void __launch_bounds__(kThreads) k_runs_prepare(RunParams P) {
+  const int64_t total = (int64_t)P.nwin * P.pc * P.nt * P.m;
+  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
+    const int n = (int)(e % P.m);
+    const int64_t line = e / P.m;
+    const int t = (int)(line % P.nt);
+    const int64_t wp = line / P.nt;
+    const int64_t pl = wp % P.pc;
+    const int w = (int)(wp / P.pc);
+    P.fbuf[e] = n < P.nchan ? row_value(P, pl, n, t, w) : make_double2(0.0, 0.0);
+  }
+}
+
+// rocFFT route, after the unnormalised inverse transform F: spectrum[i] = (scale / m) F[(i - floor(m/2)) mod m], then the selection
+__global__ void __launch_bounds__(kThreads) k_runs_finish(RunParams P) {
+  const int m = P.m, half = m / 2;
+  const int64_t total = (int64_t)P.nwin * P.pc * P.nout * P.nt;
+  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
+    const int t = (int)(e % P.nt);
+    const int64_t r = e / P.nt;
+    const int j = (int)(r % P.nout);
+    const int64_t wp = r / P.nout;
+    const double2* row = P.fbuf + (wp * P.nt + t) * m;
+    P.out[e] = select_lag(P, j, [&](int i) { return rmul(row[(i + m - half) % m], P.s); });
+  }
+}
+
+// resampling.  LDS: z [nout][tile]
+__global__ void __launch_bounds__(kThreads) k_runs_resample(RunParams P) {
+  extern __shared__ double2 lds[];
+  const int nout = P.nout, tile = P.tile;
+  double2* z = lds;
+  const int64_t pl = blockIdx.x / P.ntiles;
+  const int t0 = (int)(blockIdx.x % P.ntiles) * tile;
+  const int w = blockIdx.y;
+  const int tcount = min(tile, P.nt - t0);
+  for (int e = threadIdx.x; e < nout * tile; e += kThreads) {
+    const int k = e / tile, tt = e - k * tile;
+    double2 v = make_double2(0.0, 0.0);
+    if (tt < tcount) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int i = P.rs_in[s * nout + k];
+        if (i >= 0) v = cadd(v, cmul(row_value(P, pl, i, t0 + tt, w), P.rs_c[s * nout + k]));
+      }
+    }
+    z[e] = v;
+  }
+  __syncthreads();
+  const int32_t* kl = P.klist + P.kofs[w];
+  const int nk = P.kofs[w + 1] - P.kofs[w];
+  double2* dst = P.out + ((int64_t)w * P.pc + pl) * nout * P.nt + t0;
+  for (int e = threadIdx.x; e < nout * tile; e += kThreads) {
+    const int q = e / tile, tt = e - q * tile;
+    double2 acc = make_double2(0.0, 0.0);
+    for (int i = 0; i < nk; ++i) {
+      const int k = kl[i];
+      acc = cadd(acc, cmul(z[k * tile + tt], P.rtw[(int)(((int64_t)k * q) % nout)]));
+    }
+    if (tt < tcount) dst[(int64_t)q * P.nt + tt] = acc;
+  }
+}
+
+__device__ __forceinline__ float fmaf_or_fma(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ double fmaf_or_fma(double a, double b, double c) { return fma(a, b, c); }
+
+// power: out[e] = Re(a conj(b)) * factor[(e0 + e) / inner] (* 2).  numpy's complex product a * conj(b) has the real part
+// ar br - ai (-bi); its SIMD loop fuses that into fma(ar, br, ai bi).  The complex64 product is rounded in fp32 and then widened.
+template <typename T>
+__global__ void __launch_bounds__(kThreads) k_runs_power(const T* a, const T* b, const double* factor, int64_t e0, int64_t n, int64_t inner,
+                                                         int cross, int fused, double* out) {
+  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < n; e += (int64_t)gridDim.x * kThreads) {
+    const T x = a[e], y = b[e];
+    double p;
+    if (fused) p = (double)fmaf_or_fma(x.x, y.x, x.y * y.y);
+    else p = (double)(x.x * y.x + x.y * y.y);
+    double v = p * factor[(e0 + e) / inner];
+    if (cross) v = v * 2.0;
+    out[e] = v;
+  }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+
+struct Dev {
+  std::vector<void*> ptrs;
+  ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
+};
+
+#define RUNS_ALLOC(ctx, dev, ptr, bytes)                                                               \
+  do {                                                                                                 \
+    void* p_ = nullptr;                                                                                \
+    HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
+    (dev).ptrs.push_back(p_);                                                                          \
+    (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
+  } while (0)
+
+// the call's streams: drained before the buffers they use are freed (declared after Dev, destroyed before it)
+struct Streams {
+  hipStream_t s[kMaxStreams] = {};
+  int n = 0;
+  ~Streams() {
+    for (int i = 0; i < n; ++i) {
+      (void)hipStreamSynchronize(s[i]);
+      (void)hipStreamDestroy(s[i]);
+    }
+  }
+};
+
+struct FftPlans {
+  std::map<size_t, rocfft_plan> plans;              // by batch
+  rocfft_execution_info info[kMaxStreams] = {};
+  ~FftPlans() {
+    for (auto& kv : plans) g_rocfft.plan_destroy(kv.second);
+    for (rocfft_execution_info i : info) if (i) g_rocfft.execution_info_destroy(i);
+  }
+};
+
+// elements a strided weight array spans (strides >= 0)
+int64_t span_of(const int64_t* st, int64_t nbl, int64_t nchan, int64_t nt) {
+  return (nbl - 1) * st[0] + (nchan - 1) * st[1] + (nt - 1) * st[2] + 1;
+}
+
+int64_t budget_or_default(int64_t budget) { return budget > 0 ? budget : kDefaultBudget; }
+
+int grid_for(const prisim_ctx* ctx, int64_t n) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)std::max(ctx->cu_count, 1) * 16));
+}
+
+}  // namespace
+
+extern "C" {
+
+int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan, int64_t nt, const void* vis, int32_t vis_is_c64,
+                          const double* bp, const int64_t* bp_strides, const double* wts, const int64_t* wts_strides, int32_t nwin,
+                          const double* win, int64_t m, double scale, int32_t out_mode, int64_t nout, double factor, int64_t nmap,
+                          const int64_t* map_out, const int64_t* map_in, const double* map_w, int32_t route, int64_t budget_bytes,
+                          double* out, prisim_runs_stats* stats) {
+  return guarded(ctx, [&]() -> int {
+  if (!ctx) return PRISIM_EINVAL;
+  const auto wall0 = std::chrono::steady_clock::now();
+  if (m < 1 || m > PRISIM_RUNS_MAX_LEN)
+    return fail(ctx, PRISIM_EINVAL, "delay spectra of runs take 1 to " + std::to_string(PRISIM_RUNS_MAX_LEN) +
+                                        " lags (PRISIM_SUBBAND_MAX_LEN); got m = " + std::to_string(m));
+  if (out_mode < PRISIM_RUNS_ALL || out_mode > PRISIM_RUNS_RESAMPLE) return fail(ctx, PRISIM_EINVAL, "unknown out_mode");
+  if (out_mode == PRISIM_RUNS_ALL && nout != m) return fail(ctx, PRISIM_EINVAL, "out_mode PRISIM_RUNS_ALL writes nout == m lags");
+  if (nout < 1 || nout > PRISIM_RUNS_MAX_LEN)
+    return fail(ctx, PRISIM_EINVAL, "delay spectra of runs write 1 to " + std::to_string(PRISIM_RUNS_MAX_LEN) +
+                                        " lags (PRISIM_SUBBAND_MAX_LEN); got nout = " + std::to_string(nout));
+  if (out_mode == PRISIM_RUNS_INTERP && !(factor > 0.0 && (double)(nout - 1) * factor < (double)m + 1.0))
+    return fail(ctx, PRISIM_EINVAL, "out_mode PRISIM_RUNS_INTERP needs factor > 0 and positions inside the m lags");
+  if (R < 1 || nbl < 1 || nt < 1 || nchan < 1 || nchan > m || nwin < 1 || nwin > 65535 || (!win && nwin != 1))
+    return fail(ctx, PRISIM_EINVAL, "need R, nbl, nt >= 1, 1 <= nchan <= m and 1 <= nwin <= 65535 (nwin == 1 without windows)");
+  if (nt > (int64_t)1 << 30 || nchan > (int64_t)1 << 30) return fail(ctx, PRISIM_EINVAL, "nt and nchan must fit in 32 bits");
+  if (!out || (bp && !bp_strides) || (wts && !wts_strides)) return fail(ctx, PRISIM_EINVAL, "null array");
+  for (int i = 0; i < 3; ++i)
+    if ((bp && bp_strides[i] < 0) || (wts && wts_strides[i] < 0)) return fail(ctx, PRISIM_EINVAL, "weight strides must be >= 0");
+  if (route < PRISIM_RUNS_AUTO || route > PRISIM_RUNS_ROCFFT) return fail(ctx, PRISIM_EINVAL, "unknown route");
+  int logm = 0;
+  while ((int64_t(1) << logm) < m) ++logm;
+  const bool pow2 = (int64_t(1) << logm) == m;
+  const bool resample = out_mode == PRISIM_RUNS_RESAMPLE;
+  if (route == PRISIM_RUNS_FUSED && !pow2 && !resample)
+    return fail(ctx, PRISIM_EINVAL, "the fused route takes power-of-two m; got m = " + std::to_string(m));
+  const int rt = resample ? PRISIM_RUNS_DIRECT : (route == PRISIM_RUNS_ROCFFT || (route == PRISIM_RUNS_AUTO && !pow2))
+                                                    ? PRISIM_RUNS_ROCFFT : PRISIM_RUNS_FUSED;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (rt == PRISIM_RUNS_ROCFFT) {
+    std::string lerr;
+    if (!load_rocfft(lerr)) return fail(ctx, PRISIM_ELIB, lerr);
+    if (!g_rocfft.setup_done) {
+      if (g_rocfft.setup() != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_setup failed");
+      g_rocfft.setup_done = true;
+    }
+  }
+
+  // the resampling tables: per output bin at most two input bins (padding bins dropped), and per window the bins it can make nonzero
+  std::vector<int32_t> rs_in, klist, kofs((size_t)nwin + 1, 0);
+  std::vector<double> rs_c, rtw;
+  const double s = scale / (double)m;
+  if (resample) {
+    if (nmap < 1 || !map_out || !map_in || !map_w) return fail(ctx, PRISIM_EINVAL, "the resampled spectra need the selection map");
+    rs_in.assign(2 * (size_t)nout, -1);
+    rs_c.assign(4 * (size_t)nout, 0.0);
+    rtw.assign(2 * (size_t)nout, 0.0);
+    std::vector<int> used((size_t)nout, 0);
+    const int64_t half = m / 2;
+    for (int64_t e = 0; e < nmap; ++e) {
+      const int64_t k = map_out[e], kin = map_in[e];
+      if (k < 0 || k >= nout || kin < 0 || kin >= m) return fail(ctx, PRISIM_EINVAL, "selection map entry out of range");
+      if (used[(size_t)k] == 2) return fail(ctx, PRISIM_EINVAL, "selection map: more than two entries for one output bin");
+      const int sl = used[(size_t)k]++;
+      if (kin >= nchan) continue;                    // a bin of the zero padding
+      const int64_t red = (kin * half) % m;          // e^{-2 pi i k_in floor(m/2) / m}
+      const double a = -2.0 * M_PI * (double)red / (double)m;
+      const double sc = map_w[e] * s;
+      rs_in[(size_t)sl * nout + k] = (int32_t)kin;
+      rs_c[2 * ((size_t)sl * nout + k)] = sc * std::cos(a);
+      rs_c[2 * ((size_t)sl * nout + k) + 1] = sc * std::sin(a);
+    }
+    for (int64_t q = 0; q < nout; ++q) {
+      const double a = 2.0 * M_PI * (double)q / (double)nout;
+      rtw[2 * q] = std::cos(a);
+      rtw[2 * q + 1] = std::sin(a);
+    }
+    for (int w = 0; w < nwin; ++w) {
+      int64_t lo = 0, hi = nchan;
+      if (win) {
+        lo = nchan;
+        hi = 0;
+        for (int64_t n = 0; n < nchan; ++n)
+          if (win[w * nchan + n] != 0.0) { lo = std::min(lo, n); hi = n + 1; }
+      }
+      for (int64_t k = 0; k < nout; ++k)
+        for (int sl = 0; sl < 2; ++sl) {
+          const int32_t i = rs_in[(size_t)sl * nout + k];
+          if (i >= lo && i < hi) { klist.push_back((int32_t)k); break; }
+        }
+      kofs[(size_t)w + 1] = (int32_t)klist.size();
+    }
+  }
+
+  // snapshot tile, LDS and chunking
+  int lds_max = 0;
+  HIPCHK(ctx, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  const int64_t tw_bytes = 16 * std::max<int64_t>(m / 2, 1);
+  const int64_t row_bytes = 16 * (resample ? nout : m);
+  int64_t tile = 1;
+  if (rt != PRISIM_RUNS_ROCFFT) tile = std::max<int64_t>(1, std::min<int64_t>({nt, (int64_t)kMaxTile, (kTileLds - (resample ? 0 : tw_bytes)) / row_bytes}));
+  const int64_t lds = rt == PRISIM_RUNS_ROCFFT ? 0 : tile * row_bytes + (resample ? 0 : tw_bytes);
+  if (lds > lds_max) return fail(ctx, PRISIM_EINVAL, "rows do not fit in LDS (" + std::to_string(lds) + " B needed)");
+  const int64_t ntiles = (nt + tile - 1) / tile;
+  const int64_t P = R * nbl;
+  const int64_t in_pair = vis ? nchan * nt * (vis_is_c64 ? 8 : 16) : 0;
+  const int64_t out_pair = (int64_t)nwin * nout * nt * 16;
+  const int64_t fbuf_pair = rt == PRISIM_RUNS_ROCFFT ? (int64_t)nwin * nt * m * 16 : 0;
+  const int64_t per_pair = in_pair + out_pair + fbuf_pair;
+  const int64_t budget = budget_or_default(budget_bytes);
+  int64_t pc = std::max<int64_t>(1, std::min<int64_t>(P, budget / (kMaxStreams * per_pair)));
+  pc = std::min<int64_t>(pc, ((int64_t)1 << 31) / std::max<int64_t>(ntiles, 1) - 1);      // grid x of the tiled kernels
+  const int64_t nchunks = (P + pc - 1) / pc;
+  const int nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
+
+  Dev dev;
+  const int64_t bp_n = bp ? span_of(bp_strides, nbl, nchan, nt) : 0, wts_n = wts ? span_of(wts_strides, nbl, nchan, nt) : 0;
+  double *d_bp = nullptr, *d_wts = nullptr, *d_win = nullptr;
+  int32_t *d_rsin = nullptr, *d_klist = nullptr, *d_kofs = nullptr;
+  double2 *d_rsc = nullptr, *d_rtw = nullptr;
+  if (bp) RUNS_ALLOC(ctx, dev, d_bp, bp_n * 8);
+  if (wts) RUNS_ALLOC(ctx, dev, d_wts, wts_n * 8);
+  if (win) RUNS_ALLOC(ctx, dev, d_win, (size_t)nwin * nchan * 8);
+  if (resample) {
+    RUNS_ALLOC(ctx, dev, d_rsin, rs_in.size() * 4);
+    RUNS_ALLOC(ctx, dev, d_rsc, rs_c.size() * 8);
+    RUNS_ALLOC(ctx, dev, d_rtw, rtw.size() * 8);
+    RUNS_ALLOC(ctx, dev, d_klist, std::max<size_t>(klist.size(), 1) * 4);
+    RUNS_ALLOC(ctx, dev, d_kofs, kofs.size() * 4);
+  }
+  void* d_in[kMaxStreams] = {};
+  double2* d_out[kMaxStreams] = {};
+  double2* d_fbuf[kMaxStreams] = {};
+  for (int i = 0; i < nstreams; ++i) {
+    if (vis) RUNS_ALLOC(ctx, dev, d_in[i], pc * in_pair);
+    RUNS_ALLOC(ctx, dev, d_out[i], pc * out_pair);
+    if (fbuf_pair) RUNS_ALLOC(ctx, dev, d_fbuf[i], pc * fbuf_pair);
+  }
+  FftPlans fft;
+  Streams st;
+  for (int i = 0; i < nstreams; ++i) {
+    HIPCHK(ctx, hipStreamCreateWithFlags(&st.s[i], hipStreamNonBlocking));
+    st.n = i + 1;
+  }
+  if (rt == PRISIM_RUNS_ROCFFT) {
+    RocfftApi& F = g_rocfft;
+    size_t wmax = 0;
+    for (int64_t c : {pc, P - (nchunks - 1) * pc}) {
+      const size_t batch = (size_t)nwin * (size_t)c * (size_t)nt;
+      if (fft.plans.count(batch)) continue;
+      size_t len = (size_t)m;
+      rocfft_plan p = nullptr;
+      if (F.plan_create(&p, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, rocfft_precision_double, 1, &len, batch,
+                        nullptr) != rocfft_status_success)
+        return fail(ctx, PRISIM_ELIB, "rocfft_plan_create failed");
+      fft.plans[batch] = p;
+      size_t wb = 0;
+      F.plan_get_work_buffer_size(p, &wb);
+      wmax = std::max(wmax, wb);
+    }
+    for (int i = 0; i < nstreams; ++i) {
+      if (F.execution_info_create(&fft.info[i]) != rocfft_status_success) {
+        fft.info[i] = nullptr;
+        return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_create failed");
+      }
+      if (F.execution_info_set_stream(fft.info[i], st.s[i]) != rocfft_status_success)
+        return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_stream failed");
+      if (wmax) {
+        void* wb;
+        RUNS_ALLOC(ctx, dev, wb, wmax);
+        if (F.execution_info_set_work_buffer(fft.info[i], wb, wmax) != rocfft_status_success)
+          return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_work_buffer failed");
+      }
+    }
+  }
+
+  // the tables on stream 0; stream 1 waits for them
+  hipStream_t s0 = st.s[0];
+  if (bp) HIPCHK(ctx, hipMemcpyAsync(d_bp, bp, bp_n * 8, hipMemcpyHostToDevice, s0));
+  if (wts) HIPCHK(ctx, hipMemcpyAsync(d_wts, wts, wts_n * 8, hipMemcpyHostToDevice, s0));
+  if (win) HIPCHK(ctx, hipMemcpyAsync(d_win, win, (size_t)nwin * nchan * 8, hipMemcpyHostToDevice, s0));
+  if (resample) {
+    HIPCHK(ctx, hipMemcpyAsync(d_rsin, rs_in.data(), rs_in.size() * 4, hipMemcpyHostToDevice, s0));
+    HIPCHK(ctx, hipMemcpyAsync(d_rsc, rs_c.data(), rs_c.size() * 8, hipMemcpyHostToDevice, s0));
+    HIPCHK(ctx, hipMemcpyAsync(d_rtw, rtw.data(), rtw.size() * 8, hipMemcpyHostToDevice, s0));
+    if (!klist.empty()) HIPCHK(ctx, hipMemcpyAsync(d_klist, klist.data(), klist.size() * 4, hipMemcpyHostToDevice, s0));
+    HIPCHK(ctx, hipMemcpyAsync(d_kofs, kofs.data(), kofs.size() * 4, hipMemcpyHostToDevice, s0));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(s0));            // the tables are host vectors of this call and caller memory
+
+  RunParams base;
+  base.vis = nullptr; base.c64 = vis_is_c64 != 0;
+  base.bp = d_bp; base.bs0 = bp ? bp_strides[0] : 0; base.bs1 = bp ? bp_strides[1] : 0; base.bs2 = bp ? bp_strides[2] : 0;
+  base.wts = d_wts; base.ws0 = wts ? wts_strides[0] : 0; base.ws1 = wts ? wts_strides[1] : 0; base.ws2 = wts ? wts_strides[2] : 0;
+  base.win = d_win;
+  base.nwin = nwin; base.nchan = (int)nchan; base.nt = (int)nt; base.m = (int)m; base.logm = logm; base.nout = (int)nout;
+  base.mode = out_mode; base.tile = (int)tile; base.ntiles = (int)ntiles;
+  base.nbl = nbl; base.p0 = 0; base.pc = 0; base.s = s; base.factor = factor;
+  base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw; base.klist = d_klist; base.kofs = d_kofs;
+  base.out = nullptr; base.fbuf = nullptr;
+  if (lds > 65536) {
+    if (rt == PRISIM_RUNS_FUSED) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_runs_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (rt == PRISIM_RUNS_DIRECT) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_runs_resample, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+
+  for (int64_t c = 0; c < nchunks; ++c) {
+    const int i = (int)(c % nstreams);
+    hipStream_t sc = st.s[i];
+    const int64_t p0 = c * pc, pn = std::min(pc, P - p0);
+    RunParams Pm = base;
+    Pm.p0 = p0; Pm.pc = pn; Pm.out = d_out[i]; Pm.fbuf = d_fbuf[i];
+    if (vis) {
+      const size_t off = (size_t)p0 * (size_t)in_pair;
+      HIPCHK(ctx, hipMemcpyAsync(d_in[i], (const char*)vis + off, (size_t)pn * in_pair, hipMemcpyHostToDevice, sc));
+      Pm.vis = d_in[i];
+    }
+    if (rt == PRISIM_RUNS_FUSED) {
+      hipLaunchKernelGGL(k_runs_fused, dim3((unsigned)(pn * ntiles), (unsigned)nwin), dim3(kThreads), (size_t)lds, sc, Pm);
+      HIPCHK(ctx, hipGetLastError());
+    } else if (rt == PRISIM_RUNS_DIRECT) {
+      hipLaunchKernelGGL(k_runs_resample, dim3((unsigned)(pn * ntiles), (unsigned)nwin), dim3(kThreads), (size_t)lds, sc, Pm);
+      HIPCHK(ctx, hipGetLastError());
+    } else {
+      const int64_t nf = (int64_t)nwin * pn * nt * m, no = (int64_t)nwin * pn * nout * nt;
+      hipLaunchKernelGGL(k_runs_prepare, dim3((unsigned)grid_for(ctx, nf)), dim3(kThreads), 0, sc, Pm);
+      HIPCHK(ctx, hipGetLastError());
+      void* b[1] = {d_fbuf[i]};
+      if (g_rocfft.execute(fft.plans.at((size_t)nwin * (size_t)pn * (size_t)nt), b, nullptr, fft.info[i]) != rocfft_status_success)
+        return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
+      hipLaunchKernelGGL(k_runs_finish, dim3((unsigned)grid_for(ctx, no)), dim3(kThreads), 0, sc, Pm);
+      HIPCHK(ctx, hipGetLastError());
+    }
+    const size_t blk = (size_t)pn * nout * nt;      // complex elements of one window's block
+    for (int w = 0; w < nwin; ++w)
+      HIPCHK(ctx, hipMemcpyAsync(out + 2 * (((size_t)w * P + p0) * nout * nt), d_out[i] + (size_t)w * blk, blk * 16,
+                                 hipMemcpyDeviceToHost, sc));
+  }
+  for (int i = 0; i < nstreams; ++i) HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
+  if (stats) {
+    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    stats->pairs = P;
+    stats->chunks = nchunks;
+    stats->chunk_pairs = pc;
+    stats->route = rt;
+    stats->streams = nstreams;
+    stats->tile = (int32_t)tile;
+    stats->lds_bytes = (int32_t)lds;
+  }
+  return PRISIM_OK;
+  });
+}
+
+int prisim_runs_power(prisim_ctx* ctx, int64_t nf, int64_t inner, const void* v1, const void* v2, int32_t is_c64, const double* factor,
+                      int32_t cross, int32_t fused_product, int64_t budget_bytes, double* out, prisim_runs_stats* stats) {
+  return guarded(ctx, [&]() -> int {
+  if (!ctx) return PRISIM_EINVAL;
+  const auto wall0 = std::chrono::steady_clock::now();
+  if (nf < 1 || inner < 1) return fail(ctx, PRISIM_EINVAL, "need nf >= 1 and inner >= 1");
+  if (!v1 || !factor || !out) return fail(ctx, PRISIM_EINVAL, "null array");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int64_t n = nf * inner;
+  const int64_t esz = is_c64 ? 8 : 16;
+  const int64_t per = esz * (v2 ? 2 : 1) + 8;
+  const int64_t budget = budget_or_default(budget_bytes);
+  const int64_t ce = std::max<int64_t>(1, std::min<int64_t>(n, budget / (kMaxStreams * per)));
+  const int64_t nchunks = (n + ce - 1) / ce;
+  const int nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
+  Dev dev;
+  double* d_f;
+  RUNS_ALLOC(ctx, dev, d_f, nf * 8);
+  void* d_a[kMaxStreams] = {};
+  void* d_b[kMaxStreams] = {};
+  double* d_o[kMaxStreams] = {};
+  for (int i = 0; i < nstreams; ++i) {
+    RUNS_ALLOC(ctx, dev, d_a[i], ce * esz);
+    if (v2) RUNS_ALLOC(ctx, dev, d_b[i], ce * esz);
+    RUNS_ALLOC(ctx, dev, d_o[i], ce * 8);
+  }
+  Streams st;
+  for (int i = 0; i < nstreams; ++i) {
+    HIPCHK(ctx, hipStreamCreateWithFlags(&st.s[i], hipStreamNonBlocking));
+    st.n = i + 1;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(d_f, factor, nf * 8, hipMemcpyHostToDevice, st.s[0]));
+  HIPCHK(ctx, hipStreamSynchronize(st.s[0]));
+  for (int64_t c = 0; c < nchunks; ++c) {
+    const int i = (int)(c % nstreams);
+    hipStream_t sc = st.s[i];
+    const int64_t e0 = c * ce, en = std::min(ce, n - e0);
+    HIPCHK(ctx, hipMemcpyAsync(d_a[i], (const char*)v1 + e0 * esz, en * esz, hipMemcpyHostToDevice, sc));
+    if (v2) HIPCHK(ctx, hipMemcpyAsync(d_b[i], (const char*)v2 + e0 * esz, en * esz, hipMemcpyHostToDevice, sc));
+    const void* b = v2 ? d_b[i] : d_a[i];
+    if (is_c64)
+      hipLaunchKernelGGL(k_runs_power<float2>, dim3((unsigned)grid_for(ctx, en)), dim3(kThreads), 0, sc, (const float2*)d_a[i],
+                         (const float2*)b, (const double*)d_f, e0, en, inner, (int)(cross != 0), (int)(fused_product != 0), d_o[i]);
+    else
+      hipLaunchKernelGGL(k_runs_power<double2>, dim3((unsigned)grid_for(ctx, en)), dim3(kThreads), 0, sc, (const double2*)d_a[i],
+                         (const double2*)b, (const double*)d_f, e0, en, inner, (int)(cross != 0), (int)(fused_product != 0), d_o[i]);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out + e0, d_o[i], en * 8, hipMemcpyDeviceToHost, sc));
+  }
+  for (int i = 0; i < nstreams; ++i) HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
+  if (stats) {
+    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    stats->pairs = n;
+    stats->chunks = nchunks;
+    stats->chunk_pairs = ce;
+    stats->route = PRISIM_RUNS_DIRECT;
+    stats->streams = nstreams;
+    stats->tile = 0;
+    stats->lds_bytes = 0;
+  }
+  return PRISIM_OK;
+  });
+}
+
+}  // extern "C"

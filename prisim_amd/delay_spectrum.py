@@ -16,7 +16,11 @@ transforms every window of every (baseline, snapshot) row in one device call (in
 the astroutils functions it calls are read once in prisim_amd/dsp_readings.py.  ``compute_power_spectrum`` fills the sub-band power
 spectra (:4004-4063).
 
-Not here (out of scope): subband_delay_transform_allruns, closure-phase spectra, FITS persistence.
+Stacks of runs: ``delay_transform_allruns`` (:1475-1618), ``subband_delay_transform_allruns`` (:2252-2513) and
+``DelayPowerSpectrum.compute_power_spectrum_allruns`` (:4067-4195) take the caller's (..., nbl, nchan, n_acc) visibilities, whose leading
+axes are runs, and stream them through include/prisim_runs.h (prisim_amd/csrc_runs/) in the reference's layout, with no host transpose.
+
+Not here (out of scope): closure-phase spectra, FITS persistence.
 
 Cosmology.  The reference takes ``astropy.cosmology.Planck15.clone(H0=100)`` (:34-35); astropy is not in this image, so ``cosmo100`` here
 is this module's own flat LambdaCDM with Planck15's Om0 = 0.3075, Tcmb0 = 2.7255 K, Neff = 3.046 (photons + massless neutrinos in the
@@ -705,6 +709,158 @@ class DelaySpectrum(object):
             return result_resampled
 
 
+    # ------------------------------------------------------------------------------------------
+    # stacks of runs: the caller's visibilities (..., nbl, nchan, n_acc), prisim_runs_transform (include/prisim_runs.h)
+    def _check_runs_vis(self, vis):
+        """The vis checks of :1543-1556 / :2393-2406.  Returns vis with at least one leading axis (a view) and (nbl, nchan, nt)."""
+        nbl, nchan, nt = self.ia.baselines.shape[0], self.f.size, self.n_acc
+        if not isinstance(vis, NP.ndarray):
+            raise TypeError('Input vis must be a numpy array')
+        elif vis.ndim < 3:
+            raise ValueError('Input vis must be at least 3-dimensional')
+        elif vis.shape[-3:] == (nbl, nchan, nt):
+            vis = vis.reshape((1,) + vis.shape if vis.ndim == 3 else vis.shape)
+        else:
+            raise ValueError('Input vis does not have compatible shape')
+        return vis, nbl, nchan, nt
+
+    def delay_transform_allruns(self, vis, pad=1.0, freq_wts=None, downsample=True, verbose=True):
+        """Delay spectra of a stack of runs on the GPU (:1475-1618, prisim_runs_transform): vis (..., nbl, nchan, n_acc), the leading
+        axes being runs, times self.bp times the weights, zero-padded to M = nchan + int(nchan pad) lags and transformed,
+        M df fftshift(ifft(.)) along the channel axis (nchan df without padding); with downsample every (1 + pad)-th lag, linearly
+        interpolated for a non-integer factor (the reading DelaySpectrum.delay_transform takes).  Returns freq_wts (reshaped as the
+        reference does), pad, lags, vis_lag (..., nbl, nlags, n_acc) and lag_kernel (1, ..., nbl, nlags, n_acc), the transform of
+        bp * freq_wts, computed once for all runs.  freq_wts: (nchan,), (nchan, n_acc), (nbl, nchan) or (nbl, nchan, n_acc); None: bp_wts.
+        Nothing is set on self and the caller's arrays are not modified; the spectra are written by the device in the reference's layout.
+
+        Reproduced literally: a freq_wts of vis's own shape raises ValueError (:1583, ``elif not freq_wts.shape != vis.shape``); the lags
+        are the int(nchan (1 + pad)) of :1600, downsampled like the spectra.
+        Departures (one test each in tests/test_allruns.py): other freq_wts shapes, which the reference leaves to numpy broadcasting,
+        are taken when they broadcast over the trailing (nbl, nchan, n_acc) axes only, and weights that vary from run to run raise
+        NotImplementedError; spectra longer than PRISIM_SUBBAND_MAX_LEN lags raise ValueError before any device work."""
+        if verbose:
+            print('Preparing to compute delay transform...\n\tChecking input parameters for compatibility...')
+        vis, nbl, nchan, nt = self._check_runs_vis(vis)
+        if not isinstance(pad, (int, float)):
+            raise TypeError('pad fraction must be a scalar value.')
+        if pad < 0.0:
+            pad = 0.0
+            if verbose:
+                print('\tPad fraction found to be negative. Resetting to 0.0 (no padding will be applied).')
+        ones = (1,) * (vis.ndim - 3)
+        if freq_wts is not None:
+            shp = NP.shape(freq_wts)
+            fw = NP.asarray(freq_wts)
+            if shp == self.f.shape:
+                report = fw.reshape(ones + (1, -1, 1))
+            elif shp == (nchan, nt):
+                report = fw.reshape(ones + (1, nchan, nt))
+            elif shp == (nbl, nchan):
+                report = fw.reshape(ones + (nbl, nchan, 1))
+            elif shp == (nbl, nchan, nt):
+                report = fw.reshape(ones + (nbl, nchan, nt))
+            elif not shp != vis.shape:
+                raise ValueError('window shape dimensions incompatible with number of channels and/or number of tiemstamps.')
+            else:
+                report = fw                                                              # left to numpy broadcasting in the reference
+                try:
+                    full = NP.broadcast_shapes(shp, vis.shape)
+                except ValueError:
+                    raise ValueError('window shape dimensions incompatible with number of channels and/or number of tiemstamps.')
+                if full != vis.shape or any(d != 1 for d in shp[:-3]):
+                    raise NotImplementedError('freq_wts that vary from run to run (shape %s) are not supported; weights must broadcast '
+                                              'over the trailing (nbl, nchan, n_acc) axes' % (shp,))
+            wts3 = report.reshape(report.shape[-3:]) if report.ndim > 3 else report
+        else:
+            wts3 = NP.asarray(self.bp_wts)
+            report = wts3.reshape(ones + wts3.shape)
+        if verbose:
+            print('\tFrequency window weights assigned.')
+        if not isinstance(downsample, bool):
+            raise TypeError('Input downsample must be of boolean type')
+        npad = int(nchan * pad) if pad != 0.0 else 0
+        m = nchan + npad
+        if m > _abi.PRISIM_SUBBAND_MAX_LEN:
+            raise ValueError('delay spectra of %d lags exceed PRISIM_SUBBAND_MAX_LEN = %d' % (m, _abi.PRISIM_SUBBAND_MAX_LEN))
+        if verbose:
+            print('\tInput parameters have been verified to be compatible.\n\tProceeding to compute delay transform.')
+        lags = DSP.spectral_axis(int(nchan * (1 + pad)), delx=self.df, use_real=False, shift=True)         # :1600
+        kw = {'m': m, 'scale': m * self.df, 'mode': 'all'}
+        if downsample:
+            kw.update(mode='interp', factor=1 + pad, nout=NP.arange(0, m, 1 + pad).size)
+            lags = DSP.downsampler(lags, 1 + pad, method='interp').flatten()
+        bp = NP.asarray(self.bp)
+        ctx = self.ia._ctx
+        vis_lag, _ = ctx.runs_transform(vis, nbl, nchan, nt, bp=bp, wts=wts3, **kw)
+        kernel, _ = ctx.runs_transform(None, nbl, nchan, nt, bp=bp, wts=wts3, **kw)
+        nlags = vis_lag.shape[-2]
+        if verbose:
+            print('\tDelay transform computed ' + ('without padding.' if pad == 0.0 else 'with padding fraction {0:.1f}'.format(pad)))
+            if downsample:
+                print('\tDelay transform products downsampled by factor of {0:.1f}'.format(1 + pad))
+                print('delay_transform() completed successfully.')
+        return {'freq_wts': report, 'pad': pad, 'lags': lags, 'vis_lag': vis_lag.reshape(vis.shape[:-3] + (nbl, nlags, nt)),
+                'lag_kernel': kernel.reshape(ones + (nbl, nlags, nt))}
+
+    def subband_delay_transform_allruns(self, vis, bw_eff, freq_center=None, shape=None, fftpow=None, pad=None, bpcorrect=False,
+                                        action=None, verbose=True):
+        """Sub-band delay spectra of a stack of runs on the GPU (:2252-2513, prisim_runs_transform): vis (..., nbl, nchan, n_acc) times
+        self.bp times every window of subband_freq_wts, zero-padded to M = nchan + int(nchan pad) lags; returned FFT-resampled
+        (DSP.downsampler 'FFT', read in prisim_amd/dsp_readings.py) to round(M / factor) lags with factor = min(M df / bw_eff), the
+        spectra formed on the device from the windowed channels directly (the M-lag spectra are never formed).  Returns freq_center,
+        shape, freq_wts (n_win, 1, ..., 1, nchan, 1), bw_eff, npad, lags and lag_kernel (n_win, 1, ..., nbl, nlags, n_acc) linearly
+        interpolated at arange(0, M, factor), vis_lag (n_win, ..., nbl, nres, n_acc) and lag_corr_length.  Nothing is set on self.
+
+        Reproduced literally: any action other than None returns the resampled dictionary (:2490, ``action = 'return_resampled'``);
+        windows sorted by channel while freq_center / bw_eff keep the given order; 'interp' lags (ceil(M / factor)) and 'FFT' spectra
+        (round(M / factor)) may differ in length; bpcorrect has no effect.
+        Departures (one test each in tests/test_allruns.py): action=None raises its ValueError before anything is computed (the
+        reference computes first); the default freq_center is f[int(nchan / 2)]; fftpow other than 1 raises NotImplementedError
+        (dsp_readings.window_fftpow)."""
+        vis, nbl, nchan, nt = self._check_runs_vis(vis)
+        f, df = self.f, self.df
+        if not isinstance(bw_eff, (int, float, list, NP.ndarray)):
+            raise TypeError('Value of effective bandwidth must be a scalar, list or numpy array')
+        # the checks of :2408-2447 are those of subband_delay_transform for one key (both keys given the caller's value), but for the
+        # window shape, which is compared case-insensitively here (shape.lower())
+        if shape is not None:
+            if not isinstance(shape, str):
+                raise TypeError('Window shape must be a string')
+            if shape.lower() not in ['rect', 'bhw', 'bnw']:
+                raise ValueError('Invalid value for window shape specified.')
+        else:
+            shape = 'rect'
+        both = lambda v: None if v is None else {'sim': v, 'cc': v}
+        bw, fc, _, fpow, pd = _check_subband_args(f, df, both(bw_eff), both(freq_center), None, both(fftpow), both(pad), False, verbose)
+        bw_eff, freq_center, fftpow, pad = bw['sim'], fc['sim'], fpow['sim'], pd['sim']
+        if action is None:
+            raise ValueError('Invalid value specified for keyword input action')
+        freq_wts = subband_freq_wts(f, df, bw_eff, freq_center, shape, fftpow)
+        nwin = freq_wts.shape[0]
+        npad = int(nchan * pad)
+        m = nchan + npad
+        if m > _abi.PRISIM_SUBBAND_MAX_LEN:
+            raise ValueError('sub-band spectra of %d lags exceed PRISIM_SUBBAND_MAX_LEN = %d' % (m, _abi.PRISIM_SUBBAND_MAX_LEN))
+        factor = NP.min((nchan + npad) * df / bw_eff)
+        nres = DSP.fft_downsample_length(m, factor)
+        if not 1 <= nres <= _abi.PRISIM_SUBBAND_MAX_LEN:
+            raise ValueError('resampled sub-band spectra of %d lags must lie in 1 .. PRISIM_SUBBAND_MAX_LEN = %d'
+                             % (nres, _abi.PRISIM_SUBBAND_MAX_LEN))
+        lags = DSP.downsampler(DSP.spectral_axis(m, delx=df, use_real=False, shift=True), factor, axis=-1, method='interp', kind='linear')
+        bp = NP.asarray(self.bp)
+        ctx = self.ia._ctx
+        vis_lag, _ = ctx.runs_transform(vis, nbl, nchan, nt, bp=bp, win=freq_wts, m=m, scale=m * df, mode='resample', nout=nres)
+        kernel, _ = ctx.runs_transform(None, nbl, nchan, nt, bp=bp, win=freq_wts, m=m, scale=m * df, mode='interp', factor=factor,
+                                       nout=NP.arange(0, m, factor).size)
+        if verbose:
+            print('\tSub-band(s) delay transform computed')
+        ones = (1,) * (vis.ndim - 3)
+        dlag = lags[1] - lags[0]
+        return {'freq_center': freq_center, 'shape': shape, 'freq_wts': freq_wts.reshape((nwin,) + ones + (1, nchan, 1)), 'bw_eff': bw_eff,
+                'npad': npad, 'lags': lags, 'vis_lag': vis_lag.reshape((nwin,) + vis.shape[:-3] + (nbl, nres, nt)),
+                'lag_kernel': kernel.reshape((nwin,) + ones + (nbl, kernel.shape[-2], nt)), 'lag_corr_length': (1 / bw_eff) / dlag}
+
+
 
 SUBBAND_KEYS = ('cc', 'sim')
 
@@ -988,6 +1144,52 @@ class DelayPowerSpectrum(object):
                 out = self.subband_delay_power_spectra_resampled[key] = {}
                 out['kprll'], out['kperp'], out['horizon_kprll_limits'] = self._subband_k(sb['lags'], self.subband_delay_power_spectra[key]['z'])
                 self._subband_power(sb, out, self.subband_delay_power_spectra[key]['factor'].reshape(1, -1, 1, 1))
+
+    def compute_power_spectrum_allruns(self, dspec, subband=False):
+        """Delay power spectra of stacks of runs on the GPU (:4067-4195, prisim_runs_power): dspec['vislag1'] * dspec['vislag2'].conj()
+        * factor, its real part, times 2 for cross power (mode 'cross' iff 'vislag2' is given; auto power reads vislag1 twice without
+        copying it), rounded as numpy rounds that statement.  Full band (subband=False): factor = jacobian1 jacobian2 Jy2K**2, key
+        'fullband'.  Sub-bands: per window 1 / beam3Dvol(squeeze(freq_wts)) * rz_los**2 drz_los / bw_eff * Jy2K**2 at the redshift of
+        each raveled freq_center, key 'subband' (the reference's unused kprll / kperp are not formed).  complex64 spectra are multiplied
+        in fp32, as numpy does.
+        Departure (one test in tests/test_allruns.py): the reference writes vislag2, freq_center and bw_eff back into the caller's
+        dspec; this port leaves dspec as it was."""
+        if not isinstance(dspec, dict):
+            raise TypeError('Input dspec must be a dictionary')
+        mode = 'auto'
+        if 'vislag1' not in dspec:
+            raise KeyError('Key "vislag1" not found in input dspec')
+        v1 = dspec['vislag1']
+        if not isinstance(v1, NP.ndarray):
+            raise TypeError('Value under key "vislag1" must be a numpy array')
+        v2 = None
+        if 'vislag2' in dspec:
+            mode = 'cross'
+            v2 = dspec['vislag2']
+            if not isinstance(v2, NP.ndarray):
+                raise TypeError('Value under key "vislag2" must be a numpy array')
+            if v1.shape != v2.shape:
+                raise ValueError('Value under keys "vislag1" and "vislag2" must have same shape')
+        if not isinstance(subband, bool):
+            raise TypeError('Input subband must be boolean')
+        if not subband:
+            factor = NP.ravel(self.jacobian1 * self.jacobian2 * self.Jy2K ** 2)
+            key = 'fullband'
+        else:
+            freq_center = NP.asarray(dspec['freq_center']).ravel()
+            bw_eff = NP.asarray(dspec['bw_eff']).ravel()
+            wl = FCNST.c / freq_center
+            redshift = REST_FREQ_HI / freq_center - 1
+            rz_los = self.cosmo.comoving_distance(redshift).to('Mpc').value
+            drz_los = self.comoving_los_depth(bw_eff, redshift, action='return')
+            omega_bw = self.beam3Dvol(freq_wts=NP.squeeze(dspec['freq_wts']))
+            jacobian1 = 1 / omega_bw
+            jacobian2 = rz_los ** 2 * drz_los / bw_eff
+            Jy2K = wl ** 2 * JY / (2 * FCNST.k)
+            factor = NP.ravel(jacobian1 * jacobian2 * Jy2K ** 2)
+            key = 'subband'
+        power, _ = self.ds.ia._ctx.runs_power(v1, v2, factor, cross=(mode == 'cross'))
+        return {key: power}
 
     def _subband_k(self, lags, zs):
         """kprll (n_win, nlags), kperp (n_win, nbl) and horizon_kprll_limits (n_acc, n_win, nbl, 2) at the redshifts zs (:4011-4018)."""
