@@ -59,6 +59,13 @@ PRISIM_RUNS_AUTO, PRISIM_RUNS_FUSED, PRISIM_RUNS_ROCFFT, PRISIM_RUNS_DIRECT = -1
 RUNS_ROUTES = {PRISIM_RUNS_FUSED: 'fused', PRISIM_RUNS_ROCFFT: 'rocfft', PRISIM_RUNS_DIRECT: 'direct'}
 RUNS_BUDGET = 1 << 30               # device bytes one call of the runs entries streams through by default
 
+# every symbol include/prisim_closure.h declares: closure phases of antenna triads (prisim_amd/csrc_closure/), linked into the same library
+CLOSURE_EXPORTS = ('prisim_closure_phase',)
+PRISIM_CLOSURE_MAX_LEN = PRISIM_SUBBAND_MAX_LEN
+PRISIM_CLOSURE_AUTO, PRISIM_CLOSURE_DIRECT, PRISIM_CLOSURE_FUSED, PRISIM_CLOSURE_ROCFFT = -1, 0, 1, 2
+CLOSURE_ROUTES = {PRISIM_CLOSURE_DIRECT: 'direct', PRISIM_CLOSURE_FUSED: 'fused', PRISIM_CLOSURE_ROCFFT: 'rocfft'}
+CLOSURE_BUDGET = 1 << 30            # device bytes the chunk buffers of one closure-phase call take by default
+
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
                  'prisim_gains_table_free', 'prisim_gains_apply')
@@ -194,6 +201,12 @@ class PrisimRunsStats(C.Structure):
                 ('streams', C.c_int32), ('tile', C.c_int32), ('lds_bytes', C.c_int32)]
 
 
+class PrisimClosureStats(C.Structure):
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('triads', C.c_int64), ('chunks', C.c_int64),
+                ('chunk_triads', C.c_int64), ('kernel_bytes', C.c_int64), ('download_bytes', C.c_int64), ('route', C.c_int32),
+                ('streams', C.c_int32), ('tile', C.c_int32), ('lds_bytes', C.c_int32)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -299,6 +312,10 @@ def load_library():
                                           dbl, i64, vp, vp, vp, C.c_int32, i64, vp, C.POINTER(PrisimRunsStats)]
     lib.prisim_runs_power.argtypes = [vp, i64, i64, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, i64, vp, C.POINTER(PrisimRunsStats)]
     for name in RUNS_EXPORTS:
+        getattr(lib, name).restype = C.c_int
+    lib.prisim_closure_phase.argtypes = [vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, i64, vp, C.c_int32, i64, vp, vp,
+                                         C.POINTER(PrisimClosureStats)]
+    for name in CLOSURE_EXPORTS:
         getattr(lib, name).restype = C.c_int
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
@@ -990,6 +1007,51 @@ class Context(object):
     def _runs_stats(st):
         return {'wall_ms': st.wall_ms, 'pairs': int(st.pairs), 'chunks': int(st.chunks), 'chunk_pairs': int(st.chunk_pairs),
                 'route': RUNS_ROUTES.get(st.route, st.route), 'streams': int(st.streams), 'tile': int(st.tile), 'lds_bytes': int(st.lds_bytes)}
+
+    # ---- closure phases of antenna triads (include/prisim_closure.h) ----
+    def closure_phase(self, cube, legs, conj, bpwts, freq_wts=None, masks=None, mask_index=None, nt=None, route='auto',
+                      budget_bytes=CLOSURE_BUDGET):
+        """Visibility triplets and closure phases of antenna triads on the device (prisim_closure_phase).  cube: (nbl, nchan, nt)
+        complex128 on the host, or None for the resident visibility slots [0, nt) of this context; legs, conj: (ntriads, 3) cube rows
+        and conjugation flags of the legs 12, 23, 31; bpwts: bp * bp_wts, broadcastable to (nbl, nchan, nt); freq_wts: (nchan,) or a
+        scalar (None: ones); masks: None (no delay filter) or (nmask, nchan) filter_unmask vectors on the unshifted FFT delay axis, with
+        mask_index (nbl,) the mask of each cube row (None: mask 0).  The outputs are streamed in chunks of triads within budget_bytes
+        of device memory; an uploaded cube (16 B per element) and the dense bpwts (8 B per element of (nbl, nchan, nt), also when bp is
+        constant in time) lie on the device for the call on top of that budget.  Returns (triplets (ntriads, 3, nchan, nt) complex128, phases (ntriads, nchan, nt) float64, stats); stats['resident']: the resident cube was read."""
+        if cube is None:
+            if nt is None:
+                raise ValueError('nt is required with resident input')
+            x, nbl, nchan, nt = None, self.nbl, self.nchan, int(nt)
+        else:
+            x = NP.ascontiguousarray(cube, dtype=NP.complex128)
+            if x.ndim != 3:
+                raise ValueError('cube must be (nbl, nchan, nt)')
+            nbl, nchan, nt = x.shape
+        lg = NP.ascontiguousarray(legs, dtype=NP.int32).reshape(-1, 3)
+        cj = NP.ascontiguousarray(conj, dtype=NP.int32).reshape(-1, 3)
+        if cj.shape != lg.shape:
+            raise ValueError('legs and conj must both be (ntriads, 3)')
+        ntriads = lg.shape[0]
+        bw = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(bpwts, dtype=NP.float64), (nbl, nchan, nt)))
+        fw = NP.ones(nchan) if freq_wts is None else NP.ascontiguousarray(NP.broadcast_to(NP.asarray(freq_wts, dtype=NP.float64).ravel(), (nchan,)))
+        mk = mi = None
+        if masks is not None:
+            mk = NP.ascontiguousarray(masks, dtype=NP.float64).reshape(-1, nchan)
+            if mask_index is not None:
+                mi = NP.ascontiguousarray(mask_index, dtype=NP.int32).ravel()
+                if mi.size != nbl:
+                    raise ValueError('mask_index must have one entry per cube row')
+        trip = NP.empty((ntriads, 3, nchan, nt), dtype=NP.complex128)
+        phase = NP.empty((ntriads, nchan, nt), dtype=NP.float64)
+        st = PrisimClosureStats()
+        r = {'auto': PRISIM_CLOSURE_AUTO, 'direct': PRISIM_CLOSURE_DIRECT, 'fused': PRISIM_CLOSURE_FUSED, 'rocfft': PRISIM_CLOSURE_ROCFFT}[route]
+        self._check(self._lib.prisim_closure_phase(self._h, _ptr(x), nt, nbl, nchan, _ptr(lg), _ptr(cj), ntriads, _ptr(fw), _ptr(bw),
+                                                   _ptr(mk), 0 if mk is None else mk.shape[0], _ptr(mi), r, int(budget_bytes),
+                                                   _ptr(trip), _ptr(phase), C.byref(st)), 'prisim_closure_phase')
+        return trip, phase, {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'triads': int(st.triads), 'chunks': int(st.chunks),
+                             'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes),
+                             'download_bytes': int(st.download_bytes), 'route': CLOSURE_ROUTES.get(st.route, st.route),
+                             'streams': int(st.streams), 'tile': int(st.tile), 'lds_bytes': int(st.lds_bytes), 'resident': x is None}
 
     # ---- instrument gain tables (include/prisim_gains.h) ----
     @staticmethod

@@ -20,7 +20,8 @@ Stacks of runs: ``delay_transform_allruns`` (:1475-1618), ``subband_delay_transf
 ``DelayPowerSpectrum.compute_power_spectrum_allruns`` (:4067-4195) take the caller's (..., nbl, nchan, n_acc) visibilities, whose leading
 axes are runs, and stream them through include/prisim_runs.h (prisim_amd/csrc_runs/) in the reference's layout, with no host transpose.
 
-Not here (out of scope): closure-phase spectra, FITS persistence.
+Not here (out of scope): closure-phase delay spectra and their power spectra (the closure phases of the visibilities themselves are
+InterferometerArray.getClosurePhase), FITS persistence.
 
 Cosmology.  The reference takes ``astropy.cosmology.Planck15.clone(H0=100)`` (:34-35); astropy is not in this image, so ``cosmo100`` here
 is this module's own flat LambdaCDM with Planck15's Om0 = 0.3075, Tcmb0 = 2.7255 K, Neff = 3.046 (photons + massless neutrinos in the

@@ -329,6 +329,40 @@ def _lst_and_jd(timeobj, lst):
     raise TypeError('timeobj must be a Time-like object, a (jd, lst_deg) pair, or a Julian date with lst given.')
 
 
+def closure_filter_masks(fft_delays, filter_type, filter_mode, delay_min, delay_width, baseline_lengths):
+    """The filter_unmask vectors of getClosurePhase's delay filter (interferometry.py:7536-7543 'regular', :7570-7587 'horizon') on the
+    unshifted FFT delay axis: ones with zeros on the filtered delays.  'regular': one mask, zero where delay_min <= |tau| <= delay_min +
+    delay_width ('discard') or where |tau| <= delay_min or |tau| >= delay_min + delay_width ('retain').  'horizon': one mask per
+    baseline with delay_max = |b| / c + delay_width, zero where |tau| <= delay_max ('discard') or |tau| >= delay_max ('retain').
+    Returns (masks (nmask, nchan), mask_index (nbl,) int32 or None: mask 0 for every baseline)."""
+    tau = NP.abs(NP.asarray(fft_delays, dtype=NP.float64))
+    if filter_type == 'regular':
+        delay_max = delay_min + delay_width
+        if filter_mode == 'discard':
+            zero = NP.logical_and(tau >= delay_min, tau <= delay_max)
+        else:
+            zero = NP.logical_or(tau <= delay_min, tau >= delay_max)
+        return NP.where(zero, 0.0, 1.0).reshape(1, -1), None
+    delay_max = NP.asarray(baseline_lengths, dtype=NP.float64) / C_LIGHT + delay_width
+    zero = tau[NP.newaxis, :] <= delay_max[:, NP.newaxis] if filter_mode == 'discard' else tau[NP.newaxis, :] >= delay_max[:, NP.newaxis]
+    rows, mask_index = NP.unique(zero, axis=0, return_inverse=True)
+    return NP.where(rows, 0.0, 1.0), NP.asarray(mask_index, dtype=NP.int32).ravel()
+
+
+def _label_from_text(s):
+    """A baseline label back from the text save() wrote for it (str(label), '/' written as '|' in dataset names): the tuple of
+    strings that ast.literal_eval gives (interferometry.py:5394-5397), or, for a text that is no literal (numpy scalars inside the
+    tuple), its quoted fields; any other text stays a string."""
+    import ast
+    import re
+    try:
+        v = ast.literal_eval(s)
+    except (ValueError, SyntaxError):
+        fields = re.findall(r"'([^']*)'", s)
+        return tuple(fields) if fields else s
+    return tuple(str(x) for x in v) if isinstance(v, (tuple, list)) else v
+
+
 class InterferometerArray(object):
     """Interferometer array whose snapshots are simulated on one MI355X (see module docstring).
 
@@ -569,10 +603,18 @@ class InterferometerArray(object):
                 self.gradient_mode = 'baseline'
                 self.gradient = {'baseline': f.read('gradients/baseline')}
             gainsfile = get('gaininfo/gainsfile')                                      # :5387-5389
+            blgroups = bl_reversemap = None                                            # :5390-5397
+            if f.exists('blgroupinfo'):
+                blgroups, bl_reversemap = {}, {}
+                for name in (f.list('blgroupinfo/groups') if f.exists('blgroupinfo/groups') else []):
+                    blgroups[_label_from_text(name.replace('|', '/'))] = [_label_from_text(text(m)) for m in
+                                                                          NP.asarray(f.read('blgroupinfo/groups/' + name)).ravel()]
+                for name in (f.list('blgroupinfo/reversemap') if f.exists('blgroupinfo/reversemap') else []):
+                    bl_reversemap[_label_from_text(name.replace('|', '/'))] = _label_from_text(
+                        text(NP.asarray(f.read('blgroupinfo/reversemap/' + name)).ravel()[0]))
         self.gaininfo = None if gainsfile is None else GainInfo(init_file=text(gainsfile))
         self.gain_padding = None
-        self.blgroups = None
-        self.bl_reversemap = None
+        self.blgroups, self.bl_reversemap = blgroups, bl_reversemap
         self.lag_kernel = None
         self.obs_catalog_indices = []
         self.geometric_delays = []
@@ -2146,6 +2188,235 @@ class InterferometerArray(object):
             self._upload_cube()
         self.generate_noise()                                                          # :6905-6906
         self.add_noise()
+
+    # ------------------------------------------------------------------------------------------
+    def getThreePointCombinations(self, unique=False):
+        """All (unique=False, the default) or only the unique triads of the antenna layout whose three baselines were simulated
+        (interferometry.py:6989-7085): the triple loop over layout['labels'] in the reference's order, baselines matched through
+        their '%.2f_%.2f_%.2f' strings with one sign flip, a warning (not an error) for a pair that was not simulated, and with
+        unique=True only the first triad of every set of three baseline strings.  Returns what the reference returns: the list of
+        antenna-label triplets and the list of [bl12, bl23, bl31] baseline vectors as matched (flipped legs flipped).  Host code;
+        needs `layout` and `baselines` only."""
+        if not isinstance(unique, bool):
+            raise TypeError('Input unique must be boolean')
+
+        def blstring(v):
+            return '{0[0]:.2f}_{0[1]:.2f}_{0[2]:.2f}'.format(v)
+
+        def match(v):
+            """v cleaned as :7020-7028; (vector, string) of the simulated baseline it is, or of its negative; string None: neither"""
+            v = v + 0.0
+            v[NP.abs(v) < 1e-10] = 0.0
+            if not NP.sqrt(NP.sum(v ** 2)) > 0.0:
+                return v, False
+            s = blstring(v)
+            if s not in blstr:
+                v = -1 * v + 0.0
+                s = blstring(v)
+            return v, (s if s in blstr else None)
+
+        blstr = set(blstring(lo) for lo in (self.baselines + 0.0))
+        pos = NP.asarray(self.layout['positions'], dtype=NP.float64)
+        labels = self.layout['labels']
+        missing = 'A baseline not found in the simulated reference baselines. Proceeding with the rest'
+        anttriplets, blvecttriplets, seen = [], [], set()
+        for aind1, albl1 in enumerate(labels):
+            for aind2, albl2 in enumerate(labels):
+                bl12, s12 = match(pos[aind2] - pos[aind1])
+                if s12 is False:
+                    continue
+                if s12 is None:
+                    warnings.warn(missing)
+                    continue
+                for aind3, albl3 in enumerate(labels):
+                    bl23, s23 = match(pos[aind3] - pos[aind2])
+                    bl31, s31 = match(pos[aind1] - pos[aind3])
+                    if s23 is False or s31 is False:
+                        continue
+                    if s23 is None or s31 is None:                 # (the reference looks at 31 only once 23 is found: one warning)
+                        warnings.warn(missing)
+                        continue
+                    if unique:
+                        key = frozenset((s12, s23, s31))          # setdiff1d(new, old).size == 0 with three strings each
+                        if any(key <= old for old in seen) if len(key) < 3 else key in seen:
+                            continue
+                        seen.add(key)
+                    blvecttriplets += [[bl12, bl23, bl31]]
+                    anttriplets += [(albl1, albl2, albl3)]
+        return (anttriplets, blvecttriplets)
+
+    def closure_leg_table(self, antenna_triplets):
+        """The legs of antenna triplets as rows of the visibility cube (interferometry.py:7412-7485): for each (a1, a2, a3) the
+        baseline ids (a2, a1), (a3, a2), (a1, a3) are looked up in bl_reversemap; an id found reversed is a conjugated leg; one
+        found neither way raises the reference's ValueError.  Returns (legs (ntriads, 3) int32 rows ind12, ind23, ind31,
+        conj (ntriads, 3) int32 flags, blvecttriplets: a list of (3, 3) arrays of the legs' baseline vectors, negated on conjugated
+        legs).  An array built without blgroupinfo has no bl_reversemap (the reference then fails on `in None`): the identity map
+        {label: label} of `labels` is used for the call; no attribute is changed.  A reversemap value that is not among `labels`
+        raises the same ValueError (the reference: IndexError from NP.where(...)[0][0])."""
+        from .dsp_readings import _key
+        row_of = {}
+        for i, lab in enumerate(self.labels):
+            row_of.setdefault(_key(lab), i)
+        if self.bl_reversemap is None:
+            revmap = {k: k for k in row_of}
+        else:
+            revmap = {_key(k): _key(v) for k, v in self.bl_reversemap.items()}
+        n = len(antenna_triplets)
+        legs, conj = NP.zeros((n, 3), dtype=NP.int32), NP.zeros((n, 3), dtype=NP.int32)
+        blvecttriplets = []
+        for ti, anttriplet in enumerate(antenna_triplets):
+            a1, a2, a3 = (str(_key(a)) for a in anttriplet)
+            vec = NP.zeros((3, 3))
+            for li, bl_id in enumerate(((a2, a1), (a3, a2), (a1, a3))):
+                if bl_id in revmap:
+                    ref = revmap[bl_id]
+                elif tuple(reversed(bl_id)) in revmap:
+                    ref = revmap[tuple(reversed(bl_id))]
+                    conj[ti, li] = 1
+                else:
+                    raise ValueError('Baseline ({0[0]}, {0[1]}) not found in simulated baselines'.format(bl_id))
+                if ref not in row_of:
+                    raise ValueError('Baseline ({0[0]}, {0[1]}) not found in simulated baselines'.format(ref))
+                legs[ti, li] = row_of[ref]
+                vec[li, :] = -self.baselines[legs[ti, li], :] if conj[ti, li] else self.baselines[legs[ti, li], :]
+            blvecttriplets += [vec]
+        return legs, conj, blvecttriplets
+
+    def getClosurePhase(self, antenna_triplets=None, delay_filter_info=None, specsmooth_info=None, spectral_window_info=None,
+                        unique=False):
+        """Closure phases (bispectrum phases) of the visibilities on triads of antennas, on the GPU (interferometry.py:7087-7651;
+        include/prisim_closure.h).  Arguments and the returned dictionary are the reference's:
+
+        antenna_triplets      list of antenna-label triplets; None: getThreePointCombinations(unique=unique)
+        delay_filter_info     None, or {'type': 'horizon' (default) | 'regular', 'mode': 'discard' (default) | 'retain',
+                              'min': seconds, 'width': in units of the delay resolution}: every leg is filtered as
+                              ifft(mask * fft(freq_wts * v)) before the closure phase (:7348-7399, :7536-7599)
+        spectral_window_info  None, or {'freq_center', 'bw_eff', 'shape', 'fftpow'} (each may be None): one spectral window, built
+                              by delay_spectrum.subband_freq_wts (:7296-7344); default centre channels[nchan // 2]
+        specsmooth_info       must be None (below)
+
+        Returns {'closure_phase_skyvis', 'closure_phase_vis', 'closure_phase_noise': (ntriads, nchan, nt) radians;
+        'antenna_triplets'; 'baseline_triplets': list of (3, 3) arrays; 'skyvis', 'vis', 'noisevis': (ntriads, 3, nchan, nt) the
+        visibilities that went into the phases; 'spectral_weights': (1,) ones, or (nchan,)}.
+
+        Departures, all stated: the noisy and noise entries are None when the array holds no vis_freq / vis_noise_freq (the
+        reference fails there); specsmooth_info raises NotImplementedError (the reference's 'median' branch indexes
+        specsmooth_info[specsmooth_info['window_size']] and cannot run, and 'interp' redraws noise from numpy's global generator);
+        fftpow other than 1 raises NotImplementedError as everywhere in this package (DSP.window_fftpow is unread); without
+        blgroupinfo the identity bl_reversemap is used (closure_leg_table).  DSP.FT1D is read as numpy's fft / ifft
+        (prisim_amd/dsp_readings.py).  The noiseless cube is read where it lies on the device when the device slots are in step
+        with skyvis_freq; the other cubes are uploaded once each.  bp * bp_wts is handed over dense, (nbl, nchan, nt) float64, also when
+        it is constant in time; it and an uploaded cube lie on the device for the call, outside the chunk budget.  The stats of the
+        device calls are left in closure_stats, per cube.  There is no CPU path."""
+        from . import delay_spectrum as DS
+        from . import dsp_readings as DSP
+        if antenna_triplets is None:
+            antenna_triplets, _ = self.getThreePointCombinations(unique=unique)
+        if not isinstance(antenna_triplets, list):
+            raise TypeError('Input antenna triplets must be a list of triplet tuples')
+        if specsmooth_info is not None:
+            raise NotImplementedError("specsmooth_info is not supported: the reference's 'median' branch indexes specsmooth_info["
+                                      "specsmooth_info['window_size']] and cannot run, and 'interp' redraws noise from numpy's global "
+                                      "generator")
+        nchan = self.channels.size
+        if spectral_window_info is not None:                                       # :7296-7344
+            freq_center, bw_eff = spectral_window_info['freq_center'], spectral_window_info['bw_eff']
+            shape, fftpow = spectral_window_info['shape'], spectral_window_info['fftpow']
+            if freq_center is None:
+                freq_center = self.channels[nchan // 2]
+            shape = 'rect' if shape is None else shape.lower()
+            if bw_eff is None:
+                if shape == 'rect':
+                    bw_eff = nchan * self.freq_resolution
+                elif shape == 'bhw':
+                    bw_eff = 0.5 * nchan * self.freq_resolution
+                else:
+                    raise ValueError('Specified window shape not currently supported')
+            if fftpow is None:
+                fftpow = 1.0
+            elif isinstance(fftpow, (int, float)):
+                if fftpow <= 0.0:
+                    raise ValueError('Value fftpow must be positive')
+            else:
+                raise ValueError('Value fftpow must be a scalar (int or float)')
+            wts = DS.subband_freq_wts(self.channels, self.freq_resolution, NP.asarray(bw_eff, dtype=NP.float64).reshape(-1),
+                                      NP.asarray(freq_center, dtype=NP.float64).reshape(-1), shape, fftpow)
+            if wts.shape[0] != 1:
+                raise ValueError('freq_center is outside the band')
+            freq_wts = wts[0]
+        else:
+            freq_wts = NP.asarray(1.0).reshape(-1)
+
+        masks = mask_index = None
+        if delay_filter_info is not None:                                          # :7350-7399
+            fft_delays = DSP.spectral_axis(nchan, delx=self.freq_resolution, shift=False, use_real=False)
+            dtau = fft_delays[1] - fft_delays[0]
+            if not isinstance(delay_filter_info, dict):
+                raise TypeError('Delay filter info must be specified as a dictionary')
+            filter_mode = delay_filter_info.get('mode', 'discard')
+            if filter_mode.lower() not in ['discard', 'retain']:
+                raise ValueError('Invalid delay filter mode specified')
+            filter_type = delay_filter_info.get('type', 'horizon')
+            if filter_type.lower() not in ['horizon', 'regular']:
+                raise ValueError('Invalid delay filter type specified')
+            if filter_type.lower() == 'regular':
+                if ('min' not in delay_filter_info) or ('width' not in delay_filter_info):
+                    raise KeyError('Keys "min" and "width" must be specified in input delay_filter_info')
+                delay_min, delay_width = delay_filter_info['min'], delay_filter_info['width']
+                if delay_min is None:
+                    delay_min = 0.0
+                elif isinstance(delay_min, (int, float)):
+                    delay_min = max([0.0, delay_min])
+                else:
+                    raise TypeError('Minimum delay in the filter must be a scalar value (int or float)')
+                if isinstance(delay_width, (int, float)):
+                    if delay_width <= 0.0:
+                        raise ValueError('Delay filter width must be positive')
+                else:
+                    raise TypeError('Delay width in the filter must be a scalar value (int or float)')
+            else:
+                delay_width = delay_filter_info.get('width', 0.0)
+                if delay_width is None:
+                    delay_width = 0.0
+                elif isinstance(delay_width, (int, float)):
+                    if delay_width <= 0.0:
+                        raise ValueError('Delay filter width must be positive')
+                else:
+                    raise TypeError('Delay width in the filter must be a scalar value (int or float)')
+            delay_width = delay_width * dtau
+            masks, mask_index = closure_filter_masks(fft_delays, filter_type.lower(), filter_mode.lower(),
+                                                     delay_min if filter_type.lower() == 'regular' else 0.0, delay_width,
+                                                     self.baseline_lengths)
+
+        legs, conj, blvecttriplets = self.closure_leg_table(antenna_triplets)
+        nbl = self.baselines.shape[0]
+        if self.skyvis_freq is None and not getattr(self, '_cube', None):
+            raise ValueError('no visibilities: call observe() first')
+        nt = len(self._cube)
+        # the noiseless cube is read where it lies when the device slots [0, nt) hold skyvis_freq itself, in fp64 (the rule of add_noise)
+        resident = bool(self._device_in_step) and nt <= self._reserved and all(
+            sn.dtype == NP.complex128 and (not isinstance(sn, _DeviceSlot) or sn.slot == i) for i, sn in enumerate(self._cube))
+        bpwts = NP.asarray(self.bp * self.bp_wts, dtype=NP.float64).reshape(nbl, nchan, -1)      # :7433, formed once for the call
+        out = {}
+        self.closure_stats = {}                    # the device call's stats per cube: 'skyvis', 'vis', 'noisevis'
+        for name, key in (('skyvis', 'skyvis'), ('vis', 'vis'), ('noise', 'noisevis')):
+            if name == 'skyvis':
+                cube = None if resident else self.skyvis_freq
+            else:
+                cube = self.vis_freq if name == 'vis' else self.vis_noise_freq
+                if cube is None:
+                    out[key], out['closure_phase_' + name] = None, None
+                    continue
+            if not legs.shape[0]:
+                out[key] = NP.zeros((0, 3, nchan, nt), dtype=NP.complex128)
+                out['closure_phase_' + name] = NP.zeros((0, nchan, nt))
+                continue
+            trip, phase, stats = self._ctx.closure_phase(cube, legs, conj, bpwts, freq_wts=freq_wts, masks=masks, mask_index=mask_index,
+                                                         nt=nt)
+            out[key], out['closure_phase_' + name] = trip, phase
+            self.closure_stats[key] = stats
+        out.update({'antenna_triplets': antenna_triplets, 'baseline_triplets': blvecttriplets, 'spectral_weights': freq_wts})
+        return out
 
     # ------------------------------------------------------------------------------------------
     def delay_transform(self, pad=1.0, freq_wts=None, verbose=True):
