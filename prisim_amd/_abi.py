@@ -66,6 +66,14 @@ PRISIM_CLOSURE_AUTO, PRISIM_CLOSURE_DIRECT, PRISIM_CLOSURE_FUSED, PRISIM_CLOSURE
 CLOSURE_ROUTES = {PRISIM_CLOSURE_DIRECT: 'direct', PRISIM_CLOSURE_FUSED: 'fused', PRISIM_CLOSURE_ROCFFT: 'rocfft'}
 CLOSURE_BUDGET = 1 << 30            # device bytes the chunk buffers of one closure-phase call take by default
 
+# every symbol include/prisim_cpdelay.h declares: delay spectra of closure phases and their power spectra (prisim_amd/csrc_closure/cpdelay.hip)
+CPDELAY_EXPORTS = ('prisim_closure_delay_spectra', 'prisim_closure_power')
+PRISIM_CPDELAY_MAX_LEN = PRISIM_SUBBAND_MAX_LEN
+PRISIM_CPDELAY_OVER, PRISIM_CPDELAY_OVER_POWER, PRISIM_CPDELAY_RES, PRISIM_CPDELAY_RES_POWER = 1, 2, 4, 8
+PRISIM_CPDELAY_AUTO, PRISIM_CPDELAY_FUSED, PRISIM_CPDELAY_ROCFFT = -1, 0, 1
+CPDELAY_ROUTES = {PRISIM_CPDELAY_FUSED: 'fused', PRISIM_CPDELAY_ROCFFT: 'rocfft'}
+PRISIM_CPPOWER_INDIVIDUAL, PRISIM_CPPOWER_AUTO, PRISIM_CPPOWER_CROSS = 1, 2, 4
+
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
                  'prisim_gains_table_free', 'prisim_gains_apply')
@@ -207,6 +215,12 @@ class PrisimClosureStats(C.Structure):
                 ('streams', C.c_int32), ('tile', C.c_int32), ('lds_bytes', C.c_int32)]
 
 
+class PrisimCpdelayStats(C.Structure):
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('rows', C.c_int64), ('chunks', C.c_int64), ('chunk_rows', C.c_int64),
+                ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('route', C.c_int32), ('phase_route', C.c_int32),
+                ('streams', C.c_int32), ('tile', C.c_int32), ('lds_bytes', C.c_int32), ('reserved_', C.c_int32)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -316,6 +330,12 @@ def load_library():
     lib.prisim_closure_phase.argtypes = [vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, i64, vp, C.c_int32, i64, vp, vp,
                                          C.POINTER(PrisimClosureStats)]
     for name in CLOSURE_EXPORTS:
+        getattr(lib, name).restype = C.c_int
+    lib.prisim_closure_delay_spectra.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, C.c_int32, C.c_int32, vp, i64,
+                                                 dbl, i64, i64, vp, vp, vp, vp, C.c_int32, C.c_int32, i64, vp, vp, vp, vp, vp,
+                                                 C.POINTER(PrisimCpdelayStats)]
+    lib.prisim_closure_power.argtypes = [vp, i64, i64, i64, vp, vp, C.c_int32, i64, vp, vp, vp, C.POINTER(PrisimCpdelayStats)]
+    for name in CPDELAY_EXPORTS:
         getattr(lib, name).restype = C.c_int
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
@@ -1052,6 +1072,114 @@ class Context(object):
                              'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes),
                              'download_bytes': int(st.download_bytes), 'route': CLOSURE_ROUTES.get(st.route, st.route),
                              'streams': int(st.streams), 'tile': int(st.tile), 'lds_bytes': int(st.lds_bytes), 'resident': x is None}
+
+    # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
+    @staticmethod
+    def _cpdelay_stats(st):
+        return {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows), 'chunks': int(st.chunks),
+                'chunk_rows': int(st.chunk_rows), 'upload_bytes': int(st.upload_bytes), 'download_bytes': int(st.download_bytes),
+                'route': CPDELAY_ROUTES.get(st.route, st.route), 'phase_route': CLOSURE_ROUTES.get(st.phase_route),
+                'streams': int(st.streams), 'tile': int(st.tile), 'lds_bytes': int(st.lds_bytes)}
+
+    def closure_delay_spectra(self, wts, m, df, phases=None, cube=None, legs=None, conj=None, bpwts=None, freq_wts=None, masks=None,
+                              mask_index=None, nt=None, phase_route='auto', nres=0, pscale=None, want=('res',), route='auto',
+                              want_phase=False, budget_bytes=CLOSURE_BUDGET):
+        """Delay spectra of closure phases on the device (prisim_closure_delay_spectra).  Either phases (..., nchan, nt) float64 --
+        every leading axis is a row --, or the arguments of closure_phase (cube (nbl, nchan, nt) or None for the resident slots [0, nt),
+        legs, conj, bpwts, freq_wts, masks, mask_index, phase_route): the phases are then formed on the device and transformed there, no
+        triplet is downloaded, and the phases come back only with want_phase.  wts (nwin, nchan) windows, m lags, nres resampled
+        lags, pscale (nwin,) for the power products; want: any of 'over', 'over_power', 'res', 'res_power'.  Returns a dict of the
+        wanted outputs, (rows..., nwin, m | nres, nt), 'phase' (ntriads, nchan, nt) with want_phase, and 'stats'."""
+        w = NP.ascontiguousarray(wts, dtype=NP.float64)
+        w = w.reshape(-1, w.shape[-1])
+        nwin, nchan = w.shape
+        m, nres = int(m), int(nres)
+        lg = cj = bw = fw = mk = mi = x = ph = None
+        nbl = 0
+        if phases is not None:
+            ph = NP.ascontiguousarray(phases, dtype=NP.float64)
+            if ph.ndim < 2 or ph.shape[-2] != nchan:
+                raise ValueError('phases must be (..., nchan, nt) with the channel count of wts')
+            lead, nt = ph.shape[:-2], ph.shape[-1]
+            nrows = int(NP.prod(lead, dtype=NP.int64))
+        else:
+            if legs is None or conj is None or bpwts is None:
+                raise ValueError('without phases, legs, conj and bpwts are required')
+            if cube is None:
+                if nt is None:
+                    raise ValueError('nt is required with resident input')
+                nbl, nt = self.nbl, int(nt)
+                if self.nchan != nchan:
+                    raise ValueError('wts must have the channel count of the resident cube')
+            else:
+                x = NP.ascontiguousarray(cube, dtype=NP.complex128)
+                if x.ndim != 3 or x.shape[1] != nchan:
+                    raise ValueError('cube must be (nbl, nchan, nt) with the channel count of wts')
+                nbl, _, nt = x.shape
+            lg = NP.ascontiguousarray(legs, dtype=NP.int32).reshape(-1, 3)
+            cj = NP.ascontiguousarray(conj, dtype=NP.int32).reshape(-1, 3)
+            if cj.shape != lg.shape:
+                raise ValueError('legs and conj must both be (ntriads, 3)')
+            nrows, lead = lg.shape[0], (lg.shape[0],)
+            bw = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(bpwts, dtype=NP.float64), (nbl, nchan, nt)))
+            fw = NP.ones(nchan) if freq_wts is None else NP.ascontiguousarray(NP.broadcast_to(NP.asarray(freq_wts, dtype=NP.float64).ravel(),
+                                                                                                  (nchan,)))
+            if masks is not None:
+                mk = NP.ascontiguousarray(masks, dtype=NP.float64).reshape(-1, nchan)
+                if mask_index is not None:
+                    mi = NP.ascontiguousarray(mask_index, dtype=NP.int32).ravel()
+                    if mi.size != nbl:
+                        raise ValueError('mask_index must have one entry per cube row')
+        bits = {'over': PRISIM_CPDELAY_OVER, 'over_power': PRISIM_CPDELAY_OVER_POWER, 'res': PRISIM_CPDELAY_RES,
+                'res_power': PRISIM_CPDELAY_RES_POWER}
+        flag = 0
+        for name in want:
+            flag |= bits[name]
+        ps = None if pscale is None else NP.ascontiguousarray(NP.broadcast_to(NP.asarray(pscale, dtype=NP.float64).ravel(), (nwin,)))
+        out = {}
+        for name in want:
+            n = m if name.startswith('over') else max(nres, 1)
+            out[name] = NP.empty(tuple(lead) + (nwin, n, nt), dtype=NP.complex128 if name in ('over', 'res') else NP.float64)
+        if want_phase and phases is None:
+            out['phase'] = NP.empty((nrows, nchan, nt), dtype=NP.float64)
+        mo = mi_ = mw = None
+        if flag & (PRISIM_CPDELAY_RES | PRISIM_CPDELAY_RES_POWER) and 1 <= nres <= PRISIM_CPDELAY_MAX_LEN and 1 <= m <= PRISIM_CPDELAY_MAX_LEN:
+            mo, mi_, mw = (NP.ascontiguousarray(a) for a in dsp_readings.resample_map(m, nres))   # the one reading of the resampling
+        st = PrisimCpdelayStats()
+        r = {'auto': PRISIM_CPDELAY_AUTO, 'fused': PRISIM_CPDELAY_FUSED, 'rocfft': PRISIM_CPDELAY_ROCFFT}[route]
+        pr = {'auto': PRISIM_CLOSURE_AUTO, 'direct': PRISIM_CLOSURE_DIRECT, 'fused': PRISIM_CLOSURE_FUSED,
+              'rocfft': PRISIM_CLOSURE_ROCFFT}[phase_route]
+        self._check(self._lib.prisim_closure_delay_spectra(
+            self._h, _ptr(ph), nrows, _ptr(x), int(nt), int(nbl), nchan, _ptr(lg), _ptr(cj), _ptr(fw), _ptr(bw), _ptr(mk),
+            0 if mk is None else mk.shape[0], _ptr(mi), pr, nwin, _ptr(w), m, float(df), nres, 0 if mo is None else mo.size, _ptr(mo),
+            _ptr(mi_), _ptr(mw), _ptr(ps), flag, r, int(budget_bytes), _ptr(out.get('phase')), _ptr(out.get('over')),
+            _ptr(out.get('over_power')), _ptr(out.get('res')), _ptr(out.get('res_power')), C.byref(st)), 'prisim_closure_delay_spectra')
+        out['stats'] = self._cpdelay_stats(st)
+        out['stats']['resident'] = phases is None and x is None
+        return out
+
+    def closure_power(self, spectra, scale, want=('individual',), budget_bytes=CLOSURE_BUDGET):
+        """Power spectra of closure-phase delay spectra on the device (prisim_closure_power).  spectra (n0, nwin, ...) complex128, scale
+        (nwin,); want: any of 'individual' (|x|^2 scale, spectra's shape), 'auto' (mean over axis 0 of |x|^2, times scale; axis 0 kept
+        with one entry) and 'cross' ((scale |sum over axis 0 of x|^2 - n0 auto) / (n0 (n0 - 1)); n0 >= 2).  Returns a dict of the wanted
+        outputs and 'stats'."""
+        x = NP.ascontiguousarray(spectra, dtype=NP.complex128)
+        if x.ndim < 2:
+            raise ValueError('spectra must be (n0, nwin, ...)')
+        n0, nwin = x.shape[0], x.shape[1]
+        inner = int(NP.prod(x.shape[2:], dtype=NP.int64))
+        sc = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(scale, dtype=NP.float64).ravel(), (nwin,)))
+        bits = {'individual': PRISIM_CPPOWER_INDIVIDUAL, 'auto': PRISIM_CPPOWER_AUTO, 'cross': PRISIM_CPPOWER_CROSS}
+        flag = 0
+        for name in want:
+            flag |= bits[name]
+        out = {name: NP.empty(x.shape if name == 'individual' else (1,) + x.shape[1:], dtype=NP.float64) for name in want}
+        st = PrisimCpdelayStats()
+        self._check(self._lib.prisim_closure_power(self._h, n0, nwin, inner, _ptr(x), _ptr(sc), flag, int(budget_bytes),
+                                                   _ptr(out.get('individual')), _ptr(out.get('auto')), _ptr(out.get('cross')),
+                                                   C.byref(st)), 'prisim_closure_power')
+        out['stats'] = self._cpdelay_stats(st)
+        return out
 
     # ---- instrument gain tables (include/prisim_gains.h) ----
     @staticmethod

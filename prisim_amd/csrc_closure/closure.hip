@@ -33,8 +33,7 @@
 #include <string>
 #include <vector>
 
-#include "../csrc/ctx_internal.h"
-#include "../../include/prisim_closure.h"
+#include "closure_internal.h"
 
 namespace {
 
@@ -289,19 +288,18 @@ int grid_for(const prisim_ctx* ctx, int64_t n) {
 
 }  // namespace
 
-extern "C" {
-
-int prisim_closure_phase(prisim_ctx* ctx, const double* cube, int64_t nt, int64_t nbl, int64_t nchan, const int32_t* legs,
+// The call itself.  With a sink (closure_internal.h) the phases of every chunk are handed on where they lie, and the caller's
+// out_triplets / out_phase may each be null: what is null is not downloaded.
+int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_t nbl, int64_t nchan, const int32_t* legs,
                          const int32_t* conj, int64_t ntriads, const double* freq_wts, const double* bpwts, const double* masks,
                          int64_t nmask, const int32_t* mask_index, int32_t route, int64_t budget_bytes, double* out_triplets,
-                         double* out_phase, prisim_closure_stats* stats) {
-  return guarded(ctx, [&]() -> int {
+                         double* out_phase, prisim_closure_stats* stats, const ClosureSink* sink) {
   if (!ctx) return PRISIM_EINVAL;
   const auto wall0 = std::chrono::steady_clock::now();
   if (nt < 1 || nbl < 1 || nchan < 1 || ntriads < 1) return fail(ctx, PRISIM_EINVAL, "need nt, nbl, nchan and ntriads >= 1");
   if (nt > (int64_t)1 << 30 || nchan > (int64_t)1 << 30 || nbl > (int64_t)1 << 30)
     return fail(ctx, PRISIM_EINVAL, "nt, nbl and nchan must fit in 32 bits");
-  if (!legs || !conj || !freq_wts || !bpwts || !out_triplets || !out_phase) return fail(ctx, PRISIM_EINVAL, "null array");
+  if (!legs || !conj || !freq_wts || !bpwts || (!sink && (!out_triplets || !out_phase))) return fail(ctx, PRISIM_EINVAL, "null array");
   if (!cube) {
     if (!ctx->array_set || !ctx->cube.p) return fail(ctx, PRISIM_ESTATE, "no resident visibility cube: set the array first");
     if (nbl != ctx->nbl || nchan != ctx->nchan || nt > ctx->nt_max)
@@ -364,7 +362,7 @@ int prisim_closure_phase(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
   const int64_t nct = (nchan + kTile - 1) / kTile, ntt = (nt + kTile - 1) / kTile;
   const int64_t per = nchan * nt;
   const int64_t trip_triad = 3 * per * 16, phase_triad = per * 8, fbuf_triad = rt == PRISIM_CLOSURE_ROCFFT ? 3 * per * 16 : 0;
-  const int64_t per_triad = trip_triad + phase_triad + fbuf_triad;
+  const int64_t per_triad = trip_triad + phase_triad + fbuf_triad + (sink ? sink->bytes_per_triad : 0);
   const int64_t budget = budget_bytes > 0 ? budget_bytes : kDefaultBudget;
   int64_t tc = std::max<int64_t>(1, std::min<int64_t>(ntriads, budget / (kMaxStreams * per_triad)));
   const int64_t blocks_triad = tiled ? nct * ntt : 3 * ntiles;                      // grid x of the tiled kernels
@@ -401,6 +399,8 @@ int prisim_closure_phase(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
     HIPCHK(ctx, hipEventCreate(&st.k0[i]));
     HIPCHK(ctx, hipEventCreate(&st.k1[i]));
   }
+  if (sink)
+    if (int rc = sink->prepare(tc, ntriads - (nchunks - 1) * tc, nstreams, st.s)) return rc;
   if (rt == PRISIM_CLOSURE_ROCFFT) {
     RocfftApi& F = g_rocfft;
     size_t wmax = 0;
@@ -503,10 +503,15 @@ int prisim_closure_phase(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
       hipLaunchKernelGGL(k_cl_phase, dim3((unsigned)grid_for(ctx, ne)), dim3(kThreads), 0, sc, P);
       HIPCHK(ctx, hipGetLastError());
     }
+    if (sink)
+      if (int rc = sink->kernels(i, sc, T0, tn, d_phase[i])) return rc;
     HIPCHK(ctx, hipEventRecord(st.k1[i], sc));
     st.timed[i] = true;
-    HIPCHK(ctx, hipMemcpyAsync(out_triplets + 2 * (size_t)T0 * 3 * per, d_trip[i], (size_t)tn * trip_triad, hipMemcpyDeviceToHost, sc));
-    HIPCHK(ctx, hipMemcpyAsync(out_phase + (size_t)T0 * per, d_phase[i], (size_t)tn * phase_triad, hipMemcpyDeviceToHost, sc));
+    if (out_triplets)
+      HIPCHK(ctx, hipMemcpyAsync(out_triplets + 2 * (size_t)T0 * 3 * per, d_trip[i], (size_t)tn * trip_triad, hipMemcpyDeviceToHost, sc));
+    if (out_phase) HIPCHK(ctx, hipMemcpyAsync(out_phase + (size_t)T0 * per, d_phase[i], (size_t)tn * phase_triad, hipMemcpyDeviceToHost, sc));
+    if (sink)
+      if (int rc = sink->download(i, sc, T0, tn)) return rc;
   }
   for (int i = 0; i < nstreams; ++i) {
     HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
@@ -524,13 +529,24 @@ int prisim_closure_phase(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
     stats->chunks = nchunks;
     stats->chunk_triads = tc;
     stats->kernel_bytes = ntriads * per * point;
-    stats->download_bytes = ntriads * (trip_triad + phase_triad);
+    stats->download_bytes = ntriads * ((out_triplets ? trip_triad : 0) + (out_phase ? phase_triad : 0));
     stats->route = rt;
     stats->streams = nstreams;
     stats->tile = (int32_t)tile;
     stats->lds_bytes = (int32_t)lds;
   }
   return PRISIM_OK;
+}
+
+extern "C" {
+
+int prisim_closure_phase(prisim_ctx* ctx, const double* cube, int64_t nt, int64_t nbl, int64_t nchan, const int32_t* legs,
+                         const int32_t* conj, int64_t ntriads, const double* freq_wts, const double* bpwts, const double* masks,
+                         int64_t nmask, const int32_t* mask_index, int32_t route, int64_t budget_bytes, double* out_triplets,
+                         double* out_phase, prisim_closure_stats* stats) {
+  return guarded(ctx, [&]() -> int {
+    return closure_phase_chunks(ctx, cube, nt, nbl, nchan, legs, conj, ntriads, freq_wts, bpwts, masks, nmask, mask_index, route,
+                                budget_bytes, out_triplets, out_phase, stats, nullptr);
   });
 }
 

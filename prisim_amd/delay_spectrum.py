@@ -20,8 +20,12 @@ Stacks of runs: ``delay_transform_allruns`` (:1475-1618), ``subband_delay_transf
 ``DelayPowerSpectrum.compute_power_spectrum_allruns`` (:4067-4195) take the caller's (..., nbl, nchan, n_acc) visibilities, whose leading
 axes are runs, and stream them through include/prisim_runs.h (prisim_amd/csrc_runs/) in the reference's layout, with no host transpose.
 
-Not here (out of scope): closure-phase delay spectra and their power spectra (the closure phases of the visibilities themselves are
-InterferometerArray.getClosurePhase), FITS persistence.
+Closure phases: ``DelaySpectrum.subband_delay_transform_closure_phase`` (:2518-2972) transforms exp(-i closure phase) of every antenna
+triad in sub-bands, the phases formed on the device by InterferometerArray.getClosurePhase's code and consumed there
+(include/prisim_cpdelay.h, prisim_amd/csrc_closure/cpdelay.hip); ``DelayPowerSpectrum.compute_individual_closure_phase_power_spectrum``
+(:4199-4348) and ``compute_averaged_closure_phase_power_spectrum`` (:4352-4540) form their power spectra there.
+
+Not here (out of scope): FITS persistence.
 
 Cosmology.  The reference takes ``astropy.cosmology.Planck15.clone(H0=100)`` (:34-35); astropy is not in this image, so ``cosmo100`` here
 is this module's own flat LambdaCDM with Planck15's Om0 = 0.3075, Tcmb0 = 2.7255 K, Neff = 3.046 (photons + massless neutrinos in the
@@ -861,6 +865,129 @@ class DelaySpectrum(object):
                 'npad': npad, 'lags': lags, 'vis_lag': vis_lag.reshape((nwin,) + vis.shape[:-3] + (nbl, nres, nt)),
                 'lag_kernel': kernel.reshape((nwin,) + ones + (nbl, kernel.shape[-2], nt)), 'lag_corr_length': (1 / bw_eff) / dlag}
 
+    def subband_delay_transform_closure_phase(self, bw_eff, cpinfo=None, antenna_triplets=None, specsmooth_info=None,
+                                              delay_filter_info=None, spectral_window_info=None, freq_center=None, shape=None,
+                                              fftpow=None, pad=None, action=None, verbose=True):
+        """Sub-band delay spectra of closure phases on the GPU (:2518-2972, prisim_closure_delay_spectra): for every antenna triad,
+        snapshot and window of subband_freq_wts, exp(-1j closure phase) times the window, zero-padded to M = nchan + int(nchan pad) lags
+        and transformed, M df fftshift(ifft(.)) (:2943), and that FFT-resampled (DSP.downsampler 'FFT', read in
+        prisim_amd/dsp_readings.py) to round(M / factor) lags, factor = min(M df / bw_eff) (:2955-2962).
+
+        cpinfo None: the closure phases are those InterferometerArray.getClosurePhase(antenna_triplets, specsmooth_info,
+        delay_filter_info, spectral_window_info) gives, formed on the device by the same code and transformed where they lie -- neither
+        the triplets nor the phases are downloaded -- for skyvis, and for vis / noise when those cubes exist.  cpinfo given: its
+        'closure_phase_skyvis' / '_vis' / '_noise' arrays (ntriplets, ..., nchan, nt), any number of middle axes, are uploaded and
+        transformed; antenna_triplets and the three *_info arguments are then unused, as in the reference.
+
+        Returns, for action None or 'return_resampled': antenna_triplets, baseline_triplets, freq_center, bw_eff, freq_wts, lags and
+        lag_kernel (linearly interpolated at arange(0, M, factor)), lag_corr_length = (1 / bw_eff) / dlag, and the spectra
+        (ntriplets, ..., n_win, nres, nt); the M-lag spectra are then not downloaded.  For 'return_oversampled': freq_center, shape,
+        freq_wts, bw_eff, npad, lags, lag_kernel, lag_corr_length = nchan / sum(freq_wts) and the spectra (ntriplets, ..., n_win, M, nt).
+        No attribute of self is set; the stats of the device calls are left in ia.closure_delay_stats, per key.
+
+        Reproduced literally (one test each in tests/test_cpdelay.py):
+          - the oversampled dictionary carries no antenna_triplets / baseline_triplets (:2937 rebinds the result);
+          - windows are sorted by channel while freq_center / bw_eff keep the given order;
+          - lag_kernel is the transform of the windows alone, of shape (1, ..., n_win, M, 1);
+          - lag_corr_length of the resampled result is (1 / bw_eff) / dlag.
+        Departures (one test each):
+          - the default freq_center is f[int(nchan / 2)] (the reference indexes with a float);
+          - fftpow other than 1 raises NotImplementedError (dsp_readings.window_fftpow), and so does specsmooth_info when cpinfo is None
+            (getClosurePhase);
+          - a closure_phase_* entry that is None (a noiseless array) is skipped and comes back as None;
+          - a cpinfo with none of the three keys raises ValueError (the reference: NameError on available_CP_key);
+          - M or the resampled length above PRISIM_CPDELAY_MAX_LEN, and an action other than None, 'return_resampled' or
+            'return_oversampled', raise ValueError before any device work (the reference computes first)."""
+        f, df, ia = self.f, self.df, self.ia
+        nchan = f.size
+        if not isinstance(bw_eff, (int, float, list, NP.ndarray)):
+            raise TypeError('Value of effective bandwidth must be a scalar, list or numpy array')
+        # the checks of :2855-2900 are those of subband_delay_transform for one key (both keys given the caller's value)
+        both = lambda v: None if v is None else {'sim': v, 'cc': v}
+        if freq_center is not None and not isinstance(freq_center, (int, float, list, NP.ndarray)):
+            raise TypeError('Values(s) of frequency center must be scalar, list or numpy array')
+        bw, fc, shp, fpow, pd = _check_subband_args(f, df, both(bw_eff), both(freq_center), both(shape), both(fftpow), both(pad), False,
+                                                    verbose)
+        bw_eff, freq_center, shape, fftpow, pad = bw['sim'], fc['sim'], shp['sim'], fpow['sim'], pd['sim']
+        if cpinfo is not None and not isinstance(cpinfo, dict):
+            raise TypeError('Input cpinfo must be a dictionary')
+        if action is not None and (not isinstance(action, str) or action.lower() not in ('return_resampled', 'return_oversampled')):
+            raise ValueError('Invalid action specified')
+        oversampled = action is not None and action.lower() == 'return_oversampled'
+        freq_wts = subband_freq_wts(f, df, bw_eff, freq_center, shape, fftpow)
+        nwin = freq_wts.shape[0]
+        npad = int(nchan * pad)
+        m = nchan + npad
+        if m > _abi.PRISIM_CPDELAY_MAX_LEN:
+            raise ValueError('closure-phase delay spectra of %d lags exceed PRISIM_CPDELAY_MAX_LEN = %d' % (m, _abi.PRISIM_CPDELAY_MAX_LEN))
+        factor = NP.min(m * df / bw_eff)
+        nres = DSP.fft_downsample_length(m, factor)
+        if not 1 <= nres <= _abi.PRISIM_CPDELAY_MAX_LEN:
+            raise ValueError('resampled closure-phase delay spectra of %d lags must lie in 1 .. PRISIM_CPDELAY_MAX_LEN = %d'
+                             % (nres, _abi.PRISIM_CPDELAY_MAX_LEN))
+        keys = ('closure_phase_skyvis', 'closure_phase_vis', 'closure_phase_noise')
+        want = ('over',) if oversampled else ('res',)
+        kw = {'nres': 0 if oversampled else nres, 'want': want}
+        spectra, stats, nlead = {}, {}, 1
+        if cpinfo is not None:
+            triplets = {'antenna_triplets': cpinfo['antenna_triplets'], 'baseline_triplets': cpinfo['baseline_triplets']}     # :2907
+            have = [key for key in cpinfo if key in keys]
+            if not have:
+                raise ValueError('Input cpinfo holds none of closure_phase_skyvis, closure_phase_vis, closure_phase_noise')
+            arrays = {}
+            for key in have:
+                if cpinfo[key] is None:
+                    continue
+                arr = NP.asarray(cpinfo[key], dtype=NP.float64)
+                if arr.ndim < 3 or arr.shape[-2] != nchan:
+                    raise ValueError('%s must have shape ntriplets x ... x nchan x ntimes' % key)
+                arrays[key] = arr
+                nlead = arr.ndim - 2                                                      # (:2945 takes the last key found)
+            ctx = ia._ctx
+            for key in have:
+                if key not in arrays:
+                    spectra[key] = None
+                    continue
+                out = ctx.closure_delay_spectra(freq_wts, m, df, phases=arrays[key], **kw)
+                spectra[key], stats[key] = out[want[0]], out['stats']
+        else:
+            p = RI._closure_prepare(ia, antenna_triplets, delay_filter_info, specsmooth_info, spectral_window_info, False)
+            triplets = {'antenna_triplets': p['antenna_triplets'], 'baseline_triplets': p['baseline_triplets']}
+            ntriads, nt = p['legs'].shape[0], p['nt']
+            for key, cube in ((keys[0], None if p['resident'] else ia.skyvis_freq), (keys[1], ia.vis_freq), (keys[2], ia.vis_noise_freq)):
+                if key != keys[0] and cube is None:
+                    spectra[key] = None
+                    continue
+                if not ntriads:
+                    spectra[key] = NP.zeros((0, nwin, m if oversampled else nres, nt), dtype=NP.complex128)
+                    continue
+                out = ia._ctx.closure_delay_spectra(freq_wts, m, df, cube=cube, legs=p['legs'], conj=p['conj'], bpwts=p['bpwts'],
+                                                    freq_wts=p['freq_wts'], masks=p['masks'], mask_index=p['mask_index'], nt=nt, **kw)
+                spectra[key], stats[key] = out[want[0]], out['stats']
+        ia.closure_delay_stats = stats
+        lags = DSP.spectral_axis(m, delx=df, use_real=False, shift=True)
+        padded = NP.zeros((nwin, m), dtype=NP.float64)
+        padded[:, :nchan] = freq_wts
+        lag_kernel = (NP.fft.fftshift(NP.fft.ifft(padded, axis=-1), axes=-1) * m * df).reshape((1,) * nlead + (nwin, m, 1))      # :2945
+        if verbose:
+            print('\tSub-band(s) delay transform computed')
+        if oversampled:
+            result = {'freq_center': freq_center, 'shape': shape, 'freq_wts': freq_wts, 'bw_eff': bw_eff, 'npad': npad, 'lags': lags,
+                      'lag_corr_length': nchan / NP.sum(freq_wts, axis=-1)}
+            result.update(spectra)
+            result['lag_kernel'] = lag_kernel
+            return result
+        result = dict(triplets)
+        result.update({'freq_center': freq_center, 'bw_eff': bw_eff, 'freq_wts': freq_wts})
+        result['lags'] = DSP.downsampler(lags, factor, axis=-1, method='interp', kind='linear')
+        result['lag_kernel'] = DSP.downsampler(lag_kernel, factor, axis=-2, method='interp', kind='linear')
+        dlag = result['lags'][1] - result['lags'][0]
+        result['lag_corr_length'] = (1 / bw_eff) / dlag
+        result.update(spectra)
+        if verbose:
+            print('\tDownsampled Sub-band(s) delay transform computed')
+        return result
+
 
 
 SUBBAND_KEYS = ('cc', 'sim')
@@ -1191,6 +1318,85 @@ class DelayPowerSpectrum(object):
             key = 'subband'
         power, _ = self.ds.ia._ctx.runs_power(v1, v2, factor, cross=(mode == 'cross'))
         return {key: power}
+
+    # ------------------------------------------------------------------------------------------
+    # power spectra of closure-phase delay spectra (prisim_closure_power, include/prisim_cpdelay.h)
+    CP_KEYS = ('closure_phase_skyvis', 'closure_phase_vis', 'closure_phase_noise')
+
+    def _closure_phase_k(self, cpds):
+        """z, kprll (n_win, nlags), kperp (n_win, ntriplets, 3), horizon_kprll_limits (n_acc, n_win, ntriplets, 3, 2) and
+        factor = (1 / bw_eff) (drz_los / bw_eff) of a closure-phase delay spectrum dictionary (:4314-4342, :4494-4522)."""
+        fc = NP.asarray(cpds['freq_center'])
+        bw_eff = NP.asarray(cpds['bw_eff'])
+        z = REST_FREQ_HI / fc - 1
+        ntrip = len(cpds['antenna_triplets'])
+        kprll = NP.empty((fc.size, cpds['lags'].size))
+        kperp = NP.empty((fc.size, ntrip, 3))
+        horizon_kprll_limits = NP.empty((self.ds.n_acc, fc.size, ntrip, 3, 2))
+        bl_lengths = [NP.sqrt(NP.sum(NP.asarray(cpds['baseline_triplets'][i]) ** 2, axis=1)) for i in range(ntrip)]
+        for zind, redshift in enumerate(z):
+            kprll[zind, :] = self.k_parallel(cpds['lags'], redshift, action='return')
+            for ti in range(ntrip):
+                kperp[zind, ti, :] = self.k_perp(bl_lengths[ti], redshift, action='return')
+                hdl = bl_lengths[ti].reshape(1, -1, 1) / FCNST.c
+                hdl = NP.concatenate((hdl, -hdl), axis=2)                                    # (1, 3, 2): upper and lower limit
+                horizon_kprll_limits[:, zind, ti, :, :] = self.k_parallel(hdl, redshift, action='return')
+        drz_los = self.comoving_los_depth(bw_eff, z, action='return')
+        factor = (1 / bw_eff) * (drz_los / bw_eff)                                           # jacobian1 * jacobian2, :4340-4342
+        return {'z': z, 'kprll': kprll, 'kperp': kperp, 'horizon_kprll_limits': horizon_kprll_limits}, NP.ravel(factor)
+
+    def compute_individual_closure_phase_power_spectrum(self, closure_phase_delay_spectra):
+        """Power spectra of closure-phase delay spectra, triad by triad, on the GPU (:4199-4348, prisim_closure_power):
+        abs(spectrum)**2 * factor with factor = drz_los / bw_eff**2 per window.  Takes a dictionary of
+        DelaySpectrum.subband_delay_transform_closure_phase; returns z, kprll (n_win, nlags), kperp (n_win, ntriplets, 3),
+        horizon_kprll_limits (n_acc, n_win, ntriplets, 3, 2) and the power of every closure_phase_* key present (None stays None).
+        Reproduced literally: the factor is reshaped to (1, -1, 1, 1), so the spectra must be 4-D (ntriplets, n_win, nlags, nt) --
+        anything else raises ValueError here (the reference broadcasts or fails in numpy).  The caller's dictionary is not modified."""
+        cpds = closure_phase_delay_spectra
+        out, factor = self._closure_phase_k(cpds)
+        todo = [key for key in self.CP_KEYS if key in cpds]
+        for key in todo:
+            if cpds[key] is not None and (NP.ndim(cpds[key]) != 4 or NP.shape(cpds[key])[1] != factor.size):
+                raise ValueError('%s must have shape ntriplets x n_win x nlags x nt' % key)
+        for key in todo:
+            if cpds[key] is None:
+                out[key] = None
+            elif NP.size(cpds[key]) == 0:
+                out[key] = NP.zeros(NP.shape(cpds[key]))
+            else:
+                out[key] = self.ds.ia._ctx.closure_power(cpds[key], factor, want=('individual',))['individual']
+        return out
+
+    def compute_averaged_closure_phase_power_spectrum(self, closure_phase_delay_spectra):
+        """Power spectra of closure-phase delay spectra averaged over axis 0 on the GPU (:4352-4540, prisim_closure_power).  Returns z,
+        kprll, kperp, horizon_kprll_limits and {'auto': {key: mean over axis 0 of abs(spectrum)**2, times factor}, 'cross': {key:
+        (factor abs(sum over axis 0 of spectrum)**2 - n0 auto) / (n0 (n0 - 1))}}, each (1, ..., n_win, nlags, nt); factor =
+        drz_los / bw_eff**2 sits on axis -3 and axis 0 is averaged whatever it holds, as in the reference.  None stays None.
+        Departures: one entry on axis 0 raises ValueError before any device work (the reference: ZeroDivisionError in the cross term,
+        after the auto term was computed); spectra of fewer than four axes, where axis 0 is the window axis itself, raise ValueError.
+        The caller's dictionary is not modified."""
+        cpds = closure_phase_delay_spectra
+        out, factor = self._closure_phase_k(cpds)
+        todo = [key for key in self.CP_KEYS if key in cpds]
+        for key in todo:
+            if cpds[key] is None:
+                continue
+            shp = NP.shape(cpds[key])
+            if len(shp) < 4 or shp[-3] != factor.size:
+                raise ValueError('%s must have shape n0 x ... x n_win x nlags x nt' % key)
+            if shp[0] < 2:
+                raise ValueError('%s has %d entry on axis 0: the cross power divides by n0 (n0 - 1)' % (key, shp[0]))
+        out['auto'], out['cross'] = {}, {}
+        for key in todo:
+            if cpds[key] is None:
+                out['auto'][key] = out['cross'][key] = None
+                continue
+            x = NP.asarray(cpds[key])
+            nmid = int(NP.prod(x.shape[1:-3], dtype=NP.int64))
+            r = self.ds.ia._ctx.closure_power(x.reshape(x.shape[0], nmid * factor.size, -1), NP.tile(factor, nmid), want=('auto', 'cross'))
+            for mode in ('auto', 'cross'):
+                out[mode][key] = r[mode].reshape((1,) + x.shape[1:])
+        return out
 
     def _subband_k(self, lags, zs):
         """kprll (n_win, nlags), kperp (n_win, nbl) and horizon_kprll_limits (n_acc, n_win, nbl, 2) at the redshifts zs (:4011-4018)."""

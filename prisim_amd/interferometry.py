@@ -329,6 +329,104 @@ def _lst_and_jd(timeobj, lst):
     raise TypeError('timeobj must be a Time-like object, a (jd, lst_deg) pair, or a Julian date with lst given.')
 
 
+def _closure_prepare(self, antenna_triplets, delay_filter_info, specsmooth_info, spectral_window_info, unique):
+    """What getClosurePhase prepares before its device calls (interferometry.py:7296-7485), for it and for
+    DelaySpectrum.subband_delay_transform_closure_phase: the argument checks in the reference's order, the spectral window, the filter
+    masks, the leg table, bp * bp_wts, and whether the noiseless cube can be read where it lies on the device.  `self` is the array (or a
+    stand-in with the attributes read)."""
+    from . import delay_spectrum as DS
+    from . import dsp_readings as DSP
+    if antenna_triplets is None:
+        antenna_triplets, _ = self.getThreePointCombinations(unique=unique)
+    if not isinstance(antenna_triplets, list):
+        raise TypeError('Input antenna triplets must be a list of triplet tuples')
+    if specsmooth_info is not None:
+        raise NotImplementedError("specsmooth_info is not supported: the reference's 'median' branch indexes specsmooth_info["
+                                  "specsmooth_info['window_size']] and cannot run, and 'interp' redraws noise from numpy's global "
+                                  "generator")
+    nchan = self.channels.size
+    if spectral_window_info is not None:                                       # :7296-7344
+        freq_center, bw_eff = spectral_window_info['freq_center'], spectral_window_info['bw_eff']
+        shape, fftpow = spectral_window_info['shape'], spectral_window_info['fftpow']
+        if freq_center is None:
+            freq_center = self.channels[nchan // 2]
+        shape = 'rect' if shape is None else shape.lower()
+        if bw_eff is None:
+            if shape == 'rect':
+                bw_eff = nchan * self.freq_resolution
+            elif shape == 'bhw':
+                bw_eff = 0.5 * nchan * self.freq_resolution
+            else:
+                raise ValueError('Specified window shape not currently supported')
+        if fftpow is None:
+            fftpow = 1.0
+        elif isinstance(fftpow, (int, float)):
+            if fftpow <= 0.0:
+                raise ValueError('Value fftpow must be positive')
+        else:
+            raise ValueError('Value fftpow must be a scalar (int or float)')
+        wts = DS.subband_freq_wts(self.channels, self.freq_resolution, NP.asarray(bw_eff, dtype=NP.float64).reshape(-1),
+                                  NP.asarray(freq_center, dtype=NP.float64).reshape(-1), shape, fftpow)
+        if wts.shape[0] != 1:
+            raise ValueError('freq_center is outside the band')
+        freq_wts = wts[0]
+    else:
+        freq_wts = NP.asarray(1.0).reshape(-1)
+
+    masks = mask_index = None
+    if delay_filter_info is not None:                                          # :7350-7399
+        fft_delays = DSP.spectral_axis(nchan, delx=self.freq_resolution, shift=False, use_real=False)
+        dtau = fft_delays[1] - fft_delays[0]
+        if not isinstance(delay_filter_info, dict):
+            raise TypeError('Delay filter info must be specified as a dictionary')
+        filter_mode = delay_filter_info.get('mode', 'discard')
+        if filter_mode.lower() not in ['discard', 'retain']:
+            raise ValueError('Invalid delay filter mode specified')
+        filter_type = delay_filter_info.get('type', 'horizon')
+        if filter_type.lower() not in ['horizon', 'regular']:
+            raise ValueError('Invalid delay filter type specified')
+        if filter_type.lower() == 'regular':
+            if ('min' not in delay_filter_info) or ('width' not in delay_filter_info):
+                raise KeyError('Keys "min" and "width" must be specified in input delay_filter_info')
+            delay_min, delay_width = delay_filter_info['min'], delay_filter_info['width']
+            if delay_min is None:
+                delay_min = 0.0
+            elif isinstance(delay_min, (int, float)):
+                delay_min = max([0.0, delay_min])
+            else:
+                raise TypeError('Minimum delay in the filter must be a scalar value (int or float)')
+            if isinstance(delay_width, (int, float)):
+                if delay_width <= 0.0:
+                    raise ValueError('Delay filter width must be positive')
+            else:
+                raise TypeError('Delay width in the filter must be a scalar value (int or float)')
+        else:
+            delay_width = delay_filter_info.get('width', 0.0)
+            if delay_width is None:
+                delay_width = 0.0
+            elif isinstance(delay_width, (int, float)):
+                if delay_width <= 0.0:
+                    raise ValueError('Delay filter width must be positive')
+            else:
+                raise TypeError('Delay width in the filter must be a scalar value (int or float)')
+        delay_width = delay_width * dtau
+        masks, mask_index = closure_filter_masks(fft_delays, filter_type.lower(), filter_mode.lower(),
+                                                 delay_min if filter_type.lower() == 'regular' else 0.0, delay_width,
+                                                 self.baseline_lengths)
+
+    legs, conj, blvecttriplets = self.closure_leg_table(antenna_triplets)
+    nbl = self.baselines.shape[0]
+    if self.skyvis_freq is None and not getattr(self, '_cube', None):
+        raise ValueError('no visibilities: call observe() first')
+    nt = len(self._cube)
+    # the noiseless cube is read where it lies when the device slots [0, nt) hold skyvis_freq itself, in fp64 (the rule of add_noise)
+    resident = bool(self._device_in_step) and nt <= self._reserved and all(
+        sn.dtype == NP.complex128 and (not isinstance(sn, _DeviceSlot) or sn.slot == i) for i, sn in enumerate(self._cube))
+    bpwts = NP.asarray(self.bp * self.bp_wts, dtype=NP.float64).reshape(nbl, nchan, -1)      # :7433, formed once for the call
+    return {'antenna_triplets': antenna_triplets, 'freq_wts': freq_wts, 'masks': masks, 'mask_index': mask_index, 'legs': legs,
+            'conj': conj, 'baseline_triplets': blvecttriplets, 'nbl': nbl, 'nchan': nchan, 'nt': nt, 'resident': resident, 'bpwts': bpwts}
+
+
 def closure_filter_masks(fft_delays, filter_type, filter_mode, delay_min, delay_width, baseline_lengths):
     """The filter_unmask vectors of getClosurePhase's delay filter (interferometry.py:7536-7543 'regular', :7570-7587 'horizon') on the
     unshifted FFT delay axis: ones with zeros on the filtered delays.  'regular': one mask, zero where delay_min <= |tau| <= delay_min +
@@ -2308,95 +2406,10 @@ class InterferometerArray(object):
         with skyvis_freq; the other cubes are uploaded once each.  bp * bp_wts is handed over dense, (nbl, nchan, nt) float64, also when
         it is constant in time; it and an uploaded cube lie on the device for the call, outside the chunk budget.  The stats of the
         device calls are left in closure_stats, per cube.  There is no CPU path."""
-        from . import delay_spectrum as DS
-        from . import dsp_readings as DSP
-        if antenna_triplets is None:
-            antenna_triplets, _ = self.getThreePointCombinations(unique=unique)
-        if not isinstance(antenna_triplets, list):
-            raise TypeError('Input antenna triplets must be a list of triplet tuples')
-        if specsmooth_info is not None:
-            raise NotImplementedError("specsmooth_info is not supported: the reference's 'median' branch indexes specsmooth_info["
-                                      "specsmooth_info['window_size']] and cannot run, and 'interp' redraws noise from numpy's global "
-                                      "generator")
-        nchan = self.channels.size
-        if spectral_window_info is not None:                                       # :7296-7344
-            freq_center, bw_eff = spectral_window_info['freq_center'], spectral_window_info['bw_eff']
-            shape, fftpow = spectral_window_info['shape'], spectral_window_info['fftpow']
-            if freq_center is None:
-                freq_center = self.channels[nchan // 2]
-            shape = 'rect' if shape is None else shape.lower()
-            if bw_eff is None:
-                if shape == 'rect':
-                    bw_eff = nchan * self.freq_resolution
-                elif shape == 'bhw':
-                    bw_eff = 0.5 * nchan * self.freq_resolution
-                else:
-                    raise ValueError('Specified window shape not currently supported')
-            if fftpow is None:
-                fftpow = 1.0
-            elif isinstance(fftpow, (int, float)):
-                if fftpow <= 0.0:
-                    raise ValueError('Value fftpow must be positive')
-            else:
-                raise ValueError('Value fftpow must be a scalar (int or float)')
-            wts = DS.subband_freq_wts(self.channels, self.freq_resolution, NP.asarray(bw_eff, dtype=NP.float64).reshape(-1),
-                                      NP.asarray(freq_center, dtype=NP.float64).reshape(-1), shape, fftpow)
-            if wts.shape[0] != 1:
-                raise ValueError('freq_center is outside the band')
-            freq_wts = wts[0]
-        else:
-            freq_wts = NP.asarray(1.0).reshape(-1)
-
-        masks = mask_index = None
-        if delay_filter_info is not None:                                          # :7350-7399
-            fft_delays = DSP.spectral_axis(nchan, delx=self.freq_resolution, shift=False, use_real=False)
-            dtau = fft_delays[1] - fft_delays[0]
-            if not isinstance(delay_filter_info, dict):
-                raise TypeError('Delay filter info must be specified as a dictionary')
-            filter_mode = delay_filter_info.get('mode', 'discard')
-            if filter_mode.lower() not in ['discard', 'retain']:
-                raise ValueError('Invalid delay filter mode specified')
-            filter_type = delay_filter_info.get('type', 'horizon')
-            if filter_type.lower() not in ['horizon', 'regular']:
-                raise ValueError('Invalid delay filter type specified')
-            if filter_type.lower() == 'regular':
-                if ('min' not in delay_filter_info) or ('width' not in delay_filter_info):
-                    raise KeyError('Keys "min" and "width" must be specified in input delay_filter_info')
-                delay_min, delay_width = delay_filter_info['min'], delay_filter_info['width']
-                if delay_min is None:
-                    delay_min = 0.0
-                elif isinstance(delay_min, (int, float)):
-                    delay_min = max([0.0, delay_min])
-                else:
-                    raise TypeError('Minimum delay in the filter must be a scalar value (int or float)')
-                if isinstance(delay_width, (int, float)):
-                    if delay_width <= 0.0:
-                        raise ValueError('Delay filter width must be positive')
-                else:
-                    raise TypeError('Delay width in the filter must be a scalar value (int or float)')
-            else:
-                delay_width = delay_filter_info.get('width', 0.0)
-                if delay_width is None:
-                    delay_width = 0.0
-                elif isinstance(delay_width, (int, float)):
-                    if delay_width <= 0.0:
-                        raise ValueError('Delay filter width must be positive')
-                else:
-                    raise TypeError('Delay width in the filter must be a scalar value (int or float)')
-            delay_width = delay_width * dtau
-            masks, mask_index = closure_filter_masks(fft_delays, filter_type.lower(), filter_mode.lower(),
-                                                     delay_min if filter_type.lower() == 'regular' else 0.0, delay_width,
-                                                     self.baseline_lengths)
-
-        legs, conj, blvecttriplets = self.closure_leg_table(antenna_triplets)
-        nbl = self.baselines.shape[0]
-        if self.skyvis_freq is None and not getattr(self, '_cube', None):
-            raise ValueError('no visibilities: call observe() first')
-        nt = len(self._cube)
-        # the noiseless cube is read where it lies when the device slots [0, nt) hold skyvis_freq itself, in fp64 (the rule of add_noise)
-        resident = bool(self._device_in_step) and nt <= self._reserved and all(
-            sn.dtype == NP.complex128 and (not isinstance(sn, _DeviceSlot) or sn.slot == i) for i, sn in enumerate(self._cube))
-        bpwts = NP.asarray(self.bp * self.bp_wts, dtype=NP.float64).reshape(nbl, nchan, -1)      # :7433, formed once for the call
+        p = _closure_prepare(self, antenna_triplets, delay_filter_info, specsmooth_info, spectral_window_info, unique)
+        antenna_triplets, freq_wts, masks, mask_index = p['antenna_triplets'], p['freq_wts'], p['masks'], p['mask_index']
+        legs, conj, blvecttriplets, nchan, nt, resident, bpwts = (p['legs'], p['conj'], p['baseline_triplets'], p['nchan'], p['nt'],
+                                                                  p['resident'], p['bpwts'])
         out = {}
         self.closure_stats = {}                    # the device call's stats per cube: 'skyvis', 'vis', 'noisevis'
         for name, key in (('skyvis', 'skyvis'), ('vis', 'vis'), ('noise', 'noisevis')):
