@@ -74,6 +74,13 @@ PRISIM_CPDELAY_AUTO, PRISIM_CPDELAY_FUSED, PRISIM_CPDELAY_ROCFFT = -1, 0, 1
 CPDELAY_ROUTES = {PRISIM_CPDELAY_FUSED: 'fused', PRISIM_CPDELAY_ROCFFT: 'rocfft'}
 PRISIM_CPPOWER_INDIVIDUAL, PRISIM_CPPOWER_AUTO, PRISIM_CPPOWER_CROSS = 1, 2, 4
 
+# every symbol include/prisim_cpbins.h declares: day and LST binning of closure phases (prisim_amd/csrc_closure/cpbins.hip)
+CPBINS_EXPORTS = ('prisim_cphase_bin', 'prisim_cphase_stack_free')
+PRISIM_CPBINS_MAX_BIN = 256
+PRISIM_CPBINS_PHASE_FLAGS, PRISIM_CPBINS_BINNED = 0, 1
+CPBINS_WANT = {'wts': 1, 'eicp_mean': 2, 'eicp_median': 4, 'cp_mean': 8, 'cp_median': 16, 'rms': 32, 'mad': 64}
+PRISIM_CPBINS_ALL = 127
+
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
                  'prisim_gains_table_free', 'prisim_gains_apply')
@@ -221,6 +228,12 @@ class PrisimCpdelayStats(C.Structure):
                 ('streams', C.c_int32), ('tile', C.c_int32), ('lds_bytes', C.c_int32), ('reserved_', C.c_int32)]
 
 
+class PrisimCpbinsStats(C.Structure):
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('elements', C.c_int64), ('chunks', C.c_int64),
+                ('chunk_triads', C.c_int64), ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64),
+                ('max_bin', C.c_int32), ('resident_in', C.c_int32)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -337,6 +350,11 @@ def load_library():
     lib.prisim_closure_power.argtypes = [vp, i64, i64, i64, vp, vp, C.c_int32, i64, vp, vp, vp, C.POINTER(PrisimCpdelayStats)]
     for name in CPDELAY_EXPORTS:
         getattr(lib, name).restype = C.c_int
+    lib.prisim_cphase_bin.argtypes = [vp, C.c_int32, vp, vp, vp, vp, i64, i64, i64, i64, C.c_int32, i64, vp, vp, C.c_int32, C.c_int32, i64,
+                                      C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, vp, vp, vp, C.POINTER(PrisimCpbinsStats)]
+    lib.prisim_cphase_bin.restype = C.c_int
+    lib.prisim_cphase_stack_free.argtypes = [vp]
+    lib.prisim_cphase_stack_free.restype = None
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
                                              C.POINTER(vp), pst]
@@ -1181,6 +1199,72 @@ class Context(object):
         out['stats'] = self._cpdelay_stats(st)
         return out
 
+    # ---- day and LST binning of closure phases (include/prisim_cpbins.h) ----
+    def cphase_upload(self, phases, flags):
+        """Upload a (n0, n1, ntriads, nchan) stack of closure phases and its flags once; returns the resident CphaseStack."""
+        ph = NP.ascontiguousarray(phases, dtype=NP.float64)
+        fl = NP.ascontiguousarray(NP.asarray(flags) != 0, dtype=NP.uint8)
+        if ph.ndim != 4 or fl.shape != ph.shape:
+            raise ValueError('phases and flags must both be (n0, n1, ntriads, nchan)')
+        h = C.c_void_p()
+        st = PrisimCpbinsStats()
+        self._check(self._lib.prisim_cphase_bin(self._h, PRISIM_CPBINS_PHASE_FLAGS, _ptr(ph), None, None, _ptr(fl), *ph.shape, 0, 0, None,
+                                                None, 0, 0, 0, C.byref(h), None, None, None, None, None, None, None, None, C.byref(st)),
+                    'prisim_cphase_bin')
+        return CphaseStack(self, h, PRISIM_CPBINS_PHASE_FLAGS, ph.shape)
+
+    def cphase_bin(self, axis, offsets, members, phases=None, flags=None, binned=None, stack=None, want=tuple(CPBINS_WANT),
+                   mad_ignores_flags=False, keep=False, budget_bytes=CLOSURE_BUDGET):
+        """Flagged binning of one axis (0 or 1) of a (n0, n1, ntriads, nchan) stack of closure phases on the device
+        (prisim_cphase_bin).  The bins are the CSR pair offsets (nbins + 1,), members (indices on the axis).  The input is one of:
+        phases and flags (the native stack); binned = (mean phases, median phases, weights) of an earlier pass, masked where the weight
+        is <= 0; or stack, a resident CphaseStack of either kind (cphase_upload, or a call with keep=True).  want: any of 'wts',
+        'eicp_mean', 'eicp_median', 'cp_mean', 'cp_median', 'rms', 'mad', the outputs copied back; keep: the (mean phase, median phase,
+        weights) of this call stay on the device and come back as out['stack'].  Under the mask (no unmasked member) the device writes
+        eicp = 1, everything else 0.  Returns a dict of the wanted outputs and 'stats'."""
+        a = b = w = f = None
+        if stack is not None:
+            kind, shape = stack.kind, stack.shape
+        elif binned is not None:
+            kind = PRISIM_CPBINS_BINNED
+            a, b, w = (NP.ascontiguousarray(x, dtype=NP.float64) for x in binned)
+            shape = a.shape
+            if a.ndim != 4 or b.shape != shape or w.shape != shape:
+                raise ValueError('the binned arrays must all be (n0, n1, ntriads, nchan)')
+        else:
+            kind = PRISIM_CPBINS_PHASE_FLAGS
+            a = NP.ascontiguousarray(phases, dtype=NP.float64)
+            f = NP.ascontiguousarray(NP.asarray(flags) != 0, dtype=NP.uint8)
+            shape = a.shape
+            if a.ndim != 4 or f.shape != shape:
+                raise ValueError('phases and flags must both be (n0, n1, ntriads, nchan)')
+        if axis not in (0, 1):
+            raise ValueError('axis must be 0 or 1')
+        off = NP.ascontiguousarray(offsets, dtype=NP.int64).ravel()
+        mem = NP.ascontiguousarray(members, dtype=NP.int32).ravel()
+        nbins = off.size - 1
+        if nbins < 1 or off[0] != 0 or off[-1] != mem.size:
+            raise ValueError('offsets must be (nbins + 1,), from 0 to the number of members')
+        oshape = tuple(nbins if i == axis else n for i, n in enumerate(shape))
+        flag = 0
+        for name in want:
+            flag |= CPBINS_WANT[name]
+        out = {name: NP.empty(oshape, dtype=NP.complex128 if name.startswith('eicp') else NP.float64) for name in want}
+        st = PrisimCpbinsStats()
+        hin = C.c_void_p(stack.handle.value) if stack is not None else None
+        hout = C.c_void_p()
+        self._check(self._lib.prisim_cphase_bin(
+            self._h, kind, _ptr(a), _ptr(b), _ptr(w), _ptr(f), *shape, int(axis), nbins, _ptr(off), _ptr(mem), flag,
+            1 if mad_ignores_flags else 0, int(budget_bytes), None if hin is None else C.byref(hin), C.byref(hout) if keep else None,
+            _ptr(out.get('wts')), _ptr(out.get('eicp_mean')), _ptr(out.get('eicp_median')), _ptr(out.get('cp_mean')),
+            _ptr(out.get('cp_median')), _ptr(out.get('rms')), _ptr(out.get('mad')), C.byref(st)), 'prisim_cphase_bin')
+        if keep:
+            out['stack'] = CphaseStack(self, hout, PRISIM_CPBINS_BINNED, oshape)
+        out['stats'] = {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements), 'chunks': int(st.chunks),
+                        'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes), 'upload_bytes': int(st.upload_bytes),
+                        'download_bytes': int(st.download_bytes), 'max_bin': int(st.max_bin), 'resident': bool(st.resident_in)}
+        return out
+
     # ---- instrument gain tables (include/prisim_gains.h) ----
     @staticmethod
     def _gains_stats(st):
@@ -1385,6 +1469,28 @@ class Context(object):
     def set_tuning(self, chan_tile=0, src_chunk=0, nsplit=0):
         self._check(self._lib.prisim_hip_set_tuning(self._h, int(chan_tile), int(src_chunk), int(nsplit)),
                     'prisim_hip_set_tuning')
+
+
+class CphaseStack(object):
+    """A stack of closure phases resident on the device (prisim_cphase_stack).  Freed by close() or with the last reference; it must not
+    outlive its context."""
+
+    def __init__(self, ctx, handle, kind, shape):
+        self._ctx = ctx                    # keeps the context alive
+        self.handle = handle
+        self.kind = kind
+        self.shape = tuple(int(n) for n in shape)
+
+    def close(self):
+        if getattr(self, 'handle', None) is not None and self.handle.value:
+            self._ctx._lib.prisim_cphase_stack_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class GainTable(object):
