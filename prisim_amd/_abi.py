@@ -80,6 +80,10 @@ PRISIM_CPBINS_MAX_BIN = 256
 PRISIM_CPBINS_PHASE_FLAGS, PRISIM_CPBINS_BINNED = 0, 1
 CPBINS_WANT = {'wts': 1, 'eicp_mean': 2, 'eicp_median': 4, 'cp_mean': 8, 'cp_median': 16, 'rms': 32, 'mad': 64}
 PRISIM_CPBINS_ALL = 127
+# every symbol include/prisim_cpdiff.h declares: differences of day sub-samples of binned closure phases (prisim_amd/csrc_closure/cpdiff.hip)
+CPDIFF_EXPORTS = ('prisim_cphase_diff',)
+CPDIFF_OUTPUTS = ('diff0_mean', 'diff0_median', 'diff1_mean', 'diff1_median', 'wts0', 'wts1', 'mask0', 'mask1')
+PRISIM_CPDIFF_OUT_BYTES = 82
 
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
@@ -234,6 +238,12 @@ class PrisimCpbinsStats(C.Structure):
                 ('max_bin', C.c_int32), ('resident_in', C.c_int32)]
 
 
+class PrisimCpdiffStats(C.Structure):
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('elements', C.c_int64), ('chunks', C.c_int64),
+                ('chunk_triads', C.c_int64), ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64),
+                ('resident_in', C.c_int32), ('ncomb', C.c_int32)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -355,6 +365,9 @@ def load_library():
     lib.prisim_cphase_bin.restype = C.c_int
     lib.prisim_cphase_stack_free.argtypes = [vp]
     lib.prisim_cphase_stack_free.restype = None
+    lib.prisim_cphase_diff.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                       C.POINTER(PrisimCpdiffStats)]
+    lib.prisim_cphase_diff.restype = C.c_int
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
                                              C.POINTER(vp), pst]
@@ -1263,6 +1276,53 @@ class Context(object):
         out['stats'] = {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements), 'chunks': int(st.chunks),
                         'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes), 'upload_bytes': int(st.upload_bytes),
                         'download_bytes': int(st.download_bytes), 'max_bin': int(st.max_bin), 'resident': bool(st.resident_in)}
+        return out
+
+    # ---- differences of day sub-samples of binned closure phases (include/prisim_cpdiff.h) ----
+    def cphase_diff(self, pairs, stack=None, binned=None, budget_bytes=0):
+        """Half differences of the unit phasors of pairs of day bins of a binned (n0, n1, ntriads, nchan) stack on the device
+        (prisim_cphase_diff).  pairs: (ncomb, 4) integers (i, j, k, m), indices on axis 1 with i != j and k != m.  The input is one of:
+        stack, a resident CphaseStack of kind BINNED (a cphase_bin call with keep=True), or binned = (mean phases, median phases,
+        weights) on the host.  Returns a dict of 'diff0_mean', 'diff0_median' (0.5 (e_j - e_i)), 'diff1_mean', 'diff1_median'
+        (0.5 (e_m - e_k)) complex128, 'wts0', 'wts1' (the root of the sum of the squared weights) float64 and 'mask0', 'mask1' bool (a
+        member's weight is not > 0), each (n0, ncomb, ntriads, nchan), and 'stats'.  Under the mask the differences are 0; the weights
+        are written everywhere."""
+        a = b = w = None
+        if stack is not None:
+            if stack.kind != PRISIM_CPBINS_BINNED:
+                raise ValueError('the resident stack is not of kind BINNED, or of another shape or device')
+            shape = stack.shape
+        elif binned is not None:
+            a, b, w = (NP.ascontiguousarray(x, dtype=NP.float64) for x in binned)
+            shape = a.shape
+            if a.ndim != 4 or b.shape != shape or w.shape != shape:
+                raise ValueError('the binned arrays must all be (n0, n1, ntriads, nchan)')
+        else:
+            raise ValueError('need a resident stack or the binned arrays')
+        pr = NP.asarray(pairs)
+        if pr.size and not NP.issubdtype(pr.dtype, NP.integer):
+            raise ValueError('pairs must be integers')
+        if pr.ndim != 2 or pr.shape[1] != 4 or pr.shape[0] < 1:
+            raise ValueError('need ncomb >= 1 pairs of pairs')
+        for q, row in enumerate(pr.tolist()):
+            for v in row:
+                if v < 0 or v >= shape[1]:
+                    raise ValueError('pair of pairs {0} holds {1}, not an index of axis 1'.format(q, v))
+            if row[0] == row[1] or row[2] == row[3]:
+                raise ValueError('pair of pairs {0} holds a pair of one index with itself'.format(q))
+        pr = NP.ascontiguousarray(pr, dtype=NP.int32)
+        oshape = (shape[0], pr.shape[0], shape[2], shape[3])
+        out = {name: NP.empty(oshape, dtype=NP.complex128 if name.startswith('diff') else (NP.float64 if name.startswith('wts') else NP.uint8))
+               for name in CPDIFF_OUTPUTS}
+        st = PrisimCpdiffStats()
+        self._check(self._lib.prisim_cphase_diff(
+            self._h, _ptr(a), _ptr(b), _ptr(w), *shape, None if stack is None else stack.handle, pr.shape[0], _ptr(pr), int(budget_bytes),
+            *[_ptr(out[name]) for name in CPDIFF_OUTPUTS], C.byref(st)), 'prisim_cphase_diff')
+        for name in ('mask0', 'mask1'):
+            out[name] = out[name].view(NP.bool_)
+        out['stats'] = {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements), 'chunks': int(st.chunks),
+                        'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes), 'upload_bytes': int(st.upload_bytes),
+                        'download_bytes': int(st.download_bytes), 'resident': bool(st.resident_in), 'ncomb': int(st.ncomb)}
         return out
 
     # ---- instrument gain tables (include/prisim_gains.h) ----

@@ -1,5 +1,7 @@
 """Closure (bispectrum) phases of observed data: prisim/bispectrum_phase.py's loadnpz and the first steps of its ClosurePhase class,
-with the day and LST binning of smooth_in_tbins on the GPU (include/prisim_cpbins.h, prisim_amd/csrc_closure/cpbins.hip).
+with the day and LST binning of smooth_in_tbins and of subsample_differencing on the GPU (include/prisim_cpbins.h,
+prisim_amd/csrc_closure/cpbins.hip) and the differences of the day sub-samples there too (include/prisim_cpdiff.h,
+prisim_amd/csrc_closure/cpdiff.hip).
 
 Readings and departures
 - astropy is not a dependency.  The reference uses astropy.time.Time only to carry Julian dates, so loadnpz does that arithmetic
@@ -18,7 +20,19 @@ Readings and departures
 - A daybinsize that does not exceed the day resolution ends the reference in an UnboundLocalError (:1841); here it is a ValueError.
 - ClosurePhase takes, besides an NPZ file name, a ready cpinfo dictionary ({'raw': {...}}), so that simulated phases can be wrapped
   without a file; and a keyword ctx, the device context to use (default: a new one on device 0 at the first binning).
-- infmt='hdf5', save(), subtract() and subsample_differencing() are not implemented.
+- subsample_differencing bins in days, then in LST, then differences, all on the device: the day-binned and the LST-binned stack
+  never reach the host, and cpinfo['errinfo'] receives the reference's keys.  The reference computes the rms and the mad of both
+  passes there and stores neither; they are not requested.  Under the masks of 'eicp_diff' the reference leaves unspecified values
+  (MA.empty); here the data are 0 + 0i, the reading of the commented-out .filled(0.0) of its delay transform (:2728).  'wts' holds
+  sqrt(w_j^2 + w_i^2) everywhere, as the reference's .data does.
+- Several LSTs with lstbinsize=None end the reference's subsample_differencing in a NameError (eicp_tmean is never bound, :2231);
+  here that case takes the single-LST route: the differences of the day-binned stack.  ndaybins=None with daybinsize=None and a
+  daybinsize that does not exceed the day resolution end the reference in an UnboundLocalError (wts_daybins, :2119); here each is a
+  ValueError.  These, the reference's own ValueError for a daybinsize that gives fewer than 4 bins, and every other type and value
+  error are raised before any device work.
+- subtract is host numpy, like expicp: it is elementwise on arrays the host already holds.  Under the masks of 'residual' (the mask of
+  prelim or of the model; NaN in the model is masked) the data are 0.
+- infmt='hdf5' and save() are not implemented.
 """
 import warnings
 
@@ -151,6 +165,25 @@ def lst_bins(rawlst, lstbinsize, nrows):
         if len(m) and NP.max(m) >= nrows:
             raise IndexError('LST bin member {0} is out of bounds for axis 0 with size {1}'.format(int(NP.max(m)), nrows))
     return (centers, widths) + _csr(lists)
+
+
+def pairs_of_day_bin_pairs(ndaybins):
+    """[[i, j, k, m], ...]: every unordered pair of disjoint pairs {i, j}, {k, m} of day bins once, 3 C(ndaybins, 4) of them, in the
+    order of the reference's enumeration (:2218-2228): (i, j) ascending, then (k, m) ascending among the pairs disjoint from it, a
+    pair of pairs left out where it was listed before with its halves exchanged."""
+    seen = set()
+    out = []
+    for i in range(ndaybins - 1):
+        for j in range(i + 1, ndaybins):
+            for k in range(ndaybins - 1):
+                if k in (i, j):
+                    continue
+                for m in range(k + 1, ndaybins):
+                    if m in (i, j) or ((k, m), (i, j)) in seen:
+                        continue
+                    seen.add(((i, j), (k, m)))
+                    out.append([i, j, k, m])
+    return out
 
 
 class ClosurePhase(object):
@@ -287,3 +320,91 @@ class ClosurePhase(object):
         else:
             prelim['lstbins'] = NP.mean(rawlst, axis=1)
             prelim['dlstbins'] = NP.asarray(lstbinsize).reshape(-1) if lstbinsize is not None else NP.zeros(1)
+
+    def subtract(self, cphase):
+        """Subtract a model of the closure phase (radians; an array that broadcasts against the binned phases, NaN or a mask where
+        there is no model) from the binned phasors of smooth_in_tbins, on the host.  Fills cpinfo['processed']['submodel'] = {'cphase',
+        'eicp'} at the model's shape with leading axes of length 1, and cpinfo['processed']['residual'] = {'eicp': {'mean', 'median'},
+        'cphase': {'mean', 'median'}} with eicp = prelim - model and cphase = angle(prelim / model), masked where prelim or the model
+        is; under the mask the data are 0."""
+        if not isinstance(cphase, NP.ndarray):
+            raise TypeError('Input cphase must be a numpy array')
+        if not isinstance(cphase, MA.MaskedArray):
+            cphase = MA.array(cphase, mask=NP.isnan(cphase))
+        proc = self.cpinfo['processed']
+        prelim = proc.get('prelim', {})
+        if 'eicp' not in prelim or 'cphase' not in prelim:
+            raise ValueError('smooth_in_tbins must fill the binned closure phases before a model can be subtracted')
+        shape = prelim['cphase']['median'].shape
+        try:
+            ok = cphase.ndim <= len(shape) and NP.broadcast_shapes(cphase.shape, shape) is not None
+        except ValueError:
+            ok = False
+        if not ok:
+            raise ValueError('Input cphase has shape incompatible with that in instance attribute')
+        cphase = cphase.reshape((1,) * (len(shape) - cphase.ndim) + cphase.shape)
+        mmask = MA.getmaskarray(cphase)
+        cphase = MA.array(NP.where(mmask, 0.0, MA.getdata(cphase)), mask=mmask)
+        eicp = MA.array(NP.where(mmask, 0.0, NP.exp(1j * cphase.data)), mask=mmask)
+        proc['submodel'] = {'cphase': cphase, 'eicp': eicp}
+        proc['residual'] = {'eicp': {}, 'cphase': {}}
+        model = NP.exp(1j * cphase.data)                                  # of modulus 1 everywhere, so that the ratio is finite
+        for key in ('mean', 'median'):
+            pre = prelim['eicp'][key]
+            mask = MA.getmaskarray(pre) | mmask
+            proc['residual']['eicp'][key] = MA.array(NP.where(mask, 0.0, MA.getdata(pre) - model), mask=mask)
+            proc['residual']['cphase'][key] = MA.array(NP.where(mask, 0.0, NP.angle(MA.getdata(pre) / model)), mask=mask)
+
+    def subsample_differencing(self, daybinsize=None, ndaybins=4, lstbinsize=None):
+        """Noise estimate from differences of day sub-samples: bin the closure phases in at least 4 day bins (daybinsize in days, or
+        ndaybins bins of roughly equal numbers of days), bin those in LST (lstbinsize in seconds; only with several LSTs), and take
+        0.5 (e_j - e_i) and 0.5 (e_m - e_k) of the binned unit phasors for every pair of disjoint pairs {i, j}, {k, m} of day bins,
+        all on the device.  Fills cpinfo['errinfo'] with 'daybins', 'diff_dbins', 'lstbins', 'dlstbins', 'list_of_pair_of_pairs',
+        'wts' {'0', '1'} and 'eicp_diff' {'0', '1'} -> {'mean', 'median'}, (nlstbins, 3 C(ndaybins, 4), ntriads, nchan) masked
+        arrays, as the reference does.  Only the bin tables and the list of pairs go to the device and only those arrays come back."""
+        if (ndaybins is not None) and (daybinsize is not None):
+            raise ValueError('Only one of daybinsize or ndaybins should be set')
+        if ndaybins is None and daybinsize is None:
+            raise ValueError('One of daybinsize or ndaybins must be set')
+        if daybinsize is None:
+            if not isinstance(ndaybins, int):
+                raise TypeError('Input ndaybins must be an integer')
+            if ndaybins < 4:
+                raise ValueError('Input ndaybins must be greater than or equal to 4')
+        raw = self.cpinfo['raw']
+        centers, widths, doff, dmem, mad_all = day_bins(raw['days'], daybinsize, ndaybins)
+        ndaybins = doff.size - 1
+        if ndaybins < 4:
+            raise ValueError('Could not find at least 4 bins along repeating days. Adjust binning interval.')
+        rawlst = unwrapped_lst(raw['lst'])
+        lst = rawlst.shape[0] > 1 and lstbinsize is not None
+        if lst:
+            lstcenters, lstwidths, loff, lmem = lst_bins(rawlst, lstbinsize, rawlst.shape[0])
+        pairs = pairs_of_day_bin_pairs(ndaybins)
+        self.binning_stats = []
+        ctx = self._context()
+        kept = []
+        try:
+            res = ctx.cphase_bin(1, doff, dmem, stack=self._native_stack(), want=(), mad_ignores_flags=mad_all, keep=True)
+            kept.append(res['stack'])
+            self.binning_stats.append(res['stats'])
+            if lst:
+                res = ctx.cphase_bin(0, loff, lmem, stack=kept[-1], want=(), keep=True)
+                kept.append(res['stack'])
+                self.binning_stats.append(res['stats'])
+            res = ctx.cphase_diff(pairs, stack=kept[-1])
+            self.binning_stats.append(res['stats'])
+        finally:
+            for stack in kept:
+                stack.close()
+        err = self.cpinfo['errinfo']
+        err['daybins'], err['diff_dbins'] = centers, widths
+        if lst:
+            err['lstbins'], err['dlstbins'] = lstcenters, lstwidths
+        else:
+            err['lstbins'] = NP.mean(rawlst, axis=1)
+            err['dlstbins'] = NP.asarray(lstbinsize).reshape(-1) if lstbinsize is not None else NP.zeros(1)
+        err['list_of_pair_of_pairs'] = pairs
+        err['wts'] = {str(g): MA.array(res['wts%d' % g], mask=res['mask%d' % g]) for g in range(2)}
+        err['eicp_diff'] = {str(g): {stat: MA.array(res['diff%d_%s' % (g, stat)], mask=res['mask%d' % g]) for stat in ('mean', 'median')}
+                            for g in range(2)}

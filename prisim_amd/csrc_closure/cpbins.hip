@@ -25,28 +25,13 @@
 
 #include "../csrc/ctx_internal.h"
 #include "../../include/prisim_cpbins.h"
+#include "cpstack_internal.h"
 
-struct prisim_cphase_stack {
-  int device = 0;
-  int32_t kind = 0;
-  int64_t n0 = 0, n1 = 0, nt = 0, nc = 0;
-  double* a = nullptr;       // the phases (PHASE_FLAGS) or the mean phases (BINNED)
-  double* b = nullptr;       // BINNED: the median phases
-  double* w = nullptr;       // BINNED: the weights
-  uint8_t* f = nullptr;      // PHASE_FLAGS: the flags
-  ~prisim_cphase_stack() {
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
-    if (w) (void)hipFree(w);
-    if (f) (void)hipFree(f);
-  }
-};
+using namespace cpint;
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int64_t kDefaultBudget = int64_t(1) << 30;
-constexpr int64_t kMaxBlocks = int64_t(1) << 20;
 constexpr int kKept = PRISIM_CPBINS_WTS | PRISIM_CPBINS_CP_MEAN | PRISIM_CPBINS_CP_MEDIAN;
 
 struct BinParams {
@@ -208,43 +193,12 @@ __global__ __launch_bounds__(kThreads) void k_cpbins(const BinParams p) {
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
-struct Dev {
-  std::vector<void*> ptrs;
-  ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
-};
-
-#define CB_ALLOC(ctx, dev, ptr, bytes)                                                                 \
-  do {                                                                                                 \
-    void* p_ = nullptr;                                                                                \
-    HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
-    (dev).ptrs.push_back(p_);                                                                          \
-    (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
-  } while (0)
-
 #define CB_STACK_ALLOC(ctx, field, bytes)                                                              \
   do {                                                                                                 \
     void* p_ = nullptr;                                                                                \
     HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
     (field) = reinterpret_cast<decltype(field)>(p_);                                                   \
   } while (0)
-
-// the call's stream and its timing events: drained before the buffers it uses are freed (declared after them)
-struct Stream {
-  hipStream_t s = nullptr;
-  hipEvent_t k0 = nullptr, k1 = nullptr;
-  ~Stream() {
-    if (s) (void)hipStreamSynchronize(s);
-    if (k0) (void)hipEventDestroy(k0);
-    if (k1) (void)hipEventDestroy(k1);
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-
-// `rows` rows of `width` bytes between arrays whose rows are dpitch and spitch bytes apart
-hipError_t copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipMemcpyKind kind, hipStream_t s) {
-  if (width == dpitch && width == spitch) return hipMemcpyAsync(dst, src, width * rows, kind, s);
-  return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, kind, s);
-}
 
 }  // namespace
 
