@@ -1,0 +1,248 @@
+// addon_internal.h -- what the add-on entries share (csrc_clean, csrc_subband, csrc_gains, csrc_runs, csrc_closure): the per-call
+// device buffers, streams, events and rocFFT plans of their chunk loops on the host, and the complex helpers and the in-LDS radix-2
+// inverse transform of their fused kernels on the device.  Not part of the public ABI.
+#ifndef PRISIM_ADDON_INTERNAL_H
+#define PRISIM_ADDON_INTERNAL_H
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../csrc/ctx_internal.h"
+
+namespace pint {
+
+constexpr int kThreads = 256;                         // threads per workgroup of the add-on kernels
+constexpr int kMaxStreams = 2;
+constexpr int kMaxTile = 64;                          // snapshots per workgroup of the tiled fused kernels
+constexpr int kTileLds = 65536;                       // LDS their snapshot rows may fill
+constexpr int64_t kDefaultBudget = int64_t(1) << 30;  // device bytes of a call's chunk buffers when the caller gives none
+constexpr int64_t kMaxBlocks = int64_t(1) << 20;
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+
+struct Dev {
+  std::vector<void*> ptrs;
+  ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
+};
+
+#define DEV_ALLOC(ctx, dev, ptr, bytes)                                                                \
+  do {                                                                                                 \
+    void* p_ = nullptr;                                                                                \
+    HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
+    (dev).ptrs.push_back(p_);                                                                          \
+    (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
+  } while (0)
+
+// a call's own streams, each with an optional pair of kernel-timing events.  Drained when they go.
+struct Streams {
+  hipStream_t s[kMaxStreams] = {};
+  hipEvent_t k0[kMaxStreams] = {}, k1[kMaxStreams] = {};
+  bool timed[kMaxStreams] = {};
+  int n = 0;
+  ~Streams() {
+    for (int i = 0; i < n; ++i) {
+      (void)hipStreamSynchronize(s[i]);
+      if (k0[i]) (void)hipEventDestroy(k0[i]);
+      if (k1[i]) (void)hipEventDestroy(k1[i]);
+      (void)hipStreamDestroy(s[i]);
+    }
+  }
+  int create(prisim_ctx* ctx, int count, bool events) {
+    for (int i = 0; i < count; ++i) {
+      HIPCHK(ctx, hipStreamCreateWithFlags(&s[i], hipStreamNonBlocking));
+      n = i + 1;
+      if (events) {
+        HIPCHK(ctx, hipEventCreate(&k0[i]));
+        HIPCHK(ctx, hipEventCreate(&k1[i]));
+      }
+    }
+    return PRISIM_OK;
+  }
+  // adds the kernel time of the chunk stream i ran last (between k0 and k1) to kernel_ms
+  int harvest(prisim_ctx* ctx, int i, double& kernel_ms) {
+    if (!timed[i]) return PRISIM_OK;
+    HIPCHK(ctx, hipEventSynchronize(k1[i]));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, k0[i], k1[i]) == hipSuccess) kernel_ms += ms;
+    timed[i] = false;
+    return PRISIM_OK;
+  }
+};
+
+// in-place fp64 1-D rocFFT plans by (inverse, batch) and one execution info per stream
+struct FftPlans {
+  std::map<std::pair<bool, size_t>, rocfft_plan> plans;
+  rocfft_execution_info info[kMaxStreams] = {};
+  ~FftPlans() {
+    for (auto& kv : plans) g_rocfft.plan_destroy(kv.second);
+    for (rocfft_execution_info i : info) if (i) g_rocfft.execution_info_destroy(i);
+  }
+  rocfft_plan at(bool inverse, size_t batch) const { return plans.at({inverse, batch}); }
+  // plans of length len for every (inverse, batch) of want (repeats are made once); the infos run on streams[0 .. nstreams) and
+  // each gets a work buffer from dev that serves the largest plan
+  int create(prisim_ctx* ctx, Dev& dev, size_t len, const std::vector<std::pair<bool, size_t>>& want, const hipStream_t* streams,
+             int nstreams) {
+    RocfftApi& F = g_rocfft;
+    size_t wmax = 0;
+    for (const auto& key : want) {
+      if (plans.count(key)) continue;
+      rocfft_plan p = nullptr;
+      if (F.plan_create(&p, rocfft_placement_inplace, key.first ? rocfft_transform_type_complex_inverse : rocfft_transform_type_complex_forward,
+                        rocfft_precision_double, 1, &len, key.second, nullptr) != rocfft_status_success)
+        return fail(ctx, PRISIM_ELIB, "rocfft_plan_create failed");
+      plans[key] = p;
+      size_t wb = 0;
+      F.plan_get_work_buffer_size(p, &wb);
+      wmax = std::max(wmax, wb);
+    }
+    for (int i = 0; i < nstreams; ++i) {
+      if (F.execution_info_create(&info[i]) != rocfft_status_success) {
+        info[i] = nullptr;
+        return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_create failed");
+      }
+      if (F.execution_info_set_stream(info[i], streams[i]) != rocfft_status_success)
+        return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_stream failed");
+      if (wmax) {
+        void* wb;
+        DEV_ALLOC(ctx, dev, wb, wmax);
+        if (F.execution_info_set_work_buffer(info[i], wb, wmax) != rocfft_status_success)
+          return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_work_buffer failed");
+      }
+    }
+    return PRISIM_OK;
+  }
+};
+
+// What a call owns on the device.  The buffers must outlive the streams that use them, and members go in reverse order: the
+// streams are drained and destroyed first, then the plans, then the buffers are freed -- on every return path.  An entry that
+// runs on the context's stream leaves st empty and synchronises that stream itself before it returns.
+struct Work {
+  Dev dev;
+  FftPlans fft;
+  Streams st;
+};
+
+// the four events of the entries that run on the context's stream: e[0] .. e[3] span the call, e[1] .. e[2] its kernels
+struct Events {
+  hipEvent_t e[4] = {};
+  ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  int create(prisim_ctx* ctx) {
+    for (hipEvent_t& x : e) HIPCHK(ctx, hipEventCreate(&x));
+    return PRISIM_OK;
+  }
+};
+
+// rocFFT loaded and set up, once per process
+inline int ensure_rocfft(prisim_ctx* ctx) {
+  std::string lerr;
+  if (!load_rocfft(lerr)) return fail(ctx, PRISIM_ELIB, lerr);
+  if (!g_rocfft.setup_done) {
+    if (g_rocfft.setup() != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_setup failed");
+    g_rocfft.setup_done = true;
+  }
+  return PRISIM_OK;
+}
+
+inline int64_t budget_or_default(int64_t budget) { return budget > 0 ? budget : kDefaultBudget; }
+
+// workgroups of a grid-stride kernel over n elements
+inline int grid_for(const prisim_ctx* ctx, int64_t n) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)std::max(ctx->cu_count, 1) * 16));
+}
+
+// `rows` rows of `width` bytes between arrays whose rows are dpitch and spitch bytes apart
+inline hipError_t copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipMemcpyKind kind,
+                            hipStream_t s) {
+  if (width == dpitch && width == spitch) return hipMemcpyAsync(dst, src, width * rows, kind, s);
+  return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, kind, s);
+}
+
+using WallTime = std::chrono::steady_clock::time_point;
+inline WallTime wall_now() { return std::chrono::steady_clock::now(); }
+inline double wall_ms_since(WallTime t0) { return std::chrono::duration<double, std::milli>(wall_now() - t0).count(); }
+
+// The tables of scipy.signal.resample's spectrum from the caller's selection map (prisim_amd/dsp_readings.py:resample_map): per output
+// bin at most two input bins rs_in [2][nout] (-1: none; bins of the zero padding are dropped) with the coefficients rs_c [2][nout]
+// = map_w * scale * e^{-2 pi i k_in floor(m/2) / m}, and rtw [nout] = e^{+2 pi i q / nout}.  nout < 1: tables of one empty bin.
+inline int build_resample_tables(prisim_ctx* ctx, int64_t nout, int64_t m, int64_t nchan, double scale, int64_t nmap, const int64_t* map_out,
+                                 const int64_t* map_in, const double* map_w, std::vector<int32_t>& rs_in, std::vector<double>& rs_c,
+                                 std::vector<double>& rtw) {
+  const int64_t nr = std::max<int64_t>(nout, 1);
+  rs_in.assign(2 * (size_t)nr, -1);
+  rs_c.assign(4 * (size_t)nr, 0.0);
+  rtw.assign(2 * (size_t)nr, 0.0);
+  if (nout < 1) return PRISIM_OK;
+  if (nmap < 1 || !map_out || !map_in || !map_w) return fail(ctx, PRISIM_EINVAL, "the resampled spectra need the selection map");
+  std::vector<int> used((size_t)nout, 0);
+  const int64_t half = m / 2;
+  for (int64_t e = 0; e < nmap; ++e) {
+    const int64_t k = map_out[e], kin = map_in[e];
+    if (k < 0 || k >= nout || kin < 0 || kin >= m) return fail(ctx, PRISIM_EINVAL, "selection map entry out of range");
+    if (used[(size_t)k] == 2) return fail(ctx, PRISIM_EINVAL, "selection map: more than two entries for one output bin");
+    const int s = used[(size_t)k]++;
+    if (kin >= nchan) continue;                    // a bin of the zero padding
+    const int64_t red = (kin * half) % m;          // e^{-2 pi i k_in floor(m/2) / m}
+    const double a = -2.0 * M_PI * (double)red / (double)m;
+    const double sc = map_w[e] * scale;
+    rs_in[(size_t)s * nout + k] = (int32_t)kin;
+    rs_c[2 * ((size_t)s * nout + k)] = sc * std::cos(a);
+    rs_c[2 * ((size_t)s * nout + k) + 1] = sc * std::sin(a);
+  }
+  for (int64_t q = 0; q < nout; ++q) {
+    const double a = 2.0 * M_PI * (double)q / (double)nout;
+    rtw[2 * q] = std::cos(a);
+    rtw[2 * q + 1] = std::sin(a);
+  }
+  return PRISIM_OK;
+}
+
+// ---- device side: fp64 without contraction (the including files are built with -ffp-contract=off) -------------------------------
+
+__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ double2 cmulc(double2 a, double2 b) { return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a conj(b)
+__device__ __forceinline__ double2 rmul(double2 a, double s) { return make_double2(a.x * s, a.y * s); }
+
+// tw[k] = e^{+2 pi i k / m}, k < m / 2, by the whole workgroup (no barrier)
+__device__ __forceinline__ void lds_twiddles(double2* tw, int m) {
+  for (int k = threadIdx.x; k < m / 2; k += kThreads) {
+    double sn, cs;
+    sincospi(2.0 * (double)k / (double)m, &sn, &cs);
+    tw[k] = make_double2(cs, sn);
+  }
+}
+
+// n < 2^logm with its logm bits reversed
+__device__ __forceinline__ int bitrev(int n, int logm) { return logm ? (int)(__brev((unsigned)n) >> (32 - logm)) : 0; }
+
+// Radix-2 decimation-in-time butterflies with the twiddles e^{+2 pi i / m} over `tile` rows of m elements, ld apart, that were stored
+// bit-reversed: sum_n x[n] e^{+2 pi i j n / m} in natural order.  By the whole workgroup, behind a barrier that the caller sets after
+// its stores; ends with a barrier.
+__device__ __forceinline__ void lds_ifft_dit(double2* buf, int ld, int tile, int m, const double2* tw) {
+  const int half = m / 2;
+  for (int h = 1; h < m; h <<= 1) {                 // butterflies of span 2h; twiddle W_{2h}^pos = tw[pos * m / (2h)]
+    const int step = m / (2 * h);
+    for (int i = threadIdx.x; i < tile * half; i += kThreads) {
+      const int tt = tile == 1 ? 0 : i / half, ii = i - tt * half;   // one row: the compiler drops the division
+      const int pos = ii & (h - 1);
+      const int a = tt * ld + ((ii - pos) << 1) + pos, b = a + h;
+      const double2 u = buf[a], v = cmul(buf[b], tw[pos * step]);
+      buf[a] = cadd(u, v);
+      buf[b] = csub(u, v);
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace pint
+
+#endif  // PRISIM_ADDON_INTERNAL_H

@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../csrc/ctx_internal.h"
+#include "../csrc_addon/addon_internal.h"
 #include "../../include/prisim_clean.h"
 
 namespace {
@@ -423,24 +423,6 @@ __global__ void k_clean_scale(double2* x, int64_t n, double s1, double s2, int t
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
-struct Dev {
-  std::vector<void*> ptrs;
-  ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
-};
-
-#define CLEAN_ALLOC(ctx, dev, ptr, bytes)                                                              \
-  do {                                                                                                 \
-    void* p_ = nullptr;                                                                                \
-    HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
-    (dev).ptrs.push_back(p_);                                                                          \
-    (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
-  } while (0)
-
-struct Events {
-  hipEvent_t e[4] = {};
-  ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 int check_common(prisim_ctx* ctx, int64_t nrows, int64_t m, int64_t nkern, const int32_t* kidx, int64_t nkidx, double gain,
                  int64_t maxiter, double threshold) {
   if (m < 1 || m > PRISIM_CLEAN_MAX_LEN)
@@ -465,9 +447,9 @@ int run_clean(prisim_ctx* ctx, Dev& dev, const double2* d_inp, int64_t nrows, in
   double2* knorm;
   int* kmax;
   unsigned long long* counter;
-  CLEAN_ALLOC(ctx, dev, knorm, (size_t)nkern * m * 16);
-  CLEAN_ALLOC(ctx, dev, kmax, (size_t)nkern * sizeof(int));
-  CLEAN_ALLOC(ctx, dev, counter, sizeof(unsigned long long));
+  DEV_ALLOC(ctx, dev, knorm, (size_t)nkern * m * 16);
+  DEV_ALLOC(ctx, dev, kmax, (size_t)nkern * sizeof(int));
+  DEV_ALLOC(ctx, dev, counter, sizeof(unsigned long long));
   HIPCHK(ctx, hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(d_cc, 0, (size_t)nrows * m * 16, ctx->stream));
   hipLaunchKernelGGL(k_clean_norm, dim3((unsigned)nkern), dim3(kWave), 0, ctx->stream, d_kern, knorm, kmax, m);
@@ -523,41 +505,6 @@ int finish_stats(prisim_ctx* ctx, const Events& ev, const int32_t* iters, int64_
   return PRISIM_OK;
 }
 
-int fft_plan(prisim_ctx* ctx, Dev& dev, rocfft_transform_type type, size_t len, size_t batch, rocfft_plan* plan,
-             rocfft_execution_info* info) {
-  RocfftApi& F = g_rocfft;
-  if (F.plan_create(plan, rocfft_placement_inplace, type, rocfft_precision_double, 1, &len, batch, nullptr) != rocfft_status_success) {
-    *plan = nullptr;
-    return fail(ctx, PRISIM_ELIB, "rocfft_plan_create failed");
-  }
-  if (F.execution_info_create(info) != rocfft_status_success) {
-    *info = nullptr;
-    return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_create failed");
-  }
-  if (F.execution_info_set_stream(*info, ctx->stream) != rocfft_status_success)
-    return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_stream failed");
-  size_t wbytes = 0;
-  F.plan_get_work_buffer_size(*plan, &wbytes);
-  if (wbytes) {
-    void* w;
-    CLEAN_ALLOC(ctx, dev, w, wbytes);
-    if (F.execution_info_set_work_buffer(*info, w, wbytes) != rocfft_status_success)
-      return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_work_buffer failed");
-  }
-  return PRISIM_OK;
-}
-
-struct Plans {
-  rocfft_plan p[2] = {};
-  rocfft_execution_info i[2] = {};
-  ~Plans() {
-    for (int k = 0; k < 2; ++k) {
-      if (p[k]) g_rocfft.plan_destroy(p[k]);
-      if (i[k]) g_rocfft.execution_info_destroy(i[k]);
-    }
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -574,20 +521,20 @@ int prisim_clean_rows(prisim_ctx* ctx, int64_t nrows, int64_t m, const double* i
   HIPCHK(ctx, hipSetDevice(ctx->device));
   Dev dev;
   Events ev;
-  for (hipEvent_t& e : ev.e) HIPCHK(ctx, hipEventCreate(&e));
+  if ((rc = ev.create(ctx))) return rc;
   const size_t rb = (size_t)nrows * m * 16;
   double2 *d_inp, *d_kern, *d_cc, *d_res, *d_rms;
   int32_t *d_kidx = nullptr, *d_iters, *d_flags;
   uint8_t* d_cbox;
-  CLEAN_ALLOC(ctx, dev, d_inp, rb);
-  CLEAN_ALLOC(ctx, dev, d_kern, (size_t)nkern * m * 16);
-  CLEAN_ALLOC(ctx, dev, d_cc, rb);
-  CLEAN_ALLOC(ctx, dev, d_res, rb);
-  CLEAN_ALLOC(ctx, dev, d_rms, (size_t)nrows * 16);
-  CLEAN_ALLOC(ctx, dev, d_iters, (size_t)nrows * 4);
-  CLEAN_ALLOC(ctx, dev, d_flags, (size_t)nrows * 4);
-  CLEAN_ALLOC(ctx, dev, d_cbox, (size_t)nrows * m);
-  if (kidx) CLEAN_ALLOC(ctx, dev, d_kidx, (size_t)nrows * 4);
+  DEV_ALLOC(ctx, dev, d_inp, rb);
+  DEV_ALLOC(ctx, dev, d_kern, (size_t)nkern * m * 16);
+  DEV_ALLOC(ctx, dev, d_cc, rb);
+  DEV_ALLOC(ctx, dev, d_res, rb);
+  DEV_ALLOC(ctx, dev, d_rms, (size_t)nrows * 16);
+  DEV_ALLOC(ctx, dev, d_iters, (size_t)nrows * 4);
+  DEV_ALLOC(ctx, dev, d_flags, (size_t)nrows * 4);
+  DEV_ALLOC(ctx, dev, d_cbox, (size_t)nrows * m);
+  if (kidx) DEV_ALLOC(ctx, dev, d_kidx, (size_t)nrows * 4);
   HIPCHK(ctx, hipEventRecord(ev.e[0], ctx->stream));
   if (nrows > 0) {
     HIPCHK(ctx, hipMemcpyAsync(d_inp, inp, rb, hipMemcpyHostToDevice, ctx->stream));
@@ -623,36 +570,31 @@ int prisim_clean_delay(prisim_ctx* ctx, int32_t ncubes, int64_t nrows, int64_t n
   if (ncubes < 1 || nchan < 1 || nchan > m) return fail(ctx, PRISIM_EINVAL, "ncubes must be >= 1 and 1 <= nchan <= m");
   if (!win || !kwin || !cbox || !lag || !kern_lag || !cc || !res || !cc_freq || !res_freq || !iters || !flags || !rms)
     return fail(ctx, PRISIM_EINVAL, "null array");
-  std::string lerr;
-  if (!load_rocfft(lerr)) return fail(ctx, PRISIM_ELIB, lerr);
+  if ((rc = ensure_rocfft(ctx))) return rc;
   RocfftApi& F = g_rocfft;
-  if (!F.setup_done) {
-    if (F.setup() != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_setup failed");
-    F.setup_done = true;
-  }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  Dev dev;
+  Work wk;
+  Dev& dev = wk.dev;
   Events ev;
-  Plans pl;
-  for (hipEvent_t& e : ev.e) HIPCHK(ctx, hipEventCreate(&e));
+  if ((rc = ev.create(ctx))) return rc;
   const int64_t nclean = (int64_t)ncubes * nrows, nall = nclean + nkern;
   const size_t rb = (size_t)nclean * m * 16;
   double2 *d_x, *d_cc, *d_res, *d_ccf, *d_resf, *d_rms;
   int32_t *d_kidx = nullptr, *d_iters, *d_flags;
   uint8_t* d_cbox;
-  CLEAN_ALLOC(ctx, dev, d_x, (size_t)nall * m * 16);
-  CLEAN_ALLOC(ctx, dev, d_cc, rb);
-  CLEAN_ALLOC(ctx, dev, d_res, rb);
-  CLEAN_ALLOC(ctx, dev, d_ccf, rb);
-  CLEAN_ALLOC(ctx, dev, d_resf, rb);
-  CLEAN_ALLOC(ctx, dev, d_rms, (size_t)nclean * 16);
-  CLEAN_ALLOC(ctx, dev, d_iters, (size_t)nclean * 4);
-  CLEAN_ALLOC(ctx, dev, d_flags, (size_t)nclean * 4);
-  CLEAN_ALLOC(ctx, dev, d_cbox, (size_t)std::max<int64_t>(nrows, 1) * m);
-  if (kidx) CLEAN_ALLOC(ctx, dev, d_kidx, (size_t)std::max<int64_t>(nrows, 1) * 4);
-  if ((rc = fft_plan(ctx, dev, rocfft_transform_type_complex_inverse, (size_t)m, (size_t)nall, &pl.p[0], &pl.i[0]))) return rc;
-  if (nclean > 0 && (rc = fft_plan(ctx, dev, rocfft_transform_type_complex_forward, (size_t)m, (size_t)nclean, &pl.p[1], &pl.i[1])))
-    return rc;
+  DEV_ALLOC(ctx, dev, d_x, (size_t)nall * m * 16);
+  DEV_ALLOC(ctx, dev, d_cc, rb);
+  DEV_ALLOC(ctx, dev, d_res, rb);
+  DEV_ALLOC(ctx, dev, d_ccf, rb);
+  DEV_ALLOC(ctx, dev, d_resf, rb);
+  DEV_ALLOC(ctx, dev, d_rms, (size_t)nclean * 16);
+  DEV_ALLOC(ctx, dev, d_iters, (size_t)nclean * 4);
+  DEV_ALLOC(ctx, dev, d_flags, (size_t)nclean * 4);
+  DEV_ALLOC(ctx, dev, d_cbox, (size_t)std::max<int64_t>(nrows, 1) * m);
+  if (kidx) DEV_ALLOC(ctx, dev, d_kidx, (size_t)std::max<int64_t>(nrows, 1) * 4);
+  std::vector<std::pair<bool, size_t>> plans = {{true, (size_t)nall}};            // the inverse of every row; forward of the CLEANed ones
+  if (nclean > 0) plans.push_back({false, (size_t)nclean});
+  if ((rc = wk.fft.create(ctx, dev, (size_t)m, plans, &ctx->stream, 1))) return rc;
 
   HIPCHK(ctx, hipEventRecord(ev.e[0], ctx->stream));
   // zero-padded rows (:1738-1740): the windowed channels first, m - nchan zeros after them
@@ -667,7 +609,7 @@ int prisim_clean_delay(prisim_ctx* ctx, int32_t ncubes, int64_t nrows, int64_t n
     if (kidx) HIPCHK(ctx, hipMemcpyAsync(d_kidx, kidx, (size_t)nrows * 4, hipMemcpyHostToDevice, ctx->stream));
   }
   void* b0[1] = {d_x};
-  if (F.execute(pl.p[0], b0, nullptr, pl.i[0]) != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
+  if (F.execute(wk.fft.at(true, (size_t)nall), b0, nullptr, wk.fft.info[0]) != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
   // rocFFT's inverse is unnormalised: m df ifft(x) = df * sum_n x[n] e^{+2 pi i k n / m}
   hipLaunchKernelGGL(k_clean_scale, dim3(1024), dim3(256), 0, ctx->stream, d_x, nall * m, lag_scale, 1.0, 0);
   HIPCHK(ctx, hipGetLastError());
@@ -680,7 +622,8 @@ int prisim_clean_delay(prisim_ctx* ctx, int32_t ncubes, int64_t nrows, int64_t n
     HIPCHK(ctx, hipMemcpyAsync(d_resf, d_res, rb, hipMemcpyDeviceToDevice, ctx->stream));
     void* b1[1] = {d_ccf};
     void* b2[1] = {d_resf};
-    if (F.execute(pl.p[1], b1, nullptr, pl.i[1]) != rocfft_status_success || F.execute(pl.p[1], b2, nullptr, pl.i[1]) != rocfft_status_success)
+    const rocfft_plan fwd = wk.fft.at(false, (size_t)nclean);
+    if (F.execute(fwd, b1, nullptr, wk.fft.info[0]) != rocfft_status_success || F.execute(fwd, b2, nullptr, wk.fft.info[0]) != rocfft_status_success)
       return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
     hipLaunchKernelGGL(k_clean_scale, dim3(1024), dim3(256), 0, ctx->stream, d_ccf, nclean * m, freq_scale1, freq_scale2, 1);
     hipLaunchKernelGGL(k_clean_scale, dim3(1024), dim3(256), 0, ctx->stream, d_resf, nclean * m, freq_scale1, freq_scale2, 1);

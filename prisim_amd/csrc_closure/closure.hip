@@ -26,10 +26,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -37,19 +35,8 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxStreams = 2;
 constexpr int kTile = 32;                             // k_cl_tiled: channels and snapshots per tile
-constexpr int kMaxTile = 64;                          // fused filter: snapshots per workgroup
-constexpr int kTileLds = 65536;                       // LDS the snapshot rows of the fused filter may fill
 constexpr int kTiledMinNt = 16;                       // fewer snapshots than this: the plain kernel
-constexpr int64_t kDefaultBudget = int64_t(1) << 30;  // device bytes of a call's chunk buffers when the caller gives none
-
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 cmulc(double2 a, double2 b) { return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a conj(b)
-__device__ __forceinline__ double2 rmul(double2 a, double s) { return make_double2(a.x * s, a.y * s); }
 
 struct ClParams {
   const double2* cube;
@@ -156,11 +143,7 @@ __global__ void __launch_bounds__(kThreads) k_cl_fused(ClParams P) {
   const int tcount = min(tile, P.nt - t0);
   const int ind = P.legs[P.T0 * 3 + row], cj = P.conj[P.T0 * 3 + row];
   const double* mask = P.masks + (int64_t)(P.midx ? P.midx[ind] : 0) * n;
-  for (int k = threadIdx.x; k < half; k += kThreads) {
-    double sn, cs;
-    sincospi(2.0 * (double)k / (double)n, &sn, &cs);
-    tw[k] = make_double2(cs, sn);                                      // e^{+2 pi i k / n}
-  }
+  lds_twiddles(tw, n);
   for (int e = threadIdx.x; e < n * tile; e += kThreads) {
     int ch, tt;
     if (P.sc == 1) { tt = e / n; ch = e - tt * n; } else { ch = e / tile; tt = e - ch * tile; }      // the cube's fastest axis on the lanes
@@ -182,22 +165,11 @@ __global__ void __launch_bounds__(kThreads) k_cl_fused(ClParams P) {
   const double inv = 1.0 / (double)n;
   for (int e = threadIdx.x; e < n * tile; e += kThreads) {             // position p holds fft(x)[rev(p)]
     const int tt = e / n, p = e - tt * n;
-    const int j = P.logn ? (int)(__brev((unsigned)p) >> (32 - P.logn)) : 0;
+    const int j = bitrev(p, P.logn);
     buf[tt * ld + p] = rmul(buf[tt * ld + p], mask[j] * inv);
   }
   __syncthreads();
-  for (int h = 1; h < n; h <<= 1) {                                    // inverse, decimation in time
-    const int step = n / (2 * h);
-    for (int i = threadIdx.x; i < tile * half; i += kThreads) {
-      const int tt = i / half, ii = i - tt * half;
-      const int pos = ii & (h - 1);
-      const int a = tt * ld + ((ii - pos) << 1) + pos, b = a + h;
-      const double2 u = buf[a], v = cmul(buf[b], tw[pos * step]);
-      buf[a] = cadd(u, v);
-      buf[b] = csub(u, v);
-    }
-    __syncthreads();
-  }
+  lds_ifft_dit(buf, ld, tile, n, tw);                                  // inverse, decimation in time
   double2* dst = P.trip + row * n * (int64_t)P.nt + t0;
   for (int e = threadIdx.x; e < n * tile; e += kThreads) {
     const int ch = e / tile, tt = e - ch * tile;
@@ -241,51 +213,6 @@ __global__ void __launch_bounds__(kThreads) k_cl_finish(ClParams P) {
   }
 }
 
-// ---- host side --------------------------------------------------------------------------------------------------------------
-
-struct Dev {
-  std::vector<void*> ptrs;
-  ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
-};
-
-#define CL_ALLOC(ctx, dev, ptr, bytes)                                                                 \
-  do {                                                                                                 \
-    void* p_ = nullptr;                                                                                \
-    HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
-    (dev).ptrs.push_back(p_);                                                                          \
-    (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
-  } while (0)
-
-// the call's streams and their kernel-timing events: drained before the buffers they use are freed (declared after Dev)
-struct Streams {
-  hipStream_t s[kMaxStreams] = {};
-  hipEvent_t k0[kMaxStreams] = {}, k1[kMaxStreams] = {};
-  bool timed[kMaxStreams] = {};
-  int n = 0;
-  ~Streams() {
-    for (int i = 0; i < n; ++i) {
-      (void)hipStreamSynchronize(s[i]);
-      if (k0[i]) (void)hipEventDestroy(k0[i]);
-      if (k1[i]) (void)hipEventDestroy(k1[i]);
-      (void)hipStreamDestroy(s[i]);
-    }
-  }
-};
-
-struct FftPlans {
-  std::map<size_t, rocfft_plan> fwd, inv;           // by batch
-  rocfft_execution_info info[kMaxStreams] = {};
-  ~FftPlans() {
-    for (auto& kv : fwd) g_rocfft.plan_destroy(kv.second);
-    for (auto& kv : inv) g_rocfft.plan_destroy(kv.second);
-    for (rocfft_execution_info i : info) if (i) g_rocfft.execution_info_destroy(i);
-  }
-};
-
-int grid_for(const prisim_ctx* ctx, int64_t n) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)std::max(ctx->cu_count, 1) * 16));
-}
-
 }  // namespace
 
 // The call itself.  With a sink (closure_internal.h) the phases of every chunk are handed on where they lie, and the caller's
@@ -295,7 +222,7 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
                          int64_t nmask, const int32_t* mask_index, int32_t route, int64_t budget_bytes, double* out_triplets,
                          double* out_phase, prisim_closure_stats* stats, const ClosureSink* sink) {
   if (!ctx) return PRISIM_EINVAL;
-  const auto wall0 = std::chrono::steady_clock::now();
+  const WallTime wall0 = wall_now();
   if (nt < 1 || nbl < 1 || nchan < 1 || ntriads < 1) return fail(ctx, PRISIM_EINVAL, "need nt, nbl, nchan and ntriads >= 1");
   if (nt > (int64_t)1 << 30 || nchan > (int64_t)1 << 30 || nbl > (int64_t)1 << 30)
     return fail(ctx, PRISIM_EINVAL, "nt, nbl and nchan must fit in 32 bits");
@@ -350,89 +277,48 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
       lds = 0;
     }
   }
-  if (rt == PRISIM_CLOSURE_ROCFFT) {
-    std::string lerr;
-    if (!load_rocfft(lerr)) return fail(ctx, PRISIM_ELIB, lerr);
-    if (!g_rocfft.setup_done) {
-      if (g_rocfft.setup() != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_setup failed");
-      g_rocfft.setup_done = true;
-    }
-  }
+  if (rt == PRISIM_CLOSURE_ROCFFT)
+    if (int rc = ensure_rocfft(ctx)) return rc;
   const int64_t ntiles = rt == PRISIM_CLOSURE_FUSED ? (nt + tile - 1) / tile : 1;
   const int64_t nct = (nchan + kTile - 1) / kTile, ntt = (nt + kTile - 1) / kTile;
   const int64_t per = nchan * nt;
   const int64_t trip_triad = 3 * per * 16, phase_triad = per * 8, fbuf_triad = rt == PRISIM_CLOSURE_ROCFFT ? 3 * per * 16 : 0;
   const int64_t per_triad = trip_triad + phase_triad + fbuf_triad + (sink ? sink->bytes_per_triad : 0);
-  const int64_t budget = budget_bytes > 0 ? budget_bytes : kDefaultBudget;
+  const int64_t budget = budget_or_default(budget_bytes);
   int64_t tc = std::max<int64_t>(1, std::min<int64_t>(ntriads, budget / (kMaxStreams * per_triad)));
   const int64_t blocks_triad = tiled ? nct * ntt : 3 * ntiles;                      // grid x of the tiled kernels
   tc = std::max<int64_t>(1, std::min<int64_t>(tc, (((int64_t)1 << 31) - 1) / blocks_triad));
   const int64_t nchunks = (ntriads + tc - 1) / tc;
   const int nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
 
-  Dev dev;
+  Work wk;
   double2* d_cube = nullptr;
   double *d_bpw = nullptr, *d_fw = nullptr, *d_masks = nullptr;
   int32_t *d_midx = nullptr, *d_legs = nullptr, *d_conj = nullptr;
-  if (cube) CL_ALLOC(ctx, dev, d_cube, nbl * per * 16);
-  CL_ALLOC(ctx, dev, d_bpw, nbl * per * 8);
-  CL_ALLOC(ctx, dev, d_fw, nchan * 8);
-  CL_ALLOC(ctx, dev, d_legs, ntriads * 3 * 4);
-  CL_ALLOC(ctx, dev, d_conj, ntriads * 3 * 4);
+  if (cube) DEV_ALLOC(ctx, wk.dev, d_cube, nbl * per * 16);
+  DEV_ALLOC(ctx, wk.dev, d_bpw, nbl * per * 8);
+  DEV_ALLOC(ctx, wk.dev, d_fw, nchan * 8);
+  DEV_ALLOC(ctx, wk.dev, d_legs, ntriads * 3 * 4);
+  DEV_ALLOC(ctx, wk.dev, d_conj, ntriads * 3 * 4);
   if (filter) {
-    CL_ALLOC(ctx, dev, d_masks, nmask * nchan * 8);
-    if (mask_index) CL_ALLOC(ctx, dev, d_midx, nbl * 4);
+    DEV_ALLOC(ctx, wk.dev, d_masks, nmask * nchan * 8);
+    if (mask_index) DEV_ALLOC(ctx, wk.dev, d_midx, nbl * 4);
   }
   double2* d_trip[kMaxStreams] = {};
   double* d_phase[kMaxStreams] = {};
   double2* d_fbuf[kMaxStreams] = {};
   for (int i = 0; i < nstreams; ++i) {
-    CL_ALLOC(ctx, dev, d_trip[i], tc * trip_triad);
-    CL_ALLOC(ctx, dev, d_phase[i], tc * phase_triad);
-    if (fbuf_triad) CL_ALLOC(ctx, dev, d_fbuf[i], tc * fbuf_triad);
+    DEV_ALLOC(ctx, wk.dev, d_trip[i], tc * trip_triad);
+    DEV_ALLOC(ctx, wk.dev, d_phase[i], tc * phase_triad);
+    if (fbuf_triad) DEV_ALLOC(ctx, wk.dev, d_fbuf[i], tc * fbuf_triad);
   }
-  FftPlans fft;
-  Streams st;
-  for (int i = 0; i < nstreams; ++i) {
-    HIPCHK(ctx, hipStreamCreateWithFlags(&st.s[i], hipStreamNonBlocking));
-    st.n = i + 1;
-    HIPCHK(ctx, hipEventCreate(&st.k0[i]));
-    HIPCHK(ctx, hipEventCreate(&st.k1[i]));
-  }
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, nstreams, true)) return rc;
   if (sink)
     if (int rc = sink->prepare(tc, ntriads - (nchunks - 1) * tc, nstreams, st.s)) return rc;
   if (rt == PRISIM_CLOSURE_ROCFFT) {
-    RocfftApi& F = g_rocfft;
-    size_t wmax = 0;
-    for (int64_t c : {tc, ntriads - (nchunks - 1) * tc}) {
-      const size_t batch = (size_t)c * 3 * (size_t)nt;
-      if (fft.fwd.count(batch)) continue;
-      size_t len = (size_t)nchan;
-      for (int dir = 0; dir < 2; ++dir) {
-        rocfft_plan p = nullptr;
-        if (F.plan_create(&p, rocfft_placement_inplace, dir ? rocfft_transform_type_complex_inverse : rocfft_transform_type_complex_forward,
-                          rocfft_precision_double, 1, &len, batch, nullptr) != rocfft_status_success)
-          return fail(ctx, PRISIM_ELIB, "rocfft_plan_create failed");
-        (dir ? fft.inv : fft.fwd)[batch] = p;
-        size_t wb = 0;
-        F.plan_get_work_buffer_size(p, &wb);
-        wmax = std::max(wmax, wb);
-      }
-    }
-    for (int i = 0; i < nstreams; ++i) {
-      if (F.execution_info_create(&fft.info[i]) != rocfft_status_success) {
-        fft.info[i] = nullptr;
-        return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_create failed");
-      }
-      if (F.execution_info_set_stream(fft.info[i], st.s[i]) != rocfft_status_success)
-        return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_stream failed");
-      if (wmax) {
-        void* wb;
-        CL_ALLOC(ctx, dev, wb, wmax);
-        if (F.execution_info_set_work_buffer(fft.info[i], wb, wmax) != rocfft_status_success)
-          return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_work_buffer failed");
-      }
-    }
+    const size_t b0 = (size_t)tc * 3 * (size_t)nt, b1 = (size_t)(ntriads - (nchunks - 1) * tc) * 3 * (size_t)nt;
+    if (int rc = wk.fft.create(ctx, wk.dev, (size_t)nchan, {{false, b0}, {true, b0}, {false, b1}, {true, b1}}, st.s, nstreams)) return rc;
   }
 
   // the cube and the tables on stream 0, behind whatever the context's stream still writes into the resident cube
@@ -460,18 +346,10 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
     HIPCHK(ctx, hipFuncSetAttribute((const void*)k_cl_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 
   double kernel_ms = 0.0;
-  auto harvest = [&](int i) -> int {                // the kernel time of the chunk stream i ran last
-    if (!st.timed[i]) return PRISIM_OK;
-    HIPCHK(ctx, hipEventSynchronize(st.k1[i]));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, st.k0[i], st.k1[i]) == hipSuccess) kernel_ms += ms;
-    st.timed[i] = false;
-    return PRISIM_OK;
-  };
   for (int64_t c = 0; c < nchunks; ++c) {
     const int i = (int)(c % nstreams);
     hipStream_t sc = st.s[i];
-    if (int rc = harvest(i)) return rc;
+    if (int rc = st.harvest(ctx, i, kernel_ms)) return rc;
     const int64_t T0 = c * tc, tn = std::min(tc, ntriads - T0);
     ClParams P = base;
     P.T0 = T0; P.tc = tn; P.trip = d_trip[i]; P.phase = d_phase[i]; P.fbuf = d_fbuf[i];
@@ -491,11 +369,11 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
         void* b[1] = {d_fbuf[i]};
         hipLaunchKernelGGL(k_cl_prepare, dim3((unsigned)g), dim3(kThreads), 0, sc, P);
         HIPCHK(ctx, hipGetLastError());
-        if (g_rocfft.execute(fft.fwd.at(batch), b, nullptr, fft.info[i]) != rocfft_status_success)
+        if (g_rocfft.execute(wk.fft.at(false, batch), b, nullptr, wk.fft.info[i]) != rocfft_status_success)
           return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
         hipLaunchKernelGGL(k_cl_mask, dim3((unsigned)g), dim3(kThreads), 0, sc, P);
         HIPCHK(ctx, hipGetLastError());
-        if (g_rocfft.execute(fft.inv.at(batch), b, nullptr, fft.info[i]) != rocfft_status_success)
+        if (g_rocfft.execute(wk.fft.at(true, batch), b, nullptr, wk.fft.info[i]) != rocfft_status_success)
           return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
         hipLaunchKernelGGL(k_cl_finish, dim3((unsigned)g), dim3(kThreads), 0, sc, P);
         HIPCHK(ctx, hipGetLastError());
@@ -515,7 +393,7 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
   }
   for (int i = 0; i < nstreams; ++i) {
     HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
-    if (int rc = harvest(i)) return rc;
+    if (int rc = st.harvest(ctx, i, kernel_ms)) return rc;
   }
   if (stats) {
     // per output point: three legs read (16 B) with their weights (8 B) and written (16 B), one phase written (8 B); the filter's
@@ -523,7 +401,7 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
     int64_t point = 3 * (16 + 8 + 16) + 8;
     if (rt != PRISIM_CLOSURE_DIRECT) point += 3 * 16;
     if (rt == PRISIM_CLOSURE_ROCFFT) point += 3 * 16 * 8;
-    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    stats->wall_ms = wall_ms_since(wall0);
     stats->kernel_ms = kernel_ms;
     stats->triads = ntriads;
     stats->chunks = nchunks;

@@ -8,7 +8,7 @@
 #include <cstdint>
 #include <functional>
 
-#include "../csrc/ctx_internal.h"
+#include "../csrc_addon/addon_internal.h"
 #include "../../include/prisim_closure.h"
 
 // What follows the phases of a chunk.  The loop sizes its chunks so that its own buffers and bytes_per_triad of the sink's, per triad

@@ -16,22 +16,17 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "../csrc/ctx_internal.h"
 #include "../../include/prisim_cpbins.h"
 #include "cpstack_internal.h"
 
-using namespace cpint;
-
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kKept = PRISIM_CPBINS_WTS | PRISIM_CPBINS_CP_MEAN | PRISIM_CPBINS_CP_MEDIAN;
 
 struct BinParams {
@@ -218,7 +213,7 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
                       prisim_cpbins_stats* stats) {
   return guarded(ctx, [&]() -> int {
   if (!ctx) return PRISIM_EINVAL;
-  const auto wall0 = std::chrono::steady_clock::now();
+  const WallTime wall0 = wall_now();
   const bool pf = kind == PRISIM_CPBINS_PHASE_FLAGS;
   if (!pf && kind != PRISIM_CPBINS_BINNED) return fail(ctx, PRISIM_EINVAL, "unknown input kind");
   if (n0 < 1 || n1 < 1 || ntriads < 1 || nchan < 1) return fail(ctx, PRISIM_EINVAL, "need n0, n1, ntriads and nchan >= 1");
@@ -289,7 +284,7 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
     *resident_in = made_in.release();
     if (stats) {
       *stats = prisim_cpbins_stats{};
-      stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+      stats->wall_ms = wall_ms_since(wall0);
       stats->upload_bytes = upload_bytes;
     }
     return PRISIM_OK;
@@ -318,34 +313,32 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
       if (!is_kept) out_doubles += (o == 1 || o == 2) ? 2 : 1;
     }
   const int64_t per_triad = in_per_triad + rows_out * nchan * 8 * out_doubles;
-  const int64_t budget = budget_bytes > 0 ? budget_bytes : kDefaultBudget;
+  const int64_t budget = budget_or_default(budget_bytes);
   const int64_t tc = per_triad > 0 ? std::max<int64_t>(1, std::min<int64_t>(ntriads, budget / per_triad)) : ntriads;
   const int64_t nchunks = (ntriads + tc - 1) / tc;
 
-  Dev dev;
+  Work wk;
   int64_t* d_off;
   int32_t* d_mem;
-  CB_ALLOC(ctx, dev, d_off, (nbins + 1) * 8);
-  CB_ALLOC(ctx, dev, d_mem, nmem * 4);
+  DEV_ALLOC(ctx, wk.dev, d_off, (nbins + 1) * 8);
+  DEV_ALLOC(ctx, wk.dev, d_mem, nmem * 4);
   double *d_a = nullptr, *d_b = nullptr, *d_w = nullptr;
   uint8_t* d_f = nullptr;
   if (!rin) {
-    CB_ALLOC(ctx, dev, d_a, rows_in * tc * nchan * 8);
+    DEV_ALLOC(ctx, wk.dev, d_a, rows_in * tc * nchan * 8);
     if (pf) {
-      CB_ALLOC(ctx, dev, d_f, rows_in * tc * nchan);
+      DEV_ALLOC(ctx, wk.dev, d_f, rows_in * tc * nchan);
     } else {
-      CB_ALLOC(ctx, dev, d_b, rows_in * tc * nchan * 8);
-      CB_ALLOC(ctx, dev, d_w, rows_in * tc * nchan * 8);
+      DEV_ALLOC(ctx, wk.dev, d_b, rows_in * tc * nchan * 8);
+      DEV_ALLOC(ctx, wk.dev, d_w, rows_in * tc * nchan * 8);
     }
   }
   double* d_out[7] = {};
   for (int o = 0; o < 7; ++o)
-    if ((comp >> o & 1) && !(keep_out && (kKept >> o & 1))) CB_ALLOC(ctx, dev, d_out[o], rows_out * tc * nchan * ((o == 1 || o == 2) ? 16 : 8));
-  Stream st;
-  HIPCHK(ctx, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-  HIPCHK(ctx, hipEventCreate(&st.k0));
-  HIPCHK(ctx, hipEventCreate(&st.k1));
-  hipStream_t s = st.s;
+    if ((comp >> o & 1) && !(keep_out && (kKept >> o & 1))) DEV_ALLOC(ctx, wk.dev, d_out[o], rows_out * tc * nchan * ((o == 1 || o == 2) ? 16 : 8));
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, 1, true)) return rc;
+  hipStream_t s = st.s[0];
   HIPCHK(ctx, hipMemcpyAsync(d_off, offsets, (nbins + 1) * 8, hipMemcpyHostToDevice, s));
   if (nmem > 0) HIPCHK(ctx, hipMemcpyAsync(d_mem, members, nmem * 4, hipMemcpyHostToDevice, s));
   upload_bytes += (nbins + 1) * 8 + nmem * 4;
@@ -405,10 +398,10 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
     p.mad_all = mad_ignores_flags ? 1 : 0;
     const int64_t total = rows_out * tn * nchan;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((total + kThreads - 1) / kThreads, kMaxBlocks));
-    HIPCHK(ctx, hipEventRecord(st.k0, s));
+    HIPCHK(ctx, hipEventRecord(st.k0[0], s));
     hipLaunchKernelGGL(k_cpbins, dim3((unsigned)blocks), dim3(kThreads), 0, s, p);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(st.k1, s));
+    HIPCHK(ctx, hipEventRecord(st.k1[0], s));
     for (int o = 0; o < 7; ++o) {
       if (!(want >> o & 1)) continue;
       const size_t es = (o == 1 || o == 2) ? 16 : 8;
@@ -421,7 +414,7 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
     }
     HIPCHK(ctx, hipStreamSynchronize(s));           // the chunk's buffers are reused by the next one
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, st.k0, st.k1) == hipSuccess) kernel_ms += ms;
+    if (hipEventElapsedTime(&ms, st.k0[0], st.k1[0]) == hipSuccess) kernel_ms += ms;
   }
   if (made_in) *resident_in = made_in.release();
   if (keep_out) *keep_out = kept.release();
@@ -429,7 +422,7 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
     int64_t outb = 0;
     for (int o = 0; o < 7; ++o)
       if (comp >> o & 1) outb += (o == 1 || o == 2) ? 16 : 8;
-    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    stats->wall_ms = wall_ms_since(wall0);
     stats->kernel_ms = kernel_ms;
     stats->elements = rows_out * row_elems;
     stats->chunks = nchunks;

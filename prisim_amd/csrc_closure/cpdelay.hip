@@ -23,10 +23,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -35,18 +33,8 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxStreams = 2;
 constexpr int kTile = 32;                             // turning kernels of the rocFFT route: lags and snapshots per tile
-constexpr int kMaxTile = 64;                          // snapshots per workgroup of the fused and resampling kernels
-constexpr int kTileLds = 65536;                       // LDS their snapshot rows may fill
-constexpr int64_t kDefaultBudget = int64_t(1) << 30;
 constexpr int64_t kMaxGrid = (int64_t(1) << 31) - 1;
-
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 rmul(double2 a, double s) { return make_double2(a.x * s, a.y * s); }
 
 struct CdParams {
   const double* phase;      // this chunk's [rows][nchan][nt]
@@ -78,7 +66,7 @@ __device__ __forceinline__ double2 phasor(double phi) {
 // fused route.  grid: x = (line - line0) * ntiles + (snapshot tile), line = row * nwin + window.  LDS: buf [tile][m + 1] | tw [m / 2]
 __global__ void __launch_bounds__(kThreads) k_cpd_fused(CdParams P, int64_t line0) {
   extern __shared__ double2 lds[];
-  const int m = P.m, ld = m + 1, tile = P.tile, half = m / 2;
+  const int m = P.m, ld = m + 1, tile = P.tile;
   double2* buf = lds;
   double2* tw = buf + (int64_t)tile * ld;
   const int64_t line = line0 + blockIdx.x / P.ntiles;
@@ -88,14 +76,10 @@ __global__ void __launch_bounds__(kThreads) k_cpd_fused(CdParams P, int64_t line
   const int w = (int)(line - row * P.nwin);
   const double* ph = P.phase + row * (int64_t)P.nchan * P.nt + t0;
   const double* wt = P.wts + (int64_t)w * P.nchan;
-  for (int k = threadIdx.x; k < half; k += kThreads) {
-    double sn, cs;
-    sincospi(2.0 * (double)k / (double)m, &sn, &cs);
-    tw[k] = make_double2(cs, sn);                                      // e^{+2 pi i k / m}
-  }
+  lds_twiddles(tw, m);
   for (int e = threadIdx.x; e < m * tile; e += kThreads) {             // lanes along the snapshots
     const int n = e / tile, tt = e - n * tile;
-    const int j = P.logm ? (int)(__brev((unsigned)n) >> (32 - P.logm)) : 0;
+    const int j = bitrev(n, P.logm);
     double2 v = make_double2(0.0, 0.0);
     if (n < P.nchan && tt < tcount) {
       const double wv = wt[n];
@@ -104,18 +88,7 @@ __global__ void __launch_bounds__(kThreads) k_cpd_fused(CdParams P, int64_t line
     buf[tt * ld + j] = v;
   }
   __syncthreads();
-  for (int h = 1; h < m; h <<= 1) {                                    // butterflies of span 2h; twiddle W_{2h}^pos = tw[pos * m / (2h)]
-    const int step = m / (2 * h);
-    for (int i = threadIdx.x; i < tile * half; i += kThreads) {
-      const int tt = i / half, ii = i - tt * half;
-      const int pos = ii & (h - 1);
-      const int a = tt * ld + ((ii - pos) << 1) + pos, b = a + h;
-      const double2 u = buf[a], v = cmul(buf[b], tw[pos * step]);
-      buf[a] = cadd(u, v);
-      buf[b] = csub(u, v);
-    }
-    __syncthreads();
-  }
+  lds_ifft_dit(buf, ld, tile, m, tw);
   const int64_t o = line * m * (int64_t)P.nt + t0;
   const double ps = P.pscale ? P.pscale[w] : 0.0;
   for (int e = threadIdx.x; e < m * tile; e += kThreads) {
@@ -259,48 +232,6 @@ __global__ void __launch_bounds__(kThreads) k_cpp_finish(int64_t n0, int64_t npt
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
-struct Dev {
-  std::vector<void*> ptrs;
-  ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
-};
-
-#define CD_ALLOC(ctx, dev, ptr, bytes)                                                                 \
-  do {                                                                                                 \
-    void* p_ = nullptr;                                                                                \
-    HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
-    (dev).ptrs.push_back(p_);                                                                          \
-    (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
-  } while (0)
-
-// the streams of the phases form and their kernel-timing events: drained before the buffers they use are freed (declared after Dev)
-struct Streams {
-  hipStream_t s[kMaxStreams] = {};
-  hipEvent_t k0[kMaxStreams] = {}, k1[kMaxStreams] = {};
-  bool timed[kMaxStreams] = {};
-  int n = 0;
-  ~Streams() {
-    for (int i = 0; i < n; ++i) {
-      (void)hipStreamSynchronize(s[i]);
-      if (k0[i]) (void)hipEventDestroy(k0[i]);
-      if (k1[i]) (void)hipEventDestroy(k1[i]);
-      (void)hipStreamDestroy(s[i]);
-    }
-  }
-};
-
-struct FftPlans {
-  std::map<size_t, rocfft_plan> inv;                // by batch
-  rocfft_execution_info info[kMaxStreams] = {};
-  ~FftPlans() {
-    for (auto& kv : inv) g_rocfft.plan_destroy(kv.second);
-    for (rocfft_execution_info i : info) if (i) g_rocfft.execution_info_destroy(i);
-  }
-};
-
-int grid_for(const prisim_ctx* ctx, int64_t n) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)std::max(ctx->cu_count, 1) * 16));
-}
-
 // the transform of the chunks: the tables, the per-stream output buffers, the launches and the downloads
 struct Transform {
   prisim_ctx* ctx;
@@ -309,8 +240,7 @@ struct Transform {
   bool fused, w_over, w_opow, w_res, w_rpow;
   int64_t tile = 0, ntiles = 1, lds = 0, rtile = 0, rntiles = 1, rlds = 0;
   double *over, *over_pow, *res, *res_pow;          // the caller's
-  Dev dev;
-  FftPlans fft;
+  Work wk;                                          // st: the streams of the phases form; from a cube, closure.hip's loop has its own
   CdParams base;
   double2 *d_over[kMaxStreams] = {}, *d_res[kMaxStreams] = {}, *d_fbuf[kMaxStreams] = {};
   double *d_opow[kMaxStreams] = {}, *d_rpow[kMaxStreams] = {};
@@ -338,50 +268,23 @@ struct Transform {
     double *d_wts, *d_ps = nullptr;
     int32_t *d_rsn, *d_rsk, *d_rsin;
     double2 *d_rsc, *d_rtw;
-    CD_ALLOC(ctx, dev, d_wts, (size_t)nwin * nchan * 8);
-    if (pscale) CD_ALLOC(ctx, dev, d_ps, (size_t)nwin * 8);
-    CD_ALLOC(ctx, dev, d_rsn, rs_n.size() * 4);
-    CD_ALLOC(ctx, dev, d_rsk, rs_k.size() * 4);
-    CD_ALLOC(ctx, dev, d_rsin, rs_in.size() * 4);
-    CD_ALLOC(ctx, dev, d_rsc, rs_c.size() * 8);
-    CD_ALLOC(ctx, dev, d_rtw, rtw.size() * 8);
+    DEV_ALLOC(ctx, wk.dev, d_wts, (size_t)nwin * nchan * 8);
+    if (pscale) DEV_ALLOC(ctx, wk.dev, d_ps, (size_t)nwin * 8);
+    DEV_ALLOC(ctx, wk.dev, d_rsn, rs_n.size() * 4);
+    DEV_ALLOC(ctx, wk.dev, d_rsk, rs_k.size() * 4);
+    DEV_ALLOC(ctx, wk.dev, d_rsin, rs_in.size() * 4);
+    DEV_ALLOC(ctx, wk.dev, d_rsc, rs_c.size() * 8);
+    DEV_ALLOC(ctx, wk.dev, d_rtw, rtw.size() * 8);
     for (int i = 0; i < nstreams; ++i) {
-      if (w_over) CD_ALLOC(ctx, dev, d_over[i], (size_t)lines * m * 16);
-      if (w_opow) CD_ALLOC(ctx, dev, d_opow[i], (size_t)lines * m * 8);
-      if (w_res) CD_ALLOC(ctx, dev, d_res[i], (size_t)lines * nres * 16);
-      if (w_rpow) CD_ALLOC(ctx, dev, d_rpow[i], (size_t)lines * nres * 8);
-      if (!fused && want_over()) CD_ALLOC(ctx, dev, d_fbuf[i], (size_t)lines * m * 16);
+      if (w_over) DEV_ALLOC(ctx, wk.dev, d_over[i], (size_t)lines * m * 16);
+      if (w_opow) DEV_ALLOC(ctx, wk.dev, d_opow[i], (size_t)lines * m * 8);
+      if (w_res) DEV_ALLOC(ctx, wk.dev, d_res[i], (size_t)lines * nres * 16);
+      if (w_rpow) DEV_ALLOC(ctx, wk.dev, d_rpow[i], (size_t)lines * nres * 8);
+      if (!fused && want_over()) DEV_ALLOC(ctx, wk.dev, d_fbuf[i], (size_t)lines * m * 16);
     }
     if (!fused && want_over()) {
-      RocfftApi& F = g_rocfft;
-      size_t wmax = 0;
-      for (int64_t c : {tc, last}) {
-        const size_t batch = (size_t)c * nwin * (size_t)nt;
-        if (fft.inv.count(batch)) continue;
-        size_t len = (size_t)m;
-        rocfft_plan p = nullptr;
-        if (F.plan_create(&p, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, rocfft_precision_double, 1, &len, batch,
-                          nullptr) != rocfft_status_success)
-          return fail(ctx, PRISIM_ELIB, "rocfft_plan_create failed");
-        fft.inv[batch] = p;
-        size_t wb = 0;
-        F.plan_get_work_buffer_size(p, &wb);
-        wmax = std::max(wmax, wb);
-      }
-      for (int i = 0; i < nstreams; ++i) {
-        if (F.execution_info_create(&fft.info[i]) != rocfft_status_success) {
-          fft.info[i] = nullptr;
-          return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_create failed");
-        }
-        if (F.execution_info_set_stream(fft.info[i], streams[i]) != rocfft_status_success)
-          return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_stream failed");
-        if (wmax) {
-          void* wb;
-          CD_ALLOC(ctx, dev, wb, wmax);
-          if (F.execution_info_set_work_buffer(fft.info[i], wb, wmax) != rocfft_status_success)
-            return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_work_buffer failed");
-        }
-      }
+      const size_t per_row = (size_t)nwin * (size_t)nt;
+      if (int rc = wk.fft.create(ctx, wk.dev, (size_t)m, {{true, per_row * (size_t)tc}, {true, per_row * (size_t)last}}, streams, nstreams)) return rc;
     }
     hipStream_t s0 = streams[0];
     HIPCHK(ctx, hipMemcpyAsync(d_wts, wts, (size_t)nwin * nchan * 8, hipMemcpyHostToDevice, s0));
@@ -427,7 +330,7 @@ struct Transform {
           HIPCHK(ctx, hipGetLastError());
         }
         void* b[1] = {d_fbuf[i]};
-        if (g_rocfft.execute(fft.inv.at((size_t)lines * (size_t)nt), b, nullptr, fft.info[i]) != rocfft_status_success)
+        if (g_rocfft.execute(wk.fft.at(true, (size_t)lines * (size_t)nt), b, nullptr, wk.fft.info[i]) != rocfft_status_success)
           return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
         for (int64_t l0 = 0; l0 < lines; l0 += step) {
           hipLaunchKernelGGL(k_cpd_finish, dim3((unsigned)(std::min(step, lines - l0) * nct * ntt)), dim3(kThreads), 0, s, P, l0, (int)nct,
@@ -470,7 +373,7 @@ int prisim_closure_delay_spectra(prisim_ctx* ctx, const double* phases, int64_t 
                                  prisim_cpdelay_stats* stats) {
   return guarded(ctx, [&]() -> int {
   if (!ctx) return PRISIM_EINVAL;
-  const auto wall0 = std::chrono::steady_clock::now();
+  const WallTime wall0 = wall_now();
   if (m < 1 || m > PRISIM_CPDELAY_MAX_LEN)
     return fail(ctx, PRISIM_EINVAL, "closure-phase delay spectra take 1 to " + std::to_string(PRISIM_CPDELAY_MAX_LEN) +
                                         " lags (PRISIM_CPDELAY_MAX_LEN); got m = " + std::to_string(m));
@@ -519,12 +422,7 @@ int prisim_closure_delay_spectra(prisim_ctx* ctx, const double* phases, int64_t 
     if (tr.rlds > lds_max) return fail(ctx, PRISIM_EINVAL, "a resampled row does not fit in LDS");
   }
   if (!tr.fused && tr.want_over()) {
-    std::string lerr;
-    if (!load_rocfft(lerr)) return fail(ctx, PRISIM_ELIB, lerr);
-    if (!g_rocfft.setup_done) {
-      if (g_rocfft.setup() != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_setup failed");
-      g_rocfft.setup_done = true;
-    }
+    if (int rc = ensure_rocfft(ctx)) return rc;
   }
 
   // the resampling tables: per window, the output bins that some nonzero channel of the window feeds
@@ -592,33 +490,19 @@ int prisim_closure_delay_spectra(prisim_ctx* ctx, const double* phases, int64_t 
     upload += (cube ? nbl * per * 16 : 0) + nbl * per * 8 + nchan * 8 + nrows * 24 + (masks ? nmask * nchan * 8 + (mask_index ? nbl * 4 : 0) : 0);
   } else {
     const int64_t per_row = per * 8 + tr.bytes_per_row();
-    const int64_t budget = budget_bytes > 0 ? budget_bytes : kDefaultBudget;
+    const int64_t budget = budget_or_default(budget_bytes);
     tc = std::max<int64_t>(1, std::min<int64_t>(nrows, budget / (kMaxStreams * per_row)));
     nchunks = (nrows + tc - 1) / tc;
     nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
-    Dev dev;
     double* d_phase[kMaxStreams] = {};
-    for (int i = 0; i < nstreams; ++i) CD_ALLOC(ctx, dev, d_phase[i], tc * per * 8);
-    Streams st;
-    for (int i = 0; i < nstreams; ++i) {
-      HIPCHK(ctx, hipStreamCreateWithFlags(&st.s[i], hipStreamNonBlocking));
-      st.n = i + 1;
-      HIPCHK(ctx, hipEventCreate(&st.k0[i]));
-      HIPCHK(ctx, hipEventCreate(&st.k1[i]));
-    }
+    for (int i = 0; i < nstreams; ++i) DEV_ALLOC(ctx, tr.wk.dev, d_phase[i], tc * per * 8);
+    Streams& st = tr.wk.st;
+    if (int rc = st.create(ctx, nstreams, true)) return rc;
     if (int rc = tr.prepare(tc, nrows - (nchunks - 1) * tc, nstreams, st.s)) return rc;
-    auto harvest = [&](int i) -> int {
-      if (!st.timed[i]) return PRISIM_OK;
-      HIPCHK(ctx, hipEventSynchronize(st.k1[i]));
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, st.k0[i], st.k1[i]) == hipSuccess) kernel_ms += ms;
-      st.timed[i] = false;
-      return PRISIM_OK;
-    };
     for (int64_t c = 0; c < nchunks; ++c) {
       const int i = (int)(c % nstreams);
       hipStream_t sc = st.s[i];
-      if (int rc = harvest(i)) return rc;
+      if (int rc = st.harvest(ctx, i, kernel_ms)) return rc;
       const int64_t T0 = c * tc, tn = std::min(tc, nrows - T0);
       HIPCHK(ctx, hipMemcpyAsync(d_phase[i], phases + (size_t)T0 * per, (size_t)tn * per * 8, hipMemcpyHostToDevice, sc));
       HIPCHK(ctx, hipEventRecord(st.k0[i], sc));
@@ -629,12 +513,12 @@ int prisim_closure_delay_spectra(prisim_ctx* ctx, const double* phases, int64_t 
     }
     for (int i = 0; i < nstreams; ++i) {
       HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
-      if (int rc = harvest(i)) return rc;
+      if (int rc = st.harvest(ctx, i, kernel_ms)) return rc;
     }
     upload += nrows * per * 8;
   }
   if (stats) {
-    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    stats->wall_ms = wall_ms_since(wall0);
     stats->kernel_ms = kernel_ms;
     stats->rows = nrows;
     stats->chunks = nchunks;
@@ -657,7 +541,7 @@ int prisim_closure_power(prisim_ctx* ctx, int64_t n0, int64_t nwin, int64_t inne
                          prisim_cpdelay_stats* stats) {
   return guarded(ctx, [&]() -> int {
   if (!ctx) return PRISIM_EINVAL;
-  const auto wall0 = std::chrono::steady_clock::now();
+  const WallTime wall0 = wall_now();
   const bool w_ind = want & PRISIM_CPPOWER_INDIVIDUAL, w_auto = want & PRISIM_CPPOWER_AUTO, w_cross = want & PRISIM_CPPOWER_CROSS;
   if (n0 < 1 || nwin < 1 || inner < 1) return fail(ctx, PRISIM_EINVAL, "need n0, nwin and inner >= 1");
   if (!(w_ind || w_auto || w_cross)) return fail(ctx, PRISIM_EINVAL, "nothing requested (want)");
@@ -669,26 +553,23 @@ int prisim_closure_power(prisim_ctx* ctx, int64_t n0, int64_t nwin, int64_t inne
   const int64_t npts = nwin * inner;
   const bool sums = w_auto || w_cross;
   const int64_t per_row = npts * (16 + (w_ind ? 8 : 0));
-  const int64_t budget = budget_bytes > 0 ? budget_bytes : kDefaultBudget;
+  const int64_t budget = budget_or_default(budget_bytes);
   const int64_t rc_rows = std::max<int64_t>(1, std::min<int64_t>(n0, budget / per_row));
   const int64_t nchunks = (n0 + rc_rows - 1) / rc_rows;
-  Dev dev;
+  Work wk;
   double2 *d_x, *d_sum = nullptr;
   double *d_scale, *d_ind = nullptr, *d_sumsq = nullptr, *d_auto = nullptr, *d_cross = nullptr;
-  CD_ALLOC(ctx, dev, d_x, rc_rows * npts * 16);
-  CD_ALLOC(ctx, dev, d_scale, nwin * 8);
-  if (w_ind) CD_ALLOC(ctx, dev, d_ind, rc_rows * npts * 8);
+  DEV_ALLOC(ctx, wk.dev, d_x, rc_rows * npts * 16);
+  DEV_ALLOC(ctx, wk.dev, d_scale, nwin * 8);
+  if (w_ind) DEV_ALLOC(ctx, wk.dev, d_ind, rc_rows * npts * 8);
   if (sums) {
-    CD_ALLOC(ctx, dev, d_sumsq, npts * 8);
-    CD_ALLOC(ctx, dev, d_sum, npts * 16);
-    CD_ALLOC(ctx, dev, d_auto, npts * 8);
-    if (w_cross) CD_ALLOC(ctx, dev, d_cross, npts * 8);
+    DEV_ALLOC(ctx, wk.dev, d_sumsq, npts * 8);
+    DEV_ALLOC(ctx, wk.dev, d_sum, npts * 16);
+    DEV_ALLOC(ctx, wk.dev, d_auto, npts * 8);
+    if (w_cross) DEV_ALLOC(ctx, wk.dev, d_cross, npts * 8);
   }
-  Streams st;
-  HIPCHK(ctx, hipStreamCreateWithFlags(&st.s[0], hipStreamNonBlocking));
-  st.n = 1;
-  HIPCHK(ctx, hipEventCreate(&st.k0[0]));
-  HIPCHK(ctx, hipEventCreate(&st.k1[0]));
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, 1, true)) return rc;
   hipStream_t s = st.s[0];
   HIPCHK(ctx, hipMemcpyAsync(d_scale, scale, nwin * 8, hipMemcpyHostToDevice, s));
   if (sums) {
@@ -717,7 +598,7 @@ int prisim_closure_power(prisim_ctx* ctx, int64_t n0, int64_t nwin, int64_t inne
   if (w_cross) HIPCHK(ctx, hipMemcpyAsync(out_cross, d_cross, npts * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
   if (stats) {
-    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    stats->wall_ms = wall_ms_since(wall0);
     stats->kernel_ms = kernel_ms;
     stats->rows = n0;
     stats->chunks = nchunks;

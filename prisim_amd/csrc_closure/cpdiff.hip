@@ -22,21 +22,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
 
-#include "../csrc/ctx_internal.h"
 #include "../../include/prisim_cpdiff.h"
 #include "cpstack_internal.h"
 
-using namespace cpint;
-
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kRun = 16;     // pairs of pairs per thread
 
 struct DiffParams {
@@ -112,7 +107,7 @@ int prisim_cphase_diff(prisim_ctx* ctx, const double* in_mean, const double* in_
                        prisim_cpdiff_stats* stats) {
   return guarded(ctx, [&]() -> int {
   if (!ctx) return PRISIM_EINVAL;
-  const auto wall0 = std::chrono::steady_clock::now();
+  const WallTime wall0 = wall_now();
   if (n0 < 1 || n1 < 1 || ntriads < 1 || nchan < 1) return fail(ctx, PRISIM_EINVAL, "need n0, n1, ntriads and nchan >= 1");
   if (n0 > (int64_t)1 << 24 || n1 > (int64_t)1 << 24 || ntriads > (int64_t)1 << 24 || nchan > (int64_t)1 << 24 ||
       n0 * n1 > ((int64_t)1 << 38) / (ntriads * nchan))
@@ -140,29 +135,27 @@ int prisim_cphase_diff(prisim_ctx* ctx, const double* in_mean, const double* in_
   const int64_t rows_in = n0 * n1, rows_out = n0 * ncomb, row_elems = ntriads * nchan;
   // chunks of triads: the chunk's input (unless resident) and its outputs within the budget
   const int64_t per_triad = (resident ? 0 : rows_in * nchan * 24) + rows_out * nchan * PRISIM_CPDIFF_OUT_BYTES;
-  const int64_t budget = budget_bytes > 0 ? budget_bytes : kDefaultBudget;
+  const int64_t budget = budget_or_default(budget_bytes);
   const int64_t tc = std::max<int64_t>(1, std::min<int64_t>(ntriads, budget / per_triad));
   const int64_t nchunks = (ntriads + tc - 1) / tc;
 
-  Dev dev;
+  Work wk;
   int4* d_pairs;
-  CB_ALLOC(ctx, dev, d_pairs, ncomb * 16);
+  DEV_ALLOC(ctx, wk.dev, d_pairs, ncomb * 16);
   double *d_a = nullptr, *d_b = nullptr, *d_w = nullptr;
   if (!resident) {
-    CB_ALLOC(ctx, dev, d_a, rows_in * tc * nchan * 8);
-    CB_ALLOC(ctx, dev, d_b, rows_in * tc * nchan * 8);
-    CB_ALLOC(ctx, dev, d_w, rows_in * tc * nchan * 8);
+    DEV_ALLOC(ctx, wk.dev, d_a, rows_in * tc * nchan * 8);
+    DEV_ALLOC(ctx, wk.dev, d_b, rows_in * tc * nchan * 8);
+    DEV_ALLOC(ctx, wk.dev, d_w, rows_in * tc * nchan * 8);
   }
   // the eight outputs: four complex128, two float64, two uint8
   constexpr size_t es[8] = {16, 16, 16, 16, 8, 8, 1, 1};
   void* const host_out[8] = {out_diff0_mean, out_diff0_median, out_diff1_mean, out_diff1_median, out_wts0, out_wts1, out_mask0, out_mask1};
   char* d_out[8] = {};
-  for (int o = 0; o < 8; ++o) CB_ALLOC(ctx, dev, d_out[o], rows_out * tc * nchan * (int64_t)es[o]);
-  Stream st;
-  HIPCHK(ctx, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-  HIPCHK(ctx, hipEventCreate(&st.k0));
-  HIPCHK(ctx, hipEventCreate(&st.k1));
-  hipStream_t s = st.s;
+  for (int o = 0; o < 8; ++o) DEV_ALLOC(ctx, wk.dev, d_out[o], rows_out * tc * nchan * (int64_t)es[o]);
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, 1, true)) return rc;
+  hipStream_t s = st.s[0];
   HIPCHK(ctx, hipMemcpyAsync(d_pairs, pairs, ncomb * 16, hipMemcpyHostToDevice, s));
   int64_t upload_bytes = ncomb * 16, download_bytes = 0;
 
@@ -200,10 +193,10 @@ int prisim_cphase_diff(prisim_ctx* ctx, const double* in_mean, const double* in_
     p.nruns = (ncomb + kRun - 1) / kRun;
     const int64_t total = n0 * p.nruns * tn * nchan;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((total + kThreads - 1) / kThreads, kMaxBlocks));
-    HIPCHK(ctx, hipEventRecord(st.k0, s));
+    HIPCHK(ctx, hipEventRecord(st.k0[0], s));
     hipLaunchKernelGGL(k_cpdiff, dim3((unsigned)blocks), dim3(kThreads), 0, s, p);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(st.k1, s));
+    HIPCHK(ctx, hipEventRecord(st.k1[0], s));
     for (int o = 0; o < 8; ++o) {
       HIPCHK(ctx, copy_rows(static_cast<char*>(host_out[o]) + (size_t)(T0 * nchan) * es[o], (size_t)row_elems * es[o], d_out[o],
                             (size_t)(tn * nchan) * es[o], (size_t)(tn * nchan) * es[o], rows_out, hipMemcpyDeviceToHost, s));
@@ -211,10 +204,10 @@ int prisim_cphase_diff(prisim_ctx* ctx, const double* in_mean, const double* in_
     }
     HIPCHK(ctx, hipStreamSynchronize(s));           // the chunk's buffers are reused by the next one
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, st.k0, st.k1) == hipSuccess) kernel_ms += ms;
+    if (hipEventElapsedTime(&ms, st.k0[0], st.k1[0]) == hipSuccess) kernel_ms += ms;
   }
   if (stats) {
-    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    stats->wall_ms = wall_ms_since(wall0);
     stats->kernel_ms = kernel_ms;
     stats->elements = rows_out * row_elems;
     stats->chunks = nchunks;

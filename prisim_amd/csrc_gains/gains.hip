@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "../csrc/ctx_internal.h"
+#include "../csrc_addon/addon_internal.h"
 #include "../../include/prisim_gains.h"
 
 struct prisim_gains_table {
@@ -31,37 +31,11 @@ namespace {
 using pint::fail;
 using pint::guarded;
 
-constexpr int kThreads = 256;
 constexpr int kMaxK = PRISIM_GAINS_MAX_DEGREE;
 constexpr int kW = kMaxK + 1;                 // B-spline weights stored per point
-constexpr int64_t kMaxBlocks = int64_t(1) << 20;
 constexpr size_t kApplyChunkBytes = size_t(512) << 20;   // device bytes per streamed cube (sky, noise, output) of one apply chunk
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ double2 cconj(double2 a) { return make_double2(a.x, -a.y); }
-
-struct Dev {
-  std::vector<void*> ptrs;
-  ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
-};
-
-#define GN_ALLOC(ctx, dev, ptr, bytes)                                                                 \
-  do {                                                                                                 \
-    void* p_ = nullptr;                                                                                \
-    HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
-    (dev).ptrs.push_back(p_);                                                                          \
-    (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
-  } while (0)
-
-struct Events {
-  hipEvent_t e[4] = {};
-  ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-int events_create(prisim_ctx* ctx, Events& ev) {
-  for (hipEvent_t& e : ev.e) HIPCHK(ctx, hipEventCreate(&e));
-  return PRISIM_OK;
-}
 
 int fill_stats(prisim_ctx* ctx, Events& ev, int64_t elements, prisim_gains_stats* stats) {
   if (!stats) return PRISIM_OK;
@@ -311,23 +285,23 @@ int prisim_gains_eval_spline(prisim_ctx* ctx, int64_t nrows, int32_t kx, int32_t
   Dev dev;
   Events ev;
   int rc;
-  if ((rc = events_create(ctx, ev))) return rc;
+  if ((rc = ev.create(ctx))) return rc;
   int64_t *d_nx, *d_ny, *d_kxo, *d_kyo, *d_co;
   double *d_kn, *d_c, *d_t, *d_f, *d_wx, *d_wy;
   int32_t *d_sx, *d_sy;
-  GN_ALLOC(ctx, dev, d_nx, nspl * 8);
-  GN_ALLOC(ctx, dev, d_ny, nspl * 8);
-  GN_ALLOC(ctx, dev, d_kxo, nspl * 8);
-  GN_ALLOC(ctx, dev, d_kyo, nspl * 8);
-  GN_ALLOC(ctx, dev, d_co, nspl * 8);
-  GN_ALLOC(ctx, dev, d_kn, nknots * 8);
-  GN_ALLOC(ctx, dev, d_c, ncoefs * 8);
-  GN_ALLOC(ctx, dev, d_t, nt * 8);
-  GN_ALLOC(ctx, dev, d_f, nchan * 8);
-  GN_ALLOC(ctx, dev, d_sx, nspl * nt * 4);
-  GN_ALLOC(ctx, dev, d_sy, nspl * nchan * 4);
-  GN_ALLOC(ctx, dev, d_wx, nspl * nt * kW * 8);
-  GN_ALLOC(ctx, dev, d_wy, nspl * nchan * kW * 8);
+  DEV_ALLOC(ctx, dev, d_nx, nspl * 8);
+  DEV_ALLOC(ctx, dev, d_ny, nspl * 8);
+  DEV_ALLOC(ctx, dev, d_kxo, nspl * 8);
+  DEV_ALLOC(ctx, dev, d_kyo, nspl * 8);
+  DEV_ALLOC(ctx, dev, d_co, nspl * 8);
+  DEV_ALLOC(ctx, dev, d_kn, nknots * 8);
+  DEV_ALLOC(ctx, dev, d_c, ncoefs * 8);
+  DEV_ALLOC(ctx, dev, d_t, nt * 8);
+  DEV_ALLOC(ctx, dev, d_f, nchan * 8);
+  DEV_ALLOC(ctx, dev, d_sx, nspl * nt * 4);
+  DEV_ALLOC(ctx, dev, d_sy, nspl * nchan * 4);
+  DEV_ALLOC(ctx, dev, d_wx, nspl * nt * kW * 8);
+  DEV_ALLOC(ctx, dev, d_wy, nspl * nchan * kW * 8);
   prisim_gains_table* tab = nullptr;
   if ((rc = new_table(ctx, nt, nrows, nchan, &tab))) return rc;
   struct Guard {
@@ -381,13 +355,13 @@ int prisim_gains_gather(prisim_ctx* ctx, int64_t nrows, int64_t ngf, int64_t ngt
   Dev dev;
   Events ev;
   int rc;
-  if ((rc = events_create(ctx, ev))) return rc;
+  if ((rc = ev.create(ctx))) return rc;
   double2* d_g;
   int64_t *d_fi, *d_ti;
   const size_t gbytes = (size_t)nrows * ngf * ngt * 16;
-  GN_ALLOC(ctx, dev, d_g, gbytes);
-  GN_ALLOC(ctx, dev, d_fi, nchan * 8);
-  GN_ALLOC(ctx, dev, d_ti, nt * 8);
+  DEV_ALLOC(ctx, dev, d_g, gbytes);
+  DEV_ALLOC(ctx, dev, d_fi, nchan * 8);
+  DEV_ALLOC(ctx, dev, d_ti, nt * 8);
   prisim_gains_table* tab = nullptr;
   if ((rc = new_table(ctx, nt, nrows, nchan, &tab))) return rc;
   struct Guard {
@@ -466,7 +440,7 @@ int prisim_gains_apply(prisim_ctx* ctx, int64_t nt, int64_t nbl, int64_t nchan, 
   Dev dev;
   Events ev;
   int rc;
-  if ((rc = events_create(ctx, ev))) return rc;
+  if ((rc = ev.create(ctx))) return rc;
   const int64_t nel = nt * nbl * nchan;
   const size_t snap_bytes = (size_t)nbl * nchan * 16;
   // the cube streams through the device in chunks of whole snapshots: sky, noise and output buffers of at most kApplyChunkBytes each
@@ -474,11 +448,11 @@ int prisim_gains_apply(prisim_ctx* ctx, int64_t nt, int64_t nbl, int64_t nchan, 
   const size_t cbytes = (size_t)tc * snap_bytes;
   double2 *d_sky = nullptr, *d_noise = nullptr, *d_out;
   int64_t *d_aa = nullptr, *d_ca = nullptr, *d_ab = nullptr, *d_cb = nullptr;
-  GN_ALLOC(ctx, dev, d_out, cbytes);
-  if (!want_gain && sky) GN_ALLOC(ctx, dev, d_sky, cbytes);
-  if (!want_gain && noise) GN_ALLOC(ctx, dev, d_noise, cbytes);
-  if (ta) { GN_ALLOC(ctx, dev, d_aa, nbl * 8); GN_ALLOC(ctx, dev, d_ca, nbl * 8); }
-  if (tb) { GN_ALLOC(ctx, dev, d_ab, nbl * 8); GN_ALLOC(ctx, dev, d_cb, nbl * 8); }
+  DEV_ALLOC(ctx, dev, d_out, cbytes);
+  if (!want_gain && sky) DEV_ALLOC(ctx, dev, d_sky, cbytes);
+  if (!want_gain && noise) DEV_ALLOC(ctx, dev, d_noise, cbytes);
+  if (ta) { DEV_ALLOC(ctx, dev, d_aa, nbl * 8); DEV_ALLOC(ctx, dev, d_ca, nbl * 8); }
+  if (tb) { DEV_ALLOC(ctx, dev, d_ab, nbl * 8); DEV_ALLOC(ctx, dev, d_cb, nbl * 8); }
   hipStream_t st = ctx->stream;
   HIPCHK(ctx, hipEventRecord(ev.e[0], st));
   if (ta) {

@@ -21,28 +21,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "../csrc/ctx_internal.h"
+#include "../csrc_addon/addon_internal.h"
 #include "../../include/prisim_runs.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kMaxStreams = 2;
-constexpr int kMaxTile = 64;
-constexpr int kTileLds = 65536;                       // LDS the snapshot tile may fill (the fused kernel of m = 4096 takes 96 KiB)
-constexpr int64_t kDefaultBudget = int64_t(1) << 30;  // device bytes of a call when the caller gives none
-
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 rmul(double2 a, double s) { return make_double2(a.x * s, a.y * s); }
 
 struct RunParams {
   const void* vis;          // this chunk's [pc][nchan][nt] (complex128 or complex64), or null: ones
@@ -107,32 +94,16 @@ __global__ void __launch_bounds__(kThreads) k_runs_fused(RunParams P) {
   const int t0 = (int)(blockIdx.x % P.ntiles) * tile;
   const int w = blockIdx.y;
   const int tcount = min(tile, P.nt - t0);
-  for (int k = threadIdx.x; k < m / 2; k += kThreads) {
-    double sn, cs;
-    sincospi(2.0 * (double)k / (double)m, &sn, &cs);
-    tw[k] = make_double2(cs, sn);
-  }
+  lds_twiddles(tw, m);
   for (int e = threadIdx.x; e < m * tile; e += kThreads) {
     const int n = e / tile, tt = e - n * tile;
-    const int j = P.logm ? (int)(__brev((unsigned)n) >> (32 - P.logm)) : 0;
+    const int j = bitrev(n, P.logm);
     double2 v = make_double2(0.0, 0.0);
     if (n < P.nchan && tt < tcount) v = rmul(row_value(P, pl, n, t0 + tt, w), (m > 1 && (n & 1)) ? -P.s : P.s);
     buf[tt * m + j] = v;
   }
   __syncthreads();
-  const int half = m / 2;
-  for (int h = 1; h < m; h <<= 1) {               // butterflies of span 2h; twiddle W_{2h}^pos = tw[pos * m / (2h)]
-    const int step = m / (2 * h);
-    for (int i = threadIdx.x; i < tile * half; i += kThreads) {
-      const int tt = i / half, ii = i - tt * half;
-      const int pos = ii & (h - 1);
-      const int a = tt * m + ((ii - pos) << 1) + pos, b = a + h;
-      const double2 u = buf[a], v = cmul(buf[b], tw[pos * step]);
-      buf[a] = cadd(u, v);
-      buf[b] = csub(u, v);
-    }
-    __syncthreads();
-  }
+  lds_ifft_dit(buf, m, tile, m, tw);
   double2* dst = P.out + ((int64_t)w * P.pc + pl) * P.nout * P.nt + t0;
   for (int e = threadIdx.x; e < P.nout * tile; e += kThreads) {
     const int j = e / tile, tt = e - j * tile;
@@ -227,49 +198,9 @@ __global__ void __launch_bounds__(kThreads) k_runs_power(const T* a, const T* b,
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
-struct Dev {
-  std::vector<void*> ptrs;
-  ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
-};
-
-#define RUNS_ALLOC(ctx, dev, ptr, bytes)                                                               \
-  do {                                                                                                 \
-    void* p_ = nullptr;                                                                                \
-    HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
-    (dev).ptrs.push_back(p_);                                                                          \
-    (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
-  } while (0)
-
-// the call's streams: drained before the buffers they use are freed (declared after Dev, destroyed before it)
-struct Streams {
-  hipStream_t s[kMaxStreams] = {};
-  int n = 0;
-  ~Streams() {
-    for (int i = 0; i < n; ++i) {
-      (void)hipStreamSynchronize(s[i]);
-      (void)hipStreamDestroy(s[i]);
-    }
-  }
-};
-
-struct FftPlans {
-  std::map<size_t, rocfft_plan> plans;              // by batch
-  rocfft_execution_info info[kMaxStreams] = {};
-  ~FftPlans() {
-    for (auto& kv : plans) g_rocfft.plan_destroy(kv.second);
-    for (rocfft_execution_info i : info) if (i) g_rocfft.execution_info_destroy(i);
-  }
-};
-
 // elements a strided weight array spans (strides >= 0)
 int64_t span_of(const int64_t* st, int64_t nbl, int64_t nchan, int64_t nt) {
   return (nbl - 1) * st[0] + (nchan - 1) * st[1] + (nt - 1) * st[2] + 1;
-}
-
-int64_t budget_or_default(int64_t budget) { return budget > 0 ? budget : kDefaultBudget; }
-
-int grid_for(const prisim_ctx* ctx, int64_t n) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)std::max(ctx->cu_count, 1) * 16));
 }
 
 }  // namespace
@@ -283,7 +214,7 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
                           double* out, prisim_runs_stats* stats) {
   return guarded(ctx, [&]() -> int {
   if (!ctx) return PRISIM_EINVAL;
-  const auto wall0 = std::chrono::steady_clock::now();
+  const WallTime wall0 = wall_now();
   if (m < 1 || m > PRISIM_RUNS_MAX_LEN)
     return fail(ctx, PRISIM_EINVAL, "delay spectra of runs take 1 to " + std::to_string(PRISIM_RUNS_MAX_LEN) +
                                         " lags (PRISIM_SUBBAND_MAX_LEN); got m = " + std::to_string(m));
@@ -310,44 +241,15 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
   const int rt = resample ? PRISIM_RUNS_DIRECT : (route == PRISIM_RUNS_ROCFFT || (route == PRISIM_RUNS_AUTO && !pow2))
                                                     ? PRISIM_RUNS_ROCFFT : PRISIM_RUNS_FUSED;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (rt == PRISIM_RUNS_ROCFFT) {
-    std::string lerr;
-    if (!load_rocfft(lerr)) return fail(ctx, PRISIM_ELIB, lerr);
-    if (!g_rocfft.setup_done) {
-      if (g_rocfft.setup() != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_setup failed");
-      g_rocfft.setup_done = true;
-    }
-  }
+  if (rt == PRISIM_RUNS_ROCFFT)
+    if (int rc = ensure_rocfft(ctx)) return rc;
 
   // the resampling tables: per output bin at most two input bins (padding bins dropped), and per window the bins it can make nonzero
   std::vector<int32_t> rs_in, klist, kofs((size_t)nwin + 1, 0);
   std::vector<double> rs_c, rtw;
   const double s = scale / (double)m;
   if (resample) {
-    if (nmap < 1 || !map_out || !map_in || !map_w) return fail(ctx, PRISIM_EINVAL, "the resampled spectra need the selection map");
-    rs_in.assign(2 * (size_t)nout, -1);
-    rs_c.assign(4 * (size_t)nout, 0.0);
-    rtw.assign(2 * (size_t)nout, 0.0);
-    std::vector<int> used((size_t)nout, 0);
-    const int64_t half = m / 2;
-    for (int64_t e = 0; e < nmap; ++e) {
-      const int64_t k = map_out[e], kin = map_in[e];
-      if (k < 0 || k >= nout || kin < 0 || kin >= m) return fail(ctx, PRISIM_EINVAL, "selection map entry out of range");
-      if (used[(size_t)k] == 2) return fail(ctx, PRISIM_EINVAL, "selection map: more than two entries for one output bin");
-      const int sl = used[(size_t)k]++;
-      if (kin >= nchan) continue;                    // a bin of the zero padding
-      const int64_t red = (kin * half) % m;          // e^{-2 pi i k_in floor(m/2) / m}
-      const double a = -2.0 * M_PI * (double)red / (double)m;
-      const double sc = map_w[e] * s;
-      rs_in[(size_t)sl * nout + k] = (int32_t)kin;
-      rs_c[2 * ((size_t)sl * nout + k)] = sc * std::cos(a);
-      rs_c[2 * ((size_t)sl * nout + k) + 1] = sc * std::sin(a);
-    }
-    for (int64_t q = 0; q < nout; ++q) {
-      const double a = 2.0 * M_PI * (double)q / (double)nout;
-      rtw[2 * q] = std::cos(a);
-      rtw[2 * q + 1] = std::sin(a);
-    }
+    if (int rc = build_resample_tables(ctx, nout, m, nchan, s, nmap, map_out, map_in, map_w, rs_in, rs_c, rtw)) return rc;
     for (int w = 0; w < nwin; ++w) {
       int64_t lo = 0, hi = nchan;
       if (win) {
@@ -386,65 +288,35 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
   const int64_t nchunks = (P + pc - 1) / pc;
   const int nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
 
-  Dev dev;
+  Work wk;
   const int64_t bp_n = bp ? span_of(bp_strides, nbl, nchan, nt) : 0, wts_n = wts ? span_of(wts_strides, nbl, nchan, nt) : 0;
   double *d_bp = nullptr, *d_wts = nullptr, *d_win = nullptr;
   int32_t *d_rsin = nullptr, *d_klist = nullptr, *d_kofs = nullptr;
   double2 *d_rsc = nullptr, *d_rtw = nullptr;
-  if (bp) RUNS_ALLOC(ctx, dev, d_bp, bp_n * 8);
-  if (wts) RUNS_ALLOC(ctx, dev, d_wts, wts_n * 8);
-  if (win) RUNS_ALLOC(ctx, dev, d_win, (size_t)nwin * nchan * 8);
+  if (bp) DEV_ALLOC(ctx, wk.dev, d_bp, bp_n * 8);
+  if (wts) DEV_ALLOC(ctx, wk.dev, d_wts, wts_n * 8);
+  if (win) DEV_ALLOC(ctx, wk.dev, d_win, (size_t)nwin * nchan * 8);
   if (resample) {
-    RUNS_ALLOC(ctx, dev, d_rsin, rs_in.size() * 4);
-    RUNS_ALLOC(ctx, dev, d_rsc, rs_c.size() * 8);
-    RUNS_ALLOC(ctx, dev, d_rtw, rtw.size() * 8);
-    RUNS_ALLOC(ctx, dev, d_klist, std::max<size_t>(klist.size(), 1) * 4);
-    RUNS_ALLOC(ctx, dev, d_kofs, kofs.size() * 4);
+    DEV_ALLOC(ctx, wk.dev, d_rsin, rs_in.size() * 4);
+    DEV_ALLOC(ctx, wk.dev, d_rsc, rs_c.size() * 8);
+    DEV_ALLOC(ctx, wk.dev, d_rtw, rtw.size() * 8);
+    DEV_ALLOC(ctx, wk.dev, d_klist, std::max<size_t>(klist.size(), 1) * 4);
+    DEV_ALLOC(ctx, wk.dev, d_kofs, kofs.size() * 4);
   }
   void* d_in[kMaxStreams] = {};
   double2* d_out[kMaxStreams] = {};
   double2* d_fbuf[kMaxStreams] = {};
   for (int i = 0; i < nstreams; ++i) {
-    if (vis) RUNS_ALLOC(ctx, dev, d_in[i], pc * in_pair);
-    RUNS_ALLOC(ctx, dev, d_out[i], pc * out_pair);
-    if (fbuf_pair) RUNS_ALLOC(ctx, dev, d_fbuf[i], pc * fbuf_pair);
+    if (vis) DEV_ALLOC(ctx, wk.dev, d_in[i], pc * in_pair);
+    DEV_ALLOC(ctx, wk.dev, d_out[i], pc * out_pair);
+    if (fbuf_pair) DEV_ALLOC(ctx, wk.dev, d_fbuf[i], pc * fbuf_pair);
   }
-  FftPlans fft;
-  Streams st;
-  for (int i = 0; i < nstreams; ++i) {
-    HIPCHK(ctx, hipStreamCreateWithFlags(&st.s[i], hipStreamNonBlocking));
-    st.n = i + 1;
-  }
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, nstreams, false)) return rc;
   if (rt == PRISIM_RUNS_ROCFFT) {
-    RocfftApi& F = g_rocfft;
-    size_t wmax = 0;
-    for (int64_t c : {pc, P - (nchunks - 1) * pc}) {
-      const size_t batch = (size_t)nwin * (size_t)c * (size_t)nt;
-      if (fft.plans.count(batch)) continue;
-      size_t len = (size_t)m;
-      rocfft_plan p = nullptr;
-      if (F.plan_create(&p, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, rocfft_precision_double, 1, &len, batch,
-                        nullptr) != rocfft_status_success)
-        return fail(ctx, PRISIM_ELIB, "rocfft_plan_create failed");
-      fft.plans[batch] = p;
-      size_t wb = 0;
-      F.plan_get_work_buffer_size(p, &wb);
-      wmax = std::max(wmax, wb);
-    }
-    for (int i = 0; i < nstreams; ++i) {
-      if (F.execution_info_create(&fft.info[i]) != rocfft_status_success) {
-        fft.info[i] = nullptr;
-        return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_create failed");
-      }
-      if (F.execution_info_set_stream(fft.info[i], st.s[i]) != rocfft_status_success)
-        return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_stream failed");
-      if (wmax) {
-        void* wb;
-        RUNS_ALLOC(ctx, dev, wb, wmax);
-        if (F.execution_info_set_work_buffer(fft.info[i], wb, wmax) != rocfft_status_success)
-          return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_work_buffer failed");
-      }
-    }
+    const size_t lines = (size_t)nwin * (size_t)nt;
+    if (int rc = wk.fft.create(ctx, wk.dev, (size_t)m, {{true, lines * (size_t)pc}, {true, lines * (size_t)(P - (nchunks - 1) * pc)}}, st.s, nstreams))
+      return rc;
   }
 
   // the tables on stream 0; stream 1 waits for them
@@ -498,7 +370,7 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
       hipLaunchKernelGGL(k_runs_prepare, dim3((unsigned)grid_for(ctx, nf)), dim3(kThreads), 0, sc, Pm);
       HIPCHK(ctx, hipGetLastError());
       void* b[1] = {d_fbuf[i]};
-      if (g_rocfft.execute(fft.plans.at((size_t)nwin * (size_t)pn * (size_t)nt), b, nullptr, fft.info[i]) != rocfft_status_success)
+      if (g_rocfft.execute(wk.fft.at(true, (size_t)nwin * (size_t)nt * (size_t)pn), b, nullptr, wk.fft.info[i]) != rocfft_status_success)
         return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
       hipLaunchKernelGGL(k_runs_finish, dim3((unsigned)grid_for(ctx, no)), dim3(kThreads), 0, sc, Pm);
       HIPCHK(ctx, hipGetLastError());
@@ -510,7 +382,7 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
   }
   for (int i = 0; i < nstreams; ++i) HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
   if (stats) {
-    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    stats->wall_ms = wall_ms_since(wall0);
     stats->pairs = P;
     stats->chunks = nchunks;
     stats->chunk_pairs = pc;
@@ -527,7 +399,7 @@ int prisim_runs_power(prisim_ctx* ctx, int64_t nf, int64_t inner, const void* v1
                       int32_t cross, int32_t fused_product, int64_t budget_bytes, double* out, prisim_runs_stats* stats) {
   return guarded(ctx, [&]() -> int {
   if (!ctx) return PRISIM_EINVAL;
-  const auto wall0 = std::chrono::steady_clock::now();
+  const WallTime wall0 = wall_now();
   if (nf < 1 || inner < 1) return fail(ctx, PRISIM_EINVAL, "need nf >= 1 and inner >= 1");
   if (!v1 || !factor || !out) return fail(ctx, PRISIM_EINVAL, "null array");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -538,22 +410,19 @@ int prisim_runs_power(prisim_ctx* ctx, int64_t nf, int64_t inner, const void* v1
   const int64_t ce = std::max<int64_t>(1, std::min<int64_t>(n, budget / (kMaxStreams * per)));
   const int64_t nchunks = (n + ce - 1) / ce;
   const int nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
-  Dev dev;
+  Work wk;
   double* d_f;
-  RUNS_ALLOC(ctx, dev, d_f, nf * 8);
+  DEV_ALLOC(ctx, wk.dev, d_f, nf * 8);
   void* d_a[kMaxStreams] = {};
   void* d_b[kMaxStreams] = {};
   double* d_o[kMaxStreams] = {};
   for (int i = 0; i < nstreams; ++i) {
-    RUNS_ALLOC(ctx, dev, d_a[i], ce * esz);
-    if (v2) RUNS_ALLOC(ctx, dev, d_b[i], ce * esz);
-    RUNS_ALLOC(ctx, dev, d_o[i], ce * 8);
+    DEV_ALLOC(ctx, wk.dev, d_a[i], ce * esz);
+    if (v2) DEV_ALLOC(ctx, wk.dev, d_b[i], ce * esz);
+    DEV_ALLOC(ctx, wk.dev, d_o[i], ce * 8);
   }
-  Streams st;
-  for (int i = 0; i < nstreams; ++i) {
-    HIPCHK(ctx, hipStreamCreateWithFlags(&st.s[i], hipStreamNonBlocking));
-    st.n = i + 1;
-  }
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, nstreams, false)) return rc;
   HIPCHK(ctx, hipMemcpyAsync(d_f, factor, nf * 8, hipMemcpyHostToDevice, st.s[0]));
   HIPCHK(ctx, hipStreamSynchronize(st.s[0]));
   for (int64_t c = 0; c < nchunks; ++c) {
@@ -574,7 +443,7 @@ int prisim_runs_power(prisim_ctx* ctx, int64_t nf, int64_t inner, const void* v1
   }
   for (int i = 0; i < nstreams; ++i) HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
   if (stats) {
-    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    stats->wall_ms = wall_ms_since(wall0);
     stats->pairs = n;
     stats->chunks = nchunks;
     stats->chunk_pairs = ce;

@@ -23,18 +23,12 @@
 #include <string>
 #include <vector>
 
-#include "../csrc/ctx_internal.h"
+#include "../csrc_addon/addon_internal.h"
 #include "../../include/prisim_subband.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int64_t kMaxGridRows = int64_t(1) << 22;     // rows per launch: grid x threads stays far inside 32 bits
-
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 rmul(double2 a, double s) { return make_double2(a.x * s, a.y * s); }
 
 struct SbParams {
   const double2* src;       // row r of cube c: src + c * cube_stride + r * nchan
@@ -124,11 +118,7 @@ __global__ void __launch_bounds__(kThreads) k_sb_fused(SbParams P) {
   int* cnt = zi + P.nres;
   const int64_t r = P.row0 + blockIdx.x;
   const bool want_over = P.over || P.over_pow, want_res = P.res || P.res_pow;
-  for (int k = threadIdx.x; k < m / 2; k += kThreads) {
-    double s, co;
-    sincospi(2.0 * (double)k / (double)m, &s, &co);
-    tw[k] = make_double2(co, s);
-  }
+  lds_twiddles(tw, m);
   for (int c = 0; c < P.ncubes; ++c) {
     load_row(P, c, r, xs);
     __syncthreads();
@@ -137,23 +127,13 @@ __global__ void __launch_bounds__(kThreads) k_sb_fused(SbParams P) {
       if (want_over) {
         const double* wt = P.wts + (int64_t)w * nchan;
         for (int n = threadIdx.x; n < m; n += kThreads) {
-          const int j = P.logm ? (int)(__brev((unsigned)n) >> (32 - P.logm)) : 0;
+          const int j = bitrev(n, P.logm);
           double2 v = make_double2(0.0, 0.0);
           if (n >= lo && n < hi) v = rmul(rmul(xs[n], wt[n]), (m > 1 && (n & 1)) ? -P.df : P.df);
           buf[j] = v;
         }
         __syncthreads();
-        for (int h = 1; h < m; h <<= 1) {             // butterflies of span 2h; twiddle W_{2h}^pos = tw[pos * m / (2h)]
-          const int step = m / (2 * h);
-          for (int i = threadIdx.x; i < m / 2; i += kThreads) {
-            const int pos = i & (h - 1);
-            const int a = ((i - pos) << 1) + pos, b = a + h;
-            const double2 u = buf[a], v = cmul(buf[b], tw[pos * step]);
-            buf[a] = cadd(u, v);
-            buf[b] = csub(u, v);
-          }
-          __syncthreads();
-        }
+        lds_ifft_dit(buf, m, 1, m, tw);
         const int64_t o = (((int64_t)c * P.nrows + r) * P.nwin + w) * m;
         const double ps = P.pscale ? P.pscale[w] : 0.0;
         for (int j = threadIdx.x; j < m; j += kThreads) {
@@ -209,33 +189,6 @@ __global__ void __launch_bounds__(kThreads) k_sb_finish(SbParams P, int64_t nlin
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-
-struct Dev {
-  std::vector<void*> ptrs;
-  ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
-};
-
-#define SB_ALLOC(ctx, dev, ptr, bytes)                                                                 \
-  do {                                                                                                 \
-    void* p_ = nullptr;                                                                                \
-    HIPCHK(ctx, hipMalloc(&p_, std::max<size_t>((size_t)(bytes), 16)));                                \
-    (dev).ptrs.push_back(p_);                                                                          \
-    (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
-  } while (0)
-
-struct Events {
-  hipEvent_t e[4] = {};
-  ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-struct FftPlan {
-  rocfft_plan p = nullptr;
-  rocfft_execution_info i = nullptr;
-  ~FftPlan() {
-    if (p) g_rocfft.plan_destroy(p);
-    if (i) g_rocfft.execution_info_destroy(i);
-  }
-};
 
 int lds_fused(int64_t nchan, int64_t m, int64_t nres) {
   return (int)(16 * (nchan + m + std::max<int64_t>(m / 2, 1) + nres) + 4 * nres + 16);
@@ -295,12 +248,7 @@ int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_
   if (!fused && lp > lds_max) return fail(ctx, PRISIM_EINVAL, "sub-band rows do not fit in LDS");
   const bool want_over = w_over || w_opow;
   if (!fused && want_over) {
-    std::string lerr;
-    if (!load_rocfft(lerr)) return fail(ctx, PRISIM_ELIB, lerr);
-    if (!g_rocfft.setup_done) {
-      if (g_rocfft.setup() != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_setup failed");
-      g_rocfft.setup_done = true;
-    }
+    if (int rc = ensure_rocfft(ctx)) return rc;
   }
 
   // window spans and the resampling tables
@@ -312,36 +260,14 @@ int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_
     span[2 * w] = (int32_t)(lo < hi ? lo : 0);
     span[2 * w + 1] = (int32_t)(lo < hi ? hi : 0);
   }
-  const int64_t nr = std::max<int64_t>(nres, 1);
-  std::vector<int32_t> rs_in(2 * (size_t)nr, -1);
-  std::vector<double> rs_c(4 * (size_t)nr, 0.0), rtw(2 * (size_t)nr, 0.0);
-  if (nres > 0) {
-    if (nmap < 1 || !map_out || !map_in || !map_w) return fail(ctx, PRISIM_EINVAL, "the resampled spectra need the selection map");
-    std::vector<int> used((size_t)nres, 0);
-    const int64_t half = m / 2;
-    for (int64_t e = 0; e < nmap; ++e) {
-      const int64_t k = map_out[e], kin = map_in[e];
-      if (k < 0 || k >= nres || kin < 0 || kin >= m) return fail(ctx, PRISIM_EINVAL, "selection map entry out of range");
-      if (used[(size_t)k] == 2) return fail(ctx, PRISIM_EINVAL, "selection map: more than two entries for one output bin");
-      const int s = used[(size_t)k]++;
-      if (kin >= nchan) continue;                    // a bin of the zero padding
-      const int64_t red = (kin * half) % m;          // e^{-2 pi i k_in floor(m/2) / m}
-      const double a = -2.0 * M_PI * (double)red / (double)m;
-      const double sc = map_w[e] * df;               // weight * (m df) * (1 / m): the ifft's 1 / nres times resample's nres / m
-      rs_in[(size_t)s * nr + k] = (int32_t)kin;
-      rs_c[2 * ((size_t)s * nr + k)] = sc * std::cos(a);
-      rs_c[2 * ((size_t)s * nr + k) + 1] = sc * std::sin(a);
-    }
-    for (int64_t q = 0; q < nres; ++q) {
-      const double a = 2.0 * M_PI * (double)q / (double)nres;
-      rtw[2 * q] = std::cos(a);
-      rtw[2 * q + 1] = std::sin(a);
-    }
-  }
+  std::vector<int32_t> rs_in;
+  std::vector<double> rs_c, rtw;
+  // weight * (m df) * (1 / m): the ifft's 1 / nres times resample's nres / m
+  if (int rc = build_resample_tables(ctx, nres, m, nchan, df, nmap, map_out, map_in, map_w, rs_in, rs_c, rtw)) return rc;
 
-  Dev dev;
+  Work wk;
   Events ev;
-  for (hipEvent_t& e : ev.e) HIPCHK(ctx, hipEventCreate(&e));
+  if (int rc = ev.create(ctx)) return rc;
   const size_t in_bytes = (size_t)ncubes * nrows * nchan * 16;
   const size_t bp_bytes = (size_t)nbp * nchan * 8, w_bytes = (size_t)nwin * nchan * 8;
   const int64_t nlines = (int64_t)ncubes * nrows * nwin;
@@ -351,43 +277,21 @@ int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_
   int32_t *d_span, *d_rsin;
   double2 *d_rsc, *d_rtw, *d_over = nullptr, *d_res = nullptr, *d_fbuf = nullptr;
   double *d_opow = nullptr, *d_rpow = nullptr;
-  if (cubes) SB_ALLOC(ctx, dev, d_in, in_bytes);
-  SB_ALLOC(ctx, dev, d_bp, bp_bytes);
-  SB_ALLOC(ctx, dev, d_wts, w_bytes);
-  SB_ALLOC(ctx, dev, d_ps, (size_t)nwin * 8);
-  SB_ALLOC(ctx, dev, d_span, span.size() * 4);
-  SB_ALLOC(ctx, dev, d_rsin, rs_in.size() * 4);
-  SB_ALLOC(ctx, dev, d_rsc, rs_c.size() * 8);
-  SB_ALLOC(ctx, dev, d_rtw, rtw.size() * 8);
-  if (w_over) SB_ALLOC(ctx, dev, d_over, over_n * 16);
-  if (w_opow) SB_ALLOC(ctx, dev, d_opow, over_n * 8);
-  if (w_res) SB_ALLOC(ctx, dev, d_res, res_n * 16);
-  if (w_rpow) SB_ALLOC(ctx, dev, d_rpow, res_n * 8);
-  if (!fused && want_over) SB_ALLOC(ctx, dev, d_fbuf, over_n * 16);
-  FftPlan plan;
-  if (!fused && want_over && nlines > 0) {
-    size_t len = (size_t)m;
-    RocfftApi& F = g_rocfft;
-    if (F.plan_create(&plan.p, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, rocfft_precision_double, 1, &len,
-                      (size_t)nlines, nullptr) != rocfft_status_success) {
-      plan.p = nullptr;
-      return fail(ctx, PRISIM_ELIB, "rocfft_plan_create failed");
-    }
-    if (F.execution_info_create(&plan.i) != rocfft_status_success) {
-      plan.i = nullptr;
-      return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_create failed");
-    }
-    if (F.execution_info_set_stream(plan.i, ctx->stream) != rocfft_status_success)
-      return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_stream failed");
-    size_t wbytes = 0;
-    F.plan_get_work_buffer_size(plan.p, &wbytes);
-    if (wbytes) {
-      void* wb;
-      SB_ALLOC(ctx, dev, wb, wbytes);
-      if (F.execution_info_set_work_buffer(plan.i, wb, wbytes) != rocfft_status_success)
-        return fail(ctx, PRISIM_ELIB, "rocfft_execution_info_set_work_buffer failed");
-    }
-  }
+  if (cubes) DEV_ALLOC(ctx, wk.dev, d_in, in_bytes);
+  DEV_ALLOC(ctx, wk.dev, d_bp, bp_bytes);
+  DEV_ALLOC(ctx, wk.dev, d_wts, w_bytes);
+  DEV_ALLOC(ctx, wk.dev, d_ps, (size_t)nwin * 8);
+  DEV_ALLOC(ctx, wk.dev, d_span, span.size() * 4);
+  DEV_ALLOC(ctx, wk.dev, d_rsin, rs_in.size() * 4);
+  DEV_ALLOC(ctx, wk.dev, d_rsc, rs_c.size() * 8);
+  DEV_ALLOC(ctx, wk.dev, d_rtw, rtw.size() * 8);
+  if (w_over) DEV_ALLOC(ctx, wk.dev, d_over, over_n * 16);
+  if (w_opow) DEV_ALLOC(ctx, wk.dev, d_opow, over_n * 8);
+  if (w_res) DEV_ALLOC(ctx, wk.dev, d_res, res_n * 16);
+  if (w_rpow) DEV_ALLOC(ctx, wk.dev, d_rpow, res_n * 8);
+  if (!fused && want_over) DEV_ALLOC(ctx, wk.dev, d_fbuf, over_n * 16);
+  if (!fused && want_over && nlines > 0)
+    if (int rc = wk.fft.create(ctx, wk.dev, (size_t)m, {{true, (size_t)nlines}}, &ctx->stream, 1)) return rc;
 
   HIPCHK(ctx, hipEventRecord(ev.e[0], ctx->stream));
   if (cubes && in_bytes) HIPCHK(ctx, hipMemcpyAsync(d_in, cubes, in_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -428,7 +332,7 @@ int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_
       }
       if (want_over) {
         void* b[1] = {d_fbuf};
-        if (g_rocfft.execute(plan.p, b, nullptr, plan.i) != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
+        if (g_rocfft.execute(wk.fft.at(true, (size_t)nlines), b, nullptr, wk.fft.info[0]) != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
         const int64_t blocks = std::min<int64_t>((int64_t)over_n / kThreads + 1, (int64_t)std::max(ctx->cu_count, 1) * 16);
         hipLaunchKernelGGL(k_sb_finish, dim3((unsigned)blocks), dim3(kThreads), 0, ctx->stream, P, nlines);
         HIPCHK(ctx, hipGetLastError());

@@ -90,6 +90,12 @@ def test_seeded_sweep_through_every_route():
         ((2,), 3, 100, 70, 0.0, 'all', False, 'auto', _abi.RUNS_BUDGET, 'dense'),
         ((1,), 2, 2048, 2, 1.0, 'all', False, 'auto', _abi.RUNS_BUDGET, 'chan'),        # m = PRISIM_SUBBAND_MAX_LEN, fused
         ((1,), 2, 2000, 2, 1.0, 'interp', False, 'auto', _abi.RUNS_BUDGET, 'chan'),     # m = 4000, rocFFT
+        ((2,), 2, 1, 3, 0.0, 'all', False, 'fused', _abi.RUNS_BUDGET, 'dense'),         # m = 1: no bit to reverse, no butterfly
+        ((2,), 2, 2, 3, 0.0, 'all', False, 'fused', _abi.RUNS_BUDGET, 'dense'),         # m = 2: one butterfly
+        ((2,), 2, 8, 65, 0.0, 'all', False, 'fused', _abi.RUNS_BUDGET, 'dense'),        # a full tile of 64 snapshots and one more
+        ((3,), 3, 12, 5, 0.0, 'all', False, 'auto', 2 * 2 * 3 * 12 * 5 * 16, 'dense'),  # m = 12, rocFFT: four chunks of 2 pairs, one of 1
+        ((2,), 2, 3, 4, 0.0, 'resample', False, 'auto', _abi.RUNS_BUDGET, 'dense'),     # resampled to 1 lag
+        ((2,), 2, 15, 4, 0.0, 'resample', False, 'auto', _abi.RUNS_BUDGET, 'dense'),    # resampled to 5 lags
     ]
     with _abi.Context(0) as ctx:
         routes = set()
@@ -116,6 +122,14 @@ def test_seeded_sweep_through_every_route():
         assert routes == {'fused', 'rocfft', 'direct'}
         with pytest.raises(ValueError, match='PRISIM_SUBBAND_MAX_LEN'):
             ctx.runs_transform(NP.ones((1, 1, 8, 1), complex), 1, 8, 1, m=_abi.PRISIM_SUBBAND_MAX_LEN + 1)
+
+
+def test_a_selection_map_with_three_entries_for_one_bin_is_refused(monkeypatch):
+    from prisim_amd import dsp_readings as D
+    monkeypatch.setattr(D, 'resample_map', lambda m, n: (NP.zeros(3, dtype=NP.int64), NP.arange(3, dtype=NP.int64), NP.ones(3)))
+    with _abi.Context(0) as ctx:
+        with pytest.raises(ValueError, match='more than two entries'):
+            ctx.runs_transform(NP.ones((1, 1, 8, 1), complex), 1, 8, 1, m=8, mode='resample', nout=5)
 
 
 def _config2_array(nt, noise=False):

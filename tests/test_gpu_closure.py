@@ -178,6 +178,30 @@ def test_filter_branches_against_the_checker(ctx, nchan, ftype, fmode, window):
             ctx.closure_phase(x, legs, conj, bp * wts, masks=masks, mask_index=idx, route='fused')
 
 
+@pytest.mark.parametrize('nchan,nt,route', [(1, 3, 'fused'), (2, 3, 'fused'), (8, 65, 'fused'), (12, 5, 'rocfft')])
+def test_filter_on_the_shortest_rows_and_one_snapshot_past_the_tile(ctx, nchan, nt, route):
+    """Rows of 1 and 2 channels (no bit to reverse, one butterfly), 65 snapshots of 8 channels (a full tile of 64 and one more), and 12
+    channels through rocFFT; three chunks of 3, 3 and 1 triads on two streams."""
+    rng = NP.random.default_rng(1000 + nchan)
+    nbl, ntriads, df = 5, 7, 1e5
+    x, bp, wts, legs, conj = _random_case(rng, nbl, nchan, nt, ntriads)
+    tau, dtau = NP.fft.fftfreq(nchan, df), 1.0 / (nchan * df)
+    fw = rng.uniform(0.3, 1.3, nchan)
+    want_t, _ = CK.closure_phase(x, legs, conj, bp, wts, freq_wts=fw, delay_filter=('regular', 'discard', 2 * dtau, 5 * dtau), df=df)
+    masks, idx = RI.closure_filter_masks(tau, 'regular', 'discard', 2 * dtau, 5 * dtau, None)
+    per_triad = nchan * nt * (3 * 16 + 8 + (3 * 16 if route == 'rocfft' else 0))
+    trip, ph, st = ctx.closure_phase(x, legs, conj, bp * wts, freq_wts=fw, masks=masks, mask_index=idx, route=route,
+                                     budget_bytes=2 * 3 * per_triad)
+    assert st['route'] == route and st['chunk_triads'] == 3 and st['chunks'] == 3 and st['streams'] == 2
+    if route == 'fused':
+        assert st['tile'] == min(nt, 64)
+    err = float(NP.max(NP.abs(trip - want_t) / NP.max(NP.abs(want_t), axis=2, keepdims=True)))
+    print(nchan, nt, route, 'triplet error %.3e of the row maximum' % err)
+    assert err <= 1e-12
+    own = NP.prod(trip, axis=1)
+    _check_phases(ph, NP.angle(own), own, 'short rows %s' % route)
+
+
 def test_entry_rejects_bad_input(ctx):
     rng = NP.random.default_rng(1)
     x, bp, wts, legs, conj = _random_case(rng, 4, 8, 2, 3)

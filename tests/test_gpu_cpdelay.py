@@ -67,7 +67,8 @@ def _windows(rng, nwin, nchan):
     return wts
 
 
-@pytest.mark.parametrize('nchan,m,nt,nrows', [(2048, 4096, 1, 3), (3000, 4096, 3, 2), (70, 128, 37, 5), (70, 100, 37, 5), (1, 1, 2, 2)])
+@pytest.mark.parametrize('nchan,m,nt,nrows', [(2048, 4096, 1, 3), (3000, 4096, 3, 2), (70, 128, 37, 5), (70, 100, 37, 5), (1, 1, 2, 2),
+                                                (2, 2, 3, 3), (5, 8, 65, 3), (7, 12, 5, 5)])
 def test_long_rows_odd_tiles_and_streaming(ctx, nchan, m, nt, nrows):
     """m = 4096 (98320 B of LDS, above the 64 KiB a kernel gets without asking), nt = 1, an nt that is no multiple of the tile, and
     budgets that force several chunks with a partial last one: every budget gives the one-chunk output, bit for bit."""

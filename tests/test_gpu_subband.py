@@ -99,6 +99,36 @@ def test_seeded_sweep_against_the_checker():
     assert routes == {'fused', 'rocfft'}
 
 
+@pytest.mark.parametrize('nchan,m,nt,route,nres', [(1, 1, 2, 'fused', 1), (2, 2, 2, 'fused', 1), (5, 8, 3, 'fused', 5), (7, 12, 3, 'rocfft', 5),
+                                                   (7, 12, 3, 'rocfft', 1)])
+def test_shortest_rows_and_shortest_resampled_spectra(nchan, m, nt, route, nres):
+    """m = 1 and 2 (no bit to reverse, one butterfly), m = 8, and m = 12 through rocFFT; resampled to 1 and to 5 lags."""
+    rng = NP.random.default_rng(100 * m + nres)
+    nbl, nwin, df = 3, 2, 97.65625e3
+    fw = rng.uniform(0.2, 1.5, (nwin, nchan))
+    x = rng.normal(size=(2, nbl, nchan, nt)) + 1j * rng.normal(size=(2, nbl, nchan, nt))
+    bp = 0.5 + rng.uniform(size=(nbl, nchan, 1))
+    ps = rng.uniform(1.0, 2.0, nwin)
+    xin = NP.stack([NP.transpose(c, (2, 0, 1)) for c in x])
+    with _abi.Context(0) as ctx:
+        out = ctx.subband_transform(xin, bp[:, :, 0], fw, m, df, nres=nres, pscale=ps, want=('over', 'over_power', 'res', 'res_power'),
+                                    route=route)
+    assert out['stats']['route'] == route and out['res'].shape[-1] == nres
+    for c in range(2):
+        want = CK.transform(x[c], bp, fw, m - nchan, df)
+        assert CK.rel_err(_to_ref(out['over'])[c], want) <= 1e-12
+        assert CK.rel_err(_to_ref(out['res'])[c], D.resample(want, nres, axis=2), scale_of=want) <= 1e-12
+        assert CK.rel_err(_to_ref(out['over_power'])[c], NP.abs(want) ** 2 * ps.reshape(1, -1, 1, 1)) <= 1e-12
+        assert NP.allclose(_to_ref(out['res_power'])[c], NP.abs(_to_ref(out['res'])[c]) ** 2 * ps.reshape(1, -1, 1, 1), rtol=1e-13, atol=0)
+
+
+def test_a_selection_map_with_three_entries_for_one_bin_is_refused(monkeypatch):
+    monkeypatch.setattr(D, 'resample_map', lambda m, n: (NP.zeros(3, dtype=NP.int64), NP.arange(3, dtype=NP.int64), NP.ones(3)))
+    with _abi.Context(0) as ctx:
+        with pytest.raises(ValueError, match='more than two entries'):
+            ctx.subband_transform(NP.ones((1, 1, 1, 8), dtype=complex), NP.ones((1, 8)), NP.ones((1, 8)), 8, 1.0, nres=5, want=('res',))
+
+
 def test_length_limit_is_a_clear_error():
     with _abi.Context(0) as ctx:
         x = NP.ones((1, 1, 1, 8), dtype=complex)
