@@ -84,6 +84,12 @@ PRISIM_CPBINS_ALL = 127
 CPDIFF_EXPORTS = ('prisim_cphase_diff',)
 CPDIFF_OUTPUTS = ('diff0_mean', 'diff0_median', 'diff1_mean', 'diff1_median', 'wts0', 'wts1', 'mask0', 'mask1')
 PRISIM_CPDIFF_OUT_BYTES = 82
+# every symbol include/prisim_cpft.h declares: delay spectra of binned closure phasors (prisim_amd/csrc_closure/cpft.hip)
+CPFT_EXPORTS = ('prisim_cphase_ft',)
+PRISIM_CPFT_MAX_LEN, PRISIM_CPFT_MAX_IN = PRISIM_SUBBAND_MAX_LEN, 8
+PRISIM_CPFT_OVER, PRISIM_CPFT_RES, PRISIM_CPFT_LAG = 1, 2, 4
+PRISIM_CPFT_AUTO, PRISIM_CPFT_FUSED, PRISIM_CPFT_ROCFFT = -1, 0, 1
+CPFT_ROUTES = {PRISIM_CPFT_FUSED: 'fused', PRISIM_CPFT_ROCFFT: 'rocfft'}
 
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
@@ -244,6 +250,12 @@ class PrisimCpdiffStats(C.Structure):
                 ('resident_in', C.c_int32), ('ncomb', C.c_int32)]
 
 
+class PrisimCpftStats(C.Structure):
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('rows', C.c_int64), ('chunks', C.c_int64), ('chunk_rows', C.c_int64),
+                ('row_bytes', C.c_int64), ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64),
+                ('route', C.c_int32), ('streams', C.c_int32), ('group_rows', C.c_int32), ('lds_bytes', C.c_int32)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -368,6 +380,9 @@ def load_library():
     lib.prisim_cphase_diff.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
                                        C.POINTER(PrisimCpdiffStats)]
     lib.prisim_cphase_diff.restype = C.c_int
+    lib.prisim_cphase_ft.argtypes = [vp, i64, i64, i64, i64, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, i64, dbl, i64, i64, vp, vp, vp, C.c_int32,
+                                     C.c_int32, i64, vp, vp, vp, vp, C.POINTER(PrisimCpftStats)]
+    lib.prisim_cphase_ft.restype = C.c_int
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
                                              C.POINTER(vp), pst]
@@ -1323,6 +1338,89 @@ class Context(object):
         out['stats'] = {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements), 'chunks': int(st.chunks),
                         'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes), 'upload_bytes': int(st.upload_bytes),
                         'download_bytes': int(st.download_bytes), 'resident': bool(st.resident_in), 'ncomb': int(st.ncomb)}
+        return out
+
+    # ---- delay spectra of binned closure phasors (include/prisim_cpft.h) ----
+    def cphase_ft(self, inputs, wts, m, df, weights=None, vscale=None, nres=None, want=('over', 'res', 'lag_kernel'), route='auto',
+                  budget_bytes=0, shape=None):
+        """Delay spectra of stacks of complex numbers (n0, n1, n2, nchan) on the device (prisim_cphase_ft).  inputs: up to 8 complex
+        arrays, each (b0, b1, b2, nchan) with every b the full extent or 1 (read with stride 0 on the device, never materialised);
+        the full shape is that of weights, else `shape` (n0, n1, n2), else the broadcast of the inputs' shapes.  wts (nwin, nchan)
+        frequency windows, m lags, df; weights (n0, n1, n2, nchan) float64 flag weights shared by all inputs, divided by their mean
+        over the channels on the device (None: no weights); vscale (nwin, n0) (None: 1); nres resampled lags.  want: any of 'over',
+        'res' and 'lag_kernel'.  Returns a dict of 'over' and 'res' (lists, one (nwin, n0, n1, n2, m | nres) array per input),
+        'lag_kernel' and 'lag_kernel_res' ((nwin, n0, n1, n2, m | nres) with weights, (nwin, 1, 1, 1, m | nres) without) -- None
+        where not wanted -- and 'stats'."""
+        fw = NP.ascontiguousarray(wts, dtype=NP.float64)
+        fw = fw.reshape(-1, fw.shape[-1])
+        nwin, nchan = fw.shape
+        xs = [NP.asarray(x) for x in inputs]
+        if len(xs) > PRISIM_CPFT_MAX_IN:
+            raise ValueError('need 0 <= nin <= {0} input stacks'.format(PRISIM_CPFT_MAX_IN))
+        for x in xs:
+            if x.ndim != 4 or x.shape[-1] != nchan:
+                raise ValueError('every input must be (b0, b1, b2, nchan) with the channel count of wts')
+        w = None
+        if weights is not None:
+            w = NP.ascontiguousarray(weights, dtype=NP.float64)
+            if w.ndim != 4 or w.shape[-1] != nchan:
+                raise ValueError('weights must be (n0, n1, n2, nchan) with the channel count of wts')
+            lead = w.shape[:3]
+        elif shape is not None:
+            lead = tuple(int(n) for n in shape)
+        elif xs:
+            lead = NP.broadcast_shapes(*[x.shape[:3] for x in xs])
+        else:
+            lead = (1, 1, 1)
+        for i, x in enumerate(xs):
+            for a in range(3):
+                if x.shape[a] not in (lead[a], 1):
+                    raise ValueError('input {0}: axis {1} has {2} entries, neither the full extent nor 1'.format(i, a, x.shape[a]))
+        xs = [NP.ascontiguousarray(x, dtype=NP.complex128) for x in xs]
+        vs = None
+        if vscale is not None:
+            vs = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(vscale, dtype=NP.float64), (nwin, lead[0])))
+        m = int(m)
+        bits = {'over': PRISIM_CPFT_OVER, 'res': PRISIM_CPFT_RES, 'lag_kernel': PRISIM_CPFT_LAG}
+        flag = 0
+        for name in want:
+            flag |= bits[name]
+        nres = 0 if nres is None else int(nres)
+        if flag & PRISIM_CPFT_RES and nres < 1:
+            raise ValueError('the resampled spectra need nres >= 1')
+        mo = mi = mw = None
+        if flag & PRISIM_CPFT_RES and nres <= PRISIM_CPFT_MAX_LEN and 1 <= m <= PRISIM_CPFT_MAX_LEN:
+            mo, mi, mw = (NP.ascontiguousarray(a) for a in dsp_readings.resample_map(m, nres))      # the one reading of the resampling
+        nin = len(xs)
+        out = {'over': None, 'res': None, 'lag_kernel': None, 'lag_kernel_res': None}
+        if flag & PRISIM_CPFT_OVER:
+            out['over'] = [NP.empty((nwin,) + tuple(lead) + (m,), dtype=NP.complex128) for _ in xs]
+        if flag & PRISIM_CPFT_RES:
+            out['res'] = [NP.empty((nwin,) + tuple(lead) + (nres,), dtype=NP.complex128) for _ in xs]
+        if flag & PRISIM_CPFT_LAG:
+            klead = tuple(lead) if w is not None else (1, 1, 1)
+            out['lag_kernel'] = NP.empty((nwin,) + klead + (m,), dtype=NP.complex128)
+            if flag & PRISIM_CPFT_RES:
+                out['lag_kernel_res'] = NP.empty((nwin,) + klead + (nres,), dtype=NP.complex128)
+
+        def pointers(arrays):
+            if not arrays:
+                return None
+            return (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+        shapes = NP.ascontiguousarray([x.shape[:3] for x in xs], dtype=NP.int64).reshape(-1, 3)
+        st = PrisimCpftStats()
+        r = {'auto': PRISIM_CPFT_AUTO, 'fused': PRISIM_CPFT_FUSED, 'rocfft': PRISIM_CPFT_ROCFFT}[route]
+        self._check(self._lib.prisim_cphase_ft(
+            self._h, int(lead[0]), int(lead[1]), int(lead[2]), nchan, nin, pointers(xs), _ptr(shapes) if nin else None, _ptr(w), nwin,
+            _ptr(fw), _ptr(vs), m, float(df), nres, 0 if mo is None else mo.size, _ptr(mo), _ptr(mi), _ptr(mw), flag, r, int(budget_bytes),
+            pointers(out['over']), pointers(out['res']), _ptr(out['lag_kernel']), _ptr(out['lag_kernel_res']), C.byref(st)),
+            'prisim_cphase_ft')
+        out['stats'] = {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows), 'chunks': int(st.chunks),
+                        'chunk_rows': int(st.chunk_rows), 'row_bytes': int(st.row_bytes), 'kernel_bytes': int(st.kernel_bytes),
+                        'upload_bytes': int(st.upload_bytes), 'download_bytes': int(st.download_bytes),
+                        'route': CPFT_ROUTES.get(st.route, st.route), 'streams': int(st.streams), 'group_rows': int(st.group_rows),
+                        'lds_bytes': int(st.lds_bytes)}
         return out
 
     # ---- instrument gain tables (include/prisim_gains.h) ----

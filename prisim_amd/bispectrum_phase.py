@@ -1,7 +1,8 @@
 """Closure (bispectrum) phases of observed data: prisim/bispectrum_phase.py's loadnpz and the first steps of its ClosurePhase class,
 with the day and LST binning of smooth_in_tbins and of subsample_differencing on the GPU (include/prisim_cpbins.h,
 prisim_amd/csrc_closure/cpbins.hip) and the differences of the day sub-samples there too (include/prisim_cpdiff.h,
-prisim_amd/csrc_closure/cpdiff.hip).
+prisim_amd/csrc_closure/cpdiff.hip); and ClosurePhaseDelaySpectrum with its FT, the delay spectra of the binned phasors, of the
+residuals, of the sub-model and of the half differences on the GPU (include/prisim_cpft.h, prisim_amd/csrc_closure/cpft.hip).
 
 Readings and departures
 - astropy is not a dependency.  The reference uses astropy.time.Time only to carry Julian dates, so loadnpz does that arithmetic
@@ -33,13 +34,40 @@ Readings and departures
 - subtract is host numpy, like expicp: it is elementwise on arrays the host already holds.  Under the masks of 'residual' (the mask of
   prelim or of the model; NaN in the model is masked) the data are 0.
 - infmt='hdf5' and save() are not implemented.
+
+Readings and departures of ClosurePhaseDelaySpectrum.FT (:2573-2784).  Every error is raised before any device work.
+- visscaleinfo=None ends the reference in an AttributeError (visscale = 1.0 is a float and :2732 calls .filled); here the scale is 1.
+- freq_center=None is read as f[f.size // 2] (the reference's / is Python 2).
+- pad < 0 becomes 0 silently (the reference raises a NameError on `verbose`).
+- method='nufft' raises NotImplementedError (the reference falls through to an UnboundLocalError).
+- datapool: only 'prelim' is accepted, as in the reference.
+- Missing inputs raise a ValueError that names the step to run (the reference raises a KeyError at :2713): smooth_in_tbins where
+  cpinfo['processed']['prelim'] lacks 'eicp' or 'wts', subsample_differencing where cpinfo['errinfo'] lacks 'wts' or 'eicp_diff'.
+- The reference transforms the .data under masks (:2727, :2741, :2749), whose content it leaves unspecified.  Here the data under a
+  mask are what this module documents above: 1 + 0i for prelim 'eicp', 0 for the residual, the sub-model and 'eicp_diff'.  They matter
+  only with apply_flags=False: a weight of 0 zeroes the term whatever the data hold.
+- A row (LST bin, day bin, triad) whose weights average to 0 is NaN in the reference (0 / 0, :2725, :2738); here its spectra and its
+  lag kernel are 0.
+- Kept quirks: the residual and the sub-model use the prelim weights; 'lag_kernel' uses the weights of the last pool processed
+  (prelim's) and has the shape (nspw, 1, 1, 1, nlags) with apply_flags=False; 'residual' always carries 'twts'; 'submodel' is {}
+  unless subtract ran; 'freq_center' and 'bw_eff' are returned as given while the rows of 'freq_wts' are in channel order.
+- The frequency windows are those of delay_spectrum.subband_freq_wts (the statements of :2688-2709 in the readings of
+  dsp_readings.py; fftpow other than 1 has no reading there).
+- visscaleinfo: 'vis' as a numpy or masked array (3, nlst_vis, nchan) with 'lst' and nlst_vis == 1 (:2669-2670, :2716-2717, on the
+  host: the scale is one number per window and LST bin).  Several reference LSTs need OPS.interpolate_masked_array_1D and an
+  InterferometerArray under 'vis' needs its baseline search; both raise NotImplementedError.
+- subset, compute_power_spectrum and what follows it are not implemented; the spectra are copied to the host and do not stay on the
+  device.
 """
 import warnings
+
+import copy
 
 import numpy as NP
 import numpy.ma as MA
 
 from . import _abi
+from . import dsp_readings as DSP
 
 
 def loadnpz(npzfile, longitude=0.0, latitude=0.0, lst_format='fracday'):
@@ -408,3 +436,200 @@ class ClosurePhase(object):
         err['wts'] = {str(g): MA.array(res['wts%d' % g], mask=res['mask%d' % g]) for g in range(2)}
         err['eicp_diff'] = {str(g): {stat: MA.array(res['diff%d_%s' % (g, stat)], mask=res['mask%d' % g]) for stat in ('mean', 'median')}
                             for g in range(2)}
+
+
+def _vis_scale(visscaleinfo, freq_wts, nlst):
+    """visscale (nspw, nlst) of :2631-2672 and :2716-2717 for one reference LST, or None"""
+    if visscaleinfo is None:
+        return None
+    if not isinstance(visscaleinfo, dict):
+        raise TypeError('Input visscaleinfo must be a dictionary')
+    if 'vis' not in visscaleinfo:
+        raise KeyError('Input visscaleinfo does not contain key "vis"')
+    vis = visscaleinfo['vis']
+    if not isinstance(vis, NP.ndarray):
+        if hasattr(vis, 'skyvis_freq'):
+            raise NotImplementedError('an InterferometerArray under visscaleinfo["vis"] is not supported: pass the (3, nlst_vis, nchan) array')
+        raise TypeError('Input visibilities must be a numpy or a masked array')
+    if 'lst' not in visscaleinfo:
+        raise KeyError('Input visscaleinfo does not contain key "lst"')
+    lst_vis = NP.asarray(visscaleinfo['lst']) * 15.0
+    if vis.ndim != 3 or vis.shape[0] != 3 or vis.shape[2] != freq_wts.shape[1]:
+        raise ValueError('Input visibilities must have the shape (3, nlst_vis, nchan)')
+    if lst_vis.size != 1 or vis.shape[1] != 1:
+        raise NotImplementedError('several reference LSTs in visscaleinfo need OPS.interpolate_masked_array_1D, which is not available')
+    if not isinstance(vis, MA.MaskedArray):
+        vis = MA.array(vis, mask=NP.isnan(vis))
+    vis_ref = MA.copy(vis) * NP.ones(nlst).reshape(1, -1, 1)                                    # (3, nlst, nchan)
+    fw = freq_wts[:, NP.newaxis, NP.newaxis, NP.newaxis, :]
+    visscale = NP.nansum(NP.transpose(vis_ref[NP.newaxis, NP.newaxis, :, :, :], axes=(0, 3, 1, 2, 4)) * fw, axis=-1, keepdims=True) \
+        / NP.nansum(fw, axis=-1, keepdims=True)                                                # nspw x nlst x 1 x 3 x 1
+    visscale = NP.sqrt(1.0 / NP.nansum(1 / NP.abs(visscale) ** 2, axis=-2, keepdims=True))
+    return NP.ascontiguousarray(MA.filled(visscale, NP.nan).reshape(freq_wts.shape[0], nlst), dtype=NP.float64)
+
+
+class ClosurePhaseDelaySpectrum(object):
+    """Delay spectra of the binned closure phasors of a ClosurePhase.
+
+    Attributes: cPhase, f (Hz), df, cPhaseDS (the oversampled result of the last FT), cPhaseDS_resampled (its resampled result, set
+    with resample=True).  ft_stats: the device statistics of the calls of the last FT, by weight set."""
+
+    def __init__(self, cPhase):
+        if not isinstance(cPhase, ClosurePhase):
+            raise TypeError('Input cPhase must be an instance of class ClosurePhase')
+        self.cPhase = cPhase
+        self.f = self.cPhase.f
+        self.df = self.cPhase.df
+        self.cPhaseDS = None
+        self.cPhaseDS_resampled = None
+        self.ft_stats = {}
+
+    def FT(self, bw_eff, freq_center=None, shape=None, fftpow=None, pad=None, datapool='prelim', visscaleinfo=None, method='fft',
+           resample=True, apply_flags=True):
+        """Delay transform of the binned phasors (cpinfo['processed']['prelim']), of the residuals and the sub-model where subtract
+        ran, and of the half differences of subsample_differencing (cpinfo['errinfo']), in the frequency windows (bw_eff, freq_center,
+        shape, fftpow), zero-padded by pad * nchan channels, under the flag weights divided by their mean over the channels
+        (apply_flags) and scaled to visibilities (visscaleinfo), on the device.  Returns the reference's dictionary: 'freq_center',
+        'shape', 'freq_wts', 'bw_eff', 'fftpow', 'npad', 'lags', 'lag_corr_length', 'lag_kernel', 'whole' / 'residual' -> 'dspec' ->
+        'twts', 'mean', 'median', 'submodel' -> 'dspec', 'errinfo' -> 'dspec0' / 'dspec1' -> 'twts', 'mean', 'median'; spectra are
+        (nspw, nlst, ndays, ntriads, nlags).  With resample the spectra are FFT-resampled to round(nlags / min((nchan + npad) df /
+        bw_eff)) lags and 'lags' and 'lag_kernel' interpolated; the oversampled result stays in cPhaseDS.  See the module docstring for
+        the departures."""
+        from .delay_spectrum import subband_freq_wts
+        if not isinstance(bw_eff, (int, float, list, NP.ndarray)):
+            raise TypeError('Value of effective bandwidth must be a scalar, list or numpy array')
+        bw_eff = NP.asarray(bw_eff).reshape(-1)
+        if NP.any(bw_eff <= 0.0):
+            raise ValueError('All values in effective bandwidth must be strictly positive')
+        if freq_center is None:
+            freq_center = NP.asarray(self.f[self.f.size // 2]).reshape(-1)
+        elif isinstance(freq_center, (int, float, list, NP.ndarray)):
+            freq_center = NP.asarray(freq_center).reshape(-1)
+            if NP.any((freq_center <= self.f.min()) | (freq_center >= self.f.max())):
+                raise ValueError('Value(s) of frequency center(s) must lie strictly inside the observing band')
+        else:
+            raise TypeError('Values(s) of frequency center must be scalar, list or numpy array')
+        if (bw_eff.size == 1) and (freq_center.size > 1):
+            bw_eff = NP.repeat(bw_eff, freq_center.size)
+        elif (bw_eff.size > 1) and (freq_center.size == 1):
+            freq_center = NP.repeat(freq_center, bw_eff.size)
+        elif bw_eff.size != freq_center.size:
+            raise ValueError('Effective bandwidth(s) and frequency center(s) must have same number of elements')
+        if shape is not None:
+            if not isinstance(shape, str):
+                raise TypeError('Window shape must be a string')
+            if shape not in ['rect', 'bhw', 'bnw', 'RECT', 'BHW', 'BNW']:
+                raise ValueError('Invalid value for window shape specified.')
+        else:
+            shape = 'rect'
+        if fftpow is None:
+            fftpow = 1.0
+        else:
+            if not isinstance(fftpow, (int, float)):
+                raise TypeError('Power to raise window FFT by must be a scalar value.')
+            if fftpow < 0.0:
+                raise ValueError('Power for raising FFT of window by must be positive.')
+        if pad is None:
+            pad = 1.0
+        else:
+            if not isinstance(pad, (int, float)):
+                raise TypeError('pad fraction must be a scalar value.')
+            if pad < 0.0:
+                pad = 0.0
+        if not isinstance(datapool, str):
+            raise TypeError('Input datapool must be a string')
+        if datapool.lower() not in ['prelim']:
+            raise ValueError('Specified datapool not supported')
+        if not isinstance(method, str):
+            raise TypeError('Input method must be a string')
+        if method.lower() not in ['fft', 'nufft']:
+            raise ValueError('Specified FFT method not supported')
+        if method.lower() == 'nufft':
+            raise NotImplementedError('method="nufft" is not implemented')
+        if not isinstance(apply_flags, bool):
+            raise TypeError('Input apply_flags must be boolean')
+        cpinfo = self.cPhase.cpinfo
+        proc = cpinfo.get('processed', {})
+        prelim = proc.get('prelim', {})
+        if 'eicp' not in prelim or 'wts' not in prelim:
+            raise ValueError('smooth_in_tbins must fill the binned closure phases before they can be transformed')
+        err = cpinfo.get('errinfo', {})
+        if 'wts' not in err or 'eicp_diff' not in err:
+            raise ValueError('subsample_differencing must fill the sub-sample differences before they can be transformed')
+        nchan = self.f.size
+        freq_wts = subband_freq_wts(self.f, self.df, bw_eff, freq_center, shape, fftpow)        # nspw x nchan
+        nlst = NP.asarray(prelim['lstbins']).size
+        vscale = _vis_scale(visscaleinfo, freq_wts, nlst)
+        npad = int(nchan * pad)
+        m = nchan + npad
+        if m > _abi.PRISIM_CPFT_MAX_LEN:
+            raise ValueError('nchan + npad = {0} exceeds the {1} lags of the device transform'.format(m, _abi.PRISIM_CPFT_MAX_LEN))
+        lags = DSP.spectral_axis(m, delx=self.df, use_real=False, shift=True)
+        downsample_factor = NP.min(m * self.df / bw_eff)
+        nres = DSP.fft_downsample_length(m, downsample_factor) if resample else None
+        if resample and not 1 <= nres <= _abi.PRISIM_CPFT_MAX_LEN:
+            raise ValueError('the resampled spectra would have {0} lags'.format(nres))
+
+        def data(x, fill):
+            """the data of a masked array with `fill` under its mask, at its stored shape with leading axes of length 1 added"""
+            x = MA.array(x)
+            d = NP.where(MA.getmaskarray(x), fill, MA.getdata(x)).astype(NP.complex128)
+            return d.reshape((1,) * (4 - d.ndim) + d.shape)
+
+        # one call per weight set: (weights, names, input stacks)
+        names = [('whole', key) for key in prelim['eicp']]
+        stacks = [data(prelim['eicp'][key], 1.0) for key in prelim['eicp']]
+        if 'submodel' in proc:
+            names.append(('submodel', None))
+            stacks.append(data(proc['submodel']['eicp'], 0.0))
+        if 'residual' in proc:
+            names += [('residual', key) for key in proc['residual']['eicp']]
+            stacks += [data(proc['residual']['eicp'][key], 0.0) for key in proc['residual']['eicp']]
+        calls = [('prelim', MA.getdata(prelim['wts']), names, stacks)]
+        for g in ('0', '1'):
+            calls.append(('errinfo' + g, MA.getdata(err['wts'][g]), [('errinfo', 'dspec' + g, stat) for stat in err['eicp_diff'][g]],
+                          [data(err['eicp_diff'][g][stat], 0.0) for stat in err['eicp_diff'][g]]))
+        for label, wts, _, stk in calls:
+            for x in stk:
+                if x.ndim != 4 or x.shape[-1] != nchan or any(b not in (n, 1) for b, n in zip(x.shape[:3], wts.shape[:3])):
+                    raise ValueError('a stack of {0} does not broadcast against its weights'.format(label))
+            if vscale is not None and wts.shape[0] != nlst:
+                raise ValueError('the weights of {0} do not have the LST bins of prelim'.format(label))
+
+        result = {'freq_center': freq_center, 'shape': shape, 'freq_wts': freq_wts, 'bw_eff': bw_eff, 'fftpow': fftpow, 'npad': npad,
+                  'lags': lags, 'lag_corr_length': nchan / NP.sum(freq_wts, axis=-1),
+                  'whole': {'dspec': {'twts': prelim['wts']}}, 'residual': {'dspec': {'twts': prelim['wts']}},
+                  'errinfo': {'dspec0': {'twts': err['wts']['0']}, 'dspec1': {'twts': err['wts']['1']}}, 'submodel': {}}
+        resampled = None
+        if resample:
+            resampled = copy.deepcopy(result)
+
+        def put(res, name, value):
+            if name[0] == 'errinfo':
+                res['errinfo'][name[1]][name[2]] = value
+            elif name[0] == 'submodel':
+                res['submodel']['dspec'] = value
+            else:
+                res[name[0]]['dspec'][name[1]] = value
+
+        ctx = self.cPhase._context()
+        self.ft_stats = {}
+        want = ('over', 'res') if resample else ('over',)
+        for label, wts, names, stk in calls:
+            lagk = label == 'prelim'
+            out = ctx.cphase_ft(stk, freq_wts, m, self.df, weights=wts if apply_flags else None, vscale=vscale, nres=nres,
+                                want=want + (('lag_kernel',) if lagk else ()), shape=wts.shape[:3])
+            self.ft_stats[label] = out['stats']
+            for i, name in enumerate(names):
+                put(result, name, out['over'][i])
+                if resample:
+                    put(resampled, name, out['res'][i])
+            if lagk:
+                result['lag_kernel'] = out['lag_kernel']
+        self.cPhaseDS = result
+        if not resample:
+            return result
+        resampled['lags'] = DSP.downsampler(result['lags'], downsample_factor, axis=-1, method='interp', kind='linear')
+        resampled['lag_kernel'] = DSP.downsampler(result['lag_kernel'], downsample_factor, axis=-1, method='interp', kind='linear')
+        self.cPhaseDS_resampled = resampled
+        return resampled
