@@ -271,6 +271,43 @@ class PrisimGainsStats(C.Structure):
     _fields_ = [('device_ms', C.c_double), ('kernel_ms', C.c_double), ('elements', C.c_int64)]
 
 
+def _stats_dict(st, rename=None, **maps):
+    """A stats struct as a dict of its fields without reserved_, each value as ctypes hands it over: a Python int for the integer
+    fields, a float for the doubles (tests/test_abi_helpers.py pins the type per key).  maps: per field, a table of names (a value it
+    lacks stays as it is) or a function of the value; rename: the keys that differ from the field names ('resident_in')."""
+    out = {}
+    for name, _ in st._fields_:
+        if name == 'reserved_':
+            continue
+        v, f = getattr(st, name), maps.get(name)
+        if f is not None:
+            v = f.get(v, v) if isinstance(f, dict) else f(v)
+        out[(rename or {}).get(name, name)] = v
+    return out
+
+
+def _resample_map(wanted, m, nout):
+    """(nmap, map_out, map_in, map_w) of dsp_readings.resample_map(m, nout), the one reading of the resampling, as the library takes
+    them; (0, None, None, None) when not wanted (no resampled output, or lengths that the library is left to refuse)."""
+    if not wanted:
+        return 0, None, None, None
+    mo, mi, mw = (NP.ascontiguousarray(a) for a in dsp_readings.resample_map(m, nout))
+    return mo.size, mo, mi, mw
+
+
+def _want_bits(want, bits):
+    """The OR of bits[name] over the names of want; KeyError on an unknown name."""
+    flag = 0
+    for name in want:
+        flag |= bits[name]
+    return flag
+
+
+def _route_code(name, routes):
+    """The library's code of a route: 'auto' (-1 in every header) or a name of the table routes (code: name); KeyError on another."""
+    return -1 if name == 'auto' else {v: k for k, v in routes.items()}[name]
+
+
 class PrisimHipError(RuntimeError):
     """Raised when libprisim_hip.so is missing/unloadable or no GPU is usable."""
 
@@ -877,11 +914,6 @@ class Context(object):
 
     # ---- delay CLEAN (include/prisim_clean.h) ----
     @staticmethod
-    def _clean_stats(st):
-        return {'device_ms': st.device_ms, 'clean_ms': st.clean_ms, 'sum_iter': int(st.sum_iter), 'rows': int(st.rows),
-                'waves_per_block': int(st.waves_per_block), 'kernel_in_lds': bool(st.kernel_in_lds), 'lds_bytes': int(st.lds_bytes)}
-
-    @staticmethod
     def _clean_kernels(kern, kidx, nrows, n):
         k = NP.ascontiguousarray(kern, dtype=NP.complex128).reshape(-1, n)
         if kidx is None:
@@ -907,7 +939,7 @@ class Context(object):
         self._check(self._lib.prisim_clean_rows(self._h, nrows, m, _ptr(x), k.shape[0], _ptr(k), _ptr(ix), _ptr(box), float(gain),
                                                 int(maxiter), float(threshold), int(bool(absolute)), _ptr(cc), _ptr(res), _ptr(iters),
                                                 _ptr(flags), _ptr(rms), C.byref(st)), 'prisim_clean_rows')
-        return cc, res, iters, flags, rms, self._clean_stats(st)
+        return cc, res, iters, flags, rms, _stats_dict(st, kernel_in_lds=bool)
 
     def clean_delay(self, win, kwin, cbox, m, lag_scale, freq_scale1, freq_scale2, gain, maxiter, threshold, absolute=False, kidx=None):
         """The delayClean chain (prisim_clean_delay) for win (ncubes, nrows, nchan) windowed rows zero-padded to m lags, kernels
@@ -928,7 +960,7 @@ class Context(object):
                                                  float(threshold), int(bool(absolute)), _ptr(out['lag']), _ptr(out['kern_lag']),
                                                  _ptr(out['cc']), _ptr(out['res']), _ptr(out['cc_freq']), _ptr(out['res_freq']),
                                                  _ptr(out['iters']), _ptr(out['flags']), _ptr(out['rms']), C.byref(st)), 'prisim_clean_delay')
-        out['stats'] = self._clean_stats(st)
+        out['stats'] = _stats_dict(st, kernel_in_lds=bool)
         return out
 
     # ---- sub-band delay spectra (include/prisim_subband.h) ----
@@ -951,27 +983,23 @@ class Context(object):
             if x.shape[3] != nchan:
                 raise ValueError('cubes and wts must have the same channel count')
         b = NP.ascontiguousarray(bp, dtype=NP.float64).reshape(-1, nchan)
-        bits = {'over': PRISIM_SUBBAND_OVER, 'over_power': PRISIM_SUBBAND_OVER_POWER, 'res': PRISIM_SUBBAND_RES,
-                'res_power': PRISIM_SUBBAND_RES_POWER}
-        flag = 0
-        for name in want:
-            flag |= bits[name]
+        flag = _want_bits(want, {'over': PRISIM_SUBBAND_OVER, 'over_power': PRISIM_SUBBAND_OVER_POWER, 'res': PRISIM_SUBBAND_RES,
+                                 'res_power': PRISIM_SUBBAND_RES_POWER})
         ps = None if pscale is None else NP.ascontiguousarray(NP.broadcast_to(NP.asarray(pscale, dtype=NP.float64).ravel(), (nwin,)))
         out = {}
         for name in want:
             n = m if name.startswith('over') else max(int(nres), 1)
             out[name] = NP.empty((ncubes, nt, nbl, nwin, n), dtype=NP.complex128 if name in ('over', 'res') else NP.float64)
-        mo = mi = mw = None
-        if flag & (PRISIM_SUBBAND_RES | PRISIM_SUBBAND_RES_POWER) and 1 <= int(nres) <= PRISIM_SUBBAND_MAX_LEN:
-            mo, mi, mw = (NP.ascontiguousarray(a) for a in dsp_readings.resample_map(m, nres))    # the one reading of the resampling
+        nmap, mo, mi, mw = _resample_map(flag & (PRISIM_SUBBAND_RES | PRISIM_SUBBAND_RES_POWER) and 1 <= int(nres) <= PRISIM_SUBBAND_MAX_LEN,
+                                         m, nres)
         st = PrisimSubbandStats()
-        r = {'auto': PRISIM_SUBBAND_AUTO, 'fused': PRISIM_SUBBAND_FUSED, 'rocfft': PRISIM_SUBBAND_ROCFFT}[route]
+        r = _route_code(route, SUBBAND_ROUTES)
         self._check(self._lib.prisim_subband_transform(self._h, ncubes, int(nt), int(nbl), nchan, _ptr(x), int(t0), _ptr(b), b.shape[0],
-                                                       nwin, _ptr(w), int(m), float(df), int(nres), 0 if mo is None else mo.size,
+                                                       nwin, _ptr(w), int(m), float(df), int(nres), nmap,
                                                        _ptr(mo), _ptr(mi), _ptr(mw), _ptr(ps), flag, r,
                                                        _ptr(out.get('over')), _ptr(out.get('over_power')), _ptr(out.get('res')),
                                                        _ptr(out.get('res_power')), C.byref(st)), 'prisim_subband_transform')
-        out['stats'] = self._subband_stats(st)
+        out['stats'] = _stats_dict(st, route=SUBBAND_ROUTES)
         return out
 
     def subband_power_resident(self, t0, nt, bp, wts, m, df, pscale, nres=0, route='auto'):
@@ -981,11 +1009,6 @@ class Context(object):
         want = ('over_power', 'res_power') if nres > 0 else ('over_power',)
         out = self.subband_transform(None, bp, wts, m, df, nres=nres, pscale=pscale, want=want, route=route, t0=t0, nt=nt)
         return out['over_power'][0], (out['res_power'][0] if nres > 0 else None), out['stats']
-
-    @staticmethod
-    def _subband_stats(st):
-        return {'device_ms': st.device_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows), 'route': SUBBAND_ROUTES.get(st.route, st.route),
-                'lds_bytes': int(st.lds_bytes)}
 
     # ---- delay spectra and power spectra of runs (include/prisim_runs.h) ----
     def runs_transform(self, vis, nbl, nchan, nt, bp=None, wts=None, win=None, m=None, scale=1.0, mode='all', nout=None, factor=1.0,
@@ -1027,18 +1050,17 @@ class Context(object):
         modes = {'all': PRISIM_RUNS_ALL, 'interp': PRISIM_RUNS_INTERP, 'resample': PRISIM_RUNS_RESAMPLE}
         md = modes[mode]
         nout = m if md == PRISIM_RUNS_ALL else int(nout)
-        mo = mi = mw = None
-        if md == PRISIM_RUNS_RESAMPLE and 1 <= nout <= PRISIM_RUNS_MAX_LEN and 1 <= m <= PRISIM_RUNS_MAX_LEN:
-            mo, mi, mw = (NP.ascontiguousarray(a) for a in dsp_readings.resample_map(m, nout))    # the one reading of the resampling
+        nmap, mo, mi, mw = _resample_map(md == PRISIM_RUNS_RESAMPLE and 1 <= nout <= PRISIM_RUNS_MAX_LEN and 1 <= m <= PRISIM_RUNS_MAX_LEN,
+                                         m, nout)
         out = NP.empty((nwin, R, nbl, max(nout, 1), nt), dtype=NP.complex128)
         st = PrisimRunsStats()
-        r = {'auto': PRISIM_RUNS_AUTO, 'fused': PRISIM_RUNS_FUSED, 'rocfft': PRISIM_RUNS_ROCFFT}[route]
+        r = {'auto': PRISIM_RUNS_AUTO, 'fused': PRISIM_RUNS_FUSED, 'rocfft': PRISIM_RUNS_ROCFFT}[route]      # 'direct' is not the caller's to ask for
         (bpa, bps), (wa, wss) = weights
         self._check(self._lib.prisim_runs_transform(self._h, R, nbl, nchan, nt, _ptr(x), c64, _ptr(bpa), _ptr(bps), _ptr(wa), _ptr(wss),
                                                     nwin, _ptr(wn), m, float(scale), md, nout, float(factor),
-                                                    0 if mo is None else mo.size, _ptr(mo), _ptr(mi), _ptr(mw), r, int(budget_bytes),
+                                                    nmap, _ptr(mo), _ptr(mi), _ptr(mw), r, int(budget_bytes),
                                                     _ptr(out), C.byref(st)), 'prisim_runs_transform')
-        return out, self._runs_stats(st)
+        return out, _stats_dict(st, route=RUNS_ROUTES)
 
     def runs_power(self, vislag1, vislag2=None, factor=1.0, cross=False, budget_bytes=RUNS_BUDGET):
         """(vislag1 * vislag2.conj() * factor).real (* 2 when cross) on the device (prisim_runs_power), rounded as numpy rounds it on
@@ -1063,16 +1085,11 @@ class Context(object):
         out = NP.empty(v1.shape, dtype=NP.float64)
         st = PrisimRunsStats()
         if n == 0:
-            return out, self._runs_stats(st)
+            return out, _stats_dict(st, route=RUNS_ROUTES)
         self._check(self._lib.prisim_runs_power(self._h, nf, inner, _ptr(v1), _ptr(v2), int(dt == NP.complex64), _ptr(f), int(bool(cross)),
                                                 int(numpy_fuses_complex_product(dt)), int(budget_bytes), _ptr(out), C.byref(st)),
                     'prisim_runs_power')
-        return out, self._runs_stats(st)
-
-    @staticmethod
-    def _runs_stats(st):
-        return {'wall_ms': st.wall_ms, 'pairs': int(st.pairs), 'chunks': int(st.chunks), 'chunk_pairs': int(st.chunk_pairs),
-                'route': RUNS_ROUTES.get(st.route, st.route), 'streams': int(st.streams), 'tile': int(st.tile), 'lds_bytes': int(st.lds_bytes)}
+        return out, _stats_dict(st, route=RUNS_ROUTES)
 
     # ---- closure phases of antenna triads (include/prisim_closure.h) ----
     def closure_phase(self, cube, legs, conj, bpwts, freq_wts=None, masks=None, mask_index=None, nt=None, route='auto',
@@ -1110,23 +1127,13 @@ class Context(object):
         trip = NP.empty((ntriads, 3, nchan, nt), dtype=NP.complex128)
         phase = NP.empty((ntriads, nchan, nt), dtype=NP.float64)
         st = PrisimClosureStats()
-        r = {'auto': PRISIM_CLOSURE_AUTO, 'direct': PRISIM_CLOSURE_DIRECT, 'fused': PRISIM_CLOSURE_FUSED, 'rocfft': PRISIM_CLOSURE_ROCFFT}[route]
+        r = _route_code(route, CLOSURE_ROUTES)
         self._check(self._lib.prisim_closure_phase(self._h, _ptr(x), nt, nbl, nchan, _ptr(lg), _ptr(cj), ntriads, _ptr(fw), _ptr(bw),
                                                    _ptr(mk), 0 if mk is None else mk.shape[0], _ptr(mi), r, int(budget_bytes),
                                                    _ptr(trip), _ptr(phase), C.byref(st)), 'prisim_closure_phase')
-        return trip, phase, {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'triads': int(st.triads), 'chunks': int(st.chunks),
-                             'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes),
-                             'download_bytes': int(st.download_bytes), 'route': CLOSURE_ROUTES.get(st.route, st.route),
-                             'streams': int(st.streams), 'tile': int(st.tile), 'lds_bytes': int(st.lds_bytes), 'resident': x is None}
+        return trip, phase, dict(_stats_dict(st, route=CLOSURE_ROUTES), resident=x is None)
 
     # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
-    @staticmethod
-    def _cpdelay_stats(st):
-        return {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows), 'chunks': int(st.chunks),
-                'chunk_rows': int(st.chunk_rows), 'upload_bytes': int(st.upload_bytes), 'download_bytes': int(st.download_bytes),
-                'route': CPDELAY_ROUTES.get(st.route, st.route), 'phase_route': CLOSURE_ROUTES.get(st.phase_route),
-                'streams': int(st.streams), 'tile': int(st.tile), 'lds_bytes': int(st.lds_bytes)}
-
     def closure_delay_spectra(self, wts, m, df, phases=None, cube=None, legs=None, conj=None, bpwts=None, freq_wts=None, masks=None,
                               mask_index=None, nt=None, phase_route='auto', nres=0, pscale=None, want=('res',), route='auto',
                               want_phase=False, budget_bytes=CLOSURE_BUDGET):
@@ -1176,11 +1183,8 @@ class Context(object):
                     mi = NP.ascontiguousarray(mask_index, dtype=NP.int32).ravel()
                     if mi.size != nbl:
                         raise ValueError('mask_index must have one entry per cube row')
-        bits = {'over': PRISIM_CPDELAY_OVER, 'over_power': PRISIM_CPDELAY_OVER_POWER, 'res': PRISIM_CPDELAY_RES,
-                'res_power': PRISIM_CPDELAY_RES_POWER}
-        flag = 0
-        for name in want:
-            flag |= bits[name]
+        flag = _want_bits(want, {'over': PRISIM_CPDELAY_OVER, 'over_power': PRISIM_CPDELAY_OVER_POWER, 'res': PRISIM_CPDELAY_RES,
+                                 'res_power': PRISIM_CPDELAY_RES_POWER})
         ps = None if pscale is None else NP.ascontiguousarray(NP.broadcast_to(NP.asarray(pscale, dtype=NP.float64).ravel(), (nwin,)))
         out = {}
         for name in want:
@@ -1188,19 +1192,16 @@ class Context(object):
             out[name] = NP.empty(tuple(lead) + (nwin, n, nt), dtype=NP.complex128 if name in ('over', 'res') else NP.float64)
         if want_phase and phases is None:
             out['phase'] = NP.empty((nrows, nchan, nt), dtype=NP.float64)
-        mo = mi_ = mw = None
-        if flag & (PRISIM_CPDELAY_RES | PRISIM_CPDELAY_RES_POWER) and 1 <= nres <= PRISIM_CPDELAY_MAX_LEN and 1 <= m <= PRISIM_CPDELAY_MAX_LEN:
-            mo, mi_, mw = (NP.ascontiguousarray(a) for a in dsp_readings.resample_map(m, nres))   # the one reading of the resampling
+        nmap, mo, mi_, mw = _resample_map(flag & (PRISIM_CPDELAY_RES | PRISIM_CPDELAY_RES_POWER) and 1 <= nres <= PRISIM_CPDELAY_MAX_LEN
+                                          and 1 <= m <= PRISIM_CPDELAY_MAX_LEN, m, nres)
         st = PrisimCpdelayStats()
-        r = {'auto': PRISIM_CPDELAY_AUTO, 'fused': PRISIM_CPDELAY_FUSED, 'rocfft': PRISIM_CPDELAY_ROCFFT}[route]
-        pr = {'auto': PRISIM_CLOSURE_AUTO, 'direct': PRISIM_CLOSURE_DIRECT, 'fused': PRISIM_CLOSURE_FUSED,
-              'rocfft': PRISIM_CLOSURE_ROCFFT}[phase_route]
+        r, pr = _route_code(route, CPDELAY_ROUTES), _route_code(phase_route, CLOSURE_ROUTES)
         self._check(self._lib.prisim_closure_delay_spectra(
             self._h, _ptr(ph), nrows, _ptr(x), int(nt), int(nbl), nchan, _ptr(lg), _ptr(cj), _ptr(fw), _ptr(bw), _ptr(mk),
-            0 if mk is None else mk.shape[0], _ptr(mi), pr, nwin, _ptr(w), m, float(df), nres, 0 if mo is None else mo.size, _ptr(mo),
+            0 if mk is None else mk.shape[0], _ptr(mi), pr, nwin, _ptr(w), m, float(df), nres, nmap, _ptr(mo),
             _ptr(mi_), _ptr(mw), _ptr(ps), flag, r, int(budget_bytes), _ptr(out.get('phase')), _ptr(out.get('over')),
             _ptr(out.get('over_power')), _ptr(out.get('res')), _ptr(out.get('res_power')), C.byref(st)), 'prisim_closure_delay_spectra')
-        out['stats'] = self._cpdelay_stats(st)
+        out['stats'] = _stats_dict(st, route=CPDELAY_ROUTES, phase_route=CLOSURE_ROUTES.get)   # phase_route: None where no phases were formed
         out['stats']['resident'] = phases is None and x is None
         return out
 
@@ -1215,16 +1216,13 @@ class Context(object):
         n0, nwin = x.shape[0], x.shape[1]
         inner = int(NP.prod(x.shape[2:], dtype=NP.int64))
         sc = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(scale, dtype=NP.float64).ravel(), (nwin,)))
-        bits = {'individual': PRISIM_CPPOWER_INDIVIDUAL, 'auto': PRISIM_CPPOWER_AUTO, 'cross': PRISIM_CPPOWER_CROSS}
-        flag = 0
-        for name in want:
-            flag |= bits[name]
+        flag = _want_bits(want, {'individual': PRISIM_CPPOWER_INDIVIDUAL, 'auto': PRISIM_CPPOWER_AUTO, 'cross': PRISIM_CPPOWER_CROSS})
         out = {name: NP.empty(x.shape if name == 'individual' else (1,) + x.shape[1:], dtype=NP.float64) for name in want}
         st = PrisimCpdelayStats()
         self._check(self._lib.prisim_closure_power(self._h, n0, nwin, inner, _ptr(x), _ptr(sc), flag, int(budget_bytes),
                                                    _ptr(out.get('individual')), _ptr(out.get('auto')), _ptr(out.get('cross')),
                                                    C.byref(st)), 'prisim_closure_power')
-        out['stats'] = self._cpdelay_stats(st)
+        out['stats'] = _stats_dict(st, route=CPDELAY_ROUTES, phase_route=CLOSURE_ROUTES.get)   # phase_route: None where no phases were formed
         return out
 
     # ---- day and LST binning of closure phases (include/prisim_cpbins.h) ----
@@ -1274,9 +1272,7 @@ class Context(object):
         if nbins < 1 or off[0] != 0 or off[-1] != mem.size:
             raise ValueError('offsets must be (nbins + 1,), from 0 to the number of members')
         oshape = tuple(nbins if i == axis else n for i, n in enumerate(shape))
-        flag = 0
-        for name in want:
-            flag |= CPBINS_WANT[name]
+        flag = _want_bits(want, CPBINS_WANT)
         out = {name: NP.empty(oshape, dtype=NP.complex128 if name.startswith('eicp') else NP.float64) for name in want}
         st = PrisimCpbinsStats()
         hin = C.c_void_p(stack.handle.value) if stack is not None else None
@@ -1288,9 +1284,7 @@ class Context(object):
             _ptr(out.get('cp_median')), _ptr(out.get('rms')), _ptr(out.get('mad')), C.byref(st)), 'prisim_cphase_bin')
         if keep:
             out['stack'] = CphaseStack(self, hout, PRISIM_CPBINS_BINNED, oshape)
-        out['stats'] = {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements), 'chunks': int(st.chunks),
-                        'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes), 'upload_bytes': int(st.upload_bytes),
-                        'download_bytes': int(st.download_bytes), 'max_bin': int(st.max_bin), 'resident': bool(st.resident_in)}
+        out['stats'] = _stats_dict(st, rename={'resident_in': 'resident'}, resident_in=bool)
         return out
 
     # ---- differences of day sub-samples of binned closure phases (include/prisim_cpdiff.h) ----
@@ -1335,9 +1329,7 @@ class Context(object):
             *[_ptr(out[name]) for name in CPDIFF_OUTPUTS], C.byref(st)), 'prisim_cphase_diff')
         for name in ('mask0', 'mask1'):
             out[name] = out[name].view(NP.bool_)
-        out['stats'] = {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements), 'chunks': int(st.chunks),
-                        'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes), 'upload_bytes': int(st.upload_bytes),
-                        'download_bytes': int(st.download_bytes), 'resident': bool(st.resident_in), 'ncomb': int(st.ncomb)}
+        out['stats'] = _stats_dict(st, rename={'resident_in': 'resident'}, resident_in=bool)
         return out
 
     # ---- delay spectra of binned closure phasors (include/prisim_cpft.h) ----
@@ -1381,16 +1373,11 @@ class Context(object):
         if vscale is not None:
             vs = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(vscale, dtype=NP.float64), (nwin, lead[0])))
         m = int(m)
-        bits = {'over': PRISIM_CPFT_OVER, 'res': PRISIM_CPFT_RES, 'lag_kernel': PRISIM_CPFT_LAG}
-        flag = 0
-        for name in want:
-            flag |= bits[name]
+        flag = _want_bits(want, {'over': PRISIM_CPFT_OVER, 'res': PRISIM_CPFT_RES, 'lag_kernel': PRISIM_CPFT_LAG})
         nres = 0 if nres is None else int(nres)
         if flag & PRISIM_CPFT_RES and nres < 1:
             raise ValueError('the resampled spectra need nres >= 1')
-        mo = mi = mw = None
-        if flag & PRISIM_CPFT_RES and nres <= PRISIM_CPFT_MAX_LEN and 1 <= m <= PRISIM_CPFT_MAX_LEN:
-            mo, mi, mw = (NP.ascontiguousarray(a) for a in dsp_readings.resample_map(m, nres))      # the one reading of the resampling
+        nmap, mo, mi, mw = _resample_map(flag & PRISIM_CPFT_RES and nres <= PRISIM_CPFT_MAX_LEN and 1 <= m <= PRISIM_CPFT_MAX_LEN, m, nres)
         nin = len(xs)
         out = {'over': None, 'res': None, 'lag_kernel': None, 'lag_kernel_res': None}
         if flag & PRISIM_CPFT_OVER:
@@ -1410,24 +1397,16 @@ class Context(object):
 
         shapes = NP.ascontiguousarray([x.shape[:3] for x in xs], dtype=NP.int64).reshape(-1, 3)
         st = PrisimCpftStats()
-        r = {'auto': PRISIM_CPFT_AUTO, 'fused': PRISIM_CPFT_FUSED, 'rocfft': PRISIM_CPFT_ROCFFT}[route]
+        r = _route_code(route, CPFT_ROUTES)
         self._check(self._lib.prisim_cphase_ft(
             self._h, int(lead[0]), int(lead[1]), int(lead[2]), nchan, nin, pointers(xs), _ptr(shapes) if nin else None, _ptr(w), nwin,
-            _ptr(fw), _ptr(vs), m, float(df), nres, 0 if mo is None else mo.size, _ptr(mo), _ptr(mi), _ptr(mw), flag, r, int(budget_bytes),
+            _ptr(fw), _ptr(vs), m, float(df), nres, nmap, _ptr(mo), _ptr(mi), _ptr(mw), flag, r, int(budget_bytes),
             pointers(out['over']), pointers(out['res']), _ptr(out['lag_kernel']), _ptr(out['lag_kernel_res']), C.byref(st)),
             'prisim_cphase_ft')
-        out['stats'] = {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows), 'chunks': int(st.chunks),
-                        'chunk_rows': int(st.chunk_rows), 'row_bytes': int(st.row_bytes), 'kernel_bytes': int(st.kernel_bytes),
-                        'upload_bytes': int(st.upload_bytes), 'download_bytes': int(st.download_bytes),
-                        'route': CPFT_ROUTES.get(st.route, st.route), 'streams': int(st.streams), 'group_rows': int(st.group_rows),
-                        'lds_bytes': int(st.lds_bytes)}
+        out['stats'] = _stats_dict(st, route=CPFT_ROUTES)
         return out
 
     # ---- instrument gain tables (include/prisim_gains.h) ----
-    @staticmethod
-    def _gains_stats(st):
-        return {'device_ms': st.device_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements)}
-
     def gains_eval_spline(self, packed, times, freqs):
         """Evaluate a packed spline table (prisim_amd/gains.py:pack_splines) at every (time, channel) on the device: a GainTable
         [nt][nrows][nchan] and the stats."""
@@ -1442,7 +1421,7 @@ class Context(object):
                                                        _ptr(arr['kx_off']), _ptr(arr['ky_off']), _ptr(arr['c_off']), kn.size, _ptr(kn),
                                                        co.size, _ptr(co), t.size, _ptr(t), f.size, _ptr(f), C.byref(h), C.byref(st)),
                     'prisim_gains_eval_spline')
-        return GainTable(self, h), self._gains_stats(st)
+        return GainTable(self, h), _stats_dict(st)
 
     def gains_gather(self, gains, fidx, tidx):
         """Nearest-neighbour table on the device: table[t][r][f] = gains[r][fidx[f]][tidx[t]] for gains (nrows, ngf, ngt)."""
@@ -1454,7 +1433,7 @@ class Context(object):
         h, st = C.c_void_p(), PrisimGainsStats()
         self._check(self._lib.prisim_gains_gather(self._h, g.shape[0], g.shape[1], g.shape[2], _ptr(g), fi.size, _ptr(fi), ti.size, _ptr(ti),
                                                   C.byref(h), C.byref(st)), 'prisim_gains_gather')
-        return GainTable(self, h), self._gains_stats(st)
+        return GainTable(self, h), _stats_dict(st)
 
     def gains_apply(self, nt, nbl, nchan, fa=None, fb=None, sky=None, t0=0, sky_c64=False, noise=None, want_gain=False):
         """vis [nt][nbl][nchan] = (fa * fb) * sky + noise on the device (prisim_gains_apply).  fa / fb: None or (GainTable, mode, a, c)
@@ -1481,7 +1460,7 @@ class Context(object):
         self._check(self._lib.prisim_gains_apply(self._h, int(nt), int(nbl), int(nchan), ta, ma, _ptr(aa), _ptr(ca), tb, mb, _ptr(ab), _ptr(cb),
                                                  _ptr(s), int(t0), int(bool(sky_c64)), _ptr(n), int(bool(want_gain)), _ptr(out), C.byref(st)),
                     'prisim_gains_apply')
-        return out, self._gains_stats(st)
+        return out, _stats_dict(st)
 
     # ---- multi-GPU ----
     @staticmethod

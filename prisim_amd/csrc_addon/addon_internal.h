@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../csrc/ctx_internal.h"
+#include "addon_plan.h"
 
 namespace pint {
 
@@ -23,7 +24,6 @@ constexpr int kThreads = 256;                         // threads per workgroup o
 constexpr int kMaxStreams = 2;
 constexpr int kMaxTile = 64;                          // snapshots per workgroup of the tiled fused kernels
 constexpr int kTileLds = 65536;                       // LDS their snapshot rows may fill
-constexpr int64_t kDefaultBudget = int64_t(1) << 30;  // device bytes of a call's chunk buffers when the caller gives none
 constexpr int64_t kMaxBlocks = int64_t(1) << 20;
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
@@ -41,12 +41,34 @@ struct Dev {
     (ptr) = reinterpret_cast<decltype(ptr)>(p_);                                                       \
   } while (0)
 
-// a call's own streams, each with an optional pair of kernel-timing events.  Drained when they go.
+// a table: `count` elements of T allocated and, where there are any on the host, copied up on stream s.  ptr may point to a type
+// that packs whole T's (double2 for pairs of doubles, int4 for four int32): count is in T's, and the one byte count serves both.
+template <typename P, typename T>
+inline int dev_upload(prisim_ctx* ctx, Dev& dev, P*& ptr, const T* host, size_t count, hipStream_t s) {
+  static_assert(sizeof(P) % sizeof(T) == 0, "the device element is a whole number of host elements");
+  DEV_ALLOC(ctx, dev, ptr, count * sizeof(T));
+  if (host && count) HIPCHK(ctx, hipMemcpyAsync(ptr, host, count * sizeof(T), hipMemcpyHostToDevice, s));
+  return PRISIM_OK;
+}
+template <typename P, typename T>
+inline int dev_upload(prisim_ctx* ctx, Dev& dev, P*& ptr, const std::vector<T>& host, hipStream_t s) {
+  return dev_upload(ctx, dev, ptr, host.data(), host.size(), s);
+}
+
+#define DEV_UPLOAD(ctx, dev, ptr, ...)                                                                 \
+  do {                                                                                                 \
+    if (int rc_ = dev_upload(ctx, dev, ptr, __VA_ARGS__)) return rc_;                                  \
+  } while (0)
+
+// A call's own streams, each with an optional pair of kernel-timing events.  Drained when they go.  A chunk loop deals chunk c to
+// stream i = c % n: harvest(i), the uploads, open(i), the kernels, close(i), the downloads; then drain().  Without events open and
+// close do nothing and kernel_ms stays 0.
 struct Streams {
   hipStream_t s[kMaxStreams] = {};
   hipEvent_t k0[kMaxStreams] = {}, k1[kMaxStreams] = {};
   bool timed[kMaxStreams] = {};
   int n = 0;
+  double kernel_ms = 0.0;                             // of the chunks harvested so far
   ~Streams() {
     for (int i = 0; i < n; ++i) {
       (void)hipStreamSynchronize(s[i]);
@@ -66,13 +88,30 @@ struct Streams {
     }
     return PRISIM_OK;
   }
-  // adds the kernel time of the chunk stream i ran last (between k0 and k1) to kernel_ms
-  int harvest(prisim_ctx* ctx, int i, double& kernel_ms) {
+  // waits for the kernels of the chunk stream i ran last, if any, and adds their time (between k0 and k1) to kernel_ms
+  int harvest(prisim_ctx* ctx, int i) {
     if (!timed[i]) return PRISIM_OK;
     HIPCHK(ctx, hipEventSynchronize(k1[i]));
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, k0[i], k1[i]) == hipSuccess) kernel_ms += ms;
     timed[i] = false;
+    return PRISIM_OK;
+  }
+  int open(prisim_ctx* ctx, int i) {
+    if (k0[i]) HIPCHK(ctx, hipEventRecord(k0[i], s[i]));
+    return PRISIM_OK;
+  }
+  int close(prisim_ctx* ctx, int i) {
+    if (k1[i]) HIPCHK(ctx, hipEventRecord(k1[i], s[i]));
+    timed[i] = k1[i] != nullptr;
+    return PRISIM_OK;
+  }
+  // every stream idle and harvested
+  int drain(prisim_ctx* ctx) {
+    for (int i = 0; i < n; ++i) {
+      HIPCHK(ctx, hipStreamSynchronize(s[i]));
+      if (int rc = harvest(ctx, i)) return rc;
+    }
     return PRISIM_OK;
   }
 };
@@ -151,8 +190,6 @@ inline int ensure_rocfft(prisim_ctx* ctx) {
   return PRISIM_OK;
 }
 
-inline int64_t budget_or_default(int64_t budget) { return budget > 0 ? budget : kDefaultBudget; }
-
 // workgroups of a grid-stride kernel over n elements
 inline int grid_for(const prisim_ctx* ctx, int64_t n) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)std::max(ctx->cu_count, 1) * 16));
@@ -168,6 +205,19 @@ inline hipError_t copy_rows(void* dst, size_t dpitch, const void* src, size_t sp
 using WallTime = std::chrono::steady_clock::time_point;
 inline WallTime wall_now() { return std::chrono::steady_clock::now(); }
 inline double wall_ms_since(WallTime t0) { return std::chrono::duration<double, std::milli>(wall_now() - t0).count(); }
+
+// the LDS a workgroup may have on the context's device
+inline int lds_limit(prisim_ctx* ctx, int& lds_max) {
+  HIPCHK(ctx, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  return PRISIM_OK;
+}
+
+// lets `kernel` take `bytes` of dynamic LDS: beyond 64 KiB a kernel has to be told
+template <typename K>
+inline int allow_lds(prisim_ctx* ctx, K* kernel, int64_t bytes) {
+  if (bytes > 65536) HIPCHK(ctx, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return PRISIM_OK;
+}
 
 // The tables of scipy.signal.resample's spectrum from the caller's selection map (prisim_amd/dsp_readings.py:resample_map): per output
 // bin at most two input bins rs_in [2][nout] (-1: none; bins of the zero padding are dropped) with the coefficients rs_c [2][nout]

@@ -456,7 +456,7 @@ int run_clean(prisim_ctx* ctx, Dev& dev, const double2* d_inp, int64_t nrows, in
   HIPCHK(ctx, hipGetLastError());
 
   int lds_max = 0;
-  HIPCHK(ctx, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  if (int rc = lds_limit(ctx, lds_max)) return rc;
   const int wave_bytes = (26 * m + 15) / 16 * 16;          // r (16 B), sk (8 B), perm (2 B) per lag; every row 16-B aligned
   const int kern_bytes = 16 * m;
   const bool kern_lds = nkern == 1 && kern_bytes + wave_bytes <= lds_max;
@@ -467,7 +467,7 @@ int run_clean(prisim_ctx* ctx, Dev& dev, const double2* d_inp, int64_t nrows, in
                                         " B of LDS; the device offers " + std::to_string(lds_max) + " B per workgroup");
   waves = (int)std::max<int64_t>(1, std::min<int64_t>(waves, (nrows + ctx->cu_count - 1) / std::max(1, ctx->cu_count)));
   const size_t lds = (size_t)(kern_lds ? kern_bytes : 0) + (size_t)waves * wave_bytes;
-  if (lds > 65536) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_clean_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (int rc = allow_lds(ctx, k_clean_rows, (int64_t)lds)) return rc;
   const int64_t per_cu = std::max<int64_t>(1, kCuLds / (int64_t)lds);
   const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((nrows + waves - 1) / waves, (int64_t)ctx->cu_count * per_cu));
 

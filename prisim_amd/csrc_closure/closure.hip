@@ -240,9 +240,8 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
                                           std::to_string(legs[i]) + " of a cube of " + std::to_string(nbl) + " baselines");
   const bool filter = masks != nullptr;
   if (route < PRISIM_CLOSURE_AUTO || route > PRISIM_CLOSURE_ROCFFT) return fail(ctx, PRISIM_EINVAL, "unknown route");
-  int logn = 0;
-  while ((int64_t(1) << logn) < nchan) ++logn;
-  const bool pow2 = (int64_t(1) << logn) == nchan;
+  bool pow2;
+  const int logn = ceil_log2(nchan, pow2);
   int rt = PRISIM_CLOSURE_DIRECT;
   if (filter) {
     if (nmask < 1) return fail(ctx, PRISIM_EINVAL, "the delay filter needs at least one mask");
@@ -266,7 +265,7 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
   int64_t tile = tiled ? 1 : 0, lds = tiled ? (int64_t)sizeof(double2) * kTile * (kTile + 1) : 0;
   if (rt == PRISIM_CLOSURE_FUSED) {
     int lds_max = 0;
-    HIPCHK(ctx, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+    if (int rc = lds_limit(ctx, lds_max)) return rc;
     const int64_t tw_bytes = 16 * std::max<int64_t>(nchan / 2, 1), row_bytes = 16 * (nchan + 1);
     tile = std::max<int64_t>(1, std::min<int64_t>({nt, (int64_t)kMaxTile, (kTileLds - tw_bytes) / row_bytes}));
     lds = tile * row_bytes + tw_bytes;
@@ -284,25 +283,29 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
   const int64_t per = nchan * nt;
   const int64_t trip_triad = 3 * per * 16, phase_triad = per * 8, fbuf_triad = rt == PRISIM_CLOSURE_ROCFFT ? 3 * per * 16 : 0;
   const int64_t per_triad = trip_triad + phase_triad + fbuf_triad + (sink ? sink->bytes_per_triad : 0);
-  const int64_t budget = budget_or_default(budget_bytes);
-  int64_t tc = std::max<int64_t>(1, std::min<int64_t>(ntriads, budget / (kMaxStreams * per_triad)));
+  const int64_t fit = plan_chunks(ntriads, per_triad, budget_bytes, kMaxStreams).size;
   const int64_t blocks_triad = tiled ? nct * ntt : 3 * ntiles;                      // grid x of the tiled kernels
-  tc = std::max<int64_t>(1, std::min<int64_t>(tc, (((int64_t)1 << 31) - 1) / blocks_triad));
-  const int64_t nchunks = (ntriads + tc - 1) / tc;
-  const int nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
+  const int64_t grid_max = std::max<int64_t>(1, (((int64_t)1 << 31) - 1) / blocks_triad);
+  const Chunks ch = chunks_of(ntriads, std::min(fit, grid_max), kMaxStreams);
+  const int64_t tc = ch.size, nchunks = ch.count;
+  const int nstreams = ch.nstreams;
 
+  // the cube and the tables go up on stream 0 as they are allocated
   Work wk;
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, nstreams, true)) return rc;
+  hipStream_t s0 = st.s[0];
   double2* d_cube = nullptr;
   double *d_bpw = nullptr, *d_fw = nullptr, *d_masks = nullptr;
   int32_t *d_midx = nullptr, *d_legs = nullptr, *d_conj = nullptr;
-  if (cube) DEV_ALLOC(ctx, wk.dev, d_cube, nbl * per * 16);
-  DEV_ALLOC(ctx, wk.dev, d_bpw, nbl * per * 8);
-  DEV_ALLOC(ctx, wk.dev, d_fw, nchan * 8);
-  DEV_ALLOC(ctx, wk.dev, d_legs, ntriads * 3 * 4);
-  DEV_ALLOC(ctx, wk.dev, d_conj, ntriads * 3 * 4);
+  if (cube) DEV_UPLOAD(ctx, wk.dev, d_cube, cube, (size_t)(nbl * per * 2), s0);
+  DEV_UPLOAD(ctx, wk.dev, d_bpw, bpwts, (size_t)(nbl * per), s0);
+  DEV_UPLOAD(ctx, wk.dev, d_fw, freq_wts, (size_t)nchan, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_legs, legs, (size_t)(ntriads * 3), s0);
+  DEV_UPLOAD(ctx, wk.dev, d_conj, conj, (size_t)(ntriads * 3), s0);
   if (filter) {
-    DEV_ALLOC(ctx, wk.dev, d_masks, nmask * nchan * 8);
-    if (mask_index) DEV_ALLOC(ctx, wk.dev, d_midx, nbl * 4);
+    DEV_UPLOAD(ctx, wk.dev, d_masks, masks, (size_t)(nmask * nchan), s0);
+    if (mask_index) DEV_UPLOAD(ctx, wk.dev, d_midx, mask_index, (size_t)nbl, s0);
   }
   double2* d_trip[kMaxStreams] = {};
   double* d_phase[kMaxStreams] = {};
@@ -312,27 +315,15 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
     DEV_ALLOC(ctx, wk.dev, d_phase[i], tc * phase_triad);
     if (fbuf_triad) DEV_ALLOC(ctx, wk.dev, d_fbuf[i], tc * fbuf_triad);
   }
-  Streams& st = wk.st;
-  if (int rc = st.create(ctx, nstreams, true)) return rc;
   if (sink)
-    if (int rc = sink->prepare(tc, ntriads - (nchunks - 1) * tc, nstreams, st.s)) return rc;
+    if (int rc = sink->prepare(tc, ch.last, nstreams, st.s)) return rc;
   if (rt == PRISIM_CLOSURE_ROCFFT) {
-    const size_t b0 = (size_t)tc * 3 * (size_t)nt, b1 = (size_t)(ntriads - (nchunks - 1) * tc) * 3 * (size_t)nt;
+    const size_t b0 = (size_t)tc * 3 * (size_t)nt, b1 = (size_t)ch.last * 3 * (size_t)nt;
     if (int rc = wk.fft.create(ctx, wk.dev, (size_t)nchan, {{false, b0}, {true, b0}, {false, b1}, {true, b1}}, st.s, nstreams)) return rc;
   }
 
-  // the cube and the tables on stream 0, behind whatever the context's stream still writes into the resident cube
-  hipStream_t s0 = st.s[0];
+  // the kernels start behind whatever the context's stream still writes into the resident cube
   if (!cube) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (cube) HIPCHK(ctx, hipMemcpyAsync(d_cube, cube, nbl * per * 16, hipMemcpyHostToDevice, s0));
-  HIPCHK(ctx, hipMemcpyAsync(d_bpw, bpwts, nbl * per * 8, hipMemcpyHostToDevice, s0));
-  HIPCHK(ctx, hipMemcpyAsync(d_fw, freq_wts, nchan * 8, hipMemcpyHostToDevice, s0));
-  HIPCHK(ctx, hipMemcpyAsync(d_legs, legs, ntriads * 3 * 4, hipMemcpyHostToDevice, s0));
-  HIPCHK(ctx, hipMemcpyAsync(d_conj, conj, ntriads * 3 * 4, hipMemcpyHostToDevice, s0));
-  if (filter) {
-    HIPCHK(ctx, hipMemcpyAsync(d_masks, masks, nmask * nchan * 8, hipMemcpyHostToDevice, s0));
-    if (mask_index) HIPCHK(ctx, hipMemcpyAsync(d_midx, mask_index, nbl * 4, hipMemcpyHostToDevice, s0));
-  }
   HIPCHK(ctx, hipStreamSynchronize(s0));            // stream 1 starts behind the uploads; the tables are caller memory
 
   ClParams base;
@@ -342,19 +333,18 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
   base.T0 = 0; base.tc = 0;
   base.nchan = (int)nchan; base.nt = (int)nt; base.logn = logn; base.tile = (int)tile; base.ntiles = (int)ntiles;
   base.trip = nullptr; base.phase = nullptr; base.fbuf = nullptr;
-  if (rt == PRISIM_CLOSURE_FUSED && lds > 65536)
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)k_cl_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (rt == PRISIM_CLOSURE_FUSED)
+    if (int rc = allow_lds(ctx, k_cl_fused, lds)) return rc;
 
-  double kernel_ms = 0.0;
   for (int64_t c = 0; c < nchunks; ++c) {
     const int i = (int)(c % nstreams);
     hipStream_t sc = st.s[i];
-    if (int rc = st.harvest(ctx, i, kernel_ms)) return rc;
+    if (int rc = st.harvest(ctx, i)) return rc;
     const int64_t T0 = c * tc, tn = std::min(tc, ntriads - T0);
     ClParams P = base;
     P.T0 = T0; P.tc = tn; P.trip = d_trip[i]; P.phase = d_phase[i]; P.fbuf = d_fbuf[i];
     const int64_t ne = tn * per;
-    HIPCHK(ctx, hipEventRecord(st.k0[i], sc));
+    if (int rc = st.open(ctx, i)) return rc;
     if (rt == PRISIM_CLOSURE_DIRECT) {
       if (tiled) hipLaunchKernelGGL(k_cl_tiled, dim3((unsigned)(tn * nct * ntt)), dim3(kThreads), 0, sc, P, (int)nct, (int)ntt);
       else hipLaunchKernelGGL(k_cl_plain, dim3((unsigned)grid_for(ctx, ne)), dim3(kThreads), 0, sc, P);
@@ -383,18 +373,14 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
     }
     if (sink)
       if (int rc = sink->kernels(i, sc, T0, tn, d_phase[i])) return rc;
-    HIPCHK(ctx, hipEventRecord(st.k1[i], sc));
-    st.timed[i] = true;
+    if (int rc = st.close(ctx, i)) return rc;
     if (out_triplets)
       HIPCHK(ctx, hipMemcpyAsync(out_triplets + 2 * (size_t)T0 * 3 * per, d_trip[i], (size_t)tn * trip_triad, hipMemcpyDeviceToHost, sc));
     if (out_phase) HIPCHK(ctx, hipMemcpyAsync(out_phase + (size_t)T0 * per, d_phase[i], (size_t)tn * phase_triad, hipMemcpyDeviceToHost, sc));
     if (sink)
       if (int rc = sink->download(i, sc, T0, tn)) return rc;
   }
-  for (int i = 0; i < nstreams; ++i) {
-    HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
-    if (int rc = st.harvest(ctx, i, kernel_ms)) return rc;
-  }
+  if (int rc = st.drain(ctx)) return rc;
   if (stats) {
     // per output point: three legs read (16 B) with their weights (8 B) and written (16 B), one phase written (8 B); the filter's
     // phase kernel reads the triplets again, and the rocFFT route passes its row buffer through five kernels (read and write)
@@ -402,7 +388,7 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
     if (rt != PRISIM_CLOSURE_DIRECT) point += 3 * 16;
     if (rt == PRISIM_CLOSURE_ROCFFT) point += 3 * 16 * 8;
     stats->wall_ms = wall_ms_since(wall0);
-    stats->kernel_ms = kernel_ms;
+    stats->kernel_ms = st.kernel_ms;
     stats->triads = ntriads;
     stats->chunks = nchunks;
     stats->chunk_triads = tc;

@@ -313,15 +313,17 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
       if (!is_kept) out_doubles += (o == 1 || o == 2) ? 2 : 1;
     }
   const int64_t per_triad = in_per_triad + rows_out * nchan * 8 * out_doubles;
-  const int64_t budget = budget_or_default(budget_bytes);
-  const int64_t tc = per_triad > 0 ? std::max<int64_t>(1, std::min<int64_t>(ntriads, budget / per_triad)) : ntriads;
-  const int64_t nchunks = (ntriads + tc - 1) / tc;
+  const Chunks ch = per_triad > 0 ? plan_chunks(ntriads, per_triad, budget_bytes, 1) : chunks_of(ntriads, ntriads, 1);
+  const int64_t tc = ch.size, nchunks = ch.count;
 
   Work wk;
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, 1, true)) return rc;
+  hipStream_t s = st.s[0];
   int64_t* d_off;
   int32_t* d_mem;
-  DEV_ALLOC(ctx, wk.dev, d_off, (nbins + 1) * 8);
-  DEV_ALLOC(ctx, wk.dev, d_mem, nmem * 4);
+  DEV_UPLOAD(ctx, wk.dev, d_off, offsets, (size_t)nbins + 1, s);
+  DEV_UPLOAD(ctx, wk.dev, d_mem, members, (size_t)nmem, s);
   double *d_a = nullptr, *d_b = nullptr, *d_w = nullptr;
   uint8_t* d_f = nullptr;
   if (!rin) {
@@ -336,15 +338,9 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
   double* d_out[7] = {};
   for (int o = 0; o < 7; ++o)
     if ((comp >> o & 1) && !(keep_out && (kKept >> o & 1))) DEV_ALLOC(ctx, wk.dev, d_out[o], rows_out * tc * nchan * ((o == 1 || o == 2) ? 16 : 8));
-  Streams& st = wk.st;
-  if (int rc = st.create(ctx, 1, true)) return rc;
-  hipStream_t s = st.s[0];
-  HIPCHK(ctx, hipMemcpyAsync(d_off, offsets, (nbins + 1) * 8, hipMemcpyHostToDevice, s));
-  if (nmem > 0) HIPCHK(ctx, hipMemcpyAsync(d_mem, members, nmem * 4, hipMemcpyHostToDevice, s));
   upload_bytes += (nbins + 1) * 8 + nmem * 4;
 
   double* const host_out[7] = {out_wts, out_eicp_mean, out_eicp_median, out_cp_mean, out_cp_median, out_rms, out_mad};
-  double kernel_ms = 0.0;
   for (int64_t c = 0; c < nchunks; ++c) {
     const int64_t T0 = c * tc, tn = std::min(tc, ntriads - T0);
     BinParams p{};
@@ -398,10 +394,10 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
     p.mad_all = mad_ignores_flags ? 1 : 0;
     const int64_t total = rows_out * tn * nchan;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((total + kThreads - 1) / kThreads, kMaxBlocks));
-    HIPCHK(ctx, hipEventRecord(st.k0[0], s));
+    if (int rc = st.open(ctx, 0)) return rc;
     hipLaunchKernelGGL(k_cpbins, dim3((unsigned)blocks), dim3(kThreads), 0, s, p);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(st.k1[0], s));
+    if (int rc = st.close(ctx, 0)) return rc;
     for (int o = 0; o < 7; ++o) {
       if (!(want >> o & 1)) continue;
       const size_t es = (o == 1 || o == 2) ? 16 : 8;
@@ -412,9 +408,7 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
                             (size_t)(tn * nchan) * es, rows_out, hipMemcpyDeviceToHost, s));
       download_bytes += rows_out * tn * nchan * (int64_t)es;
     }
-    HIPCHK(ctx, hipStreamSynchronize(s));           // the chunk's buffers are reused by the next one
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, st.k0[0], st.k1[0]) == hipSuccess) kernel_ms += ms;
+    if (int rc = st.drain(ctx)) return rc;          // the chunk's buffers are reused by the next one
   }
   if (made_in) *resident_in = made_in.release();
   if (keep_out) *keep_out = kept.release();
@@ -423,7 +417,7 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
     for (int o = 0; o < 7; ++o)
       if (comp >> o & 1) outb += (o == 1 || o == 2) ? 16 : 8;
     stats->wall_ms = wall_ms_since(wall0);
-    stats->kernel_ms = kernel_ms;
+    stats->kernel_ms = st.kernel_ms;
     stats->elements = rows_out * row_elems;
     stats->chunks = nchunks;
     stats->chunk_triads = tc;

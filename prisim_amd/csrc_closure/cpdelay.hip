@@ -268,13 +268,14 @@ struct Transform {
     double *d_wts, *d_ps = nullptr;
     int32_t *d_rsn, *d_rsk, *d_rsin;
     double2 *d_rsc, *d_rtw;
-    DEV_ALLOC(ctx, wk.dev, d_wts, (size_t)nwin * nchan * 8);
-    if (pscale) DEV_ALLOC(ctx, wk.dev, d_ps, (size_t)nwin * 8);
-    DEV_ALLOC(ctx, wk.dev, d_rsn, rs_n.size() * 4);
-    DEV_ALLOC(ctx, wk.dev, d_rsk, rs_k.size() * 4);
-    DEV_ALLOC(ctx, wk.dev, d_rsin, rs_in.size() * 4);
-    DEV_ALLOC(ctx, wk.dev, d_rsc, rs_c.size() * 8);
-    DEV_ALLOC(ctx, wk.dev, d_rtw, rtw.size() * 8);
+    hipStream_t s0 = streams[0];
+    DEV_UPLOAD(ctx, wk.dev, d_wts, wts, (size_t)nwin * nchan, s0);
+    if (pscale) DEV_UPLOAD(ctx, wk.dev, d_ps, pscale, (size_t)nwin, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_rsn, rs_n, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_rsk, rs_k, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_rsin, rs_in, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_rsc, rs_c, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_rtw, rtw, s0);
     for (int i = 0; i < nstreams; ++i) {
       if (w_over) DEV_ALLOC(ctx, wk.dev, d_over[i], (size_t)lines * m * 16);
       if (w_opow) DEV_ALLOC(ctx, wk.dev, d_opow[i], (size_t)lines * m * 8);
@@ -286,14 +287,6 @@ struct Transform {
       const size_t per_row = (size_t)nwin * (size_t)nt;
       if (int rc = wk.fft.create(ctx, wk.dev, (size_t)m, {{true, per_row * (size_t)tc}, {true, per_row * (size_t)last}}, streams, nstreams)) return rc;
     }
-    hipStream_t s0 = streams[0];
-    HIPCHK(ctx, hipMemcpyAsync(d_wts, wts, (size_t)nwin * nchan * 8, hipMemcpyHostToDevice, s0));
-    if (pscale) HIPCHK(ctx, hipMemcpyAsync(d_ps, pscale, (size_t)nwin * 8, hipMemcpyHostToDevice, s0));
-    HIPCHK(ctx, hipMemcpyAsync(d_rsn, rs_n.data(), rs_n.size() * 4, hipMemcpyHostToDevice, s0));
-    HIPCHK(ctx, hipMemcpyAsync(d_rsk, rs_k.data(), rs_k.size() * 4, hipMemcpyHostToDevice, s0));
-    HIPCHK(ctx, hipMemcpyAsync(d_rsin, rs_in.data(), rs_in.size() * 4, hipMemcpyHostToDevice, s0));
-    HIPCHK(ctx, hipMemcpyAsync(d_rsc, rs_c.data(), rs_c.size() * 8, hipMemcpyHostToDevice, s0));
-    HIPCHK(ctx, hipMemcpyAsync(d_rtw, rtw.data(), rtw.size() * 8, hipMemcpyHostToDevice, s0));
     HIPCHK(ctx, hipStreamSynchronize(s0));          // the other stream starts behind the tables
     base.phase = nullptr;
     base.wts = d_wts; base.pscale = d_ps;
@@ -302,11 +295,9 @@ struct Transform {
     base.df = df;
     base.rs_n = d_rsn; base.rs_k = d_rsk; base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw;
     base.over = nullptr; base.over_pow = nullptr; base.res = nullptr; base.res_pow = nullptr; base.fbuf = nullptr;
-    if (fused && want_over() && lds > 65536)
-      HIPCHK(ctx, hipFuncSetAttribute((const void*)k_cpd_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (want_res() && rlds > 65536)
-      HIPCHK(ctx, hipFuncSetAttribute((const void*)k_cpd_resample, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
-    return PRISIM_OK;
+    if (fused && want_over())
+      if (int rc = allow_lds(ctx, k_cpd_fused, lds)) return rc;
+    return want_res() ? allow_lds(ctx, k_cpd_resample, rlds) : PRISIM_OK;
   }
 
   int kernels(int i, hipStream_t s, int64_t tn, const double* d_phase) {
@@ -393,12 +384,11 @@ int prisim_closure_delay_spectra(prisim_ctx* ctx, const double* phases, int64_t 
       ((tr.w_opow || tr.w_rpow) && !pscale))
     return fail(ctx, PRISIM_EINVAL, "null array");
   if (route < PRISIM_CPDELAY_AUTO || route > PRISIM_CPDELAY_ROCFFT) return fail(ctx, PRISIM_EINVAL, "unknown route");
-  int logm = 0;
-  while ((int64_t(1) << logm) < m) ++logm;
-  const bool pow2 = (int64_t(1) << logm) == m;
+  bool pow2;
+  const int logm = ceil_log2(m, pow2);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int lds_max = 0;
-  HIPCHK(ctx, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  if (int rc = lds_limit(ctx, lds_max)) return rc;
   const int64_t tw_bytes = 16 * std::max<int64_t>(m / 2, 1), row_bytes = 16 * (m + 1);
   const int64_t ftile = std::max<int64_t>(1, std::min<int64_t>({nt, (int64_t)kMaxTile, (kTileLds - tw_bytes) / row_bytes}));
   const int64_t flds = ftile * row_bytes + tw_bytes;
@@ -489,32 +479,26 @@ int prisim_closure_delay_spectra(prisim_ctx* ctx, const double* phases, int64_t 
     nchunks = cs.chunks; tc = cs.chunk_triads; nstreams = cs.streams; phase_rt = cs.route; kernel_ms = cs.kernel_ms;
     upload += (cube ? nbl * per * 16 : 0) + nbl * per * 8 + nchan * 8 + nrows * 24 + (masks ? nmask * nchan * 8 + (mask_index ? nbl * 4 : 0) : 0);
   } else {
-    const int64_t per_row = per * 8 + tr.bytes_per_row();
-    const int64_t budget = budget_or_default(budget_bytes);
-    tc = std::max<int64_t>(1, std::min<int64_t>(nrows, budget / (kMaxStreams * per_row)));
-    nchunks = (nrows + tc - 1) / tc;
-    nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
+    const Chunks ch = plan_chunks(nrows, per * 8 + tr.bytes_per_row(), budget_bytes, kMaxStreams);
+    tc = ch.size; nchunks = ch.count; nstreams = ch.nstreams;
     double* d_phase[kMaxStreams] = {};
     for (int i = 0; i < nstreams; ++i) DEV_ALLOC(ctx, tr.wk.dev, d_phase[i], tc * per * 8);
     Streams& st = tr.wk.st;
     if (int rc = st.create(ctx, nstreams, true)) return rc;
-    if (int rc = tr.prepare(tc, nrows - (nchunks - 1) * tc, nstreams, st.s)) return rc;
+    if (int rc = tr.prepare(tc, ch.last, nstreams, st.s)) return rc;
     for (int64_t c = 0; c < nchunks; ++c) {
       const int i = (int)(c % nstreams);
       hipStream_t sc = st.s[i];
-      if (int rc = st.harvest(ctx, i, kernel_ms)) return rc;
+      if (int rc = st.harvest(ctx, i)) return rc;
       const int64_t T0 = c * tc, tn = std::min(tc, nrows - T0);
       HIPCHK(ctx, hipMemcpyAsync(d_phase[i], phases + (size_t)T0 * per, (size_t)tn * per * 8, hipMemcpyHostToDevice, sc));
-      HIPCHK(ctx, hipEventRecord(st.k0[i], sc));
+      if (int rc = st.open(ctx, i)) return rc;
       if (int rc = tr.kernels(i, sc, tn, d_phase[i])) return rc;
-      HIPCHK(ctx, hipEventRecord(st.k1[i], sc));
-      st.timed[i] = true;
+      if (int rc = st.close(ctx, i)) return rc;
       if (int rc = tr.download(i, sc, T0, tn)) return rc;
     }
-    for (int i = 0; i < nstreams; ++i) {
-      HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
-      if (int rc = st.harvest(ctx, i, kernel_ms)) return rc;
-    }
+    if (int rc = st.drain(ctx)) return rc;
+    kernel_ms = st.kernel_ms;
     upload += nrows * per * 8;
   }
   if (stats) {
@@ -553,14 +537,16 @@ int prisim_closure_power(prisim_ctx* ctx, int64_t n0, int64_t nwin, int64_t inne
   const int64_t npts = nwin * inner;
   const bool sums = w_auto || w_cross;
   const int64_t per_row = npts * (16 + (w_ind ? 8 : 0));
-  const int64_t budget = budget_or_default(budget_bytes);
-  const int64_t rc_rows = std::max<int64_t>(1, std::min<int64_t>(n0, budget / per_row));
-  const int64_t nchunks = (n0 + rc_rows - 1) / rc_rows;
+  const Chunks ch = plan_chunks(n0, per_row, budget_bytes, 1);
+  const int64_t rc_rows = ch.size, nchunks = ch.count;
   Work wk;
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, 1, true)) return rc;
+  hipStream_t s = st.s[0];
   double2 *d_x, *d_sum = nullptr;
   double *d_scale, *d_ind = nullptr, *d_sumsq = nullptr, *d_auto = nullptr, *d_cross = nullptr;
   DEV_ALLOC(ctx, wk.dev, d_x, rc_rows * npts * 16);
-  DEV_ALLOC(ctx, wk.dev, d_scale, nwin * 8);
+  DEV_UPLOAD(ctx, wk.dev, d_scale, scale, (size_t)nwin, s);
   if (w_ind) DEV_ALLOC(ctx, wk.dev, d_ind, rc_rows * npts * 8);
   if (sums) {
     DEV_ALLOC(ctx, wk.dev, d_sumsq, npts * 8);
@@ -568,38 +554,31 @@ int prisim_closure_power(prisim_ctx* ctx, int64_t n0, int64_t nwin, int64_t inne
     DEV_ALLOC(ctx, wk.dev, d_auto, npts * 8);
     if (w_cross) DEV_ALLOC(ctx, wk.dev, d_cross, npts * 8);
   }
-  Streams& st = wk.st;
-  if (int rc = st.create(ctx, 1, true)) return rc;
-  hipStream_t s = st.s[0];
-  HIPCHK(ctx, hipMemcpyAsync(d_scale, scale, nwin * 8, hipMemcpyHostToDevice, s));
   if (sums) {
     HIPCHK(ctx, hipMemsetAsync(d_sumsq, 0, npts * 8, s));
     HIPCHK(ctx, hipMemsetAsync(d_sum, 0, npts * 16, s));
   }
   const int g = grid_for(ctx, npts);
-  double kernel_ms = 0.0;
   for (int64_t c = 0; c < nchunks; ++c) {
     const int64_t r0 = c * rc_rows, rn = std::min(rc_rows, n0 - r0);
     HIPCHK(ctx, hipMemcpyAsync(d_x, spectra + 2 * (size_t)r0 * npts, (size_t)rn * npts * 16, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipEventRecord(st.k0[0], s));
+    if (int rc = st.open(ctx, 0)) return rc;
     hipLaunchKernelGGL(k_cpp_accumulate, dim3((unsigned)g), dim3(kThreads), 0, s, d_x, rn, npts, inner, d_scale, d_ind, d_sumsq, d_sum);
     HIPCHK(ctx, hipGetLastError());
     if (sums && c == nchunks - 1) {
       hipLaunchKernelGGL(k_cpp_finish, dim3((unsigned)g), dim3(kThreads), 0, s, n0, npts, inner, d_scale, d_sumsq, d_sum, d_auto, d_cross);
       HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(st.k1[0], s));
+    if (int rc = st.close(ctx, 0)) return rc;
     if (w_ind) HIPCHK(ctx, hipMemcpyAsync(out_individual + (size_t)r0 * npts, d_ind, (size_t)rn * npts * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));           // the chunk's buffers are reused by the next one
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, st.k0[0], st.k1[0]) == hipSuccess) kernel_ms += ms;
+    if (int rc = st.drain(ctx)) return rc;          // the chunk's buffers are reused by the next one
   }
   if (w_auto) HIPCHK(ctx, hipMemcpyAsync(out_auto, d_auto, npts * 8, hipMemcpyDeviceToHost, s));
   if (w_cross) HIPCHK(ctx, hipMemcpyAsync(out_cross, d_cross, npts * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
   if (stats) {
     stats->wall_ms = wall_ms_since(wall0);
-    stats->kernel_ms = kernel_ms;
+    stats->kernel_ms = st.kernel_ms;
     stats->rows = n0;
     stats->chunks = nchunks;
     stats->chunk_rows = rc_rows;

@@ -135,13 +135,15 @@ int prisim_cphase_diff(prisim_ctx* ctx, const double* in_mean, const double* in_
   const int64_t rows_in = n0 * n1, rows_out = n0 * ncomb, row_elems = ntriads * nchan;
   // chunks of triads: the chunk's input (unless resident) and its outputs within the budget
   const int64_t per_triad = (resident ? 0 : rows_in * nchan * 24) + rows_out * nchan * PRISIM_CPDIFF_OUT_BYTES;
-  const int64_t budget = budget_or_default(budget_bytes);
-  const int64_t tc = std::max<int64_t>(1, std::min<int64_t>(ntriads, budget / per_triad));
-  const int64_t nchunks = (ntriads + tc - 1) / tc;
+  const Chunks ch = plan_chunks(ntriads, per_triad, budget_bytes, 1);
+  const int64_t tc = ch.size, nchunks = ch.count;
 
   Work wk;
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, 1, true)) return rc;
+  hipStream_t s = st.s[0];
   int4* d_pairs;
-  DEV_ALLOC(ctx, wk.dev, d_pairs, ncomb * 16);
+  DEV_UPLOAD(ctx, wk.dev, d_pairs, pairs, (size_t)ncomb * 4, s);
   double *d_a = nullptr, *d_b = nullptr, *d_w = nullptr;
   if (!resident) {
     DEV_ALLOC(ctx, wk.dev, d_a, rows_in * tc * nchan * 8);
@@ -153,13 +155,8 @@ int prisim_cphase_diff(prisim_ctx* ctx, const double* in_mean, const double* in_
   void* const host_out[8] = {out_diff0_mean, out_diff0_median, out_diff1_mean, out_diff1_median, out_wts0, out_wts1, out_mask0, out_mask1};
   char* d_out[8] = {};
   for (int o = 0; o < 8; ++o) DEV_ALLOC(ctx, wk.dev, d_out[o], rows_out * tc * nchan * (int64_t)es[o]);
-  Streams& st = wk.st;
-  if (int rc = st.create(ctx, 1, true)) return rc;
-  hipStream_t s = st.s[0];
-  HIPCHK(ctx, hipMemcpyAsync(d_pairs, pairs, ncomb * 16, hipMemcpyHostToDevice, s));
   int64_t upload_bytes = ncomb * 16, download_bytes = 0;
 
-  double kernel_ms = 0.0;
   for (int64_t c = 0; c < nchunks; ++c) {
     const int64_t T0 = c * tc, tn = std::min(tc, ntriads - T0);
     DiffParams p{};
@@ -193,22 +190,20 @@ int prisim_cphase_diff(prisim_ctx* ctx, const double* in_mean, const double* in_
     p.nruns = (ncomb + kRun - 1) / kRun;
     const int64_t total = n0 * p.nruns * tn * nchan;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((total + kThreads - 1) / kThreads, kMaxBlocks));
-    HIPCHK(ctx, hipEventRecord(st.k0[0], s));
+    if (int rc = st.open(ctx, 0)) return rc;
     hipLaunchKernelGGL(k_cpdiff, dim3((unsigned)blocks), dim3(kThreads), 0, s, p);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(st.k1[0], s));
+    if (int rc = st.close(ctx, 0)) return rc;
     for (int o = 0; o < 8; ++o) {
       HIPCHK(ctx, copy_rows(static_cast<char*>(host_out[o]) + (size_t)(T0 * nchan) * es[o], (size_t)row_elems * es[o], d_out[o],
                             (size_t)(tn * nchan) * es[o], (size_t)(tn * nchan) * es[o], rows_out, hipMemcpyDeviceToHost, s));
       download_bytes += rows_out * tn * nchan * (int64_t)es[o];
     }
-    HIPCHK(ctx, hipStreamSynchronize(s));           // the chunk's buffers are reused by the next one
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, st.k0[0], st.k1[0]) == hipSuccess) kernel_ms += ms;
+    if (int rc = st.drain(ctx)) return rc;          // the chunk's buffers are reused by the next one
   }
   if (stats) {
     stats->wall_ms = wall_ms_since(wall0);
-    stats->kernel_ms = kernel_ms;
+    stats->kernel_ms = st.kernel_ms;
     stats->elements = rows_out * row_elems;
     stats->chunks = nchunks;
     stats->chunk_triads = tc;

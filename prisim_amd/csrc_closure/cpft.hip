@@ -267,9 +267,8 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
   if ((w_lag && !lag_kernel) || (lag_res && !lag_kernel_res)) return fail(ctx, PRISIM_EINVAL, "an output is NULL");
   if (!(in_over || in_res || w_lag)) return fail(ctx, PRISIM_EINVAL, "nothing requested: no input and no lag kernel");
   if (route < PRISIM_CPFT_AUTO || route > PRISIM_CPFT_ROCFFT) return fail(ctx, PRISIM_EINVAL, "unknown route");
-  int logm = 0;
-  while ((int64_t(1) << logm) < m) ++logm;
-  const bool pow2 = (int64_t(1) << logm) == m;
+  bool pow2;
+  const int logm = ceil_log2(m, pow2);
   if (route == PRISIM_CPFT_FUSED && !pow2)
     return fail(ctx, PRISIM_EINVAL, "the fused route takes a power-of-two m; got m = " + std::to_string(m));
   std::vector<int32_t> rs_in;
@@ -277,7 +276,7 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
   if (int rc = build_resample_tables(ctx, nres, m, nchan, df, nmap, map_out, map_in, map_w, rs_in, rs_c, rtw)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int lds_max = 0;
-  HIPCHK(ctx, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  if (int rc = lds_limit(ctx, lds_max)) return rc;
 
   const bool has_w = w != nullptr;
   const size_t fused_row = (size_t)m * 16 + (size_t)std::max<int64_t>(m / 2, 1) * 16 + group_lds(1, (int)nchan, has_w);
@@ -332,27 +331,28 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
   }
   const int64_t row_bytes = nstreamed * nchan * 16 + (has_w ? nchan * 8 : 0) +
                             (int64_t)nwin * (npass_over * m * 16 * (fused ? 1 : 2) + npass_res * nres * 16);
-  const int64_t budget = budget_or_default(budget_bytes);
-  const int64_t tc = std::max<int64_t>(1, std::min<int64_t>(rows, budget / (kMaxStreams * std::max<int64_t>(row_bytes, 1))));
-  const int64_t nchunks = (rows + tc - 1) / tc, last = rows - (nchunks - 1) * tc;
-  const int nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
+  const Chunks ch = plan_chunks(rows, row_bytes, budget_bytes, kMaxStreams);
+  const int64_t tc = ch.size, nchunks = ch.count;
+  const int nstreams = ch.nstreams;
 
+  // the tables go up on stream 0 as they are allocated
   Work wk;
   Streams& st = wk.st;
   if (int rc = st.create(ctx, nstreams, true)) return rc;
+  hipStream_t s0 = st.s[0];
   double *d_wts, *d_vs = nullptr;
   int32_t *d_rsn, *d_rsk, *d_rsin;
   double2 *d_rsc, *d_rtw;
-  DEV_ALLOC(ctx, wk.dev, d_wts, (size_t)nwin * nchan * 8);
-  if (vscale) DEV_ALLOC(ctx, wk.dev, d_vs, (size_t)nwin * n0 * 8);
-  DEV_ALLOC(ctx, wk.dev, d_rsn, rs_n.size() * 4);
-  DEV_ALLOC(ctx, wk.dev, d_rsk, rs_k.size() * 4);
-  DEV_ALLOC(ctx, wk.dev, d_rsin, rs_in.size() * 4);
-  DEV_ALLOC(ctx, wk.dev, d_rsc, rs_c.size() * 8);
-  DEV_ALLOC(ctx, wk.dev, d_rtw, rtw.size() * 8);
+  DEV_UPLOAD(ctx, wk.dev, d_wts, wts, (size_t)nwin * nchan, s0);
+  if (vscale) DEV_UPLOAD(ctx, wk.dev, d_vs, vscale, (size_t)nwin * n0, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_rsn, rs_n, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_rsk, rs_k, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_rsin, rs_in, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_rsc, rs_c, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_rtw, rtw, s0);
   double2* d_bcast[kMaxIn] = {};
   for (int i = 0; i < nin; ++i)
-    if (!chunked[i]) DEV_ALLOC(ctx, wk.dev, d_bcast[i], (size_t)in_rows[i] * nchan * 16);
+    if (!chunked[i]) DEV_UPLOAD(ctx, wk.dev, d_bcast[i], inputs[i], (size_t)in_rows[i] * nchan * 2, s0);
   double2 *d_in[kMaxStreams][kMaxIn] = {}, *d_over[kMaxStreams][kMaxPass] = {}, *d_res[kMaxStreams][kMaxPass] = {}, *d_fbuf[kMaxStreams] = {};
   double* d_w[kMaxStreams] = {};
   const int fpass0 = in_over ? 0 : nin;
@@ -379,21 +379,11 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
     std::vector<std::pair<bool, size_t>> plans;
     if (npass_over) {
       plans.push_back({true, (size_t)npass_over * nwin * tc});
-      plans.push_back({true, (size_t)npass_over * nwin * last});
+      plans.push_back({true, (size_t)npass_over * nwin * ch.last});
     }
     if (lone_lag) plans.push_back({true, (size_t)nwin});
     if (int rc = wk.fft.create(ctx, wk.dev, (size_t)m, plans, st.s, nstreams)) return rc;
   }
-  hipStream_t s0 = st.s[0];
-  HIPCHK(ctx, hipMemcpyAsync(d_wts, wts, (size_t)nwin * nchan * 8, hipMemcpyHostToDevice, s0));
-  if (vscale) HIPCHK(ctx, hipMemcpyAsync(d_vs, vscale, (size_t)nwin * n0 * 8, hipMemcpyHostToDevice, s0));
-  HIPCHK(ctx, hipMemcpyAsync(d_rsn, rs_n.data(), rs_n.size() * 4, hipMemcpyHostToDevice, s0));
-  HIPCHK(ctx, hipMemcpyAsync(d_rsk, rs_k.data(), rs_k.size() * 4, hipMemcpyHostToDevice, s0));
-  HIPCHK(ctx, hipMemcpyAsync(d_rsin, rs_in.data(), rs_in.size() * 4, hipMemcpyHostToDevice, s0));
-  HIPCHK(ctx, hipMemcpyAsync(d_rsc, rs_c.data(), rs_c.size() * 8, hipMemcpyHostToDevice, s0));
-  HIPCHK(ctx, hipMemcpyAsync(d_rtw, rtw.data(), rtw.size() * 8, hipMemcpyHostToDevice, s0));
-  for (int i = 0; i < nin; ++i)
-    if (!chunked[i]) HIPCHK(ctx, hipMemcpyAsync(d_bcast[i], inputs[i], (size_t)in_rows[i] * nchan * 16, hipMemcpyHostToDevice, s0));
   HIPCHK(ctx, hipStreamSynchronize(s0));            // the other stream starts behind the tables
   const int64_t tables = (int64_t)nwin * nchan * 8 + (vscale ? (int64_t)nwin * n0 * 8 : 0) + (int64_t)nwin * 4 + (int64_t)nwin * nr * 4 +
                          nr * (8 + 32 + 16);
@@ -416,11 +406,10 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
   base.fpass0 = fpass0;
   base.rs_n = d_rsn; base.rs_k = d_rsk; base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw;
   const size_t lds_rows = rows_lds(R), lds_res = res_lds(Rr);
-  if (any_over && lds_rows > 65536)
-    HIPCHK(ctx, hipFuncSetAttribute(fused ? (const void*)k_cpft_rows<true> : (const void*)k_cpft_rows<false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows));
-  if (any_res && lds_res > 65536)
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)k_cpft_resample, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_res));
+  if (any_over)
+    if (int rc = fused ? allow_lds(ctx, k_cpft_rows<true>, lds_rows) : allow_lds(ctx, k_cpft_rows<false>, lds_rows)) return rc;
+  if (any_res)
+    if (int rc = allow_lds(ctx, k_cpft_resample, lds_res)) return rc;
 
   // the kernels of one set of rows on stream s: P holds the rows, the passes and their buffers
   auto launch = [&](FtParams P, int si, size_t batch) -> int {
@@ -456,12 +445,11 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
     return PRISIM_OK;
   };
 
-  double kernel_ms = 0.0;
   int64_t upload = tables + bcast_bytes, download = 0;
   for (int64_t c = 0; c < nchunks; ++c) {
     const int si = (int)(c % nstreams);
     hipStream_t s = st.s[si];
-    if (int rc = st.harvest(ctx, si, kernel_ms)) return rc;
+    if (int rc = st.harvest(ctx, si)) return rc;
     const int64_t r0 = c * tc, rn = std::min(tc, rows - r0);
     for (int i = 0; i < nin; ++i)
       if (chunked[i]) HIPCHK(ctx, hipMemcpyAsync(d_in[si][i], inputs[i] + 2 * (size_t)r0 * nchan, (size_t)rn * nchan * 16, hipMemcpyHostToDevice, s));
@@ -477,7 +465,7 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
       P.res[p] = d_res[si][p];
     }
     P.fbuf = d_fbuf[si];
-    HIPCHK(ctx, hipEventRecord(st.k0[si], s));
+    if (int rc = st.open(ctx, si)) return rc;
     if (int rc = launch(P, si, (size_t)npass_over * nwin * rn)) return rc;
     if (lone_lag && c == 0) {
       FtParams L = base;
@@ -486,8 +474,7 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
       L.over[0] = d_lagk; L.res[0] = d_lagk_res; L.fbuf = d_lagk_f; L.fpass0 = 0;
       if (int rc = launch(L, si, (size_t)nwin)) return rc;
     }
-    HIPCHK(ctx, hipEventRecord(st.k1[si], s));
-    st.timed[si] = true;
+    if (int rc = st.close(ctx, si)) return rc;
     // a chunk's [nwin][rn][len] into the caller's [nwin][rows][len]
     auto fetch = [&](double* host, const double2* dev, int64_t len) -> int {
       HIPCHK(ctx, copy_rows(host + 2 * (size_t)r0 * len, (size_t)rows * len * 16, dev, (size_t)rn * len * 16, (size_t)rn * len * 16, (size_t)nwin,
@@ -508,13 +495,10 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
       download += (int64_t)nwin * (m + nres) * 16;
     }
   }
-  for (int i = 0; i < nstreams; ++i) {
-    HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
-    if (int rc = st.harvest(ctx, i, kernel_ms)) return rc;
-  }
+  if (int rc = st.drain(ctx)) return rc;
   if (stats) {
     stats->wall_ms = wall_ms_since(wall0);
-    stats->kernel_ms = kernel_ms;
+    stats->kernel_ms = st.kernel_ms;
     stats->rows = rows;
     stats->chunks = nchunks;
     stats->chunk_rows = tc;

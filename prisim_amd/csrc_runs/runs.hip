@@ -232,9 +232,8 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
   for (int i = 0; i < 3; ++i)
     if ((bp && bp_strides[i] < 0) || (wts && wts_strides[i] < 0)) return fail(ctx, PRISIM_EINVAL, "weight strides must be >= 0");
   if (route < PRISIM_RUNS_AUTO || route > PRISIM_RUNS_ROCFFT) return fail(ctx, PRISIM_EINVAL, "unknown route");
-  int logm = 0;
-  while ((int64_t(1) << logm) < m) ++logm;
-  const bool pow2 = (int64_t(1) << logm) == m;
+  bool pow2;
+  const int logm = ceil_log2(m, pow2);
   const bool resample = out_mode == PRISIM_RUNS_RESAMPLE;
   if (route == PRISIM_RUNS_FUSED && !pow2 && !resample)
     return fail(ctx, PRISIM_EINVAL, "the fused route takes power-of-two m; got m = " + std::to_string(m));
@@ -269,7 +268,7 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
 
   // snapshot tile, LDS and chunking
   int lds_max = 0;
-  HIPCHK(ctx, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  if (int rc = lds_limit(ctx, lds_max)) return rc;
   const int64_t tw_bytes = 16 * std::max<int64_t>(m / 2, 1);
   const int64_t row_bytes = 16 * (resample ? nout : m);
   int64_t tile = 1;
@@ -282,26 +281,30 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
   const int64_t out_pair = (int64_t)nwin * nout * nt * 16;
   const int64_t fbuf_pair = rt == PRISIM_RUNS_ROCFFT ? (int64_t)nwin * nt * m * 16 : 0;
   const int64_t per_pair = in_pair + out_pair + fbuf_pair;
-  const int64_t budget = budget_or_default(budget_bytes);
-  int64_t pc = std::max<int64_t>(1, std::min<int64_t>(P, budget / (kMaxStreams * per_pair)));
-  pc = std::min<int64_t>(pc, ((int64_t)1 << 31) / std::max<int64_t>(ntiles, 1) - 1);      // grid x of the tiled kernels
-  const int64_t nchunks = (P + pc - 1) / pc;
-  const int nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
+  const int64_t fit = plan_chunks(P, per_pair, budget_bytes, kMaxStreams).size;
+  const int64_t grid_max = ((int64_t)1 << 31) / std::max<int64_t>(ntiles, 1) - 1;          // grid x of the tiled kernels
+  const Chunks ch = chunks_of(P, std::min(fit, grid_max), kMaxStreams);
+  const int64_t pc = ch.size, nchunks = ch.count;
+  const int nstreams = ch.nstreams;
 
+  // the tables go up on stream 0 as they are allocated; stream 1 waits for them
   Work wk;
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, nstreams, false)) return rc;
+  hipStream_t s0 = st.s[0];
   const int64_t bp_n = bp ? span_of(bp_strides, nbl, nchan, nt) : 0, wts_n = wts ? span_of(wts_strides, nbl, nchan, nt) : 0;
   double *d_bp = nullptr, *d_wts = nullptr, *d_win = nullptr;
   int32_t *d_rsin = nullptr, *d_klist = nullptr, *d_kofs = nullptr;
   double2 *d_rsc = nullptr, *d_rtw = nullptr;
-  if (bp) DEV_ALLOC(ctx, wk.dev, d_bp, bp_n * 8);
-  if (wts) DEV_ALLOC(ctx, wk.dev, d_wts, wts_n * 8);
-  if (win) DEV_ALLOC(ctx, wk.dev, d_win, (size_t)nwin * nchan * 8);
+  if (bp) DEV_UPLOAD(ctx, wk.dev, d_bp, bp, (size_t)bp_n, s0);
+  if (wts) DEV_UPLOAD(ctx, wk.dev, d_wts, wts, (size_t)wts_n, s0);
+  if (win) DEV_UPLOAD(ctx, wk.dev, d_win, win, (size_t)nwin * nchan, s0);
   if (resample) {
-    DEV_ALLOC(ctx, wk.dev, d_rsin, rs_in.size() * 4);
-    DEV_ALLOC(ctx, wk.dev, d_rsc, rs_c.size() * 8);
-    DEV_ALLOC(ctx, wk.dev, d_rtw, rtw.size() * 8);
-    DEV_ALLOC(ctx, wk.dev, d_klist, std::max<size_t>(klist.size(), 1) * 4);
-    DEV_ALLOC(ctx, wk.dev, d_kofs, kofs.size() * 4);
+    DEV_UPLOAD(ctx, wk.dev, d_rsin, rs_in, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_rsc, rs_c, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_rtw, rtw, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_klist, klist, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_kofs, kofs, s0);
   }
   void* d_in[kMaxStreams] = {};
   double2* d_out[kMaxStreams] = {};
@@ -311,25 +314,9 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
     DEV_ALLOC(ctx, wk.dev, d_out[i], pc * out_pair);
     if (fbuf_pair) DEV_ALLOC(ctx, wk.dev, d_fbuf[i], pc * fbuf_pair);
   }
-  Streams& st = wk.st;
-  if (int rc = st.create(ctx, nstreams, false)) return rc;
   if (rt == PRISIM_RUNS_ROCFFT) {
     const size_t lines = (size_t)nwin * (size_t)nt;
-    if (int rc = wk.fft.create(ctx, wk.dev, (size_t)m, {{true, lines * (size_t)pc}, {true, lines * (size_t)(P - (nchunks - 1) * pc)}}, st.s, nstreams))
-      return rc;
-  }
-
-  // the tables on stream 0; stream 1 waits for them
-  hipStream_t s0 = st.s[0];
-  if (bp) HIPCHK(ctx, hipMemcpyAsync(d_bp, bp, bp_n * 8, hipMemcpyHostToDevice, s0));
-  if (wts) HIPCHK(ctx, hipMemcpyAsync(d_wts, wts, wts_n * 8, hipMemcpyHostToDevice, s0));
-  if (win) HIPCHK(ctx, hipMemcpyAsync(d_win, win, (size_t)nwin * nchan * 8, hipMemcpyHostToDevice, s0));
-  if (resample) {
-    HIPCHK(ctx, hipMemcpyAsync(d_rsin, rs_in.data(), rs_in.size() * 4, hipMemcpyHostToDevice, s0));
-    HIPCHK(ctx, hipMemcpyAsync(d_rsc, rs_c.data(), rs_c.size() * 8, hipMemcpyHostToDevice, s0));
-    HIPCHK(ctx, hipMemcpyAsync(d_rtw, rtw.data(), rtw.size() * 8, hipMemcpyHostToDevice, s0));
-    if (!klist.empty()) HIPCHK(ctx, hipMemcpyAsync(d_klist, klist.data(), klist.size() * 4, hipMemcpyHostToDevice, s0));
-    HIPCHK(ctx, hipMemcpyAsync(d_kofs, kofs.data(), kofs.size() * 4, hipMemcpyHostToDevice, s0));
+    if (int rc = wk.fft.create(ctx, wk.dev, (size_t)m, {{true, lines * (size_t)pc}, {true, lines * (size_t)ch.last}}, st.s, nstreams)) return rc;
   }
   HIPCHK(ctx, hipStreamSynchronize(s0));            // the tables are host vectors of this call and caller memory
 
@@ -343,10 +330,10 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
   base.nbl = nbl; base.p0 = 0; base.pc = 0; base.s = s; base.factor = factor;
   base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw; base.klist = d_klist; base.kofs = d_kofs;
   base.out = nullptr; base.fbuf = nullptr;
-  if (lds > 65536) {
-    if (rt == PRISIM_RUNS_FUSED) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_runs_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (rt == PRISIM_RUNS_DIRECT) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_runs_resample, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
+  if (rt == PRISIM_RUNS_FUSED)
+    if (int rc = allow_lds(ctx, k_runs_fused, lds)) return rc;
+  if (rt == PRISIM_RUNS_DIRECT)
+    if (int rc = allow_lds(ctx, k_runs_resample, lds)) return rc;
 
   for (int64_t c = 0; c < nchunks; ++c) {
     const int i = (int)(c % nstreams);
@@ -380,7 +367,7 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
       HIPCHK(ctx, hipMemcpyAsync(out + 2 * (((size_t)w * P + p0) * nout * nt), d_out[i] + (size_t)w * blk, blk * 16,
                                  hipMemcpyDeviceToHost, sc));
   }
-  for (int i = 0; i < nstreams; ++i) HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
+  if (int rc = st.drain(ctx)) return rc;
   if (stats) {
     stats->wall_ms = wall_ms_since(wall0);
     stats->pairs = P;
@@ -406,13 +393,14 @@ int prisim_runs_power(prisim_ctx* ctx, int64_t nf, int64_t inner, const void* v1
   const int64_t n = nf * inner;
   const int64_t esz = is_c64 ? 8 : 16;
   const int64_t per = esz * (v2 ? 2 : 1) + 8;
-  const int64_t budget = budget_or_default(budget_bytes);
-  const int64_t ce = std::max<int64_t>(1, std::min<int64_t>(n, budget / (kMaxStreams * per)));
-  const int64_t nchunks = (n + ce - 1) / ce;
-  const int nstreams = (int)std::min<int64_t>(kMaxStreams, nchunks);
+  const Chunks ch = plan_chunks(n, per, budget_bytes, kMaxStreams);
+  const int64_t ce = ch.size, nchunks = ch.count;
+  const int nstreams = ch.nstreams;
   Work wk;
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, nstreams, false)) return rc;
   double* d_f;
-  DEV_ALLOC(ctx, wk.dev, d_f, nf * 8);
+  DEV_UPLOAD(ctx, wk.dev, d_f, factor, (size_t)nf, st.s[0]);
   void* d_a[kMaxStreams] = {};
   void* d_b[kMaxStreams] = {};
   double* d_o[kMaxStreams] = {};
@@ -421,9 +409,6 @@ int prisim_runs_power(prisim_ctx* ctx, int64_t nf, int64_t inner, const void* v1
     if (v2) DEV_ALLOC(ctx, wk.dev, d_b[i], ce * esz);
     DEV_ALLOC(ctx, wk.dev, d_o[i], ce * 8);
   }
-  Streams& st = wk.st;
-  if (int rc = st.create(ctx, nstreams, false)) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(d_f, factor, nf * 8, hipMemcpyHostToDevice, st.s[0]));
   HIPCHK(ctx, hipStreamSynchronize(st.s[0]));
   for (int64_t c = 0; c < nchunks; ++c) {
     const int i = (int)(c % nstreams);
@@ -441,7 +426,7 @@ int prisim_runs_power(prisim_ctx* ctx, int64_t nf, int64_t inner, const void* v1
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out + e0, d_o[i], en * 8, hipMemcpyDeviceToHost, sc));
   }
-  for (int i = 0; i < nstreams; ++i) HIPCHK(ctx, hipStreamSynchronize(st.s[i]));
+  if (int rc = st.drain(ctx)) return rc;
   if (stats) {
     stats->wall_ms = wall_ms_since(wall0);
     stats->pairs = n;

@@ -233,12 +233,11 @@ int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_
     if (t0 < 0 || t0 + nt > ctx->nt_max) return fail(ctx, PRISIM_EINVAL, "resident slots out of range");
   }
   if (route < PRISIM_SUBBAND_AUTO || route > PRISIM_SUBBAND_ROCFFT) return fail(ctx, PRISIM_EINVAL, "unknown route");
-  int logm = 0;
-  while ((int64_t(1) << logm) < m) ++logm;
-  const bool pow2 = (int64_t(1) << logm) == m;
+  bool pow2;
+  const int logm = ceil_log2(m, pow2);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int lds_max = 0;
-  HIPCHK(ctx, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  if (int rc = lds_limit(ctx, lds_max)) return rc;
   const int lf = lds_fused(nchan, m, nres), lp = lds_prepare(nchan, nres);
   const bool fused_ok = pow2 && lf <= lds_max;
   if (route == PRISIM_SUBBAND_FUSED && !fused_ok)
@@ -317,14 +316,14 @@ int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_
   HIPCHK(ctx, hipEventRecord(ev.e[1], ctx->stream));
   if (nrows > 0) {
     if (fused) {
-      if (lds > 65536) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_sb_fused, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      if (int rc = allow_lds(ctx, k_sb_fused, lds)) return rc;
       for (int64_t r0 = 0; r0 < nrows; r0 += kMaxGridRows) {
         P.row0 = r0;
         hipLaunchKernelGGL(k_sb_fused, dim3((unsigned)std::min(kMaxGridRows, nrows - r0)), dim3(kThreads), (size_t)lds, ctx->stream, P);
         HIPCHK(ctx, hipGetLastError());
       }
     } else {
-      if (lds > 65536) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_sb_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      if (int rc = allow_lds(ctx, k_sb_prepare, lds)) return rc;
       for (int64_t r0 = 0; r0 < nrows; r0 += kMaxGridRows) {
         P.row0 = r0;
         hipLaunchKernelGGL(k_sb_prepare, dim3((unsigned)std::min(kMaxGridRows, nrows - r0)), dim3(kThreads), (size_t)lds, ctx->stream, P);

@@ -1,0 +1,147 @@
+"""The helpers the add-on wrappers of prisim_amd/_abi.py share: _stats_dict against the dict each wrapper used to write out by hand
+(keys, Python types and values), the want bits, the route codes and the resample map.  No library is loaded."""
+import numpy as NP
+import pytest
+
+from prisim_amd import _abi as A
+from prisim_amd import dsp_readings
+
+F, I, B, S = float, int, bool, str
+
+# per stats struct: the call the wrapper makes, the dict it used to build by hand, and the keys with their types in order ('route' and
+# 'phase_route' are typed by the case: a name where the table has the code, the code itself (route) or None (phase_route) where not)
+CASES = {
+    'clean': (A.PrisimCleanStats, lambda st: A._stats_dict(st, kernel_in_lds=bool),
+              lambda st: {'device_ms': st.device_ms, 'clean_ms': st.clean_ms, 'sum_iter': int(st.sum_iter), 'rows': int(st.rows),
+                          'waves_per_block': int(st.waves_per_block), 'kernel_in_lds': bool(st.kernel_in_lds),
+                          'lds_bytes': int(st.lds_bytes)},
+              [('device_ms', F), ('clean_ms', F), ('sum_iter', I), ('rows', I), ('waves_per_block', I), ('kernel_in_lds', B),
+               ('lds_bytes', I)], None),
+    'subband': (A.PrisimSubbandStats, lambda st: A._stats_dict(st, route=A.SUBBAND_ROUTES),
+                lambda st: {'device_ms': st.device_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows),
+                            'route': A.SUBBAND_ROUTES.get(st.route, st.route), 'lds_bytes': int(st.lds_bytes)},
+                [('device_ms', F), ('kernel_ms', F), ('rows', I), ('route', None), ('lds_bytes', I)], A.SUBBAND_ROUTES),
+    'runs': (A.PrisimRunsStats, lambda st: A._stats_dict(st, route=A.RUNS_ROUTES),
+             lambda st: {'wall_ms': st.wall_ms, 'pairs': int(st.pairs), 'chunks': int(st.chunks), 'chunk_pairs': int(st.chunk_pairs),
+                         'route': A.RUNS_ROUTES.get(st.route, st.route), 'streams': int(st.streams), 'tile': int(st.tile),
+                         'lds_bytes': int(st.lds_bytes)},
+             [('wall_ms', F), ('pairs', I), ('chunks', I), ('chunk_pairs', I), ('route', None), ('streams', I), ('tile', I),
+              ('lds_bytes', I)], A.RUNS_ROUTES),
+    'closure': (A.PrisimClosureStats, lambda st: dict(A._stats_dict(st, route=A.CLOSURE_ROUTES), resident=True),
+                lambda st: {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'triads': int(st.triads), 'chunks': int(st.chunks),
+                            'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes),
+                            'download_bytes': int(st.download_bytes), 'route': A.CLOSURE_ROUTES.get(st.route, st.route),
+                            'streams': int(st.streams), 'tile': int(st.tile), 'lds_bytes': int(st.lds_bytes), 'resident': True},
+                [('wall_ms', F), ('kernel_ms', F), ('triads', I), ('chunks', I), ('chunk_triads', I), ('kernel_bytes', I),
+                 ('download_bytes', I), ('route', None), ('streams', I), ('tile', I), ('lds_bytes', I), ('resident', B)],
+                A.CLOSURE_ROUTES),
+    'cpdelay': (A.PrisimCpdelayStats, lambda st: A._stats_dict(st, route=A.CPDELAY_ROUTES, phase_route=A.CLOSURE_ROUTES.get),
+                lambda st: {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows), 'chunks': int(st.chunks),
+                            'chunk_rows': int(st.chunk_rows), 'upload_bytes': int(st.upload_bytes),
+                            'download_bytes': int(st.download_bytes), 'route': A.CPDELAY_ROUTES.get(st.route, st.route),
+                            'phase_route': A.CLOSURE_ROUTES.get(st.phase_route), 'streams': int(st.streams), 'tile': int(st.tile),
+                            'lds_bytes': int(st.lds_bytes)},
+                [('wall_ms', F), ('kernel_ms', F), ('rows', I), ('chunks', I), ('chunk_rows', I), ('upload_bytes', I),
+                 ('download_bytes', I), ('route', None), ('phase_route', None), ('streams', I), ('tile', I), ('lds_bytes', I)],
+                A.CPDELAY_ROUTES),
+    'cpbins': (A.PrisimCpbinsStats, lambda st: A._stats_dict(st, rename={'resident_in': 'resident'}, resident_in=bool),
+               lambda st: {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements), 'chunks': int(st.chunks),
+                           'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes),
+                           'upload_bytes': int(st.upload_bytes), 'download_bytes': int(st.download_bytes), 'max_bin': int(st.max_bin),
+                           'resident': bool(st.resident_in)},
+               [('wall_ms', F), ('kernel_ms', F), ('elements', I), ('chunks', I), ('chunk_triads', I), ('kernel_bytes', I),
+                ('upload_bytes', I), ('download_bytes', I), ('max_bin', I), ('resident', B)], None),
+    'cpdiff': (A.PrisimCpdiffStats, lambda st: A._stats_dict(st, rename={'resident_in': 'resident'}, resident_in=bool),
+               lambda st: {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements), 'chunks': int(st.chunks),
+                           'chunk_triads': int(st.chunk_triads), 'kernel_bytes': int(st.kernel_bytes),
+                           'upload_bytes': int(st.upload_bytes), 'download_bytes': int(st.download_bytes),
+                           'resident': bool(st.resident_in), 'ncomb': int(st.ncomb)},
+               [('wall_ms', F), ('kernel_ms', F), ('elements', I), ('chunks', I), ('chunk_triads', I), ('kernel_bytes', I),
+                ('upload_bytes', I), ('download_bytes', I), ('resident', B), ('ncomb', I)], None),
+    'cpft': (A.PrisimCpftStats, lambda st: A._stats_dict(st, route=A.CPFT_ROUTES),
+             lambda st: {'wall_ms': st.wall_ms, 'kernel_ms': st.kernel_ms, 'rows': int(st.rows), 'chunks': int(st.chunks),
+                         'chunk_rows': int(st.chunk_rows), 'row_bytes': int(st.row_bytes), 'kernel_bytes': int(st.kernel_bytes),
+                         'upload_bytes': int(st.upload_bytes), 'download_bytes': int(st.download_bytes),
+                         'route': A.CPFT_ROUTES.get(st.route, st.route), 'streams': int(st.streams), 'group_rows': int(st.group_rows),
+                         'lds_bytes': int(st.lds_bytes)},
+             [('wall_ms', F), ('kernel_ms', F), ('rows', I), ('chunks', I), ('chunk_rows', I), ('row_bytes', I), ('kernel_bytes', I),
+              ('upload_bytes', I), ('download_bytes', I), ('route', None), ('streams', I), ('group_rows', I), ('lds_bytes', I)],
+             A.CPFT_ROUTES),
+    'gains': (A.PrisimGainsStats, lambda st: A._stats_dict(st),
+              lambda st: {'device_ms': st.device_ms, 'kernel_ms': st.kernel_ms, 'elements': int(st.elements)},
+              [('device_ms', F), ('kernel_ms', F), ('elements', I)], None),
+}
+
+
+def filled(struct, **over):
+    """The struct with distinct non-zero values: k + 1.5 in the k-th double, k + 2 in the k-th integer."""
+    st = struct()
+    for k, (name, ctype) in enumerate(struct._fields_):
+        setattr(st, name, k + 1.5 if ctype is A.C.c_double else k + 2)
+    for name, v in over.items():
+        setattr(st, name, v)
+    return st
+
+
+def route_cases():
+    for name, (struct, _, _, _, routes) in CASES.items():
+        if routes is None:
+            yield name, {}
+            continue
+        for code in list(routes) + [99]:                  # every named route, and a code the table lacks
+            if name == 'cpdelay':
+                for pcode in list(A.CLOSURE_ROUTES) + [-1]:
+                    yield name, {'route': code, 'phase_route': pcode}
+            else:
+                yield name, {'route': code}
+
+
+@pytest.mark.parametrize('name,over', list(route_cases()), ids=lambda v: v if isinstance(v, str) else '-'.join(str(x) for x in v.values()))
+def test_stats_dict_is_the_handwritten_dict(name, over):
+    struct, call, literal, keys, routes = CASES[name]
+    st = filled(struct, **over)
+    got, want = call(st), literal(st)
+    assert list(got) == [k for k, _ in keys], 'keys and their order'
+    assert 'reserved_' not in got
+    assert got == want
+    for k, typ in keys:
+        assert type(got[k]) is type(want[k]), k
+        if typ is not None:
+            assert type(got[k]) is typ, k
+    if routes is not None:
+        assert type(got['route']) is (S if over['route'] in routes else I)
+    if 'phase_route' in over:
+        assert got['phase_route'] is None if over['phase_route'] not in A.CLOSURE_ROUTES else type(got['phase_route']) is S
+    values = [v for v in got.values() if type(v) in (I, F)]
+    assert len(set(values)) == len(values) and all(values), 'the fill is distinct and non-zero, so a swapped field shows'
+
+
+def test_every_stats_struct_is_covered():
+    structs = {v for k, v in vars(A).items() if k.startswith('Prisim') and k.endswith('Stats') and k != 'PrisimCommStats'}
+    assert structs == {c[0] for c in CASES.values()}
+
+
+def test_want_bits_and_route_codes():
+    assert A._want_bits((), A.CPBINS_WANT) == 0
+    assert A._want_bits(('wts', 'mad', 'wts'), A.CPBINS_WANT) == 65
+    with pytest.raises(KeyError):
+        A._want_bits(('wts', 'nope'), A.CPBINS_WANT)
+    for routes, auto in ((A.SUBBAND_ROUTES, A.PRISIM_SUBBAND_AUTO), (A.CLOSURE_ROUTES, A.PRISIM_CLOSURE_AUTO),
+                         (A.CPDELAY_ROUTES, A.PRISIM_CPDELAY_AUTO), (A.CPFT_ROUTES, A.PRISIM_CPFT_AUTO)):
+        assert A._route_code('auto', routes) == auto == -1
+        for code, rname in routes.items():
+            assert A._route_code(rname, routes) == code
+        with pytest.raises(KeyError):
+            A._route_code('nope', routes)
+    with pytest.raises(KeyError):
+        A._route_code('direct', A.CPFT_ROUTES)
+
+
+def test_resample_map_helper():
+    assert A._resample_map(False, 16, 8) == (0, None, None, None)
+    assert A._resample_map(0, 16, 8) == (0, None, None, None)
+    nmap, mo, mi, mw = A._resample_map(True, 16, 6)
+    ref = dsp_readings.resample_map(16, 6)
+    assert nmap == len(ref[0]) > 0
+    for got, want in zip((mo, mi, mw), ref):
+        assert got.flags['C_CONTIGUOUS'] and got.dtype == NP.asarray(want).dtype and NP.array_equal(got, want)

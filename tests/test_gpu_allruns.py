@@ -124,6 +124,38 @@ def test_seeded_sweep_through_every_route():
             ctx.runs_transform(NP.ones((1, 1, 8, 1), complex), 1, 8, 1, m=_abi.PRISIM_SUBBAND_MAX_LEN + 1)
 
 
+@pytest.mark.parametrize('m', [16, 12])
+def test_transform_in_three_chunks_is_the_one_chunk_output(m):
+    """Five (run, baseline) pairs in chunks of 2, 2 and 1 on two streams, fused (m = 16) and through rocFFT (m = 12, whose plan for the
+    last chunk has another batch): bit for bit the output of one chunk."""
+    rng = NP.random.default_rng(m)
+    nbl, nchan, nt = 5, 8, 4
+    vis = rng.standard_normal((1, nbl, nchan, nt)) + 1j * rng.standard_normal((1, nbl, nchan, nt))
+    kw = dict(bp=0.5 + rng.uniform(size=(nbl, nchan, nt)), wts=rng.uniform(size=(nbl, nchan, nt)), m=m, scale=m * 1e5)
+    route = 'fused' if m == 16 else 'rocfft'
+    per_pair = nchan * nt * 16 + m * nt * 16 + (m * nt * 16 if route == 'rocfft' else 0)      # input, output, the rocFFT rows
+    with _abi.Context(0) as ctx:
+        one, st1 = ctx.runs_transform(vis, nbl, nchan, nt, **kw)
+        three, st3 = ctx.runs_transform(vis, nbl, nchan, nt, budget_bytes=2 * 2 * per_pair, **kw)
+    assert st1['chunks'] == 1 and st1['route'] == st3['route'] == route
+    assert st3['chunks'] == 3 and st3['chunk_pairs'] == 2 and st3['streams'] == 2
+    assert NP.array_equal(one, three)
+
+
+@pytest.mark.parametrize('cross', [False, True])
+def test_power_in_three_chunks_is_the_one_chunk_output(cross):
+    """Five elements in chunks of 2, 2 and 1 on two streams: bit for bit the output of one chunk."""
+    rng = NP.random.default_rng(31)
+    v1 = rng.standard_normal(5) + 1j * rng.standard_normal(5)
+    v2 = rng.standard_normal(5) + 1j * rng.standard_normal(5) if cross else None
+    per = 16 * (2 if cross else 1) + 8                                                       # the inputs and the output
+    with _abi.Context(0) as ctx:
+        one, st1 = ctx.runs_power(v1, v2, 3e7, cross=cross)
+        three, st3 = ctx.runs_power(v1, v2, 3e7, cross=cross, budget_bytes=2 * 2 * per)
+    assert st1['chunks'] == 1 and st3['chunks'] == 3 and st3['chunk_pairs'] == 2 and st3['streams'] == 2
+    assert NP.array_equal(one, three) and NP.array_equal(one, CK.power(v1, v2, 3e7, cross))
+
+
 def test_a_selection_map_with_three_entries_for_one_bin_is_refused(monkeypatch):
     from prisim_amd import dsp_readings as D
     monkeypatch.setattr(D, 'resample_map', lambda m, n: (NP.zeros(3, dtype=NP.int64), NP.arange(3, dtype=NP.int64), NP.ones(3)))

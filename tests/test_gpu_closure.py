@@ -202,6 +202,17 @@ def test_filter_on_the_shortest_rows_and_one_snapshot_past_the_tile(ctx, nchan, 
     _check_phases(ph, NP.angle(own), own, 'short rows %s' % route)
 
 
+def test_three_chunks_are_the_one_chunk_output(ctx):
+    """Five triads in chunks of 2, 2 and 1 on two streams: triplets and phases bit for bit those of one chunk."""
+    rng = NP.random.default_rng(77)
+    nbl, nchan, nt, ntriads = 5, 8, 4, 5
+    x, bp, wts, legs, conj = _random_case(rng, nbl, nchan, nt, ntriads)
+    trip1, ph1, st1 = ctx.closure_phase(x, legs, conj, bp * wts)
+    trip3, ph3, st3 = ctx.closure_phase(x, legs, conj, bp * wts, budget_bytes=2 * 2 * nchan * nt * (3 * 16 + 8))
+    assert st1['chunks'] == 1 and st3['chunks'] == 3 and st3['chunk_triads'] == 2 and st3['streams'] == 2
+    assert NP.array_equal(trip1, trip3) and NP.array_equal(ph1, ph3)
+
+
 def test_entry_rejects_bad_input(ctx):
     rng = NP.random.default_rng(1)
     x, bp, wts, legs, conj = _random_case(rng, 4, 8, 2, 3)

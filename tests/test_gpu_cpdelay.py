@@ -146,6 +146,39 @@ def test_spectra_from_a_cube_against_the_reference(ctx):
         assert 'phase' not in out and out['stats']['download_bytes'] == out['res'].nbytes
 
 
+def test_a_cube_in_three_chunks_is_the_one_chunk_output(ctx):
+    """Five triads of an uploaded cube in chunks of 2, 2 and 1 on two streams: phases and spectra bit for bit those of one chunk."""
+    rng = NP.random.default_rng(78)
+    nbl, nchan, nt, ntriads, m, nres, nwin = 5, 8, 4, 5, 16, 6, 2
+    x = rng.standard_normal((nbl, nchan, nt)) + 1j * rng.standard_normal((nbl, nchan, nt))
+    bpw = rng.uniform(0.5, 1.5, (nbl, nchan, nt))
+    legs = rng.integers(0, nbl, (ntriads, 3)).astype(NP.int32)
+    conj = rng.integers(0, 2, (ntriads, 3)).astype(NP.int32)
+    wts = _windows(rng, nwin, nchan)
+    kw = dict(cube=x, legs=legs, conj=conj, bpwts=bpw, nres=nres, want=('over', 'res'), want_phase=True)
+    per_triad = nchan * nt * (3 * 16 + 8) + nwin * nt * (m + nres) * 16         # triplets, phases; the fused route's spectra
+    one = ctx.closure_delay_spectra(wts, m, 1e5, **kw)
+    three = ctx.closure_delay_spectra(wts, m, 1e5, budget_bytes=2 * 2 * per_triad, **kw)
+    st = three['stats']
+    assert one['stats']['chunks'] == 1 and st['route'] == 'fused' and st['phase_route'] == 'direct'
+    assert st['chunks'] == 3 and st['chunk_rows'] == 2 and st['streams'] == 2
+    assert all(NP.array_equal(one[k], three[k]) for k in ('phase', 'over', 'res'))
+
+
+def test_power_in_three_chunks_is_the_one_chunk_output(ctx):
+    """Five spectra in chunks of 2, 2 and 1 on the entry's one stream: every output bit for bit that of one chunk."""
+    rng = NP.random.default_rng(79)
+    n0, nwin, nlags, nt = 5, 2, 16, 4
+    x = rng.standard_normal((n0, nwin, nlags, nt)) + 1j * rng.standard_normal((n0, nwin, nlags, nt))
+    scale = rng.uniform(1e-12, 1e-10, nwin)
+    want = ('individual', 'auto', 'cross')
+    one = ctx.closure_power(x, scale, want=want)
+    three = ctx.closure_power(x, scale, want=want, budget_bytes=2 * nwin * nlags * nt * 24)
+    st = three['stats']
+    assert one['stats']['chunks'] == 1 and st['chunks'] == 3 and st['chunk_rows'] == 2 and st['streams'] == 1
+    assert all(NP.array_equal(one[k], three[k]) for k in want)
+
+
 def test_entry_rejects_bad_input(ctx):
     ph = NP.zeros((2, 8, 3))
     wts = NP.ones((1, 8))

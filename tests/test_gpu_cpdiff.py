@@ -162,6 +162,21 @@ def test_three_chunks_equal_one(ctx, count):
         assert NP.array_equal(r_one[q], r_three[q]) and NP.array_equal(r_one[q], h_one[q]), q
 
 
+def test_five_triads_in_chunks_of_two_equal_one_chunk(ctx):
+    """Five triads in chunks of 2, 2 and 1: the eight outputs bit for bit those of one chunk."""
+    rng = NP.random.default_rng(81)
+    n0, n1, ntriads, nchan = 2, 4, 5, 8
+    shape = (n0, n1, ntriads, nchan)
+    binned = (rng.uniform(-NP.pi, NP.pi, shape), rng.uniform(-NP.pi, NP.pi, shape), rng.integers(0, 3, shape).astype(NP.float64))
+    pairs = NP.array([[0, 1, 2, 3], [0, 2, 1, 3]])
+    per_triad = n0 * n1 * nchan * 24 + n0 * len(pairs) * nchan * _abi.PRISIM_CPDIFF_OUT_BYTES
+    one = ctx.cphase_diff(pairs, binned=binned)
+    three = ctx.cphase_diff(pairs, binned=binned, budget_bytes=2 * per_triad)
+    assert one['stats']['chunks'] == 1 and three['stats']['chunks'] == 3 and three['stats']['chunk_triads'] == 2
+    for q in _abi.CPDIFF_OUTPUTS:
+        assert NP.array_equal(one[q], three[q]), q
+
+
 def test_refusals(ctx):
     """argument checks made before any launch: PRISIM_EINVAL through the raw entry with the outputs found unchanged, ValueError
     through the binding"""

@@ -113,6 +113,23 @@ def test_chunks_and_broadcasting(ctx, nchan, m, lead):
     compare(other, ref, df, 'nchan %d m %d rocfft' % (nchan, m))
 
 
+@pytest.mark.parametrize('m', [16, 12])
+def test_five_rows_in_chunks_of_two_equal_one_chunk(ctx, m):
+    """Five rows in chunks of 2, 2 and 1 on two streams, fused (m = 16) and through rocFFT (m = 12, whose plan for the last chunk has
+    another batch): every output bit for bit that of one chunk."""
+    inputs, w, wts, vs = synthetic(8, lead=(1, 1, 5))
+    one = ctx.cphase_ft(inputs, wts, m, 1e5, weights=w, vscale=vs, nres=5)
+    three = ctx.cphase_ft(inputs, wts, m, 1e5, weights=w, vscale=vs, nres=5, budget_bytes=2 * 2 * one['stats']['row_bytes'])
+    st = three['stats']
+    assert one['stats']['chunks'] == 1 and st['route'] == ('fused' if m == 16 else 'rocfft')
+    assert st['chunks'] == 3 and st['chunk_rows'] == 2 and st['streams'] == 2
+    for kind in ('over', 'res'):
+        for i in range(len(inputs)):
+            assert NP.array_equal(one[kind][i], three[kind][i], equal_nan=True), (kind, i)
+    for kind in ('lag_kernel', 'lag_kernel_res'):
+        assert NP.array_equal(one[kind], three[kind], equal_nan=True), kind
+
+
 @pytest.mark.parametrize('m', [32, 30])
 def test_without_weights(ctx, m):
     """no weights: the lag kernel has one row per window, [nwin][1][1][1][m]; no input at all gives the lag kernel alone"""

@@ -174,6 +174,21 @@ def test_three_chunks_equal_one(ctx):
         assert NP.array_equal(one2[q], three2[q]), q
 
 
+def test_five_triads_in_chunks_of_two_equal_one_chunk(ctx):
+    """Five triads in chunks of 2, 2 and 1: every quantity bit for bit that of one chunk."""
+    rng = NP.random.default_rng(80)
+    n0, n1, ntriads, nchan = 2, 4, 5, 8
+    ph = rng.uniform(-NP.pi, NP.pi, (n0, n1, ntriads, nchan))
+    fl = rng.uniform(size=ph.shape) < 0.2
+    off, mem = NP.array([0, 2, 4], dtype=NP.int64), NP.arange(4, dtype=NP.int32)
+    per_triad = n0 * n1 * nchan * 9 + n0 * 2 * nchan * 8 * 9                    # phases and flags in; nine doubles per output point
+    one = ctx.cphase_bin(1, off, mem, phases=ph, flags=fl)
+    three = ctx.cphase_bin(1, off, mem, phases=ph, flags=fl, budget_bytes=2 * per_triad)
+    assert one['stats']['chunks'] == 1 and three['stats']['chunks'] == 3 and three['stats']['chunk_triads'] == 2
+    for q in _abi.CPBINS_WANT:
+        assert NP.array_equal(one[q], three[q]), q
+
+
 def test_resident_two_pass_equals_two_round_trips(ctx):
     raw, nchan, kw = case('day_lst_67')
     prelim, detail, day, lst = reference('day_lst_67')
