@@ -90,6 +90,11 @@ PRISIM_CPFT_MAX_LEN, PRISIM_CPFT_MAX_IN = PRISIM_SUBBAND_MAX_LEN, 8
 PRISIM_CPFT_OVER, PRISIM_CPFT_RES, PRISIM_CPFT_LAG = 1, 2, 4
 PRISIM_CPFT_AUTO, PRISIM_CPFT_FUSED, PRISIM_CPFT_ROCFFT = -1, 0, 1
 CPFT_ROUTES = {PRISIM_CPFT_FUSED: 'fused', PRISIM_CPFT_ROCFFT: 'rocfft'}
+# every symbol include/prisim_cpxps.h declares: cross power of closure-phase delay spectra (prisim_amd/csrc_closure/cpxps.hip)
+CPXPS_EXPORTS = ('prisim_cphase_xpower',)
+PRISIM_CPXPS_MAX_MEDIAN = 256
+CPXPS_MODES = {'none': 0, 'full': 1, 'collapse': 2}
+CPXPS_STATS = {'mean': 0, 'median': 1}
 
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
@@ -256,6 +261,13 @@ class PrisimCpftStats(C.Structure):
                 ('route', C.c_int32), ('streams', C.c_int32), ('group_rows', C.c_int32), ('lds_bytes', C.c_int32)]
 
 
+class _PrisimCpxpsStats(C.Structure):
+    """prisim_cpxps_stats, public as Context.PrisimCpxpsStats: tests/test_abi_helpers.py pins the Prisim*Stats names of this module's
+    namespace, and tests/test_cpxps.py holds this struct to the same rules."""
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('chunks', C.c_int64), ('chunk_lags', C.c_int64),
+                ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('cross_bytes', C.c_int64)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -420,6 +432,9 @@ def load_library():
     lib.prisim_cphase_ft.argtypes = [vp, i64, i64, i64, i64, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, i64, dbl, i64, i64, vp, vp, vp, C.c_int32,
                                      C.c_int32, i64, vp, vp, vp, vp, C.POINTER(PrisimCpftStats)]
     lib.prisim_cphase_ft.restype = C.c_int
+    lib.prisim_cphase_xpower.argtypes = [vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, C.c_int32, vp, C.c_int32, i64, vp,
+                                         C.POINTER(_PrisimCpxpsStats)]
+    lib.prisim_cphase_xpower.restype = C.c_int
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
                                              C.POINTER(vp), pst]
@@ -1405,6 +1420,73 @@ class Context(object):
             'prisim_cphase_ft')
         out['stats'] = _stats_dict(st, route=CPFT_ROUTES)
         return out
+
+    # ---- cross power of closure-phase delay spectra (include/prisim_cpxps.h) ----
+    PrisimCpxpsStats = _PrisimCpxpsStats
+
+    @staticmethod
+    def cphase_xpower_shape(shape, modes, nshift):
+        """The shape of cphase_xpower's result for inputs of `shape` (nspw, n1, n2, n3, nlags)"""
+        out = [int(shape[0])]
+        for ax, mode in enumerate(modes):
+            n = int(shape[ax + 1])
+            if mode == 'none':
+                out.append(n)
+            elif mode == 'full':
+                out += [int(nshift), n] if ax == 0 else [n, n]
+            else:
+                out.append(int(nshift) if ax == 0 else 2 * n - 1)
+        return tuple(out) + (int(shape[4]),)
+
+    def cphase_xpower(self, a, b=None, factor=None, weights=None, modes=('none', 'none', 'none'), shifts=None, collapse=(), stat='mean',
+                      budget_bytes=0):
+        """Cross power of delay spectra on the device (prisim_cphase_xpower): P = (factor (a wa)) conj(b wb) over pairs of LST bins, day
+        bins and triads, and its collapses.  a, b (None: a): complex (nspw, n1, n2, n3, nlags); factor (nspw,) (None: 1); weights: None
+        or three entries, per axis a complex vector of the axis' length or None; modes: per axis 'none', 'full' or 'collapse'; shifts:
+        the LST shifts, needed where axis 1 is crossed; collapse: the collapsed axes (1, 2, 3) in the order of their collapse; stat:
+        'mean' or 'median' of the LST collapse.  Returns {'out': complex (nspw, per axis n | nshift, n1 | n, n | nshift | 2n-1, nlags),
+        'stats'}."""
+        a = NP.ascontiguousarray(a, dtype=NP.complex128)
+        if a.ndim != 5:
+            raise ValueError('a must be (nspw, n1, n2, n3, nlags)')
+        if b is not None:
+            b = NP.ascontiguousarray(b, dtype=NP.complex128)
+            if b.shape != a.shape:
+                raise ValueError('b must have the shape of a')
+        nspw = a.shape[0]
+        f = NP.ones(nspw) if factor is None else NP.ascontiguousarray(factor, dtype=NP.float64).reshape(-1)
+        if f.size != nspw:
+            raise ValueError('factor must have one entry per window')
+        modes = tuple(modes)
+        if len(modes) != 3:
+            raise ValueError('modes must have three entries')
+        mcodes = NP.ascontiguousarray([CPXPS_MODES[m] for m in modes], dtype=NP.int32)
+        ws = [None] * 3
+        if weights is not None:
+            if len(weights) != 3:
+                raise ValueError('weights must have three entries')
+            for ax, w in enumerate(weights):
+                if w is not None:
+                    ws[ax] = NP.ascontiguousarray(w, dtype=NP.complex128).reshape(-1)
+                    if ws[ax].size != a.shape[ax + 1]:
+                        raise ValueError('the weights of axis {0} must have {1} entries'.format(ax + 1, a.shape[ax + 1]))
+        wptr = (C.c_void_p * 3)(*[None if w is None else w.ctypes.data for w in ws])
+        sh = None
+        if modes[0] != 'none':
+            if shifts is None:
+                raise ValueError('a crossed LST axis needs its shifts')
+            sh = NP.ascontiguousarray(shifts, dtype=NP.int64).reshape(-1)
+        nshift = 0 if sh is None else sh.size
+        order = NP.ascontiguousarray(collapse, dtype=NP.int32).reshape(-1)
+        scode = CPXPS_STATS[stat]
+        if nshift < 1 and sh is not None:
+            raise ValueError('a crossed LST axis needs 1 to 2^20 shifts')
+        out = NP.empty(self.cphase_xpower_shape(a.shape, modes, nshift), dtype=NP.complex128)
+        st = self.PrisimCpxpsStats()
+        self._check(self._lib.prisim_cphase_xpower(
+            self._h, nspw, a.shape[1], a.shape[2], a.shape[3], a.shape[4], _ptr(a), _ptr(b), _ptr(f), wptr, _ptr(mcodes), nshift, _ptr(sh),
+            order.size, _ptr(order), scode, int(budget_bytes), _ptr(out), C.byref(st)), 'prisim_cphase_xpower')
+        return {'out': out, 'stats': _stats_dict(st)}
 
     # ---- instrument gain tables (include/prisim_gains.h) ----
     def gains_eval_spline(self, packed, times, freqs):

@@ -2,7 +2,9 @@
 with the day and LST binning of smooth_in_tbins and of subsample_differencing on the GPU (include/prisim_cpbins.h,
 prisim_amd/csrc_closure/cpbins.hip) and the differences of the day sub-samples there too (include/prisim_cpdiff.h,
 prisim_amd/csrc_closure/cpdiff.hip); and ClosurePhaseDelaySpectrum with its FT, the delay spectra of the binned phasors, of the
-residuals, of the sub-model and of the half differences on the GPU (include/prisim_cpft.h, prisim_amd/csrc_closure/cpft.hip).
+residuals, of the sub-model and of the half differences on the GPU (include/prisim_cpft.h, prisim_amd/csrc_closure/cpft.hip), and with
+subset, compute_power_spectrum, compute_power_spectrum_uncertainty and beam3Dvol: the cross products of those spectra over pairs of LST
+bins, day bins and triads and their collapses on the GPU (include/prisim_cpxps.h, prisim_amd/csrc_closure/cpxps.hip).
 
 Readings and departures
 - astropy is not a dependency.  The reference uses astropy.time.Time only to carry Julian dates, so loadnpz does that arithmetic
@@ -56,8 +58,44 @@ Readings and departures of ClosurePhaseDelaySpectrum.FT (:2573-2784).  Every err
 - visscaleinfo: 'vis' as a numpy or masked array (3, nlst_vis, nchan) with 'lst' and nlst_vis == 1 (:2669-2670, :2716-2717, on the
   host: the scale is one number per window and LST bin).  Several reference LSTs need OPS.interpolate_masked_array_1D and an
   InterferometerArray under 'vis' needs its baseline search; both raise NotImplementedError.
-- subset, compute_power_spectrum and what follows it are not implemented; the spectra are copied to the host and do not stay on the
-  device.
+- The spectra are copied to the host and do not stay on the device.  save, rescale_power_spectrum and
+  average_rescaled_power_spectrum are not implemented.
+
+Readings and departures of subset, compute_power_spectrum (:2888-3601), compute_power_spectrum_uncertainty (:3605-4357) and beam3Dvol
+(:4638-4879).  Every error is raised, and every departure decided, before any device work.
+- On the host, as O(input) work on arrays it already holds: the normalisation of the arguments, subset, the LST shifts of dlst_range,
+  z, kprll and the factor (power_factor), the selection and the coherent average over autoinfo['axes'] (the twts awts weighted mean
+  with twts at the channel of largest total weight, NP.median for 'median').  On the device: one prisim_cphase_xpower call per pool,
+  statistic and sampling -- the cross product under the preX weights and its collapses, in the order of xinfo['collapse_axes'].  Back
+  on the host, on the collapsed result: postX, postXnorm, avgcov, diagoffsets, diagweights, axesmap and the sample counts.
+- For days and triads the reference puts the first spectrum at the second index of a pair and the second spectrum at the first
+  (:3482, :3509); the entry puts a at the first.  The host swaps the two axes of a full pair and reverses the offsets of a collapsed
+  one, so the results have the reference's layout.
+- astropy is not a dependency: cosmo is delay_spectrum.cosmo100 by default (h = 1: lengths are Mpc/h) and the results are plain
+  complex128 arrays in Jy^2 Mpc/h or K^2 (Mpc/h)^3 for both statistics; the reference converts the units of the last one only.
+  OPS.array_trace is read in dsp_readings.array_trace.
+- No collapsed axis (xinfo['collapse_axes'] empty) and no incoherent axis (xinfo['axes'] absent, or all of length 1) end the reference
+  in an UnboundLocalError on diagweights / diagoffsets (:3594-3595).  Here diagoffsets = {} and diagweights = {} and the full
+  cross-power matrix, or factor |dspec|^2 (formed on the host), is returned.
+- autoinfo=None, xinfo=None and xinfo={'axes': None} end the reference in TypeErrors (dtpye, :3262, :3291, :3298); here they mean no
+  coherent and no incoherent axes.
+- A selection together with coherent axes indexes the selected array a second time in the reference (:3465, IndexError); here it is
+  indexed once.
+- avgcov=True without a collapsed axis fails in the reference; here it is a ValueError.  preXnorm=True calls an undefined logical_or
+  (:3518); here it is NotImplementedError.  collapse_axes that are not among xinfo['axes'] (a KeyError in the reference), axes outside
+  1..3 and weights of a length that is neither 1 nor the axis' are ValueErrors.
+- An LST shift that leaves no LST bin (the default shifts 0 and 1 on a single selected LST bin) fills the reference's row with NaN;
+  here it is a ValueError.
+- A cpds argument leaves the reference's `sampling` unbound; here the samplings are those present in cpds, and a sampling that FT did
+  not produce (resample=False) is skipped.  A pool without spectra ('submodel' and 'residual' unless subtract ran) is skipped.
+- The caller's dictionaries (selection, autoinfo, xinfo, beamparms, cpds) are not modified.
+- Uncertainty: the days axis 2 is dropped from the coherent, incoherent and collapsed axes, as in the reference; avgcov is the plain
+  nanmean over the collapsed axes (:4327; the reference's weighted average behind it multiplies and divides by the same sum); the
+  coherent average follows the intent of :4196-4210, which raises a KeyError in the reference ('dspec'); the weights of both halves are
+  taken at the channel where those of 'dspec0' total most.  No incoherent axis left is a ValueError (:4340 reads an unbound name).
+- beam3Dvol: delay_spectrum.beam3Dvol of delay_spectrum.healpix_power_pattern(freqs, telescope, nside) (the analytic pattern on the
+  device), nside 64 and chromatic True by default; chromatic=False takes the pattern at select_freq, by default the mean of the
+  frequencies.  A beamfile raises NotImplementedError: its formats need astropy or pyuvdata.
 """
 import warnings
 
@@ -483,6 +521,7 @@ class ClosurePhaseDelaySpectrum(object):
         self.cPhaseDS = None
         self.cPhaseDS_resampled = None
         self.ft_stats = {}
+        self.xps_stats = {}
 
     def FT(self, bw_eff, freq_center=None, shape=None, fftpow=None, pad=None, datapool='prelim', visscaleinfo=None, method='fft',
            resample=True, apply_flags=True):
@@ -633,3 +672,388 @@ class ClosurePhaseDelaySpectrum(object):
         resampled['lag_kernel'] = DSP.downsampler(result['lag_kernel'], downsample_factor, axis=-1, method='interp', kind='linear')
         self.cPhaseDS_resampled = resampled
         return resampled
+
+    def subset(self, selection=None):
+        """(triad_ind, lst_ind, day_ind, day_ind_eicpdiff): the indices that `selection` ({'triads': list of 3-tuples, 'lst': indices,
+        'days': indices}; a missing key, None or selection=None: all) picks of the triads, of the LST and day bins of
+        cpinfo['processed']['prelim'] and of the pairs of day-bin pairs of cpinfo['errinfo'] (those made of selected day bins only).
+        The caller's dictionary is not modified."""
+        if selection is None:
+            selection = {}
+        elif not isinstance(selection, dict):
+            raise TypeError('Input selection must be a dictionary')
+        cpinfo = self.cPhase.cpinfo
+        triads = [tuple(t) for t in NP.asarray(cpinfo['raw']['triads']).tolist()]
+        seltriads = selection.get('triads')
+        if seltriads is None:
+            seltriads = triads
+        triad_ind = NP.asarray([triads.index(tuple(NP.asarray(triad).tolist())) for triad in seltriads], dtype=int)
+        prelim = cpinfo['processed'].get('prelim', {})
+        shape = prelim['wts'].shape if 'wts' in prelim else None
+
+        def indices(key, axis, what):
+            sel = selection.get(key)
+            if shape is None:
+                return None
+            if sel is None:
+                return NP.arange(shape[axis])
+            if not isinstance(sel, (list, NP.ndarray)):
+                raise TypeError('Wrong type for processed {0} indices'.format(what))
+            sel = NP.asarray(sel, dtype=int).reshape(-1)
+            if NP.any((sel < 0) | (sel >= shape[axis])):
+                raise ValueError('Input processed {0} indices out of bounds'.format(what))
+            return sel
+
+        lst_ind = indices('lst', 0, 'lst')
+        if lst_ind is None:
+            raise ValueError('LST index selection could not be performed')
+        day_ind = indices('days', 1, 'day')
+        if day_ind is None:
+            raise ValueError('Day index selection could not be performed')
+        day_ind_eicpdiff = None
+        pairs = cpinfo.get('errinfo', {}).get('list_of_pair_of_pairs')
+        if pairs is not None:
+            if selection.get('days') is None:
+                day_ind_eicpdiff = NP.arange(len(pairs))
+            else:
+                chosen = set(day_ind.tolist())
+                day_ind_eicpdiff = NP.asarray([i for i, item in enumerate(pairs) if len(set(NP.asarray(item).ravel().tolist()) - chosen) == 0],
+                                              dtype=int)
+        return (triad_ind, lst_ind, day_ind, day_ind_eicpdiff)
+
+    def beam3Dvol(self, beamparms, freq_wts=None):
+        """Integral of the squared power pattern over solid angle and frequency, in Sr Hz, per window of freq_wts (nwin, nchan):
+        delay_spectrum.beam3Dvol of the analytic power pattern of beamparms['telescope'] at beamparms['freqs'] on a HEALPix grid of
+        beamparms['nside'] (64), evaluated on the device; with 'chromatic' False (default True) the pattern at 'select_freq' (the mean
+        of the frequencies) at every channel.  A 'beamfile' raises NotImplementedError.  The caller's dictionary is not modified."""
+        from . import delay_spectrum as DS
+        if not isinstance(beamparms, dict):
+            raise TypeError('Input beamparms must be a dictionary')
+        if ('beamfile' not in beamparms) and ('telescope' not in beamparms):
+            raise KeyError('Input beamparms does not contain either "beamfile" or "telescope" keys')
+        if 'freqs' not in beamparms:
+            raise KeyError('Key "freqs" not found in input beamparms')
+        freqs = beamparms['freqs']
+        if not isinstance(freqs, NP.ndarray):
+            raise TypeError('Key "freqs" in input beamparms must contain a numpy array')
+        nside = beamparms.get('nside', 64)
+        if not isinstance(nside, int):
+            raise TypeError('"nside" parameter in input beamparms must be an integer')
+        chromatic = beamparms.get('chromatic', True)
+        if not isinstance(chromatic, bool):
+            raise TypeError('Beam chromaticity parameter in input beamparms must be a boolean')
+        if beamparms.get('beamfile') is not None:
+            raise NotImplementedError('a beamfile is not supported (its formats need astropy or pyuvdata): give the "telescope"')
+        if 'telescope' not in beamparms:
+            raise KeyError('Input beamparms does not contain the key "telescope"')
+        device = getattr(self.cPhase._ctx, 'device', 0)
+        if chromatic:
+            beam = DS.healpix_power_pattern(freqs, beamparms['telescope'], nside=nside, device=device)
+        else:
+            select_freq = beamparms.get('select_freq')
+            if select_freq is None:
+                select_freq = NP.mean(freqs)
+            beam = DS.healpix_power_pattern(NP.asarray([select_freq], dtype=NP.float64), beamparms['telescope'], nside=nside, device=device)
+        return DS.beam3Dvol(beam, freqs, freq_wts=freq_wts, hemisphere=True)
+
+    def power_factor(self, cpds, units='K', beamparms=None, cosmo=None):
+        """(z, kprll, factor) of one sampling of FT's result (:3395-3416): the redshifts of the windows, k_parallel (nspw, nlags) in
+        h/Mpc and the factor that turns (Jy Hz)^2 into Jy^2 Mpc/h, drz_los / bw_eff^2, or into K^2 (Mpc/h)^3,
+        rz_los^2 drz_los / bw_eff / omega_bw (wl^2 Jy / 2 k_B)^2."""
+        from . import delay_spectrum as DS
+        import scipy.constants as FCNST
+        cosmo = DS.cosmo100 if cosmo is None else cosmo
+        fc, bw = NP.asarray(cpds['freq_center'], dtype=NP.float64).reshape(-1), NP.asarray(cpds['bw_eff'], dtype=NP.float64).reshape(-1)
+        wl = FCNST.c / fc
+        z = DS.REST_FREQ_HI / fc - 1
+        kprll = DS.dkprll_deta(z, cosmo=cosmo).reshape(-1, 1) * NP.asarray(cpds['lags'])
+        drz_los = (FCNST.c / 1e3) * bw * (1 + z) ** 2 / DS.REST_FREQ_HI / cosmo.H0.value / cosmo.efunc(z)                 # Mpc/h
+        if units == 'Jy':
+            factor = (1 / bw) * (drz_los / bw)
+        elif units == 'K':
+            rz_los = NP.asarray(cosmo.comoving_distance(z).to('Mpc').value, dtype=NP.float64).reshape(-1)
+            omega_bw = self.beam3Dvol(beamparms, freq_wts=cpds['freq_wts'])
+            factor = (1 / omega_bw) * (rz_los ** 2 * drz_los / bw) * (wl ** 2 * DS.JY / (2 * FCNST.k)) ** 2
+        else:
+            raise ValueError('Input value for units invalid')
+        return z, kprll, NP.ascontiguousarray(factor, dtype=NP.float64)
+
+    def compute_power_spectrum(self, cpds=None, selection=None, autoinfo=None, xinfo=None, cosmo=None, units='K', beamparms=None):
+        """Delay power spectra of the closure phases (:2888-3601): the spectra of FT (cpds, by default those of the last FT) of the
+        pools 'whole', 'submodel' and 'residual', averaged coherently over autoinfo['axes'] on the host, are cross-multiplied over the
+        pairs of xinfo['axes'] (1 LST with the shifts of xinfo['dlst_range'], 2 days, 3 triads) under xinfo['wts']['preX'] and
+        collapsed over xinfo['collapse_axes'] on the device (prisim_cphase_xpower), then weighted by xinfo['wts']['postX'], normalised
+        ('postXnorm') and averaged ('avgcov') on the host.  Returns the reference's dictionary: 'triads', 'triads_ind', 'lst',
+        'lst_ind', 'dlst', 'days', 'day_ind', 'dday', 'lstXoffsets' and per sampling ('oversampled', 'resampled') 'z', 'kprll', 'lags',
+        'freq_center', 'bw_eff', 'shape', 'freq_wts', 'lag_corr_length' and per pool 'mean', 'median' (complex128, Jy^2 Mpc/h or
+        K^2 (Mpc/h)^3), 'diagoffsets', 'diagweights', 'axesmap', 'nsamples_incoh', 'nsamples_coh'.  xps_stats holds the device
+        statistics of the calls.  See the module docstring for the departures."""
+        return self._power_spectrum(False, cpds, selection, autoinfo, xinfo, cosmo, units, beamparms)
+
+    def compute_power_spectrum_uncertainty(self, cpds=None, selection=None, autoinfo=None, xinfo=None, cosmo=None, units='K',
+                                           beamparms=None):
+        """Uncertainty of the delay power spectra from the sub-sample differences (:3605-4357): as compute_power_spectrum on the pool
+        'errinfo', dspec0 conj(dspec1) over the pairs of xinfo['axes'], with the reference's keys (top level from cpinfo['errinfo'],
+        'day_ind' the pairs of day-bin pairs).  The days axis 2 is dropped from every list of axes."""
+        return self._power_spectrum(True, cpds, selection, autoinfo, xinfo, cosmo, units, beamparms)
+
+    @staticmethod
+    def _xps_arguments(autoinfo, xinfo, uncertainty):
+        """The normalised arguments of the power spectra (:3261-3356) as a dictionary, from copies of the caller's"""
+        def axes_of(info, name):
+            axes = info.get('axes')
+            if axes is None:
+                return None
+            if isinstance(axes, bool) or not isinstance(axes, (list, tuple, NP.ndarray, int, NP.integer)):
+                raise TypeError('Value under key axes in input {0} must be an integer, list, tuple or numpy array'.format(name))
+            axes = NP.asarray(axes).reshape(-1)
+            if axes.size and (not NP.issubdtype(axes.dtype, NP.integer) or NP.any((axes < 1) | (axes > 3)) or NP.unique(axes).size != axes.size):
+                raise ValueError('axes in input {0} must be distinct and among 1 (LST), 2 (days) and 3 (triads)'.format(name))
+            return [int(ax) for ax in axes]
+
+        one = [NP.ones(1, dtype=NP.float64)]
+        if autoinfo is None:
+            autoinfo = {}
+        elif not isinstance(autoinfo, dict):
+            raise TypeError('Input autoinfo must be a dictionary')
+        cohax = axes_of(autoinfo, 'autoinfo')
+        awts = autoinfo.get('wts')
+        if cohax is None or awts is None:
+            awts = one * (1 if cohax is None else len(cohax))
+        else:
+            if not isinstance(awts, list):
+                raise TypeError('wts in input autoinfo must be a list of numpy arrays')
+            if len(awts) != len(cohax):
+                raise ValueError('Input list of wts must be same as length of autoinfo axes')
+        if xinfo is None:
+            xinfo = {}
+        elif not isinstance(xinfo, dict):
+            raise TypeError('Input xinfo must be a dictionary')
+        incohax = axes_of(xinfo, 'xinfo')
+        nax = 1 if incohax is None else len(incohax)
+        wts = xinfo.get('wts')
+        X = {'preX': one * nax, 'postX': one * nax, 'preXnorm': False, 'postXnorm': False}
+        if wts is not None:
+            if incohax is not None:
+                if not isinstance(wts, dict):
+                    raise TypeError('wts in input xinfo must be a dictionary')
+                for xkey in ('preX', 'postX'):
+                    if xkey not in wts:
+                        raise KeyError('wts in input xinfo lacks the key {0}'.format(xkey))
+                    if not isinstance(wts[xkey], list):
+                        raise TypeError('{0} wts in input xinfo must be a list of numpy arrays'.format(xkey))
+                    if len(wts[xkey]) != len(incohax):
+                        raise ValueError('Input list of {0} wts must be same as length of xinfo axes'.format(xkey))
+                    X[xkey] = list(wts[xkey])
+            if isinstance(wts, dict):
+                for nkey in ('preXnorm', 'postXnorm'):
+                    if not isinstance(wts.get(nkey, False), (bool, NP.bool_)):
+                        raise TypeError('{0} in input xinfo must be a boolean'.format(nkey))
+                    X[nkey] = bool(wts.get(nkey, False))
+        avgcov = xinfo.get('avgcov', False)
+        if not isinstance(avgcov, (bool, NP.bool_)):
+            raise TypeError('avgcov under input xinfo must be boolean')
+        colax = xinfo.get('collapse_axes', [])
+        if isinstance(colax, bool) or not isinstance(colax, (int, NP.integer, list, tuple, NP.ndarray)):
+            raise TypeError('collapse_axes under input xinfo must be an integer, tuple, list or numpy array')
+        colax = [int(ax) for ax in NP.asarray(colax).reshape(-1)]
+        cohax = [] if cohax is None else cohax
+        incohax = [] if incohax is None else incohax
+        if set(cohax) & set(incohax):
+            raise ValueError("Inputs autoinfo['axes'] and xinfo['axes'] must have no intersection")
+        if X['preXnorm']:
+            raise NotImplementedError('preXnorm is not implemented (the reference calls an undefined logical_or there)')
+        preX = dict(zip(incohax, X['preX']))
+        if uncertainty:                                   # the days axis is that of the pairs of day-bin pairs: never averaged or crossed
+            awts = [w for ax, w in zip(cohax, awts) if ax != 2]
+            cohax = [ax for ax in cohax if ax != 2]
+            incohax = [ax for ax in incohax if ax != 2]
+            colax = [ax for ax in colax if ax != 2]
+        if len(set(colax)) != len(colax) or not set(colax) <= set(incohax):
+            raise ValueError("xinfo['collapse_axes'] must be distinct axes of xinfo['axes']")
+        if len(colax) > len(X['postX']):
+            raise ValueError('Input list of postX wts is shorter than the collapsed axes')
+        return {'cohax': cohax, 'awts': [NP.asarray(w) for w in awts], 'incohax': incohax, 'preX': {ax: NP.asarray(preX[ax]) for ax in incohax},
+                'postX': [NP.asarray(w) for w in X['postX']], 'postXnorm': X['postXnorm'], 'avgcov': bool(avgcov), 'colax': colax,
+                'dlst_range': xinfo.get('dlst_range')}
+
+    def _power_spectrum(self, uncertainty, cpds, selection, autoinfo, xinfo, cosmo, units, beamparms):
+        from . import delay_spectrum as DS
+        if not isinstance(units, str):
+            raise TypeError('Input parameter units must be a string')
+        if units not in ('Jy', 'K'):
+            raise ValueError('Input value for units invalid')
+        if units == 'K':
+            if not isinstance(beamparms, dict):
+                raise TypeError('Input beamparms must be a dictionary')
+            beamparms = dict(beamparms)
+            if 'freqs' not in beamparms:
+                beamparms['freqs'] = self.f
+        cosmo = DS.cosmo100 if cosmo is None else cosmo
+        A = self._xps_arguments(autoinfo, xinfo, uncertainty)
+        cohax, incohax, colax = A['cohax'], A['incohax'], A['colax']
+        if selection is not None and not isinstance(selection, dict):
+            raise TypeError('Input selection must be a dictionary')
+        if cpds is None:
+            cpds = {'oversampled': self.cPhaseDS, 'resampled': self.cPhaseDS_resampled}
+        elif not isinstance(cpds, dict):
+            raise TypeError('Input cpds must be a dictionary')
+        sampling = [s for s in ('oversampled', 'resampled') if cpds.get(s) is not None]
+        if not sampling:
+            raise ValueError('FT must compute the delay spectra before their power spectra')
+        triad_ind, lst_ind, day_ind, day_ind_eicpdiff = self.subset(selection=selection)
+        cpinfo = self.cPhase.cpinfo
+        if uncertainty:
+            if day_ind_eicpdiff is None:
+                raise ValueError('subsample_differencing must fill the sub-sample differences before their power spectra')
+            bins, mid_ind = cpinfo['errinfo'], day_ind_eicpdiff
+        else:
+            bins, mid_ind = cpinfo['processed']['prelim'], day_ind
+        dlst = NP.asarray(bins['dlstbins']).reshape(-1)
+        result = {'triads': NP.asarray(cpinfo['raw']['triads'])[triad_ind], 'triads_ind': triad_ind, 'lst': NP.asarray(bins['lstbins'])[lst_ind],
+                  'lst_ind': lst_ind, 'dlst': dlst[lst_ind] if dlst.size > 1 else dlst,
+                  'days': NP.asarray(bins['daybins'])[day_ind], 'day_ind': mid_ind, 'dday': NP.asarray(bins['diff_dbins'])[day_ind]}
+        dlstbin = NP.mean(bins['dlstbins'])
+        if A['dlst_range'] is None:
+            lstshifts = NP.arange(2)                      # LST index offsets of 0 and 1 only
+        else:
+            dlst_range = NP.asarray(A['dlst_range'], dtype=NP.float64).ravel() / 60.0
+            if dlst_range.size == 1:
+                dlst_range = NP.insert(dlst_range, 0, 0.0)
+            if not dlstbin > 0.0:
+                raise ValueError('dlst_range needs LST bins of a non-zero width')
+            lstshifts = NP.arange(max(0, int(NP.ceil(dlst_range.min() / dlstbin))), min(int(NP.ceil(dlst_range.max() / dlstbin)), lst_ind.size))
+        result['lstXoffsets'] = lstshifts * dlstbin
+        sizes = {1: lst_ind.size, 2: mid_ind.size, 3: triad_ind.size}
+        nsamples_coh = int(NP.prod([sizes[ax] for ax in cohax])) if cohax else 1
+        nsamples = int(NP.prod([sizes[ax] for ax in incohax])) if incohax else 1
+        nsamples_incoh = nsamples * (nsamples - 1) if incohax else 1
+        crossed = nsamples_incoh > 1
+        collapsing = crossed and len(colax) > 0
+        if A['avgcov'] and not collapsing:
+            raise ValueError('avgcov needs collapsed axes to average over')
+        if uncertainty and not crossed:
+            raise ValueError('the uncertainty needs an axis of xinfo to cross the sub-sample differences over')
+        modes = tuple(('collapse' if ax in colax else 'full') if (crossed and ax in incohax) else 'none' for ax in (1, 2, 3))
+        if crossed and 1 in incohax:
+            if lstshifts.size < 1 or NP.any(lstshifts >= lst_ind.size):
+                raise ValueError('the LST shifts {0} do not lie inside the {1} selected LST bins'.format(lstshifts.tolist(), lst_ind.size))
+        weights = [None, None, None]
+        for ax in incohax:
+            w = A['preX'][ax].astype(NP.complex128).reshape(-1)
+            if w.size not in (1, sizes[ax]):
+                raise ValueError('the preX weights of axis {0} must have 1 or {1} entries'.format(ax, sizes[ax]))
+            weights[ax - 1] = NP.ascontiguousarray(NP.broadcast_to(w, (sizes[ax],)))
+        # the output axes of every input axis: (shift, LST) or (i, j) where crossed, one where collapsed or not crossed
+        width = {ax: 2 if modes[ax - 1] == 'full' else 1 for ax in (1, 2, 3)}
+        pos = {ax: 1 + sum(width[y] for y in range(1, ax)) for ax in (1, 2, 3)}
+        outlen = {1: lstshifts.size, 2: 2 * sizes[2] - 1, 3: 2 * sizes[3] - 1}
+        ndim_out = 2 + sum(width.values())
+        postX = NP.ones((1,) * ndim_out, dtype=NP.complex128)
+        for colaxind, ax in enumerate(colax if collapsing else []):
+            w = A['postX'][colaxind].astype(NP.complex128).reshape(-1)
+            if w.size not in (1, outlen[ax]):
+                raise ValueError('the postX weights of axis {0} must have 1 or {1} entries'.format(ax, outlen[ax]))
+            shp = [1] * ndim_out
+            shp[pos[ax]] = -1
+            postX = postX * w.reshape(shp)
+        axes_to_sum = tuple(pos[ax] for ax in colax)
+
+        # the pools: (name, statistic or None) -> the spectra a (and b) and the weights of their coherent average
+        def pools_of(ds):
+            if uncertainty:
+                err = ds.get('errinfo', {})
+                if 'dspec0' not in err or 'dspec1' not in err:
+                    return []
+                return [('errinfo', stat, err['dspec0'][stat], err['dspec1'][stat], err['dspec0']['twts'], err['dspec1']['twts'])
+                        for stat in ('mean', 'median') if stat in err['dspec0'] and stat in err['dspec1']]
+            out = []
+            twts = ds['whole']['dspec']['twts']
+            for dpool in ('whole', 'submodel', 'residual'):
+                spec = ds.get(dpool, {}).get('dspec')
+                if spec is None:
+                    continue
+                for stat in ('mean', 'median'):
+                    x = spec if dpool == 'submodel' else spec.get(stat)
+                    if x is not None:
+                        out.append((dpool, stat, x, None, twts, None))
+            return out
+
+        def coherent(x, twts, stat, chan_twts):
+            """the selected spectra averaged over the coherent axes (:3445-3467), the weights at the channel where chan_twts total most"""
+            x = NP.asarray(x)[NP.ix_(NP.arange(NP.shape(x)[0]), lst_ind, mid_ind, triad_ind, NP.arange(NP.shape(x)[4]))]
+            if nsamples_coh > 1:
+                if stat == 'median':
+                    return NP.median(x, axis=tuple(cohax), keepdims=True)
+                tw = MA.getdata(twts)
+                tw = tw[..., [int(NP.argmax(NP.sum(MA.getdata(chan_twts), axis=(0, 1, 2))))]][NP.ix_(lst_ind, mid_ind, triad_ind, NP.arange(1))][NP.newaxis, ...]
+                aw = NP.ones((1,) * 5, dtype=NP.complex128)
+                for caxind, ax in enumerate(cohax):
+                    w = A['awts'][caxind].reshape(-1)
+                    if w.size not in (1, sizes[ax]):
+                        raise ValueError('the wts of autoinfo axis {0} must have 1 or {1} entries'.format(ax, sizes[ax]))
+                    shp = [1] * 5
+                    shp[ax] = -1
+                    aw = aw * w.reshape(shp)
+                return NP.sum(tw * aw * x, axis=tuple(cohax), keepdims=True) / NP.sum(tw * aw, axis=tuple(cohax), keepdims=True)
+            return x
+
+        work = []
+        for smplng in sampling:
+            ds = cpds[smplng]
+            z, kprll, factor = self.power_factor(ds, units=units, beamparms=beamparms, cosmo=cosmo)
+            result[smplng] = {'z': z, 'kprll': kprll, 'lags': NP.copy(ds['lags']), 'freq_center': ds['freq_center'], 'bw_eff': ds['bw_eff'],
+                              'shape': ds['shape'], 'freq_wts': ds['freq_wts'], 'lag_corr_length': ds['lag_corr_length']}
+            for dpool, stat, xa, xb, ta, tb in pools_of(ds):
+                a = NP.ascontiguousarray(coherent(xa, ta, stat, ta), dtype=NP.complex128)
+                b = None if xb is None else NP.ascontiguousarray(coherent(xb, tb, stat, ta), dtype=NP.complex128)
+                work.append((smplng, dpool, stat, factor, a, b))
+
+        ctx = self.cPhase._context() if crossed and work else None
+        self.xps_stats = {}
+        for smplng, dpool, stat, factor, a, b in work:
+            out = result[smplng].setdefault(dpool, {})
+            diagoffsets, diagweights, axesmap = {}, {}, {}
+            if not crossed:
+                f5 = factor.reshape(-1, 1, 1, 1, 1)
+                p = (f5 * NP.abs(a) ** 2).astype(NP.complex128)
+            else:
+                res = ctx.cphase_xpower(a, b=b, factor=factor, weights=weights, modes=modes, shifts=lstshifts if 1 in incohax else None,
+                                        collapse=colax, stat=stat)
+                self.xps_stats[(smplng, dpool, stat)] = res['stats']
+                p = res['out']
+                for ax in (2, 3):                           # the reference has a at the second and b at the first index of a pair
+                    if modes[ax - 1] == 'full':
+                        p = NP.swapaxes(p, pos[ax], pos[ax] + 1)
+                    elif modes[ax - 1] == 'collapse':
+                        p = NP.flip(p, axis=pos[ax])
+                axesmap = {ax: (pos[ax] + NP.arange(2) if modes[ax - 1] == 'full' else NP.asarray([pos[ax]])) for ax in incohax}
+                if collapsing:
+                    for ax in colax:
+                        if ax == 1:
+                            diagweights[ax] = int(NP.sum(NP.logical_not(NP.isnan(a[0, :, 0, 0, 0])))) - lstshifts
+                            diagoffsets[ax] = lstshifts
+                        else:
+                            diagoffsets[ax] = NP.arange(-(sizes[ax] - 1), sizes[ax])
+                            diagweights[ax] = sizes[ax] - NP.abs(diagoffsets[ax])
+                    p = p * postX
+                    if A['postXnorm']:
+                        p = p / NP.nansum(postX, axis=axes_to_sum, keepdims=True)
+                    if A['avgcov']:
+                        if uncertainty:
+                            with warnings.catch_warnings():
+                                warnings.simplefilter('ignore', RuntimeWarning)
+                                p = NP.nanmean(p, axis=axes_to_sum, keepdims=True)
+                        else:
+                            dw = NP.ones((1,) * p.ndim)
+                            for ax in colax:
+                                shp = [1] * p.ndim
+                                shp[pos[ax]] = -1
+                                dw = dw * NP.asarray(diagweights[ax], dtype=NP.float64).reshape(shp)
+                            p = NP.nansum(p * dw, axis=axes_to_sum, keepdims=True) / NP.nansum(dw, axis=axes_to_sum, keepdims=True)
+                        for ax in colax:
+                            del diagoffsets[ax]
+            out[stat] = p
+            out.update({'diagoffsets': diagoffsets, 'diagweights': diagweights, 'axesmap': axesmap, 'nsamples_incoh': nsamples_incoh,
+                        'nsamples_coh': nsamples_coh})
+        return result

@@ -1,8 +1,9 @@
 """Readings of the astroutils functions that prisim/delay_spectrum.py:subband_delay_transform (:2073-2250) calls and that have no
 source and no fixtures here: ``DSP.windowing`` / ``DSP.window_fftpow``, ``DSP.window_N2width``, ``LKP.find_1NN`` and
-``DSP.downsampler``; and ``NMO.find_list_in_list``, which the gain tables of prisim/interferometry.py (read_gaintable, extract_gains,
+``DSP.downsampler``; ``OPS.array_trace``, which the closure-phase power spectra of prisim/bispectrum_phase.py (:3542) collapse their
+covariances with; and ``NMO.find_list_in_list``, which the gain tables of prisim/interferometry.py (read_gaintable, extract_gains,
 GainInfo) use to match axis names and antenna / baseline labels.  Each function below is ONE explicit reading of its name -- PARITY UNPINNED against astroutils --
-pinned by known answers in tests/test_subband.py, and the only place the reading lives: the host chain, the device call and the
+pinned by known answers in tests/test_subband.py (array_trace: tests/test_cpxps.py), and the only place the reading lives: the host chain, the device call and the
 fixtures' stand-in modules all use these functions.
 
 No scipy: ``downsampler(..., method='FFT')`` restates ``scipy.signal.resample`` in numpy (checked against scipy where it is installed).
@@ -173,6 +174,27 @@ def spectral_axis(length, delx=1.0, shift=False, use_real=False):
 def fft_downsample_length(n, factor):
     """Samples of downsampler(x of n samples, factor, method='FFT'): round(n / factor) (Python's rounding, halves to even)."""
     return int(round(n / float(factor)))
+
+
+def array_trace(inparr, offsets=None, axis1=0, axis2=1, outaxis='axis1'):
+    """READING of OPS.array_trace (prisim/bispectrum_phase.py:3542): numpy.trace of `inparr` over (axis1, axis2), which must be of
+    equal length n, for every diagonal offset k = -(n-1) .. n-1 (or those of `offsets`); a[i, i + k] is summed in increasing i and NaN
+    propagates.  Returns (traces, offsets, diagwts): the traces as the one axis that replaces the two, at the place of axis1 (`outaxis`
+    'axis1') or of axis2 ('axis2'); the offsets; and diagwts = n - |k|, the number of elements of every diagonal.  The caller divides."""
+    inparr = NP.asarray(inparr)
+    axis1, axis2 = axis1 % inparr.ndim, axis2 % inparr.ndim
+    if axis1 == axis2 or inparr.shape[axis1] != inparr.shape[axis2]:
+        raise ValueError('array_trace needs two different axes of equal length')
+    if outaxis not in ('axis1', 'axis2'):
+        raise ValueError('outaxis must be "axis1" or "axis2"')
+    n = inparr.shape[axis1]
+    offsets = NP.arange(-(n - 1), n) if offsets is None else NP.asarray(offsets, dtype=int).reshape(-1)
+    if NP.any(NP.abs(offsets) >= n):
+        raise ValueError('array_trace: an offset lies outside the array')
+    traces = [NP.trace(inparr, offset=int(k), axis1=axis1, axis2=axis2) for k in offsets]
+    keep = axis1 if outaxis == 'axis1' else axis2
+    gone = axis2 if outaxis == 'axis1' else axis1
+    return NP.stack(traces, axis=keep - (1 if gone < keep else 0)), offsets, n - NP.abs(offsets)
 
 
 def _key(x):
