@@ -36,7 +36,7 @@ EXPORTS = (
     'prisim_hip_allgather_grad', 'prisim_hip_comm_selftest', 'prisim_hip_get_comm_stats', 'prisim_hip_set_gather_root', 'prisim_hip_set_shard_map', 'prisim_hip_device_pci', 'prisim_hip_comm_last_error',
     'prisim_hip_host_alloc', 'prisim_hip_host_free', 'prisim_hip_get_vis_async', 'prisim_hip_wait_downloads',
     'prisim_hip_set_catalog', 'prisim_hip_set_sky_from_catalog', 'prisim_hip_catalog_roi', 'prisim_hip_observe_catalog',
-    'prisim_hip_comm_version',
+    'prisim_hip_comm_version', 'prisim_hip_get_fold_info',
 )
 
 # every symbol include/prisim_clean.h declares: delay CLEAN (prisim_amd/csrc_clean/), linked into the same library
@@ -382,6 +382,7 @@ def load_library():
     lib.prisim_hip_get_timing.argtypes = [vp, C.POINTER(PrisimTiming), i32]
     lib.prisim_hip_device_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.c_char_p]
     lib.prisim_hip_set_tuning.argtypes = [vp, i32, i32, i32]
+    lib.prisim_hip_get_fold_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     lib.prisim_hip_allgather_grad.argtypes = [vp, i64, i32]
     lib.prisim_hip_comm_selftest.argtypes = [vp, i64]
     lib.prisim_hip_set_gather_root.argtypes = [vp, i32]
@@ -1677,7 +1678,15 @@ class Context(object):
     def timing(self, reset=False):
         t = PrisimTiming()
         self._check(self._lib.prisim_hip_get_timing(self._h, C.byref(t), 1 if reset else 0), 'prisim_hip_get_timing')
-        return {k: getattr(t, k) for k, _ in PrisimTiming._fields_ if k != 'reserved_'}
+        out = {k: getattr(t, k) for k, _ in PrisimTiming._fields_ if k != 'reserved_'}
+        # baseline folding: rows the last compute() summed (distinct baseline vectors of a folded array) and the terms its kernels
+        # evaluated, and the groups of 256 summed rows that lifted; last_terms stays the delivered count, last_lift_groups in groups of cube rows
+        nsum, nterms, nlift = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.prisim_hip_get_fold_info(self._h, C.byref(nsum), C.byref(nterms), C.byref(nlift)), 'prisim_hip_get_fold_info')
+        out['last_sum_lift_groups'] = nlift.value
+        out['last_sum_baselines'] = nsum.value
+        out['last_terms_evaluated'] = nterms.value
+        return out
 
     def device_info(self):
         cu, clk = C.c_int(), C.c_int()

@@ -63,7 +63,7 @@ Plan make_plan(const prisim_ctx* ctx, int precision, int kernel) {
   pl.f32 = (precision == PRISIM_FP32);
   pl.kernel = kernel;
   if (kernel == PRISIM_KERNEL_AUTO) pl.kernel = ctx->uniform ? PRISIM_KERNEL_RECURRENCE : PRISIM_KERNEL_DIRECT;
-  const int64_t nbl = ctx->nbl, nchan = ctx->nchan, nsrc = ctx->nsrc;
+  const int64_t nbl = ctx->nbl_sum, nchan = ctx->nchan, nsrc = ctx->nsrc;      // (the rows the sky-sum computes: baseline folding)
   pl.nbgroups = (int)((nbl + kBlockThreads - 1) / kBlockThreads);
   // channel tile: the cheapest tile (seed + 5 instructions per term, tiles past nchan are wasted work) that still yields enough
   // blocks to fill 256 CUs x 4 blocks
@@ -262,7 +262,7 @@ void prisim_hip_destroy(prisim_ctx* ctx) {
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   if (ctx->fft_plan && g_rocfft.plan_destroy) g_rocfft.plan_destroy(ctx->fft_plan);
   if (ctx->fft_info && g_rocfft.execution_info_destroy) g_rocfft.execution_info_destroy(ctx->fft_info);
-  for (DevBuf* b : {&ctx->blx, &ctx->bly, &ctx->blz, &ctx->freqs, &ctx->fsq, &ctx->fsq_pairs, &ctx->cube, &ctx->grad, &ctx->dirs,
+  for (DevBuf* b : {&ctx->blx, &ctx->bly, &ctx->blz, &ctx->ublx, &ctx->ubly, &ctx->ublz, &ctx->fold_map, &ctx->fold_vis, &ctx->fold_grad, &ctx->freqs, &ctx->fsq, &ctx->fsq_pairs, &ctx->cube, &ctx->grad, &ctx->dirs,
                     &ctx->partial, &ctx->scratch, &ctx->gathered, &ctx->sendbuf, &ctx->shard_map, &ctx->stage_main, &ctx->stage_comm, &ctx->ext_table,
                     &ctx->ext_work, &ctx->ext_colmax, &ctx->sky_flux, &ctx->sky_sp, &ctx->sky_bf, &ctx->sky_flag,
                     &ctx->dl_stage, &ctx->grp_hz, &ctx->fft_work, &ctx->fft_buf, &ctx->dt_out, &ctx->dt_pow, &ctx->dt_wts, &ctx->dt_lag_all, &ctx->dt_pow_all, &ctx->dt_tw})
@@ -312,8 +312,39 @@ int prisim_hip_set_array(prisim_ctx* ctx, const double* bl_enu, int64_t nbl, con
     if (!std::isfinite(x[b]) || !std::isfinite(y[b]) || !std::isfinite(z[b]))
       return fail(ctx, PRISIM_EINVAL, "non-finite baseline component");
   }
+  // Fold map: rows of equal vectors are summed once and expanded into the cube (baseline_fold.h).  On when it removes at least an
+  // eighth of the rows and the folded array is still more than one baseline group, so that a folded context never enters the
+  // wave-item or batched small-array paths (those are chosen by ctx->nbl <= kBlockThreads).  PRISIM_HIP_FOLD=0: off (the A/B hook).
+  std::vector<int64_t> fold_rep;
+  std::vector<int32_t> fold_map;
+  fold_baselines(bl_enu, nbl, fold_rep, fold_map);
+  const int64_t nbl_u = (int64_t)fold_rep.size();
+  bool fold = nbl_u * 8 <= nbl * 7 && nbl_u > kBlockThreads;
+  if (const char* env = getenv("PRISIM_HIP_FOLD")) fold = fold && atoi(env) != 0;
+  const int64_t nbl_sum = fold ? nbl_u : nbl;
+  std::vector<double> ux, uy, uz;
+  if (fold) {
+    ux.resize((size_t)nbl_u); uy.resize((size_t)nbl_u); uz.resize((size_t)nbl_u);
+    for (int64_t u = 0; u < nbl_u; ++u) { ux[u] = x[fold_rep[u]]; uy[u] = y[fold_rep[u]]; uz[u] = z[fold_rep[u]]; }
+  }
+  const std::vector<double>&sx = fold ? ux : x, &sy = fold ? uy : y, &sz = fold ? uz : z;      // the array the sky-sum kernels see
   int rc;
   const size_t bb = (size_t)nbl * sizeof(double);
+  ctx->folded = false;
+  if (fold) {
+    const size_t ub = (size_t)nbl_u * sizeof(double);
+    if ((rc = ensure(ctx, ctx->ublx, ub)) || (rc = ensure(ctx, ctx->ubly, ub)) || (rc = ensure(ctx, ctx->ublz, ub)) ||
+        (rc = ensure(ctx, ctx->fold_map, (size_t)nbl * sizeof(int32_t))) ||
+        (rc = ensure(ctx, ctx->fold_vis, (size_t)nbl_u * nchan * 2 * sizeof(double))))
+      return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ublx.p, ux.data(), ub, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ubly.p, uy.data(), ub, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ublz.p, uz.data(), ub, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->fold_map.p, fold_map.data(), (size_t)nbl * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    for (DevBuf* b : {&ctx->ublx, &ctx->ubly, &ctx->ublz, &ctx->fold_map, &ctx->fold_vis}) release(*b);
+  }
+  release(ctx->fold_grad);           // (sized by compute() when a gradient is first asked for)
   if ((rc = ensure(ctx, ctx->blx, bb)) || (rc = ensure(ctx, ctx->bly, bb)) || (rc = ensure(ctx, ctx->blz, bb))) return rc;
   ctx->nchan_pad = round_up(nchan, 64);
   if ((rc = ensure(ctx, ctx->freqs, (size_t)nchan * sizeof(double)))) return rc;
@@ -328,20 +359,27 @@ int prisim_hip_set_array(prisim_ctx* ctx, const double* bl_enu, int64_t nbl, con
   HIPCHK(ctx, launch_fsq((const double*)ctx->freqs.p, (float*)ctx->fsq.p, nchan, ctx->nchan_pad, 1e-8, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->h_freqs.assign(freqs_hz, freqs_hz + nchan);
-  ctx->grp_maxlen.assign((size_t)((nbl + kBlockThreads - 1) / kBlockThreads), 0.0);
+  // (last_lift_groups is reported in the caller's units, groups of 256 cube rows: their longest baselines, folded or not)
+  ctx->row_grp_maxlen.assign((size_t)((nbl + kBlockThreads - 1) / kBlockThreads), 0.0);
+  for (int64_t b = 0; b < nbl; ++b) {
+    const double len = std::sqrt(x[b] * x[b] + y[b] * y[b] + z[b] * z[b]);
+    const size_t g = (size_t)(b / kBlockThreads);
+    if (len > ctx->row_grp_maxlen[g]) ctx->row_grp_maxlen[g] = len;
+  }
+  ctx->grp_maxlen.assign((size_t)((nbl_sum + kBlockThreads - 1) / kBlockThreads), 0.0);
   ctx->grp_maxh.assign(ctx->grp_maxlen.size(), 0.0);
   ctx->grp_maxz.assign(ctx->grp_maxlen.size(), 0.0);
   ctx->grp_minh.assign(ctx->grp_maxlen.size(), 1e300);
   ctx->fsq_pairs_ct = ctx->fsq_pairs_ntiles = -1;
   for (SkyBufs& k : ctx->skb) k.lift_key_k = -1.0;             // the cached lifting flags belong to the previous array
-  for (int64_t b = 0; b < nbl; ++b) {
-    const double len = std::sqrt(x[b] * x[b] + y[b] * y[b] + z[b] * z[b]);
+  for (int64_t b = 0; b < nbl_sum; ++b) {
+    const double len = std::sqrt(sx[b] * sx[b] + sy[b] * sy[b] + sz[b] * sz[b]);
     const size_t g = (size_t)(b / kBlockThreads);
     if (len > ctx->grp_maxlen[g]) ctx->grp_maxlen[g] = len;
-    const double hl = std::sqrt(x[b] * x[b] + y[b] * y[b]);
+    const double hl = std::sqrt(sx[b] * sx[b] + sy[b] * sy[b]);
     if (hl < ctx->grp_minh[g]) ctx->grp_minh[g] = hl;
     if (hl > ctx->grp_maxh[g]) ctx->grp_maxh[g] = hl;
-    if (std::fabs(z[b]) > ctx->grp_maxz[g]) ctx->grp_maxz[g] = std::fabs(z[b]);
+    if (std::fabs(sz[b]) > ctx->grp_maxz[g]) ctx->grp_maxz[g] = std::fabs(sz[b]);
   }
   {
     const size_t ng = ctx->grp_maxh.size();
@@ -351,6 +389,7 @@ int prisim_hip_set_array(prisim_ctx* ctx, const double* bl_enu, int64_t nbl, con
     HIPCHK(ctx, hipMemcpy(ctx->grp_hz.p, hz.data(), 4 * ng * sizeof(double), hipMemcpyHostToDevice));
   }
   ctx->nbl = nbl; ctx->nchan = nchan; ctx->nt_max = nt_max;
+  ctx->nbl_sum = nbl_sum; ctx->folded = fold;
   // uniform channel grid?  f_k = f0 + k*df to within 1e-7 Hz (phase error <= 1e-13 cycles at 1 us delay)
   ctx->f0 = freqs_hz[0];
   ctx->df = nchan > 1 ? (freqs_hz[nchan - 1] - freqs_hz[0]) / (double)(nchan - 1) : 0.0;
@@ -496,7 +535,7 @@ int upload_common(prisim_ctx* ctx, int64_t nsrc, const double* dircos, const dou
               tab[(pr * nruns + r) * ng + g] = (int32_t)sfirst;
               if (sfirst > run.lo) {
                 ctx->cull_any[pr] = true;
-                const int64_t nb = std::min<int64_t>(kBlockThreads, ctx->nbl - (int64_t)g * kBlockThreads);
+                const int64_t nb = std::min<int64_t>(kBlockThreads, ctx->nbl_sum - (int64_t)g * kBlockThreads);
                 culled[pr] += (double)(sfirst - run.lo) * (double)nb;
               }
             }
@@ -506,7 +545,7 @@ int upload_common(prisim_ctx* ctx, int64_t nsrc, const double* dircos, const dou
           if ((rc = ensure(ctx, ctx->sk->cull_first, 2 * nruns * ng * sizeof(int32_t)))) return rc;
           HIPCHK(ctx, stage_send(ctx, ctx->sk->cull_first.p, tab, 2 * nruns * ng * sizeof(int32_t)));
           ctx->cull_nruns = (int)nruns;
-          for (int pr = 0; pr < 2; ++pr) ctx->cull_frac[pr] = culled[pr] / ((double)nsrc * (double)ctx->nbl);
+          for (int pr = 0; pr < 2; ++pr) ctx->cull_frac[pr] = culled[pr] / ((double)nsrc * (double)ctx->nbl_sum);
         }
       }
     }
@@ -843,8 +882,9 @@ int prisim_hip_get_pbflux(prisim_ctx* ctx, double* out) {
 
 // kernel parameters common to every sky-sum launch of the current array / sky / plan
 static void fill_params(prisim_ctx* ctx, const Plan& pl, SkyvisParams& p) {
-  p.bl_x = (const double*)ctx->blx.p; p.bl_y = (const double*)ctx->bly.p; p.bl_z = (const double*)ctx->blz.p;
-  p.nbl = ctx->nbl; p.nchan = ctx->nchan;
+  if (ctx->folded) { p.bl_x = (const double*)ctx->ublx.p; p.bl_y = (const double*)ctx->ubly.p; p.bl_z = (const double*)ctx->ublz.p; }
+  else { p.bl_x = (const double*)ctx->blx.p; p.bl_y = (const double*)ctx->bly.p; p.bl_z = (const double*)ctx->blz.p; }
+  p.nbl = ctx->nbl_sum; p.nchan = ctx->nchan;
   p.f0 = ctx->f0; p.df = ctx->df; p.inv_c = 1.0 / kC;
   p.dirs = ctx->dirs_p;
   p.dirs_prep = (const double*)ctx->sk->dirs_prep.p;
@@ -936,7 +976,7 @@ static bool taper_split_plan(prisim_ctx* ctx, const Plan& pl, const SkyvisParams
   return true;
 }
 
-// one sky-sum pass into `dst` ([nbl][nchan] complex128); scale_comp >= 0 multiplies pbflux rows by dircos[:,comp]
+// one sky-sum pass into `dst` ([nbl_sum][nchan] complex128: the cube slot, or the compact buffer of a folded array); scale_comp >= 0 multiplies pbflux rows by dircos[:,comp]
 // Wave items (k_skyvis_taper_f64_wave): the grouped fp64 taper kernel on an array of one baseline group whose sources are split.
 // PRISIM_HIP_WAVE_ITEMS=0: block items (the A/B baseline).
 static bool wave_items(const prisim_ctx* ctx, const Plan& pl) {
@@ -993,7 +1033,7 @@ static int run_pass(prisim_ctx* ctx, const Plan& pl, double* dst, int scale_comp
   // fp32 kernels whose splits each flush exactly once store their partial sums as complex64: half the partial traffic
   const bool part_f32 = pl.nsplit > 1 && pl.f32 && pl.kernel == PRISIM_KERNEL_RECURRENCE && max_per <= (int64_t)p.flush_src;
   p.out_f32 = part_f32 ? 1 : 0;
-  const size_t set_reals = (size_t)pl.nsplit * (size_t)ctx->nbl * (size_t)ctx->nchan * 2;       // reals of one run's partial cubes
+  const size_t set_reals = (size_t)pl.nsplit * (size_t)ctx->nbl_sum * (size_t)ctx->nchan * 2;       // reals of one run's partial cubes
   auto set_out = [&](size_t r) -> double* {
     if (nsets == 1) return p.out;
     return part_f32 ? (double*)((float*)ctx->partial.p + r * set_reals) : (double*)ctx->partial.p + r * set_reals;
@@ -1081,11 +1121,11 @@ static int run_pass(prisim_ctx* ctx, const Plan& pl, double* dst, int scale_comp
   }
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k1[ctx->ring_head], ctx->stream));
   if (pl.nsplit > 1)
-    HIPCHK(ctx, launch_reduce_partials(ctx->partial.p, part_f32, dst, ctx->nbl * ctx->nchan * 2, pl.nsplit * nsets, ctx->stream));
+    HIPCHK(ctx, launch_reduce_partials(ctx->partial.p, part_f32, dst, ctx->nbl_sum * ctx->nchan * 2, pl.nsplit * nsets, ctx->stream));
   return PRISIM_OK;
 }
 
-// V + the three baseline-gradient sums of one snapshot in one pass: dst [nbl][nchan], gdst [3][nbl][nchan] complex128.
+// V + the three baseline-gradient sums of one snapshot in one pass: dst [nbl_sum][nchan], gdst [3][nbl_sum][nchan] complex128.
 // fp64: k_skyvis_grad_f64 (MFMA 4x4x4, groups of 64 baselines); fp32: the GRAD bodies of the packed kernel (16-channel tiles).
 static int run_grad_pass(prisim_ctx* ctx, const Plan& pl, double* dst, double* gdst) {
   SkyvisParams p{};
@@ -1112,7 +1152,7 @@ static int run_grad_pass(prisim_ctx* ctx, const Plan& pl, double* dst, double* g
     p.dirs_c32 = (const float*)ctx->sk->dirs_c32.p;
     HIPCHK(ctx, launch_skyvis_grad_f32(p, ctx->stream));
   } else {
-    p.nbgroups = (int)((ctx->nbl + 63) / 64);      // the MFMA kernel's blocks own 64 baselines; lift flags stay per 256 (it reads [group >> 2])
+    p.nbgroups = (int)((ctx->nbl_sum + 63) / 64);      // the MFMA kernel's blocks own 64 baselines; lift flags stay per 256 (it reads [group >> 2])
     HIPCHK(ctx, launch_skyvis_grad_f64(p, pl.ct, ctx->stream));
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev_k1[ctx->ring_head], ctx->stream));
@@ -1145,9 +1185,19 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
     if (want_grad)
       HIPCHK(ctx, hipMemsetAsync((double*)ctx->grad.p + (size_t)slot * 3 * slot_elems, 0, 3 * slot_elems * sizeof(double), ctx->stream));
     ctx->timing.last_terms = 0;
+    ctx->last_sum_baselines = ctx->nbl_sum; ctx->last_terms_evaluated = 0;
     catalog_after_compute(ctx);      // (an empty region of interest still releases the catalogue's buffer set in stream order)
     return PRISIM_OK;
   }
+  // A folded array (set_array): everything below sums the nbl_sum distinct vectors into the compact buffers, and k_expand_rows copies
+  // compact row fold_map[b] into row b of the slot (and of its gradient block) at the end.
+  const size_t sum_elems = (size_t)ctx->nbl_sum * ctx->nchan * 2;
+  double* const slot_dst = dst;
+  if (ctx->folded) {
+    dst = (double*)ctx->fold_vis.p;
+    if (want_grad && (rc = ensure(ctx, ctx->fold_grad, 3 * sum_elems * sizeof(double)))) return rc;
+  }
+  double* const gbase = !want_grad ? nullptr : ctx->folded ? (double*)ctx->fold_grad.p : (double*)ctx->grad.p + (size_t)slot * 3 * slot_elems;
   Plan pl = make_plan(ctx, precision, kernel);
   // Visibility + baseline gradient on a uniform channel grid: ONE fused pass -- fp64: the MFMA kernel k_skyvis_grad_f64 (2.4 x a plain
   // fp64 pass instead of 4 x); fp32: the GRAD bodies of the packed kernel on 16-channel tiles (13 packed instructions per pair of terms
@@ -1168,6 +1218,7 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
     pl.src_per_split = pl.nsrc_pad;
   }
   ctx->timing.last_lift_groups = 0;
+  ctx->last_sum_lift_groups = 0;
   ctx->timing.last_taper_group = 0;
   ctx->timing.last_taper_split = 0;
   ctx->timing.last_split_uncorrected_groups = 0;
@@ -1179,7 +1230,7 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
     if ((rc = ensure(ctx, ctx->sk->dirs_prep, (size_t)pl.nsrc_pad * 4 * sizeof(double)))) return rc;
     // (a sky of several runs of one source size writes one set of partial cubes per run: run_pass)
     const size_t part_sets = (ctx->taper && ctx->kappa_runs.size() > 1 && ctx->kappa_runs.size() <= (size_t)kMaxRunSets) ? ctx->kappa_runs.size() : 1;
-    if (pl.nsplit > 1 && (rc = ensure(ctx, ctx->partial, part_sets * (size_t)pl.nsplit * slot_elems * sizeof(double)))) return rc;
+    if (pl.nsplit > 1 && (rc = ensure(ctx, ctx->partial, part_sets * (size_t)pl.nsplit * sum_elems * sizeof(double)))) return rc;
     {
       // lifting rotation is used for a baseline group only when |step phase| <= 1/8 cycle (fp32; 1/4 cycle in fp64, where the
       // angle error alpha*eps is irrelevant and only tan(alpha/2) must stay bounded) is guaranteed for every source:
@@ -1196,11 +1247,17 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
         ctx->sk->lift_key_f32 = (int)pl.f32;
         ctx->sk->lift_groups = pl.nbgroups;
       }
-      int nlift = 0;
-      for (int g = 0; g < pl.nbgroups; ++g) nlift += (ctx->grp_maxlen[(size_t)g] * k <= lift_limit) ? 1 : 0;
+      // Reported per group of 256 CUBE rows (the caller's units): the groups whose longest baseline is within the limit.  Unfolded that
+      // is the kernel's own flag count.  On a folded array the kernel's flags are per group of 256 SUMMED rows (last_sum_lift_groups,
+      // prisim_hip_get_fold_info); a cube row within the limit whose vector shares a summed group with a longer one runs the plain
+      // rotation, which is valid for every step angle.
+      int nlift = 0, nlift_sum = 0;
+      for (double len : ctx->row_grp_maxlen) nlift += (len * k <= lift_limit) ? 1 : 0;
+      for (int g = 0; g < pl.nbgroups; ++g) nlift_sum += (ctx->grp_maxlen[(size_t)g] * k <= lift_limit) ? 1 : 0;
       // the packed taper kernel folds the amplitude into the phasor (a scaled rotation: no lifting there, the flags only select its
       // re-anchored body); every other kernel lifts the flagged groups
       ctx->timing.last_lift_groups = (ctx->taper && pl.pk) ? 0 : nlift;
+      ctx->last_sum_lift_groups = (ctx->taper && pl.pk) ? 0 : nlift_sum;
     }
     if (pl.f32 && ctx->taper) {
       if ((rc = ensure(ctx, ctx->fsq_pairs, (size_t)pl.ntiles * pl.ct * sizeof(float)))) return rc;
@@ -1221,16 +1278,20 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
                                  ctx->pc[1], ctx->pc[2], 1.0 / kC, pstream(ctx)));
   }
   if (fused_grad) {
-    if ((rc = run_grad_pass(ctx, pl, dst, (double*)ctx->grad.p + (size_t)slot * 3 * slot_elems))) return rc;
+    if ((rc = run_grad_pass(ctx, pl, dst, gbase))) return rc;
   } else if ((rc = run_pass(ctx, pl, dst, -1, true, /*prep=*/true))) {      // (prepares the directions with its first launch)
     return rc;
   }
   if (want_grad && !fused_grad) {
     for (int comp = 0; comp < 3; ++comp) {
-      double* gdst = (double*)ctx->grad.p + ((size_t)slot * 3 + comp) * slot_elems;
+      double* gdst = gbase + (size_t)comp * sum_elems;
       if ((rc = run_pass(ctx, pl, gdst, comp, false))) return rc;
     }
   }
+  if (ctx->folded)      // inside last_compute_ms; last_kernel_ms stays the sky-sum alone
+    HIPCHK(ctx, launch_expand_rows(dst, gbase, (const int32_t*)ctx->fold_map.p, slot_dst,
+                                   want_grad ? (double*)ctx->grad.p + (size_t)slot * 3 * slot_elems : nullptr, ctx->nbl, ctx->nbl_sum, ctx->nchan,
+                                   ctx->stream));
   HIPCHK(ctx, hipEventRecord(ctx->ev_c1[ctx->ring_head], ctx->stream));
   if (ctx->prep_async) {
     HIPCHK(ctx, hipEventRecord(ctx->sk->ev_sum, ctx->stream));
@@ -1239,7 +1300,9 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
   catalog_after_compute(ctx);
   ctx->ring_head = (ctx->ring_head + 1) % prisim_ctx::kTimingRing;
   ctx->ring_pending += 1;
-  ctx->timing.last_terms = ctx->nbl * ctx->nchan * ctx->nsrc;
+  ctx->timing.last_terms = ctx->nbl * ctx->nchan * ctx->nsrc;          // delivered; the kernels evaluated nbl_sum rows of them
+  ctx->last_sum_baselines = ctx->nbl_sum;
+  ctx->last_terms_evaluated = ctx->nbl_sum * ctx->nchan * ctx->nsrc;
   ctx->timing.last_kernel_id = pl.kernel;
   ctx->timing.last_chan_tile = pl.kernel == PRISIM_KERNEL_RECURRENCE ? pl.ct : 1;
   ctx->timing.last_nsplit = pl.kernel == PRISIM_KERNEL_RECURRENCE ? pl.nsplit : 1;
@@ -1350,6 +1413,16 @@ int prisim_hip_get_timing(prisim_ctx* ctx, prisim_timing* out, int reset) {
   }
   *out = ctx->timing;
   if (reset) { ctx->timing.sum_kernel_ms = 0.0; ctx->timing.n_kernel = 0; }
+  return PRISIM_OK;
+  });
+}
+
+int prisim_hip_get_fold_info(prisim_ctx* ctx, int64_t* last_sum_baselines, int64_t* last_terms_evaluated, int64_t* last_sum_lift_groups) {
+  return guarded(ctx, [&]() -> int {
+  if (!ctx) return PRISIM_EINVAL;
+  if (last_sum_baselines) *last_sum_baselines = ctx->last_sum_baselines;
+  if (last_terms_evaluated) *last_terms_evaluated = ctx->last_terms_evaluated;
+  if (last_sum_lift_groups) *last_sum_lift_groups = ctx->last_sum_lift_groups;
   return PRISIM_OK;
   });
 }

@@ -372,7 +372,7 @@ int activate_snapshot(prisim_ctx* ctx, const prisim_obs* obs, const prisim_snaps
       cp.grp_maxz = (const double*)ctx->grp_hz.p + ng;
       cp.grp_minh = (const double*)ctx->grp_hz.p + 3 * ng;
       cp.fc2 = fc2;
-      cp.nbl = ctx->nbl;
+      cp.nbl = ctx->nbl_sum;         // (the groups are those of the array the sky-sum sees)
       if ((rc = ensure(ctx, ctx->sk->cull_first, 2 * (size_t)ncr * ng * sizeof(int32_t))) || (rc = ensure(ctx, C.culled, 2 * sizeof(uint64_t)))) return rc;
       cp.first = (int32_t*)ctx->sk->cull_first.p;
       cp.culled = (uint64_t*)C.culled.p;
@@ -643,10 +643,12 @@ int run_wave_batch(prisim_ctx* ctx, const prisim_obs* obs, const prisim_snapshot
     ntot += N;
   }
   ctx->timing.last_terms = ctx->nbl * ctx->nchan * ntot;
+  ctx->last_sum_baselines = ctx->nbl; ctx->last_terms_evaluated = ctx->timing.last_terms;      // (arrays of <= 256 baselines never fold)
   ctx->timing.last_kernel_id = PRISIM_KERNEL_RECURRENCE;
   ctx->timing.last_chan_tile = ct;
   ctx->timing.last_nsplit = (int32_t)nsplit;
   ctx->timing.last_lift_groups = 0;
+  ctx->last_sum_lift_groups = 0;
   ctx->timing.last_taper_group = 0;
   ctx->timing.last_taper_split = 0;
   ctx->timing.last_split_uncorrected_groups = 0;

@@ -18,6 +18,7 @@
 
 #include "../../include/prisim_hip.h"
 #include "skyvis_kernels.h"
+#include "baseline_fold.h"
 
 using namespace prisim;
 
@@ -117,7 +118,16 @@ struct prisim_ctx {
   bool array_set = false;
   int64_t nbl = 0, nchan = 0, nt_max = 0;
   DevBuf blx, bly, blz, freqs, fsq, fsq_pairs, cube, grad;
-  std::vector<double> grp_maxlen;     // max |b| per group of kBlockThreads baselines (lifting-rotation guarantee)
+  // Baseline folding (baseline_fold.h): rows of equal baseline vectors are summed once.  When `folded`, the sky-sum kernels see the
+  // nbl_sum distinct vectors (ublx/y/z, in order of first appearance), write the compact buffers fold_vis [nbl_sum][nchan] /
+  // fold_grad [3][nbl_sum][nchan] complex128, and k_expand_rows copies compact row fold_map[b] into cube row b.  nbl stays the
+  // caller's count (cube, gathers, delay transform, noise); the per-group tables below (grp_*) are those of the array the kernels see.
+  bool folded = false;
+  int64_t nbl_sum = 0;                // rows the sky-sum computes: distinct vectors when folded, nbl otherwise
+  DevBuf ublx, ubly, ublz, fold_map, fold_vis, fold_grad;
+  int64_t last_sum_baselines = 0, last_terms_evaluated = 0, last_sum_lift_groups = 0;      // of the last compute() (prisim_hip_get_fold_info)
+  std::vector<double> row_grp_maxlen; // max |b| per group of kBlockThreads CUBE rows: the units last_lift_groups is reported in
+  std::vector<double> grp_maxlen;    // max |b| per group of kBlockThreads baselines (lifting-rotation guarantee)
   std::vector<double> grp_maxh, grp_maxz;   // max horizontal length / max |b_z| per group (bound of the split taper's parabola)
   std::vector<double> grp_minh;             // min horizontal length per group (taper culling)
   // Taper culling: cull_first[prec][run][group] = first source of the run that group still has to sum (device, int32); the sources before

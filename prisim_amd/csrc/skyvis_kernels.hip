@@ -2150,6 +2150,30 @@ __global__ void k_reduce_partials(const TP* __restrict__ part, double* __restric
   }
 }
 
+// Expansion of a folded array's sums: cube row b = compact row map[b].  Destination-major: a wavefront owns a row at a time (its map
+// entry is wave-uniform) and every instruction writes 64 double2 = 1 KiB contiguous.  blockIdx.y = plane: 0 the visibilities, 1..3 the
+// gradient components.  Only rows [0, nbl) of the addressed slot are written.
+__global__ void __launch_bounds__(256) k_expand_rows(const double2* __restrict__ vis_c, const double2* __restrict__ grad_c,
+                                                     const int32_t* __restrict__ map, double2* __restrict__ vis_out,
+                                                     double2* __restrict__ grad_out, int64_t nbl, int64_t nbl_sum, int64_t nchan) {
+  const int plane = blockIdx.y;
+  const double2* __restrict__ src = plane == 0 ? vis_c : grad_c + (size_t)(plane - 1) * (size_t)nbl_sum * (size_t)nchan;
+  double2* __restrict__ dst = plane == 0 ? vis_out : grad_out + (size_t)(plane - 1) * (size_t)nbl * (size_t)nchan;
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t b = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); b < nbl; b += nwaves) {
+    const int64_t u = __builtin_amdgcn_readfirstlane(map[b]);
+    const double2* __restrict__ in = src + (size_t)u * (size_t)nchan;
+    double2* __restrict__ out = dst + (size_t)b * (size_t)nchan;
+    int64_t k = lane;
+    for (; k + 192 < nchan; k += 256) {              // four loads in flight per lane
+      const double2 a0 = in[k], a1 = in[k + 64], a2 = in[k + 128], a3 = in[k + 192];
+      out[k] = a0; out[k + 64] = a1; out[k + 128] = a2; out[k + 192] = a3;
+    }
+    for (; k < nchan; k += 64) out[k] = in[k];
+  }
+}
+
 __global__ void k_f32_to_f64(const float* __restrict__ in, double* __restrict__ out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     out[i] = (double)in[i];
@@ -2400,6 +2424,15 @@ hipError_t launch_reduce_partials(const void* part, bool part_f32, double* out, 
     hipLaunchKernelGGL(k_reduce_partials<float>, dim3(grid_for(n2)), dim3(256), 0, stream, (const float*)part, out, n2, nsplit);
   else
     hipLaunchKernelGGL(k_reduce_partials<double>, dim3(grid_for(n2)), dim3(256), 0, stream, (const double*)part, out, n2, nsplit);
+  return hipGetLastError();
+}
+
+hipError_t launch_expand_rows(const double* vis_c, const double* grad_c, const int32_t* map, double* vis_out, double* grad_out, int64_t nbl,
+                              int64_t nbl_sum, int64_t nchan, hipStream_t stream) {
+  if (nbl <= 0 || nchan <= 0) return hipSuccess;
+  const bool grad = grad_c && grad_out;
+  hipLaunchKernelGGL(k_expand_rows, dim3(grid_for(nbl * 64), grad ? 4 : 1), dim3(256), 0, stream, (const double2*)vis_c, (const double2*)grad_c, map,
+                     (double2*)vis_out, (double2*)grad_out, nbl, nbl_sum, nchan);
   return hipGetLastError();
 }
 
