@@ -95,6 +95,11 @@ CPXPS_EXPORTS = ('prisim_cphase_xpower',)
 PRISIM_CPXPS_MAX_MEDIAN = 256
 CPXPS_MODES = {'none': 0, 'full': 1, 'collapse': 2}
 CPXPS_STATS = {'mean': 0, 'median': 1}
+# every symbol include/prisim_cpavg.h declares: incoherent averages of closure-phase power spectra (prisim_amd/csrc_closure/cpavg.hip)
+CPAVG_EXPORTS = ('prisim_cphase_xavg', 'prisim_cphase_kbin')
+PRISIM_CPAVG_MIN_DIM, PRISIM_CPAVG_MAX_DIM = 5, 8
+PRISIM_CPAVG_AUTO, PRISIM_CPAVG_LDS, PRISIM_CPAVG_GLOBAL = -1, 0, 1
+CPAVG_ROUTES = {PRISIM_CPAVG_LDS: 'lds', PRISIM_CPAVG_GLOBAL: 'global'}
 
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
@@ -268,6 +273,13 @@ class _PrisimCpxpsStats(C.Structure):
                 ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('cross_bytes', C.c_int64)]
 
 
+class _PrisimCpavgStats(C.Structure):
+    """prisim_cpavg_stats of both entries of include/prisim_cpavg.h, public as Context.PrisimCpavgStats (see _PrisimCpxpsStats);
+    tests/test_cpavg.py holds it to the header."""
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('chunks', C.c_int64), ('kernel_bytes', C.c_int64),
+                ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('route', C.c_int32), ('lds_limit', C.c_int32)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -436,6 +448,10 @@ def load_library():
     lib.prisim_cphase_xpower.argtypes = [vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, C.c_int32, vp, C.c_int32, i64, vp,
                                          C.POINTER(_PrisimCpxpsStats)]
     lib.prisim_cphase_xpower.restype = C.c_int
+    lib.prisim_cphase_xavg.argtypes = [vp, C.c_int32, vp, i64, vp, vp, vp, C.c_int32, vp, vp, i64, vp, vp, vp, vp, C.POINTER(_PrisimCpavgStats)]
+    lib.prisim_cphase_kbin.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, C.c_int32, i64, vp, vp, vp, C.POINTER(_PrisimCpavgStats)]
+    for name in CPAVG_EXPORTS:
+        getattr(lib, name).restype = C.c_int
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
                                              C.POINTER(vp), pst]
@@ -1488,6 +1504,130 @@ class Context(object):
             self._h, nspw, a.shape[1], a.shape[2], a.shape[3], a.shape[4], _ptr(a), _ptr(b), _ptr(f), wptr, _ptr(mcodes), nshift, _ptr(sh),
             order.size, _ptr(order), scode, int(budget_bytes), _ptr(out), C.byref(st)), 'prisim_cphase_xpower')
         return {'out': out, 'stats': _stats_dict(st)}
+
+    # ---- incoherent averages of closure-phase power spectra (include/prisim_cpavg.h) ----
+    PrisimCpavgStats = _PrisimCpavgStats
+
+    @staticmethod
+    def cphase_xavg_arguments(arrays, weights, combos=()):
+        """The checked arguments of cphase_xavg: (arrays complex128, weights float64, masks), masks a list of {axis: uint8 mask}.
+        ValueError where the header would refuse them."""
+        arrays = [NP.ascontiguousarray(a, dtype=NP.complex128) for a in arrays]
+        weights = [NP.ascontiguousarray(w, dtype=NP.float64) for w in weights]
+        if len(arrays) < 1 or len(weights) != len(arrays):
+            raise ValueError('need at least one array and one weight array per array')
+        shape = arrays[0].shape
+        ndim = len(shape)
+        if not PRISIM_CPAVG_MIN_DIM <= ndim <= PRISIM_CPAVG_MAX_DIM:
+            raise ValueError('the arrays must have {0} to {1} axes'.format(PRISIM_CPAVG_MIN_DIM, PRISIM_CPAVG_MAX_DIM))
+        if min(shape) < 1:
+            raise ValueError('every axis needs at least one entry')
+        for a, w in zip(arrays, weights):
+            if a.shape != shape:
+                raise ValueError('the arrays must have one shape')
+            if w.ndim != ndim or w.shape[-1] != 1 or any(b not in (1, n) for b, n in zip(w.shape, shape)):
+                raise ValueError('weights of shape {0} do not broadcast against {1} with 1 on the lags'.format(w.shape, shape))
+        masks = []
+        for combo in combos:
+            if len(combo) < 1:
+                raise ValueError('a combination must reduce at least one axis')
+            mk = {}
+            for ax, sel in combo.items():
+                ax = int(ax)
+                if not 0 < ax < ndim - 1:
+                    raise ValueError('a combination cannot reduce axis {0}: neither the windows nor the lags'.format(ax))
+                sel = NP.ascontiguousarray(NP.asarray(sel).astype(bool).reshape(-1), dtype=NP.uint8)
+                if sel.size != shape[ax] or not sel.any():
+                    raise ValueError('the mask of axis {0} must have {1} entries and select at least one'.format(ax, shape[ax]))
+                mk[ax] = sel
+            masks.append(mk)
+        return arrays, weights, masks
+
+    @staticmethod
+    def cphase_xavg_shapes(shape, wshapes, masks):
+        """(U, [shape of out], [shape of wout]) of cphase_xavg: the common shape of the weights and the results per combination"""
+        u = tuple(int(max(ws[x] for ws in wshapes)) for x in range(len(shape)))
+        oshapes = [tuple(1 if x in mk else int(n) for x, n in enumerate(shape)) for mk in masks]
+        woshapes = [tuple(1 if x in mk else n for x, n in enumerate(u)) for mk in masks]
+        return u, oshapes, woshapes
+
+    def cphase_xavg(self, arrays, weights, combos=(), want_avg=True, budget_bytes=0):
+        """The weighted average of several arrays and averages of it over selected positions, on the device (prisim_cphase_xavg).
+        arrays: complex, one shape of 5 to 8 axes, axis 0 the windows and the last the lags; weights: per array a float array with
+        every extent 1 or the array's and 1 on the lags; combos: dictionaries {axis: boolean mask of the selected positions}.
+        Returns {'avg': sum(a w) / sum(w) with NaN products counted as 0 (None unless want_avg), 'wsum': sum(w) at the common shape
+        of the weights, 'out': per combination (sum of avg wsum) / (sum of wsum) over its positions, the reduced axes kept at 1,
+        'wout': those sums of wsum, 'stats'}."""
+        arrays, weights, masks = self.cphase_xavg_arguments(arrays, weights, combos)
+        shape = arrays[0].shape
+        ndim, nsets, ncombo = len(shape), len(arrays), len(masks)
+        wshapes = NP.ascontiguousarray([w.shape for w in weights], dtype=NP.int64)
+        u, oshapes, woshapes = self.cphase_xavg_shapes(shape, wshapes, masks)
+        avg = NP.empty(shape, dtype=NP.complex128) if want_avg else None
+        wsum = NP.empty(u, dtype=NP.float64)
+        out = [NP.empty(s, dtype=NP.complex128) for s in oshapes]
+        wout = [NP.empty(s, dtype=NP.float64) for s in woshapes]
+        reduce = NP.zeros((max(ncombo, 1), ndim), dtype=NP.int32)
+        mptr = (C.c_void_p * max(ncombo * ndim, 1))()
+        for c, mk in enumerate(masks):
+            for ax, sel in mk.items():
+                reduce[c, ax] = 1
+                mptr[c * ndim + ax] = sel.ctypes.data
+
+        def pointers(xs):
+            return (C.c_void_p * max(len(xs), 1))(*[x.ctypes.data for x in xs])
+
+        st = self.PrisimCpavgStats()
+        self._check(self._lib.prisim_cphase_xavg(
+            self._h, ndim, _ptr(NP.ascontiguousarray(shape, dtype=NP.int64)), nsets, pointers(arrays), pointers(weights), _ptr(wshapes),
+            ncombo, _ptr(reduce), mptr, int(budget_bytes), _ptr(avg), _ptr(wsum), pointers(out), pointers(wout), C.byref(st)),
+            'prisim_cphase_xavg')
+        return {'avg': avg, 'wsum': wsum, 'out': out, 'wout': wout, 'stats': _stats_dict(st, route=CPAVG_ROUTES)}
+
+    @staticmethod
+    def cphase_kbin_arguments(p, kprll, offsets, members):
+        """The checked arguments of cphase_kbin: (p complex128 (nspw, m, nlags), kprll, offsets int64 (nspw, nk + 1), the members of all
+        windows int32, the leading shape of p).  ValueError where the header would refuse them."""
+        p = NP.asarray(p)
+        k = NP.ascontiguousarray(kprll, dtype=NP.float64)
+        if k.ndim != 2 or p.ndim < 2 or p.shape[0] != k.shape[0] or p.shape[-1] != k.shape[1] or p.size < 1:
+            raise ValueError('p must be (nspw, ..., nlags) and kprll (nspw, nlags), none of them empty')
+        lead = p.shape[:-1]
+        p = NP.ascontiguousarray(p, dtype=NP.complex128).reshape(k.shape[0], -1, k.shape[1])
+        off = NP.ascontiguousarray(offsets, dtype=NP.int64)
+        if off.ndim != 2 or off.shape[0] != k.shape[0] or off.shape[1] < 2:
+            raise ValueError('offsets must be (nspw, nk + 1) with nk >= 1')
+        if len(members) != k.shape[0]:
+            raise ValueError('members must hold one array per window')
+        mem = [NP.asarray(m).reshape(-1) for m in members]
+        for w, m in enumerate(mem):
+            o = off[w]
+            if o[0] != 0 or NP.any(NP.diff(o) < 0) or o[-1] != m.size:
+                raise ValueError('window {0}: the offsets must start at 0, not decrease and end at the number of members'.format(w))
+            if m.size and (m.min() < 0 or m.max() >= k.shape[1]):
+                raise ValueError('window {0}: a member is not a lag in [0, {1})'.format(w, k.shape[1]))
+            for b in range(o.size - 1):
+                if NP.any(NP.diff(m[o[b]:o[b + 1]]) <= 0):
+                    raise ValueError('window {0}, bin {1}: the members must increase'.format(w, b))
+        allmem = NP.ascontiguousarray(NP.concatenate(mem) if mem else NP.zeros(0), dtype=NP.int32)
+        return p, k, off, allmem, lead
+
+    def cphase_kbin(self, p, kprll, offsets, members, route='auto', budget_bytes=0):
+        """Averages of a power spectrum in bins of |k_parallel| on the device (prisim_cphase_kbin).  p: complex (nspw, ..., nlags);
+        kprll (nspw, nlags); offsets (nspw, nk + 1) and members (one array of lag indices per window): per window the CSR pair of its
+        bins, the members of a bin increasing; route: 'auto', 'lds' or 'global'.  Returns {'ps': the mean of the members that are not
+        NaN, 'del2': the mean of |k|^3 p over 2 pi^2, 'kc': sum |k| |p| / sum |p|, each (nspw, ..., nk), NaN for an empty bin,
+        'stats'}."""
+        r = _route_code(route, CPAVG_ROUTES)
+        p, k, off, mem, lead = self.cphase_kbin_arguments(p, kprll, offsets, members)
+        nk = off.shape[1] - 1
+        ps = NP.empty(lead + (nk,), dtype=NP.complex128)
+        del2 = NP.empty(lead + (nk,), dtype=NP.complex128)
+        kc = NP.empty(lead + (nk,), dtype=NP.float64)
+        st = self.PrisimCpavgStats()
+        self._check(self._lib.prisim_cphase_kbin(self._h, p.shape[0], p.shape[1], p.shape[2], nk, _ptr(p), _ptr(k), _ptr(off), _ptr(mem), r,
+                                                 int(budget_bytes), _ptr(ps), _ptr(del2), _ptr(kc), C.byref(st)), 'prisim_cphase_kbin')
+        return {'ps': ps, 'del2': del2, 'kc': kc, 'stats': _stats_dict(st, route=CPAVG_ROUTES)}
 
     # ---- instrument gain tables (include/prisim_gains.h) ----
     def gains_eval_spline(self, packed, times, freqs):

@@ -4,7 +4,9 @@ prisim_amd/csrc_closure/cpbins.hip) and the differences of the day sub-samples t
 prisim_amd/csrc_closure/cpdiff.hip); and ClosurePhaseDelaySpectrum with its FT, the delay spectra of the binned phasors, of the
 residuals, of the sub-model and of the half differences on the GPU (include/prisim_cpft.h, prisim_amd/csrc_closure/cpft.hip), and with
 subset, compute_power_spectrum, compute_power_spectrum_uncertainty and beam3Dvol: the cross products of those spectra over pairs of LST
-bins, day bins and triads and their collapses on the GPU (include/prisim_cpxps.h, prisim_amd/csrc_closure/cpxps.hip).
+bins, day bins and triads and their collapses on the GPU (include/prisim_cpxps.h, prisim_amd/csrc_closure/cpxps.hip); and the
+module-level incoherent_cross_power_spectrum_average and incoherent_kbin_averaging: the weighted averages of those power spectra over
+data sets, diagonals and bins of |k_parallel| on the GPU (include/prisim_cpavg.h, prisim_amd/csrc_closure/cpavg.hip).
 
 Readings and departures
 - astropy is not a dependency.  The reference uses astropy.time.Time only to carry Julian dates, so loadnpz does that arithmetic
@@ -96,6 +98,37 @@ Readings and departures of subset, compute_power_spectrum (:2888-3601), compute_
 - beam3Dvol: delay_spectrum.beam3Dvol of delay_spectrum.healpix_power_pattern(freqs, telescope, nside) (the analytic pattern on the
   device), nside 64 and chromatic True by default; chromatic=False takes the pattern at select_freq, by default the mean of the
   frequencies.  A beamfile raises NotImplementedError: its formats need astropy or pyuvdata.
+
+Readings and departures of incoherent_cross_power_spectrum_average (:806-1231) and incoherent_kbin_averaging (:1235-1493).  Every error
+is raised before any device work, and the callers' dictionaries are not modified.
+- On the host, as O(input) bookkeeping: the broadcast weight arrays from 'diagweights' and 'axesmap', the masks of the selected
+  offsets, the bin edges and the CSR of the bins.  On the device: every sum -- one prisim_cphase_xavg call per sampling, pool and
+  statistic, one prisim_cphase_kbin call per sampling, pool, statistic and combination.  The results are plain numpy arrays without
+  units, never masked arrays.
+- excpdps=None: the reference raises a TypeError (:1124 indexes excpdps[0]); here the second result is None.
+- 'diagweights' is a dictionary, as compute_power_spectrum returns, or an ndarray, as this function returns, as in the reference; the
+  array must have the axes of the spectra, every extent 1 or the spectra's and 1 on the lags.  Axes of a dictionary that are absent
+  from that pool's 'diagoffsets' (the avgcov=True case) have weight 1; the reference would broadcast the averaged axis back to 2n - 1.
+  'diagoffsets' and 'axesmap' of the result are those of the first data set, as in the reference.
+- Each of these is a ValueError where the reference fails otherwise or returns masked values: an axis in diagoffsets that is not a
+  collapsed axis of the input (not a key of its 'diagoffsets'); a selection that matches no offset; diagoffsets for an axis whose
+  'diagweights' are missing (an empty 'diagweights' together with diagoffsets); data sets of different shapes.
+- Axis 2 of a combination is skipped for excpdps, as in the reference; a combination left with no axis returns the stage-1 array and
+  its weights (the reference multiplies and divides it by the weights).
+- Kept quirk of stage 1 (:1118): a NaN element contributes nothing to the weighted sum while its weight still counts in the
+  divisor, so it becomes 0 / weights.  The structural NaN of an LST axis that is crossed and not collapsed therefore come out as 0.
+  Stage 2 (MA.sum over the unmasked entries) propagates NaN.
+- 'lstXoffsets', which the reference drops, is carried into both results when the first data set has it.
+- incoherent_kbin_averaging: a statistic that is a bare array, because diagoffsets=None was used before, is taken as a list of one (the
+  reference iterates over its first axis).  kprll.shape[1] / 2 + 1 is read as //, as in Python 2.  With kbintype='log' and
+  num_kbins=None, num_kbins is 10.  -eps is inserted in front of the generated edges, so that bin 0 holds k = 0.  Explicit kbins are
+  used as given (at least two increasing edges, else a ValueError) and lags outside every bin are dropped.  Kept quirk: num_kbins is
+  overwritten with the number of bins of the sampling just binned (:1448), which counts the bin of k = 0, so with 'log' the resampled
+  spectra get one bin more than the oversampled ones.
+- 'kbininfo' carries 'counts', 'kbin_edges', 'kbinnum' and 'ri' exactly as binned_statistic_count reads OPS.binned_statistic: kbinnum
+  is 1 + the bin, 0 below the first edge and nbins + 1 from the last edge on.  Per bin the device walks the members in increasing lag:
+  the mean of the members that are not NaN, the mean of |k|^3 P over 2 pi^2 with |k|^3 = (|k| |k|) |k|, and sum |k| |P| / sum |P| with
+  each sum dropping its own NaN terms; an empty bin is NaN in all three.  The progress bar and the print are dropped.
 """
 import warnings
 
@@ -146,6 +179,15 @@ def binned_count(x, edges):
     counts = NP.asarray([m.size for m in members], dtype=NP.int64)
     ri = NP.concatenate([nbins + 1 + NP.concatenate(([0], NP.cumsum(counts)))] + members).astype(NP.int64)
     return counts, ri
+
+
+def binned_statistic_count(x, edges):
+    """(counts, edges, binnum, ri) as OPS.binned_statistic(x, statistic='count', bins=edges) returns them, in binned_count's reading:
+    binnum[i] is 1 + the bin of x[i], 0 below the first edge and nbins + 1 from the last edge on."""
+    x = NP.asarray(x, dtype=NP.float64).ravel()
+    edges = NP.asarray(edges, dtype=NP.float64).ravel()
+    counts, ri = binned_count(x, edges)
+    return counts, edges, NP.searchsorted(edges, x, side='right').astype(NP.int64), ri
 
 
 def _csr(lists):
@@ -250,6 +292,234 @@ def pairs_of_day_bin_pairs(ndaybins):
                     seen.add(((i, j), (k, m)))
                     out.append([i, j, k, m])
     return out
+
+
+_TOP_KEYS = ('triads', 'triads_ind', 'lst', 'lst_ind', 'dlst', 'days', 'day_ind', 'dday')
+_SAMPLING_KEYS = ('z', 'kprll', 'lags', 'freq_center', 'bw_eff', 'shape', 'freq_wts', 'lag_corr_length')
+
+
+def _diag_weights(pool, stat, where):
+    """The diagweights of one data set of a pool at a shape that broadcasts against its spectra: from the dictionary that
+    compute_power_spectrum returns (axes absent from the pool's diagoffsets have weight 1) or from the array that
+    incoherent_cross_power_spectrum_average returns"""
+    arr = NP.asarray(pool[stat])
+    dw = pool['diagweights']
+    if isinstance(dw, dict):
+        w = NP.ones((1,) * arr.ndim, dtype=NP.float64)
+        for ax in dw:
+            if ax not in pool.get('diagoffsets', {}):
+                continue
+            v = NP.asarray(dw[ax], dtype=NP.float64).reshape(-1)
+            pos = int(NP.asarray(pool['axesmap'][ax]).reshape(-1)[0])
+            if not 0 < pos < arr.ndim - 1 or v.size != arr.shape[pos]:
+                raise ValueError('{0}: the diagweights of axis {1} do not match the spectra'.format(where, ax))
+            shp = [1] * arr.ndim
+            shp[pos] = v.size
+            w = w * v.reshape(shp)
+        return w
+    if isinstance(dw, NP.ndarray):
+        w = NP.asarray(dw, dtype=NP.float64)
+        if w.ndim != arr.ndim or w.shape[-1] != 1 or any(b not in (1, n) for b, n in zip(w.shape, arr.shape)):
+            raise ValueError('{0}: diagweights of shape {1} do not broadcast against spectra of shape {2}'.format(where, w.shape, arr.shape))
+        return w
+    raise TypeError('Diagonal weights in input must be a dictionary or a numpy array')
+
+
+def incoherent_cross_power_spectrum_average(xcpdps, excpdps=None, diagoffsets=None, ctx=None):
+    """Incoherent average of cross-power spectra (:806-1231).  xcpdps: a result of compute_power_spectrum or a list of them, one per
+    data set; excpdps: None, or as many results of compute_power_spectrum_uncertainty.  Stage 1 averages the data sets of every
+    sampling, pool and statistic under their diagweights: sum(a w) / sum(w), a NaN product counted as 0.  Stage 2, with diagoffsets (a
+    dictionary {axis: offsets} with the axes 1 LST, 2 days, 3 triads, or a list of them): per combination the diagweights-weighted
+    average over the selected offsets of its axes; the statistics are then lists with one array per combination, the reduced axes
+    kept at length 1, and 'diagweights' is the list of the summed weights.  Axis 2 does not apply to excpdps.  Every sum runs on the
+    device (prisim_cphase_xavg), one call per sampling, pool and statistic.  Returns (out_xcpdps, out_excpdps), plain arrays;
+    out_excpdps is None without excpdps.  ctx: the device context (default: a new one on device 0).  See the module docstring for the
+    departures."""
+    if isinstance(xcpdps, dict):
+        xcpdps = [xcpdps]
+    if not isinstance(xcpdps, list):
+        raise TypeError('Invalid data type provided for input xcpdps')
+    if len(xcpdps) < 1:
+        raise ValueError('Input xcpdps is empty')
+    if excpdps is not None:
+        if isinstance(excpdps, dict):
+            excpdps = [excpdps]
+        if not isinstance(excpdps, list):
+            raise TypeError('Invalid data type provided for input excpdps')
+        if len(xcpdps) != len(excpdps):
+            raise ValueError('Inputs xcpdps and excpdps found to have unequal number of values')
+    combos = None
+    if diagoffsets is not None:
+        if isinstance(diagoffsets, dict):
+            diagoffsets = [diagoffsets]
+        if not isinstance(diagoffsets, list):
+            raise TypeError('Input diagoffsets must be a list of dictionaries')
+        combos = []
+        for item in diagoffsets:
+            if not isinstance(item, dict):
+                raise TypeError('Input diagoffsets must be a list of dictionaries')
+            for ax in item:
+                if not isinstance(item[ax], (list, NP.ndarray)):
+                    raise TypeError('Values in input dictionary diagoffsets must be a list or numpy array')
+            combos.append({ax: NP.asarray(item[ax]).reshape(-1) for ax in item})
+
+    # the plan: per output, sampling, pool and statistic the arrays, their weights and the masks of every combination
+    plan = []
+    outs = []
+    for sets, pools, skip in ((xcpdps, ('whole', 'submodel', 'residual'), ()), (excpdps, ('errinfo',), (2,))):
+        if sets is None:
+            outs.append(None)
+            continue
+        first = sets[0]
+        out = {key: first[key] for key in _TOP_KEYS}
+        if 'lstXoffsets' in first:
+            out['lstXoffsets'] = first['lstXoffsets']
+        for smplng in ('oversampled', 'resampled'):
+            if smplng not in first:
+                continue
+            out[smplng] = {key: first[smplng][key] for key in _SAMPLING_KEYS}
+            for dpool in pools:
+                if dpool not in first[smplng]:
+                    continue
+                pool0 = first[smplng][dpool]
+                out[smplng][dpool] = {'diagoffsets': pool0['diagoffsets'], 'axesmap': pool0['axesmap']}
+                for stat in ('mean', 'median'):
+                    if stat not in pool0:
+                        continue
+                    where = '{0} {1} {2}'.format(smplng, dpool, stat)
+                    arrays = [NP.asarray(d[smplng][dpool][stat]) for d in sets]
+                    if any(a.shape != arrays[0].shape for a in arrays) or not 5 <= arrays[0].ndim <= 8:
+                        raise ValueError('{0}: the data sets must have one shape of 5 to 8 axes'.format(where))
+                    weights = [_diag_weights(d[smplng][dpool], stat, where) for d in sets]
+                    masks = None
+                    if combos is not None:
+                        masks = []
+                        for combo in combos:
+                            mask = {}
+                            for ax in combo:
+                                if ax in skip:
+                                    continue
+                                if ax not in pool0['diagoffsets']:
+                                    raise ValueError('{0}: axis {1} in diagoffsets is not a collapsed axis of the input'.format(where, ax))
+                                for d in sets:
+                                    dw = d[smplng][dpool]['diagweights']
+                                    if isinstance(dw, dict) and ax not in dw:
+                                        raise ValueError('{0}: the diagoffsets of axis {1} need its diagweights, and there are none'.format(where, ax))
+                                sel = NP.isin(NP.asarray(pool0['diagoffsets'][ax]).reshape(-1), combo[ax])
+                                if not NP.any(sel):
+                                    raise ValueError('{0}: no offset of axis {1} is among {2}'.format(where, ax, combo[ax].tolist()))
+                                pos = int(NP.asarray(pool0['axesmap'][ax]).reshape(-1)[0])
+                                if not 0 < pos < arrays[0].ndim - 1 or sel.size != arrays[0].shape[pos]:
+                                    raise ValueError('{0}: the diagoffsets of axis {1} do not match the spectra'.format(where, ax))
+                                mask[pos] = sel
+                            masks.append(mask)
+                    plan.append((out[smplng][dpool], stat, arrays, weights, masks))
+        outs.append(out)
+
+    if plan and ctx is None:
+        ctx = _abi.Context(0)
+    for pool, stat, arrays, weights, masks in plan:
+        if masks is None:
+            res = ctx.cphase_xavg(arrays, weights)
+            pool[stat], pool['diagweights'] = res['avg'], res['wsum']
+            continue
+        res = ctx.cphase_xavg(arrays, weights, combos=[m for m in masks if m], want_avg=not all(masks))
+        reduced, wreduced = iter(res['out']), iter(res['wout'])
+        # a combination left with no axis: the average itself
+        pool[stat] = [next(reduced) if m else res['avg'] for m in masks]
+        pool['diagweights'] = [next(wreduced) if m else res['wsum'] for m in masks]
+    return tuple(outs)
+
+
+def incoherent_kbin_averaging(xcpdps, kbins=None, num_kbins=None, kbintype='log', ctx=None):
+    """Power spectra in bins of |k_parallel| (:1235-1493).  xcpdps: a result of incoherent_cross_power_spectrum_average.  kbins: the
+    bin edges, or None: edges from eps to max |kprll| + eps, linear (kprll.shape[1] // 2 + 1 of them, folding -k on +k) or logarithmic
+    (num_kbins + 1 of them, num_kbins 10 by default), behind an edge at -eps so that bin 0 holds k = 0.  Returns the reference's
+    dictionary: the top-level keys, and per sampling its keys, 'kbininfo' ('counts', 'kbin_edges', 'kbinnum', 'ri', one entry per
+    window, and per pool and statistic the list of the |P|-weighted bin centres) and per pool 'diagoffsets', 'diagweights', 'axesmap'
+    and per statistic {'PS': [...], 'Del2': [...]}, one array per combination with nkbins in the place of the lags; an empty bin is
+    NaN.  Every sum runs on the device (prisim_cphase_kbin), one call per sampling, pool, statistic and combination.  ctx: the device
+    context (default: a new one on device 0).  See the module docstring for the departures."""
+    if not isinstance(xcpdps, dict):
+        raise TypeError('Input xcpdps must be a dictionary')
+    if kbins is not None:
+        if not isinstance(kbins, (list, NP.ndarray)):
+            raise TypeError('Input kbins must be a list or numpy array')
+        edges_given = NP.asarray(kbins, dtype=NP.float64).reshape(-1)
+        if edges_given.size < 2 or NP.any(NP.diff(edges_given) <= 0):
+            raise ValueError('Input kbins must hold at least two increasing edges')
+    else:
+        if not isinstance(kbintype, str):
+            raise TypeError('Input kbintype must be a string')
+        if kbintype.lower() not in ['linear', 'log']:
+            raise ValueError('Input kbintype must be set to "linear" or "log"')
+        if kbintype.lower() == 'log':
+            if num_kbins is None:
+                num_kbins = 10
+            if isinstance(num_kbins, bool) or not isinstance(num_kbins, (int, NP.integer)):
+                raise TypeError('Input num_kbins must be an integer')
+            if num_kbins < 1:
+                raise ValueError('Input num_kbins must be positive')
+    psinfo = {key: xcpdps[key] for key in _TOP_KEYS}
+    if 'lstXoffsets' in xcpdps:
+        psinfo['lstXoffsets'] = xcpdps['lstXoffsets']
+    eps = 1e-10
+    plan = []
+    for smplng in ('oversampled', 'resampled'):
+        if smplng not in xcpdps:
+            continue
+        psinfo[smplng] = {key: xcpdps[smplng][key] for key in _SAMPLING_KEYS if key not in ('kprll', 'lags')}
+        kprll = NP.asarray(xcpdps[smplng]['kprll'], dtype=NP.float64)
+        if kprll.ndim != 2:
+            raise ValueError('{0}: kprll must be (nspw, nlags)'.format(smplng))
+        if kbins is None:
+            if kbintype.lower() == 'linear':
+                bins_kprll = NP.linspace(eps, NP.abs(kprll).max() + eps, num=kprll.shape[1] // 2 + 1, endpoint=True)
+            else:
+                bins_kprll = NP.geomspace(eps, NP.abs(kprll).max() + eps, num=num_kbins + 1, endpoint=True)
+            bins_kprll = NP.insert(bins_kprll, 0, -eps)
+        else:
+            bins_kprll = edges_given
+        num_kbins = bins_kprll.size - 1                # carried to the next sampling, as in the reference
+        info = {'counts': [], 'kbin_edges': [], 'kbinnum': [], 'ri': []}
+        psinfo[smplng]['kbininfo'] = info
+        lists = []
+        for spw in range(kprll.shape[0]):
+            counts, kbin_edges, kbinnum, ri = binned_statistic_count(NP.abs(kprll[spw, :]), bins_kprll)
+            info['counts'].append(counts)
+            info['kbin_edges'].append(NP.copy(kbin_edges))
+            info['kbinnum'].append(kbinnum)
+            info['ri'].append(ri)
+            lists.append([ri[ri[k]:ri[k + 1]] for k in range(num_kbins)])
+        offsets = NP.asarray([_csr(l)[0] for l in lists], dtype=NP.int64)
+        members = [_csr(l)[1] for l in lists]
+        for dpool in ('whole', 'submodel', 'residual', 'errinfo'):
+            if dpool not in xcpdps[smplng]:
+                continue
+            pool = xcpdps[smplng][dpool]
+            psinfo[smplng][dpool] = {key: pool[key] for key in ('diagoffsets', 'diagweights', 'axesmap')}
+            info[dpool] = {}
+            for stat in ('mean', 'median'):
+                if stat not in pool:
+                    continue
+                arrays = pool[stat] if isinstance(pool[stat], (list, tuple)) else [pool[stat]]
+                arrays = [NP.asarray(a) for a in arrays]
+                for a in arrays:
+                    if a.ndim < 2 or a.shape[0] != kprll.shape[0] or a.shape[-1] != kprll.shape[1]:
+                        raise ValueError('{0} {1} {2}: spectra of shape {3} do not have the windows and lags of kprll {4}'.format(
+                            smplng, dpool, stat, a.shape, kprll.shape))
+                psinfo[smplng][dpool][stat] = {'PS': [], 'Del2': []}
+                info[dpool][stat] = []
+                plan.append((psinfo[smplng][dpool][stat], info[dpool][stat], arrays, kprll, offsets, members))
+    if plan and ctx is None:
+        ctx = _abi.Context(0)
+    for ps, centres, arrays, kprll, offsets, members in plan:
+        for a in arrays:
+            res = ctx.cphase_kbin(a, kprll, offsets, members)
+            ps['PS'].append(res['ps'])
+            ps['Del2'].append(res['del2'])
+            centres.append(res['kc'])
+    return psinfo
 
 
 class ClosurePhase(object):
