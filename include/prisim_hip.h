@@ -445,8 +445,10 @@ typedef struct prisim_timing {
   int32_t last_kernel_id;    /* PRISIM_KERNEL_* actually used */
   int32_t last_chan_tile;    /* channels per thread of the recurrence kernel */
   int32_t last_nsplit;       /* source split factor */
-  int32_t last_lift_groups;  /* baseline groups (of 256 cube rows) within the limit of the lifting rotation, which they ran (a folded array:
-                                see prisim_hip_get_fold_info); 0 for the packed fp32 taper kernel */
+  int32_t last_lift_groups;  /* baseline groups (of 256 cube rows) whose longest baseline passes the LENGTH rule of the lifting rotation,
+                                max|b| max_s|s - s_pc| |df| / c <= 1/8 cycle (fp32; 1/4 fp64): a lower bound of the groups that lifted
+                                on an unfolded array -- the kernels flag by the sharper per-axis bound, whose count is
+                                last_sum_lift_groups (prisim_hip_get_fold_info); 0 for the packed fp32 taper kernel */
   int32_t last_taper_group;  /* 1: the packed fp32 taper kernel ran its grouped recurrence (df/f_min <= 3.4e-3), 0: exact per-step form */
   int32_t last_delay_fused;  /* 1: the last delay_transform_device ran the fused LDS FFT kernel, 0: the rocFFT pipeline */
   double last_delay_ms;      /* hipEvent duration of the last prisim_hip_delay_transform_device (all batches) */
@@ -466,10 +468,13 @@ int prisim_hip_get_timing(prisim_ctx* ctx, prisim_timing* out, int reset);
  * 7/8 of the rows are distinct and more than 256 are, compute() sums every distinct vector once and copies the result into all the
  * cube rows (and gradient rows) that carry it.  last_sum_baselines: rows the last compute() summed (nbl when the array is not folded);
  * last_terms_evaluated: last_sum_baselines * nchan * nsrc.  prisim_timing.last_terms stays the delivered nbl * nchan * nsrc, and
- * prisim_timing.last_lift_groups stays in the caller's units: the groups of 256 CUBE rows whose longest baseline is within the lifting
- * limit.  last_sum_lift_groups: the groups of 256 SUMMED rows that ran the lifting rotation -- the kernel's own flags; equal to
- * last_lift_groups when the array is not folded.  On a folded array a cube row within the limit whose vector shares a summed group
- * with a longer one runs the plain rotation (valid for every step angle), so last_lift_groups bounds the rows that lifted from above.
+ * prisim_timing.last_lift_groups stays in the caller's units and keeps the length rule: the groups of 256 CUBE rows whose longest
+ * baseline satisfies max|b| max_s|s - s_pc| |df| / c <= the lifting limit.  last_sum_lift_groups is what the kernel ran: the groups
+ * of 256 SUMMED rows (the rows themselves when the array is not folded) its own flags sent to the lifting rotation.  The flags use
+ * the per-axis bound min(max|b| max_s|e|, max|b_xy| max_s|e_xy| + max|b_z| max_s|e_z|) |df| / c, e = s - s_pc (csrc/step_bound.h),
+ * which never exceeds the length rule's: on an unfolded array last_lift_groups <= last_sum_lift_groups, a lower bound of what
+ * lifted.  On a folded array the two count different groups: a cube row within the limit whose vector shares a summed group with a
+ * longer one runs the plain rotation (valid for every step angle).
  * last_culled_fraction and last_split_uncorrected_groups refer to the summed rows.  Any pointer may be NULL.  (Kept out of
  * prisim_timing: its layout is frozen at 96 bytes.)  PRISIM_HIP_FOLD=0 in the environment turns folding off. */
 int prisim_hip_get_fold_info(prisim_ctx* ctx, int64_t* last_sum_baselines, int64_t* last_terms_evaluated, int64_t* last_sum_lift_groups);

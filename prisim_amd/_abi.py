@@ -1820,7 +1820,9 @@ class Context(object):
         self._check(self._lib.prisim_hip_get_timing(self._h, C.byref(t), 1 if reset else 0), 'prisim_hip_get_timing')
         out = {k: getattr(t, k) for k, _ in PrisimTiming._fields_ if k != 'reserved_'}
         # baseline folding: rows the last compute() summed (distinct baseline vectors of a folded array) and the terms its kernels
-        # evaluated, and the groups of 256 summed rows that lifted; last_terms stays the delivered count, last_lift_groups in groups of cube rows
+        # evaluated, and the groups of 256 summed rows that lifted (last_sum_lift_groups: the kernel's own flags, by the per-axis step
+        # bound of csrc/step_bound.h -- what the kernel ran); last_terms stays the delivered count, and last_lift_groups stays the
+        # length-rule count max|b| max|s - s_pc| |df| / c <= limit in groups of 256 cube rows, a lower bound of what lifts
         nsum, nterms, nlift = C.c_int64(), C.c_int64(), C.c_int64()
         self._check(self._lib.prisim_hip_get_fold_info(self._h, C.byref(nsum), C.byref(nterms), C.byref(nlift)), 'prisim_hip_get_fold_info')
         out['last_sum_lift_groups'] = nlift.value

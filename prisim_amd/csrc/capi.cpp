@@ -371,7 +371,7 @@ int prisim_hip_set_array(prisim_ctx* ctx, const double* bl_enu, int64_t nbl, con
   ctx->grp_maxz.assign(ctx->grp_maxlen.size(), 0.0);
   ctx->grp_minh.assign(ctx->grp_maxlen.size(), 1e300);
   ctx->fsq_pairs_ct = ctx->fsq_pairs_ntiles = -1;
-  for (SkyBufs& k : ctx->skb) k.lift_key_k = -1.0;             // the cached lifting flags belong to the previous array
+  for (SkyBufs& k : ctx->skb) k.lift_key_k[0] = -1.0;             // the cached lifting flags belong to the previous array
   for (int64_t b = 0; b < nbl_sum; ++b) {
     const double len = std::sqrt(sx[b] * sx[b] + sy[b] * sy[b] + sz[b] * sz[b]);
     const size_t g = (size_t)(b / kBlockThreads);
@@ -431,12 +431,15 @@ int upload_common(prisim_ctx* ctx, int64_t nsrc, const double* dircos, const dou
   double* d4 = (double*)stage_alloc(ctx, d4_bytes);
   if (!d4) return fail(ctx, PRISIM_EINTERNAL, "staging area too small");
   d4[0] = d4[1] = d4[2] = d4[3] = 0.0;
-  double dmax2 = 0.0;
+  double dmax2 = 0.0, hmax2 = 0.0, zmax2 = 0.0;        // extrema of e = s - s_pc: |e|^2, its horizontal part, its vertical part (step_bound.h)
   for (int64_t s = 0; s < nsrc; ++s) {
     {
       const double ex = dircos[3 * s] - pc_dircos[0], ey = dircos[3 * s + 1] - pc_dircos[1], ez = dircos[3 * s + 2] - pc_dircos[2];
-      const double e2 = ex * ex + ey * ey + ez * ez;
+      const double h2 = ex * ex + ey * ey, z2 = ez * ez;
+      const double e2 = h2 + z2;
       if (e2 > dmax2) dmax2 = e2;
+      if (h2 > hmax2) hmax2 = h2;
+      if (z2 > zmax2) zmax2 = z2;
     }
     for (int i = 0; i < 3; ++i) {
       const double v = dircos[3 * s + i];
@@ -552,6 +555,8 @@ int upload_common(prisim_ctx* ctx, int64_t nsrc, const double* dircos, const dou
   }
   ctx->nsrc = nsrc;
   ctx->dmax = std::sqrt(dmax2);
+  ctx->hmax = std::sqrt(hmax2);
+  ctx->zmax = std::sqrt(zmax2);
   ctx->taper = fwhm_deg != nullptr;
   for (int i = 0; i < 3; ++i) ctx->pc[i] = pc_dircos[i];
   return PRISIM_OK;
@@ -1234,26 +1239,34 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
     {
       // lifting rotation is used for a baseline group only when |step phase| <= 1/8 cycle (fp32; 1/4 cycle in fp64, where the
       // angle error alpha*eps is irrelevant and only tan(alpha/2) must stay bounded) is guaranteed for every source:
-      // |theta| = |b . (s - s_pc)| |df| / c <= max|b| * max_s|s - s_pc| * |df| / c
-      const double k = ctx->dmax * std::fabs(ctx->df) / kC;
-      const double lift_limit = (pl.f32 ? 0.125 : 0.25) * (1.0 - 1e-9);
-      if (k != ctx->sk->lift_key_k || (int)pl.f32 != ctx->sk->lift_key_f32 || ctx->sk->lift_groups != pl.nbgroups) {
-        // formed on the device from the groups' longest baselines (resident since set_array): max|s - s_pc| changes with every snapshot
+      // |theta| = |b . (s - s_pc)| |df| / c <= min(max|b| max_s|e|, max|b_xy| max_s|e_xy| + max|b_z| max_s|e_z|) |df| / c, e = s - s_pc
+      // (step_bound.h: the per-axis form does not charge a horizontal baseline for the vertical part of e)
+      const double adf = std::fabs(ctx->df);
+      const double k = ctx->dmax * adf / kC;
+      const double lift_limit = prisim::step_limit_cycles(pl.f32);
+      const double key[3] = {ctx->dmax * adf, ctx->hmax * adf, ctx->zmax * adf};
+      const size_t ng = ctx->grp_maxlen.size();
+      if ((size_t)pl.nbgroups != ng) return fail(ctx, PRISIM_EINTERNAL, "the plan's baseline groups are not those of the group tables");
+      if (key[0] != ctx->sk->lift_key_k[0] || key[1] != ctx->sk->lift_key_k[1] || key[2] != ctx->sk->lift_key_k[2] ||
+          (int)pl.f32 != ctx->sk->lift_key_f32 || ctx->sk->lift_groups != pl.nbgroups) {
+        // formed on the device from the groups' tables (resident since set_array): the extrema of s - s_pc change with every snapshot
         // of a drift scan, and a host-side table would need a stream synchronisation before it could be rewritten
         if ((rc = ensure(ctx, ctx->sk->lift_flags, (size_t)pl.nbgroups * sizeof(int32_t)))) return rc;
-        HIPCHK(ctx, launch_lift_flags((const double*)ctx->grp_hz.p + 2 * ctx->grp_maxlen.size(), k, lift_limit, (int32_t*)ctx->sk->lift_flags.p,
-                                      pl.nbgroups, pstream(ctx)));
-        ctx->sk->lift_key_k = k;
+        HIPCHK(ctx, launch_lift_flags((const double*)ctx->grp_hz.p, pl.nbgroups, ctx->dmax, ctx->hmax, ctx->zmax, adf, lift_limit,
+                                      (int32_t*)ctx->sk->lift_flags.p, pstream(ctx)));
+        for (int i = 0; i < 3; ++i) ctx->sk->lift_key_k[i] = key[i];
         ctx->sk->lift_key_f32 = (int)pl.f32;
         ctx->sk->lift_groups = pl.nbgroups;
       }
-      // Reported per group of 256 CUBE rows (the caller's units): the groups whose longest baseline is within the limit.  Unfolded that
-      // is the kernel's own flag count.  On a folded array the kernel's flags are per group of 256 SUMMED rows (last_sum_lift_groups,
-      // prisim_hip_get_fold_info); a cube row within the limit whose vector shares a summed group with a longer one runs the plain
-      // rotation, which is valid for every step angle.
+      // last_sum_lift_groups (prisim_hip_get_fold_info) is the kernel's own flag count: the groups of 256 SUMMED rows (the rows
+      // themselves on an unfolded array) that pass step_bound.h's rule, formed here as the device forms its flags.
+      // last_lift_groups stays the length-rule count per group of 256 CUBE rows (the caller's units): the groups whose longest baseline
+      // passes max|b| max_s|e| alone.  It is a lower bound of what lifts on an unfolded array; on a folded one a cube row within the
+      // limit whose vector shares a summed group with a longer one runs the plain rotation, which is valid for every step angle.
       int nlift = 0, nlift_sum = 0;
       for (double len : ctx->row_grp_maxlen) nlift += (len * k <= lift_limit) ? 1 : 0;
-      for (int g = 0; g < pl.nbgroups; ++g) nlift_sum += (ctx->grp_maxlen[(size_t)g] * k <= lift_limit) ? 1 : 0;
+      for (size_t g = 0; g < ng; ++g)
+        nlift_sum += prisim::step_flag(ctx->grp_maxlen[g], ctx->grp_maxh[g], ctx->grp_maxz[g], ctx->dmax, ctx->hmax, ctx->zmax, ctx->df, pl.f32) ? 1 : 0;
       // the packed taper kernel folds the amplitude into the phasor (a scaled rotation: no lifting there, the flags only select its
       // re-anchored body); every other kernel lifts the flagged groups
       ctx->timing.last_lift_groups = (ctx->taper && pl.pk) ? 0 : nlift;

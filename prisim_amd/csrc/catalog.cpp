@@ -221,7 +221,7 @@ int geometry_enqueue(prisim_ctx* ctx, const prisim_obs* obs, const prisim_snapsh
   C.geom_nsnap = nsnap; C.geom_set = b;
   if (C.n == 0) {
     for (int64_t t = 0; t < nsnap; ++t) {
-      C.out_host[t].nsrc = 0; C.out_host[t].dmax2_bits = 0;
+      C.out_host[t].nsrc = 0; C.out_host[t].dmax2_bits = 0; C.out_host[t].hmax2_bits = 0; C.out_host[t].zmax2_bits = 0;
       for (auto& v : C.out_host[t].run_start) v = 0;
     }
     return PRISIM_OK;
@@ -316,9 +316,13 @@ int activate_snapshot(prisim_ctx* ctx, const prisim_obs* obs, const prisim_snaps
   ctx->nsrc = N;
   ctx->taper = C.have_shape;
   for (int i = 0; i < 3; ++i) ctx->pc[i] = snap.pc_dircos[i];
-  double d2 = 0.0;
+  double d2 = 0.0, h2 = 0.0, z2 = 0.0;
   memcpy(&d2, &o.dmax2_bits, sizeof(double));
+  memcpy(&h2, &o.hmax2_bits, sizeof(double));
+  memcpy(&z2, &o.zmax2_bits, sizeof(double));
   ctx->dmax = std::sqrt(d2);
+  ctx->hmax = std::sqrt(h2);
+  ctx->zmax = std::sqrt(z2);
   ctx->kappa_runs.clear();
   const int ncr = (int)C.runs.size();
   for (int r = 0; r < ncr; ++r) {

@@ -110,6 +110,8 @@ void k_cat_scan(const CatGeomParams p) {
   if (threadIdx.x == 0) {
     p.out[snap].nsrc = carry_s;
     p.out[snap].dmax2_bits = 0;
+    p.out[snap].hmax2_bits = 0;
+    p.out[snap].zmax2_bits = 0;
     for (int r = 0; r <= PRISIM_CAT_MAX_RUNS; ++r) p.out[snap].run_start[r] = carry_s;      // runs with no catalogue source at all
     if (p.batch) {
       // the snapshot's entry of the batched launch's table (catalog.cpp run_wave_batch lays the blocks out; wave_split_sources there)
@@ -134,7 +136,7 @@ void k_cat_scan(const CatGeomParams p) {
 __global__ __launch_bounds__(kCatBlock)
 void k_cat_scatter(const CatGeomParams p) {
   __shared__ int wcount[kCatBlock / 64];
-  __shared__ double wmax[kCatBlock / 64];
+  __shared__ double wmax[3][kCatBlock / 64];
   const int snap = blockIdx.y;
   const CatSnap sn = p.snaps[snap];
   const int64_t i = (int64_t)blockIdx.x * kCatBlock + threadIdx.x;
@@ -150,7 +152,7 @@ void k_cat_scatter(const CatGeomParams p) {
   for (int w = 0; w < wave; ++w) wbase += wcount[w];
   const int64_t rank = (int64_t)p.block_off[(size_t)snap * p.nblocks + blockIdx.x] + wbase + before;     // ROI sources before catalogue source i
   const size_t row0 = (size_t)snap * (size_t)p.n;
-  double e2 = 0.0;
+  double e2 = 0.0, h2 = 0.0, z2 = 0.0;
   if (i < p.n) {
     const int run = p.run_id ? p.run_id[i] : 0;
     if (p.run_id && (i == 0 || p.run_id[i - 1] != run)) p.out[snap].run_start[run] = rank;
@@ -159,6 +161,8 @@ void k_cat_scatter(const CatGeomParams p) {
       reinterpret_cast<double4*>(p.dirs)[row0 + rank] = make_double4(l, m, n, p.kappa ? p.kappa[i] : 0.0);
       const double ex = l - sn.pc[0], ey = m - sn.pc[1], ez = n - sn.pc[2];
       e2 = ex * ex + ey * ey + ez * ez;
+      h2 = ex * ex + ey * ey;
+      z2 = ez * ez;
       if (p.want_keys) {
         // runs stay together (high bits); inside a run decreasing altitude = increasing 1 - n, 2^-28 steps
         double q = (1.0 - n) * 134217728.0;                      // (1 - n) / 2 * 2^28
@@ -169,13 +173,18 @@ void k_cat_scatter(const CatGeomParams p) {
     }
   }
 #pragma unroll
-  for (int d = 32; d > 0; d >>= 1) e2 = fmax(e2, __shfl_xor(e2, d, 64));
-  if (lane == 0) wmax[wave] = e2;
+  for (int d = 32; d > 0; d >>= 1) {
+    e2 = fmax(e2, __shfl_xor(e2, d, 64));
+    h2 = fmax(h2, __shfl_xor(h2, d, 64));
+    z2 = fmax(z2, __shfl_xor(z2, d, 64));
+  }
+  if (lane == 0) { wmax[0][wave] = e2; wmax[1][wave] = h2; wmax[2][wave] = z2; }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double mx = wmax[0];
-    for (int w = 1; w < kCatBlock / 64; ++w) mx = fmax(mx, wmax[w]);
-    if (mx > 0.0) atomicMax((unsigned long long*)&p.out[snap].dmax2_bits, (unsigned long long)__double_as_longlong(mx));   // non-negative doubles order like their bits
+  if (threadIdx.x < 3) {                                 // one thread per extremum: |e|^2, |e_xy|^2, e_z^2
+    double mx = wmax[threadIdx.x][0];
+    for (int w = 1; w < kCatBlock / 64; ++w) mx = fmax(mx, wmax[threadIdx.x][w]);
+    uint64_t* dst = threadIdx.x == 0 ? &p.out[snap].dmax2_bits : threadIdx.x == 1 ? &p.out[snap].hmax2_bits : &p.out[snap].zmax2_bits;
+    if (mx > 0.0) atomicMax((unsigned long long*)dst, (unsigned long long)__double_as_longlong(mx));   // non-negative doubles order like their bits
   }
 }
 
@@ -190,7 +199,7 @@ void k_cat_scatter(const CatGeomParams p) {
 __global__ __launch_bounds__(256)
 void k_cat_small(const CatGeomParams p) {
   __shared__ int64_t wsum[4];
-  __shared__ double wmax[4];
+  __shared__ double wmax[3][4];
   __shared__ int64_t total_s;
   const int snap = blockIdx.x;
   const CatSnap sn = p.inline_snap ? p.snap0 : p.snaps[snap];
@@ -216,7 +225,7 @@ void k_cat_small(const CatGeomParams p) {
   if (tid == 255) total_s = wbase + x;
   int64_t rank = wbase + x - cnt;                      // region-of-interest sources before source i0
   const size_t row0 = (size_t)snap * (size_t)p.n;
-  double e2 = 0.0;
+  double e2 = 0.0, h2 = 0.0, z2 = 0.0;
   for (int64_t i = i0; i < i1; ++i) {
     const int run = p.run_id ? p.run_id[i] : 0;
     if (p.run_id && i > 0 && p.run_id[i - 1] != run) p.out[snap].run_start[run] = rank;      // (run 0 starts at 0: written below)
@@ -227,6 +236,8 @@ void k_cat_small(const CatGeomParams p) {
       reinterpret_cast<double4*>(p.dirs)[row0 + rank] = make_double4(l, mm, n, p.kappa ? p.kappa[i] : 0.0);
       const double ex = l - sn.pc[0], ey = mm - sn.pc[1], ez = n - sn.pc[2];
       e2 = fmax(e2, ex * ex + ey * ey + ez * ez);
+      h2 = fmax(h2, ex * ex + ey * ey);
+      z2 = fmax(z2, ez * ez);
       if (p.want_keys) {
         double q = (1.0 - n) * 134217728.0;                      // as k_cat_scatter
         q = q < 0.0 ? 0.0 : (q > 268435455.0 ? 268435455.0 : q);
@@ -237,15 +248,24 @@ void k_cat_small(const CatGeomParams p) {
     }
   }
 #pragma unroll
-  for (int d = 32; d > 0; d >>= 1) e2 = fmax(e2, __shfl_xor(e2, d, 64));
-  if (lane == 0) wmax[wave] = e2;
+  for (int d = 32; d > 0; d >>= 1) {
+    e2 = fmax(e2, __shfl_xor(e2, d, 64));
+    h2 = fmax(h2, __shfl_xor(h2, d, 64));
+    z2 = fmax(z2, __shfl_xor(z2, d, 64));
+  }
+  if (lane == 0) { wmax[0][wave] = e2; wmax[1][wave] = h2; wmax[2][wave] = z2; }
   __syncthreads();
   if (tid == 0) {
     const int64_t N = total_s;
-    double mx = wmax[0];
-    for (int w = 1; w < 4; ++w) mx = fmax(mx, wmax[w]);
+    double mx[3];
+    for (int q = 0; q < 3; ++q) {
+      mx[q] = wmax[q][0];
+      for (int w = 1; w < 4; ++w) mx[q] = fmax(mx[q], wmax[q][w]);
+    }
     p.out[snap].nsrc = N;
-    p.out[snap].dmax2_bits = mx > 0.0 ? (uint64_t)__double_as_longlong(mx) : 0;
+    p.out[snap].dmax2_bits = mx[0] > 0.0 ? (uint64_t)__double_as_longlong(mx[0]) : 0;
+    p.out[snap].hmax2_bits = mx[1] > 0.0 ? (uint64_t)__double_as_longlong(mx[1]) : 0;
+    p.out[snap].zmax2_bits = mx[2] > 0.0 ? (uint64_t)__double_as_longlong(mx[2]) : 0;
     // runs no source of the catalogue starts (none exist past the last run id) keep "start = N"; run 0 starts at 0
     if (p.run_id) {
       const int last_run = p.run_id[p.n - 1];
@@ -323,16 +343,25 @@ void k_cull_first(const CullParams p) {
   }
 }
 
-// lifting-rotation flags of the baseline groups: |step phase| <= limit cycles guaranteed for every source of the sky
-// (capi.cpp prisim_hip_compute: k = max_s |s - s_pc| |df| / c)
-__global__ void k_lift_flags(const double* __restrict__ grp_maxlen, double k, double limit, int32_t* __restrict__ flags, int ng) {
+// lifting-rotation flags of the baseline groups: |step phase| <= limit cycles guaranteed for every source of the sky.  The bound is
+// step_bound.h's min(maxlen dmax, maxh hmax + maxz zmax) |df| / c, in its order and with every operation rounded on its own (no
+// contraction), so that the host's count (capi.cpp prisim_hip_compute) and these flags agree group for group.
+__global__ void k_lift_flags(const double* __restrict__ grp_hz, int ng, double dmax, double hmax, double zmax, double abs_df, double limit,
+                             int32_t* __restrict__ flags) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g < ng) flags[g] = (grp_maxlen[g] * k <= limit) ? 1 : 0;
+  if (g >= ng) return;
+  const double maxh = grp_hz[g], maxz = grp_hz[(size_t)ng + g], maxlen = grp_hz[2 * (size_t)ng + g];
+  const double whole = __dmul_rn(maxlen, dmax);
+  const double axes = __dadd_rn(__dmul_rn(maxh, hmax), __dmul_rn(maxz, zmax));
+  const double m = whole < axes ? whole : axes;
+  const double step = __ddiv_rn(__dmul_rn(m, abs_df), 299792458.0);
+  flags[g] = (step <= limit) ? 1 : 0;
 }
 
-hipError_t launch_lift_flags(const double* grp_maxlen, double k, double limit, int32_t* flags, int ng, hipStream_t stream) {
+hipError_t launch_lift_flags(const double* grp_hz, int ng, double dmax, double hmax, double zmax, double abs_df, double limit, int32_t* flags,
+                             hipStream_t stream) {
   if (ng <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_lift_flags, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, stream, grp_maxlen, k, limit, flags, ng);
+  hipLaunchKernelGGL(k_lift_flags, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, stream, grp_hz, ng, dmax, hmax, zmax, abs_df, limit, flags);
   return hipGetLastError();
 }
 

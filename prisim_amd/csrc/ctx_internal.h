@@ -19,6 +19,7 @@
 #include "../../include/prisim_hip.h"
 #include "skyvis_kernels.h"
 #include "baseline_fold.h"
+#include "step_bound.h"
 
 using namespace prisim;
 
@@ -88,7 +89,7 @@ struct SkyBufs {
   DevBuf dirs_prep;          // [nsrc_pad][4] (s - s_pc)/c, kappa
   DevBuf dirs_c32;           // fused fp32 gradient kernel
   DevBuf lift_flags;         // [groups] lifting-rotation flags and what they were formed for
-  double lift_key_k = -1.0;
+  double lift_key_k[3] = {-1.0, -1.0, -1.0};      // max_s |e|, |e_xy|, |e_z| (e = s - s_pc), each times |df|: all three enter the flags
   int lift_key_f32 = -1;
   int lift_groups = -1;
   DevBuf split_flags, moments, moments_part, split_count;      // split taper form: per-run moments and per-group flags
@@ -145,6 +146,7 @@ struct prisim_ctx {
   int32_t* h_split_count = nullptr;                      // pinned: uncorrected-group counts of the last split launch, per run (read after a sync)
   int split_count_runs = 0;
   double dmax = 2.0;                  // max_s |s - s_pc| of the current sky
+  double hmax = 2.0, zmax = 2.0;      // max_s of its horizontal part / of |its vertical part| (step_bound.h); = dmax: the whole-vector bound alone
   std::vector<double> h_freqs;
   bool uniform = false;
   double f0 = 0.0, df = 0.0;

@@ -180,6 +180,8 @@ struct CatOut {              // per-snapshot results the host reads back (pinned
   int64_t nsrc;              // sources inside the region of interest
   int64_t run_start[PRISIM_CAT_MAX_RUNS + 1];   // first compacted source of every catalogue run; [nruns] = nsrc
   uint64_t dmax2_bits;       // max |s - s_pc|^2, bit pattern of a non-negative double
+  uint64_t hmax2_bits;       // max of the horizontal part (s - s_pc)_x^2 + (s - s_pc)_y^2, likewise
+  uint64_t zmax2_bits;       // max (s - s_pc)_z^2, likewise
 };
 struct CatGeomParams {
   const double* ux;          // [n] catalogue unit vectors in the catalogue's own frame (RA-Dec / HA-Dec: cos d cos a, cos d sin a, sin d;
@@ -234,7 +236,9 @@ size_t cat_sort_temp_bytes(int64_t n);
 hipError_t launch_cat_sort(void* temp, size_t temp_bytes, const uint32_t* keys, uint32_t* keys_out, const uint32_t* pos, uint32_t* perm,
                            const double* dirs, const int32_t* idx, double* dirs_out, int32_t* idx_out, int64_t n, hipStream_t stream);
 hipError_t launch_cull_first(const CullParams& p, hipStream_t stream);
-hipError_t launch_lift_flags(const double* grp_maxlen, double k, double limit, int32_t* flags, int ng, hipStream_t stream);
+// grp_hz: [4][ng] (max horizontal length, max |b_z|, max length, min horizontal length); dmax / hmax / zmax: max_s |e|, |e_xy|, |e_z|, e = s - s_pc
+hipError_t launch_lift_flags(const double* grp_hz, int ng, double dmax, double hmax, double zmax, double abs_df, double limit, int32_t* flags,
+                             hipStream_t stream);
 
 // delay transform helpers (delay_kernels.hip)
 hipError_t launch_dt_prepare(const double* cube, const double* bpwts /*device [wts_rows][nchan] or NULL*/, int64_t wts_rows /*1 or nbl*/,
