@@ -319,6 +319,25 @@ def _resample_map(wanted, m, nout):
     return mo.size, mo, mi, mw
 
 
+def _closure_inputs(legs, conj, bpwts, freq_wts, masks, mask_index, nbl, nchan, nt):
+    """The closure-phase inputs as the library takes them, C-contiguous: legs, conj (ntriads, 3) int32; bpwts (nbl, nchan, nt), freq_wts
+    (nchan,) (None: ones), masks (nmask, nchan) or None: float64; mask_index (nbl,) int32 or None."""
+    lg = NP.ascontiguousarray(legs, dtype=NP.int32).reshape(-1, 3)
+    cj = NP.ascontiguousarray(conj, dtype=NP.int32).reshape(-1, 3)
+    if cj.shape != lg.shape:
+        raise ValueError('legs and conj must both be (ntriads, 3)')
+    bw = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(bpwts, dtype=NP.float64), (nbl, nchan, nt)))
+    fw = NP.ones(nchan) if freq_wts is None else NP.ascontiguousarray(NP.broadcast_to(NP.asarray(freq_wts, dtype=NP.float64).ravel(), (nchan,)))
+    mk = mi = None
+    if masks is not None:
+        mk = NP.ascontiguousarray(masks, dtype=NP.float64).reshape(-1, nchan)
+        if mask_index is not None:
+            mi = NP.ascontiguousarray(mask_index, dtype=NP.int32).ravel()
+            if mi.size != nbl:
+                raise ValueError('mask_index must have one entry per cube row')
+    return lg, cj, bw, fw, mk, mi
+
+
 def _want_bits(want, bits):
     """The OR of bits[name] over the names of want; KeyError on an unknown name."""
     flag = 0
@@ -1142,20 +1161,8 @@ class Context(object):
             if x.ndim != 3:
                 raise ValueError('cube must be (nbl, nchan, nt)')
             nbl, nchan, nt = x.shape
-        lg = NP.ascontiguousarray(legs, dtype=NP.int32).reshape(-1, 3)
-        cj = NP.ascontiguousarray(conj, dtype=NP.int32).reshape(-1, 3)
-        if cj.shape != lg.shape:
-            raise ValueError('legs and conj must both be (ntriads, 3)')
+        lg, cj, bw, fw, mk, mi = _closure_inputs(legs, conj, bpwts, freq_wts, masks, mask_index, nbl, nchan, nt)
         ntriads = lg.shape[0]
-        bw = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(bpwts, dtype=NP.float64), (nbl, nchan, nt)))
-        fw = NP.ones(nchan) if freq_wts is None else NP.ascontiguousarray(NP.broadcast_to(NP.asarray(freq_wts, dtype=NP.float64).ravel(), (nchan,)))
-        mk = mi = None
-        if masks is not None:
-            mk = NP.ascontiguousarray(masks, dtype=NP.float64).reshape(-1, nchan)
-            if mask_index is not None:
-                mi = NP.ascontiguousarray(mask_index, dtype=NP.int32).ravel()
-                if mi.size != nbl:
-                    raise ValueError('mask_index must have one entry per cube row')
         trip = NP.empty((ntriads, 3, nchan, nt), dtype=NP.complex128)
         phase = NP.empty((ntriads, nchan, nt), dtype=NP.float64)
         st = PrisimClosureStats()
@@ -1201,20 +1208,8 @@ class Context(object):
                 if x.ndim != 3 or x.shape[1] != nchan:
                     raise ValueError('cube must be (nbl, nchan, nt) with the channel count of wts')
                 nbl, _, nt = x.shape
-            lg = NP.ascontiguousarray(legs, dtype=NP.int32).reshape(-1, 3)
-            cj = NP.ascontiguousarray(conj, dtype=NP.int32).reshape(-1, 3)
-            if cj.shape != lg.shape:
-                raise ValueError('legs and conj must both be (ntriads, 3)')
+            lg, cj, bw, fw, mk, mi = _closure_inputs(legs, conj, bpwts, freq_wts, masks, mask_index, nbl, nchan, nt)
             nrows, lead = lg.shape[0], (lg.shape[0],)
-            bw = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(bpwts, dtype=NP.float64), (nbl, nchan, nt)))
-            fw = NP.ones(nchan) if freq_wts is None else NP.ascontiguousarray(NP.broadcast_to(NP.asarray(freq_wts, dtype=NP.float64).ravel(),
-                                                                                                  (nchan,)))
-            if masks is not None:
-                mk = NP.ascontiguousarray(masks, dtype=NP.float64).reshape(-1, nchan)
-                if mask_index is not None:
-                    mi = NP.ascontiguousarray(mask_index, dtype=NP.int32).ravel()
-                    if mi.size != nbl:
-                        raise ValueError('mask_index must have one entry per cube row')
         flag = _want_bits(want, {'over': PRISIM_CPDELAY_OVER, 'over_power': PRISIM_CPDELAY_OVER_POWER, 'res': PRISIM_CPDELAY_RES,
                                  'res_power': PRISIM_CPDELAY_RES_POWER})
         ps = None if pscale is None else NP.ascontiguousarray(NP.broadcast_to(NP.asarray(pscale, dtype=NP.float64).ravel(), (nwin,)))

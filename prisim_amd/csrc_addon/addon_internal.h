@@ -22,8 +22,6 @@ namespace pint {
 
 constexpr int kThreads = 256;                         // threads per workgroup of the add-on kernels
 constexpr int kMaxStreams = 2;
-constexpr int kMaxTile = 64;                          // snapshots per workgroup of the tiled fused kernels
-constexpr int kTileLds = 65536;                       // LDS their snapshot rows may fill
 constexpr int64_t kMaxBlocks = int64_t(1) << 20;
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
@@ -60,9 +58,8 @@ inline int dev_upload(prisim_ctx* ctx, Dev& dev, P*& ptr, const std::vector<T>& 
     if (int rc_ = dev_upload(ctx, dev, ptr, __VA_ARGS__)) return rc_;                                  \
   } while (0)
 
-// A call's own streams, each with an optional pair of kernel-timing events.  Drained when they go.  A chunk loop deals chunk c to
-// stream i = c % n: harvest(i), the uploads, open(i), the kernels, close(i), the downloads; then drain().  Without events open and
-// close do nothing and kernel_ms stays 0.
+// A call's own streams, each with an optional pair of kernel-timing events.  Drained when they go.  chunk_loop (below) runs the
+// chunks over them.  Without events open and close do nothing and kernel_ms stays 0.
 struct Streams {
   hipStream_t s[kMaxStreams] = {};
   hipEvent_t k0[kMaxStreams] = {}, k1[kMaxStreams] = {};
@@ -116,6 +113,31 @@ struct Streams {
   }
 };
 
+// The frame of a chunk loop over the call's streams: the chunks `ch` of n items, `reps` times over (chunk c is chunk c % ch.count of
+// repeat c / ch.count).  Chunk c goes to stream i = c % st.n: harvest(i) waits for the kernels of the chunk that last used the
+// stream's buffers and books their time, then upload, open(i), kernels, close(i), download, each called as step(c, the chunk's
+// items, i, st.s[i]) and returning 0 or a PRISIM_E* code, which ends the loop; drain() at the end.  A loop on one stream
+// needs no drain() between chunks either: everything of a chunk is enqueued behind everything of the chunk before it, and that
+// order alone protects the reused chunk buffers and the sums a kernel keeps on the device between chunks.
+template <typename Upload, typename Kernels, typename Download>
+inline int chunk_loop(prisim_ctx* ctx, Streams& st, const Chunks& ch, int64_t n, Upload&& upload, Kernels&& kernels, Download&& download,
+                      int64_t reps = 1) {
+  for (int64_t c = 0; c < reps * ch.count; ++c) {
+    const int i = (int)(c % st.n);
+    const Span sp = ch.span(c % ch.count, n);
+    if (int rc = st.harvest(ctx, i)) return rc;
+    if (int rc = upload(c, sp, i, st.s[i])) return rc;
+    if (int rc = st.open(ctx, i)) return rc;
+    if (int rc = kernels(c, sp, i, st.s[i])) return rc;
+    if (int rc = st.close(ctx, i)) return rc;
+    if (int rc = download(c, sp, i, st.s[i])) return rc;
+  }
+  return st.drain(ctx);
+}
+
+// a step of chunk_loop that has nothing to do
+inline int no_step(int64_t, Span, int, hipStream_t) { return PRISIM_OK; }
+
 // in-place fp64 1-D rocFFT plans by (inverse, batch) and one execution info per stream
 struct FftPlans {
   std::map<std::pair<bool, size_t>, rocfft_plan> plans;
@@ -124,7 +146,12 @@ struct FftPlans {
     for (auto& kv : plans) g_rocfft.plan_destroy(kv.second);
     for (rocfft_execution_info i : info) if (i) g_rocfft.execution_info_destroy(i);
   }
-  rocfft_plan at(bool inverse, size_t batch) const { return plans.at({inverse, batch}); }
+  // the plan of (inverse, batch) on `buffer`, on the stream of info[i]
+  int run(prisim_ctx* ctx, bool inverse, size_t batch, void* buffer, int i) const {
+    void* b[1] = {buffer};
+    const bool ok = g_rocfft.execute(plans.at({inverse, batch}), b, nullptr, info[i]) == rocfft_status_success;
+    return ok ? PRISIM_OK : fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
+  }
   // plans of length len for every (inverse, batch) of want (repeats are made once); the infos run on streams[0 .. nstreams) and
   // each gets a work buffer from dev that serves the largest plan
   int create(prisim_ctx* ctx, Dev& dev, size_t len, const std::vector<std::pair<bool, size_t>>& want, const hipStream_t* streams,
@@ -190,6 +217,14 @@ inline int ensure_rocfft(prisim_ctx* ctx) {
   return PRISIM_OK;
 }
 
+// `kernel` in workgroups of kThreads, and what the launch itself reports
+template <typename K, typename... A>
+inline int launch(prisim_ctx* ctx, K kernel, dim3 grid, size_t lds, hipStream_t s, A... a) {
+  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), lds, s, a...);
+  HIPCHK(ctx, hipGetLastError());
+  return PRISIM_OK;
+}
+
 // workgroups of a grid-stride kernel over n elements
 inline int grid_for(const prisim_ctx* ctx, int64_t n) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)std::max(ctx->cu_count, 1) * 16));
@@ -219,37 +254,17 @@ inline int allow_lds(prisim_ctx* ctx, K* kernel, int64_t bytes) {
   return PRISIM_OK;
 }
 
-// The tables of scipy.signal.resample's spectrum from the caller's selection map (prisim_amd/dsp_readings.py:resample_map): per output
-// bin at most two input bins rs_in [2][nout] (-1: none; bins of the zero padding are dropped) with the coefficients rs_c [2][nout]
-// = map_w * scale * e^{-2 pi i k_in floor(m/2) / m}, and rtw [nout] = e^{+2 pi i q / nout}.  nout < 1: tables of one empty bin.
+// resample_tables (addon_plan.h), a refusal as PRISIM_EINVAL; with rs_c, the coefficients under one scale for every term:
+// rs_c [2][nout] = (map_w * scale) e^{-2 pi i k_in floor(m/2) / m}
 inline int build_resample_tables(prisim_ctx* ctx, int64_t nout, int64_t m, int64_t nchan, double scale, int64_t nmap, const int64_t* map_out,
-                                 const int64_t* map_in, const double* map_w, std::vector<int32_t>& rs_in, std::vector<double>& rs_c,
-                                 std::vector<double>& rtw) {
-  const int64_t nr = std::max<int64_t>(nout, 1);
-  rs_in.assign(2 * (size_t)nr, -1);
-  rs_c.assign(4 * (size_t)nr, 0.0);
-  rtw.assign(2 * (size_t)nr, 0.0);
-  if (nout < 1) return PRISIM_OK;
-  if (nmap < 1 || !map_out || !map_in || !map_w) return fail(ctx, PRISIM_EINVAL, "the resampled spectra need the selection map");
-  std::vector<int> used((size_t)nout, 0);
-  const int64_t half = m / 2;
-  for (int64_t e = 0; e < nmap; ++e) {
-    const int64_t k = map_out[e], kin = map_in[e];
-    if (k < 0 || k >= nout || kin < 0 || kin >= m) return fail(ctx, PRISIM_EINVAL, "selection map entry out of range");
-    if (used[(size_t)k] == 2) return fail(ctx, PRISIM_EINVAL, "selection map: more than two entries for one output bin");
-    const int s = used[(size_t)k]++;
-    if (kin >= nchan) continue;                    // a bin of the zero padding
-    const int64_t red = (kin * half) % m;          // e^{-2 pi i k_in floor(m/2) / m}
-    const double a = -2.0 * M_PI * (double)red / (double)m;
-    const double sc = map_w[e] * scale;
-    rs_in[(size_t)s * nout + k] = (int32_t)kin;
-    rs_c[2 * ((size_t)s * nout + k)] = sc * std::cos(a);
-    rs_c[2 * ((size_t)s * nout + k) + 1] = sc * std::sin(a);
-  }
-  for (int64_t q = 0; q < nout; ++q) {
-    const double a = 2.0 * M_PI * (double)q / (double)nout;
-    rtw[2 * q] = std::cos(a);
-    rtw[2 * q + 1] = std::sin(a);
+                                 const int64_t* map_in, const double* map_w, ResampleTables& t, std::vector<double>* rs_c) {
+  if (const char* err = resample_tables(nout, m, nchan, nmap, map_out, map_in, map_w, t)) return fail(ctx, PRISIM_EINVAL, err);
+  if (rs_c) rs_c->assign(t.phase.size(), 0.0);
+  for (size_t at = 0; rs_c && at < t.in.size(); ++at) {
+    if (t.in[at] < 0) continue;
+    const double sc = t.w[at] * scale;
+    (*rs_c)[2 * at] = sc * t.phase[2 * at];
+    (*rs_c)[2 * at + 1] = sc * t.phase[2 * at + 1];
   }
   return PRISIM_OK;
 }

@@ -571,7 +571,6 @@ int prisim_clean_delay(prisim_ctx* ctx, int32_t ncubes, int64_t nrows, int64_t n
   if (!win || !kwin || !cbox || !lag || !kern_lag || !cc || !res || !cc_freq || !res_freq || !iters || !flags || !rms)
     return fail(ctx, PRISIM_EINVAL, "null array");
   if ((rc = ensure_rocfft(ctx))) return rc;
-  RocfftApi& F = g_rocfft;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   Work wk;
   Dev& dev = wk.dev;
@@ -608,8 +607,7 @@ int prisim_clean_delay(prisim_ctx* ctx, int32_t ncubes, int64_t nrows, int64_t n
     HIPCHK(ctx, hipMemcpyAsync(d_cbox, cbox, (size_t)nrows * m, hipMemcpyHostToDevice, ctx->stream));
     if (kidx) HIPCHK(ctx, hipMemcpyAsync(d_kidx, kidx, (size_t)nrows * 4, hipMemcpyHostToDevice, ctx->stream));
   }
-  void* b0[1] = {d_x};
-  if (F.execute(wk.fft.at(true, (size_t)nall), b0, nullptr, wk.fft.info[0]) != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
+  if ((rc = wk.fft.run(ctx, true, (size_t)nall, d_x, 0))) return rc;
   // rocFFT's inverse is unnormalised: m df ifft(x) = df * sum_n x[n] e^{+2 pi i k n / m}
   hipLaunchKernelGGL(k_clean_scale, dim3(1024), dim3(256), 0, ctx->stream, d_x, nall * m, lag_scale, 1.0, 0);
   HIPCHK(ctx, hipGetLastError());
@@ -620,11 +618,7 @@ int prisim_clean_delay(prisim_ctx* ctx, int32_t ncubes, int64_t nrows, int64_t n
     // NP.fft.fft(.) * deta * pad_factor (:1808-1811)
     HIPCHK(ctx, hipMemcpyAsync(d_ccf, d_cc, rb, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_resf, d_res, rb, hipMemcpyDeviceToDevice, ctx->stream));
-    void* b1[1] = {d_ccf};
-    void* b2[1] = {d_resf};
-    const rocfft_plan fwd = wk.fft.at(false, (size_t)nclean);
-    if (F.execute(fwd, b1, nullptr, wk.fft.info[0]) != rocfft_status_success || F.execute(fwd, b2, nullptr, wk.fft.info[0]) != rocfft_status_success)
-      return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
+    if ((rc = wk.fft.run(ctx, false, (size_t)nclean, d_ccf, 0)) || (rc = wk.fft.run(ctx, false, (size_t)nclean, d_resf, 0))) return rc;
     hipLaunchKernelGGL(k_clean_scale, dim3(1024), dim3(256), 0, ctx->stream, d_ccf, nclean * m, freq_scale1, freq_scale2, 1);
     hipLaunchKernelGGL(k_clean_scale, dim3(1024), dim3(256), 0, ctx->stream, d_resf, nclean * m, freq_scale1, freq_scale2, 1);
     HIPCHK(ctx, hipGetLastError());

@@ -262,23 +262,20 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
 
   // tile, LDS and chunking
   const bool tiled = rt == PRISIM_CLOSURE_DIRECT && !cube && nt >= kTiledMinNt;
-  int64_t tile = tiled ? 1 : 0, lds = tiled ? (int64_t)sizeof(double2) * kTile * (kTile + 1) : 0;
+  int64_t tile = tiled ? 1 : 0, ntiles = 1, lds = tiled ? (int64_t)sizeof(double2) * kTile * (kTile + 1) : 0;
   if (rt == PRISIM_CLOSURE_FUSED) {
     int lds_max = 0;
     if (int rc = lds_limit(ctx, lds_max)) return rc;
-    const int64_t tw_bytes = 16 * std::max<int64_t>(nchan / 2, 1), row_bytes = 16 * (nchan + 1);
-    tile = std::max<int64_t>(1, std::min<int64_t>({nt, (int64_t)kMaxTile, (kTileLds - tw_bytes) / row_bytes}));
-    lds = tile * row_bytes + tw_bytes;
+    const SnapshotTile sn = snapshot_tile(nt, 16 * (nchan + 1), 16 * std::max<int64_t>(nchan / 2, 1));
+    tile = sn.tile; ntiles = sn.ntiles; lds = sn.lds;
     if (lds > lds_max) {                              // (not on gfx950: a row of PRISIM_CLOSURE_MAX_LEN channels takes 96 KiB of its 160)
       if (route == PRISIM_CLOSURE_FUSED) return fail(ctx, PRISIM_EINVAL, "a row does not fit in LDS (" + std::to_string(lds) + " B needed)");
       rt = PRISIM_CLOSURE_ROCFFT;
-      tile = 0;
-      lds = 0;
+      tile = 0; ntiles = 1; lds = 0;
     }
   }
   if (rt == PRISIM_CLOSURE_ROCFFT)
     if (int rc = ensure_rocfft(ctx)) return rc;
-  const int64_t ntiles = rt == PRISIM_CLOSURE_FUSED ? (nt + tile - 1) / tile : 1;
   const int64_t nct = (nchan + kTile - 1) / kTile, ntt = (nt + kTile - 1) / kTile;
   const int64_t per = nchan * nt;
   const int64_t trip_triad = 3 * per * 16, phase_triad = per * 8, fbuf_triad = rt == PRISIM_CLOSURE_ROCFFT ? 3 * per * 16 : 0;
@@ -336,51 +333,38 @@ int closure_phase_chunks(prisim_ctx* ctx, const double* cube, int64_t nt, int64_
   if (rt == PRISIM_CLOSURE_FUSED)
     if (int rc = allow_lds(ctx, k_cl_fused, lds)) return rc;
 
-  for (int64_t c = 0; c < nchunks; ++c) {
-    const int i = (int)(c % nstreams);
-    hipStream_t sc = st.s[i];
-    if (int rc = st.harvest(ctx, i)) return rc;
-    const int64_t T0 = c * tc, tn = std::min(tc, ntriads - T0);
+  auto kernels = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+    const int64_t T0 = sp.first, tn = sp.count;
     ClParams P = base;
     P.T0 = T0; P.tc = tn; P.trip = d_trip[i]; P.phase = d_phase[i]; P.fbuf = d_fbuf[i];
     const int64_t ne = tn * per;
-    if (int rc = st.open(ctx, i)) return rc;
     if (rt == PRISIM_CLOSURE_DIRECT) {
-      if (tiled) hipLaunchKernelGGL(k_cl_tiled, dim3((unsigned)(tn * nct * ntt)), dim3(kThreads), 0, sc, P, (int)nct, (int)ntt);
-      else hipLaunchKernelGGL(k_cl_plain, dim3((unsigned)grid_for(ctx, ne)), dim3(kThreads), 0, sc, P);
-      HIPCHK(ctx, hipGetLastError());
+      if (int rc = tiled ? launch(ctx, k_cl_tiled, dim3((unsigned)(tn * nct * ntt)), 0, sc, P, (int)nct, (int)ntt)
+                         : launch(ctx, k_cl_plain, dim3((unsigned)grid_for(ctx, ne)), 0, sc, P)) return rc;
     } else {
       if (rt == PRISIM_CLOSURE_FUSED) {
-        hipLaunchKernelGGL(k_cl_fused, dim3((unsigned)(tn * 3 * ntiles)), dim3(kThreads), (size_t)lds, sc, P);
-        HIPCHK(ctx, hipGetLastError());
+        if (int rc = launch(ctx, k_cl_fused, dim3((unsigned)(tn * 3 * ntiles)), (size_t)lds, sc, P)) return rc;
       } else {
         const int g = grid_for(ctx, 3 * ne);
         const size_t batch = (size_t)tn * 3 * (size_t)nt;
-        void* b[1] = {d_fbuf[i]};
-        hipLaunchKernelGGL(k_cl_prepare, dim3((unsigned)g), dim3(kThreads), 0, sc, P);
-        HIPCHK(ctx, hipGetLastError());
-        if (g_rocfft.execute(wk.fft.at(false, batch), b, nullptr, wk.fft.info[i]) != rocfft_status_success)
-          return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
-        hipLaunchKernelGGL(k_cl_mask, dim3((unsigned)g), dim3(kThreads), 0, sc, P);
-        HIPCHK(ctx, hipGetLastError());
-        if (g_rocfft.execute(wk.fft.at(true, batch), b, nullptr, wk.fft.info[i]) != rocfft_status_success)
-          return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
-        hipLaunchKernelGGL(k_cl_finish, dim3((unsigned)g), dim3(kThreads), 0, sc, P);
-        HIPCHK(ctx, hipGetLastError());
+        if (int rc = launch(ctx, k_cl_prepare, dim3((unsigned)g), 0, sc, P)) return rc;
+        if (int rc = wk.fft.run(ctx, false, batch, d_fbuf[i], i)) return rc;
+        if (int rc = launch(ctx, k_cl_mask, dim3((unsigned)g), 0, sc, P)) return rc;
+        if (int rc = wk.fft.run(ctx, true, batch, d_fbuf[i], i)) return rc;
+        if (int rc = launch(ctx, k_cl_finish, dim3((unsigned)g), 0, sc, P)) return rc;
       }
-      hipLaunchKernelGGL(k_cl_phase, dim3((unsigned)grid_for(ctx, ne)), dim3(kThreads), 0, sc, P);
-      HIPCHK(ctx, hipGetLastError());
+      if (int rc = launch(ctx, k_cl_phase, dim3((unsigned)grid_for(ctx, ne)), 0, sc, P)) return rc;
     }
-    if (sink)
-      if (int rc = sink->kernels(i, sc, T0, tn, d_phase[i])) return rc;
-    if (int rc = st.close(ctx, i)) return rc;
+    return sink ? sink->kernels(i, sc, T0, tn, d_phase[i]) : PRISIM_OK;
+  };
+  auto download = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+    const int64_t T0 = sp.first, tn = sp.count;
     if (out_triplets)
       HIPCHK(ctx, hipMemcpyAsync(out_triplets + 2 * (size_t)T0 * 3 * per, d_trip[i], (size_t)tn * trip_triad, hipMemcpyDeviceToHost, sc));
     if (out_phase) HIPCHK(ctx, hipMemcpyAsync(out_phase + (size_t)T0 * per, d_phase[i], (size_t)tn * phase_triad, hipMemcpyDeviceToHost, sc));
-    if (sink)
-      if (int rc = sink->download(i, sc, T0, tn)) return rc;
-  }
-  if (int rc = st.drain(ctx)) return rc;
+    return sink ? sink->download(i, sc, T0, tn) : PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, ntriads, no_step, kernels, download)) return rc;
   if (stats) {
     // per output point: three legs read (16 B) with their weights (8 B) and written (16 B), one phase written (8 B); the filter's
     // phase kernel reads the triplets again, and the rocFFT route passes its row buffer through five kernels (read and write)

@@ -380,8 +380,7 @@ int prisim_cphase_xavg(prisim_ctx* ctx, int32_t ndim, const int64_t* shape, int6
   };
   // the weight sums, once, on the first stream
   if (int rc = st.open(ctx, 0)) return rc;
-  hipLaunchKernelGGL(k_avg_den, dim3((unsigned)grid_for(ctx, wtotal)), dim3(kThreads), 0, s0, d_w, nsets, wtotal, d_den);
-  HIPCHK(ctx, hipGetLastError());
+  if (int rc = launch(ctx, k_avg_den, dim3((unsigned)grid_for(ctx, wtotal)), 0, s0, d_w, nsets, wtotal, d_den)) return rc;
   for (int c = 0; c < ncombo; ++c) {
     const Combo& C = combos[(size_t)c];
     AvgWout W = {};
@@ -391,8 +390,7 @@ int prisim_cphase_xavg(prisim_ctx* ctx, int32_t ndim, const int64_t* shape, int6
     W.nsel = (int64_t)C.sel_w.size();
     W.count = C.worows;
     W.wout = d_wout[(size_t)c];
-    hipLaunchKernelGGL(k_avg_wout, dim3((unsigned)grid_for(ctx, W.count)), dim3(kThreads), 0, s0, W);
-    HIPCHK(ctx, hipGetLastError());
+    if (int rc = launch(ctx, k_avg_wout, dim3((unsigned)grid_for(ctx, W.count)), 0, s0, W)) return rc;
   }
   if (int rc = st.close(ctx, 0)) return rc;
   if (wsum) {
@@ -403,15 +401,10 @@ int prisim_cphase_xavg(prisim_ctx* ctx, int32_t ndim, const int64_t* shape, int6
     HIPCHK(ctx, hipMemcpyAsync(wout[c], d_wout[(size_t)c], (size_t)combos[(size_t)c].worows * 8, hipMemcpyDeviceToHost, s0));
     download += combos[(size_t)c].worows * 8;
   }
-  HIPCHK(ctx, hipStreamSynchronize(s0));              // the other stream starts behind the inputs and the weight sums
-  if (int rc = st.harvest(ctx, 0)) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(s0));              // the other stream starts behind the inputs and the weight sums; chunk 0 harvests
 
-  for (int64_t c = 0; c < nchunks; ++c) {
-    const int si = (int)(c % nstreams);
-    hipStream_t s = st.s[si];
-    if (int rc = st.harvest(ctx, si)) return rc;
-    const int64_t l0 = c * tc, cl = std::min(tc, nlags - l0);
-    if (int rc = st.open(ctx, si)) return rc;
+  auto kernels = [&](int64_t, Span sp, int si, hipStream_t s) -> int {
+    const int64_t l0 = sp.first, cl = sp.count;
     AvgStage1 S = {};
     S.ax = axes(rdim, ustr, nullptr, nullptr);
     S.a = d_a;
@@ -422,9 +415,7 @@ int prisim_cphase_xavg(prisim_ctx* ctx, int32_t ndim, const int64_t* shape, int6
     S.count = rows * cl;
     S.avg = d_avg[si];
     const bool narrow = rows * cl <= (int64_t)UINT32_MAX;   // every count of this chunk fits 32 bits: rows * cl is the largest
-    if (narrow) hipLaunchKernelGGL(k_avg_stage1<uint32_t>, dim3((unsigned)grid_for(ctx, S.count)), dim3(kThreads), 0, s, S);
-    else hipLaunchKernelGGL(k_avg_stage1<int64_t>, dim3((unsigned)grid_for(ctx, S.count)), dim3(kThreads), 0, s, S);
-    HIPCHK(ctx, hipGetLastError());
+    if (int rc = launch(ctx, narrow ? k_avg_stage1<uint32_t> : k_avg_stage1<int64_t>, dim3((unsigned)grid_for(ctx, S.count)), 0, s, S)) return rc;
     for (int k = 0; k < ncombo; ++k) {
       const Combo& C = combos[(size_t)k];
       int64_t wostr[kMaxRowAxes];
@@ -440,12 +431,13 @@ int prisim_cphase_xavg(prisim_ctx* ctx, int32_t ndim, const int64_t* shape, int6
       T.cl = cl;
       T.count = C.orows * cl;
       T.out = d_out[si] + (size_t)C.first * cl;
-      if (narrow) hipLaunchKernelGGL(k_avg_stage2<uint32_t>, dim3((unsigned)grid_for(ctx, T.count)), dim3(kThreads), 0, s, T);
-      else hipLaunchKernelGGL(k_avg_stage2<int64_t>, dim3((unsigned)grid_for(ctx, T.count)), dim3(kThreads), 0, s, T);
-      HIPCHK(ctx, hipGetLastError());
+      if (int rc = launch(ctx, narrow ? k_avg_stage2<uint32_t> : k_avg_stage2<int64_t>, dim3((unsigned)grid_for(ctx, T.count)), 0, s, T)) return rc;
     }
-    if (int rc = st.close(ctx, si)) return rc;
-    // the chunk's [rows][cl] into the caller's [rows][nlags]
+    return PRISIM_OK;
+  };
+  // the chunk's [rows][cl] into the caller's [rows][nlags]
+  auto fetch = [&](int64_t, Span sp, int si, hipStream_t s) -> int {
+    const int64_t l0 = sp.first, cl = sp.count;
     if (avg) {
       HIPCHK(ctx, copy_rows(avg + 2 * (size_t)l0, (size_t)nlags * 16, d_avg[si], (size_t)cl * 16, (size_t)cl * 16, (size_t)rows,
                             hipMemcpyDeviceToHost, s));
@@ -457,8 +449,9 @@ int prisim_cphase_xavg(prisim_ctx* ctx, int32_t ndim, const int64_t* shape, int6
                             (size_t)C.orows, hipMemcpyDeviceToHost, s));
       download += C.orows * cl * 16;
     }
-  }
-  if (int rc = st.drain(ctx)) return rc;
+    return PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, nlags, no_step, kernels, fetch)) return rc;
   if (stats) {
     int64_t moved = nsets * elems * 16 + elems * 16;  // the arrays once, avg written once
     for (const Combo& C : combos) moved += C.orows * nlags * 16 * ((int64_t)C.sel_t.size() + 1);   // its selected rows read, out written
@@ -553,12 +546,9 @@ int prisim_cphase_kbin(prisim_ctx* ctx, int64_t nspw, int64_t m, int64_t nlags, 
   HIPCHK(ctx, hipStreamSynchronize(s0));              // the other stream starts behind the inputs; `off` may go
 
   int64_t download = 0;
-  for (int64_t c = 0; c < nchunks; ++c) {
-    const int si = (int)(c % nstreams);
-    hipStream_t s = st.s[si];
-    if (int rc = st.harvest(ctx, si)) return rc;
-    const int64_t w = c / ch.count, r0 = (c - w * ch.count) * tc, cr = std::min(tc, m - r0);
-    if (int rc = st.open(ctx, si)) return rc;
+  // chunk c: a range of the rows of window c / ch.count
+  auto kernels = [&](int64_t c, Span sp, int si, hipStream_t s) -> int {
+    const int64_t w = c / ch.count, r0 = sp.first, cr = sp.count;
     Kbin K = {};
     K.p = d_p + ((size_t)w * m + r0) * nlags;
     K.k = d_k + (size_t)w * nlags;
@@ -567,22 +557,21 @@ int prisim_cphase_kbin(prisim_ctx* ctx, int64_t nspw, int64_t m, int64_t nlags, 
     K.cr = cr; K.nlags = nlags; K.nk = nk;
     K.tile = (int32_t)tile;
     K.ps = d_ps[si]; K.del2 = d_d2[si]; K.kc = d_kc[si];
-    if (lds) {
-      const int64_t ntiles = (cr + tile - 1) / tile;
-      const unsigned blocks = (unsigned)std::min<int64_t>(ntiles, (int64_t)std::max(ctx->cu_count, 1) * 16);
-      hipLaunchKernelGGL(k_kbin<true>, dim3(blocks), dim3(kThreads), (size_t)lds_bytes, s, K);
-    } else {
-      hipLaunchKernelGGL(k_kbin<false>, dim3((unsigned)grid_for(ctx, cr * nk)), dim3(kThreads), 0, s, K);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    if (int rc = st.close(ctx, si)) return rc;
+    if (!lds) return launch(ctx, k_kbin<false>, dim3((unsigned)grid_for(ctx, cr * nk)), 0, s, K);
+    const int64_t ntiles = (cr + tile - 1) / tile;
+    const unsigned blocks = (unsigned)std::min<int64_t>(ntiles, (int64_t)std::max(ctx->cu_count, 1) * 16);
+    return launch(ctx, k_kbin<true>, dim3(blocks), (size_t)lds_bytes, s, K);
+  };
+  auto fetch = [&](int64_t c, Span sp, int si, hipStream_t s) -> int {
+    const int64_t w = c / ch.count, r0 = sp.first, cr = sp.count;
     const size_t o = ((size_t)w * m + r0) * nk, n = (size_t)cr * nk;
     HIPCHK(ctx, hipMemcpyAsync(ps + 2 * o, d_ps[si], n * 16, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipMemcpyAsync(del2 + 2 * o, d_d2[si], n * 16, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipMemcpyAsync(kc + o, d_kc[si], n * 8, hipMemcpyDeviceToHost, s));
     download += (int64_t)n * 40;
-  }
-  if (int rc = st.drain(ctx)) return rc;
+    return PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, m, no_step, kernels, fetch, nspw)) return rc;
   if (stats) {
     const int64_t tables = nspw * nlags * 8 + nspw * (nk + 1) * 8 + nmem * 4;
     stats->wall_ms = wall_ms_since(wall0);

@@ -341,9 +341,10 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
   upload_bytes += (nbins + 1) * 8 + nmem * 4;
 
   double* const host_out[7] = {out_wts, out_eicp_mean, out_eicp_median, out_cp_mean, out_cp_median, out_rms, out_mad};
-  for (int64_t c = 0; c < nchunks; ++c) {
-    const int64_t T0 = c * tc, tn = std::min(tc, ntriads - T0);
-    BinParams p{};
+  BinParams p{};                                      // of the chunk in hand
+  auto upload = [&](int64_t, Span sp, int, hipStream_t) -> int {
+    const int64_t T0 = sp.first, tn = sp.count;
+    p = BinParams{};
     if (rin) {
       const int64_t o = T0 * nchan;
       p.pm = rin->a + o;
@@ -392,12 +393,15 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
     p.nc = nchan;
     p.axis = axis;
     p.mad_all = mad_ignores_flags ? 1 : 0;
-    const int64_t total = rows_out * tn * nchan;
+    return PRISIM_OK;
+  };
+  auto kernels = [&](int64_t, Span sp, int, hipStream_t) -> int {
+    const int64_t total = rows_out * sp.count * nchan;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((total + kThreads - 1) / kThreads, kMaxBlocks));
-    if (int rc = st.open(ctx, 0)) return rc;
-    hipLaunchKernelGGL(k_cpbins, dim3((unsigned)blocks), dim3(kThreads), 0, s, p);
-    HIPCHK(ctx, hipGetLastError());
-    if (int rc = st.close(ctx, 0)) return rc;
+    return launch(ctx, k_cpbins, dim3((unsigned)blocks), 0, s, p);
+  };
+  auto download = [&](int64_t, Span sp, int, hipStream_t) -> int {
+    const int64_t T0 = sp.first, tn = sp.count;
     for (int o = 0; o < 7; ++o) {
       if (!(want >> o & 1)) continue;
       const size_t es = (o == 1 || o == 2) ? 16 : 8;
@@ -408,8 +412,9 @@ int prisim_cphase_bin(prisim_ctx* ctx, int32_t kind, const double* in_mean, cons
                             (size_t)(tn * nchan) * es, rows_out, hipMemcpyDeviceToHost, s));
       download_bytes += rows_out * tn * nchan * (int64_t)es;
     }
-    if (int rc = st.drain(ctx)) return rc;          // the chunk's buffers are reused by the next one
-  }
+    return PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, ntriads, upload, kernels, download)) return rc;   // one stream: its order guards the reused buffers
   if (made_in) *resident_in = made_in.release();
   if (keep_out) *keep_out = kept.release();
   if (stats) {

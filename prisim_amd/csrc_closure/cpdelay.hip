@@ -44,9 +44,9 @@ struct CdParams {
   int tile, ntiles;         // fused: snapshots per workgroup, tiles per line
   int rtile, rntiles;       // resampling: the same
   double df;
-  const int32_t* rs_n;      // [nwin] kept bins of the resampled spectrum
-  const int32_t* rs_k;      // [nwin][nres] their output bins, increasing
-  const int32_t* rs_in;     // [nwin][2][nres] their channels (-1: none)
+  const int32_t* rs_o;      // [nwin + 1] kept bins of the resampled spectrum: rs_k[rs_o[w] .. rs_o[w + 1]), increasing
+  const int32_t* rs_k;
+  const int32_t* rs_in;     // [nwin][2][nres] their channels, by kept bin (-1: none)
   const double2* rs_c;      // [nwin][2][nres] wts * weight * df e^{-2 pi i k_in floor(m/2) / m}
   const double2* rtw;       // [nres] e^{+2 pi i q / nres}
   double2* over;            // this chunk's [rows][nwin][m][nt]
@@ -169,10 +169,10 @@ __global__ void __launch_bounds__(kThreads) k_cpd_resample(CdParams P, int64_t l
   const int64_t row = line / P.nwin;
   const int w = (int)(line - row * P.nwin);
   const double* ph = P.phase + row * (int64_t)P.nchan * P.nt + t0;
-  const int nz = P.rs_n[w];
+  const int nz = P.rs_o[w + 1] - P.rs_o[w];
   const int32_t* kin = P.rs_in + (int64_t)w * 2 * nres;
   const double2* coef = P.rs_c + (int64_t)w * 2 * nres;
-  const int32_t* kout = P.rs_k + (int64_t)w * nres;
+  const int32_t* kout = P.rs_k + P.rs_o[w];
   for (int e = threadIdx.x; e < nz * tile; e += kThreads) {            // lanes along the snapshots
     const int i = e / tile, tt = e - i * tile;
     double2 v = make_double2(0.0, 0.0);
@@ -245,7 +245,7 @@ struct Transform {
   double2 *d_over[kMaxStreams] = {}, *d_res[kMaxStreams] = {}, *d_fbuf[kMaxStreams] = {};
   double *d_opow[kMaxStreams] = {}, *d_rpow[kMaxStreams] = {};
   // the host tables, formed before any device work
-  std::vector<int32_t> rs_n, rs_k, rs_in;
+  std::vector<int32_t> rs_o, rs_k, rs_in;
   std::vector<double> rs_c, rtw;
   const double *wts, *pscale;
   double df;
@@ -266,12 +266,12 @@ struct Transform {
   int prepare(int64_t tc, int64_t last, int nstreams, const hipStream_t* streams) {
     const int64_t lines = tc * nwin * nt;
     double *d_wts, *d_ps = nullptr;
-    int32_t *d_rsn, *d_rsk, *d_rsin;
+    int32_t *d_rso, *d_rsk, *d_rsin;
     double2 *d_rsc, *d_rtw;
     hipStream_t s0 = streams[0];
     DEV_UPLOAD(ctx, wk.dev, d_wts, wts, (size_t)nwin * nchan, s0);
     if (pscale) DEV_UPLOAD(ctx, wk.dev, d_ps, pscale, (size_t)nwin, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_rsn, rs_n, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_rso, rs_o, s0);
     DEV_UPLOAD(ctx, wk.dev, d_rsk, rs_k, s0);
     DEV_UPLOAD(ctx, wk.dev, d_rsin, rs_in, s0);
     DEV_UPLOAD(ctx, wk.dev, d_rsc, rs_c, s0);
@@ -293,11 +293,21 @@ struct Transform {
     base.nwin = nwin; base.nchan = (int)nchan; base.nt = (int)nt; base.m = (int)m; base.logm = logm; base.nres = (int)std::max<int64_t>(nres, 1);
     base.tile = (int)tile; base.ntiles = (int)ntiles; base.rtile = (int)rtile; base.rntiles = (int)rntiles;
     base.df = df;
-    base.rs_n = d_rsn; base.rs_k = d_rsk; base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw;
+    base.rs_o = d_rso; base.rs_k = d_rsk; base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw;
     base.over = nullptr; base.over_pow = nullptr; base.res = nullptr; base.res_pow = nullptr; base.fbuf = nullptr;
     if (fused && want_over())
       if (int rc = allow_lds(ctx, k_cpd_fused, lds)) return rc;
     return want_res() ? allow_lds(ctx, k_cpd_resample, rlds) : PRISIM_OK;
+  }
+
+  // `kernel` over `lines` lines of `per_line` workgroups each, in as many launches as the grid's x extent asks for
+  template <typename K, typename... A>
+  int launch_lines(K kernel, int64_t lines, int64_t per_line, size_t lds_bytes, hipStream_t s, const CdParams& P, A... a) {
+    const int64_t step = std::max<int64_t>(1, kMaxGrid / per_line);
+    for (int64_t l0 = 0; l0 < lines; l0 += step) {
+      if (int rc = launch(ctx, kernel, dim3((unsigned)(std::min(step, lines - l0) * per_line)), lds_bytes, s, P, l0, a...)) return rc;
+    }
+    return PRISIM_OK;
   }
 
   int kernels(int i, hipStream_t s, int64_t tn, const double* d_phase) {
@@ -307,37 +317,15 @@ struct Transform {
     const int64_t lines = tn * nwin;
     if (want_over()) {
       if (fused) {
-        const int64_t step = std::max<int64_t>(1, kMaxGrid / ntiles);
-        for (int64_t l0 = 0; l0 < lines; l0 += step) {
-          hipLaunchKernelGGL(k_cpd_fused, dim3((unsigned)(std::min(step, lines - l0) * ntiles)), dim3(kThreads), (size_t)lds, s, P, l0);
-          HIPCHK(ctx, hipGetLastError());
-        }
+        if (int rc = launch_lines(k_cpd_fused, lines, ntiles, (size_t)lds, s, P)) return rc;
       } else {
         const int64_t nct = (m + kTile - 1) / kTile, ntt = (nt + kTile - 1) / kTile;
-        const int64_t step = std::max<int64_t>(1, kMaxGrid / (nct * ntt));
-        for (int64_t l0 = 0; l0 < lines; l0 += step) {
-          hipLaunchKernelGGL(k_cpd_prepare, dim3((unsigned)(std::min(step, lines - l0) * nct * ntt)), dim3(kThreads), 0, s, P, l0, (int)nct,
-                             (int)ntt);
-          HIPCHK(ctx, hipGetLastError());
-        }
-        void* b[1] = {d_fbuf[i]};
-        if (g_rocfft.execute(wk.fft.at(true, (size_t)lines * (size_t)nt), b, nullptr, wk.fft.info[i]) != rocfft_status_success)
-          return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
-        for (int64_t l0 = 0; l0 < lines; l0 += step) {
-          hipLaunchKernelGGL(k_cpd_finish, dim3((unsigned)(std::min(step, lines - l0) * nct * ntt)), dim3(kThreads), 0, s, P, l0, (int)nct,
-                             (int)ntt);
-          HIPCHK(ctx, hipGetLastError());
-        }
+        if (int rc = launch_lines(k_cpd_prepare, lines, nct * ntt, 0, s, P, (int)nct, (int)ntt)) return rc;
+        if (int rc = wk.fft.run(ctx, true, (size_t)lines * (size_t)nt, d_fbuf[i], i)) return rc;
+        if (int rc = launch_lines(k_cpd_finish, lines, nct * ntt, 0, s, P, (int)nct, (int)ntt)) return rc;
       }
     }
-    if (want_res()) {
-      const int64_t step = std::max<int64_t>(1, kMaxGrid / rntiles);
-      for (int64_t l0 = 0; l0 < lines; l0 += step) {
-        hipLaunchKernelGGL(k_cpd_resample, dim3((unsigned)(std::min(step, lines - l0) * rntiles)), dim3(kThreads), (size_t)rlds, s, P, l0);
-        HIPCHK(ctx, hipGetLastError());
-      }
-    }
-    return PRISIM_OK;
+    return want_res() ? launch_lines(k_cpd_resample, lines, rntiles, (size_t)rlds, s, P) : PRISIM_OK;
   }
 
   int download(int i, hipStream_t s, int64_t T0, int64_t tn) {
@@ -389,9 +377,8 @@ int prisim_closure_delay_spectra(prisim_ctx* ctx, const double* phases, int64_t 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int lds_max = 0;
   if (int rc = lds_limit(ctx, lds_max)) return rc;
-  const int64_t tw_bytes = 16 * std::max<int64_t>(m / 2, 1), row_bytes = 16 * (m + 1);
-  const int64_t ftile = std::max<int64_t>(1, std::min<int64_t>({nt, (int64_t)kMaxTile, (kTileLds - tw_bytes) / row_bytes}));
-  const int64_t flds = ftile * row_bytes + tw_bytes;
+  const SnapshotTile ft = snapshot_tile(nt, 16 * (m + 1), 16 * std::max<int64_t>(m / 2, 1));
+  const int64_t flds = ft.lds;
   const bool fused_ok = pow2 && flds <= lds_max;
   if (route == PRISIM_CPDELAY_FUSED && !fused_ok)
     return fail(ctx, PRISIM_EINVAL, "the fused route takes a power-of-two m whose rows fit in LDS (" + std::to_string(flds) +
@@ -401,64 +388,43 @@ int prisim_closure_delay_spectra(prisim_ctx* ctx, const double* phases, int64_t 
   tr.over = over; tr.over_pow = over_pow; tr.res = res; tr.res_pow = res_pow;
   tr.wts = wts; tr.pscale = (tr.w_opow || tr.w_rpow) ? pscale : nullptr; tr.df = df;
   if (tr.fused) {
-    tr.tile = ftile; tr.ntiles = (nt + ftile - 1) / ftile; tr.lds = flds;
+    tr.tile = ft.tile; tr.ntiles = ft.ntiles; tr.lds = flds;
   } else {
     tr.lds = (int64_t)sizeof(double2) * kTile * (kTile + 1);
   }
   if (tr.want_res()) {
-    tr.rtile = std::max<int64_t>(1, std::min<int64_t>({nt, (int64_t)kMaxTile, kTileLds / (16 * nres)}));
-    tr.rntiles = (nt + tr.rtile - 1) / tr.rtile;
-    tr.rlds = 16 * nres * tr.rtile;
+    const SnapshotTile rt = snapshot_tile(nt, 16 * nres, 0);
+    tr.rtile = rt.tile; tr.rntiles = rt.ntiles; tr.rlds = rt.lds;
     if (tr.rlds > lds_max) return fail(ctx, PRISIM_EINVAL, "a resampled row does not fit in LDS");
   }
   if (!tr.fused && tr.want_over()) {
     if (int rc = ensure_rocfft(ctx)) return rc;
   }
 
-  // the resampling tables: per window, the output bins that some nonzero channel of the window feeds
+  // the resampling tables: per window, the output bins that some nonzero channel of the window feeds, and their terms compacted,
+  // with the window's weight folded into the coefficient
   const int64_t nr = std::max<int64_t>(nres, 1);
-  tr.rs_n.assign((size_t)nwin, 0);
-  tr.rs_k.assign((size_t)nwin * nr, 0);
+  ResampleTables rs;
+  if (int rc = build_resample_tables(ctx, nres, m, nchan, df, nmap, map_out, map_in, map_w, rs, nullptr)) return rc;
+  fed_bins(rs, nres, nwin, nchan, wts, Feeds::kNonzero, tr.rs_o, tr.rs_k);
   tr.rs_in.assign((size_t)nwin * 2 * nr, -1);
   tr.rs_c.assign((size_t)nwin * 4 * nr, 0.0);
-  tr.rtw.assign(2 * (size_t)nr, 0.0);
-  if (nres > 0) {
-    if (nmap < 1 || !map_out || !map_in || !map_w) return fail(ctx, PRISIM_EINVAL, "the resampled spectra need the selection map");
-    std::vector<int64_t> first((size_t)nres, -1), second((size_t)nres, -1);
-    for (int64_t e = 0; e < nmap; ++e) {
-      const int64_t k = map_out[e], kin = map_in[e];
-      if (k < 0 || k >= nres || kin < 0 || kin >= m) return fail(ctx, PRISIM_EINVAL, "selection map entry out of range");
-      if (first[(size_t)k] < 0) first[(size_t)k] = e;
-      else if (second[(size_t)k] < 0) second[(size_t)k] = e;
-      else return fail(ctx, PRISIM_EINVAL, "selection map: more than two entries for one output bin");
-    }
-    const int64_t half = m / 2;
-    for (int w = 0; w < nwin; ++w) {
-      int32_t n = 0;
-      for (int64_t k = 0; k < nres; ++k) {
-        int terms = 0;
-        for (int64_t e : {first[(size_t)k], second[(size_t)k]}) {
-          if (e < 0) continue;
-          const int64_t kin = map_in[e];
-          if (kin >= nchan || wts[(int64_t)w * nchan + kin] == 0.0) continue;     // a bin of the zero padding, or outside the window
-          const double a = -2.0 * M_PI * (double)((kin * half) % m) / (double)m;  // e^{-2 pi i k_in floor(m/2) / m}
-          const double sc = wts[(int64_t)w * nchan + kin] * map_w[e] * df;        // weight * (m df) * (1 / m)
-          const size_t at = ((size_t)w * 2 + terms) * nr + n;
-          tr.rs_in[at] = (int32_t)kin;
-          tr.rs_c[2 * at] = sc * std::cos(a);
-          tr.rs_c[2 * at + 1] = sc * std::sin(a);
-          ++terms;
-        }
-        if (terms) tr.rs_k[(size_t)w * nr + n++] = (int32_t)k;
+  tr.rtw = rs.rtw;
+  for (int w = 0; w < nwin; ++w)
+    for (int32_t n = 0; n < tr.rs_o[(size_t)w + 1] - tr.rs_o[(size_t)w]; ++n) {
+      const int64_t k = tr.rs_k[(size_t)tr.rs_o[(size_t)w] + n];
+      int terms = 0;
+      for (int sl = 0; sl < 2; ++sl) {
+        const size_t e = (size_t)sl * nres + k;
+        const int64_t kin = rs.in[e];
+        if (kin < 0 || wts[(int64_t)w * nchan + kin] == 0.0) continue;          // none, a bin of the zero padding, or outside the window
+        const double sc = wts[(int64_t)w * nchan + kin] * rs.w[e] * df;          // weight * (m df) * (1 / m)
+        const size_t at = ((size_t)w * 2 + terms++) * nr + n;
+        tr.rs_in[at] = (int32_t)kin;
+        tr.rs_c[2 * at] = sc * rs.phase[2 * e];
+        tr.rs_c[2 * at + 1] = sc * rs.phase[2 * e + 1];
       }
-      tr.rs_n[(size_t)w] = n;
     }
-    for (int64_t q = 0; q < nres; ++q) {
-      const double a = 2.0 * M_PI * (double)q / (double)nres;
-      tr.rtw[2 * q] = std::cos(a);
-      tr.rtw[2 * q + 1] = std::sin(a);
-    }
-  }
 
   const int64_t per = nchan * nt;
   const int64_t tables = (int64_t)nwin * nchan * 8 + (int64_t)nwin * 8 + (int64_t)nwin * nr * 44 + nr * 16;
@@ -486,18 +452,13 @@ int prisim_closure_delay_spectra(prisim_ctx* ctx, const double* phases, int64_t 
     Streams& st = tr.wk.st;
     if (int rc = st.create(ctx, nstreams, true)) return rc;
     if (int rc = tr.prepare(tc, ch.last, nstreams, st.s)) return rc;
-    for (int64_t c = 0; c < nchunks; ++c) {
-      const int i = (int)(c % nstreams);
-      hipStream_t sc = st.s[i];
-      if (int rc = st.harvest(ctx, i)) return rc;
-      const int64_t T0 = c * tc, tn = std::min(tc, nrows - T0);
-      HIPCHK(ctx, hipMemcpyAsync(d_phase[i], phases + (size_t)T0 * per, (size_t)tn * per * 8, hipMemcpyHostToDevice, sc));
-      if (int rc = st.open(ctx, i)) return rc;
-      if (int rc = tr.kernels(i, sc, tn, d_phase[i])) return rc;
-      if (int rc = st.close(ctx, i)) return rc;
-      if (int rc = tr.download(i, sc, T0, tn)) return rc;
-    }
-    if (int rc = st.drain(ctx)) return rc;
+    auto send = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+      HIPCHK(ctx, hipMemcpyAsync(d_phase[i], phases + (size_t)sp.first * per, (size_t)sp.count * per * 8, hipMemcpyHostToDevice, sc));
+      return PRISIM_OK;
+    };
+    auto kernels = [&](int64_t, Span sp, int i, hipStream_t sc) { return tr.kernels(i, sc, sp.count, d_phase[i]); };
+    auto fetch = [&](int64_t, Span sp, int i, hipStream_t sc) { return tr.download(i, sc, sp.first, sp.count); };
+    if (int rc = chunk_loop(ctx, st, ch, nrows, send, kernels, fetch)) return rc;
     kernel_ms = st.kernel_ms;
     upload += nrows * per * 8;
   }
@@ -559,20 +520,20 @@ int prisim_closure_power(prisim_ctx* ctx, int64_t n0, int64_t nwin, int64_t inne
     HIPCHK(ctx, hipMemsetAsync(d_sum, 0, npts * 16, s));
   }
   const int g = grid_for(ctx, npts);
-  for (int64_t c = 0; c < nchunks; ++c) {
-    const int64_t r0 = c * rc_rows, rn = std::min(rc_rows, n0 - r0);
-    HIPCHK(ctx, hipMemcpyAsync(d_x, spectra + 2 * (size_t)r0 * npts, (size_t)rn * npts * 16, hipMemcpyHostToDevice, s));
-    if (int rc = st.open(ctx, 0)) return rc;
-    hipLaunchKernelGGL(k_cpp_accumulate, dim3((unsigned)g), dim3(kThreads), 0, s, d_x, rn, npts, inner, d_scale, d_ind, d_sumsq, d_sum);
-    HIPCHK(ctx, hipGetLastError());
-    if (sums && c == nchunks - 1) {
-      hipLaunchKernelGGL(k_cpp_finish, dim3((unsigned)g), dim3(kThreads), 0, s, n0, npts, inner, d_scale, d_sumsq, d_sum, d_auto, d_cross);
-      HIPCHK(ctx, hipGetLastError());
-    }
-    if (int rc = st.close(ctx, 0)) return rc;
-    if (w_ind) HIPCHK(ctx, hipMemcpyAsync(out_individual + (size_t)r0 * npts, d_ind, (size_t)rn * npts * 8, hipMemcpyDeviceToHost, s));
-    if (int rc = st.drain(ctx)) return rc;          // the chunk's buffers are reused by the next one
-  }
+  auto upload = [&](int64_t, Span sp, int, hipStream_t) -> int {
+    HIPCHK(ctx, hipMemcpyAsync(d_x, spectra + 2 * (size_t)sp.first * npts, (size_t)sp.count * npts * 16, hipMemcpyHostToDevice, s));
+    return PRISIM_OK;
+  };
+  auto kernels = [&](int64_t c, Span sp, int, hipStream_t) -> int {
+    if (int rc = launch(ctx, k_cpp_accumulate, dim3((unsigned)g), 0, s, d_x, sp.count, npts, inner, d_scale, d_ind, d_sumsq, d_sum)) return rc;
+    if (!sums || c < nchunks - 1) return PRISIM_OK;
+    return launch(ctx, k_cpp_finish, dim3((unsigned)g), 0, s, n0, npts, inner, d_scale, d_sumsq, d_sum, d_auto, d_cross);
+  };
+  auto download = [&](int64_t, Span sp, int, hipStream_t) -> int {
+    if (w_ind) HIPCHK(ctx, hipMemcpyAsync(out_individual + (size_t)sp.first * npts, d_ind, (size_t)sp.count * npts * 8, hipMemcpyDeviceToHost, s));
+    return PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, n0, upload, kernels, download)) return rc;   // one stream: its order guards d_x, d_ind and the sums
   if (w_auto) HIPCHK(ctx, hipMemcpyAsync(out_auto, d_auto, npts * 8, hipMemcpyDeviceToHost, s));
   if (w_cross) HIPCHK(ctx, hipMemcpyAsync(out_cross, d_cross, npts * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));

@@ -157,9 +157,10 @@ int prisim_cphase_diff(prisim_ctx* ctx, const double* in_mean, const double* in_
   for (int o = 0; o < 8; ++o) DEV_ALLOC(ctx, wk.dev, d_out[o], rows_out * tc * nchan * (int64_t)es[o]);
   int64_t upload_bytes = ncomb * 16, download_bytes = 0;
 
-  for (int64_t c = 0; c < nchunks; ++c) {
-    const int64_t T0 = c * tc, tn = std::min(tc, ntriads - T0);
-    DiffParams p{};
+  DiffParams p{};                                     // of the chunk in hand
+  auto upload = [&](int64_t, Span sp, int, hipStream_t) -> int {
+    const int64_t T0 = sp.first, tn = sp.count;
+    p = DiffParams{};
     if (resident) {
       const int64_t o = T0 * nchan;
       p.pm = resident->a + o;
@@ -188,19 +189,23 @@ int prisim_cphase_diff(prisim_ctx* ctx, const double* in_mean, const double* in_
     p.n1 = n1;
     p.ncomb = ncomb;
     p.nruns = (ncomb + kRun - 1) / kRun;
-    const int64_t total = n0 * p.nruns * tn * nchan;
+    return PRISIM_OK;
+  };
+  auto kernels = [&](int64_t, Span sp, int, hipStream_t) -> int {
+    const int64_t total = n0 * p.nruns * sp.count * nchan;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((total + kThreads - 1) / kThreads, kMaxBlocks));
-    if (int rc = st.open(ctx, 0)) return rc;
-    hipLaunchKernelGGL(k_cpdiff, dim3((unsigned)blocks), dim3(kThreads), 0, s, p);
-    HIPCHK(ctx, hipGetLastError());
-    if (int rc = st.close(ctx, 0)) return rc;
+    return launch(ctx, k_cpdiff, dim3((unsigned)blocks), 0, s, p);
+  };
+  auto download = [&](int64_t, Span sp, int, hipStream_t) -> int {
+    const int64_t T0 = sp.first, tn = sp.count;
     for (int o = 0; o < 8; ++o) {
       HIPCHK(ctx, copy_rows(static_cast<char*>(host_out[o]) + (size_t)(T0 * nchan) * es[o], (size_t)row_elems * es[o], d_out[o],
                             (size_t)(tn * nchan) * es[o], (size_t)(tn * nchan) * es[o], rows_out, hipMemcpyDeviceToHost, s));
       download_bytes += rows_out * tn * nchan * (int64_t)es[o];
     }
-    if (int rc = st.drain(ctx)) return rc;          // the chunk's buffers are reused by the next one
-  }
+    return PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, ntriads, upload, kernels, download)) return rc;   // one stream: its order guards the reused buffers
   if (stats) {
     stats->wall_ms = wall_ms_since(wall0);
     stats->kernel_ms = st.kernel_ms;

@@ -60,8 +60,8 @@ struct FtParams {
   double2* res[kMaxPass];   // per pass this chunk's [nwin][rn][nres], or null
   double2* fbuf;            // rocFFT route: [pass - fpass0][nwin][rn][m]
   int fpass0;
-  const int32_t* rs_n;      // [nwin] bins of the resampled spectrum that the window feeds
-  const int32_t* rs_k;      // [nwin][nres] those bins, increasing
+  const int32_t* rs_o;      // [nwin + 1] bins of the resampled spectrum that window k feeds: rs_k[rs_o[k] .. rs_o[k + 1]), increasing
+  const int32_t* rs_k;
   const int32_t* rs_in;     // [2][nres] channels of a bin (-1: none)
   const double2* rs_c;      // [2][nres] weight df e^{-2 pi i k_in floor(m/2) / m}
   const double2* rtw;       // [nres] e^{+2 pi i q / nres}
@@ -192,8 +192,8 @@ __global__ void __launch_bounds__(kThreads) k_cpft_resample(const FtParams P) {
   for (int p = 0; p < npass; ++p) {
     if (!P.res[p]) continue;
     for (int k = 0; k < P.nwin; ++k) {
-      const int nz = P.rs_n[k];
-      const int32_t* kout = P.rs_k + (int64_t)k * nres;
+      const int nz = P.rs_o[k + 1] - P.rs_o[k];
+      const int32_t* kout = P.rs_k + P.rs_o[k];
       for (int e = threadIdx.x; e < g.rc * nz; e += kThreads) {
         const int rr = e / nz, i = e - rr * nz, kk = kout[i];
         double2 v = make_double2(0.0, 0.0);
@@ -271,9 +271,9 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
   const int logm = ceil_log2(m, pow2);
   if (route == PRISIM_CPFT_FUSED && !pow2)
     return fail(ctx, PRISIM_EINVAL, "the fused route takes a power-of-two m; got m = " + std::to_string(m));
-  std::vector<int32_t> rs_in;
-  std::vector<double> rs_c, rtw;
-  if (int rc = build_resample_tables(ctx, nres, m, nchan, df, nmap, map_out, map_in, map_w, rs_in, rs_c, rtw)) return rc;
+  ResampleTables rs;
+  std::vector<double> rs_c;
+  if (int rc = build_resample_tables(ctx, nres, m, nchan, df, nmap, map_out, map_in, map_w, rs, &rs_c)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int lds_max = 0;
   if (int rc = lds_limit(ctx, lds_max)) return rc;
@@ -302,19 +302,8 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
   }
 
   // the bins of the resampled spectrum that a window feeds
-  std::vector<int32_t> rs_n((size_t)nwin, 0), rs_k((size_t)nwin * nr, 0);
-  for (int k = 0; k < nwin && nres > 0; ++k) {
-    int32_t n = 0;
-    for (int64_t q = 0; q < nres; ++q) {
-      bool fed = false;
-      for (int s = 0; s < 2; ++s) {
-        const int32_t ch = rs_in[(size_t)s * nres + q];
-        if (ch >= 0 && wts[(int64_t)k * nchan + ch] != 0.0) fed = true;
-      }
-      if (fed) rs_k[(size_t)k * nr + n++] = (int32_t)q;
-    }
-    rs_n[(size_t)k] = n;
-  }
+  std::vector<int32_t> rs_o, rs_k;
+  fed_bins(rs, nres, nwin, nchan, wts, Feeds::kNonzero, rs_o, rs_k);
 
   // passes: the inputs, then the lag kernel.  With weights the lag kernel is one more output per row; without, one row of its own.
   const int lag_rows = (w_lag && has_w) ? 1 : 0;
@@ -341,15 +330,15 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
   if (int rc = st.create(ctx, nstreams, true)) return rc;
   hipStream_t s0 = st.s[0];
   double *d_wts, *d_vs = nullptr;
-  int32_t *d_rsn, *d_rsk, *d_rsin;
+  int32_t *d_rso, *d_rsk, *d_rsin;
   double2 *d_rsc, *d_rtw;
   DEV_UPLOAD(ctx, wk.dev, d_wts, wts, (size_t)nwin * nchan, s0);
   if (vscale) DEV_UPLOAD(ctx, wk.dev, d_vs, vscale, (size_t)nwin * n0, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_rsn, rs_n, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_rso, rs_o, s0);
   DEV_UPLOAD(ctx, wk.dev, d_rsk, rs_k, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_rsin, rs_in, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_rsin, rs.in, s0);
   DEV_UPLOAD(ctx, wk.dev, d_rsc, rs_c, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_rtw, rtw, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_rtw, rs.rtw, s0);
   double2* d_bcast[kMaxIn] = {};
   for (int i = 0; i < nin; ++i)
     if (!chunked[i]) DEV_UPLOAD(ctx, wk.dev, d_bcast[i], inputs[i], (size_t)in_rows[i] * nchan * 2, s0);
@@ -404,7 +393,7 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
   base.nwin = nwin; base.nchan = (int)nchan; base.m = (int)m; base.logm = logm; base.nres = (int)nr;
   base.df = df;
   base.fpass0 = fpass0;
-  base.rs_n = d_rsn; base.rs_k = d_rsk; base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw;
+  base.rs_o = d_rso; base.rs_k = d_rsk; base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw;
   const size_t lds_rows = rows_lds(R), lds_res = res_lds(Rr);
   if (any_over)
     if (int rc = fused ? allow_lds(ctx, k_cpft_rows<true>, lds_rows) : allow_lds(ctx, k_cpft_rows<false>, lds_rows)) return rc;
@@ -412,7 +401,7 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
     if (int rc = allow_lds(ctx, k_cpft_resample, lds_res)) return rc;
 
   // the kernels of one set of rows on stream s: P holds the rows, the passes and their buffers
-  auto launch = [&](FtParams P, int si, size_t batch) -> int {
+  auto run_rows = [&](FtParams P, int si, size_t batch) -> int {
     hipStream_t s = st.s[si];
     bool has_over = false, has_res = false;
     for (int p = 0; p < P.nin + P.lagk; ++p) {
@@ -424,37 +413,32 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
       P.G = kThreads / pow2_at_least(R);
       const unsigned blocks = (unsigned)((P.rn + R - 1) / R);
       if (fused) {
-        hipLaunchKernelGGL(k_cpft_rows<true>, dim3(blocks), dim3(kThreads), lds_rows, s, P);
-        HIPCHK(ctx, hipGetLastError());
+        if (int rc = launch(ctx, k_cpft_rows<true>, dim3(blocks), lds_rows, s, P)) return rc;
       } else {
-        hipLaunchKernelGGL(k_cpft_rows<false>, dim3(blocks), dim3(kThreads), lds_rows, s, P);
-        HIPCHK(ctx, hipGetLastError());
-        void* b[1] = {P.fbuf};
-        if (g_rocfft.execute(wk.fft.at(true, batch), b, nullptr, wk.fft.info[si]) != rocfft_status_success)
-          return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
-        hipLaunchKernelGGL(k_cpft_finish, dim3((unsigned)grid_for(ctx, (int64_t)P.nwin * P.rn * m)), dim3(kThreads), 0, s, P);
-        HIPCHK(ctx, hipGetLastError());
+        if (int rc = launch(ctx, k_cpft_rows<false>, dim3(blocks), lds_rows, s, P)) return rc;
+        if (int rc = wk.fft.run(ctx, true, batch, P.fbuf, si)) return rc;
+        if (int rc = launch(ctx, k_cpft_finish, dim3((unsigned)grid_for(ctx, (int64_t)P.nwin * P.rn * m)), 0, s, P)) return rc;
       }
     }
     if (has_res) {
       P.R = Rr;
       P.G = kThreads / pow2_at_least(Rr);
-      hipLaunchKernelGGL(k_cpft_resample, dim3((unsigned)((P.rn + Rr - 1) / Rr)), dim3(kThreads), lds_res, s, P);
-      HIPCHK(ctx, hipGetLastError());
+      if (int rc = launch(ctx, k_cpft_resample, dim3((unsigned)((P.rn + Rr - 1) / Rr)), lds_res, s, P)) return rc;
     }
     return PRISIM_OK;
   };
 
   int64_t upload = tables + bcast_bytes, download = 0;
-  for (int64_t c = 0; c < nchunks; ++c) {
-    const int si = (int)(c % nstreams);
-    hipStream_t s = st.s[si];
-    if (int rc = st.harvest(ctx, si)) return rc;
-    const int64_t r0 = c * tc, rn = std::min(tc, rows - r0);
+  auto upload_rows = [&](int64_t, Span sp, int si, hipStream_t s) -> int {
+    const int64_t r0 = sp.first, rn = sp.count;
     for (int i = 0; i < nin; ++i)
       if (chunked[i]) HIPCHK(ctx, hipMemcpyAsync(d_in[si][i], inputs[i] + 2 * (size_t)r0 * nchan, (size_t)rn * nchan * 16, hipMemcpyHostToDevice, s));
     if (has_w) HIPCHK(ctx, hipMemcpyAsync(d_w[si], w + (size_t)r0 * nchan, (size_t)rn * nchan * 8, hipMemcpyHostToDevice, s));
     upload += rn * nchan * (nstreamed * 16 + (has_w ? 8 : 0));
+    return PRISIM_OK;
+  };
+  auto kernels = [&](int64_t c, Span sp, int si, hipStream_t) -> int {
+    const int64_t r0 = sp.first, rn = sp.count;
     FtParams P = base;
     for (int i = 0; i < nin; ++i)
       if (chunked[i]) P.in[i].p = d_in[si][i];
@@ -465,16 +449,18 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
       P.res[p] = d_res[si][p];
     }
     P.fbuf = d_fbuf[si];
-    if (int rc = st.open(ctx, si)) return rc;
-    if (int rc = launch(P, si, (size_t)npass_over * nwin * rn)) return rc;
+    if (int rc = run_rows(P, si, (size_t)npass_over * nwin * rn)) return rc;
     if (lone_lag && c == 0) {
       FtParams L = base;
       L.nin = 0; L.lagk = 1; L.w = nullptr; L.vscale = nullptr;
       L.row0 = 0; L.rn = 1; L.n0 = L.n1 = L.n2 = 1;
       L.over[0] = d_lagk; L.res[0] = d_lagk_res; L.fbuf = d_lagk_f; L.fpass0 = 0;
-      if (int rc = launch(L, si, (size_t)nwin)) return rc;
+      if (int rc = run_rows(L, si, (size_t)nwin)) return rc;
     }
-    if (int rc = st.close(ctx, si)) return rc;
+    return PRISIM_OK;
+  };
+  auto fetch_rows = [&](int64_t c, Span sp, int si, hipStream_t s) -> int {
+    const int64_t r0 = sp.first, rn = sp.count;
     // a chunk's [nwin][rn][len] into the caller's [nwin][rows][len]
     auto fetch = [&](double* host, const double2* dev, int64_t len) -> int {
       HIPCHK(ctx, copy_rows(host + 2 * (size_t)r0 * len, (size_t)rows * len * 16, dev, (size_t)rn * len * 16, (size_t)rn * len * 16, (size_t)nwin,
@@ -494,8 +480,9 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
       if (lag_res) HIPCHK(ctx, hipMemcpyAsync(lag_kernel_res, d_lagk_res, (size_t)nwin * nres * 16, hipMemcpyDeviceToHost, s));
       download += (int64_t)nwin * (m + nres) * 16;
     }
-  }
-  if (int rc = st.drain(ctx)) return rc;
+    return PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, rows, upload_rows, kernels, fetch_rows)) return rc;
   if (stats) {
     stats->wall_ms = wall_ms_since(wall0);
     stats->kernel_ms = st.kernel_ms;

@@ -248,12 +248,9 @@ int prisim_cphase_xpower(prisim_ctx* ctx, int64_t nspw, int64_t n1, int64_t n2, 
   HIPCHK(ctx, hipStreamSynchronize(s0));              // the other stream starts behind the inputs
 
   int64_t download = 0;
-  for (int64_t c = 0; c < nchunks; ++c) {
-    const int si = (int)(c % nstreams);
-    hipStream_t s = st.s[si];
-    if (int rc = st.harvest(ctx, si)) return rc;
-    const int64_t w = c / ch.count, l0 = (c - w * ch.count) * tc, cl = std::min(tc, nlags - l0);
-    if (int rc = st.open(ctx, si)) return rc;
+  // chunk c: a range of the lags of window c / ch.count
+  auto kernels = [&](int64_t c, Span sp, int si, hipStream_t s) -> int {
+    const int64_t w = c / ch.count, l0 = sp.first, cl = sp.count;
     XpCross X = {};
     X.a = d_a + (size_t)w * n1 * n2 * n3 * nlags;
     X.b = d_b + (size_t)w * n1 * n2 * n3 * nlags;
@@ -269,8 +266,7 @@ int prisim_cphase_xpower(prisim_ctx* ctx, int64_t nspw, int64_t n1, int64_t n2, 
     X.l0 = l0; X.cl = cl;
     X.total = pe * cl;
     X.out = d_buf[si][0];
-    hipLaunchKernelGGL(k_xp_cross, dim3((unsigned)grid_for(ctx, X.total)), dim3(kThreads), 0, s, X);
-    HIPCHK(ctx, hipGetLastError());
+    if (int rc = launch(ctx, k_xp_cross, dim3((unsigned)grid_for(ctx, X.total)), 0, s, X)) return rc;
     int64_t ca[3], cb[3];
     std::copy(da, da + 3, ca);
     std::copy(db, db + 3, cb);
@@ -286,20 +282,21 @@ int prisim_cphase_xpower(prisim_ctx* ctx, int64_t nspw, int64_t n1, int64_t n2, 
       C.da = ca[x]; C.db = cb[x];
       C.dout = x == 0 ? nshift : 2 * n[x] - 1;
       const unsigned blocks = (unsigned)grid_for(ctx, C.outer * C.dout * C.inner);
-      if (x != 0) hipLaunchKernelGGL(k_xp_trace, dim3(blocks), dim3(kThreads), 0, s, C);
-      else if (stat == PRISIM_CPXPS_MEAN) hipLaunchKernelGGL(k_xp_lst_mean, dim3(blocks), dim3(kThreads), 0, s, C);
-      else hipLaunchKernelGGL(k_xp_lst_median, dim3(blocks), dim3(kThreads), 0, s, C);
-      HIPCHK(ctx, hipGetLastError());
+      if (int rc = launch(ctx, x != 0 ? k_xp_trace : stat == PRISIM_CPXPS_MEAN ? k_xp_lst_mean : k_xp_lst_median, dim3(blocks), 0, s, C)) return rc;
       ca[x] = C.dout;
       cb[x] = 1;
     }
-    if (int rc = st.close(ctx, si)) return rc;
-    // the chunk's [oe][cl] into the caller's [nspw][oe][nlags]
+    return PRISIM_OK;
+  };
+  // the chunk's [oe][cl] into the caller's [nspw][oe][nlags]
+  auto fetch = [&](int64_t c, Span sp, int si, hipStream_t s) -> int {
+    const int64_t w = c / ch.count, l0 = sp.first, cl = sp.count;
     HIPCHK(ctx, copy_rows(out + 2 * ((size_t)w * oe * nlags + l0), (size_t)nlags * 16, d_buf[si][ncollapse & 1], (size_t)cl * 16, (size_t)cl * 16,
                           (size_t)oe, hipMemcpyDeviceToHost, s));
     download += oe * cl * 16;
-  }
-  if (int rc = st.drain(ctx)) return rc;
+    return PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, nlags, no_step, kernels, fetch, nspw)) return rc;
   if (stats) {
     int64_t moved = 0;                                // per window and lag: every buffer written once, and read once by the next kernel
     for (int k = 0; k <= ncollapse; ++k) moved += stage[k] * (k < ncollapse ? 2 : 1);

@@ -244,38 +244,23 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
     if (int rc = ensure_rocfft(ctx)) return rc;
 
   // the resampling tables: per output bin at most two input bins (padding bins dropped), and per window the bins it can make nonzero
-  std::vector<int32_t> rs_in, klist, kofs((size_t)nwin + 1, 0);
-  std::vector<double> rs_c, rtw;
+  ResampleTables rs;
+  std::vector<int32_t> klist, kofs;
+  std::vector<double> rs_c;
   const double s = scale / (double)m;
   if (resample) {
-    if (int rc = build_resample_tables(ctx, nout, m, nchan, s, nmap, map_out, map_in, map_w, rs_in, rs_c, rtw)) return rc;
-    for (int w = 0; w < nwin; ++w) {
-      int64_t lo = 0, hi = nchan;
-      if (win) {
-        lo = nchan;
-        hi = 0;
-        for (int64_t n = 0; n < nchan; ++n)
-          if (win[w * nchan + n] != 0.0) { lo = std::min(lo, n); hi = n + 1; }
-      }
-      for (int64_t k = 0; k < nout; ++k)
-        for (int sl = 0; sl < 2; ++sl) {
-          const int32_t i = rs_in[(size_t)sl * nout + k];
-          if (i >= lo && i < hi) { klist.push_back((int32_t)k); break; }
-        }
-      kofs[(size_t)w + 1] = (int32_t)klist.size();
-    }
+    if (int rc = build_resample_tables(ctx, nout, m, nchan, s, nmap, map_out, map_in, map_w, rs, &rs_c)) return rc;
+    fed_bins(rs, nout, nwin, nchan, win, Feeds::kSpan, kofs, klist);
   }
 
   // snapshot tile, LDS and chunking
   int lds_max = 0;
   if (int rc = lds_limit(ctx, lds_max)) return rc;
-  const int64_t tw_bytes = 16 * std::max<int64_t>(m / 2, 1);
-  const int64_t row_bytes = 16 * (resample ? nout : m);
-  int64_t tile = 1;
-  if (rt != PRISIM_RUNS_ROCFFT) tile = std::max<int64_t>(1, std::min<int64_t>({nt, (int64_t)kMaxTile, (kTileLds - (resample ? 0 : tw_bytes)) / row_bytes}));
-  const int64_t lds = rt == PRISIM_RUNS_ROCFFT ? 0 : tile * row_bytes + (resample ? 0 : tw_bytes);
+  SnapshotTile sn = {1, nt, 0};                       // rocFFT route: no tiled kernel
+  if (rt == PRISIM_RUNS_FUSED) sn = snapshot_tile(nt, 16 * m, 16 * std::max<int64_t>(m / 2, 1));
+  if (rt == PRISIM_RUNS_DIRECT) sn = snapshot_tile(nt, 16 * nout, 0);
+  const int64_t tile = sn.tile, ntiles = sn.ntiles, lds = sn.lds;
   if (lds > lds_max) return fail(ctx, PRISIM_EINVAL, "rows do not fit in LDS (" + std::to_string(lds) + " B needed)");
-  const int64_t ntiles = (nt + tile - 1) / tile;
   const int64_t P = R * nbl;
   const int64_t in_pair = vis ? nchan * nt * (vis_is_c64 ? 8 : 16) : 0;
   const int64_t out_pair = (int64_t)nwin * nout * nt * 16;
@@ -300,9 +285,9 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
   if (wts) DEV_UPLOAD(ctx, wk.dev, d_wts, wts, (size_t)wts_n, s0);
   if (win) DEV_UPLOAD(ctx, wk.dev, d_win, win, (size_t)nwin * nchan, s0);
   if (resample) {
-    DEV_UPLOAD(ctx, wk.dev, d_rsin, rs_in, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_rsin, rs.in, s0);
     DEV_UPLOAD(ctx, wk.dev, d_rsc, rs_c, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_rtw, rtw, s0);
+    DEV_UPLOAD(ctx, wk.dev, d_rtw, rs.rtw, s0);
     DEV_UPLOAD(ctx, wk.dev, d_klist, klist, s0);
     DEV_UPLOAD(ctx, wk.dev, d_kofs, kofs, s0);
   }
@@ -335,39 +320,36 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
   if (rt == PRISIM_RUNS_DIRECT)
     if (int rc = allow_lds(ctx, k_runs_resample, lds)) return rc;
 
-  for (int64_t c = 0; c < nchunks; ++c) {
-    const int i = (int)(c % nstreams);
-    hipStream_t sc = st.s[i];
-    const int64_t p0 = c * pc, pn = std::min(pc, P - p0);
+  auto upload = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+    if (vis) HIPCHK(ctx, hipMemcpyAsync(d_in[i], (const char*)vis + (size_t)sp.first * (size_t)in_pair, (size_t)sp.count * in_pair,
+                                        hipMemcpyHostToDevice, sc));
+    return PRISIM_OK;
+  };
+  auto kernels = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+    const int64_t pn = sp.count;
     RunParams Pm = base;
-    Pm.p0 = p0; Pm.pc = pn; Pm.out = d_out[i]; Pm.fbuf = d_fbuf[i];
-    if (vis) {
-      const size_t off = (size_t)p0 * (size_t)in_pair;
-      HIPCHK(ctx, hipMemcpyAsync(d_in[i], (const char*)vis + off, (size_t)pn * in_pair, hipMemcpyHostToDevice, sc));
-      Pm.vis = d_in[i];
-    }
+    Pm.p0 = sp.first; Pm.pc = pn; Pm.out = d_out[i]; Pm.fbuf = d_fbuf[i];
+    if (vis) Pm.vis = d_in[i];
     if (rt == PRISIM_RUNS_FUSED) {
-      hipLaunchKernelGGL(k_runs_fused, dim3((unsigned)(pn * ntiles), (unsigned)nwin), dim3(kThreads), (size_t)lds, sc, Pm);
-      HIPCHK(ctx, hipGetLastError());
+      if (int rc = launch(ctx, k_runs_fused, dim3((unsigned)(pn * ntiles), (unsigned)nwin), (size_t)lds, sc, Pm)) return rc;
     } else if (rt == PRISIM_RUNS_DIRECT) {
-      hipLaunchKernelGGL(k_runs_resample, dim3((unsigned)(pn * ntiles), (unsigned)nwin), dim3(kThreads), (size_t)lds, sc, Pm);
-      HIPCHK(ctx, hipGetLastError());
+      if (int rc = launch(ctx, k_runs_resample, dim3((unsigned)(pn * ntiles), (unsigned)nwin), (size_t)lds, sc, Pm)) return rc;
     } else {
       const int64_t nf = (int64_t)nwin * pn * nt * m, no = (int64_t)nwin * pn * nout * nt;
-      hipLaunchKernelGGL(k_runs_prepare, dim3((unsigned)grid_for(ctx, nf)), dim3(kThreads), 0, sc, Pm);
-      HIPCHK(ctx, hipGetLastError());
-      void* b[1] = {d_fbuf[i]};
-      if (g_rocfft.execute(wk.fft.at(true, (size_t)nwin * (size_t)nt * (size_t)pn), b, nullptr, wk.fft.info[i]) != rocfft_status_success)
-        return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
-      hipLaunchKernelGGL(k_runs_finish, dim3((unsigned)grid_for(ctx, no)), dim3(kThreads), 0, sc, Pm);
-      HIPCHK(ctx, hipGetLastError());
+      if (int rc = launch(ctx, k_runs_prepare, dim3((unsigned)grid_for(ctx, nf)), 0, sc, Pm)) return rc;
+      if (int rc = wk.fft.run(ctx, true, (size_t)nwin * (size_t)nt * (size_t)pn, d_fbuf[i], i)) return rc;
+      if (int rc = launch(ctx, k_runs_finish, dim3((unsigned)grid_for(ctx, no)), 0, sc, Pm)) return rc;
     }
-    const size_t blk = (size_t)pn * nout * nt;      // complex elements of one window's block
+    return PRISIM_OK;
+  };
+  auto download = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+    const size_t blk = (size_t)sp.count * nout * nt;  // complex elements of one window's block
     for (int w = 0; w < nwin; ++w)
-      HIPCHK(ctx, hipMemcpyAsync(out + 2 * (((size_t)w * P + p0) * nout * nt), d_out[i] + (size_t)w * blk, blk * 16,
+      HIPCHK(ctx, hipMemcpyAsync(out + 2 * (((size_t)w * P + sp.first) * nout * nt), d_out[i] + (size_t)w * blk, blk * 16,
                                  hipMemcpyDeviceToHost, sc));
-  }
-  if (int rc = st.drain(ctx)) return rc;
+    return PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, P, upload, kernels, download)) return rc;
   if (stats) {
     stats->wall_ms = wall_ms_since(wall0);
     stats->pairs = P;
@@ -410,23 +392,27 @@ int prisim_runs_power(prisim_ctx* ctx, int64_t nf, int64_t inner, const void* v1
     DEV_ALLOC(ctx, wk.dev, d_o[i], ce * 8);
   }
   HIPCHK(ctx, hipStreamSynchronize(st.s[0]));
-  for (int64_t c = 0; c < nchunks; ++c) {
-    const int i = (int)(c % nstreams);
-    hipStream_t sc = st.s[i];
-    const int64_t e0 = c * ce, en = std::min(ce, n - e0);
+  auto upload = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+    const int64_t e0 = sp.first, en = sp.count;
     HIPCHK(ctx, hipMemcpyAsync(d_a[i], (const char*)v1 + e0 * esz, en * esz, hipMemcpyHostToDevice, sc));
     if (v2) HIPCHK(ctx, hipMemcpyAsync(d_b[i], (const char*)v2 + e0 * esz, en * esz, hipMemcpyHostToDevice, sc));
+    return PRISIM_OK;
+  };
+  auto kernels = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+    const int64_t e0 = sp.first, en = sp.count;
     const void* b = v2 ? d_b[i] : d_a[i];
+    const dim3 grid((unsigned)grid_for(ctx, en));
     if (is_c64)
-      hipLaunchKernelGGL(k_runs_power<float2>, dim3((unsigned)grid_for(ctx, en)), dim3(kThreads), 0, sc, (const float2*)d_a[i],
-                         (const float2*)b, (const double*)d_f, e0, en, inner, (int)(cross != 0), (int)(fused_product != 0), d_o[i]);
-    else
-      hipLaunchKernelGGL(k_runs_power<double2>, dim3((unsigned)grid_for(ctx, en)), dim3(kThreads), 0, sc, (const double2*)d_a[i],
-                         (const double2*)b, (const double*)d_f, e0, en, inner, (int)(cross != 0), (int)(fused_product != 0), d_o[i]);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out + e0, d_o[i], en * 8, hipMemcpyDeviceToHost, sc));
-  }
-  if (int rc = st.drain(ctx)) return rc;
+      return launch(ctx, k_runs_power<float2>, grid, 0, sc, (const float2*)d_a[i], (const float2*)b, (const double*)d_f, e0, en, inner,
+                    (int)(cross != 0), (int)(fused_product != 0), d_o[i]);
+    return launch(ctx, k_runs_power<double2>, grid, 0, sc, (const double2*)d_a[i], (const double2*)b, (const double*)d_f, e0, en, inner,
+                  (int)(cross != 0), (int)(fused_product != 0), d_o[i]);
+  };
+  auto download = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+    HIPCHK(ctx, hipMemcpyAsync(out + sp.first, d_o[i], sp.count * 8, hipMemcpyDeviceToHost, sc));
+    return PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, n, upload, kernels, download)) return rc;
   if (stats) {
     stats->wall_ms = wall_ms_since(wall0);
     stats->pairs = n;

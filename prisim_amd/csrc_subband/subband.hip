@@ -259,10 +259,10 @@ int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_
     span[2 * w] = (int32_t)(lo < hi ? lo : 0);
     span[2 * w + 1] = (int32_t)(lo < hi ? hi : 0);
   }
-  std::vector<int32_t> rs_in;
-  std::vector<double> rs_c, rtw;
+  ResampleTables rt;
+  std::vector<double> rs_c;
   // weight * (m df) * (1 / m): the ifft's 1 / nres times resample's nres / m
-  if (int rc = build_resample_tables(ctx, nres, m, nchan, df, nmap, map_out, map_in, map_w, rs_in, rs_c, rtw)) return rc;
+  if (int rc = build_resample_tables(ctx, nres, m, nchan, df, nmap, map_out, map_in, map_w, rt, &rs_c)) return rc;
 
   Work wk;
   Events ev;
@@ -281,9 +281,9 @@ int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_
   DEV_ALLOC(ctx, wk.dev, d_wts, w_bytes);
   DEV_ALLOC(ctx, wk.dev, d_ps, (size_t)nwin * 8);
   DEV_ALLOC(ctx, wk.dev, d_span, span.size() * 4);
-  DEV_ALLOC(ctx, wk.dev, d_rsin, rs_in.size() * 4);
+  DEV_ALLOC(ctx, wk.dev, d_rsin, rt.in.size() * 4);
   DEV_ALLOC(ctx, wk.dev, d_rsc, rs_c.size() * 8);
-  DEV_ALLOC(ctx, wk.dev, d_rtw, rtw.size() * 8);
+  DEV_ALLOC(ctx, wk.dev, d_rtw, rt.rtw.size() * 8);
   if (w_over) DEV_ALLOC(ctx, wk.dev, d_over, over_n * 16);
   if (w_opow) DEV_ALLOC(ctx, wk.dev, d_opow, over_n * 8);
   if (w_res) DEV_ALLOC(ctx, wk.dev, d_res, res_n * 16);
@@ -298,9 +298,9 @@ int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_
   HIPCHK(ctx, hipMemcpyAsync(d_wts, wts, w_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (pscale) HIPCHK(ctx, hipMemcpyAsync(d_ps, pscale, (size_t)nwin * 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d_span, span.data(), span.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(d_rsin, rs_in.data(), rs_in.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_rsin, rt.in.data(), rt.in.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d_rsc, rs_c.data(), rs_c.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(d_rtw, rtw.data(), rtw.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_rtw, rt.rtw.data(), rt.rtw.size() * 8, hipMemcpyHostToDevice, ctx->stream));
 
   SbParams P;
   P.src = cubes ? d_in : (const double2*)ctx->cube.p + t0 * nbl * nchan;
@@ -319,22 +319,18 @@ int prisim_subband_transform(prisim_ctx* ctx, int32_t ncubes, int64_t nt, int64_
       if (int rc = allow_lds(ctx, k_sb_fused, lds)) return rc;
       for (int64_t r0 = 0; r0 < nrows; r0 += kMaxGridRows) {
         P.row0 = r0;
-        hipLaunchKernelGGL(k_sb_fused, dim3((unsigned)std::min(kMaxGridRows, nrows - r0)), dim3(kThreads), (size_t)lds, ctx->stream, P);
-        HIPCHK(ctx, hipGetLastError());
+        if (int rc = launch(ctx, k_sb_fused, dim3((unsigned)std::min(kMaxGridRows, nrows - r0)), (size_t)lds, ctx->stream, P)) return rc;
       }
     } else {
       if (int rc = allow_lds(ctx, k_sb_prepare, lds)) return rc;
       for (int64_t r0 = 0; r0 < nrows; r0 += kMaxGridRows) {
         P.row0 = r0;
-        hipLaunchKernelGGL(k_sb_prepare, dim3((unsigned)std::min(kMaxGridRows, nrows - r0)), dim3(kThreads), (size_t)lds, ctx->stream, P);
-        HIPCHK(ctx, hipGetLastError());
+        if (int rc = launch(ctx, k_sb_prepare, dim3((unsigned)std::min(kMaxGridRows, nrows - r0)), (size_t)lds, ctx->stream, P)) return rc;
       }
       if (want_over) {
-        void* b[1] = {d_fbuf};
-        if (g_rocfft.execute(wk.fft.at(true, (size_t)nlines), b, nullptr, wk.fft.info[0]) != rocfft_status_success) return fail(ctx, PRISIM_ELIB, "rocfft_execute failed");
+        if (int rc = wk.fft.run(ctx, true, (size_t)nlines, d_fbuf, 0)) return rc;
         const int64_t blocks = std::min<int64_t>((int64_t)over_n / kThreads + 1, (int64_t)std::max(ctx->cu_count, 1) * 16);
-        hipLaunchKernelGGL(k_sb_finish, dim3((unsigned)blocks), dim3(kThreads), 0, ctx->stream, P, nlines);
-        HIPCHK(ctx, hipGetLastError());
+        if (int rc = launch(ctx, k_sb_finish, dim3((unsigned)blocks), 0, ctx->stream, P, nlines)) return rc;
       }
     }
   }
