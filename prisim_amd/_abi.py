@@ -100,6 +100,11 @@ CPAVG_EXPORTS = ('prisim_cphase_xavg', 'prisim_cphase_kbin')
 PRISIM_CPAVG_MIN_DIM, PRISIM_CPAVG_MAX_DIM = 5, 8
 PRISIM_CPAVG_AUTO, PRISIM_CPAVG_LDS, PRISIM_CPAVG_GLOBAL = -1, 0, 1
 CPAVG_ROUTES = {PRISIM_CPAVG_LDS: 'lds', PRISIM_CPAVG_GLOBAL: 'global'}
+# every symbol include/prisim_cpreal.h declares: closure phases of noise realisations (prisim_amd/csrc_closure/cpreal.hip)
+CPREAL_EXPORTS = ('prisim_closure_realizations',)
+PRISIM_CPREAL_AUTO, PRISIM_CPREAL_DIRECT, PRISIM_CPREAL_STAGED = -1, 0, 1
+CPREAL_ROUTES = {PRISIM_CPREAL_DIRECT: 'direct', PRISIM_CPREAL_STAGED: 'staged'}
+CPREAL_KINDS = {'noisy': 0, 'noise': 1}
 
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
@@ -278,6 +283,14 @@ class _PrisimCpavgStats(C.Structure):
     tests/test_cpavg.py holds it to the header."""
     _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('chunks', C.c_int64), ('kernel_bytes', C.c_int64),
                 ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('route', C.c_int32), ('lds_limit', C.c_int32)]
+
+
+class _PrisimCprealStats(C.Structure):
+    """prisim_cpreal_stats of include/prisim_cpreal.h, public as Context.PrisimCprealStats (see _PrisimCpxpsStats); tests/test_cpreal.py
+    holds it to the header."""
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('pairs', C.c_int64), ('chunks', C.c_int64),
+                ('chunk_pairs', C.c_int64), ('draws', C.c_int64), ('kernel_bytes', C.c_int64), ('download_bytes', C.c_int64),
+                ('route', C.c_int32), ('streams', C.c_int32), ('chan_tile', C.c_int32), ('lds_bytes', C.c_int32)]
 
 
 def numpy_fuses_complex_product(dtype):
@@ -471,6 +484,9 @@ def load_library():
     lib.prisim_cphase_kbin.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, C.c_int32, i64, vp, vp, vp, C.POINTER(_PrisimCpavgStats)]
     for name in CPAVG_EXPORTS:
         getattr(lib, name).restype = C.c_int
+    lib.prisim_closure_realizations.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, i64, C.c_uint64, i64, i64, C.c_int32, C.c_int32,
+                                                i64, vp, C.POINTER(_PrisimCprealStats)]
+    lib.prisim_closure_realizations.restype = C.c_int
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
                                              C.POINTER(vp), pst]
@@ -1171,6 +1187,52 @@ class Context(object):
                                                    _ptr(mk), 0 if mk is None else mk.shape[0], _ptr(mi), r, int(budget_bytes),
                                                    _ptr(trip), _ptr(phase), C.byref(st)), 'prisim_closure_phase')
         return trip, phase, dict(_stats_dict(st, route=CLOSURE_ROUTES), resident=x is None)
+
+    # ---- closure phases of noise realisations (include/prisim_cpreal.h) ----
+    PrisimCprealStats = _PrisimCprealStats
+
+    def closure_realizations(self, cube, cube_row, bl_global, rms, bpwts, legs, conj, seed, n_realize, first=0, kind='noisy', nt=None,
+                             route='auto', budget_bytes=CLOSURE_BUDGET):
+        """Closure phases of n_realize thermal-noise realisations, drawn and closed on the device (prisim_closure_realizations).
+        cube: (nt, nrow, nchan) complex128 on the host, the visibilities of the used rows; or None for the resident visibility slots
+        [0, nt) of this context, of which cube_row (nrow,) names the rows.  bl_global: (nrow,) the global baseline index of each used
+        row, the counter of the draw as in noise(bl_index=...); rms: the noise rms and bpwts: bp * bp_wts, each broadcastable to (nt,
+        nrow, nchan); legs, conj: (ntriads, 3) used rows and conjugation flags of the legs 12, 23, 31.  Realisation r is drawn under
+        the key seed + first + r; kind: 'noisy' (the visibilities with the noise added) or 'noise'; route: 'auto', 'direct' or
+        'staged'.  The output is streamed in chunks of (snapshot, realisation) pairs within budget_bytes of device memory; the
+        uploaded rows lie on the device for the call on top of that budget.  Returns (phases (nt, n_realize, ntriads, nchan) float64,
+        stats); stats['resident']: the resident cube was read."""
+        ix = NP.ascontiguousarray(bl_global, dtype=NP.int64).ravel()
+        nrow = ix.size
+        if cube is None:
+            if nt is None or cube_row is None:
+                raise ValueError('nt and cube_row are required with resident input')
+            x, nchan, nt = None, self.nchan, int(nt)
+            cr = NP.ascontiguousarray(cube_row, dtype=NP.int32).ravel()
+            if cr.size != nrow:
+                raise ValueError('cube_row and bl_global must have one entry per used row')
+        else:
+            x = NP.ascontiguousarray(cube, dtype=NP.complex128)
+            if x.ndim != 3 or x.shape[1] != nrow:
+                raise ValueError('cube must be (nt, nrow, nchan) with one row per entry of bl_global')
+            nt, _, nchan = x.shape
+            cr = None
+        lg = NP.ascontiguousarray(legs, dtype=NP.int32).reshape(-1, 3)
+        cj = NP.ascontiguousarray(conj, dtype=NP.int32).reshape(-1, 3)
+        if cj.shape != lg.shape:
+            raise ValueError('legs and conj must both be (ntriads, 3)')
+        rm = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(rms, dtype=NP.float64), (nt, nrow, nchan)))
+        bw = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(bpwts, dtype=NP.float64), (nt, nrow, nchan)))
+        if kind not in CPREAL_KINDS:
+            raise ValueError("kind must be 'noisy' or 'noise'")
+        n_realize, ntriads = int(n_realize), lg.shape[0]
+        out = NP.empty((nt, max(n_realize, 0), ntriads, nchan), dtype=NP.float64)
+        st = self.PrisimCprealStats()
+        self._check(self._lib.prisim_closure_realizations(self._h, _ptr(x), _ptr(cr), _ptr(ix), nt, nrow, nchan, _ptr(rm), _ptr(bw), _ptr(lg),
+                                                          _ptr(cj), ntriads, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), n_realize,
+                                                          CPREAL_KINDS[kind], _route_code(route, CPREAL_ROUTES), int(budget_bytes),
+                                                          _ptr(out), C.byref(st)), 'prisim_closure_realizations')
+        return out, dict(_stats_dict(st, route=CPREAL_ROUTES), resident=x is None)
 
     # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
     def closure_delay_spectra(self, wts, m, df, phases=None, cube=None, legs=None, conj=None, bpwts=None, freq_wts=None, masks=None,

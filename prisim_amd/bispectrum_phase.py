@@ -6,7 +6,9 @@ residuals, of the sub-model and of the half differences on the GPU (include/pris
 subset, compute_power_spectrum, compute_power_spectrum_uncertainty and beam3Dvol: the cross products of those spectra over pairs of LST
 bins, day bins and triads and their collapses on the GPU (include/prisim_cpxps.h, prisim_amd/csrc_closure/cpxps.hip); and the
 module-level incoherent_cross_power_spectrum_average and incoherent_kbin_averaging: the weighted averages of those power spectra over
-data sets, diagonals and bins of |k_parallel| on the GPU (include/prisim_cpavg.h, prisim_amd/csrc_closure/cpavg.hip).
+data sets, diagonals and bins of |k_parallel| on the GPU (include/prisim_cpavg.h, prisim_amd/csrc_closure/cpavg.hip).  In front of all
+that, simulate_closure_phases and triads_of_bltriplet: the model stack of write_PRISim_bispectrum_phase_to_npz, closure phases of noise
+realisations of a simulated array drawn and closed on the GPU (include/prisim_cpreal.h, prisim_amd/csrc_closure/cpreal.hip).
 
 Readings and departures
 - astropy is not a dependency.  The reference uses astropy.time.Time only to carry Julian dates, so loadnpz does that arithmetic
@@ -38,6 +40,13 @@ Readings and departures
 - subtract is host numpy, like expicp: it is elementwise on arrays the host already holds.  Under the masks of 'residual' (the mask of
   prelim or of the model; NaN in the model is masked) the data are 0.
 - infmt='hdf5' and save() are not implemented.
+- write_PRISim_bispectrum_phase_to_npz (:40-249) reads files of noisy cubes that replicatesim_util.py wrote.  Here
+  simulate_closure_phases takes the InterferometerArray itself and has the realisations drawn and closed on the GPU
+  (include/prisim_cpreal.h), n_realize of them under the keys seed + r, with the rms divided by sqrt(n_avg): the draws are the
+  counter-based ones of generate_noise, not numpy's RandomState, so the stack is the reference's in distribution and not in value.  It
+  returns loadnpz's dictionary per key and writes the reference's NPZ files only when a prefix is given; the file-prefix and HDF5 front
+  end (:137-176) is not implemented.  The selection of triads by a baseline triplet (:178-209) is triads_of_bltriplet; LKP.find_NN,
+  which is not in the tree, is read as: the legs within a Euclidean distance of blltol.
 
 Readings and departures of ClosurePhaseDelaySpectrum.FT (:2573-2784).  Every error is raised before any device work.
 - visscaleinfo=None ends the reference in an AttributeError (visscale = 1.0 is a float and :2732 calls .filled); here the scale is 1.
@@ -155,7 +164,12 @@ def loadnpz(npzfile, longitude=0.0, latitude=0.0, lst_format='fracday'):
     for key in ('averaged_closures', 'std_dev_triad', 'std_dev_lst'):
         if key in names:
             raise NotImplementedError('{0} in the NPZ file is not supported (the reference fails on it)'.format(key))
-    days = npzdata['days'].astype(NP.float64)
+    return _cpinfo_of(npzdata, lst_format)
+
+
+def _cpinfo_of(npzdata, lst_format='fracday'):
+    """loadnpz's dictionary from the five arrays of the file ('closures', 'triads', 'flags', 'last', 'days'), given as a mapping."""
+    days = NP.asarray(npzdata['days']).astype(NP.float64)
     if lst_format.lower() == 'hourangle':
         lst = npzdata['last']
         lstday = days.reshape(1, -1) + NP.zeros(lst.shape[0]).reshape(-1, 1)
@@ -167,6 +181,104 @@ def loadnpz(npzfile, longitude=0.0, latitude=0.0, lst_format='fracday'):
         raise ValueError('Input lst_format invalid')
     return {'raw': {'cphase': npzdata['closures'].astype(NP.float64), 'triads': NP.copy(npzdata['triads']),
                     'flags': npzdata['flags'].astype(bool), 'lst': NP.copy(lst), 'lst-day': NP.copy(lstday), 'days': NP.copy(days)}}
+
+
+def triads_of_bltriplet(simvis, bltriplet, blltol=0.1):
+    """The antenna triads of a simulated array whose three baseline vectors are those of bltriplet (3, 3) (legs by ENU metres): the
+    selection of write_PRISim_bispectrum_phase_to_npz (:178-209).  The triads are those of simvis.getThreePointCombinations(
+    unique=False); leg l of a triad matches row l of bltriplet when some leg of that triad lies within blltol metres of the row
+    (LKP.find_NN is not in the tree: it is read as Euclidean distance <= blltol); the rows that match no leg of any triad are
+    reversed in sign and all rows searched again, and a triad is selected when every row found one of its legs.  The reference's two
+    ValueErrors are kept.  Returns (triads (n, 3) array of antenna labels, their baseline vectors (n, 3, 3)), in the order of
+    getThreePointCombinations."""
+    if not isinstance(bltriplet, NP.ndarray):
+        raise TypeError('Input bltriplet must be a numpy array')
+    if isinstance(blltol, bool) or not isinstance(blltol, (int, float)):
+        raise TypeError('Input blltol must be a scalar')
+    if bltriplet.ndim != 2:
+        raise ValueError('Input bltriplet must be a 2D numpy array')
+    if bltriplet.shape[0] != 3:
+        raise ValueError('Input bltriplet must contain three baseline vectors')
+    if bltriplet.shape[1] != 3:
+        raise ValueError('Input bltriplet must contain baseline vectors along three corrdinates in the ENU frame')
+    triads, bltriplets = simvis.getThreePointCombinations(unique=False)
+    triads = NP.asarray(triads).reshape(-1, 3)
+    bltriplets = NP.asarray(bltriplets, dtype=NP.float64).reshape(-1, 3, 3)
+    flat = bltriplets.reshape(-1, 3)
+
+    def find(rows):                                                        # per row: the flat indices of the legs within blltol
+        return [NP.nonzero(NP.sqrt(NP.sum((flat - row) ** 2, axis=1)) <= blltol)[0] for row in rows]
+    match = find(bltriplet)
+    revind = [i for i in range(3) if match[i].size == 0]
+    if revind:                                                             # :191-198
+        flip = NP.ones(3)
+        flip[revind] = -1.0
+        match = find(bltriplet * flip.reshape(-1, 1))
+        if any(m.size == 0 for m in match):
+            raise ValueError('Some baselines in the triplet are not found in the model triads')
+    triadinds = [NP.unravel_index(m, bltriplets.shape[:2])[0] for m in match]
+    both = NP.intersect1d(triadinds[0], NP.intersect1d(triadinds[1], triadinds[2]))
+    if both.size == 0:
+        raise ValueError('Specified triad not found in the PRISim model. Try other permutations of the baseline vectors and/or reverse '
+                         'individual baseline vectors in the triad before giving up.')
+    return triads[both, :], bltriplets[both, :, :]
+
+
+def simulate_closure_phases(simvis, n_realize, seed, triads=None, bltriplet=None, blltol=0.1, datakey='noisy', n_avg=1, outfile_prefix=None):
+    """Closure phases of n_realize noise realisations of a simulated array in the form loadnpz reads: the body of
+    write_PRISim_bispectrum_phase_to_npz (:211-249) for an InterferometerArray that is at hand, with the realisations of
+    scriptUtils/replicatesim_util.py:replicate (:82-95) drawn and closed on the GPU (InterferometerArray.closure_phase_realizations)
+    in place of its file of noisy cubes.
+
+    triads       list or array (ntriads, 3) of antenna labels; None: triads_of_bltriplet(simvis, bltriplet, blltol)
+    datakey      'noiseless', 'noisy' (default), 'noise' or a list of them.  'noiseless' is one getClosurePhase call, repeated along
+                 the realisation axis, as the reference repeats it
+    seed, n_avg  realisation r is generate_noise(seed=seed + r) with the rms divided by sqrt(n_avg)
+    Returns {key: {'raw': {'cphase' (nt, n_realize, ntriads, nchan) float64, 'triads' (ntriads, 3), 'flags' all False, 'lst' hours,
+    'lst-day', 'days'}}}: per key what loadnpz gives for the reference's file, so that ClosurePhase(result['noisy'], freqs) works
+    directly.  'last' = lst / 15 / 24 broadcast to (nt, n_realize) and 'days' = timestamp[0] + arange(n_realize), as in the reference.
+    With outfile_prefix, <prefix>_<key>.npz is written too, with the reference's five arrays ('closures', 'flags', 'triads', 'last',
+    'days'); loadnpz reads it back to the same dictionary."""
+    if (triads is None) and (bltriplet is None):
+        raise ValueError('One of triads or bltriplet must be set')
+    if outfile_prefix is not None and not isinstance(outfile_prefix, str):
+        raise TypeError('Input outfile_prefix must be a string')
+    if isinstance(datakey, str):
+        datakey = [datakey]
+    elif not isinstance(datakey, list):
+        raise TypeError('Input datakey must be a list')
+    datakey = [k.lower() for k in datakey]
+    for dkey in datakey:
+        if dkey not in ['noiseless', 'noisy', 'noise']:
+            raise ValueError('Invalid input found in datakey')
+    if isinstance(n_realize, bool) or not isinstance(n_realize, (int, NP.integer)):
+        raise TypeError('n_realize must be an integer')
+    if n_realize < 1:
+        raise ValueError('n_realize must be at least 1')
+    if triads is None:
+        triads, _ = triads_of_bltriplet(simvis, bltriplet, blltol)
+    elif not isinstance(triads, (list, NP.ndarray)):
+        raise TypeError('Input triads must be a list or numpy array')
+    triads = NP.asarray(triads).astype(str).reshape(-1, 3)
+    triplets = [tuple(t) for t in triads.tolist()]
+    last = (NP.asarray(simvis.lst, dtype=NP.float64) / 15.0 / 24.0).reshape(-1, 1) + NP.zeros((1, n_realize))     # :156-157, :248
+    days = NP.asarray(simvis.timestamp[0]).ravel() + NP.arange(n_realize)                                        # :158, :249
+    cpdata = {}
+    drawn = [k for k in datakey if k != 'noiseless']
+    if drawn:
+        res = simvis.closure_phase_realizations(n_realize, seed, antenna_triplets=triplets, datakey=drawn, n_avg=n_avg)
+        for k in drawn:
+            cpdata[k] = res['closure_phase_vis' if k == 'noisy' else 'closure_phase_noise']
+    if 'noiseless' in datakey:
+        sky = simvis.getClosurePhase(antenna_triplets=triplets)['closure_phase_skyvis']                          # (ntriads, nchan, nt)
+        cpdata['noiseless'] = NP.repeat(NP.transpose(sky, (2, 0, 1))[:, NP.newaxis, :, :], n_realize, axis=1)
+    out = {}
+    for k in datakey:
+        arrays = {'closures': cpdata[k], 'flags': NP.zeros(cpdata[k].shape, dtype=bool), 'triads': triads, 'last': last, 'days': days}
+        if outfile_prefix is not None:
+            NP.savez_compressed(outfile_prefix + '_{0}.npz'.format(k), **arrays)
+        out[k] = _cpinfo_of(arrays)
+    return out
 
 
 def binned_count(x, edges):

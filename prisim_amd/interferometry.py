@@ -1746,11 +1746,9 @@ class InterferometerArray(object):
         self.n_acc = n_acc
 
     # ------------------------------------------------------------------------------------------
-    def generate_noise(self, seed=None, bl_offset=0, bl_index=None):
-        """Thermal noise for every (baseline, channel, snapshot) from the system parameters (interferometry.py:6661-6693):
-        vis_rms_freq = 2 k / sqrt(t_acc df) * Tsys / (A_eff eff_Q) / Jy (flux_unit 'JY') or Tsys / eff_Q / sqrt(t_acc df) ('K');
-        vis_noise_freq = vis_rms_freq / sqrt(2) * (randn + 1j randn).  The normals are drawn on the GPU (counter-based Philox),
-        reproducibly for a given `seed` (None: a fresh random seed, like the reference's global numpy RNG)."""
+    def _thermal_rms(self):
+        """vis_rms_freq from the system parameters (interferometry.py:6661-6687), broadcastable to (nbl, nchan, nt): the statement of
+        generate_noise, also read by closure_phase_realizations.  No attribute is changed."""
         if not self.timestamp:
             raise ValueError('no snapshots: call observe() first')
         eff_Q = self.eff_Q if self.eff_Q.ndim == 3 else self.eff_Q[:, :, NP.newaxis]
@@ -1758,11 +1756,17 @@ class InterferometerArray(object):
         t_acc = NP.asarray(self.t_acc, dtype=NP.float64)[NP.newaxis, NP.newaxis, :]
         Tsys = self.Tsys if self.Tsys.ndim == 3 else self.Tsys[:, :, NP.newaxis]
         if self.flux_unit in ('JY', 'jy', 'Jy'):
-            self.vis_rms_freq = 2.0 * 1.380649e-23 / NP.sqrt(t_acc * self.freq_resolution) * (Tsys / A_eff / eff_Q) / 1.0e-26   # :6685
-        elif self.flux_unit in ('K', 'k'):
-            self.vis_rms_freq = 1.0 / NP.sqrt(t_acc * self.freq_resolution) * Tsys / eff_Q                                  # :6687
-        else:
-            raise ValueError('Flux density units can only be in Jy or K.')
+            return 2.0 * 1.380649e-23 / NP.sqrt(t_acc * self.freq_resolution) * (Tsys / A_eff / eff_Q) / 1.0e-26   # :6685
+        if self.flux_unit in ('K', 'k'):
+            return 1.0 / NP.sqrt(t_acc * self.freq_resolution) * Tsys / eff_Q                                  # :6687
+        raise ValueError('Flux density units can only be in Jy or K.')
+
+    def generate_noise(self, seed=None, bl_offset=0, bl_index=None):
+        """Thermal noise for every (baseline, channel, snapshot) from the system parameters (interferometry.py:6661-6693):
+        vis_rms_freq = 2 k / sqrt(t_acc df) * Tsys / (A_eff eff_Q) / Jy (flux_unit 'JY') or Tsys / eff_Q / sqrt(t_acc df) ('K');
+        vis_noise_freq = vis_rms_freq / sqrt(2) * (randn + 1j randn).  The normals are drawn on the GPU (counter-based Philox),
+        reproducibly for a given `seed` (None: a fresh random seed, like the reference's global numpy RNG)."""
+        self.vis_rms_freq = self._thermal_rms()
         if seed is None:
             seed = int(NP.random.SeedSequence().generate_state(2, dtype=NP.uint32).astype(NP.uint64) @ NP.array([1, 1 << 32], dtype=NP.uint64))
         rms_tbf = NP.ascontiguousarray(NP.transpose(NP.broadcast_to(self.vis_rms_freq, (self.baselines.shape[0], self.channels.size,
@@ -2429,6 +2433,74 @@ class InterferometerArray(object):
             out[key], out['closure_phase_' + name] = trip, phase
             self.closure_stats[key] = stats
         out.update({'antenna_triplets': antenna_triplets, 'baseline_triplets': blvecttriplets, 'spectral_weights': freq_wts})
+        return out
+
+    def closure_phase_realizations(self, n_realize, seed, antenna_triplets=None, unique=False, datakey='noisy', n_avg=1, first=0,
+                                   bl_index=None, route='auto', budget_bytes=None):
+        """Closure phases of n_realize thermal-noise realisations of this noiseless run on triads of antennas, drawn and closed on
+        the GPU (include/prisim_cpreal.h): the realisations of prisim/scriptUtils/replicatesim_util.py:replicate (:82-95) and their
+        closure phases as prisim/bispectrum_phase.py:write_PRISim_bispectrum_phase_to_npz stacks them (:211-249).
+
+        Realisation r is by definition what generate_noise(seed=seed + first + r, bl_index=bl_index); add_noise();
+        getClosurePhase(antenna_triplets) gives in 'closure_phase_vis' ('noisy') and 'closure_phase_noise' ('noise'), bit for bit,
+        with the rms divided by sqrt(n_avg) (replicate :90): the draws are keyed on (channel, global baseline, snapshot) and that seed.
+        No noise cube is formed and nothing but the baselines of the triads is drawn or copied; vis_freq, vis_noise_freq and
+        vis_rms_freq are left as they are.
+
+        n_realize          number of realisations, >= 1
+        seed, first        realisation r uses the key seed + first + r (mod 2^64)
+        antenna_triplets   list of antenna-label triplets; None: getThreePointCombinations(unique=unique)
+        datakey            'noisy', 'noise' or a list of them
+        n_avg              averages per realisation: the rms is divided by sqrt(n_avg)
+        bl_index           global index of every baseline of this array inside the whole array of a sharded run (None: its own rows)
+        route              'auto', 'direct' or 'staged' (include/prisim_cpreal.h); budget_bytes: device bytes of the chunk buffers
+
+        Returns {'closure_phase_vis' and / or 'closure_phase_noise': (nt, n_realize, ntriads, nchan) radians, 'antenna_triplets',
+        'baseline_triplets', 'seeds': (n_realize,) uint64} and leaves the stats of the device calls in cpreal_stats, per datakey.  The
+        noiseless cube is read where it lies on the device when the device slots are in step with skyvis_freq; otherwise the used rows
+        of skyvis_freq are handed over.  A gaininfo raises NotImplementedError: gains are not part of the fused route.  There is no
+        CPU path."""
+        if isinstance(n_realize, bool) or not isinstance(n_realize, (int, NP.integer)):
+            raise TypeError('n_realize must be an integer')
+        if n_realize < 1:
+            raise ValueError('n_realize must be at least 1')
+        if not (n_avg > 0):
+            raise ValueError('n_avg must be positive')
+        keys = [datakey] if isinstance(datakey, str) else datakey
+        if not isinstance(keys, list) or not keys:
+            raise TypeError('datakey must be a string or a list of strings')
+        for k in keys:
+            if k not in ('noisy', 'noise'):
+                raise ValueError("datakey can only hold 'noisy' and 'noise'")
+        if self.gaininfo is not None:
+            raise NotImplementedError('closure_phase_realizations does not apply gains: use generate_noise, add_noise and getClosurePhase')
+        p = _closure_prepare(self, antenna_triplets, None, None, None, unique)
+        legs, nbl, nchan, nt = p['legs'], p['nbl'], p['nchan'], p['nt']
+        seeds = ((int(seed) + int(first) + NP.arange(n_realize, dtype=object)) % (1 << 64)).astype(NP.uint64)
+        out = {'antenna_triplets': p['antenna_triplets'], 'baseline_triplets': p['baseline_triplets'], 'seeds': seeds}
+        self.cpreal_stats = {}
+        names = {'noisy': 'closure_phase_vis', 'noise': 'closure_phase_noise'}
+        if not legs.shape[0]:
+            for k in keys:
+                out[names[k]] = NP.zeros((nt, n_realize, 0, nchan))
+            return out
+        used, inv = NP.unique(legs, return_inverse=True)                 # the distinct rows of the legs, and the legs as rows of those
+        legs_used = NP.asarray(inv, dtype=NP.int32).reshape(legs.shape)
+        if bl_index is not None and NP.asarray(bl_index).size != nbl:
+            raise ValueError('bl_index must have one entry per baseline')
+        glob = used if bl_index is None else NP.asarray(bl_index, dtype=NP.int64).ravel()[used]
+
+        def rows_tbf(a):                                                 # (nbl | 1, nchan | 1, nt | 1) -> the used rows as (nt, nrow, nchan)
+            a = NP.broadcast_to(a, (nbl, nchan, nt))[used]
+            return NP.ascontiguousarray(NP.transpose(a, (2, 0, 1)))
+        rms = rows_tbf(self._thermal_rms() / NP.sqrt(float(n_avg)))
+        bpwts = rows_tbf(p['bpwts'])
+        cube = None if p['resident'] else rows_tbf(NP.asarray(self.skyvis_freq, dtype=NP.complex128))
+        kw = {} if budget_bytes is None else {'budget_bytes': budget_bytes}
+        for k in keys:
+            out[names[k]], self.cpreal_stats[k] = self._ctx.closure_realizations(
+                cube, used if cube is None else None, glob, rms, bpwts, legs_used, p['conj'], seed, n_realize, first=first, kind=k, nt=nt,
+                route=route, **kw)
         return out
 
     # ------------------------------------------------------------------------------------------
