@@ -105,6 +105,8 @@ CPREAL_EXPORTS = ('prisim_closure_realizations',)
 PRISIM_CPREAL_AUTO, PRISIM_CPREAL_DIRECT, PRISIM_CPREAL_STAGED = -1, 0, 1
 CPREAL_ROUTES = {PRISIM_CPREAL_DIRECT: 'direct', PRISIM_CPREAL_STAGED: 'staged'}
 CPREAL_KINDS = {'noisy': 0, 'noise': 1}
+# every symbol include/prisim_antpower.h declares: beam-weighted sky power per snapshot (prisim_amd/csrc_antpower/antpower.hip)
+ANTPOWER_EXPORTS = ('prisim_antenna_power',)
 
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
@@ -291,6 +293,24 @@ class _PrisimCprealStats(C.Structure):
     _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('pairs', C.c_int64), ('chunks', C.c_int64),
                 ('chunk_pairs', C.c_int64), ('draws', C.c_int64), ('kernel_bytes', C.c_int64), ('download_bytes', C.c_int64),
                 ('route', C.c_int32), ('streams', C.c_int32), ('chan_tile', C.c_int32), ('lds_bytes', C.c_int32)]
+
+
+class _PrisimAntpowerStats(C.Structure):
+    """prisim_antpower_stats of include/prisim_antpower.h, public as Context.PrisimAntpowerStats (see _PrisimCpxpsStats);
+    tests/test_antpower.py holds it to the header."""
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('sources_evaluated', C.c_int64), ('sources_up', C.c_int64),
+                ('spans', C.c_int64), ('span_sources', C.c_int64), ('block_sources', C.c_int64), ('kernel_bytes', C.c_int64),
+                ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('streams', C.c_int32), ('chan_tile', C.c_int32),
+                ('lds_bytes', C.c_int32), ('reserved_', C.c_int32)]
+
+
+class _PrisimAntpowerArgs(C.Structure):
+    """prisim_antpower_args of include/prisim_antpower.h, public as Context.PrisimAntpowerArgs."""
+    _fields_ = [('nsrc', C.c_int64), ('nchan', C.c_int64), ('nsnap', C.c_int64), ('unitvec', C.c_void_p), ('flux_ref', C.c_void_p),
+                ('spindex', C.c_void_p), ('ref_freq_hz', C.c_double), ('flux_spectrum', C.c_void_p), ('freqs_hz', C.c_void_p),
+                ('cel2enu', C.c_void_p), ('aberr_beta', C.c_void_p), ('beam_kind', C.c_int32), ('reserved_', C.c_int32),
+                ('diameter_m', C.c_double), ('beam_pc_dircos', C.c_double * 3), ('ext', C.c_void_p), ('n_ext', C.c_int64),
+                ('budget_bytes', C.c_int64)]
 
 
 def numpy_fuses_complex_product(dtype):
@@ -487,6 +507,8 @@ def load_library():
     lib.prisim_closure_realizations.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, i64, C.c_uint64, i64, i64, C.c_int32, C.c_int32,
                                                 i64, vp, C.POINTER(_PrisimCprealStats)]
     lib.prisim_closure_realizations.restype = C.c_int
+    lib.prisim_antenna_power.argtypes = [vp, C.POINTER(_PrisimAntpowerArgs), vp, vp, vp, C.POINTER(_PrisimAntpowerStats)]
+    lib.prisim_antenna_power.restype = C.c_int
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
                                              C.POINTER(vp), pst]
@@ -1233,6 +1255,67 @@ class Context(object):
                                                           CPREAL_KINDS[kind], _route_code(route, CPREAL_ROUTES), int(budget_bytes),
                                                           _ptr(out), C.byref(st)), 'prisim_closure_realizations')
         return out, dict(_stats_dict(st, route=CPREAL_ROUTES), resident=x is None)
+
+    # ---- beam-weighted sky power per snapshot (include/prisim_antpower.h) ----
+    PrisimAntpowerStats = _PrisimAntpowerStats
+    PrisimAntpowerArgs = _PrisimAntpowerArgs
+
+    def antenna_power(self, unitvec, freqs_hz, cel2enu, beam_kind, diameter_m, beam_pc_dircos=(0.0, 0.0, 1.0), flux_ref=None, spindex=None,
+                      ref_freq_hz=None, flux_spectrum=None, aberr_beta=None, ext=None, budget_bytes=0, want_sums=True):
+        """The power an antenna receives from the sky, sum_s pb S / sum_s pb over the sources above the horizon, per snapshot and
+        channel on the device (prisim_antenna_power).  unitvec: (nsrc, 3) unit vectors in the catalogue's frame
+        (geometry.catalog_unitvec); freqs_hz: (nchan,); cel2enu: (nsnap, 3, 3) rotations catalogue frame -> East-North-Up and
+        aberr_beta: (nsnap, 3) or None, as prisim_amd.frames.snapshot_frame gives them.  The flux is the power law flux_ref (f /
+        ref_freq_hz)^spindex, evaluated on the device, or the table flux_spectrum (nsrc, nchan).  The beam is that of set_sky_analytic:
+        beam_kind, diameter_m, beam_pc_dircos and ext, a dict (make_beam_ext), None, or a sequence of one dict per snapshot.
+        budget_bytes: device bytes of the streamed buffers (0: 1 GiB); the result does not depend on it.  Returns (power, num, den,
+        stats), each array (nsnap, nchan) float64; num and den are None without want_sums.  A snapshot with nothing above the horizon
+        is NaN in power."""
+        uv = NP.ascontiguousarray(unitvec, dtype=NP.float64).reshape(-1, 3)
+        fq = NP.ascontiguousarray(freqs_hz, dtype=NP.float64).ravel()
+        rot = NP.ascontiguousarray(cel2enu, dtype=NP.float64).reshape(-1, 9)
+        nsrc, nchan, nsnap = uv.shape[0], fq.size, rot.shape[0]
+        ab = None
+        if aberr_beta is not None:
+            ab = NP.ascontiguousarray(aberr_beta, dtype=NP.float64).reshape(-1, 3)
+            if ab.shape[0] != nsnap:
+                raise ValueError('aberr_beta must have one row per snapshot')
+        fs = fr = sp = None
+        if flux_spectrum is not None:
+            fs = NP.ascontiguousarray(flux_spectrum, dtype=NP.float64)
+            if fs.shape != (nsrc, nchan):
+                raise ValueError('flux_spectrum must have shape (nsrc, nchan)')
+        elif flux_ref is not None and spindex is not None:
+            fr = NP.ascontiguousarray(flux_ref, dtype=NP.float64).ravel()
+            sp = NP.ascontiguousarray(spindex, dtype=NP.float64).ravel()
+            if fr.size != nsrc or sp.size != nsrc:
+                raise ValueError('flux_ref and spindex must have nsrc elements')
+        exts = [] if ext is None else ([ext] if isinstance(ext, dict) else list(ext))
+        xs = (PrisimBeamExt * max(len(exts), 1))()
+        keep = []
+        for i, e in enumerate(exts):
+            x = make_beam_ext(e)
+            keep.append(x)
+            C.memmove(C.byref(xs, i * C.sizeof(PrisimBeamExt)), C.byref(x), C.sizeof(PrisimBeamExt))
+        a = self.PrisimAntpowerArgs()
+        a.nsrc, a.nchan, a.nsnap = nsrc, nchan, nsnap
+        a.unitvec, a.flux_ref, a.spindex, a.flux_spectrum = _ptr(uv), _ptr(fr), _ptr(sp), _ptr(fs)
+        a.ref_freq_hz = 0.0 if ref_freq_hz is None else float(ref_freq_hz)
+        a.freqs_hz, a.cel2enu, a.aberr_beta = _ptr(fq), _ptr(rot), _ptr(ab)
+        a.beam_kind, a.diameter_m = int(beam_kind), float(diameter_m)
+        bpc = NP.asarray(beam_pc_dircos, dtype=NP.float64).ravel()
+        if bpc.size != 3:
+            raise ValueError('beam_pc_dircos must have 3 elements')
+        a.beam_pc_dircos[:] = bpc.tolist()
+        a.ext = C.cast(xs, C.c_void_p) if exts else None
+        a.n_ext = len(exts)
+        a.budget_bytes = int(budget_bytes or 0)
+        power = NP.empty((nsnap, nchan), dtype=NP.float64)
+        num = NP.empty((nsnap, nchan), dtype=NP.float64) if want_sums else None
+        den = NP.empty((nsnap, nchan), dtype=NP.float64) if want_sums else None
+        st = self.PrisimAntpowerStats()
+        self._check(self._lib.prisim_antenna_power(self._h, C.byref(a), _ptr(power), _ptr(num), _ptr(den), C.byref(st)), 'prisim_antenna_power')
+        return power, num, den, _stats_dict(st)
 
     # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
     def closure_delay_spectra(self, wts, m, df, phases=None, cube=None, legs=None, conj=None, bpwts=None, freq_wts=None, masks=None,

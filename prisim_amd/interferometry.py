@@ -447,6 +447,151 @@ def closure_filter_masks(fft_delays, filter_type, filter_mode, delay_min, delay_
     return NP.where(rows, 0.0, 1.0), NP.asarray(mask_index, dtype=NP.int32).ravel()
 
 
+def _same_beam_spec(a, b):
+    """Whether two values of primary_beams.device_beam_spec (nested tuples and dicts of scalars and arrays) are equal."""
+    if isinstance(a, dict) or isinstance(b, dict):
+        return (isinstance(a, dict) and isinstance(b, dict) and sorted(a) == sorted(b)
+                and all(_same_beam_spec(a[k], b[k]) for k in a))
+    if isinstance(a, (tuple, list)) or isinstance(b, (tuple, list)):
+        return (isinstance(a, (tuple, list)) and isinstance(b, (tuple, list)) and len(a) == len(b)
+                and all(_same_beam_spec(x, y) for x, y in zip(a, b)))
+    if a is None or b is None:
+        return a is None and b is None
+    return NP.array_equal(NP.asarray(a), NP.asarray(b))
+
+
+def _antenna_power_pointings(pointing_info, lst, latitude):
+    """The pointing centres of antenna_power as (n_lst, 2) alt-az degrees, with the reference's checks (interferometry.py:2332-2369)."""
+    n_lst = lst.size
+    if 'pointing_center' not in pointing_info:
+        return NP.repeat(NP.asarray([90.0, 270.0]).reshape(1, -1), n_lst, axis=0)
+    if 'pointing_coords' not in pointing_info:
+        raise KeyError('key "pointing_coords" not found in input parameter pointing_info')
+    pointing_coords = pointing_info['pointing_coords']
+    if not isinstance(pointing_info['pointing_center'], NP.ndarray):
+        raise TypeError('Value in key "pointing_center" in input parameter pointing_info must be a numpy array')
+    pointing_center = pointing_info['pointing_center']
+    if pointing_center.ndim > 2:
+        raise ValueError('Value under key "pointing_center" in input parameter pointing_info cannot exceed two dimensions')
+    if pointing_center.ndim < 2:
+        pointing_center = pointing_center.reshape(1, -1)
+    if pointing_coords == 'dircos':
+        if pointing_center.shape[1] != 3:
+            raise ValueError('Value under key "pointing_center" in input parameter pointing_info must be a 3-column array for direction '
+                             'cosine coordinate system')
+    elif pointing_center.shape[1] != 2:
+        raise ValueError('Value under key "pointing_center" in input parameter pointing_info must be a 2-column array for RA-Dec, HA-Dec '
+                         'and Alt-Az coordinate systems')
+    n_pointings = pointing_center.shape[0]
+    if (n_pointings != n_lst) and (n_pointings != 1):
+        raise ValueError('Number of pointing centers and number of LST must match')
+    if n_pointings < n_lst:
+        pointing_center = NP.repeat(pointing_center, n_lst, axis=0)
+    pointing_center = NP.asarray(pointing_center, dtype=NP.float64)
+    if pointing_coords == 'dircos':
+        return GEOM.dircos2altaz(pointing_center, units='degrees')
+    if pointing_coords == 'hadec':
+        return GEOM.hadec2altaz(pointing_center, latitude, units='degrees')
+    if pointing_coords == 'radec':
+        return GEOM.hadec2altaz(NP.stack((lst - pointing_center[:, 0], pointing_center[:, 1]), axis=1), latitude, units='degrees')
+    return NP.copy(pointing_center)
+
+
+def antenna_power(skymodel, telescope_info, pointing_info, freq_scale=None, frequency=None, coords=None, frames=None, device=0,
+                  budget_bytes=None, stats=None):
+    """Antenna power received from the sky for a sky model, a telescope and pointings: for every LST and channel
+    sum_s pb(s, f) S_s(f) / sum_s pb(s, f) over the sources above the horizon (alt >= 0), the reference's antenna_power
+    (prisim/interferometry.py:2169-2408), with its signature, argument meaning and exceptions.  With a diffuse model in kelvin this is
+    the antenna temperature, with point sources the beam-weighted flux.  The rotation into the local frame, the beam and both sums run
+    on the device (include/prisim_antpower.h); only the (n_lst, nchan) result comes back.
+
+    skymodel        a SkyModel.  A 'spectrum' model is used on its own grid: skymodel.frequency is the channel axis, as in the reference.
+                    A 'func' (power-law) model has no grid here and needs frequency=; its ref_freq is in the units of that axis, and the
+                    power law is evaluated on the device.
+    telescope_info  the reference's dictionary: 'latitude' (default -26.701), 'id' or 'shape' / 'size' / 'orientation' / 'ocoords',
+                    'element_locs', 'groundplane', 'ground_modify' (prisim_amd.primary_beams.device_beam_spec; rect / square apertures
+                    raise its NotImplementedError).
+    pointing_info   'lst' (degrees, one per pointing); optionally 'pointing_center' with 'pointing_coords' ('radec', 'hadec', 'altaz':
+                    M x 2; 'dircos': M x 3; M = n_lst, or 1 for all; default alt-az [90, 270]).  As in the reference (:2392-2400) the
+                    pointing reaches the beam only as the pointing_info of a phased array's beamformer; dishes and Gaussians point
+                    where telescope_info says, the zenith by default.
+    freq_scale      units of the frequencies: 'GHz', 'MHz', 'kHz' or 'Hz'; None is Hz (how primary_beams.py:212-217 reads it).
+    coords          frame of skymodel.location: 'radec', 'hadec', 'altaz' or 'dircos'; default skymodel.coords, else 'radec'.
+    frames          one (cel2enu (3, 3), aberr_beta (3,)) per LST, as prisim_amd.frames.snapshot_frame returns.  The default for
+                    'radec' is the plain hour-angle rotation HA = LST - RA, which is what the reference computes (:2372-2379) and right
+                    for coordinates of date; frames= gives the true place of a catalogue of another epoch (precession, nutation and
+                    aberration, some degrees over decades for a narrow beam).
+    device, budget_bytes, stats    the GPU, the device bytes of the streamed buffers, and a dict that receives the entry's statistics.
+
+    Returns (n_lst, nchan) float64.  A pointing with no source above the horizon is a row of NaN.
+
+    Departures from the reference: no progress bar; a 'dircos' pointing is accepted (the reference's elif at :2350 rejects every
+    3-column array); frequency=, coords=, frames=, device=, budget_bytes= and stats= are additions; NaN rows come back without a
+    numpy warning."""
+    if not hasattr(skymodel, 'location'):
+        raise TypeError('Input parameter skymodel must be an instance of class SkyModel')
+    if not isinstance(telescope_info, dict):
+        raise TypeError('Input parameter telescope_info must be a dictionary')
+    if not isinstance(pointing_info, dict):
+        raise TypeError('Input parameter pointing_info must be a dictionary')
+    latitude = telescope_info['latitude'] if 'latitude' in telescope_info else -26.701
+    if 'lst' not in pointing_info:
+        raise KeyError('Key "lst" not provided in input parameter pointing_info')
+    lst = NP.asarray(pointing_info['lst'], dtype=NP.float64).ravel()
+    n_lst = lst.size
+    pointings_altaz = _antenna_power_pointings(pointing_info, lst, latitude)
+
+    # channels and spectra
+    scale = {'ghz': 1.0e9, 'mhz': 1.0e6, 'khz': 1.0e3}.get(freq_scale.lower() if isinstance(freq_scale, str) else None, 1.0)
+    flux = {}
+    if getattr(skymodel, 'spec_type', 'func') == 'spectrum':
+        chans = NP.asarray(skymodel.frequency if frequency is None else frequency, dtype=NP.float64).ravel()
+        flux['flux_spectrum'] = skymodel.generate_spectrum(frequency=chans, interp_method='pchip')
+    else:
+        if frequency is None:
+            raise ValueError('a power-law sky model has no frequency grid: give frequency=')
+        chans = NP.asarray(frequency, dtype=NP.float64).ravel()
+        flux.update(flux_ref=skymodel.flux_ref, spindex=skymodel.spindex, ref_freq_hz=float(skymodel.ref_freq) * scale)
+    freqs_hz = chans * scale
+
+    # the sky in its own frame, and one rotation per LST
+    coords = coords or getattr(skymodel, 'coords', None) or 'radec'
+    if coords in ('radec', 'hadec', 'altaz'):
+        unitvec = GEOM.catalog_unitvec(skymodel.location, coords)
+    elif coords == 'dircos':
+        unitvec = NP.asarray(skymodel.location, dtype=NP.float64).reshape(-1, 3)
+    else:
+        raise ValueError('coords must be "radec", "hadec", "altaz" or "dircos"')
+    beta = None
+    if frames is not None:
+        frames = list(frames)
+        if len(frames) != n_lst:
+            raise ValueError('frames must hold one (cel2enu, aberr_beta) per LST')
+        rot = NP.stack([NP.asarray(f[0], dtype=NP.float64).reshape(3, 3) for f in frames])
+        beta = NP.stack([NP.asarray(f[1], dtype=NP.float64).reshape(3) for f in frames])
+    elif coords == 'radec':
+        rot = NP.stack([FRAMES.equatorial_to_enu(l, latitude) for l in lst])
+    elif coords == 'hadec':
+        rot = NP.repeat(FRAMES.hadec_to_enu(latitude)[NP.newaxis], n_lst, axis=0)
+    else:
+        rot = NP.repeat(NP.eye(3)[NP.newaxis], n_lst, axis=0)
+
+    # the beam of every LST: one shared description unless a beamformer's delays follow the pointing
+    specs = [PB.device_beam_spec(telescope_info, pointing_info={'pointing_center': pointings_altaz[i, :], 'pointing_coords': 'altaz'},
+                                 first_frequency_hz=float(freqs_hz[0])) for i in range(n_lst)]
+    kind, dia, bpc, ext0 = specs[0]
+    if all(_same_beam_spec(specs[0], sp) for sp in specs[1:]):
+        ext = ext0
+    else:
+        ext = [sp[3] for sp in specs]
+    with _abi.Context(device) as ctx:
+        power, _, _, st = ctx.antenna_power(unitvec, freqs_hz, rot, kind, dia, beam_pc_dircos=bpc, aberr_beta=beta, ext=ext,
+                                            budget_bytes=int(budget_bytes or 0), want_sums=False, **flux)
+    if stats is not None:
+        stats.update(st)
+    return power
+
+
 def _label_from_text(s):
     """A baseline label back from the text save() wrote for it (str(label), '/' written as '|' in dataset names): the tuple of
     strings that ast.literal_eval gives (interferometry.py:5394-5397), or, for a text that is no literal (numpy scalars inside the
