@@ -120,35 +120,12 @@ Plan make_plan(const prisim_ctx* ctx, int precision, int kernel) {
   // source split so that small problems still fill the GPU; each split is a multiple of the chunk
   int nsplit = ctx->tune_nsplit;
   if (nsplit == 0) {
-    const int64_t base = (int64_t)pl.ntiles * pl.nbgroups;
     // resident blocks per CU = waves per SIMD the kernels are built for (PK_WAVES / WavesPerEU in skyvis_kernels.hip)
     // (fp64: the 16 KiB phasor table + 36 KiB flush buffer + prefetch area = 56 KiB of LDS per block allow 2 blocks per CU)
     const int per_cu = pl.pk ? 2 : (pl.f32 ? 4 : 2);
     const int64_t slots = (int64_t)std::max(ctx->cu_count, 1) * per_cu;
-    // The grid runs in rounds of `slots` resident blocks.  Measured on 1/2, 1/4 and 1/8 baseline shards of config 3
-    // (tools/shard_nsplit_sweep.py, candidates alternating): the step time is lowest when the sources are split so that the grid
-    // is again about 7.5 rounds deep, like the unsplit full problem (nsplit = 2 / 4 / 8: 1.00 / 1.02 / 1.03 x the ideal T1/N
-    // against 1.03 / 1.06 / 1.10 x unsplit) -- blocks then start and finish out of step and the tail is short; every extra split
-    // costs partial-cube traffic, so much deeper grids lose again.  Problems that are already >= 6 rounds deep keep nsplit = 1
-    // (alternating A/B on the full config 3, tools/full_nsplit.py: 1 / 2 / 4 splits within 0.4 % of each other).
-    nsplit = 1;
-    int64_t want = 1;
-    if (base * 10 < slots * 60) want = (slots * 15 / 2 + base / 2) / base;       // round(7.5 * slots / base)
-    want = std::min<int64_t>(want, std::max<int64_t>(1, nsrc / 32));             // keep >= 32 sources per split
-    {
-      // ... and every split writes a partial cube that k_reduce_partials reads again: keep that traffic (~3 TB/s effective) under
-      // ~3 % of the sky-sum's own time, but never below one round of resident blocks.  One rank's share of config 4 at N = 8
-      // (1016 bl x 768 ch x 24 576 sources): 2.86 ms at 16 splits against 3.13 ms at the 64 the round rule alone asks for.
-      const double rate = pl.f32 ? (ctx->taper ? 7.0e12 : 1.0e13) : (ctx->taper ? 2.8e12 : 5.0e12);       // terms/s of the big kernels
-      const double t_compute = (double)nbl * (double)nchan * (double)nsrc / rate;
-      const double t_split = 2.0 * (double)nbl * (double)nchan * (pl.f32 ? 8.0 : 16.0) / 3.0e12;
-      const int64_t cap = std::max<int64_t>((slots + base - 1) / std::max<int64_t>(base, 1), (int64_t)(0.03 * t_compute / t_split));
-      // (splits up to 16 keep the measured round rule.)  Deeper ones: the sweep's optimum sits where the grid is ~1.5 rounds of
-      // resident blocks -- the second, half-empty round runs one block per CU, and a lone wave per SIMD issues packed FMAs at 3/4 of
-      // the full rate -- 2.53 ms at 16 splits against 3.28 at 19 and 2.75 at 10 or 24 on the config-4 share.
-      if (want > 16) want = std::max<int64_t>(16, std::min<int64_t>((3 * slots / 2 + base / 2) / std::max<int64_t>(base, 1), cap));
-    }
-    nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(want, 64));
+    // the grid runs in rounds of `slots` resident blocks: split_plan.h holds the rule and what it was measured on
+    nsplit = prisim::split_count(pl.ntiles, pl.nbgroups, slots, nsrc, nbl, nchan, pl.f32, ctx->taper);
   }
   if (!pl.f32 && ctx->taper && (ct == 16 || ct == 32) && pl.kernel == PRISIM_KERNEL_RECURRENCE && nbl <= kBlockThreads && !ctx->tune_chunk &&
       taper_f64_grouped_enabled()) {
@@ -234,6 +211,22 @@ int prisim_hip_create(int device, prisim_ctx** out) {
   // the catalogue path's two priority streams and their events belong to the context too (5 ms to create: not in front of a run's first
   // snapshot); a failure here is not fatal -- the path tries again when it is first used and reports it then
   if (catalog_streams(ctx) != PRISIM_OK) { ctx->err.clear(); (void)hipGetLastError(); }
+  // the post stream of the deferred reduce / expand pass (ctx_internal.h): non-blocking and of the highest priority, as the side streams
+  // above -- two short memory passes that must be scheduled beside a sky-sum grid occupying every CU.  Not fatal either: without it
+  // every compute() keeps the single-stream order.
+  {
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { least = greatest = 0; (void)hipGetLastError(); }
+    bool ok = hipStreamCreateWithPriority(&ctx->post_stream, hipStreamNonBlocking, greatest) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); ctx->post_stream = nullptr; ok = hipStreamCreateWithFlags(&ctx->post_stream, hipStreamNonBlocking) == hipSuccess; }
+    for (int i = 0; i < 2 && ok; ++i) ok = hipEventCreateWithFlags(&ctx->ev_post[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      for (hipEvent_t& ev : ctx->ev_post) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+      if (ctx->post_stream) (void)hipStreamDestroy(ctx->post_stream);
+      ctx->post_stream = nullptr;
+    }
+  }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
     snprintf(ctx->devname, sizeof(ctx->devname), "%s (%s)", prop.name, prop.gcnArchName);
@@ -249,6 +242,7 @@ void prisim_hip_destroy(prisim_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  if (ctx->post_stream) (void)hipStreamSynchronize(ctx->post_stream);
   catalog_destroy(ctx);
   if (ctx->comm_stream) (void)hipStreamSynchronize(ctx->comm_stream);
   if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
@@ -263,7 +257,7 @@ void prisim_hip_destroy(prisim_ctx* ctx) {
   if (ctx->fft_plan && g_rocfft.plan_destroy) g_rocfft.plan_destroy(ctx->fft_plan);
   if (ctx->fft_info && g_rocfft.execution_info_destroy) g_rocfft.execution_info_destroy(ctx->fft_info);
   for (DevBuf* b : {&ctx->blx, &ctx->bly, &ctx->blz, &ctx->ublx, &ctx->ubly, &ctx->ublz, &ctx->fold_map, &ctx->fold_vis, &ctx->fold_grad, &ctx->freqs, &ctx->fsq, &ctx->fsq_pairs, &ctx->cube, &ctx->grad, &ctx->dirs,
-                    &ctx->partial, &ctx->scratch, &ctx->gathered, &ctx->sendbuf, &ctx->shard_map, &ctx->stage_main, &ctx->stage_comm, &ctx->ext_table,
+                    &ctx->partial, &ctx->partial_b, &ctx->scratch, &ctx->gathered, &ctx->sendbuf, &ctx->shard_map, &ctx->stage_main, &ctx->stage_comm, &ctx->ext_table,
                     &ctx->ext_work, &ctx->ext_colmax, &ctx->sky_flux, &ctx->sky_sp, &ctx->sky_bf, &ctx->sky_flag,
                     &ctx->dl_stage, &ctx->grp_hz, &ctx->fft_work, &ctx->fft_buf, &ctx->dt_out, &ctx->dt_pow, &ctx->dt_wts, &ctx->dt_lag_all, &ctx->dt_pow_all, &ctx->dt_tw})
     release(*b);
@@ -277,6 +271,8 @@ void prisim_hip_destroy(prisim_ctx* ctx) {
   for (int i = 0; i < prisim_ctx::kTimingRing; ++i)
     for (hipEvent_t ev : {ctx->ev_c0[i], ctx->ev_c1[i], ctx->ev_k0[i], ctx->ev_k1[i]})
       if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : ctx->ev_post) if (ev) (void)hipEventDestroy(ev);
+  if (ctx->post_stream) (void)hipStreamDestroy(ctx->post_stream);
   if (ctx->ev_stage) (void)hipEventDestroy(ctx->ev_stage);
   if (ctx->ev_d0) (void)hipEventDestroy(ctx->ev_d0);
   if (ctx->ev_d1) (void)hipEventDestroy(ctx->ev_d1);
@@ -321,6 +317,14 @@ int prisim_hip_set_array(prisim_ctx* ctx, const double* bl_enu, int64_t nbl, con
   const int64_t nbl_u = (int64_t)fold_rep.size();
   bool fold = nbl_u * 8 <= nbl * 7 && nbl_u > kBlockThreads;
   if (const char* env = getenv("PRISIM_HIP_FOLD")) fold = fold && atoi(env) != 0;
+  // PRISIM_HIP_DEFER_POST=0: reduce / expand stay on the compute stream behind their sky-sum (the A/B hook of the deferred post-pass)
+  ctx->defer_post = true;
+  if (const char* env = getenv("PRISIM_HIP_DEFER_POST")) ctx->defer_post = atoi(env) != 0;
+  // Four workgroups per CU.  Measured on the headline step beside the next sky-sum (profiles/LOG.md 4.1.9): the kernels' own grids
+  // (8192 workgroups) flood the CUs and the memory system while the next snapshot's pack / prep and first round of sky-sum blocks start,
+  // one or two per CU keep the passes resident for a millisecond and cost the sky-sum more than they hide.
+  ctx->post_blocks = 4 * std::max(ctx->cu_count, 1);
+  if (const char* env = getenv("PRISIM_HIP_POST_BLOCKS")) { const int v = atoi(env); if (v >= 0 && v <= 8192) ctx->post_blocks = v; }      // (0: unbounded)
   const int64_t nbl_sum = fold ? nbl_u : nbl;
   std::vector<double> ux, uy, uz;
   if (fold) {
@@ -609,7 +613,7 @@ int prisim_hip_set_sky(prisim_ctx* ctx, const prisim_sky* sky) {
   stage_end(ctx);
   ctx->sky_set = true;
   return PRISIM_OK;
-  });
+  }, /*join=*/false);      // (a sky setter touches the sky's own buffers only: the next sky-sum still runs over a deferred post-pass)
 }
 
 }  // extern "C"
@@ -756,7 +760,7 @@ int prisim_hip_set_sky_analytic(prisim_ctx* ctx, const prisim_beam_sky* sky) {
   }
   ctx->sky_set = true;
   return PRISIM_OK;
-  });
+  }, /*join=*/false);      // (a sky setter touches the sky's own buffers only: the next sky-sum still runs over a deferred post-pass)
 }
 
 int prisim_hip_set_external_beam(prisim_ctx* ctx, const double* beam, int64_t npix, int64_t nfreq, const double* interp_matrix) {
@@ -835,7 +839,7 @@ int prisim_hip_set_sky_external(prisim_ctx* ctx, const prisim_sky* sky) {
   stage_end(ctx);
   ctx->sky_set = true;
   return PRISIM_OK;
-  });
+  }, /*join=*/false);      // (a sky setter touches the sky's own buffers only: the next sky-sum still runs over a deferred post-pass)
 }
 
 int prisim_hip_set_sky_external_analytic(prisim_ctx* ctx, const prisim_beam_sky* sky) {
@@ -868,7 +872,7 @@ int prisim_hip_set_sky_external_analytic(prisim_ctx* ctx, const prisim_beam_sky*
   stage_end(ctx);
   ctx->sky_set = true;
   return PRISIM_OK;
-  });
+  }, /*join=*/false);      // (a sky setter touches the sky's own buffers only: the next sky-sum still runs over a deferred post-pass)
 }
 
 int prisim_hip_get_pbflux(prisim_ctx* ctx, double* out) {
@@ -991,7 +995,10 @@ static bool wave_items(const prisim_ctx* ctx, const Plan& pl) {
   return on;
 }
 
-static int run_pass(prisim_ctx* ctx, const Plan& pl, double* dst, int scale_comp, bool timed, bool prep = false) {
+// post_set >= 0 (a deferred compute(), ctx_internal.h): the partial cubes are those of set post_set, and k_reduce_partials runs on the
+// post stream behind the sky-sum's event ev_k1 (timed is then set).
+static int run_pass(prisim_ctx* ctx, const Plan& pl, double* dst, int scale_comp, bool timed, bool prep = false, int post_set = -1) {
+  DevBuf& part = post_set == 1 ? ctx->partial_b : ctx->partial;
   SkyvisParams p{};
   fill_params(ctx, pl, p);
   p.scale_comp = scale_comp;
@@ -1034,14 +1041,14 @@ static int run_pass(prisim_ctx* ctx, const Plan& pl, double* dst, int scale_comp
     max_per = 0;
     for (const auto& run : ctx->kappa_runs) max_per = std::max(max_per, run_per_split(run));
   }
-  p.out = pl.nsplit > 1 ? (double*)ctx->partial.p : dst;
+  p.out = pl.nsplit > 1 ? (double*)part.p : dst;
   // fp32 kernels whose splits each flush exactly once store their partial sums as complex64: half the partial traffic
   const bool part_f32 = pl.nsplit > 1 && pl.f32 && pl.kernel == PRISIM_KERNEL_RECURRENCE && max_per <= (int64_t)p.flush_src;
   p.out_f32 = part_f32 ? 1 : 0;
   const size_t set_reals = (size_t)pl.nsplit * (size_t)ctx->nbl_sum * (size_t)ctx->nchan * 2;       // reals of one run's partial cubes
   auto set_out = [&](size_t r) -> double* {
     if (nsets == 1) return p.out;
-    return part_f32 ? (double*)((float*)ctx->partial.p + r * set_reals) : (double*)ctx->partial.p + r * set_reals;
+    return part_f32 ? (double*)((float*)part.p + r * set_reals) : (double*)part.p + r * set_reals;
   };
   // taper culling: per baseline group the first source it still has to sum (tables staged by set_sky_*); a launch over the whole sky
   // can only skip the leading sources of the FIRST run
@@ -1054,6 +1061,8 @@ static int run_pass(prisim_ctx* ctx, const Plan& pl, double* dst, int scale_comp
   if (cull && !split) p.src_first = cull_table(0);
   ctx->timing.last_culled_fraction = cull ? ctx->cull_frac[cpr] : 0.0;
   ctx->cull_frac_pending = (cull && ctx->cat.cur >= 0) ? cpr + 1 : 0;      // catalogue path: the device's count is read once the events are in
+  // (the post-pass that last read this set of partial cubes, two computes ago, has to be through before the sky-sum writes it)
+  if (post_set >= 0 && ctx->post_rec[post_set]) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_post[post_set], 0));
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k0[ctx->ring_head], ctx->stream));
   if (split) {
     int launches = 0;
@@ -1125,8 +1134,14 @@ static int run_pass(prisim_ctx* ctx, const Plan& pl, double* dst, int scale_comp
     HIPCHK(ctx, launch_skyvis_rec(p, pl.f32, pl.ct, ctx->stream));
   }
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k1[ctx->ring_head], ctx->stream));
+  hipStream_t rs = ctx->stream;
+  if (post_set >= 0) {
+    rs = ctx->post_stream;
+    HIPCHK(ctx, hipStreamWaitEvent(rs, ctx->ev_k1[ctx->ring_head], 0));
+  }
   if (pl.nsplit > 1)
-    HIPCHK(ctx, launch_reduce_partials(ctx->partial.p, part_f32, dst, ctx->nbl_sum * ctx->nchan * 2, pl.nsplit * nsets, ctx->stream));
+    HIPCHK(ctx, launch_reduce_partials(part.p, part_f32, dst, ctx->nbl_sum * ctx->nchan * 2, pl.nsplit * nsets, rs,
+                                       post_set >= 0 ? (unsigned)ctx->post_blocks : 0u));
   return PRISIM_OK;
 }
 
@@ -1174,10 +1189,14 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
   if (kernel == PRISIM_KERNEL_RECURRENCE && !ctx->uniform)
     return fail(ctx, PRISIM_EINVAL, "recurrence kernel needs a uniform channel grid");
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  // Deferred post-pass (ctx_internal.h): a folded array, a source split, the recurrence kernel, no gradient.  The plan decides the rest
+  // below; every compute() that cannot be deferred joins the post stream before it enqueues anything.
+  bool defer = ctx->defer_post && ctx->post_stream && ctx->folded && !want_grad && ctx->nsrc > 0;
+  int rc;
+  if (!defer && (rc = join_post(ctx))) return rc;
   harvest_timing(ctx, /*max_wait=*/ctx->ring_pending >= prisim_ctx::kTimingRing ? 1 : 0);   // a full ring waits for its oldest entry only
   const size_t slot_elems = (size_t)ctx->nbl * ctx->nchan * 2;
   double* dst = (double*)ctx->cube.p + (size_t)slot * slot_elems;
-  int rc;
   if (want_grad) {
     const size_t gbytes = (size_t)ctx->nt_max * 3 * slot_elems * sizeof(double);
     if (!ctx->grad.p) {
@@ -1222,6 +1241,11 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
     pl.nsrc_pad = round_up(pl.nsrc_pad, 4);       // the fp64 kernel walks the sources four at a time (zero rows past nsrc)
     pl.src_per_split = pl.nsrc_pad;
   }
+  if (defer && !(pl.kernel == PRISIM_KERNEL_RECURRENCE && pl.nsplit > 1)) {      // (nothing of this compute() is enqueued yet)
+    defer = false;
+    if ((rc = join_post(ctx))) return rc;
+  }
+  const int post_set = defer ? ctx->part_next : -1;
   ctx->timing.last_lift_groups = 0;
   ctx->last_sum_lift_groups = 0;
   ctx->timing.last_taper_group = 0;
@@ -1235,7 +1259,8 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
     if ((rc = ensure(ctx, ctx->sk->dirs_prep, (size_t)pl.nsrc_pad * 4 * sizeof(double)))) return rc;
     // (a sky of several runs of one source size writes one set of partial cubes per run: run_pass)
     const size_t part_sets = (ctx->taper && ctx->kappa_runs.size() > 1 && ctx->kappa_runs.size() <= (size_t)kMaxRunSets) ? ctx->kappa_runs.size() : 1;
-    if (pl.nsplit > 1 && (rc = ensure(ctx, ctx->partial, part_sets * (size_t)pl.nsplit * sum_elems * sizeof(double)))) return rc;
+    if (pl.nsplit > 1 && (rc = ensure(ctx, post_set == 1 ? ctx->partial_b : ctx->partial, part_sets * (size_t)pl.nsplit * sum_elems * sizeof(double))))
+      return rc;
     {
       // lifting rotation is used for a baseline group only when |step phase| <= 1/8 cycle (fp32; 1/4 cycle in fp64, where the
       // angle error alpha*eps is irrelevant and only tan(alpha/2) must stay bounded) is guaranteed for every source:
@@ -1290,10 +1315,12 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
     HIPCHK(ctx, launch_prep_dirs(ctx->dirs_p, (double*)ctx->sk->dirs_prep.p, c32, ctx->nsrc, pl.nsrc_pad, ctx->pc[0],
                                  ctx->pc[1], ctx->pc[2], 1.0 / kC, pstream(ctx)));
   }
+  // (a deferred compute() that fails half-way leaves no post-pass behind that nobody would wait for: the post stream is drained)
+  auto post_abort = [&](int code) { if (defer) (void)hipStreamSynchronize(ctx->post_stream); return code; };
   if (fused_grad) {
     if ((rc = run_grad_pass(ctx, pl, dst, gbase))) return rc;
-  } else if ((rc = run_pass(ctx, pl, dst, -1, true, /*prep=*/true))) {      // (prepares the directions with its first launch)
-    return rc;
+  } else if ((rc = run_pass(ctx, pl, dst, -1, true, /*prep=*/true, post_set))) {      // (prepares the directions with its first launch)
+    return post_abort(rc);
   }
   if (want_grad && !fused_grad) {
     for (int comp = 0; comp < 3; ++comp) {
@@ -1301,11 +1328,24 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
       if ((rc = run_pass(ctx, pl, gdst, comp, false))) return rc;
     }
   }
-  if (ctx->folded)      // inside last_compute_ms; last_kernel_ms stays the sky-sum alone
-    HIPCHK(ctx, launch_expand_rows(dst, gbase, (const int32_t*)ctx->fold_map.p, slot_dst,
-                                   want_grad ? (double*)ctx->grad.p + (size_t)slot * 3 * slot_elems : nullptr, ctx->nbl, ctx->nbl_sum, ctx->nchan,
-                                   ctx->stream));
-  HIPCHK(ctx, hipEventRecord(ctx->ev_c1[ctx->ring_head], ctx->stream));
+  // the stream the compute() ends on: deferred, the post stream -- run_pass has queued the reduction there behind the sky-sum, and the
+  // expansion and ev_c1 follow it, so that last_compute_ms still spans the expansion
+  const hipStream_t end_stream = defer ? ctx->post_stream : ctx->stream;
+  if (ctx->folded) {      // inside last_compute_ms; last_kernel_ms stays the sky-sum alone
+    if (launch_expand_rows(dst, gbase, (const int32_t*)ctx->fold_map.p, slot_dst,
+                           want_grad ? (double*)ctx->grad.p + (size_t)slot * 3 * slot_elems : nullptr, ctx->nbl, ctx->nbl_sum, ctx->nchan,
+                           end_stream, defer ? (unsigned)ctx->post_blocks : 0u) != hipSuccess)
+      return post_abort(fail(ctx, PRISIM_ENODEV, "launch of k_expand_rows failed"));
+  }
+  if (hipEventRecord(ctx->ev_c1[ctx->ring_head], end_stream) != hipSuccess)
+    return post_abort(fail(ctx, PRISIM_ENODEV, "hipEventRecord(end of compute) failed"));
+  if (defer) {
+    if (hipEventRecord(ctx->ev_post[post_set], ctx->post_stream) != hipSuccess)
+      return post_abort(fail(ctx, PRISIM_ENODEV, "hipEventRecord(deferred post-pass) failed"));
+    ctx->post_rec[post_set] = true;
+    ctx->post_last = post_set;
+    ctx->part_next = post_set ^ 1;
+  }
   if (ctx->prep_async) {
     HIPCHK(ctx, hipEventRecord(ctx->sk->ev_sum, ctx->stream));
     ctx->sk->sum_recorded = true;
@@ -1320,7 +1360,7 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
   ctx->timing.last_chan_tile = pl.kernel == PRISIM_KERNEL_RECURRENCE ? pl.ct : 1;
   ctx->timing.last_nsplit = pl.kernel == PRISIM_KERNEL_RECURRENCE ? pl.nsplit : 1;
   return PRISIM_OK;
-  });
+  }, /*join=*/false);
 }
 
 static void to_c64(const double* in, float* out, size_t n2) {
@@ -1388,6 +1428,7 @@ int prisim_hip_sync(prisim_ctx* ctx) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->prep_stream) HIPCHK(ctx, hipStreamSynchronize(ctx->prep_stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->post_stream) HIPCHK(ctx, hipStreamSynchronize(ctx->post_stream));
   if (ctx->comm_stream && ctx->comm_pending) { HIPCHK(ctx, hipStreamSynchronize(ctx->comm_stream)); ctx->comm_pending = false; }
   if (ctx->copy_stream && ctx->copy_pending) { HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream)); ctx->copy_pending = false; }
   harvest_timing(ctx);
@@ -2003,6 +2044,9 @@ int prisim_hip_allgather_slot_async(prisim_ctx* ctx, int64_t slot, int as_c64) {
   // the gather of slot t waits for everything enqueued so far on the compute stream (i.e. compute(slot t)) ...
   HIPCHK(ctx, hipEventRecord(ctx->ev_gc[ri], ctx->stream));
   HIPCHK(ctx, hipStreamWaitEvent(ctx->comm_stream, ctx->ev_gc[ri], 0));
+  // ... and for the deferred post-pass that writes the slot: the communication stream joins it, not the compute stream, so that the next
+  // sky-sum still runs over the post-pass and the gather
+  if ((rc = join_post_on(ctx, ctx->comm_stream))) return rc;
   // ... and runs on the (highest-priority) communication stream, overlapping the next snapshot's compute
   HIPCHK(ctx, hipEventRecord(ctx->ev_g0[ri], ctx->comm_stream));
   if ((rc = gather_one_slot(ctx, (const double*)ctx->cube.p, ctx->nchan, 1, slot, as_c64, ctx->comm_stream, ri))) return rc;
@@ -2013,7 +2057,7 @@ int prisim_hip_allgather_slot_async(prisim_ctx* ctx, int64_t slot, int as_c64) {
   ctx->cstats.nranks = ctx->nranks;
   ctx->comm_pending = true;
   return PRISIM_OK;
-  });
+  }, /*join=*/false);
 }
 
 int prisim_hip_get_gathered(prisim_ctx* ctx, int64_t nt, void* out) {
@@ -2218,6 +2262,7 @@ int prisim_hip_get_vis_async(prisim_ctx* ctx, int64_t slot, void* vis, void* gra
   // under the next snapshot's compute
   HIPCHK(ctx, hipEventRecord(ctx->ev_copy_ready, ctx->stream));
   HIPCHK(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_copy_ready, 0));
+  if ((rc = join_post_on(ctx, ctx->copy_stream))) return rc;      // (the deferred post-pass writes the slot: the copy stream joins it)
   if (!out_is_c64) {
     HIPCHK(ctx, hipMemcpyAsync(vis, src, slot_elems * sizeof(double), hipMemcpyDeviceToHost, ctx->copy_stream));
     if (grad) HIPCHK(ctx, hipMemcpyAsync(grad, gsrc, 3 * slot_elems * sizeof(double), hipMemcpyDeviceToHost, ctx->copy_stream));
@@ -2238,7 +2283,7 @@ int prisim_hip_get_vis_async(prisim_ctx* ctx, int64_t slot, void* vis, void* gra
   }
   ctx->copy_pending = true;
   return PRISIM_OK;
-  });
+  }, /*join=*/false);
 }
 
 int prisim_hip_wait_downloads(prisim_ctx* ctx) {

@@ -853,7 +853,7 @@ int prisim_hip_set_sky_from_catalog(prisim_ctx* ctx, const prisim_obs* obs, cons
   C.next = b ^ 1;
   if (nsrc_roi) *nsrc_roi = ctx->nsrc;
   return PRISIM_OK;
-  });
+  }, /*join=*/false);      // (a sky setter touches the sky's own buffers only: the next sky-sum still runs over a deferred post-pass)
 }
 
 int prisim_hip_catalog_roi(prisim_ctx* ctx, const prisim_obs* obs, const prisim_snapshot* snap, int64_t* nsrc_roi, int64_t* indices, double* dircos,

@@ -20,6 +20,7 @@
 #include "skyvis_kernels.h"
 #include "baseline_fold.h"
 #include "step_bound.h"
+#include "split_plan.h"
 
 using namespace prisim;
 
@@ -158,6 +159,20 @@ struct prisim_ctx {
   bool taper = false;
   double pc[3] = {0, 0, 1};
   DevBuf dirs, partial, scratch;
+  // Deferred post-pass.  A folded compute() with a source split (recurrence kernel, no gradient) enqueues only pack / prep and the
+  // sky-sum on the compute stream; k_reduce_partials and k_expand_rows run on post_stream behind an event, under the NEXT sky-sum.
+  // Two sets of partial cubes alternate per compute(): part_set(0) = `partial` (also the set of every undeferred compute), part_set(1) =
+  // `partial_b`; ev_post[s] is recorded behind the post-pass that last read set s, and the compute stream waits for it before a
+  // sky-sum writes the set again.  post_last >= 0: a post-pass is queued that the compute stream has not waited for yet -- join_post().
+  // Only the post stream touches the compact buffer and the cube slot inside a deferred compute(): stream order covers their reuse.
+  DevBuf partial_b;
+  hipStream_t post_stream = nullptr;      // non-blocking, highest priority; nullptr: it could not be made, nothing is deferred
+  hipEvent_t ev_post[2] = {nullptr, nullptr};
+  bool post_rec[2] = {false, false};
+  int part_next = 0;                      // set the next deferred compute() writes
+  int post_last = -1;
+  bool defer_post = true;                 // PRISIM_HIP_DEFER_POST=0: the single-stream order (the A/B hook; read by set_array)
+  int post_blocks = 0;                    // workgroups of a deferred reduce / expand launch (PRISIM_HIP_POST_BLOCKS; 0: the kernels' own grids)
   // per-snapshot sky inputs (flux_ref / spindex or a flux table, beamformer elements, validity flag): owned by the context so that
   // a set_sky_* call allocates nothing after the first snapshot
   DevBuf sky_flux, sky_sp, sky_bf, sky_flag;
@@ -290,11 +305,31 @@ inline int fail(prisim_ctx* ctx, int code, const std::string& msg) {
   return code;
 }
 
+// The stream `s` waits (on the device, no host block) for the last deferred post-pass: everything that reads or writes the cube, the
+// compact buffer or the partial cubes outside a deferred compute() comes behind this.
+inline int join_post_on(prisim_ctx* ctx, hipStream_t s) {
+  if (ctx->post_last < 0) return PRISIM_OK;
+  if (hipStreamWaitEvent(s, ctx->ev_post[ctx->post_last], 0) != hipSuccess)
+    return fail(ctx, PRISIM_ENODEV, "hipStreamWaitEvent(deferred post-pass) failed");
+  return PRISIM_OK;
+}
+
+// ... the compute stream does, and with it every stream that orders itself behind the compute stream (communication, copy, add-ons)
+inline int join_post(prisim_ctx* ctx) {
+  if (ctx->post_last < 0) return PRISIM_OK;
+  if (int rc = join_post_on(ctx, ctx->stream)) return rc;
+  ctx->post_last = -1;
+  return PRISIM_OK;
+}
+
 // Every extern "C" entry runs its body through this: no C++ exception crosses the ABI; a failed host allocation
 // becomes PRISIM_ENOMEM, anything else PRISIM_EINTERNAL with the exception's text.
+// Before the body, the compute stream joins a deferred post-pass (join_post); prisim_hip_compute alone passes join = false and joins
+// where it does not defer.
 template <typename F>
-inline int guarded(prisim_ctx* ctx, F&& body) noexcept {
+inline int guarded(prisim_ctx* ctx, F&& body, bool join = true) noexcept {
   try {
+    if (ctx && join) { if (int rc = join_post(ctx)) return rc; }
     return body();
   } catch (const std::bad_alloc&) {
     return fail(ctx, PRISIM_ENOMEM, "out of host memory");

@@ -118,11 +118,13 @@ hipError_t launch_pack_grad(const double* pb, float* packed, int64_t nsrc, int64
                             hipStream_t stream);
 hipError_t launch_prep_dirs(const double* dirs, double* prep, float* c32 /*[nsrc_pad][8] or NULL*/, int64_t nsrc, int64_t nsrc_pad, double pcx,
                             double pcy, double pcz, double inv_c, hipStream_t stream);
-hipError_t launch_reduce_partials(const void* part, bool part_f32, double* out, int64_t n2, int nsplit, hipStream_t stream);
+// max_blocks > 0 (both launchers below): at most that many workgroups.  The kernels stride over their grid, so the results do not depend
+// on it; a pass that runs beside a sky-sum is held to a grid that leaves the sky-sum its resident blocks (capi.cpp: deferred post-pass).
+hipError_t launch_reduce_partials(const void* part, bool part_f32, double* out, int64_t n2, int nsplit, hipStream_t stream, unsigned max_blocks = 0);
 // folded arrays: row b of vis_out [nbl][nchan] (and of the three planes of grad_out, when given) = row map[b] of the compact
 // vis_c [nbl_sum][nchan] (grad_c [3][nbl_sum][nchan]); complex128
 hipError_t launch_expand_rows(const double* vis_c, const double* grad_c, const int32_t* map, double* vis_out, double* grad_out, int64_t nbl,
-                              int64_t nbl_sum, int64_t nchan, hipStream_t stream);
+                              int64_t nbl_sum, int64_t nchan, hipStream_t stream, unsigned max_blocks = 0);
 hipError_t launch_f32_to_f64(const float* in, double* out, int64_t n, hipStream_t stream);
 hipError_t launch_fsq(const double* freqs, float* fsq, int64_t nchan, int64_t npad, double scale, hipStream_t stream);
 

@@ -2419,19 +2419,23 @@ hipError_t launch_pack_grad(const double* pb, float* packed, int64_t nsrc, int64
   return hipGetLastError();
 }
 
-hipError_t launch_reduce_partials(const void* part, bool part_f32, double* out, int64_t n2, int nsplit, hipStream_t stream) {
+hipError_t launch_reduce_partials(const void* part, bool part_f32, double* out, int64_t n2, int nsplit, hipStream_t stream, unsigned max_blocks) {
+  unsigned g = grid_for(n2);
+  if (max_blocks > 0 && g > max_blocks) g = max_blocks;
   if (part_f32)
-    hipLaunchKernelGGL(k_reduce_partials<float>, dim3(grid_for(n2)), dim3(256), 0, stream, (const float*)part, out, n2, nsplit);
+    hipLaunchKernelGGL(k_reduce_partials<float>, dim3(g), dim3(256), 0, stream, (const float*)part, out, n2, nsplit);
   else
-    hipLaunchKernelGGL(k_reduce_partials<double>, dim3(grid_for(n2)), dim3(256), 0, stream, (const double*)part, out, n2, nsplit);
+    hipLaunchKernelGGL(k_reduce_partials<double>, dim3(g), dim3(256), 0, stream, (const double*)part, out, n2, nsplit);
   return hipGetLastError();
 }
 
 hipError_t launch_expand_rows(const double* vis_c, const double* grad_c, const int32_t* map, double* vis_out, double* grad_out, int64_t nbl,
-                              int64_t nbl_sum, int64_t nchan, hipStream_t stream) {
+                              int64_t nbl_sum, int64_t nchan, hipStream_t stream, unsigned max_blocks) {
   if (nbl <= 0 || nchan <= 0) return hipSuccess;
   const bool grad = grad_c && grad_out;
-  hipLaunchKernelGGL(k_expand_rows, dim3(grid_for(nbl * 64), grad ? 4 : 1), dim3(256), 0, stream, (const double2*)vis_c, (const double2*)grad_c, map,
+  unsigned g = grid_for(nbl * 64);
+  if (max_blocks > 0 && g > max_blocks) g = max_blocks;
+  hipLaunchKernelGGL(k_expand_rows, dim3(g, grad ? 4 : 1), dim3(256), 0, stream, (const double2*)vis_c, (const double2*)grad_c, map,
                      (double2*)vis_out, (double2*)grad_out, nbl, nbl_sum, nchan);
   return hipGetLastError();
 }
