@@ -107,6 +107,13 @@ CPREAL_ROUTES = {PRISIM_CPREAL_DIRECT: 'direct', PRISIM_CPREAL_STAGED: 'staged'}
 CPREAL_KINDS = {'noisy': 0, 'noise': 1}
 # every symbol include/prisim_antpower.h declares: beam-weighted sky power per snapshot (prisim_amd/csrc_antpower/antpower.hip)
 ANTPOWER_EXPORTS = ('prisim_antenna_power',)
+# every symbol include/prisim_imaging.h declares: dirty images and synthesized beams by the direct Fourier sum (prisim_amd/csrc_imaging/imaging.hip)
+IMAGING_EXPORTS = ('prisim_dirty_image',)
+PRISIM_IMAGE_DIRTY, PRISIM_IMAGE_PSF = 0, 1
+PRISIM_IMAGE_AUTO, PRISIM_IMAGE_DIRECT, PRISIM_IMAGE_STEPPED = -1, 0, 1
+PRISIM_IMAGE_W_NONE, PRISIM_IMAGE_W_BASELINE, PRISIM_IMAGE_W_FULL = 0, 1, 2
+IMAGING_ROUTES = {PRISIM_IMAGE_DIRECT: 'direct', PRISIM_IMAGE_STEPPED: 'stepped'}
+IMAGING_KINDS = {'dirty': PRISIM_IMAGE_DIRTY, 'psf': PRISIM_IMAGE_PSF}
 
 # every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
 GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
@@ -313,6 +320,22 @@ class _PrisimAntpowerArgs(C.Structure):
                 ('budget_bytes', C.c_int64)]
 
 
+class _PrisimImagingStats(C.Structure):
+    """prisim_imaging_stats of include/prisim_imaging.h, public as Context.PrisimImagingStats (see _PrisimCpxpsStats);
+    tests/test_imaging.py holds it to the header."""
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('terms', C.c_int64), ('chunks', C.c_int64), ('chunk_pixels', C.c_int64),
+                ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('route', C.c_int32),
+                ('streams', C.c_int32), ('chan_tile', C.c_int32), ('reseed', C.c_int32), ('lds_bytes', C.c_int32), ('block_pixels', C.c_int32)]
+
+
+class _PrisimImagingArgs(C.Structure):
+    """prisim_imaging_args of include/prisim_imaging.h, public as Context.PrisimImagingArgs."""
+    _fields_ = [('npix', C.c_int64), ('nbl', C.c_int64), ('nchan', C.c_int64), ('nt', C.c_int64), ('unitvec', C.c_void_p), ('rot', C.c_void_p),
+                ('aberr_beta', C.c_void_p), ('pc_dircos', C.c_void_p), ('baselines', C.c_void_p), ('freqs_hz', C.c_void_p), ('cube', C.c_void_p),
+                ('weights', C.c_void_p), ('kind', C.c_int32), ('weight_form', C.c_int32), ('chan_avg', C.c_int32), ('route', C.c_int32),
+                ('budget_bytes', C.c_int64)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -509,6 +532,8 @@ def load_library():
     lib.prisim_closure_realizations.restype = C.c_int
     lib.prisim_antenna_power.argtypes = [vp, C.POINTER(_PrisimAntpowerArgs), vp, vp, vp, C.POINTER(_PrisimAntpowerStats)]
     lib.prisim_antenna_power.restype = C.c_int
+    lib.prisim_dirty_image.argtypes = [vp, C.POINTER(_PrisimImagingArgs), vp, vp, C.POINTER(_PrisimImagingStats)]
+    lib.prisim_dirty_image.restype = C.c_int
     pst = C.POINTER(PrisimGainsStats)
     lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
                                              C.POINTER(vp), pst]
@@ -1316,6 +1341,66 @@ class Context(object):
         st = self.PrisimAntpowerStats()
         self._check(self._lib.prisim_antenna_power(self._h, C.byref(a), _ptr(power), _ptr(num), _ptr(den), C.byref(st)), 'prisim_antenna_power')
         return power, num, den, _stats_dict(st)
+
+    # ---- dirty images and synthesized beams by the direct Fourier sum (include/prisim_imaging.h) ----
+    PrisimImagingStats = _PrisimImagingStats
+    PrisimImagingArgs = _PrisimImagingArgs
+
+    def dirty_image(self, unitvec, rot, pc_dircos, baselines, freqs_hz, cube=None, weights=None, kind='dirty', chan_avg=False,
+                    aberr_beta=None, route='auto', budget_bytes=0):
+        """The dirty image (kind 'dirty') or the synthesized beam ('psf') at the given directions by the direct Fourier sum on the
+        device (prisim_dirty_image): D[p][k] = sum_t sum_b w Re(V e^{+i phi}), phi = 2 pi f_k b . (s - s0) / c, over W[k] = sum w.
+        unitvec: (npix, 3) unit vectors of the directions in their own frame (geometry.catalog_unitvec); rot: (nt, 3, 3) rotations of
+        that frame into East-North-Up and aberr_beta: (nt, 3) or None, as prisim_amd.frames.snapshot_frame gives them; pc_dircos:
+        (nt, 3) East-North-Up phase centres; baselines: (nbl, 3) metres; freqs_hz: (nchan,).  cube: (nt, nbl, nchan) complex128 on the
+        host, or None for the resident visibility slots [0, nt) of this context; not read for the PSF.  weights: None, (nbl,) or (nt,
+        nbl, nchan), finite and non-negative.  chan_avg: one image of the band instead of one per channel.  route: 'auto', 'direct'
+        or 'stepped'; budget_bytes: device bytes of the streamed buffers (0: 1 GiB), which the result does not depend on.  Returns
+        (image (npix, nchan) or (npix,), wsum (nchan,) or (1,), stats); a zero weight sum is NaN in the image; stats['resident']: the
+        resident cube was read."""
+        uv = NP.ascontiguousarray(unitvec, dtype=NP.float64).reshape(-1, 3)
+        rt = NP.ascontiguousarray(rot, dtype=NP.float64).reshape(-1, 9)
+        pc = NP.ascontiguousarray(pc_dircos, dtype=NP.float64).reshape(-1, 3)
+        bl = NP.ascontiguousarray(baselines, dtype=NP.float64).reshape(-1, 3)
+        fq = NP.ascontiguousarray(freqs_hz, dtype=NP.float64).ravel()
+        npix, nt, nbl, nchan = uv.shape[0], rt.shape[0], bl.shape[0], fq.size
+        if pc.shape[0] != nt:
+            raise ValueError('pc_dircos must have one row per snapshot')
+        ab = None
+        if aberr_beta is not None:
+            ab = NP.ascontiguousarray(aberr_beta, dtype=NP.float64).reshape(-1, 3)
+            if ab.shape[0] != nt:
+                raise ValueError('aberr_beta must have one row per snapshot')
+        if kind not in IMAGING_KINDS:
+            raise ValueError("kind must be 'dirty' or 'psf'")
+        if route != 'auto' and route not in IMAGING_ROUTES.values():
+            raise ValueError("route must be 'auto', 'direct' or 'stepped'")
+        x = None
+        if cube is not None and kind == 'dirty':
+            x = NP.ascontiguousarray(cube, dtype=NP.complex128)
+            if x.shape != (nt, nbl, nchan):
+                raise ValueError('cube must be (nt, nbl, nchan)')
+        w, form = None, PRISIM_IMAGE_W_NONE
+        if weights is not None:
+            w = NP.ascontiguousarray(weights, dtype=NP.float64)
+            if w.shape == (nbl,):
+                form = PRISIM_IMAGE_W_BASELINE
+            elif w.shape == (nt, nbl, nchan):
+                form = PRISIM_IMAGE_W_FULL
+            else:
+                raise ValueError('weights must be None, (nbl,) or (nt, nbl, nchan)')
+        a = self.PrisimImagingArgs()
+        a.npix, a.nbl, a.nchan, a.nt = npix, nbl, nchan, nt
+        a.unitvec, a.rot, a.aberr_beta, a.pc_dircos = _ptr(uv), _ptr(rt), _ptr(ab), _ptr(pc)
+        a.baselines, a.freqs_hz, a.cube, a.weights = _ptr(bl), _ptr(fq), _ptr(x), _ptr(w)
+        a.kind, a.weight_form, a.chan_avg = IMAGING_KINDS[kind], form, 1 if chan_avg else 0
+        a.route = _route_code(route, IMAGING_ROUTES)
+        a.budget_bytes = int(budget_bytes or 0)
+        image = NP.empty((npix,) if chan_avg else (npix, nchan), dtype=NP.float64)
+        wsum = NP.empty(1 if chan_avg else nchan, dtype=NP.float64)
+        st = self.PrisimImagingStats()
+        self._check(self._lib.prisim_dirty_image(self._h, C.byref(a), _ptr(image), _ptr(wsum), C.byref(st)), 'prisim_dirty_image')
+        return image, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=x is None and kind == 'dirty')
 
     # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
     def closure_delay_spectra(self, wts, m, df, phases=None, cube=None, legs=None, conj=None, bpwts=None, freq_wts=None, masks=None,

@@ -2756,3 +2756,186 @@ class InterferometerArray(object):
                     return NP.repeat(transform(NP.ones((nbl, nchan, 1), dtype=NP.complex128))[0], nt, axis=2)
                 return transform(NP.ones((nbl, nchan, nt), dtype=NP.complex128))[0]
         return sky, lags, vis_lag, vis_noise_lag, make_kernel
+
+
+class _Epoch(object):
+    """What a frame_provider reads of a sky model: its epoch."""
+
+    def __init__(self, epoch):
+        self.epoch = epoch
+
+
+class ApertureSynthesis(object):
+    """Aperture synthesis of the visibilities of an InterferometerArray: the reference's ApertureSynthesis (prisim/interferometry.py
+    :8990-9255) -- constructor, genUVW, reorderUVW, with its attributes and exceptions -- and what its docstring promises and its body
+    does not reach: the dirty image and the synthesized beam of a run, by the direct Fourier sum on the GPU (include/prisim_imaging.h),
+    the exact adjoint of the sky-sum with the same phase, phase centres and frames as observe().
+
+    Attributes as in the reference (:9136-9163): ia, f, df, n_acc, lst, phase_center, phase_center_coords, pointing_center,
+    pointing_coords, baselines, timestamp, latitude, blxyz, uvw_lambda, uvw, blc, trc, grid_blc, grid_trc, gridu, gridv, gridw,
+    grid_ready; and image_stats, the statistics of the last image() or psf().
+
+    Departures from the reference: setUVWgrid is not ported -- its grid comes from GRD.grid_3d, whose source is not part of the
+    reference tree, and the direct transform needs no grid; grid_ready stays False.  genUVW with a 'radec' phase centre takes
+    HA = LST - RA and the centre's declination, as _pc_dircos and project_baselines do (the reference puts HA = LST and Dec = 0, :9180).
+    image(), psf() and dircos_grid() are additions.  There is no CPU path."""
+
+    def __init__(self, interferometer_array=None):
+        if interferometer_array is None:
+            raise NameError('No input interferometer_array provided')
+        if not isinstance(interferometer_array, InterferometerArray):
+            raise TypeError('Input interferometer_array must be an instance of class InterferometerArray')
+        ia = self.ia = interferometer_array
+        self.f = ia.channels
+        self.df = ia.freq_resolution
+        self.n_acc = ia.n_acc
+        self.lst = ia.lst
+        self.phase_center = ia.phase_center
+        self.pointing_center = ia.pointing_center
+        self.phase_center_coords = ia.phase_center_coords
+        self.pointing_coords = ia.pointing_coords
+        self.baselines = ia.baselines
+        self.timestamp = ia.timestamp
+        self.latitude = ia.latitude
+        self.blxyz = GEOM.enu2xyz(self.baselines, self.latitude, units='degrees')
+        self.uvw_lambda = None
+        self.uvw = None
+        self.blc, self.trc = NP.zeros(2), NP.zeros(2)
+        self.grid_blc, self.grid_trc = NP.zeros(2), NP.zeros(2)
+        self.gridu, self.gridv, self.gridw = None, None, None
+        self.grid_ready = False
+        self.image_stats = None
+
+    def genUVW(self):
+        """(u, v, w) of every baseline phased to the phase centre of every snapshot: uvw_lambda (nbl, 3, n_acc) in metres and uvw
+        (nbl, 3, nchan, n_acc) in wavelengths (:9167-9195), with the rotation project_baselines carries (:7979-7981)."""
+        pc = NP.asarray(self.phase_center, dtype=NP.float64).reshape(-1, 2)
+        if self.phase_center_coords == 'hadec':
+            hadec = pc
+        elif self.phase_center_coords == 'radec':
+            hadec = NP.stack((NP.asarray(self.lst, dtype=NP.float64) - pc[:, 0], pc[:, 1]), axis=1)
+        elif self.phase_center_coords == 'altaz':
+            hadec = GEOM.altaz2hadec(pc, self.latitude, units='degrees')
+        else:
+            raise ValueError('Attribute phase_center_coords must be set to one of "hadec", "radec" or "altaz"')
+        ha, dec = NP.radians(hadec[:, 0]), NP.radians(hadec[:, 1])
+        rot = NP.asarray([[NP.sin(ha), NP.cos(ha), NP.zeros(ha.size)],
+                          [-NP.sin(dec) * NP.cos(ha), NP.sin(dec) * NP.sin(ha), NP.cos(dec)],
+                          [NP.cos(dec) * NP.cos(ha), -NP.cos(dec) * NP.sin(ha), NP.sin(dec)]])
+        self.uvw_lambda = NP.einsum('bk,jkt->bjt', self.blxyz, rot)
+        wl = C_LIGHT / NP.asarray(self.f, dtype=NP.float64)
+        self.uvw = self.uvw_lambda[:, :, NP.newaxis, :] / wl.reshape(1, 1, -1, 1)
+
+    def reorderUVW(self):
+        """uvw (nbl, 3, nchan, n_acc) as (3, nbl * nchan * n_acc) (:9208-9210)."""
+        return NP.swapaxes(self.uvw, 0, 1).reshape(3, -1)
+
+    @staticmethod
+    def dircos_grid(n, half_width):
+        """The (n * n, 3) East-North-Up direction cosines of a regular n x n grid in (l, m) over [-half_width, half_width]^2, row-major
+        in m then l (l fastest), the third from sqrt(1 - l^2 - m^2).  half_width <= 1 / sqrt(2) keeps every corner on the sphere."""
+        n = int(n)
+        if n < 1:
+            raise ValueError('n must be at least 1')
+        if not (0.0 <= half_width <= NP.sqrt(0.5)):
+            raise ValueError('half_width must lie in [0, 1/sqrt(2)]')
+        ax = NP.linspace(-float(half_width), float(half_width), n) if n > 1 else NP.zeros(1)
+        m, l = NP.meshgrid(ax, ax, indexing='ij')
+        l, m = l.ravel(), m.ravel()
+        return NP.stack((l, m, NP.sqrt(NP.maximum(0.0, 1.0 - l * l - m * m))), axis=1)
+
+    def _directions(self, directions, coords, epoch):
+        """(unit vectors (npix, 3) in their own frame, rotations (nt, 3, 3), aberration (nt, 3) or None)"""
+        ia, nt = self.ia, len(self.ia.lst)
+        d = NP.asarray(directions, dtype=NP.float64)
+        if d.ndim == 1:
+            d = d.reshape(1, -1)
+        if d.ndim != 2 or d.shape[0] < 1:
+            raise ValueError('directions must be a (npix, 2) or (npix, 3) array')
+        if coords == 'dircos':
+            if d.shape[1] not in (2, 3):
+                raise ValueError('Dimensions incompatible for direction cosine positions')
+            if NP.any(NP.sqrt(NP.sum(d ** 2, axis=1)) > 1.0 + 1e-12):
+                raise ValueError('direction cosines found to be exceeding unit magnitude.')
+            if d.shape[1] == 2:
+                d = NP.hstack((d, NP.sqrt(NP.maximum(0.0, 1.0 - NP.sum(d ** 2, axis=1))).reshape(-1, 1)))
+            return d, NP.repeat(NP.eye(3)[NP.newaxis], nt, axis=0), None
+        if coords not in ('altaz', 'hadec', 'radec'):
+            raise ValueError('coords must be "altaz", "hadec", "radec" or "dircos"')
+        if d.shape[1] != 2:
+            raise ValueError('directions in {0} must be a (npix, 2) array of degrees'.format(coords))
+        uv = GEOM.catalog_unitvec(d, coords)
+        if coords == 'altaz':
+            return uv, NP.repeat(NP.eye(3)[NP.newaxis], nt, axis=0), None
+        if coords == 'hadec':
+            return uv, NP.repeat(FRAMES.hadec_to_enu(ia.latitude)[NP.newaxis], nt, axis=0), None
+        rot, beta = [], []
+        for t in range(nt):                                            # what observe() applies to a 'radec' sky (_snapshot_frame)
+            if ia.frame_provider is not None:
+                r, b = ia.frame_provider(ia.timestamp[t], ia.lst[t], _Epoch(epoch))
+            else:
+                r, b = FRAMES.snapshot_frame('radec', ia.lst[t], ia.latitude, jd=ia.timestamp[t], epoch=epoch, model=ia.frame_model)
+            rot.append(NP.asarray(r, dtype=NP.float64).reshape(3, 3))
+            beta.append(NP.asarray(b, dtype=NP.float64).reshape(3))
+        return uv, NP.stack(rot), NP.stack(beta)
+
+    def _synthesize(self, kind, directions, coords, datakey, weights, chan_avg, epoch, route, budget_bytes):
+        ia = self.ia
+        nt = len(ia.lst)
+        if nt < 1:
+            raise ValueError('no snapshots: call observe() first')
+        if route not in ('auto', 'direct', 'stepped'):
+            raise ValueError("route must be 'auto', 'direct' or 'stepped'")
+        uv, rot, beta = self._directions(directions, coords, epoch)
+        nbl, nchan = ia.baselines.shape[0], ia.channels.size
+        w = None
+        if weights is not None:
+            w = NP.asarray(weights, dtype=NP.float64)
+            if w.shape == (nbl, nchan, nt):
+                w = NP.ascontiguousarray(NP.transpose(w, (2, 0, 1)))
+            elif w.shape != (nbl,):
+                raise ValueError('weights must be None, (nbl,) or (nbl, nchan, n_acc)')
+        cube = None
+        if kind == 'dirty':
+            names = {'noiseless': 'skyvis_freq', 'noisy': 'vis_freq', 'noise': 'vis_noise_freq'}
+            if datakey not in names:
+                raise ValueError("datakey must be 'noiseless', 'noisy' or 'noise'")
+            # the noiseless cube is read where it lies when the device slots [0, nt) hold skyvis_freq itself, in fp64 (_closure_prepare)
+            snaps = getattr(ia, '_cube', None) or []
+            resident = datakey == 'noiseless' and len(snaps) == nt and bool(ia._device_in_step) and nt <= ia._reserved and all(
+                sn.dtype == NP.complex128 and (not isinstance(sn, _DeviceSlot) or sn.slot == i) for i, sn in enumerate(snaps))
+            if not resident:
+                vis = getattr(ia, names[datakey])
+                if vis is None:
+                    raise ValueError('no {0}: the array holds no such visibilities'.format(names[datakey]))
+                vis = NP.asarray(vis)
+                if vis.shape != (nbl, nchan, nt):
+                    raise ValueError('{0} must have shape (nbl, nchan, n_acc)'.format(names[datakey]))
+                cube = NP.ascontiguousarray(NP.transpose(vis, (2, 0, 1)), dtype=NP.complex128)
+        pc = ia._pc_dircos(ia.phase_center, ia.phase_center_coords)
+        image, wsum, st = ia._ctx.dirty_image(uv, rot, pc, ia._baselines_local(), ia.channels, cube=cube, weights=w, kind=kind,
+                                              chan_avg=bool(chan_avg), aberr_beta=beta, route=route, budget_bytes=int(budget_bytes or 0))
+        self.image_stats = dict(st, wsum=wsum)
+        return image
+
+    def image(self, directions, coords='dircos', datakey='noiseless', weights=None, chan_avg=False, epoch=None, route='auto',
+              budget_bytes=None):
+        """The dirty image of the array's visibilities at the given directions, (npix, nchan) float64 or (npix,) with chan_avg: per
+        channel sum_{t,b} w Re(V e^{+i phi}) / sum_{t,b} w with phi = 2 pi f b . (s - s0) / c, s0 the array's phase centre of the
+        snapshot.  In the units of the visibilities per beam: a point source of flux S seen through a delta beam images to S at its own
+        direction.  No horizon test is made, and a channel whose weights are all zero is NaN.
+
+        directions   (npix, 2) degrees for coords 'altaz' (alt, az), 'hadec' and 'radec'; (npix, 2 | 3) for 'dircos' (East-North-Up).
+                     'radec' directions go through the frame observe() applies to a 'radec' sky (frame_model, or frame_provider when
+                     set) at every snapshot's LST and timestamp, with epoch= the epoch of the coordinates (None: of date): an image of
+                     a simulated catalogue shows its sources at the catalogue's positions.
+        datakey      'noiseless' (skyvis_freq), 'noisy' (vis_freq) or 'noise' (vis_noise_freq).  The noiseless cube is read where it
+                     lies on the device when the device slots are in step with skyvis_freq (reserve()); otherwise the cube is handed over.
+        weights      None, (nbl,) or (nbl, nchan, n_acc): finite and non-negative.
+        route        'auto', 'direct' or 'stepped' (include/prisim_imaging.h); budget_bytes: device bytes of the streamed buffers.
+        The entry's statistics, and 'wsum', are left in image_stats."""
+        return self._synthesize('dirty', directions, coords, datakey, weights, chan_avg, epoch, route, budget_bytes)
+
+    def psf(self, directions, coords='dircos', weights=None, chan_avg=False, epoch=None, route='auto', budget_bytes=None):
+        """The synthesized beam at the given directions: image() of V = 1, centred on every snapshot's phase centre, where it is 1."""
+        return self._synthesize('psf', directions, coords, None, weights, chan_avg, epoch, route, budget_bytes)
