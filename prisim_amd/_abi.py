@@ -5,6 +5,7 @@ fallback anywhere in ``prisim_amd``.
 """
 import ctypes as C
 import os
+import re
 
 import numpy as NP
 
@@ -14,110 +15,90 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PRISIM_HIP_LIB') or os.path.join(_HERE, 'lib', 'libprisim_hip.so')      # PRISIM_HIP_LIB: A/B another build of the same ABI
 ABI_VERSION = 'prisim_hip 0.5 gfx950'       # prisim_hip_version(): bumped whenever a struct or a signature of include/prisim_hip.h changes
 
+# the enumerators and macros of include/*.h, each under its own name (tests/test_abi_headers.py holds names and values to the headers)
 PRISIM_OK = 0
 PRISIM_EINVAL, PRISIM_ENODEV, PRISIM_ENOMEM, PRISIM_ESTATE, PRISIM_ELIB, PRISIM_EINTERNAL = -1, -2, -3, -4, -5, -6
 PRISIM_FP64, PRISIM_FP32 = 0, 1
 PRISIM_KERNEL_AUTO, PRISIM_KERNEL_RECURRENCE, PRISIM_KERNEL_DIRECT = 0, 1, 2
 PRISIM_BEAM_DELTA, PRISIM_BEAM_GAUSSIAN, PRISIM_BEAM_AIRY, PRISIM_BEAM_DIPOLE, PRISIM_BEAM_POLY = 0, 1, 2, 3, 4
 PRISIM_DIPOLE_GENERAL, PRISIM_DIPOLE_SHORT, PRISIM_DIPOLE_HALFWAVE = 0, 1, 2
-PRISIM_COORDS = {'radec': 0, 'hadec': 1, 'altaz': 2}
+PRISIM_COORDS_RADEC, PRISIM_COORDS_HADEC, PRISIM_COORDS_ALTAZ = 0, 1, 2
+PRISIM_COORDS = {'radec': PRISIM_COORDS_RADEC, 'hadec': PRISIM_COORDS_HADEC, 'altaz': PRISIM_COORDS_ALTAZ}
 
-# every symbol include/prisim_hip.h declares (tests check the library exports all of them)
-EXPORTS = (
-    'prisim_hip_create', 'prisim_hip_destroy', 'prisim_hip_last_error', 'prisim_hip_version',
-    'prisim_hip_set_array', 'prisim_hip_set_sky', 'prisim_hip_compute', 'prisim_hip_get_vis',
-    'prisim_hip_skyvis', 'prisim_hip_set_vis', 'prisim_hip_set_sky_analytic',
-    'prisim_hip_set_external_beam', 'prisim_hip_set_sky_external', 'prisim_hip_set_sky_external_analytic', 'prisim_hip_get_pbflux',
-    'prisim_hip_delay_transform', 'prisim_hip_delay_transform_device', 'prisim_hip_get_lags', 'prisim_hip_get_delay_power',
-    'prisim_hip_allgather_lags', 'prisim_hip_phase_rotate', 'prisim_hip_noise', 'prisim_hip_noise_indexed', 'prisim_hip_comm_unique_id',
-    'prisim_hip_comm_init',
-    'prisim_hip_allgather', 'prisim_hip_allgather_slot_async', 'prisim_hip_get_gathered', 'prisim_hip_gathered_checksum',
-    'prisim_hip_sync', 'prisim_hip_get_timing', 'prisim_hip_device_info', 'prisim_hip_set_tuning',
-    'prisim_hip_allgather_grad', 'prisim_hip_comm_selftest', 'prisim_hip_get_comm_stats', 'prisim_hip_set_gather_root', 'prisim_hip_set_shard_map', 'prisim_hip_device_pci', 'prisim_hip_comm_last_error',
-    'prisim_hip_host_alloc', 'prisim_hip_host_free', 'prisim_hip_get_vis_async', 'prisim_hip_wait_downloads',
-    'prisim_hip_set_catalog', 'prisim_hip_set_sky_from_catalog', 'prisim_hip_catalog_roi', 'prisim_hip_observe_catalog',
-    'prisim_hip_comm_version', 'prisim_hip_get_fold_info',
-)
-
-# every symbol include/prisim_clean.h declares: delay CLEAN (prisim_amd/csrc_clean/), linked into the same library
-CLEAN_EXPORTS = ('prisim_clean_rows', 'prisim_clean_delay')
+# delay CLEAN (include/prisim_clean.h, prisim_amd/csrc_clean/)
 PRISIM_CLEAN_MAX_LEN = 4096
 PRISIM_CLEAN_THRESHOLD, PRISIM_CLEAN_MAXITER, PRISIM_CLEAN_INRMS, PRISIM_CLEAN_NO_OUTRMS, PRISIM_CLEAN_BAD_THRESHOLD = 1, 2, 4, 8, 16
 
-# every symbol include/prisim_subband.h declares: sub-band delay spectra (prisim_amd/csrc_subband/), linked into the same library
-SUBBAND_EXPORTS = ('prisim_subband_transform',)
+# sub-band delay spectra (include/prisim_subband.h, prisim_amd/csrc_subband/)
 PRISIM_SUBBAND_MAX_LEN = 4096
 PRISIM_SUBBAND_OVER, PRISIM_SUBBAND_OVER_POWER, PRISIM_SUBBAND_RES, PRISIM_SUBBAND_RES_POWER = 1, 2, 4, 8
 PRISIM_SUBBAND_AUTO, PRISIM_SUBBAND_FUSED, PRISIM_SUBBAND_ROCFFT = -1, 0, 1
 SUBBAND_ROUTES = {PRISIM_SUBBAND_FUSED: 'fused', PRISIM_SUBBAND_ROCFFT: 'rocfft'}
 
-# every symbol include/prisim_runs.h declares: delay spectra and power spectra of runs (prisim_amd/csrc_runs/), linked into the same library
-RUNS_EXPORTS = ('prisim_runs_transform', 'prisim_runs_power')
+# delay spectra and power spectra of runs (include/prisim_runs.h, prisim_amd/csrc_runs/)
 PRISIM_RUNS_MAX_LEN = PRISIM_SUBBAND_MAX_LEN
 PRISIM_RUNS_ALL, PRISIM_RUNS_INTERP, PRISIM_RUNS_RESAMPLE = 1, 2, 3
 PRISIM_RUNS_AUTO, PRISIM_RUNS_FUSED, PRISIM_RUNS_ROCFFT, PRISIM_RUNS_DIRECT = -1, 0, 1, 2
 RUNS_ROUTES = {PRISIM_RUNS_FUSED: 'fused', PRISIM_RUNS_ROCFFT: 'rocfft', PRISIM_RUNS_DIRECT: 'direct'}
 RUNS_BUDGET = 1 << 30               # device bytes one call of the runs entries streams through by default
 
-# every symbol include/prisim_closure.h declares: closure phases of antenna triads (prisim_amd/csrc_closure/), linked into the same library
-CLOSURE_EXPORTS = ('prisim_closure_phase',)
+# closure phases of antenna triads (include/prisim_closure.h, prisim_amd/csrc_closure/)
 PRISIM_CLOSURE_MAX_LEN = PRISIM_SUBBAND_MAX_LEN
 PRISIM_CLOSURE_AUTO, PRISIM_CLOSURE_DIRECT, PRISIM_CLOSURE_FUSED, PRISIM_CLOSURE_ROCFFT = -1, 0, 1, 2
 CLOSURE_ROUTES = {PRISIM_CLOSURE_DIRECT: 'direct', PRISIM_CLOSURE_FUSED: 'fused', PRISIM_CLOSURE_ROCFFT: 'rocfft'}
 CLOSURE_BUDGET = 1 << 30            # device bytes the chunk buffers of one closure-phase call take by default
 
-# every symbol include/prisim_cpdelay.h declares: delay spectra of closure phases and their power spectra (prisim_amd/csrc_closure/cpdelay.hip)
-CPDELAY_EXPORTS = ('prisim_closure_delay_spectra', 'prisim_closure_power')
+# delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h, prisim_amd/csrc_closure/cpdelay.hip)
 PRISIM_CPDELAY_MAX_LEN = PRISIM_SUBBAND_MAX_LEN
 PRISIM_CPDELAY_OVER, PRISIM_CPDELAY_OVER_POWER, PRISIM_CPDELAY_RES, PRISIM_CPDELAY_RES_POWER = 1, 2, 4, 8
 PRISIM_CPDELAY_AUTO, PRISIM_CPDELAY_FUSED, PRISIM_CPDELAY_ROCFFT = -1, 0, 1
 CPDELAY_ROUTES = {PRISIM_CPDELAY_FUSED: 'fused', PRISIM_CPDELAY_ROCFFT: 'rocfft'}
 PRISIM_CPPOWER_INDIVIDUAL, PRISIM_CPPOWER_AUTO, PRISIM_CPPOWER_CROSS = 1, 2, 4
 
-# every symbol include/prisim_cpbins.h declares: day and LST binning of closure phases (prisim_amd/csrc_closure/cpbins.hip)
-CPBINS_EXPORTS = ('prisim_cphase_bin', 'prisim_cphase_stack_free')
+# day and LST binning of closure phases (include/prisim_cpbins.h, prisim_amd/csrc_closure/cpbins.hip)
 PRISIM_CPBINS_MAX_BIN = 256
 PRISIM_CPBINS_PHASE_FLAGS, PRISIM_CPBINS_BINNED = 0, 1
-CPBINS_WANT = {'wts': 1, 'eicp_mean': 2, 'eicp_median': 4, 'cp_mean': 8, 'cp_median': 16, 'rms': 32, 'mad': 64}
-PRISIM_CPBINS_ALL = 127
-# every symbol include/prisim_cpdiff.h declares: differences of day sub-samples of binned closure phases (prisim_amd/csrc_closure/cpdiff.hip)
-CPDIFF_EXPORTS = ('prisim_cphase_diff',)
+PRISIM_CPBINS_WTS, PRISIM_CPBINS_EICP_MEAN, PRISIM_CPBINS_EICP_MEDIAN, PRISIM_CPBINS_CP_MEAN = 1, 2, 4, 8
+PRISIM_CPBINS_CP_MEDIAN, PRISIM_CPBINS_RMS, PRISIM_CPBINS_MAD, PRISIM_CPBINS_ALL = 16, 32, 64, 127
+CPBINS_WANT = {'wts': PRISIM_CPBINS_WTS, 'eicp_mean': PRISIM_CPBINS_EICP_MEAN, 'eicp_median': PRISIM_CPBINS_EICP_MEDIAN,
+               'cp_mean': PRISIM_CPBINS_CP_MEAN, 'cp_median': PRISIM_CPBINS_CP_MEDIAN, 'rms': PRISIM_CPBINS_RMS, 'mad': PRISIM_CPBINS_MAD}
+
+# differences of day sub-samples of binned closure phases (include/prisim_cpdiff.h, prisim_amd/csrc_closure/cpdiff.hip)
 CPDIFF_OUTPUTS = ('diff0_mean', 'diff0_median', 'diff1_mean', 'diff1_median', 'wts0', 'wts1', 'mask0', 'mask1')
 PRISIM_CPDIFF_OUT_BYTES = 82
-# every symbol include/prisim_cpft.h declares: delay spectra of binned closure phasors (prisim_amd/csrc_closure/cpft.hip)
-CPFT_EXPORTS = ('prisim_cphase_ft',)
+
+# delay spectra of binned closure phasors (include/prisim_cpft.h, prisim_amd/csrc_closure/cpft.hip)
 PRISIM_CPFT_MAX_LEN, PRISIM_CPFT_MAX_IN = PRISIM_SUBBAND_MAX_LEN, 8
 PRISIM_CPFT_OVER, PRISIM_CPFT_RES, PRISIM_CPFT_LAG = 1, 2, 4
 PRISIM_CPFT_AUTO, PRISIM_CPFT_FUSED, PRISIM_CPFT_ROCFFT = -1, 0, 1
 CPFT_ROUTES = {PRISIM_CPFT_FUSED: 'fused', PRISIM_CPFT_ROCFFT: 'rocfft'}
-# every symbol include/prisim_cpxps.h declares: cross power of closure-phase delay spectra (prisim_amd/csrc_closure/cpxps.hip)
-CPXPS_EXPORTS = ('prisim_cphase_xpower',)
+
+# cross power of closure-phase delay spectra (include/prisim_cpxps.h, prisim_amd/csrc_closure/cpxps.hip)
 PRISIM_CPXPS_MAX_MEDIAN = 256
-CPXPS_MODES = {'none': 0, 'full': 1, 'collapse': 2}
-CPXPS_STATS = {'mean': 0, 'median': 1}
-# every symbol include/prisim_cpavg.h declares: incoherent averages of closure-phase power spectra (prisim_amd/csrc_closure/cpavg.hip)
-CPAVG_EXPORTS = ('prisim_cphase_xavg', 'prisim_cphase_kbin')
+PRISIM_CPXPS_NONE, PRISIM_CPXPS_FULL, PRISIM_CPXPS_COLLAPSE = 0, 1, 2
+PRISIM_CPXPS_MEAN, PRISIM_CPXPS_MEDIAN = 0, 1
+CPXPS_MODES = {'none': PRISIM_CPXPS_NONE, 'full': PRISIM_CPXPS_FULL, 'collapse': PRISIM_CPXPS_COLLAPSE}
+CPXPS_STATS = {'mean': PRISIM_CPXPS_MEAN, 'median': PRISIM_CPXPS_MEDIAN}
+
+# incoherent averages of closure-phase power spectra (include/prisim_cpavg.h, prisim_amd/csrc_closure/cpavg.hip)
 PRISIM_CPAVG_MIN_DIM, PRISIM_CPAVG_MAX_DIM = 5, 8
 PRISIM_CPAVG_AUTO, PRISIM_CPAVG_LDS, PRISIM_CPAVG_GLOBAL = -1, 0, 1
 CPAVG_ROUTES = {PRISIM_CPAVG_LDS: 'lds', PRISIM_CPAVG_GLOBAL: 'global'}
-# every symbol include/prisim_cpreal.h declares: closure phases of noise realisations (prisim_amd/csrc_closure/cpreal.hip)
-CPREAL_EXPORTS = ('prisim_closure_realizations',)
+
+# closure phases of noise realisations (include/prisim_cpreal.h, prisim_amd/csrc_closure/cpreal.hip)
 PRISIM_CPREAL_AUTO, PRISIM_CPREAL_DIRECT, PRISIM_CPREAL_STAGED = -1, 0, 1
+PRISIM_CPREAL_NOISY, PRISIM_CPREAL_NOISE = 0, 1
 CPREAL_ROUTES = {PRISIM_CPREAL_DIRECT: 'direct', PRISIM_CPREAL_STAGED: 'staged'}
-CPREAL_KINDS = {'noisy': 0, 'noise': 1}
-# every symbol include/prisim_antpower.h declares: beam-weighted sky power per snapshot (prisim_amd/csrc_antpower/antpower.hip)
-ANTPOWER_EXPORTS = ('prisim_antenna_power',)
-# every symbol include/prisim_imaging.h declares: dirty images and synthesized beams by the direct Fourier sum (prisim_amd/csrc_imaging/imaging.hip)
-IMAGING_EXPORTS = ('prisim_dirty_image',)
+CPREAL_KINDS = {'noisy': PRISIM_CPREAL_NOISY, 'noise': PRISIM_CPREAL_NOISE}
+
+# dirty images and synthesized beams by the direct Fourier sum (include/prisim_imaging.h, prisim_amd/csrc_imaging/imaging.hip)
 PRISIM_IMAGE_DIRTY, PRISIM_IMAGE_PSF = 0, 1
 PRISIM_IMAGE_AUTO, PRISIM_IMAGE_DIRECT, PRISIM_IMAGE_STEPPED = -1, 0, 1
 PRISIM_IMAGE_W_NONE, PRISIM_IMAGE_W_BASELINE, PRISIM_IMAGE_W_FULL = 0, 1, 2
 IMAGING_ROUTES = {PRISIM_IMAGE_DIRECT: 'direct', PRISIM_IMAGE_STEPPED: 'stepped'}
 IMAGING_KINDS = {'dirty': PRISIM_IMAGE_DIRTY, 'psf': PRISIM_IMAGE_PSF}
 
-# every symbol include/prisim_gains.h declares: instrument gain tables (prisim_amd/csrc_gains/), linked into the same library
-GAINS_EXPORTS = ('prisim_gains_eval_spline', 'prisim_gains_gather', 'prisim_gains_table_shape', 'prisim_gains_table_get',
-                 'prisim_gains_table_free', 'prisim_gains_apply')
+# instrument gain tables (include/prisim_gains.h, prisim_amd/csrc_gains/)
 PRISIM_GAINS_MAX_DEGREE = 5
 PRISIM_GAINS_ANTENNA, PRISIM_GAINS_BASELINE = 0, 1
 
@@ -282,29 +263,26 @@ class PrisimCpftStats(C.Structure):
 
 class _PrisimCpxpsStats(C.Structure):
     """prisim_cpxps_stats, public as Context.PrisimCpxpsStats: tests/test_abi_helpers.py pins the Prisim*Stats names of this module's
-    namespace, and tests/test_cpxps.py holds this struct to the same rules."""
+    namespace; like every mirror it is listed in STRUCTS, which tests/test_abi_headers.py holds to the headers."""
     _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('chunks', C.c_int64), ('chunk_lags', C.c_int64),
                 ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('cross_bytes', C.c_int64)]
 
 
 class _PrisimCpavgStats(C.Structure):
-    """prisim_cpavg_stats of both entries of include/prisim_cpavg.h, public as Context.PrisimCpavgStats (see _PrisimCpxpsStats);
-    tests/test_cpavg.py holds it to the header."""
+    """prisim_cpavg_stats of both entries of include/prisim_cpavg.h, public as Context.PrisimCpavgStats (see _PrisimCpxpsStats)."""
     _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('chunks', C.c_int64), ('kernel_bytes', C.c_int64),
                 ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('route', C.c_int32), ('lds_limit', C.c_int32)]
 
 
 class _PrisimCprealStats(C.Structure):
-    """prisim_cpreal_stats of include/prisim_cpreal.h, public as Context.PrisimCprealStats (see _PrisimCpxpsStats); tests/test_cpreal.py
-    holds it to the header."""
+    """prisim_cpreal_stats of include/prisim_cpreal.h, public as Context.PrisimCprealStats (see _PrisimCpxpsStats)."""
     _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('pairs', C.c_int64), ('chunks', C.c_int64),
                 ('chunk_pairs', C.c_int64), ('draws', C.c_int64), ('kernel_bytes', C.c_int64), ('download_bytes', C.c_int64),
                 ('route', C.c_int32), ('streams', C.c_int32), ('chan_tile', C.c_int32), ('lds_bytes', C.c_int32)]
 
 
 class _PrisimAntpowerStats(C.Structure):
-    """prisim_antpower_stats of include/prisim_antpower.h, public as Context.PrisimAntpowerStats (see _PrisimCpxpsStats);
-    tests/test_antpower.py holds it to the header."""
+    """prisim_antpower_stats of include/prisim_antpower.h, public as Context.PrisimAntpowerStats (see _PrisimCpxpsStats)."""
     _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('sources_evaluated', C.c_int64), ('sources_up', C.c_int64),
                 ('spans', C.c_int64), ('span_sources', C.c_int64), ('block_sources', C.c_int64), ('kernel_bytes', C.c_int64),
                 ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('streams', C.c_int32), ('chan_tile', C.c_int32),
@@ -321,8 +299,7 @@ class _PrisimAntpowerArgs(C.Structure):
 
 
 class _PrisimImagingStats(C.Structure):
-    """prisim_imaging_stats of include/prisim_imaging.h, public as Context.PrisimImagingStats (see _PrisimCpxpsStats);
-    tests/test_imaging.py holds it to the header."""
+    """prisim_imaging_stats of include/prisim_imaging.h, public as Context.PrisimImagingStats (see _PrisimCpxpsStats)."""
     _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('terms', C.c_int64), ('chunks', C.c_int64), ('chunk_pixels', C.c_int64),
                 ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('route', C.c_int32),
                 ('streams', C.c_int32), ('chan_tile', C.c_int32), ('reseed', C.c_int32), ('lds_bytes', C.c_int32), ('block_pixels', C.c_int32)]
@@ -407,6 +384,185 @@ def _route_code(name, routes):
     return -1 if name == 'auto' else {v: k for k, v in routes.items()}[name]
 
 
+# every struct the headers typedef -> its ctypes mirror
+STRUCTS = {
+    'prisim_sky': PrisimSky, 'prisim_beam_ext': PrisimBeamExt, 'prisim_beam_sky': PrisimBeamSky, 'prisim_catalog': PrisimCatalog,
+    'prisim_obs': PrisimObs, 'prisim_snapshot': PrisimSnapshot, 'prisim_post': PrisimPost, 'prisim_timing': PrisimTiming,
+    'prisim_comm_stats': PrisimCommStats, 'prisim_clean_stats': PrisimCleanStats, 'prisim_subband_stats': PrisimSubbandStats,
+    'prisim_runs_stats': PrisimRunsStats, 'prisim_closure_stats': PrisimClosureStats, 'prisim_cpdelay_stats': PrisimCpdelayStats,
+    'prisim_cpbins_stats': PrisimCpbinsStats, 'prisim_cpdiff_stats': PrisimCpdiffStats, 'prisim_cpft_stats': PrisimCpftStats,
+    'prisim_cpxps_stats': _PrisimCpxpsStats, 'prisim_cpavg_stats': _PrisimCpavgStats, 'prisim_cpreal_stats': _PrisimCprealStats,
+    'prisim_antpower_stats': _PrisimAntpowerStats, 'prisim_antpower_args': _PrisimAntpowerArgs,
+    'prisim_imaging_stats': _PrisimImagingStats, 'prisim_imaging_args': _PrisimImagingArgs, 'prisim_gains_stats': PrisimGainsStats,
+}
+
+# The C ABI, declared once: per header of include/, its functions in the header's order, each as
+#   <return> <function>(<class> <parameter name>, ...);
+# with the header's parameter names.  Return: int (an error code), void, or str (const char*).  Classes: p pointer (void*, arrays and
+# opaque handles), i int32, q int64, Q uint64, d double, s char*; *<struct> a pointer to a mirrored struct of STRUCTS, *<class> a
+# pointer to one such scalar (an output).  tests/test_abi_headers.py holds every row to the text of its header.
+_PROTOTYPES = {
+    'prisim_hip.h': '''
+        int prisim_hip_create(i device, *p out);
+        void prisim_hip_destroy(p ctx);
+        str prisim_hip_last_error(p ctx);
+        str prisim_hip_version();
+        int prisim_hip_set_array(p ctx, p bl_enu, q nbl, p freqs_hz, q nchan, q nt_max);
+        int prisim_hip_set_sky(p ctx, *prisim_sky sky);
+        int prisim_hip_compute(p ctx, i precision, i kernel, i want_grad, q slot);
+        int prisim_hip_get_vis(p ctx, q slot, p vis, p grad, i out_is_c64);
+        int prisim_hip_set_vis(p ctx, q slot, p vis);
+        int prisim_hip_skyvis(p ctx, *prisim_sky sky, i precision, i kernel, p vis, p grad, i out_is_c64);
+        int prisim_hip_set_sky_analytic(p ctx, *prisim_beam_sky sky);
+        int prisim_hip_set_external_beam(p ctx, p beam, q npix, q nfreq, p interp_matrix);
+        int prisim_hip_set_sky_external(p ctx, *prisim_sky sky);
+        int prisim_hip_set_sky_external_analytic(p ctx, *prisim_beam_sky sky);
+        int prisim_hip_get_pbflux(p ctx, p out);
+        int prisim_hip_set_catalog(p ctx, *prisim_catalog cat);
+        int prisim_hip_set_sky_from_catalog(p ctx, *prisim_obs obs, *prisim_snapshot snap, *q nsrc_roi);
+        int prisim_hip_catalog_roi(p ctx, *prisim_obs obs, *prisim_snapshot snap, *q nsrc_roi, p indices, p dircos, q cap);
+        int prisim_hip_observe_catalog(p ctx, *prisim_obs obs, *prisim_snapshot snaps, q nsnap, i precision, i want_grad, q slot0, p nsrc_roi,
+            *prisim_post post);
+        int prisim_hip_delay_transform(p ctx, q nt, p bpwts, d pad, p out, p lags_out, p out_power, d power_scale);
+        int prisim_hip_delay_transform_device(p ctx, q nt, p bpwts, q wts_rows, d pad, i want_lag, i want_power, d power_scale, p lags_out,
+            *q nout_out);
+        int prisim_hip_get_lags(p ctx, q t0, q nt, p rows, q nrows, p out);
+        int prisim_hip_get_delay_power(p ctx, q t0, q nt, p rows, q nrows, p out);
+        int prisim_hip_phase_rotate(p ctx, q nt, p diff_dircos);
+        int prisim_hip_noise(p ctx, q nt, p rms, Q seed, q bl_offset, p out);
+        int prisim_hip_noise_indexed(p ctx, q nt, p rms, Q seed, p bl_index, p out);
+        int prisim_hip_comm_unique_id(s id);
+        int prisim_hip_comm_version(s out);
+        int prisim_hip_comm_init(p ctx, s id, i nranks, i rank);
+        int prisim_hip_device_pci(i device, s out);
+        int prisim_hip_comm_last_error(s out);
+        int prisim_hip_allgather(p ctx, q nt, i as_c64);
+        int prisim_hip_allgather_slot_async(p ctx, q slot, i as_c64);
+        int prisim_hip_get_gathered(p ctx, q nt, p out);
+        int prisim_hip_allgather_lags(p ctx, q nt);
+        int prisim_hip_gathered_checksum(p ctx, q nt, *d out);
+        int prisim_hip_allgather_grad(p ctx, q nt, i as_c64);
+        int prisim_hip_set_shard_map(p ctx, p bl_index, q nbl_total);
+        int prisim_hip_set_gather_root(p ctx, i root);
+        int prisim_hip_comm_selftest(p ctx, q bytes);
+        int prisim_hip_get_comm_stats(p ctx, *prisim_comm_stats out, i reset);
+        int prisim_hip_host_alloc(q bytes, *p out);
+        int prisim_hip_host_free(p p);
+        int prisim_hip_get_vis_async(p ctx, q slot, p vis, p grad, i out_is_c64);
+        int prisim_hip_wait_downloads(p ctx);
+        int prisim_hip_sync(p ctx);
+        int prisim_hip_get_timing(p ctx, *prisim_timing out, i reset);
+        int prisim_hip_get_fold_info(p ctx, *q last_sum_baselines, *q last_terms_evaluated, *q last_sum_lift_groups);
+        int prisim_hip_device_info(p ctx, *i cu_count, *i clock_khz, s name);
+        int prisim_hip_set_tuning(p ctx, i chan_tile, i src_chunk, i nsplit);
+    ''',
+    'prisim_clean.h': '''
+        int prisim_clean_rows(p ctx, q nrows, q m, p inp, q nkern, p kern, p kidx, p cbox, d gain, q maxiter, d threshold, i threshold_absolute,
+            p cc, p res, p iters, p flags, p rms, *prisim_clean_stats stats);
+        int prisim_clean_delay(p ctx, i ncubes, q nrows, q nchan, q m, p win, q nkern, p kwin, p kidx, p cbox, d lag_scale, d freq_scale1,
+            d freq_scale2, d gain, q maxiter, d threshold, i threshold_absolute, p lag, p kern_lag, p cc, p res, p cc_freq, p res_freq, p iters,
+            p flags, p rms, *prisim_clean_stats stats);
+    ''',
+    'prisim_subband.h': '''
+        int prisim_subband_transform(p ctx, i ncubes, q nt, q nbl, q nchan, p cubes, q t0, p bp, q nbp, i nwin, p wts, q m, d df, q nres, q nmap,
+            p map_out, p map_in, p map_w, p pscale, i want, i route, p over, p over_pow, p res, p res_pow, *prisim_subband_stats stats);
+    ''',
+    'prisim_runs.h': '''
+        int prisim_runs_transform(p ctx, q R, q nbl, q nchan, q nt, p vis, i vis_is_c64, p bp, p bp_strides, p wts, p wts_strides, i nwin, p win,
+            q m, d scale, i out_mode, q nout, d factor, q nmap, p map_out, p map_in, p map_w, i route, q budget_bytes, p out,
+            *prisim_runs_stats stats);
+        int prisim_runs_power(p ctx, q nf, q inner, p v1, p v2, i is_c64, p factor, i cross, i fused_product, q budget_bytes, p out,
+            *prisim_runs_stats stats);
+    ''',
+    'prisim_closure.h': '''
+        int prisim_closure_phase(p ctx, p cube, q nt, q nbl, q nchan, p legs, p conj, q ntriads, p freq_wts, p bpwts, p masks, q nmask,
+            p mask_index, i route, q budget_bytes, p out_triplets, p out_phase, *prisim_closure_stats stats);
+    ''',
+    'prisim_cpdelay.h': '''
+        int prisim_closure_delay_spectra(p ctx, p phases, q nrows, p cube, q nt, q nbl, q nchan, p legs, p conj, p freq_wts, p bpwts, p masks,
+            q nmask, p mask_index, i phase_route, i nwin, p wts, q m, d df, q nres, q nmap, p map_out, p map_in, p map_w, p pscale, i want,
+            i route, q budget_bytes, p out_phase, p over, p over_pow, p res, p res_pow, *prisim_cpdelay_stats stats);
+        int prisim_closure_power(p ctx, q n0, q nwin, q inner, p spectra, p scale, i want, q budget_bytes, p out_individual, p out_auto,
+            p out_cross, *prisim_cpdelay_stats stats);
+    ''',
+    'prisim_cpbins.h': '''
+        int prisim_cphase_bin(p ctx, i kind, p in_mean, p in_median, p in_wts, p in_flags, q n0, q n1, q ntriads, q nchan, i axis, q nbins,
+            p offsets, p members, i want, i mad_ignores_flags, q budget_bytes, *p resident_in, *p keep_out, p out_wts, p out_eicp_mean,
+            p out_eicp_median, p out_cp_mean, p out_cp_median, p out_rms, p out_mad, *prisim_cpbins_stats stats);
+        void prisim_cphase_stack_free(p stack);
+    ''',
+    'prisim_cpdiff.h': '''
+        int prisim_cphase_diff(p ctx, p in_mean, p in_median, p in_wts, q n0, q n1, q ntriads, q nchan, p resident, q ncomb, p pairs,
+            q budget_bytes, p out_diff0_mean, p out_diff0_median, p out_diff1_mean, p out_diff1_median, p out_wts0, p out_wts1, p out_mask0,
+            p out_mask1, *prisim_cpdiff_stats stats);
+    ''',
+    'prisim_cpft.h': '''
+        int prisim_cphase_ft(p ctx, q n0, q n1, q n2, q nchan, i nin, p inputs, p in_shape, p w, i nwin, p wts, p vscale, q m, d df, q nres,
+            q nmap, p map_out, p map_in, p map_w, i want, i route, q budget_bytes, p over, p res, p lag_kernel, p lag_kernel_res,
+            *prisim_cpft_stats stats);
+    ''',
+    'prisim_cpxps.h': '''
+        int prisim_cphase_xpower(p ctx, q nspw, q n1, q n2, q n3, q nlags, p a, p b, p factor, p weights, p modes, q nshift, p shifts,
+            i ncollapse, p order, i stat, q budget_bytes, p out, *prisim_cpxps_stats stats);
+    ''',
+    'prisim_cpavg.h': '''
+        int prisim_cphase_xavg(p ctx, i ndim, p shape, q nsets, p arrays, p weights, p wshapes, i ncombo, p reduce, p masks, q budget_bytes,
+            p avg, p wsum, p out, p wout, *prisim_cpavg_stats stats);
+        int prisim_cphase_kbin(p ctx, q nspw, q m, q nlags, q nk, p p, p kprll, p offsets, p members, i route, q budget_bytes, p ps, p del2, p kc,
+            *prisim_cpavg_stats stats);
+    ''',
+    'prisim_cpreal.h': '''
+        int prisim_closure_realizations(p ctx, p cube, p cube_row, p bl_global, q nt, q nrow, q nchan, p rms, p bpwts, p legs, p conj, q ntriads,
+            Q seed, q first, q n_realize, i kind, i route, q budget_bytes, p out_phase, *prisim_cpreal_stats stats);
+    ''',
+    'prisim_antpower.h': '''
+        int prisim_antenna_power(p ctx, *prisim_antpower_args a, p out_power, p out_num, p out_den, *prisim_antpower_stats stats);
+    ''',
+    'prisim_imaging.h': '''
+        int prisim_dirty_image(p ctx, *prisim_imaging_args a, p out_image, p out_wsum, *prisim_imaging_stats stats);
+    ''',
+    'prisim_gains.h': '''
+        int prisim_gains_eval_spline(p ctx, q nrows, i kx, i ky, p nx, p ny, p kx_off, p ky_off, p c_off, q nknots, p knots, q ncoefs, p coefs,
+            q nt, p times, q nchan, p freqs, *p out, *prisim_gains_stats stats);
+        int prisim_gains_gather(p ctx, q nrows, q ngf, q ngt, p gains, q nchan, p fidx, q nt, p tidx, *p out, *prisim_gains_stats stats);
+        int prisim_gains_table_shape(p tab, *q nt, *q nrows, *q nchan);
+        int prisim_gains_table_get(p ctx, p tab, p out);
+        void prisim_gains_table_free(p tab);
+        int prisim_gains_apply(p ctx, q nt, q nbl, q nchan, p ta, i mode_a, p a_a, p c_a, p tb, i mode_b, p a_b, p c_b, p sky, q t0, i sky_c64,
+            p noise, i want_gain, p vis, *prisim_gains_stats stats);
+    ''',
+}
+_CLASSES = {'p': C.c_void_p, 'i': C.c_int32, 'q': C.c_int64, 'Q': C.c_uint64, 'd': C.c_double, 's': C.c_char_p}
+_RETURNS = {'int': C.c_int, 'void': None, 'str': C.c_char_p}
+
+
+def _parse_prototypes(table):
+    """(FUNCTIONS, HEADER_EXPORTS) of a table like _PROTOTYPES: function -> (restype, ((parameter name, ctypes class), ...)), and
+    header -> the names of its functions in order."""
+    functions, exports = {}, {}
+    for header, text in table.items():
+        names = []
+        for row in text.split(';')[:-1]:
+            ret, name, params = re.match(r'\s*(\w+) (\w+)\((.*)\)$', row, flags=re.S).groups()
+            pairs = []
+            for code, pname in (p.split() for p in params.split(',') if p.strip()):
+                inner = code.lstrip('*')
+                ctype = STRUCTS[inner] if inner in STRUCTS else _CLASSES[inner]
+                pairs.append((pname, C.POINTER(ctype) if code.startswith('*') else ctype))
+            functions[name] = (_RETURNS[ret], tuple(pairs))
+            names.append(name)
+        exports[header] = tuple(names)
+    return functions, exports
+
+
+FUNCTIONS, HEADER_EXPORTS = _parse_prototypes(_PROTOTYPES)
+# the functions of each header (tests and tools import these names)
+(EXPORTS, CLEAN_EXPORTS, SUBBAND_EXPORTS, RUNS_EXPORTS, CLOSURE_EXPORTS, CPDELAY_EXPORTS, CPBINS_EXPORTS, CPDIFF_EXPORTS, CPFT_EXPORTS,
+ CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, GAINS_EXPORTS) = (
+    HEADER_EXPORTS['prisim_%s.h' % h] for h in ('hip', 'clean', 'subband', 'runs', 'closure', 'cpdelay', 'cpbins', 'cpdiff', 'cpft', 'cpxps',
+                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'gains'))
+
+
 class PrisimHipError(RuntimeError):
     """Raised when libprisim_hip.so is missing/unloadable or no GPU is usable."""
 
@@ -426,137 +582,47 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
     except OSError as exc:
         raise PrisimHipError('cannot load {0}: {1}'.format(LIB_PATH, exc))
-    vp, i64, i32, dbl = C.c_void_p, C.c_int64, C.c_int, C.c_double
-    lib.prisim_hip_create.argtypes = [i32, C.POINTER(vp)]
-    lib.prisim_hip_destroy.argtypes = [vp]
-    lib.prisim_hip_destroy.restype = None
-    lib.prisim_hip_last_error.argtypes = [vp]
-    lib.prisim_hip_last_error.restype = C.c_char_p
-    lib.prisim_hip_version.argtypes = []
-    lib.prisim_hip_version.restype = C.c_char_p
+    lib.prisim_hip_version.restype, lib.prisim_hip_version.argtypes = C.c_char_p, []
     have = (lib.prisim_hip_version() or b'').decode()
     if have != ABI_VERSION:
         # a library of another round next to this binding: the structs below (prisim_timing, prisim_beam_sky ...) would be read wrongly
         raise PrisimHipError('{0} reports {1!r}, this binding is written for {2!r}: rebuild it (python -c "import __graft_entry__ as g; '
                              'g.build()")'.format(LIB_PATH, have, ABI_VERSION))
-    lib.prisim_hip_set_array.argtypes = [vp, vp, i64, vp, i64, i64]
-    lib.prisim_hip_set_sky.argtypes = [vp, C.POINTER(PrisimSky)]
-    lib.prisim_hip_compute.argtypes = [vp, i32, i32, i32, i64]
-    lib.prisim_hip_get_vis.argtypes = [vp, i64, vp, vp, i32]
-    lib.prisim_hip_set_vis.argtypes = [vp, i64, vp]
-    lib.prisim_hip_skyvis.argtypes = [vp, C.POINTER(PrisimSky), i32, i32, vp, vp, i32]
-    lib.prisim_hip_set_sky_analytic.argtypes = [vp, C.POINTER(PrisimBeamSky)]
-    lib.prisim_hip_set_external_beam.argtypes = [vp, vp, i64, i64, vp]
-    lib.prisim_hip_set_sky_external.argtypes = [vp, C.POINTER(PrisimSky)]
-    lib.prisim_hip_set_sky_external_analytic.argtypes = [vp, C.POINTER(PrisimBeamSky)]
-    lib.prisim_hip_get_pbflux.argtypes = [vp, vp]
-    lib.prisim_hip_delay_transform.argtypes = [vp, i64, vp, dbl, vp, vp, vp, dbl]
-    lib.prisim_hip_delay_transform_device.argtypes = [vp, i64, vp, i64, dbl, i32, i32, dbl, vp, C.POINTER(i64)]
-    lib.prisim_hip_get_lags.argtypes = [vp, i64, i64, vp, i64, vp]
-    lib.prisim_hip_get_delay_power.argtypes = [vp, i64, i64, vp, i64, vp]
-    lib.prisim_hip_allgather_lags.argtypes = [vp, i64]
-    lib.prisim_hip_phase_rotate.argtypes = [vp, i64, vp]
-    lib.prisim_hip_noise.argtypes = [vp, i64, vp, C.c_uint64, i64, vp]
-    lib.prisim_hip_noise_indexed.argtypes = [vp, i64, vp, C.c_uint64, vp, vp]
-    lib.prisim_hip_comm_unique_id.argtypes = [C.c_char_p]
-    lib.prisim_hip_comm_init.argtypes = [vp, C.c_char_p, i32, i32]
-    lib.prisim_hip_comm_version.argtypes = [C.c_char_p]
-    lib.prisim_hip_allgather.argtypes = [vp, i64, i32]
-    lib.prisim_hip_allgather_slot_async.argtypes = [vp, i64, i32]
-    lib.prisim_hip_get_gathered.argtypes = [vp, i64, vp]
-    lib.prisim_hip_gathered_checksum.argtypes = [vp, i64, C.POINTER(dbl)]
-    lib.prisim_hip_sync.argtypes = [vp]
-    lib.prisim_hip_get_timing.argtypes = [vp, C.POINTER(PrisimTiming), i32]
-    lib.prisim_hip_device_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.c_char_p]
-    lib.prisim_hip_set_tuning.argtypes = [vp, i32, i32, i32]
-    lib.prisim_hip_get_fold_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    lib.prisim_hip_allgather_grad.argtypes = [vp, i64, i32]
-    lib.prisim_hip_comm_selftest.argtypes = [vp, i64]
-    lib.prisim_hip_set_gather_root.argtypes = [vp, i32]
-    lib.prisim_hip_set_shard_map.argtypes = [vp, vp, i64]
-    lib.prisim_hip_device_pci.argtypes = [i32, C.c_char_p]
-    lib.prisim_hip_comm_last_error.argtypes = [C.c_char_p]
-    lib.prisim_hip_get_comm_stats.argtypes = [vp, C.POINTER(PrisimCommStats), i32]
-    lib.prisim_hip_host_alloc.argtypes = [i64, C.POINTER(vp)]
-    lib.prisim_hip_host_free.argtypes = [vp]
-    lib.prisim_hip_get_vis_async.argtypes = [vp, i64, vp, vp, i32]
-    lib.prisim_hip_wait_downloads.argtypes = [vp]
-    lib.prisim_hip_set_catalog.argtypes = [vp, C.POINTER(PrisimCatalog)]
-    lib.prisim_hip_set_sky_from_catalog.argtypes = [vp, C.POINTER(PrisimObs), C.POINTER(PrisimSnapshot), C.POINTER(i64)]
-    lib.prisim_hip_catalog_roi.argtypes = [vp, C.POINTER(PrisimObs), C.POINTER(PrisimSnapshot), C.POINTER(i64), vp, vp, i64]
-    lib.prisim_hip_observe_catalog.argtypes = [vp, C.POINTER(PrisimObs), C.POINTER(PrisimSnapshot), i64, i32, i32, i64, vp, C.POINTER(PrisimPost)]
-    lib.prisim_clean_rows.argtypes = [vp, i64, i64, vp, i64, vp, vp, vp, dbl, i64, dbl, C.c_int32, vp, vp, vp, vp, vp,
-                                      C.POINTER(PrisimCleanStats)]
-    lib.prisim_clean_delay.argtypes = [vp, C.c_int32, i64, i64, i64, vp, i64, vp, vp, vp, dbl, dbl, dbl, dbl, i64, dbl, C.c_int32, vp, vp,
-                                       vp, vp, vp, vp, vp, vp, vp, C.POINTER(PrisimCleanStats)]
-    for name in CLEAN_EXPORTS:
-        getattr(lib, name).restype = C.c_int
-    lib.prisim_subband_transform.argtypes = [vp, C.c_int32, i64, i64, i64, vp, i64, vp, i64, C.c_int32, vp, i64, dbl, i64, i64, vp, vp, vp,
-                                             vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.POINTER(PrisimSubbandStats)]
-    lib.prisim_subband_transform.restype = C.c_int
-    lib.prisim_runs_transform.argtypes = [vp, i64, i64, i64, i64, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, i64, dbl, C.c_int32, i64,
-                                          dbl, i64, vp, vp, vp, C.c_int32, i64, vp, C.POINTER(PrisimRunsStats)]
-    lib.prisim_runs_power.argtypes = [vp, i64, i64, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, i64, vp, C.POINTER(PrisimRunsStats)]
-    for name in RUNS_EXPORTS:
-        getattr(lib, name).restype = C.c_int
-    lib.prisim_closure_phase.argtypes = [vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, i64, vp, C.c_int32, i64, vp, vp,
-                                         C.POINTER(PrisimClosureStats)]
-    for name in CLOSURE_EXPORTS:
-        getattr(lib, name).restype = C.c_int
-    lib.prisim_closure_delay_spectra.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, C.c_int32, C.c_int32, vp, i64,
-                                                 dbl, i64, i64, vp, vp, vp, vp, C.c_int32, C.c_int32, i64, vp, vp, vp, vp, vp,
-                                                 C.POINTER(PrisimCpdelayStats)]
-    lib.prisim_closure_power.argtypes = [vp, i64, i64, i64, vp, vp, C.c_int32, i64, vp, vp, vp, C.POINTER(PrisimCpdelayStats)]
-    for name in CPDELAY_EXPORTS:
-        getattr(lib, name).restype = C.c_int
-    lib.prisim_cphase_bin.argtypes = [vp, C.c_int32, vp, vp, vp, vp, i64, i64, i64, i64, C.c_int32, i64, vp, vp, C.c_int32, C.c_int32, i64,
-                                      C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, vp, vp, vp, C.POINTER(PrisimCpbinsStats)]
-    lib.prisim_cphase_bin.restype = C.c_int
-    lib.prisim_cphase_stack_free.argtypes = [vp]
-    lib.prisim_cphase_stack_free.restype = None
-    lib.prisim_cphase_diff.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
-                                       C.POINTER(PrisimCpdiffStats)]
-    lib.prisim_cphase_diff.restype = C.c_int
-    lib.prisim_cphase_ft.argtypes = [vp, i64, i64, i64, i64, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, i64, dbl, i64, i64, vp, vp, vp, C.c_int32,
-                                     C.c_int32, i64, vp, vp, vp, vp, C.POINTER(PrisimCpftStats)]
-    lib.prisim_cphase_ft.restype = C.c_int
-    lib.prisim_cphase_xpower.argtypes = [vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, C.c_int32, vp, C.c_int32, i64, vp,
-                                         C.POINTER(_PrisimCpxpsStats)]
-    lib.prisim_cphase_xpower.restype = C.c_int
-    lib.prisim_cphase_xavg.argtypes = [vp, C.c_int32, vp, i64, vp, vp, vp, C.c_int32, vp, vp, i64, vp, vp, vp, vp, C.POINTER(_PrisimCpavgStats)]
-    lib.prisim_cphase_kbin.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, C.c_int32, i64, vp, vp, vp, C.POINTER(_PrisimCpavgStats)]
-    for name in CPAVG_EXPORTS:
-        getattr(lib, name).restype = C.c_int
-    lib.prisim_closure_realizations.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, i64, C.c_uint64, i64, i64, C.c_int32, C.c_int32,
-                                                i64, vp, C.POINTER(_PrisimCprealStats)]
-    lib.prisim_closure_realizations.restype = C.c_int
-    lib.prisim_antenna_power.argtypes = [vp, C.POINTER(_PrisimAntpowerArgs), vp, vp, vp, C.POINTER(_PrisimAntpowerStats)]
-    lib.prisim_antenna_power.restype = C.c_int
-    lib.prisim_dirty_image.argtypes = [vp, C.POINTER(_PrisimImagingArgs), vp, vp, C.POINTER(_PrisimImagingStats)]
-    lib.prisim_dirty_image.restype = C.c_int
-    pst = C.POINTER(PrisimGainsStats)
-    lib.prisim_gains_eval_spline.argtypes = [vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
-                                             C.POINTER(vp), pst]
-    lib.prisim_gains_gather.argtypes = [vp, i64, i64, i64, vp, i64, vp, i64, vp, C.POINTER(vp), pst]
-    lib.prisim_gains_table_shape.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    lib.prisim_gains_table_get.argtypes = [vp, vp, vp]
-    lib.prisim_gains_table_free.argtypes = [vp]
-    lib.prisim_gains_table_free.restype = None
-    lib.prisim_gains_apply.argtypes = [vp, i64, i64, i64, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, i64, C.c_int32, vp, C.c_int32,
-                                       vp, pst]
-    for name in GAINS_EXPORTS:
-        if name != 'prisim_gains_table_free':
-            getattr(lib, name).restype = C.c_int
-    for name in EXPORTS:
+    for name, (restype, params) in FUNCTIONS.items():
         fn = getattr(lib, name)
-        if name not in ('prisim_hip_destroy', 'prisim_hip_last_error', 'prisim_hip_version'):
-            fn.restype = C.c_int
+        fn.restype, fn.argtypes = restype, [ctype for _, ctype in params]
     _lib = lib
     return lib
 
 
 def _ptr(arr):
     return None if arr is None else arr.ctypes.data_as(C.c_void_p)
+
+
+def _call_declared(fn, name, params, kw):
+    """fn(*args), the arguments taken by name from kw, put into the declared order params ((name, class), ...) and marshalled by
+    class.  Integers go through int(), doubles through float().  To a pointer class, None is NULL; a numpy array goes as its data
+    pointer and must be C-contiguous (ValueError); a ctypes struct, or an instance of the class a scalar pointer points to, goes by
+    reference; any other ctypes object (a handle, an array of pointers) as it is.  TypeError, before anything is called, when kw
+    lacks a declared name or holds another."""
+    if len(kw) != len(params) or any(pname not in kw for pname, _ in params):
+        declared = set(pname for pname, _ in params)
+        raise TypeError('{0}: missing {1}, unknown {2}'.format(name, sorted(declared - set(kw)), sorted(set(kw) - declared)))
+    args = []
+    for pname, ctype in params:
+        v = kw[pname]
+        if ctype in (C.c_int32, C.c_int64, C.c_uint64):
+            v = int(v)
+        elif ctype is C.c_double:
+            v = float(v)
+        elif isinstance(v, NP.ndarray):
+            if not v.flags.c_contiguous:
+                raise ValueError('{0}: {1} must be a C-contiguous array'.format(name, pname))
+            v = v.ctypes.data
+        elif isinstance(v, C.Structure) or (ctype not in (C.c_void_p, C.c_char_p) and isinstance(v, ctype._type_)):
+            v = C.byref(v)
+        args.append(v)
+    return fn(*args)
 
 
 def _raise(code, msg):
@@ -622,6 +688,16 @@ class Context(object):
         if rc != PRISIM_OK:
             msg = self._lib.prisim_hip_last_error(self._h).decode()
             _raise(rc, '{0} failed: {1}'.format(what, msg))
+
+    def _call(self, entry, **kw):
+        """An add-on entry by parameter name: one keyword per name the table declares for it (`ctx` is this context unless given),
+        marshalled by _call_declared, and the returned code checked."""
+        restype, params = FUNCTIONS[entry]
+        if params[0][0] == 'ctx':
+            kw.setdefault('ctx', self._h)
+        rc = _call_declared(getattr(self._lib, entry), entry, params, kw)
+        if restype is not None:
+            self._check(rc, entry)
 
     # ---- array ----
     def set_array(self, baselines, freqs_hz, nt_max=1):
@@ -1050,9 +1126,8 @@ class Context(object):
         iters, flags = NP.empty(nrows, dtype=NP.int32), NP.empty(nrows, dtype=NP.int32)
         rms = NP.empty((nrows, 2))
         st = PrisimCleanStats()
-        self._check(self._lib.prisim_clean_rows(self._h, nrows, m, _ptr(x), k.shape[0], _ptr(k), _ptr(ix), _ptr(box), float(gain),
-                                                int(maxiter), float(threshold), int(bool(absolute)), _ptr(cc), _ptr(res), _ptr(iters),
-                                                _ptr(flags), _ptr(rms), C.byref(st)), 'prisim_clean_rows')
+        self._call('prisim_clean_rows', nrows=nrows, m=m, inp=x, nkern=k.shape[0], kern=k, kidx=ix, cbox=box, gain=gain, maxiter=maxiter,
+                   threshold=threshold, threshold_absolute=bool(absolute), cc=cc, res=res, iters=iters, flags=flags, rms=rms, stats=st)
         return cc, res, iters, flags, rms, _stats_dict(st, kernel_in_lds=bool)
 
     def clean_delay(self, win, kwin, cbox, m, lag_scale, freq_scale1, freq_scale2, gain, maxiter, threshold, absolute=False, kidx=None):
@@ -1069,11 +1144,9 @@ class Context(object):
         out['flags'] = NP.empty((ncubes, nrows), dtype=NP.int32)
         out['rms'] = NP.empty((ncubes, nrows, 2))
         st = PrisimCleanStats()
-        self._check(self._lib.prisim_clean_delay(self._h, ncubes, nrows, nchan, int(m), _ptr(w), k.shape[0], _ptr(k), _ptr(ix), _ptr(box),
-                                                 float(lag_scale), float(freq_scale1), float(freq_scale2), float(gain), int(maxiter),
-                                                 float(threshold), int(bool(absolute)), _ptr(out['lag']), _ptr(out['kern_lag']),
-                                                 _ptr(out['cc']), _ptr(out['res']), _ptr(out['cc_freq']), _ptr(out['res_freq']),
-                                                 _ptr(out['iters']), _ptr(out['flags']), _ptr(out['rms']), C.byref(st)), 'prisim_clean_delay')
+        self._call('prisim_clean_delay', ncubes=ncubes, nrows=nrows, nchan=nchan, m=m, win=w, nkern=k.shape[0], kwin=k, kidx=ix, cbox=box,
+                   lag_scale=lag_scale, freq_scale1=freq_scale1, freq_scale2=freq_scale2, gain=gain, maxiter=maxiter, threshold=threshold,
+                   threshold_absolute=bool(absolute), stats=st, **out)
         out['stats'] = _stats_dict(st, kernel_in_lds=bool)
         return out
 
@@ -1108,11 +1181,9 @@ class Context(object):
                                          m, nres)
         st = PrisimSubbandStats()
         r = _route_code(route, SUBBAND_ROUTES)
-        self._check(self._lib.prisim_subband_transform(self._h, ncubes, int(nt), int(nbl), nchan, _ptr(x), int(t0), _ptr(b), b.shape[0],
-                                                       nwin, _ptr(w), int(m), float(df), int(nres), nmap,
-                                                       _ptr(mo), _ptr(mi), _ptr(mw), _ptr(ps), flag, r,
-                                                       _ptr(out.get('over')), _ptr(out.get('over_power')), _ptr(out.get('res')),
-                                                       _ptr(out.get('res_power')), C.byref(st)), 'prisim_subband_transform')
+        self._call('prisim_subband_transform', ncubes=ncubes, nt=nt, nbl=nbl, nchan=nchan, cubes=x, t0=t0, bp=b, nbp=b.shape[0], nwin=nwin,
+                   wts=w, m=m, df=df, nres=nres, nmap=nmap, map_out=mo, map_in=mi, map_w=mw, pscale=ps, want=flag, route=r,
+                   over=out.get('over'), over_pow=out.get('over_power'), res=out.get('res'), res_pow=out.get('res_power'), stats=st)
         out['stats'] = _stats_dict(st, route=SUBBAND_ROUTES)
         return out
 
@@ -1170,10 +1241,9 @@ class Context(object):
         st = PrisimRunsStats()
         r = {'auto': PRISIM_RUNS_AUTO, 'fused': PRISIM_RUNS_FUSED, 'rocfft': PRISIM_RUNS_ROCFFT}[route]      # 'direct' is not the caller's to ask for
         (bpa, bps), (wa, wss) = weights
-        self._check(self._lib.prisim_runs_transform(self._h, R, nbl, nchan, nt, _ptr(x), c64, _ptr(bpa), _ptr(bps), _ptr(wa), _ptr(wss),
-                                                    nwin, _ptr(wn), m, float(scale), md, nout, float(factor),
-                                                    nmap, _ptr(mo), _ptr(mi), _ptr(mw), r, int(budget_bytes),
-                                                    _ptr(out), C.byref(st)), 'prisim_runs_transform')
+        self._call('prisim_runs_transform', R=R, nbl=nbl, nchan=nchan, nt=nt, vis=x, vis_is_c64=c64, bp=bpa, bp_strides=bps, wts=wa,
+                   wts_strides=wss, nwin=nwin, win=wn, m=m, scale=scale, out_mode=md, nout=nout, factor=factor, nmap=nmap, map_out=mo,
+                   map_in=mi, map_w=mw, route=r, budget_bytes=budget_bytes, out=out, stats=st)
         return out, _stats_dict(st, route=RUNS_ROUTES)
 
     def runs_power(self, vislag1, vislag2=None, factor=1.0, cross=False, budget_bytes=RUNS_BUDGET):
@@ -1200,9 +1270,8 @@ class Context(object):
         st = PrisimRunsStats()
         if n == 0:
             return out, _stats_dict(st, route=RUNS_ROUTES)
-        self._check(self._lib.prisim_runs_power(self._h, nf, inner, _ptr(v1), _ptr(v2), int(dt == NP.complex64), _ptr(f), int(bool(cross)),
-                                                int(numpy_fuses_complex_product(dt)), int(budget_bytes), _ptr(out), C.byref(st)),
-                    'prisim_runs_power')
+        self._call('prisim_runs_power', nf=nf, inner=inner, v1=v1, v2=v2, is_c64=dt == NP.complex64, factor=f, cross=bool(cross),
+                   fused_product=numpy_fuses_complex_product(dt), budget_bytes=budget_bytes, out=out, stats=st)
         return out, _stats_dict(st, route=RUNS_ROUTES)
 
     # ---- closure phases of antenna triads (include/prisim_closure.h) ----
@@ -1230,9 +1299,9 @@ class Context(object):
         phase = NP.empty((ntriads, nchan, nt), dtype=NP.float64)
         st = PrisimClosureStats()
         r = _route_code(route, CLOSURE_ROUTES)
-        self._check(self._lib.prisim_closure_phase(self._h, _ptr(x), nt, nbl, nchan, _ptr(lg), _ptr(cj), ntriads, _ptr(fw), _ptr(bw),
-                                                   _ptr(mk), 0 if mk is None else mk.shape[0], _ptr(mi), r, int(budget_bytes),
-                                                   _ptr(trip), _ptr(phase), C.byref(st)), 'prisim_closure_phase')
+        self._call('prisim_closure_phase', cube=x, nt=nt, nbl=nbl, nchan=nchan, legs=lg, conj=cj, ntriads=ntriads, freq_wts=fw, bpwts=bw,
+                   masks=mk, nmask=0 if mk is None else mk.shape[0], mask_index=mi, route=r, budget_bytes=budget_bytes,
+                   out_triplets=trip, out_phase=phase, stats=st)
         return trip, phase, dict(_stats_dict(st, route=CLOSURE_ROUTES), resident=x is None)
 
     # ---- closure phases of noise realisations (include/prisim_cpreal.h) ----
@@ -1275,10 +1344,9 @@ class Context(object):
         n_realize, ntriads = int(n_realize), lg.shape[0]
         out = NP.empty((nt, max(n_realize, 0), ntriads, nchan), dtype=NP.float64)
         st = self.PrisimCprealStats()
-        self._check(self._lib.prisim_closure_realizations(self._h, _ptr(x), _ptr(cr), _ptr(ix), nt, nrow, nchan, _ptr(rm), _ptr(bw), _ptr(lg),
-                                                          _ptr(cj), ntriads, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), n_realize,
-                                                          CPREAL_KINDS[kind], _route_code(route, CPREAL_ROUTES), int(budget_bytes),
-                                                          _ptr(out), C.byref(st)), 'prisim_closure_realizations')
+        self._call('prisim_closure_realizations', cube=x, cube_row=cr, bl_global=ix, nt=nt, nrow=nrow, nchan=nchan, rms=rm, bpwts=bw, legs=lg,
+                   conj=cj, ntriads=ntriads, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, first=first, n_realize=n_realize, kind=CPREAL_KINDS[kind],
+                   route=_route_code(route, CPREAL_ROUTES), budget_bytes=budget_bytes, out_phase=out, stats=st)
         return out, dict(_stats_dict(st, route=CPREAL_ROUTES), resident=x is None)
 
     # ---- beam-weighted sky power per snapshot (include/prisim_antpower.h) ----
@@ -1339,7 +1407,7 @@ class Context(object):
         num = NP.empty((nsnap, nchan), dtype=NP.float64) if want_sums else None
         den = NP.empty((nsnap, nchan), dtype=NP.float64) if want_sums else None
         st = self.PrisimAntpowerStats()
-        self._check(self._lib.prisim_antenna_power(self._h, C.byref(a), _ptr(power), _ptr(num), _ptr(den), C.byref(st)), 'prisim_antenna_power')
+        self._call('prisim_antenna_power', a=a, out_power=power, out_num=num, out_den=den, stats=st)
         return power, num, den, _stats_dict(st)
 
     # ---- dirty images and synthesized beams by the direct Fourier sum (include/prisim_imaging.h) ----
@@ -1399,7 +1467,7 @@ class Context(object):
         image = NP.empty((npix,) if chan_avg else (npix, nchan), dtype=NP.float64)
         wsum = NP.empty(1 if chan_avg else nchan, dtype=NP.float64)
         st = self.PrisimImagingStats()
-        self._check(self._lib.prisim_dirty_image(self._h, C.byref(a), _ptr(image), _ptr(wsum), C.byref(st)), 'prisim_dirty_image')
+        self._call('prisim_dirty_image', a=a, out_image=image, out_wsum=wsum, stats=st)
         return image, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=x is None and kind == 'dirty')
 
     # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
@@ -1453,11 +1521,11 @@ class Context(object):
                                           and 1 <= m <= PRISIM_CPDELAY_MAX_LEN, m, nres)
         st = PrisimCpdelayStats()
         r, pr = _route_code(route, CPDELAY_ROUTES), _route_code(phase_route, CLOSURE_ROUTES)
-        self._check(self._lib.prisim_closure_delay_spectra(
-            self._h, _ptr(ph), nrows, _ptr(x), int(nt), int(nbl), nchan, _ptr(lg), _ptr(cj), _ptr(fw), _ptr(bw), _ptr(mk),
-            0 if mk is None else mk.shape[0], _ptr(mi), pr, nwin, _ptr(w), m, float(df), nres, nmap, _ptr(mo),
-            _ptr(mi_), _ptr(mw), _ptr(ps), flag, r, int(budget_bytes), _ptr(out.get('phase')), _ptr(out.get('over')),
-            _ptr(out.get('over_power')), _ptr(out.get('res')), _ptr(out.get('res_power')), C.byref(st)), 'prisim_closure_delay_spectra')
+        self._call('prisim_closure_delay_spectra', phases=ph, nrows=nrows, cube=x, nt=nt, nbl=nbl, nchan=nchan, legs=lg, conj=cj, freq_wts=fw,
+                   bpwts=bw, masks=mk, nmask=0 if mk is None else mk.shape[0], mask_index=mi, phase_route=pr, nwin=nwin, wts=w, m=m, df=df,
+                   nres=nres, nmap=nmap, map_out=mo, map_in=mi_, map_w=mw, pscale=ps, want=flag, route=r, budget_bytes=budget_bytes,
+                   out_phase=out.get('phase'), over=out.get('over'), over_pow=out.get('over_power'), res=out.get('res'),
+                   res_pow=out.get('res_power'), stats=st)
         out['stats'] = _stats_dict(st, route=CPDELAY_ROUTES, phase_route=CLOSURE_ROUTES.get)   # phase_route: None where no phases were formed
         out['stats']['resident'] = phases is None and x is None
         return out
@@ -1476,9 +1544,8 @@ class Context(object):
         flag = _want_bits(want, {'individual': PRISIM_CPPOWER_INDIVIDUAL, 'auto': PRISIM_CPPOWER_AUTO, 'cross': PRISIM_CPPOWER_CROSS})
         out = {name: NP.empty(x.shape if name == 'individual' else (1,) + x.shape[1:], dtype=NP.float64) for name in want}
         st = PrisimCpdelayStats()
-        self._check(self._lib.prisim_closure_power(self._h, n0, nwin, inner, _ptr(x), _ptr(sc), flag, int(budget_bytes),
-                                                   _ptr(out.get('individual')), _ptr(out.get('auto')), _ptr(out.get('cross')),
-                                                   C.byref(st)), 'prisim_closure_power')
+        self._call('prisim_closure_power', n0=n0, nwin=nwin, inner=inner, spectra=x, scale=sc, want=flag, budget_bytes=budget_bytes,
+                   out_individual=out.get('individual'), out_auto=out.get('auto'), out_cross=out.get('cross'), stats=st)
         out['stats'] = _stats_dict(st, route=CPDELAY_ROUTES, phase_route=CLOSURE_ROUTES.get)   # phase_route: None where no phases were formed
         return out
 
@@ -1491,9 +1558,11 @@ class Context(object):
             raise ValueError('phases and flags must both be (n0, n1, ntriads, nchan)')
         h = C.c_void_p()
         st = PrisimCpbinsStats()
-        self._check(self._lib.prisim_cphase_bin(self._h, PRISIM_CPBINS_PHASE_FLAGS, _ptr(ph), None, None, _ptr(fl), *ph.shape, 0, 0, None,
-                                                None, 0, 0, 0, C.byref(h), None, None, None, None, None, None, None, None, C.byref(st)),
-                    'prisim_cphase_bin')
+        n0, n1, ntriads, nchan = ph.shape
+        self._call('prisim_cphase_bin', kind=PRISIM_CPBINS_PHASE_FLAGS, in_mean=ph, in_median=None, in_wts=None, in_flags=fl, n0=n0, n1=n1,
+                   ntriads=ntriads, nchan=nchan, axis=0, nbins=0, offsets=None, members=None, want=0, mad_ignores_flags=0, budget_bytes=0,
+                   resident_in=h, keep_out=None, out_wts=None, out_eicp_mean=None, out_eicp_median=None, out_cp_mean=None,
+                   out_cp_median=None, out_rms=None, out_mad=None, stats=st)
         return CphaseStack(self, h, PRISIM_CPBINS_PHASE_FLAGS, ph.shape)
 
     def cphase_bin(self, axis, offsets, members, phases=None, flags=None, binned=None, stack=None, want=tuple(CPBINS_WANT),
@@ -1534,11 +1603,11 @@ class Context(object):
         st = PrisimCpbinsStats()
         hin = C.c_void_p(stack.handle.value) if stack is not None else None
         hout = C.c_void_p()
-        self._check(self._lib.prisim_cphase_bin(
-            self._h, kind, _ptr(a), _ptr(b), _ptr(w), _ptr(f), *shape, int(axis), nbins, _ptr(off), _ptr(mem), flag,
-            1 if mad_ignores_flags else 0, int(budget_bytes), None if hin is None else C.byref(hin), C.byref(hout) if keep else None,
-            _ptr(out.get('wts')), _ptr(out.get('eicp_mean')), _ptr(out.get('eicp_median')), _ptr(out.get('cp_mean')),
-            _ptr(out.get('cp_median')), _ptr(out.get('rms')), _ptr(out.get('mad')), C.byref(st)), 'prisim_cphase_bin')
+        n0, n1, ntriads, nchan = shape
+        self._call('prisim_cphase_bin', kind=kind, in_mean=a, in_median=b, in_wts=w, in_flags=f, n0=n0, n1=n1, ntriads=ntriads, nchan=nchan,
+                   axis=axis, nbins=nbins, offsets=off, members=mem, want=flag, mad_ignores_flags=bool(mad_ignores_flags),
+                   budget_bytes=budget_bytes, resident_in=hin, keep_out=hout if keep else None, stats=st,
+                   **{'out_' + name: out.get(name) for name in CPBINS_WANT})
         if keep:
             out['stack'] = CphaseStack(self, hout, PRISIM_CPBINS_BINNED, oshape)
         out['stats'] = _stats_dict(st, rename={'resident_in': 'resident'}, resident_in=bool)
@@ -1581,9 +1650,10 @@ class Context(object):
         out = {name: NP.empty(oshape, dtype=NP.complex128 if name.startswith('diff') else (NP.float64 if name.startswith('wts') else NP.uint8))
                for name in CPDIFF_OUTPUTS}
         st = PrisimCpdiffStats()
-        self._check(self._lib.prisim_cphase_diff(
-            self._h, _ptr(a), _ptr(b), _ptr(w), *shape, None if stack is None else stack.handle, pr.shape[0], _ptr(pr), int(budget_bytes),
-            *[_ptr(out[name]) for name in CPDIFF_OUTPUTS], C.byref(st)), 'prisim_cphase_diff')
+        n0, n1, ntriads, nchan = shape
+        self._call('prisim_cphase_diff', in_mean=a, in_median=b, in_wts=w, n0=n0, n1=n1, ntriads=ntriads, nchan=nchan,
+                   resident=None if stack is None else stack.handle, ncomb=pr.shape[0], pairs=pr, budget_bytes=budget_bytes, stats=st,
+                   **{'out_' + name: out[name] for name in CPDIFF_OUTPUTS})
         for name in ('mask0', 'mask1'):
             out[name] = out[name].view(NP.bool_)
         out['stats'] = _stats_dict(st, rename={'resident_in': 'resident'}, resident_in=bool)
@@ -1655,11 +1725,10 @@ class Context(object):
         shapes = NP.ascontiguousarray([x.shape[:3] for x in xs], dtype=NP.int64).reshape(-1, 3)
         st = PrisimCpftStats()
         r = _route_code(route, CPFT_ROUTES)
-        self._check(self._lib.prisim_cphase_ft(
-            self._h, int(lead[0]), int(lead[1]), int(lead[2]), nchan, nin, pointers(xs), _ptr(shapes) if nin else None, _ptr(w), nwin,
-            _ptr(fw), _ptr(vs), m, float(df), nres, nmap, _ptr(mo), _ptr(mi), _ptr(mw), flag, r, int(budget_bytes),
-            pointers(out['over']), pointers(out['res']), _ptr(out['lag_kernel']), _ptr(out['lag_kernel_res']), C.byref(st)),
-            'prisim_cphase_ft')
+        self._call('prisim_cphase_ft', n0=lead[0], n1=lead[1], n2=lead[2], nchan=nchan, nin=nin, inputs=pointers(xs),
+                   in_shape=shapes if nin else None, w=w, nwin=nwin, wts=fw, vscale=vs, m=m, df=df, nres=nres, nmap=nmap, map_out=mo, map_in=mi,
+                   map_w=mw, want=flag, route=r, budget_bytes=budget_bytes, over=pointers(out['over']), res=pointers(out['res']),
+                   lag_kernel=out['lag_kernel'], lag_kernel_res=out['lag_kernel_res'], stats=st)
         out['stats'] = _stats_dict(st, route=CPFT_ROUTES)
         return out
 
@@ -1725,9 +1794,9 @@ class Context(object):
             raise ValueError('a crossed LST axis needs 1 to 2^20 shifts')
         out = NP.empty(self.cphase_xpower_shape(a.shape, modes, nshift), dtype=NP.complex128)
         st = self.PrisimCpxpsStats()
-        self._check(self._lib.prisim_cphase_xpower(
-            self._h, nspw, a.shape[1], a.shape[2], a.shape[3], a.shape[4], _ptr(a), _ptr(b), _ptr(f), wptr, _ptr(mcodes), nshift, _ptr(sh),
-            order.size, _ptr(order), scode, int(budget_bytes), _ptr(out), C.byref(st)), 'prisim_cphase_xpower')
+        self._call('prisim_cphase_xpower', nspw=nspw, n1=a.shape[1], n2=a.shape[2], n3=a.shape[3], nlags=a.shape[4], a=a, b=b, factor=f,
+                   weights=wptr, modes=mcodes, nshift=nshift, shifts=sh, ncollapse=order.size, order=order, stat=scode,
+                   budget_bytes=budget_bytes, out=out, stats=st)
         return {'out': out, 'stats': _stats_dict(st)}
 
     # ---- incoherent averages of closure-phase power spectra (include/prisim_cpavg.h) ----
@@ -1803,10 +1872,9 @@ class Context(object):
             return (C.c_void_p * max(len(xs), 1))(*[x.ctypes.data for x in xs])
 
         st = self.PrisimCpavgStats()
-        self._check(self._lib.prisim_cphase_xavg(
-            self._h, ndim, _ptr(NP.ascontiguousarray(shape, dtype=NP.int64)), nsets, pointers(arrays), pointers(weights), _ptr(wshapes),
-            ncombo, _ptr(reduce), mptr, int(budget_bytes), _ptr(avg), _ptr(wsum), pointers(out), pointers(wout), C.byref(st)),
-            'prisim_cphase_xavg')
+        self._call('prisim_cphase_xavg', ndim=ndim, shape=NP.ascontiguousarray(shape, dtype=NP.int64), nsets=nsets, arrays=pointers(arrays),
+                   weights=pointers(weights), wshapes=wshapes, ncombo=ncombo, reduce=reduce, masks=mptr, budget_bytes=budget_bytes, avg=avg,
+                   wsum=wsum, out=pointers(out), wout=pointers(wout), stats=st)
         return {'avg': avg, 'wsum': wsum, 'out': out, 'wout': wout, 'stats': _stats_dict(st, route=CPAVG_ROUTES)}
 
     @staticmethod
@@ -1850,8 +1918,8 @@ class Context(object):
         del2 = NP.empty(lead + (nk,), dtype=NP.complex128)
         kc = NP.empty(lead + (nk,), dtype=NP.float64)
         st = self.PrisimCpavgStats()
-        self._check(self._lib.prisim_cphase_kbin(self._h, p.shape[0], p.shape[1], p.shape[2], nk, _ptr(p), _ptr(k), _ptr(off), _ptr(mem), r,
-                                                 int(budget_bytes), _ptr(ps), _ptr(del2), _ptr(kc), C.byref(st)), 'prisim_cphase_kbin')
+        self._call('prisim_cphase_kbin', nspw=p.shape[0], m=p.shape[1], nlags=p.shape[2], nk=nk, p=p, kprll=k, offsets=off, members=mem,
+                   route=r, budget_bytes=budget_bytes, ps=ps, del2=del2, kc=kc, stats=st)
         return {'ps': ps, 'del2': del2, 'kc': kc, 'stats': _stats_dict(st, route=CPAVG_ROUTES)}
 
     # ---- instrument gain tables (include/prisim_gains.h) ----
@@ -1865,10 +1933,8 @@ class Context(object):
         co = NP.ascontiguousarray(packed['coefs'], dtype=NP.float64)
         nrows = arr['nx'].size // 2
         h, st = C.c_void_p(), PrisimGainsStats()
-        self._check(self._lib.prisim_gains_eval_spline(self._h, nrows, int(packed['kx']), int(packed['ky']), _ptr(arr['nx']), _ptr(arr['ny']),
-                                                       _ptr(arr['kx_off']), _ptr(arr['ky_off']), _ptr(arr['c_off']), kn.size, _ptr(kn),
-                                                       co.size, _ptr(co), t.size, _ptr(t), f.size, _ptr(f), C.byref(h), C.byref(st)),
-                    'prisim_gains_eval_spline')
+        self._call('prisim_gains_eval_spline', nrows=nrows, kx=packed['kx'], ky=packed['ky'], nknots=kn.size, knots=kn, ncoefs=co.size,
+                   coefs=co, nt=t.size, times=t, nchan=f.size, freqs=f, out=h, stats=st, **arr)
         return GainTable(self, h), _stats_dict(st)
 
     def gains_gather(self, gains, fidx, tidx):
@@ -1879,8 +1945,8 @@ class Context(object):
         fi = NP.ascontiguousarray(NP.asarray(fidx).ravel(), dtype=NP.int64)
         ti = NP.ascontiguousarray(NP.asarray(tidx).ravel(), dtype=NP.int64)
         h, st = C.c_void_p(), PrisimGainsStats()
-        self._check(self._lib.prisim_gains_gather(self._h, g.shape[0], g.shape[1], g.shape[2], _ptr(g), fi.size, _ptr(fi), ti.size, _ptr(ti),
-                                                  C.byref(h), C.byref(st)), 'prisim_gains_gather')
+        self._call('prisim_gains_gather', nrows=g.shape[0], ngf=g.shape[1], ngt=g.shape[2], gains=g, nchan=fi.size, fidx=fi, nt=ti.size,
+                   tidx=ti, out=h, stats=st)
         return GainTable(self, h), _stats_dict(st)
 
     def gains_apply(self, nt, nbl, nchan, fa=None, fb=None, sky=None, t0=0, sky_c64=False, noise=None, want_gain=False):
@@ -1905,9 +1971,8 @@ class Context(object):
                 raise ValueError('sky and noise must be (nt, nbl, nchan)')
         out = NP.empty((nt, nbl, nchan), dtype=NP.complex128)
         st = PrisimGainsStats()
-        self._check(self._lib.prisim_gains_apply(self._h, int(nt), int(nbl), int(nchan), ta, ma, _ptr(aa), _ptr(ca), tb, mb, _ptr(ab), _ptr(cb),
-                                                 _ptr(s), int(t0), int(bool(sky_c64)), _ptr(n), int(bool(want_gain)), _ptr(out), C.byref(st)),
-                    'prisim_gains_apply')
+        self._call('prisim_gains_apply', nt=nt, nbl=nbl, nchan=nchan, ta=ta, mode_a=ma, a_a=aa, c_a=ca, tb=tb, mode_b=mb, a_b=ab, c_b=cb, sky=s,
+                   t0=t0, sky_c64=bool(sky_c64), noise=n, want_gain=bool(want_gain), vis=out, stats=st)
         return out, _stats_dict(st)
 
     # ---- multi-GPU ----
@@ -2078,7 +2143,7 @@ class CphaseStack(object):
 
     def close(self):
         if getattr(self, 'handle', None) is not None and self.handle.value:
-            self._ctx._lib.prisim_cphase_stack_free(self.handle)
+            self._ctx._call('prisim_cphase_stack_free', stack=self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):
@@ -2095,17 +2160,17 @@ class GainTable(object):
     def __init__(self, ctx, handle):
         self._ctx, self._h = ctx, handle
         nt, nr, nf = C.c_int64(), C.c_int64(), C.c_int64()
-        ctx._lib.prisim_gains_table_shape(handle, C.byref(nt), C.byref(nr), C.byref(nf))
+        ctx._call('prisim_gains_table_shape', tab=handle, nt=nt, nrows=nr, nchan=nf)
         self.shape = (int(nt.value), int(nr.value), int(nf.value))
 
     def get(self):
         out = NP.empty(self.shape, dtype=NP.complex128)
-        self._ctx._check(self._ctx._lib.prisim_gains_table_get(self._ctx._h, self._h, _ptr(out)), 'prisim_gains_table_get')
+        self._ctx._call('prisim_gains_table_get', tab=self._h, out=out)
         return out
 
     def close(self):
         if getattr(self, '_h', None) and getattr(self._ctx, '_h', None):
-            self._ctx._lib.prisim_gains_table_free(self._h)
+            self._ctx._call('prisim_gains_table_free', tab=self._h)
         self._h = None
 
     def __del__(self):

@@ -56,54 +56,6 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_abi.PrisimSnapshot) == 160 and _abi.PrisimSnapshot.frame_given.offset == 56 and _abi.PrisimSnapshot.cel2enu.offset == 64
 
 
-def test_struct_layouts_against_the_compiled_header(tmp_path):
-    """The same by construction: include/prisim_hip.h compiled by gcc reports sizeof / offsetof of every field of every struct, and the
-    ctypes mirrors must agree field by field."""
-    import subprocess
-    pairs = {'prisim_sky': _abi.PrisimSky, 'prisim_beam_ext': _abi.PrisimBeamExt, 'prisim_beam_sky': _abi.PrisimBeamSky,
-             'prisim_catalog': _abi.PrisimCatalog, 'prisim_obs': _abi.PrisimObs, 'prisim_snapshot': _abi.PrisimSnapshot,
-             'prisim_post': _abi.PrisimPost, 'prisim_timing': _abi.PrisimTiming, 'prisim_comm_stats': _abi.PrisimCommStats}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "prisim_hip.h"', 'int main(void) {']
-    for cname, cls in pairs.items():
-        lines.append('  printf("%s %zu\\n", "{0}", sizeof({0}));'.format(cname))
-        for fname, _ in cls._fields_:
-            lines.append('  printf("%s.%s %zu\\n", "{0}", "{1}", offsetof({0}, {1}));'.format(cname, fname))
-    lines += ['  return 0;', '}']
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines))
-    exe = tmp_path / 'layout'
-    subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)])
-    got = dict(ln.split() for ln in subprocess.check_output([str(exe)]).decode().splitlines())
-    for cname, cls in pairs.items():
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for fname, _ in cls._fields_:
-            assert int(got[cname + '.' + fname]) == getattr(cls, fname).offset, (cname, fname)
-
-
-def test_every_export_is_guarded_against_cpp_exceptions():
-    """no C++ exception crosses the ABI.  Every `int prisim_hip_*` entry of capi.cpp runs its body through guarded()
-    (and of catalog.cpp) (bad_alloc -> PRISIM_ENOMEM, anything else -> PRISIM_EINTERNAL); the void / const char* entries cannot throw
-    by construction."""
-    src = ''.join(open(os.path.join(ROOT, 'prisim_amd', 'csrc', f)).read() for f in ('capi.cpp', 'catalog.cpp'))
-    entries = re.findall(r'^int (prisim_hip_\w+)\(', src, flags=re.M)
-    assert sorted(entries) == sorted(n for n in _abi.EXPORTS if n not in ('prisim_hip_destroy', 'prisim_hip_last_error', 'prisim_hip_version'))
-    for name in entries:
-        if name == 'prisim_hip_comm_last_error':
-            # a watchdog thread calls it while another thread is inside RCCL: one snprintf into the caller's buffer, no allocation, no
-            # context, no HIP call -- nothing in it can throw, and it must not wait for anything
-            body = src[src.index('int %s(' % name):]
-            body = body[:body.index('\n}\n')]
-            assert 'snprintf' in body and 'std::string' not in body and 'hip' not in body.replace('prisim_hip', '')
-            continue
-        body = src[src.index('int %s(' % name):]
-        head = body[:body.index('{') + 200]
-        assert 'return guarded(' in head.split('\n', 3)[-1] or 'return guarded(' in head, name
-    # host allocations of caller-sized vectors run inside the guard: a failed one comes back as a code, e.g. from host_alloc
-    lib = _abi.load_library()
-    p = C.c_void_p()
-    assert lib.prisim_hip_host_alloc(-5, C.byref(p)) == _abi.PRISIM_EINVAL and not p.value
-
-
 def test_null_context_is_rejected_not_crashing():
     lib = _abi.load_library()
     assert lib.prisim_hip_sync(None) == _abi.PRISIM_EINVAL

@@ -1,5 +1,6 @@
 """The helpers the add-on wrappers of prisim_amd/_abi.py share: _stats_dict against the dict each wrapper used to write out by hand
-(keys, Python types and values), the want bits, the route codes and the resample map.  No library is loaded."""
+(keys, Python types and values), the want bits, the route codes, the resample map, and the call by parameter name (_call_declared, Context._call) against a fake function.
+No library is loaded."""
 import numpy as NP
 import pytest
 
@@ -135,6 +136,81 @@ def test_want_bits_and_route_codes():
             A._route_code('nope', routes)
     with pytest.raises(KeyError):
         A._route_code('direct', A.CPFT_ROUTES)
+
+
+class FakeFunction(object):
+    """Stands for a function of the library: records the positional arguments it is called with and returns 0."""
+
+    def __init__(self):
+        self.args = None
+
+    def __call__(self, *args):
+        self.args = args
+        return 0
+
+
+POWER = A.FUNCTIONS['prisim_closure_power'][1]       # ctx, n0, nwin, inner, spectra, scale, want, budget_bytes, three outputs, stats
+
+
+def power_keywords():
+    x, sc, out = NP.arange(12.0), NP.ones(2), NP.empty(6)
+    st = A.PrisimCpdelayStats()
+    return dict(ctx=A.C.c_void_p(7), n0=NP.int64(3), nwin=2.0, inner=True, spectra=x, scale=sc, want=NP.int32(4), budget_bytes=0,
+                out_individual=None, out_auto=out, out_cross=None, stats=st)
+
+
+def test_call_declared_restores_the_declared_order_and_marshals_by_class():
+    kw = power_keywords()
+    fn = FakeFunction()
+    shuffled = {k: kw[k] for k in sorted(kw, key=lambda k: k[::-1])}
+    assert list(shuffled) != [p for p, _ in POWER]
+    assert A._call_declared(fn, 'prisim_closure_power', POWER, shuffled) == 0
+    ctx, n0, nwin, inner, spectra, scale, want, budget, ind, auto, cross, stats = fn.args
+    assert ctx is kw['ctx']                                                   # a ctypes object that is no struct goes as it is
+    assert [(type(v), v) for v in (n0, nwin, inner, want, budget)] == [(int, 3), (int, 2), (int, 1), (int, 4), (int, 0)]
+    assert (spectra, scale, auto) == (kw['spectra'].ctypes.data, kw['scale'].ctypes.data, kw['out_auto'].ctypes.data)
+    assert ind is None and cross is None                                      # None goes as NULL
+    assert type(stats) is type(A.C.byref(kw['stats'])) and stats._obj is kw['stats']    # a struct goes by reference
+    # a double goes through float(); the instance a scalar pointer points to goes by reference; a pointer array as it is
+    params = (('df', A.C.c_double), ('out', A.C.POINTER(A.C.c_void_p)), ('inputs', A.C.c_void_p), ('id', A.C.c_char_p))
+    h, ptrs = A.C.c_void_p(), (A.C.c_void_p * 2)()
+    A._call_declared(fn, 'f', params, dict(df=3, out=h, inputs=ptrs, id=b'x'))
+    assert type(fn.args[0]) is float and fn.args[0] == 3.0 and fn.args[1]._obj is h and fn.args[2] is ptrs and fn.args[3] == b'x'
+
+
+def test_call_declared_refuses_before_calling():
+    fn = FakeFunction()
+    kw = power_keywords()
+    del kw['scale']
+    with pytest.raises(TypeError, match=r"missing \['scale'\]"):
+        A._call_declared(fn, 'prisim_closure_power', POWER, kw)
+    with pytest.raises(TypeError, match=r"unknown \['scales'\]"):
+        A._call_declared(fn, 'prisim_closure_power', POWER, dict(power_keywords(), scales=None))
+    with pytest.raises(TypeError, match=r"missing \['scale'\], unknown \['scales'\]"):
+        A._call_declared(fn, 'prisim_closure_power', POWER, dict(kw, scales=None))         # as many names as declared, one of them wrong
+    with pytest.raises(ValueError, match='spectra must be a C-contiguous array'):
+        A._call_declared(fn, 'prisim_closure_power', POWER, dict(power_keywords(), spectra=NP.arange(24.0)[::2]))
+    assert fn.args is None
+
+
+def test_context_call_fills_in_the_context_and_checks_the_code():
+    """Context._call on a context that was never created: the library is a namespace of fake functions."""
+    import types
+    ctx = object.__new__(A.Context)
+    fn = FakeFunction()
+    ctx._lib, ctx._h = types.SimpleNamespace(prisim_closure_power=fn, prisim_cphase_stack_free=lambda stack: None,
+                                             prisim_hip_last_error=lambda h: b'refused'), A.C.c_void_p(5)
+    kw = power_keywords()
+    del kw['ctx']
+    ctx._call('prisim_closure_power', **kw)
+    assert fn.args[0] is ctx._h and len(fn.args) == len(POWER)
+    ctx._call('prisim_cphase_stack_free', stack=A.C.c_void_p(9))              # void: nothing to check, and no context to pass
+    ctx._lib.prisim_closure_power = lambda *args: A.PRISIM_EINVAL
+    with pytest.raises(ValueError, match='prisim_closure_power failed: refused'):
+        ctx._call('prisim_closure_power', **kw)
+    with pytest.raises(KeyError):
+        ctx._call('prisim_no_such_entry')
+    ctx._h = None                                                             # (nothing for __del__ to destroy)
 
 
 def test_resample_map_helper():

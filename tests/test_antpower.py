@@ -1,8 +1,7 @@
 """CPU: the power an antenna receives from the sky (include/prisim_antpower.h) -- the planning header compiled alone under the
-sanitizers, the ctypes mirrors of prisim_antpower_stats and prisim_antpower_args against the compiled header, the export, the Python
+sanitizers, the export (tests/test_abi_headers.py holds the ctypes mirrors and the prototype to the header), the Python
 function prisim_amd.interferometry.antenna_power against a stub context (exceptions, pointings, rotations, units, the choice of n_ext),
 and the numpy checker (tests/antpower_checker.py) on a uniform sky."""
-import ctypes as C
 import os
 import subprocess
 
@@ -116,42 +115,13 @@ def test_plan_header_compiles_alone_and_plans_soundly(tmp_path):
     assert '#include <hip' not in txt and '__device__' not in txt and '#include "addon_internal.h"' not in txt
 
 
-def test_struct_layouts_against_the_compiled_header(tmp_path):
-    pairs = {'prisim_antpower_stats': _abi.Context.PrisimAntpowerStats, 'prisim_antpower_args': _abi.Context.PrisimAntpowerArgs}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "prisim_antpower.h"', 'int main(void) {']
-    for cname, cls in pairs.items():
-        lines.append('  printf("%s %zu 0\\n", "{0}", sizeof({0}));'.format(cname))
-        for fname, _ in cls._fields_:
-            lines.append('  printf("%s.%s %zu %zu\\n", "{0}", "{1}", offsetof({0}, {1}), sizeof((({0}*)0)->{1}));'.format(cname, fname))
-    lines += ['  return 0;', '}']
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines))
-    exe = tmp_path / 'layout'
-    subprocess.check_call(['gcc', '-Wall', '-Werror', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)])
-    got = {ln.split()[0]: [int(x) for x in ln.split()[1:]] for ln in subprocess.check_output([str(exe)]).decode().splitlines()}
-    for cname, cls in pairs.items():
-        assert got[cname][0] == C.sizeof(cls), cname
-        end = 0
-        for fname, ftype in cls._fields_:
-            off, size = got[cname + '.' + fname]
-            assert off == getattr(cls, fname).offset and size == C.sizeof(ftype), (cname, fname)
-            end = max(end, off + size)
-        assert end == C.sizeof(cls), cname                            # no field of the header is missing from the mirror
-    assert [f for f, _ in pairs['prisim_antpower_stats']._fields_] == [
-        'wall_ms', 'kernel_ms', 'sources_evaluated', 'sources_up', 'spans', 'span_sources', 'block_sources', 'kernel_bytes', 'upload_bytes',
-        'download_bytes', 'streams', 'chan_tile', 'lds_bytes', 'reserved_']
-    # the struct lives on the class: the module's Prisim*Stats names are pinned by tests/test_abi_helpers.py
-    assert not hasattr(_abi, 'PrisimAntpowerStats') and 'reserved_' not in _abi._stats_dict(pairs['prisim_antpower_stats']())
-
-
 def test_export_is_in_the_library_and_outside_the_core_abi():
     lib = _abi.load_library()
-    assert _abi.ANTPOWER_EXPORTS == ('prisim_antenna_power',) and hasattr(lib, 'prisim_antenna_power')
     assert 'prisim_antenna_power' not in _abi.EXPORTS
     assert lib.prisim_antenna_power(None, None, None, None, None, None) == _abi.PRISIM_EINVAL       # a null context is refused, not read
+    # the struct lives on the class: the module's Prisim*Stats names are pinned by tests/test_abi_helpers.py
+    assert not hasattr(_abi, 'PrisimAntpowerStats') and 'reserved_' not in _abi._stats_dict(_abi.Context.PrisimAntpowerStats())
     src = open(os.path.join(ROOT, 'prisim_amd', 'csrc_antpower', 'antpower.hip')).read()
-    body = src[src.index('int prisim_antenna_power('):]
-    assert 'return guarded(' in body[:body.index('{') + 200]          # no C++ exception crosses the ABI
     assert 'atomic' not in src.replace('No atomics', '').replace('no atomic', '')
     header = open(os.path.join(ROOT, 'include', 'prisim_antpower.h')).read()
     assert 'prisim_hip_' not in header.replace('prisim_hip.h', '').replace('prisim_hip_last_error', '').replace('prisim_hip_set_sky_analytic', '')

@@ -1,9 +1,7 @@
 """CPU: antenna triads, the leg table and the numpy restatement of the closure phases against tests/golden/golden_closure.npz (the
 reference's getThreePointCombinations and getClosurePhase executed, tests/golden/make_golden_closure.py); argument validation of
 getClosurePhase; the ctypes mirror of prisim_closure_stats against the compiled header."""
-import ctypes as C
 import os
-import subprocess
 import types
 import warnings
 
@@ -165,35 +163,6 @@ def test_argument_validation_and_refusals():
         s.getClosurePhase(antenna_triplets=trip, delay_filter_info={'type': 'regular', 'min': '0', 'width': 1.0})
     with pytest.raises(TypeError, match='Delay width'):
         s.getClosurePhase(antenna_triplets=trip, delay_filter_info={'type': 'horizon', 'width': '1'})
-
-
-def test_closure_stats_layout_against_the_compiled_header(tmp_path):
-    """include/prisim_closure.h compiled by gcc reports sizeof / offsetof of every field of prisim_closure_stats; the ctypes mirror must
-    agree field by field.  The library exports the entry and the binding lists it."""
-    cls = _abi.PrisimClosureStats
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "prisim_closure.h"', 'int main(void) {',
-             '  printf("size %zu\\n", sizeof(prisim_closure_stats));']
-    for fname, _ in cls._fields_:
-        lines.append('  printf("%s %zu\\n", "{0}", offsetof(prisim_closure_stats, {0}));'.format(fname))
-    lines += ['  printf("max %d\\n", PRISIM_CLOSURE_MAX_LEN);',
-              '  printf("routes %d %d %d %d\\n", PRISIM_CLOSURE_AUTO, PRISIM_CLOSURE_DIRECT, PRISIM_CLOSURE_FUSED, PRISIM_CLOSURE_ROCFFT);',
-              '  return 0;', '}']
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines))
-    exe = tmp_path / 'layout'
-    subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)])
-    got = dict(ln.split(None, 1) for ln in subprocess.check_output([str(exe)]).decode().splitlines())
-    assert int(got['size']) == C.sizeof(cls)
-    for fname, _ in cls._fields_:
-        assert int(got[fname]) == getattr(cls, fname).offset, fname
-    assert int(got['max']) == _abi.PRISIM_CLOSURE_MAX_LEN
-    assert [int(x) for x in got['routes'].split()] == [_abi.PRISIM_CLOSURE_AUTO, _abi.PRISIM_CLOSURE_DIRECT, _abi.PRISIM_CLOSURE_FUSED,
-                                                       _abi.PRISIM_CLOSURE_ROCFFT]
-    lib = _abi.load_library()
-    assert _abi.CLOSURE_EXPORTS == ('prisim_closure_phase',) and hasattr(lib, 'prisim_closure_phase')
-    src_txt = open(os.path.join(ROOT, 'prisim_amd', 'csrc_closure', 'closure.hip')).read()
-    body = src_txt[src_txt.index('int prisim_closure_phase('):]
-    assert 'return guarded(' in body[:body.index('{') + 200]          # no C++ exception crosses the ABI
 
 
 def test_init_file_reads_blgroupinfo_back(tmp_path, monkeypatch):
