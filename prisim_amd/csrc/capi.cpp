@@ -58,122 +58,6 @@ bool load_rocfft(std::string& err) {
   return true;
 }
 
-Plan make_plan(const prisim_ctx* ctx, int precision, int kernel) {
-  Plan pl{};
-  pl.f32 = (precision == PRISIM_FP32);
-  pl.kernel = kernel;
-  if (kernel == PRISIM_KERNEL_AUTO) pl.kernel = ctx->uniform ? PRISIM_KERNEL_RECURRENCE : PRISIM_KERNEL_DIRECT;
-  const int64_t nbl = ctx->nbl_sum, nchan = ctx->nchan, nsrc = ctx->nsrc;      // (the rows the sky-sum computes: baseline folding)
-  pl.nbgroups = (int)((nbl + kBlockThreads - 1) / kBlockThreads);
-  // channel tile: the cheapest tile (seed + 5 instructions per term, tiles past nchan are wasted work) that still yields enough
-  // blocks to fill 256 CUs x 4 blocks
-  // (fp64 48-channel tiles were tried: 5.98 instead of 6.47 instructions per term, but 22 tiles x 239 groups = 10.3 rounds of resident
-  // blocks end in a 7 % tail against 14.9 rounds at 32 channels -- measured 128 ms against 125 ms on the same box)
-  int max_ct = pl.f32 ? 64 : 32;
-  {
-    // coarse channel grids with the taper run the exact per-step amplitude recurrence (the grouped form needs df/f_min <= 3.4e-3,
-    // run_pass): its rounding grows with the chain length (5.8e-6 of one term at 32 steps and df/f = 3 %, tools/fuzz_parity.py),
-    // so such runs use 32-channel tiles (16 steps from the seed)
-    const double fmin = std::min(std::fabs(ctx->f0), std::fabs(ctx->f0 + ctx->df * (double)(ctx->nchan - 1)));
-    if (pl.f32 && ctx->taper && !(fmin > 0.0 && std::fabs(ctx->df) <= 3.4e-3 * fmin)) max_ct = 32;
-  }
-  int ct = ctx->tune_ct;
-  if (ct == 0) {
-    const int64_t want_blocks = 1024;
-    const int64_t max_split = std::max<int64_t>(1, nsrc / 64);
-    const double seed = pl.f32 ? 30.0 : 48.0;             // instructions per (source, baseline, tile) outside the pair loop (ISA census)
-    const double per_term = pl.f32 ? 2.5 : 5.0;
-    double best = 0.0;
-    ct = 8;
-    // Small problems (config 2: 171 baselines = 3 wavefronts) cannot fill the chip whatever the tiling; what matters then is that
-    // every SIMD has work and that the seed is amortised over as many channels as the wave count allows.  Measured on config 2
-    // (tools/small_problem_census.py, profiles/r03_small_problem_census.jsonl): fp64 16-channel tiles 75.6 us against 85.8 at 8 and
-    // 81.0 at 32 (fp64 wants ~2 waves per SIMD to cover its dependent-issue latency), packed fp32 32-channel tiles 39.8 us against 54.2
-    // at 8 (a single wave issues v_pk_fma_f32 at near the full rate, the 2-cycle v_fma_f32 of the narrow tiles does not).  So a wider
-    // tile is admitted as soon as it still yields 1024 (fp64) / 512 (fp32) active wavefronts, even if that is fewer than 1024 blocks.
-    const int64_t waves_per_group = std::min<int64_t>(kBlockThreads / 64, (nbl + 63) / 64);
-    const int64_t active_waves_per_tile = (int64_t)(pl.nbgroups - 1) * (kBlockThreads / 64) +
-                                          std::min<int64_t>(kBlockThreads / 64, (nbl - (int64_t)(pl.nbgroups - 1) * kBlockThreads + 63) / 64);
-    (void)waves_per_group;
-    const int64_t want_waves = pl.f32 ? 512 : 1024;
-    for (int cand : {64, 32, 16, 8}) {
-      if (cand > max_ct) continue;
-      const int64_t tiles = (nchan + cand - 1) / cand;
-      if (cand > 8 && tiles * pl.nbgroups * max_split < want_blocks && tiles * active_waves_per_tile * max_split < want_waves) continue;
-      const double cost = (double)tiles * (seed + per_term * cand);
-      if (best == 0.0 || cost < best * (1.0 - 1e-9)) { best = cost; ct = cand; }
-    }
-  }
-  if (ct > max_ct) ct = max_ct;          // a tuning request never overrides the accuracy cap (or the register budget) above
-  pl.ct = ct;
-  pl.pk = pl.f32 && (ct == 32 || ct == 64) && pl.kernel == PRISIM_KERNEL_RECURRENCE;
-  pl.ntiles = (int)((nchan + ct - 1) / ct);
-  // source chunk: granularity of the zero padding and of the source split (the kernels stream rows through scalar loads)
-  const int esz = pl.f32 ? 4 : 8;
-  int chunk = ctx->tune_chunk ? ctx->tune_chunk : 64;
-  const int max_chunk = 16384 / (ct * esz);
-  if (chunk > max_chunk) chunk = max_chunk;
-  if (chunk > 256) chunk = 256;
-  if (chunk < 1) chunk = 1;
-  pl.chunk = chunk;
-  pl.nsrc_pad = round_up(std::max<int64_t>(nsrc, 1), chunk);
-  // source split so that small problems still fill the GPU; each split is a multiple of the chunk
-  int nsplit = ctx->tune_nsplit;
-  if (nsplit == 0) {
-    // resident blocks per CU = waves per SIMD the kernels are built for (PK_WAVES / WavesPerEU in skyvis_kernels.hip)
-    // (fp64: the 16 KiB phasor table + 36 KiB flush buffer + prefetch area = 56 KiB of LDS per block allow 2 blocks per CU)
-    const int per_cu = pl.pk ? 2 : (pl.f32 ? 4 : 2);
-    const int64_t slots = (int64_t)std::max(ctx->cu_count, 1) * per_cu;
-    // the grid runs in rounds of `slots` resident blocks: split_plan.h holds the rule and what it was measured on
-    nsplit = prisim::split_count(pl.ntiles, pl.nbgroups, slots, nsrc, nbl, nchan, pl.f32, ctx->taper);
-  }
-  if (!pl.f32 && ctx->taper && (ct == 16 || ct == 32) && pl.kernel == PRISIM_KERNEL_RECURRENCE && nbl <= kBlockThreads && !ctx->tune_chunk &&
-      taper_f64_grouped_enabled()) {
-    // One baseline group, fp64 with the taper: wave items (run_pass) -- two wavefronts on every SIMD, and at least 16 sources per
-    // item.  Config 2 (3 baseline waves x 16 tiles): 42 splits of 36 sources = 2016 wavefronts in 512 blocks.  A requested split
-    // count (set_tuning) is cut by the same rule: a single launch then partitions a sky exactly as a batched launch
-    // (prisim_hip_observe_catalog) with that split count does.
-    const int64_t nbw = (nbl + 63) / 64;
-    int64_t s_want;
-    if (ctx->tune_nsplit) {
-      s_want = ctx->tune_nsplit;
-    } else {
-      const int64_t waves = 2LL * 4 * std::max(ctx->cu_count, 1);
-      s_want = std::max<int64_t>(1, waves / (pl.ntiles * nbw));
-      s_want = std::min<int64_t>(s_want, std::max<int64_t>(1, nsrc / 16));
-    }
-    if (s_want > 1) {
-      const int64_t per = wave_split_sources(nsrc, s_want);
-      pl.chunk = 4;
-      pl.nsrc_pad = round_up(std::max<int64_t>(nsrc, 1), 16);
-      pl.src_per_split = per;
-      pl.nsplit = (int)std::max<int64_t>(1, (nsrc + per - 1) / per);
-      return pl;
-    }
-  }
-  if (!ctx->tune_chunk && (!pl.f32 || ctx->tune_nsplit)) {
-    // (fp64; the packed fp32 kernel's time barely moves with the split count -- 40.3 us at 47 splits against 42.2 at 24 on config 2 -- and
-    // every split costs its share of k_reduce_partials: 65.7 us per snapshot against 61.7, r04_cfg2_probe_f32.jsonl.)
-    // A small sky cut into many pieces (config 2: 1504 sources, 32 splits fill the 512 block slots exactly): 64-source chunks would cap
-    // the split count at nsrc / 64 = 24 -- 62 us against 76 with 16-source chunks and 32 splits (tools/config2_fullwave_probe.py)
-    auto realised = [&](int c) {          // split count a chunk size allows: whole chunks per split
-      const int64_t nch = round_up(std::max<int64_t>(nsrc, 1), c) / c;
-      const int64_t per = (nch + nsplit - 1) / std::max(nsplit, 1);
-      return (nch + per - 1) / std::max<int64_t>(per, 1);
-    };
-    while (chunk > 16 && realised(chunk) < nsplit) chunk /= 2;
-    pl.chunk = chunk;
-    pl.nsrc_pad = round_up(std::max<int64_t>(nsrc, 1), chunk);
-  }
-  const int64_t nchunks = pl.nsrc_pad / chunk;
-  if (nsplit > nchunks) nsplit = (int)nchunks;
-  if (nsplit < 1) nsplit = 1;
-  const int64_t chunks_per_split = (nchunks + nsplit - 1) / nsplit;
-  pl.src_per_split = chunks_per_split * chunk;
-  pl.nsplit = (int)((nchunks + chunks_per_split - 1) / chunks_per_split);
-  return pl;
-}
-
 }  // namespace pint
 
 
@@ -374,12 +258,14 @@ int prisim_hip_set_array(prisim_ctx* ctx, const double* bl_enu, int64_t nbl, con
   ctx->grp_maxh.assign(ctx->grp_maxlen.size(), 0.0);
   ctx->grp_maxz.assign(ctx->grp_maxlen.size(), 0.0);
   ctx->grp_minh.assign(ctx->grp_maxlen.size(), 1e300);
+  ctx->grp_lmax = 0.0;
   ctx->fsq_pairs_ct = ctx->fsq_pairs_ntiles = -1;
   for (SkyBufs& k : ctx->skb) k.lift_key_k[0] = -1.0;             // the cached lifting flags belong to the previous array
   for (int64_t b = 0; b < nbl_sum; ++b) {
     const double len = std::sqrt(sx[b] * sx[b] + sy[b] * sy[b] + sz[b] * sz[b]);
     const size_t g = (size_t)(b / kBlockThreads);
     if (len > ctx->grp_maxlen[g]) ctx->grp_maxlen[g] = len;
+    if (len > ctx->grp_lmax) ctx->grp_lmax = len;
     const double hl = std::sqrt(sx[b] * sx[b] + sy[b] * sy[b]);
     if (hl < ctx->grp_minh[g]) ctx->grp_minh[g] = hl;
     if (hl > ctx->grp_maxh[g]) ctx->grp_maxh[g] = hl;
@@ -462,11 +348,10 @@ int upload_common(prisim_ctx* ctx, int64_t nsrc, const double* dircos, const dou
   }
   ctx->kappa_runs.clear();
   if (fwhm_deg && nsrc > 0) {
-    constexpr size_t kMaxRuns = 8;
     int64_t lo = 0;
     for (int64_t s = 1; s <= nsrc; ++s) {
       if (s == nsrc || d4[4 * s + 3] != d4[4 * lo + 3]) {
-        if (ctx->kappa_runs.size() == kMaxRuns) { ctx->kappa_runs.clear(); break; }     // sizes vary source by source: no runs
+        if (ctx->kappa_runs.size() == (size_t)kMaxRuns) { ctx->kappa_runs.clear(); break; }     // sizes vary source by source: no runs
         ctx->kappa_runs.push_back({lo, s, d4[4 * lo + 3], (int)ctx->kappa_runs.size()});
         lo = s;
       }
@@ -489,7 +374,7 @@ int upload_common(prisim_ctx* ctx, int64_t nsrc, const double* dircos, const dou
   //   x_s = kappa_s max(Hmin |n_s| - Z rho_s, 0)^2 fmin^2/c^2 .
   // The leading sources of a run whose x_s >= T contribute together at most exp(-T) sum|pbflux|: T = 18 (1.5e-8) for fp32 requests --
   // far inside the 5e-6 tolerance -- and the packed fp32 kernels start the group's source loop behind them; T = 28 (7e-13 against
-  // fp64's 1e-11) for fp64 requests, used by the grouped fp64 kernel k_skyvis_taper_f64 (run_pass).
+  // fp64's 1e-11) for fp64 requests, used by the grouped fp64 kernel k_skyvis_taper_f64 (skyvis_plan.h: route).
   // Long baselines over coarse diffuse pixels (config 4: MWA to 2.5 km, nside 64) shed the sources nearest the zenith this way when
   // the caller lists a run's sources by decreasing altitude (InterferometerArray.observe does); unordered skies just cull little.
   ctx->cull_any[0] = ctx->cull_any[1] = false;
@@ -889,74 +774,35 @@ int prisim_hip_get_pbflux(prisim_ctx* ctx, double* out) {
   });
 }
 
-// kernel parameters common to every sky-sum launch of the current array / sky / plan
-static void fill_params(prisim_ctx* ctx, const Plan& pl, SkyvisParams& p) {
-  if (ctx->folded) { p.bl_x = (const double*)ctx->ublx.p; p.bl_y = (const double*)ctx->ubly.p; p.bl_z = (const double*)ctx->ublz.p; }
-  else { p.bl_x = (const double*)ctx->blx.p; p.bl_y = (const double*)ctx->bly.p; p.bl_z = (const double*)ctx->blz.p; }
-  p.nbl = ctx->nbl_sum; p.nchan = ctx->nchan;
-  p.f0 = ctx->f0; p.df = ctx->df; p.inv_c = 1.0 / kC;
+// kernel parameters of the current sky under route `rt`; every launch then sets its own (run_pass)
+static void sky_params(prisim_ctx* ctx, const SkyShape& s, const SkyRoute& rt, SkyvisParams& p) {
+  const Plan& pl = rt.pl;
+  fill_params(ctx, p);
   p.dirs = ctx->dirs_p;
-  p.dirs_prep = (const double*)ctx->sk->dirs_prep.p;
-  p.pb_packed = ctx->sk->packed.p;
-  p.fsq = (const float*)ctx->fsq.p;
   p.fsq_pairs = (const float*)ctx->fsq_pairs.p;
   p.lift_flags = ctx->sk->lift_flags.p ? (const int32_t*)ctx->sk->lift_flags.p : nullptr;   // taper kernels: which groups need no re-anchoring
-  p.fsq_scale = 1e16;
   p.nsrc = ctx->nsrc; p.nsrc_pad = pl.nsrc_pad;
   p.pc_x = ctx->pc[0]; p.pc_y = ctx->pc[1]; p.pc_z = ctx->pc[2];
   p.taper = ctx->taper ? 1 : 0;
   p.ntiles = pl.ntiles; p.nbgroups = pl.nbgroups; p.nsplit = pl.nsplit; p.src_per_split = pl.src_per_split;
   p.src_chunk = pl.chunk;
-  // fp32 accumulators are flushed into the fp64 cube every flush_src sources: the rounding error of a sequential
-  // fp32 sum grows like eps/2*sqrt(n/3) relative to sum|pbflux| in the fully coherent worst case (1.1e-6 at n = 16384,
-  // tolerance 5e-6), and every flush is a read-modify-write pass over the whole cube, so flush as rarely as that allows.
-  p.flush_src = 16384;
-  if (const char* env = getenv("PRISIM_HIP_FLUSH_SRC")) {        // test hook: exercise the read-modify-write flush on small skies
-    const long v = atol(env);
-    if (v > 0 && v < (1L << 30)) p.flush_src = (int32_t)v;
-  }
-  p.scale_comp = -1;
-  p.src_lo = 0; p.src_hi = ctx->nsrc; p.accumulate = 0; p.kappa0 = 0.0; p.split_flags = nullptr; p.src_first = nullptr;
-  {
-    // grouped taper recurrence (skyvis_kernels.hip): second-order residual (11.09 (df/f)^2)^2 * 0.565 <= 1e-8 of sum|pbflux|
-    const double fmin = std::min(std::fabs(ctx->f0), std::fabs(ctx->f0 + ctx->df * (double)(ctx->nchan - 1)));
-    p.taper_group = (ctx->taper && fmin > 0.0 && std::fabs(ctx->df) <= 3.4e-3 * fmin) ? 1 : 0;
-    if (const char* env = getenv("PRISIM_HIP_TAPER_GROUP")) p.taper_group = (atoi(env) != 0 && ctx->taper) ? 1 : 0;   // A/B hook
-    ctx->timing.last_taper_group = (pl.pk && p.taper_group) ? 1 : 0;
-  }
+  p.flush_src = s.flush_src;
+  p.src_lo = 0; p.src_hi = ctx->nsrc;
+  p.taper_group = rt.taper_group;
+  ctx->timing.last_taper_group = rt.last_taper_group;
 }
 
-// Decide whether this packed fp32 taper pass runs in the split form and prepare its per-run, per-group flags.  Needs: the packed
-// 64-channel kernel, the grouped recurrence's channel-grid condition, sources in <= 8 runs of one size each (exactly one when the
-// sources are split into partial cubes),
-// in-loop exponents kappa (|b| f / c)^2 <= 30 with a per-step exponent <= 1/8 (fp32 range and the series of exp2m1_small), and --
-// per baseline group -- a bound on the parabola the uncorrected grouped form leaves: relative to a term it is at most
+// The device half of the packed fp32 taper's split form (skyvis_plan.h: split_eligible): its per-run, per-group flags.  Per baseline
+// group, a bound on the parabola the uncorrected grouped form leaves: relative to a term it is at most
 // 16 kappa (b.s)^2 df^2 / c^2 with (b.s)^2 <= (H rho_s + Z |n_s|)^2 (H, Z: the group's largest horizontal length and |b_z|), so
 // relative to sum|pbflux| it is at most 16 kappa df^2/c^2 (H^2 M2 + 2 H Z M11 + Z^2 M02) with the beam-weighted moments
 // M = sum_s |p_s| (.) / sum_s |p_s| of the run's sources, maximised over the channels (k_taper_moments: one pass over pbflux;
 // k_split_flags turns them into the per-group flags ON THE DEVICE, so nothing is downloaded and a snapshot's launches never wait for
-// the previous snapshot's sky-sum).  Groups above 2e-7 keep the correction (flag bit 1).
-static bool taper_split_plan(prisim_ctx* ctx, const Plan& pl, const SkyvisParams& p) {
-  ctx->timing.last_taper_split = 0;
-  ctx->timing.last_split_uncorrected_groups = 0;
-  if (!(pl.pk && ctx->taper && pl.ct == 64 && p.taper_group && !ctx->kappa_runs.empty())) return false;
-  // (with a source split every run of the sky writes its own set of partial cubes: run_pass)
-  if (ctx->kappa_runs.size() > (size_t)kMaxRunSets) return false;
-  if (const char* env = getenv("PRISIM_HIP_TAPER_SPLIT")) { if (atoi(env) == 0) return false; }      // A/B hook
-  const double fmax = std::max(std::fabs(ctx->f0), std::fabs(ctx->f0 + ctx->df * (double)(ctx->nchan - 1)));
-  const double fmin = std::min(std::fabs(ctx->f0), std::fabs(ctx->f0 + ctx->df * (double)(ctx->nchan - 1)));
-  double lmax = 0.0;
-  for (double v : ctx->grp_maxlen) lmax = std::max(lmax, v);
-  double kmax = 0.0;
-  bool any_taper = false;
-  for (const auto& r : ctx->kappa_runs) { kmax = std::max(kmax, r.kappa); any_taper = any_taper || r.kappa > 0.0; }
-  if (!any_taper) return false;
-  const double umax = kmax * (lmax * fmax / kC) * (lmax * fmax / kC);
-  if (!(umax <= 30.0) || !(2.0 * umax * std::fabs(ctx->df) <= 0.125 * fmin)) return false;
+// the previous snapshot's sky-sum).  Groups above 2e-7 keep the correction (flag bit 1).  false: the unsplit packed kernel runs.
+static bool split_flags_prepare(prisim_ctx* ctx) {
   const int64_t nchan = ctx->nchan;
   const size_t nruns = ctx->kappa_runs.size();
   const size_t ng = ctx->grp_maxh.size();
-  if ((size_t)pl.nbgroups != ng || !ctx->sk->lift_flags.p) return false;
   if (ensure(ctx, ctx->sk->moments, (size_t)4 * nchan * sizeof(double) * nruns) != PRISIM_OK) return false;
   if (ensure(ctx, ctx->sk->split_flags, nruns * ng * sizeof(int32_t)) != PRISIM_OK) return false;
   if (ensure(ctx, ctx->sk->split_count, 8 * sizeof(int32_t)) != PRISIM_OK) return false;
@@ -985,22 +831,27 @@ static bool taper_split_plan(prisim_ctx* ctx, const Plan& pl, const SkyvisParams
   return true;
 }
 
-// one sky-sum pass into `dst` ([nbl_sum][nchan] complex128: the cube slot, or the compact buffer of a folded array); scale_comp >= 0 multiplies pbflux rows by dircos[:,comp]
-// Wave items (k_skyvis_taper_f64_wave): the grouped fp64 taper kernel on an array of one baseline group whose sources are split.
-// PRISIM_HIP_WAVE_ITEMS=0: block items (the A/B baseline).
-static bool wave_items(const prisim_ctx* ctx, const Plan& pl) {
-  bool on = !pl.f32 && ctx->taper && (pl.ct == 16 || pl.ct == 32) && pl.kernel == PRISIM_KERNEL_RECURRENCE && pl.nsplit > 1 &&
-            ctx->nbl <= kBlockThreads;
-  if (const char* env = getenv("PRISIM_HIP_WAVE_ITEMS")) on = on && atoi(env) != 0;
-  return on;
+static hipError_t launch_family(const SkyvisParams& q, int family, const Plan& pl, hipStream_t stream) {
+  switch (family) {
+    case kFamRec: return launch_skyvis_rec(q, pl.f32, pl.ct, stream);
+    case kFamPackedF32: return launch_skyvis_rec_f32pk(q, pl.ct, stream);
+    case kFamPackedF32Split: return launch_skyvis_rec_f32pk_split(q, pl.ct, stream);
+    case kFamTaperF64Block: case kFamTaperF64Wave: return launch_skyvis_taper_f64(q, pl.ct, stream);
+  }
+  return hipErrorInvalidValue;
 }
 
+// One sky-sum pass into `dst` ([nbl_sum][nchan] complex128: the cube slot, or the compact buffer of a folded array) along route rt0
+// (skyvis_plan.h; formed without the split form): rows in the route's layout, the split form's flags where it is eligible, then the
+// route's launches.  scale_comp >= 0 multiplies pbflux rows by dircos[:,comp] (a gradient component: never the split form).
 // post_set >= 0 (a deferred compute(), ctx_internal.h): the partial cubes are those of set post_set, and k_reduce_partials runs on the
 // post stream behind the sky-sum's event ev_k1 (timed is then set).
-static int run_pass(prisim_ctx* ctx, const Plan& pl, double* dst, int scale_comp, bool timed, bool prep = false, int post_set = -1) {
+static int run_pass(prisim_ctx* ctx, const SkyShape& s, const SkyToggles& t, const SkyRoute& rt0, double* dst, int scale_comp, bool timed,
+                    bool prep = false, int post_set = -1) {
   DevBuf& part = post_set == 1 ? ctx->partial_b : ctx->partial;
+  const Plan& pl = rt0.pl;
   SkyvisParams p{};
-  fill_params(ctx, pl, p);
+  sky_params(ctx, s, rt0, p);
   p.scale_comp = scale_comp;
   if (pl.kernel == PRISIM_KERNEL_DIRECT) {
     p.out = dst;
@@ -1011,128 +862,49 @@ static int run_pass(prisim_ctx* ctx, const Plan& pl, double* dst, int scale_comp
     if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k1[ctx->ring_head], ctx->stream));
     return PRISIM_OK;
   }
-  // fp64 with the source-shape taper (the reference's default precision on every run_prisim.py sky): the grouped kernel
-  // k_skyvis_taper_f64 on 16- / 32-channel tiles, rows in natural channel order (PRISIM_HIP_TAPER_F64_GROUP=0: the exact second-order
-  // form, k_skyvis_rec<double, CT, true> -- the A/B baseline and the 8-channel tiles' kernel)
-  const bool g64 = !pl.f32 && ctx->taper && (pl.ct == 16 || pl.ct == 32) && taper_f64_grouped_enabled();
+  const int interleave = rt0.layout == kRowsNatural ? 0 : 1;
   if (prep && scale_comp < 0)      // the snapshot's first pass: rows and directions in one launch
     HIPCHK(ctx, launch_pack_prep((const double*)ctx->sk->pb.p, ctx->sk->packed.p, pl.f32, ctx->nsrc, pl.nsrc_pad, ctx->nchan, pl.ct, pl.ntiles,
-                                 g64 ? 0 : 1, ctx->dirs_p, (double*)ctx->sk->dirs_prep.p, ctx->pc[0], ctx->pc[1], ctx->pc[2],
+                                 interleave, ctx->dirs_p, (double*)ctx->sk->dirs_prep.p, ctx->pc[0], ctx->pc[1], ctx->pc[2],
                                  1.0 / kC, pstream(ctx)));
   else
     HIPCHK(ctx, launch_pack((const double*)ctx->sk->pb.p, ctx->sk->packed.p, pl.f32, ctx->nsrc, pl.nsrc_pad, ctx->nchan, pl.ct,
-                            pl.ntiles, ctx->dirs_p, scale_comp, g64 ? 0 : 1, ctx->stream));
-  // Packed fp32 taper on a sky whose sources come in a few runs of one size each (every HEALPix sky; point sources + diffuse): the
-  // split form, run by run (skyvis_kernels.hip: TGROUP 2 / 3) -- size-0 runs take the plain (no-taper) bodies.
-  const bool split = scale_comp < 0 && taper_split_plan(ctx, pl, p);
+                            pl.ntiles, ctx->dirs_p, scale_comp, interleave, ctx->stream));
+  const bool split = scale_comp < 0 && split_eligible(s, t, pl, rt0.taper_group) && split_flags_prepare(ctx);
+  const SkyRoute rt_split = split ? route(s, t, pl, false, true) : SkyRoute{};
+  const SkyRoute& rt = split ? rt_split : rt0;
   if (prep) { int rcj = join_prep(ctx); if (rcj) return rcj; }      // rows, directions, flags are ready: the sums run on the compute stream
-  // Run by run under a SOURCE SPLIT (baseline shards of a mixed sky: point sources + a diffuse map): every run is cut into nsplit pieces
-  // of its own and writes its own set of nsplit partial cubes; k_reduce_partials then sums nruns x nsplit of them, in fixed order.
-  // (Before, a split sky of several runs fell back to ONE launch of the unsplit-form kernels over the whole sky: 510 ms against
-  // 453 ideal for one rank's half of config 3 + diffuse, profiles/r04_shard_balance.json.)
-  const size_t nruns_sky = ctx->kappa_runs.size();
-  const bool by_run = (split || g64) && nruns_sky > 1 && nruns_sky <= (size_t)kMaxRunSets;
-  const int nsets = (pl.nsplit > 1 && by_run) ? (int)nruns_sky : 1;
-  auto run_per_split = [&](const prisim_ctx::KappaRun& run) {
-    return round_up(((run.hi - run.lo) + pl.nsplit - 1) / pl.nsplit, pl.chunk);
-  };
-  int64_t max_per = pl.src_per_split;
-  if (nsets > 1) {
-    max_per = 0;
-    for (const auto& run : ctx->kappa_runs) max_per = std::max(max_per, run_per_split(run));
-  }
-  p.out = pl.nsplit > 1 ? (double*)part.p : dst;
-  // fp32 kernels whose splits each flush exactly once store their partial sums as complex64: half the partial traffic
-  const bool part_f32 = pl.nsplit > 1 && pl.f32 && pl.kernel == PRISIM_KERNEL_RECURRENCE && max_per <= (int64_t)p.flush_src;
-  p.out_f32 = part_f32 ? 1 : 0;
+  p.out_f32 = rt.part_f32 ? 1 : 0;
   const size_t set_reals = (size_t)pl.nsplit * (size_t)ctx->nbl_sum * (size_t)ctx->nchan * 2;       // reals of one run's partial cubes
-  auto set_out = [&](size_t r) -> double* {
-    if (nsets == 1) return p.out;
-    return part_f32 ? (double*)((float*)part.p + r * set_reals) : (double*)part.p + r * set_reals;
+  auto set_out = [&](int r) -> double* {
+    if (pl.nsplit == 1) return dst;
+    return rt.part_f32 ? (double*)((float*)part.p + (size_t)r * set_reals) : (double*)part.p + (size_t)r * set_reals;
   };
-  // taper culling: per baseline group the first source it still has to sum (tables staged by set_sky_*); a launch over the whole sky
-  // can only skip the leading sources of the FIRST run
-  const int cpr = pl.f32 ? 1 : 0;
-  const bool cull = (pl.pk || g64) && ctx->taper && ctx->cull_any[cpr] && ctx->sk->cull_first.p && ctx->cull_nruns > 0 && !ctx->kappa_runs.empty() &&
-                    (size_t)pl.nbgroups == ctx->grp_maxlen.size();             // (the packed fp32 kernels and the grouped fp64 kernel)
-  auto cull_table = [&](size_t r) {
-    return (const int32_t*)ctx->sk->cull_first.p + ((size_t)cpr * ctx->cull_nruns + (size_t)ctx->kappa_runs[r].tab_row) * (size_t)pl.nbgroups;
+  auto cull_table = [&](int row) {
+    return (const int32_t*)ctx->sk->cull_first.p + ((size_t)rt.cull_prec * ctx->cull_nruns + (size_t)row) * (size_t)pl.nbgroups;
   };
-  if (cull && !split) p.src_first = cull_table(0);
-  ctx->timing.last_culled_fraction = cull ? ctx->cull_frac[cpr] : 0.0;
-  ctx->cull_frac_pending = (cull && ctx->cat.cur >= 0) ? cpr + 1 : 0;      // catalogue path: the device's count is read once the events are in
+  ctx->timing.last_culled_fraction = rt.cull ? ctx->cull_frac[rt.cull_prec] : 0.0;
+  ctx->cull_frac_pending = (rt.cull && ctx->cat.cur >= 0) ? rt.cull_prec + 1 : 0;      // catalogue path: the device's count is read once the events are in
   // (the post-pass that last read this set of partial cubes, two computes ago, has to be through before the sky-sum writes it)
   if (post_set >= 0 && ctx->post_rec[post_set]) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_post[post_set], 0));
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k0[ctx->ring_head], ctx->stream));
-  if (split) {
-    int launches = 0;
-    for (size_t r = 0; r < ctx->kappa_runs.size(); ++r) {
-      const prisim_ctx::KappaRun& run = ctx->kappa_runs[r];
-      SkyvisParams q = p;
-      q.src_lo = run.lo; q.src_hi = run.hi;
-      if (pl.nsplit == 1) q.src_per_split = round_up(run.hi - run.lo, pl.chunk);
-      else if (nsets > 1) q.src_per_split = run_per_split(run);                        // (a split sky of ONE run: the plan's pieces stand)
-      q.accumulate = (launches > 0 && nsets == 1) ? 1 : 0;
-      q.out = set_out(r);
-      if (run.kappa > 0.0) {
-        q.kappa0 = run.kappa;
-        if (cull) q.src_first = cull_table(r);
-        q.split_flags = (const int32_t*)ctx->sk->split_flags.p + r * (size_t)pl.nbgroups;
-        HIPCHK(ctx, launch_skyvis_rec_f32pk_split(q, pl.ct, ctx->stream));
-      } else {
-        q.taper = 0;                                   // point sources: w = 1 (:6270 sigma = inf), the lifting / plain bodies
-        HIPCHK(ctx, launch_skyvis_rec_f32pk(q, pl.ct, ctx->stream));
-      }
-      ++launches;
-    }
-    ctx->timing.last_taper_split = launches;
-  } else if (pl.pk) {
-    HIPCHK(ctx, launch_skyvis_rec_f32pk(p, pl.ct, ctx->stream));
-  } else if (g64) {
-    // run by run when the sky comes in runs of one source size (so that every run's leading sources can be culled); with a source
-    // split (partial cubes, written once per split) only a sky that is one run -- otherwise one launch over the whole sky
-    const size_t nruns = ctx->kappa_runs.size();
-    if (by_run) {
-      for (size_t r = 0; r < nruns; ++r) {
-        const prisim_ctx::KappaRun& run = ctx->kappa_runs[r];
-        SkyvisParams q = p;
-        q.src_lo = run.lo; q.src_hi = run.hi;
-        q.src_per_split = pl.nsplit == 1 ? round_up(run.hi - run.lo, pl.chunk) : run_per_split(run);
-        q.accumulate = (r > 0 && nsets == 1) ? 1 : 0;
-        q.out = set_out(r);
-        q.src_first = cull ? cull_table(r) : nullptr;
-        if (run.kappa > 0.0) {
-          if (wave_items(ctx, pl)) {
-            q.wave_nbw = (int32_t)((ctx->nbl + 63) / 64);
-            q.wave_nsplit = pl.nsplit;
-            q.nsplit = 1;
-            q.nbgroups = (q.wave_nbw * pl.nsplit + kBlockThreads / 64 - 1) / (kBlockThreads / 64);
-          }
-          HIPCHK(ctx, launch_skyvis_taper_f64(q, pl.ct, ctx->stream));
-        } else {
-          // point sources (w = 1, :6270 sigma = inf): the fp64 kernel without the taper (6.2 instead of 9.8 instructions per term); its
-          // rows are (up, down) pairs: this run's rows are re-packed in that layout
-          HIPCHK(ctx, launch_pack((const double*)ctx->sk->pb.p, ctx->sk->packed.p, false, ctx->nsrc, pl.nsrc_pad, ctx->nchan, pl.ct, pl.ntiles,
-                                  ctx->dirs_p, scale_comp, 1, ctx->stream, run.lo, run.hi));
-          q.taper = 0;
-          q.src_first = nullptr;
-          HIPCHK(ctx, launch_skyvis_rec(q, false, pl.ct, ctx->stream));
-        }
-      }
-    } else {
-      SkyvisParams q = p;
-      if (wave_items(ctx, pl)) {
-        // an array of at most 256 baselines with split sources: the unit of work is a wavefront (baseline wave, split), four per block
-        q.wave_nbw = (int32_t)((ctx->nbl + 63) / 64);
-        q.wave_nsplit = pl.nsplit;
-        q.nsplit = 1;
-        q.nbgroups = (q.wave_nbw * pl.nsplit + kBlockThreads / 64 - 1) / (kBlockThreads / 64);
-      }
-      HIPCHK(ctx, launch_skyvis_taper_f64(q, pl.ct, ctx->stream));
-    }
-  } else {
-    HIPCHK(ctx, launch_skyvis_rec(p, pl.f32, pl.ct, ctx->stream));
+  for (int i = 0; i < rt.nlaunch; ++i) {
+    const SkyLaunch& l = rt.launch[i];
+    SkyvisParams q = p;
+    q.src_lo = l.src_lo; q.src_hi = l.src_hi; q.src_per_split = l.src_per_split;
+    q.accumulate = l.accumulate;
+    q.out = set_out(l.out_set);
+    q.kappa0 = l.kappa0;
+    q.taper = l.taper;
+    if (l.cull_row >= 0) q.src_first = cull_table(l.cull_row);
+    if (l.flags_row >= 0) q.split_flags = (const int32_t*)ctx->sk->split_flags.p + (size_t)l.flags_row * (size_t)pl.nbgroups;
+    if (l.wave_nbw > 0) { q.wave_nbw = l.wave_nbw; q.wave_nsplit = l.wave_nsplit; q.nsplit = 1; q.nbgroups = l.nbgroups; }
+    if (l.repack_pairs)
+      HIPCHK(ctx, launch_pack((const double*)ctx->sk->pb.p, ctx->sk->packed.p, false, ctx->nsrc, pl.nsrc_pad, ctx->nchan, pl.ct, pl.ntiles,
+                              ctx->dirs_p, scale_comp, 1, ctx->stream, l.src_lo, l.src_hi));
+    HIPCHK(ctx, launch_family(q, l.family, pl, ctx->stream));
   }
+  if (split) ctx->timing.last_taper_split = rt.nlaunch;
   if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_k1[ctx->ring_head], ctx->stream));
   hipStream_t rs = ctx->stream;
   if (post_set >= 0) {
@@ -1140,21 +912,20 @@ static int run_pass(prisim_ctx* ctx, const Plan& pl, double* dst, int scale_comp
     HIPCHK(ctx, hipStreamWaitEvent(rs, ctx->ev_k1[ctx->ring_head], 0));
   }
   if (pl.nsplit > 1)
-    HIPCHK(ctx, launch_reduce_partials(part.p, part_f32, dst, ctx->nbl_sum * ctx->nchan * 2, pl.nsplit * nsets, rs,
+    HIPCHK(ctx, launch_reduce_partials(part.p, rt.part_f32, dst, ctx->nbl_sum * ctx->nchan * 2, pl.nsplit * rt.nsets, rs,
                                        post_set >= 0 ? (unsigned)ctx->post_blocks : 0u));
   return PRISIM_OK;
 }
 
 // V + the three baseline-gradient sums of one snapshot in one pass: dst [nbl_sum][nchan], gdst [3][nbl_sum][nchan] complex128.
 // fp64: k_skyvis_grad_f64 (MFMA 4x4x4, groups of 64 baselines); fp32: the GRAD bodies of the packed kernel (16-channel tiles).
-static int run_grad_pass(prisim_ctx* ctx, const Plan& pl, double* dst, double* gdst) {
+static int run_grad_pass(prisim_ctx* ctx, const SkyShape& s, const SkyRoute& rt, double* dst, double* gdst) {
+  const Plan& pl = rt.pl;
   SkyvisParams p{};
-  fill_params(ctx, pl, p);
-  p.nsplit = 1; p.src_per_split = pl.nsrc_pad;
+  sky_params(ctx, s, rt, p);
   p.out = dst;
   p.grad_out = gdst;
-  p.out_f32 = 0;
-  if (pl.f32 && !ctx->taper) {
+  if (rt.layout == kRowsGrad) {
     // rows pre-multiplied by the gradient coefficients (1, l, m, n): 64 floats per (source, 16-channel tile)
     int rc2;
     if ((rc2 = ensure(ctx, ctx->sk->packed, (size_t)pl.ntiles * pl.nsrc_pad * 64 * sizeof(float)))) return rc2;
@@ -1162,9 +933,8 @@ static int run_grad_pass(prisim_ctx* ctx, const Plan& pl, double* dst, double* g
     HIPCHK(ctx, launch_pack_grad((const double*)ctx->sk->pb.p, (float*)ctx->sk->packed.p, ctx->nsrc, pl.nsrc_pad, ctx->nchan, pl.ntiles,
                                  ctx->dirs_p, pstream(ctx)));
   } else {
-    // (the grouped fp64 taper kernel takes its rows in natural channel order, everything else (up, down) pairs)
     HIPCHK(ctx, launch_pack((const double*)ctx->sk->pb.p, ctx->sk->packed.p, pl.f32, ctx->nsrc, pl.nsrc_pad, ctx->nchan, pl.ct, pl.ntiles,
-                            ctx->dirs_p, -1, (!pl.f32 && ctx->taper && pl.ct == 32) ? 0 : 1, pstream(ctx)));
+                            ctx->dirs_p, -1, rt.layout == kRowsNatural ? 0 : 1, pstream(ctx)));
   }
   { int rcj = join_prep(ctx); if (rcj) return rcj; }
   HIPCHK(ctx, hipEventRecord(ctx->ev_k0[ctx->ring_head], ctx->stream));
@@ -1172,7 +942,7 @@ static int run_grad_pass(prisim_ctx* ctx, const Plan& pl, double* dst, double* g
     p.dirs_c32 = (const float*)ctx->sk->dirs_c32.p;
     HIPCHK(ctx, launch_skyvis_grad_f32(p, ctx->stream));
   } else {
-    p.nbgroups = (int)((ctx->nbl_sum + 63) / 64);      // the MFMA kernel's blocks own 64 baselines; lift flags stay per 256 (it reads [group >> 2])
+    p.nbgroups = rt.launch[0].nbgroups;
     HIPCHK(ctx, launch_skyvis_grad_f64(p, pl.ct, ctx->stream));
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev_k1[ctx->ring_head], ctx->stream));
@@ -1222,26 +992,14 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
     if (want_grad && (rc = ensure(ctx, ctx->fold_grad, 3 * sum_elems * sizeof(double)))) return rc;
   }
   double* const gbase = !want_grad ? nullptr : ctx->folded ? (double*)ctx->fold_grad.p : (double*)ctx->grad.p + (size_t)slot * 3 * slot_elems;
-  Plan pl = make_plan(ctx, precision, kernel);
-  // Visibility + baseline gradient on a uniform channel grid: ONE fused pass -- fp64: the MFMA kernel k_skyvis_grad_f64 (2.4 x a plain
-  // fp64 pass instead of 4 x); fp32: the GRAD bodies of the packed kernel on 16-channel tiles (13 packed instructions per pair of terms
-  // against 4 passes x 5).  PRISIM_HIP_FUSED_GRAD=0: the four-pass form (the A/B baseline; non-uniform grids use the direct kernel).
-  bool fused_grad = want_grad && pl.kernel == PRISIM_KERNEL_RECURRENCE;
-  if (const char* env = getenv("PRISIM_HIP_FUSED_GRAD")) fused_grad = fused_grad && atoi(env) != 0;
-  if (fused_grad) {
-    const bool f32 = pl.f32;
-    pl = make_plan(ctx, f32 ? PRISIM_FP32 : PRISIM_FP64, PRISIM_KERNEL_RECURRENCE);
-    // fp32: 4 x 2 x 16 packed accumulators = 128 VGPRs; fp64: the taper's per-lane recurrence state does not fit beside 128 at 32
-    // fp64 with the taper: the grouped single-chain kernel on 32-channel tiles (k_skyvis_grad_taper_f64); PRISIM_HIP_GRAD_TAPER_GROUP=0 =
-    // round 3's exact form on 16-channel tiles (the A/B baseline)
-    pl.ct = f32 ? 16 : ((ctx->taper && !grad_taper_grouped()) ? 16 : 32);
-    pl.pk = f32;
-    pl.ntiles = (int)((ctx->nchan + pl.ct - 1) / pl.ct);
-    pl.nsplit = 1;
-    pl.nsrc_pad = round_up(pl.nsrc_pad, 4);       // the fp64 kernel walks the sources four at a time (zero rows past nsrc)
-    pl.src_per_split = pl.nsrc_pad;
-  }
-  if (defer && !(pl.kernel == PRISIM_KERNEL_RECURRENCE && pl.nsplit > 1)) {      // (nothing of this compute() is enqueued yet)
+  // The plan and the route of this sky-sum (skyvis_plan.h), formed without the packed taper's split form: run_pass takes that up once
+  // its device flags are prepared, and nothing used before then depends on it.
+  const SkyToggles tog = read_sky_toggles();
+  SkyShape shape = sky_shape(ctx, tog);
+  const SkyRoute rt = route(shape, tog, make_plan(shape, tog, precision, kernel), want_grad != 0, /*split_ready=*/false);
+  const Plan& pl = rt.pl;
+  const bool fused_grad = want_grad && rt.family != kFamGradFourPass;
+  if (defer && !rt.may_defer) {      // (nothing of this compute() is enqueued yet)
     defer = false;
     if ((rc = join_post(ctx))) return rc;
   }
@@ -1257,9 +1015,7 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
     const size_t pbytes = (size_t)pl.ntiles * pl.nsrc_pad * pl.ct * (pl.f32 ? 4 : 8);
     if ((rc = ensure(ctx, ctx->sk->packed, pbytes))) return rc;
     if ((rc = ensure(ctx, ctx->sk->dirs_prep, (size_t)pl.nsrc_pad * 4 * sizeof(double)))) return rc;
-    // (a sky of several runs of one source size writes one set of partial cubes per run: run_pass)
-    const size_t part_sets = (ctx->taper && ctx->kappa_runs.size() > 1 && ctx->kappa_runs.size() <= (size_t)kMaxRunSets) ? ctx->kappa_runs.size() : 1;
-    if (pl.nsplit > 1 && (rc = ensure(ctx, post_set == 1 ? ctx->partial_b : ctx->partial, part_sets * (size_t)pl.nsplit * sum_elems * sizeof(double))))
+    if (pl.nsplit > 1 && (rc = ensure(ctx, post_set == 1 ? ctx->partial_b : ctx->partial, (size_t)rt.alloc_sets * (size_t)pl.nsplit * sum_elems * sizeof(double))))
       return rc;
     {
       // lifting rotation is used for a baseline group only when |step phase| <= 1/8 cycle (fp32; 1/4 cycle in fp64, where the
@@ -1292,10 +1048,9 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
       for (double len : ctx->row_grp_maxlen) nlift += (len * k <= lift_limit) ? 1 : 0;
       for (size_t g = 0; g < ng; ++g)
         nlift_sum += prisim::step_flag(ctx->grp_maxlen[g], ctx->grp_maxh[g], ctx->grp_maxz[g], ctx->dmax, ctx->hmax, ctx->zmax, ctx->df, pl.f32) ? 1 : 0;
-      // the packed taper kernel folds the amplitude into the phasor (a scaled rotation: no lifting there, the flags only select its
-      // re-anchored body); every other kernel lifts the flagged groups
-      ctx->timing.last_lift_groups = (ctx->taper && pl.pk) ? 0 : nlift;
-      ctx->last_sum_lift_groups = (ctx->taper && pl.pk) ? 0 : nlift_sum;
+      ctx->timing.last_lift_groups = rt.zero_lift_counts ? 0 : nlift;
+      ctx->last_sum_lift_groups = rt.zero_lift_counts ? 0 : nlift_sum;
+      shape.have_lift_flags = ctx->sk->lift_flags.p != nullptr;      // (formed above, now or by an earlier compute() of this sky-buffer set)
     }
     if (pl.f32 && ctx->taper) {
       if ((rc = ensure(ctx, ctx->fsq_pairs, (size_t)pl.ntiles * pl.ct * sizeof(float)))) return rc;
@@ -1318,14 +1073,14 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
   // (a deferred compute() that fails half-way leaves no post-pass behind that nobody would wait for: the post stream is drained)
   auto post_abort = [&](int code) { if (defer) (void)hipStreamSynchronize(ctx->post_stream); return code; };
   if (fused_grad) {
-    if ((rc = run_grad_pass(ctx, pl, dst, gbase))) return rc;
-  } else if ((rc = run_pass(ctx, pl, dst, -1, true, /*prep=*/true, post_set))) {      // (prepares the directions with its first launch)
+    if ((rc = run_grad_pass(ctx, shape, rt, dst, gbase))) return rc;
+  } else if ((rc = run_pass(ctx, shape, tog, rt, dst, -1, true, /*prep=*/true, post_set))) {      // (prepares the directions with its first launch)
     return post_abort(rc);
   }
   if (want_grad && !fused_grad) {
     for (int comp = 0; comp < 3; ++comp) {
       double* gdst = gbase + (size_t)comp * sum_elems;
-      if ((rc = run_pass(ctx, pl, gdst, comp, false))) return rc;
+      if ((rc = run_pass(ctx, shape, tog, rt, gdst, comp, false))) return rc;
     }
   }
   // the stream the compute() ends on: deferred, the post stream -- run_pass has queued the reduction there behind the sky-sum, and the

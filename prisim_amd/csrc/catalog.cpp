@@ -103,10 +103,8 @@ bool cat_sort_wanted(const prisim_ctx* ctx) {
   const auto& C = ctx->cat;
   if (!C.have_shape || C.runs.empty() || C.n < 2) return false;
   if (const char* env = getenv("PRISIM_HIP_TAPER_CULL")) { if (atoi(env) == 0) return false; }
-  double lmax = 0.0;
-  for (double v : ctx->grp_maxlen) lmax = std::max(lmax, v);
   const double fmin = ctx->h_freqs.empty() ? 0.0 : std::min(std::fabs(ctx->h_freqs.front()), std::fabs(ctx->h_freqs.back()));
-  const double x = lmax * fmin / kC;
+  const double x = ctx->grp_lmax * fmin / kC;
   return C.kappa_max * x * x >= 18.0;
 }
 
@@ -426,34 +424,23 @@ int activate_snapshot(prisim_ctx* ctx, const prisim_obs* obs, const prisim_snaps
 // source split).  Eligible: fp64 with the source-shape taper (the grouped kernel), a uniform channel grid,
 // nothing the taper culling could skip, an analytic beam without a beamformer or the external HEALPix beam, no gradient.  Everything else
 // takes the per-snapshot loop.
-bool wave_batch_eligible(const prisim_ctx* ctx, const prisim_obs* obs, int precision, int want_grad, int64_t kc) {
+// The plan of a chunk of kc snapshots (skyvis_plan.h: batch_plan), with this chunk's reading of the hooks.
+BatchPlan chunk_plan(const prisim_ctx* ctx, int precision, int want_grad, int64_t kc) {
+  const SkyToggles tog = read_sky_toggles();
+  SkyShape shape = sky_shape(ctx, tog);
+  shape.nsrc = ctx->cat.n;      // (the counts of the snapshots' regions of interest are not known to the host)
+  return batch_plan(shape, tog, precision, kc, want_grad != 0);
+}
+
+// (sizes may vary from source to source and the sky may consist of several runs -- point sources + a diffuse map: every source
+// carries its own kappa, and with nothing to cull the runs need no separate launches; point sources then pay the taper kernel's 9.7
+// instead of the plain kernel's 6.2 instructions per term, which a launch per run and snapshot would cost many times over)
+// (a catalogue without source shapes is the same with kappa = 0 everywhere: the weight is exactly 1, the sums those of the plain kernel
+// to rounding)
+bool wave_batch_eligible(const prisim_ctx* ctx, const prisim_obs* obs, const BatchPlan& bp) {
   const auto& C = ctx->cat;
-  if (const char* env = getenv("PRISIM_HIP_WAVE_BATCH")) { if (atoi(env) == 0) return false; }
-  if (const char* env = getenv("PRISIM_HIP_WAVE_ITEMS")) { if (atoi(env) == 0) return false; }
-  // precision: a request for fp32 arithmetic (PRISim's memsave) on an array this small is served by the SAME fp64 launch -- the cost of
-  // a small array's snapshot is its launches, not its arithmetic (HERA-19: 26 us per snapshot batched in fp64 against a 45-50 us launch
-  // chain per snapshot in either precision), and the result is the fp64 one (well inside the fp32 tolerance).  PRISIM_HIP_BATCH_FP32_AS_FP64=0:
-  // fp32 requests keep the per-snapshot fp32 chain.
-  if (precision != PRISIM_FP64) { const char* env = getenv("PRISIM_HIP_BATCH_FP32_AS_FP64"); if (env && atoi(env) == 0) return false; }
-  // want_grad: the grouped fp64 gradient kernel on wave items of 16 baselines (k_skyvis_grad_taper_f64_batch), 32-channel tiles
-  if (kc < 1 || !ctx->uniform || ctx->nbl > kBlockThreads || ctx->nchan < 16) return false;
-  if (want_grad) {
-    if (!grad_taper_grouped()) return false;
-    if (const char* env = getenv("PRISIM_HIP_WAVE_BATCH_GRAD")) { if (atoi(env) == 0) return false; }
-    if (const char* env = getenv("PRISIM_HIP_FUSED_GRAD")) { if (atoi(env) == 0) return false; }
-  }
-  // one snapshot per call (observe() on a small array) takes the batched launch too -- 16-channel tiles, one round of wave slots, prepared
-  // on the preparation stream under the previous snapshot's sky-sum, queued without a count (run_wave_batch): 100 us per observe() of
-  // HERA-19 against 115 through the per-snapshot chain (tools/observe_single_ab.py).  PRISIM_HIP_WAVE_BATCH_SINGLE=0: that chain (A/B).
-  if (kc < 2) { const char* env = getenv("PRISIM_HIP_WAVE_BATCH_SINGLE"); if (env && atoi(env) == 0) return false; }
-  // (sizes may vary from source to source and the sky may consist of several runs -- point sources + a diffuse map: every source
-  // carries its own kappa, and with nothing to cull the runs need no separate launches; point sources then pay the taper kernel's 9.7
-  // instead of the plain kernel's 6.2 instructions per term, which a launch per run and snapshot would cost many times over)
-  // (a catalogue without source shapes is the same with kappa = 0 everywhere: the weight is exactly 1, the sums those of the plain kernel
-  // to rounding)
-  if (!taper_f64_grouped_enabled()) return false;
+  if (!bp.eligible) return false;
   if (!obs->use_external_beam && (beamformer_doubles(obs->ext) != 0 || obs->beam_kind == PRISIM_BEAM_POLY)) return false;
-  if (ctx->tune_chunk) return false;
   if (cat_sort_wanted(ctx)) return false;
   // nothing to cull for any precision (the cull table is per snapshot)
   {
@@ -470,8 +457,8 @@ bool wave_batch_eligible(const prisim_ctx* ctx, const prisim_obs* obs, int preci
 // buffers -- so beam x flux, packing, the sky-sums and the reduction are queued without the host having seen a single count, and the
 // compute stream waits for the geometry by event.  The host reads the counts (nsrc_roi, timing) at the END, when they have long arrived:
 // a chunk costs no round trip to the device any more (a single observe() of HERA-19 spent 45 of its 118 us waiting for one).
-int run_wave_batch(prisim_ctx* ctx, const prisim_obs* obs, const prisim_snapshot* snaps, int b, int64_t kc, int64_t slot0, int64_t* nsrc_roi,
-                   bool want_keys, bool want_grad) {
+int run_wave_batch(prisim_ctx* ctx, const BatchPlan& bp, const prisim_obs* obs, const prisim_snapshot* snaps, int b, int64_t kc, int64_t slot0,
+                   int64_t* nsrc_roi, bool want_keys, bool want_grad) {
   auto& C = ctx->cat;
   auto& S = C.set[b];
   int rc;
@@ -493,35 +480,8 @@ int run_wave_batch(prisim_ctx* ctx, const prisim_obs* obs, const prisim_snapshot
   }
   const hipStream_t ps = pstream(ctx);
   SkyBufs& K = *ctx->sk;
-  // plan: 32-channel tiles (the seed of a (source, baseline, tile) triple is 26 % of a 32-channel tile's instructions, 41 % of a
-  // 16-channel tile's), source splits so that the grid is about three rounds of two wavefronts per SIMD.  Everything here is a function
-  // of the array, the catalogue and the chunk length -- never of the counts, which the host has not seen.
-  // (one snapshot alone: 16-channel tiles and one round of wave slots -- the cut the single-launch planner arrives at for HERA-19)
-  // (V + gradient: the MFMA kernel's wave follows 16 baselines x 4 sources on 32-channel tiles)
-  int ct = ctx->tune_ct ? ctx->tune_ct : ((ctx->nchan >= 32 && kc > 1) ? 32 : 16);
-  if (ct != 16 && ct != 32) ct = 32;
-  if (want_grad) ct = 32;
-  const int ntiles = (int)((ctx->nchan + ct - 1) / ct);
-  const int nbw = want_grad ? (int)((ctx->nbl + 15) / 16) : (int)((ctx->nbl + 63) / 64);
-  const int64_t npad = round_up(std::max<int64_t>(C.n, 1), 4);
-  int64_t nsplit = ctx->tune_nsplit;
-  if (nsplit == 0) {
-    const int64_t slots = 2LL * 4 * std::max(ctx->cu_count, 1);
-    const int64_t items0 = kc * nbw * ntiles;
-    const int64_t lo = std::max<int64_t>(1, ((kc > 1 ? 5 * slots / 2 : slots) + items0 - 1) / items0);
-    // ... and of those counts the one whose last round is fullest (config 2 x 64 snapshots: 3 splits = 2.25 rounds 1.66 ms, 4 = 3.0 rounds
-    // 1.52 ms, 5 = 3.75 rounds 1.58 ms; tools/config2_batch_sweep.py)
-    double best = 1e30;
-    nsplit = lo;
-    for (int64_t n = lo; n <= 2 * lo; ++n) {
-      const double r = (double)(items0 * n) / (double)slots;
-      const double waste = std::ceil(r) / r + 0.002 * (double)(n - lo);
-      if (waste < best - 1e-12) { best = waste; nsplit = n; }
-    }
-    if (kc == 1) nsplit = std::max<int64_t>(1, slots / items0);              // one snapshot alone: ONE round of wave slots, never a second
-    nsplit = std::min<int64_t>(nsplit, std::max<int64_t>(1, C.n / 32));      // (a horizon region of interest holds about half the catalogue)
-    nsplit = std::min<int64_t>(nsplit, 64);
-  }
+  const int ct = bp.ct, ntiles = bp.ntiles, nbw = bp.nbw;
+  const int64_t npad = bp.npad, nsplit = bp.nsplit;
   const size_t slot_elems = (size_t)ctx->nbl * ctx->nchan * 2;
   const int64_t pitch = kc * npad;                     // packed rows / prepared directions: snapshot t owns rows [t npad, (t + 1) npad)
   const size_t pb_rows = (size_t)kc * (size_t)std::max<int64_t>(C.n, 1);
@@ -599,18 +559,11 @@ int run_wave_batch(prisim_ctx* ctx, const prisim_obs* obs, const prisim_snapshot
   // the sky-sums of the whole chunk: ONE launch, ONE reduction
   harvest_timing(ctx, ctx->ring_pending >= prisim_ctx::kTimingRing ? 1 : 0);
   SkyvisParams p{};
-  p.bl_x = (const double*)ctx->blx.p; p.bl_y = (const double*)ctx->bly.p; p.bl_z = (const double*)ctx->blz.p;
-  p.nbl = ctx->nbl; p.nchan = ctx->nchan;
-  p.f0 = ctx->f0; p.df = ctx->df; p.inv_c = 1.0 / kC;
+  fill_params(ctx, p);
   p.dirs = (const double*)S.dirs.p;
-  p.dirs_prep = (const double*)K.dirs_prep.p;
-  p.pb_packed = K.packed.p;
-  p.fsq = (const float*)ctx->fsq.p;
-  p.fsq_scale = 1e16;
   p.nsrc = pitch; p.nsrc_pad = pitch;                       // (the slab pitch: every snapshot's rows are a range of it)
   p.taper = 1;
   p.ntiles = ntiles; p.nsplit = 1; p.src_per_split = 0; p.src_chunk = 4;
-  p.flush_src = 16384; p.scale_comp = -1;
   p.wave_nbw = nbw; p.wave_nsplit = (int32_t)nsplit;
   p.wave_snaps = (const BatchSnap*)tabbuf.p; p.wave_nsnap = (int32_t)kc;
   p.nbgroups = (int32_t)((kc * nbw * nsplit + kBlockThreads / 64 - 1) / (kBlockThreads / 64));
@@ -903,7 +856,7 @@ int prisim_hip_observe_catalog(prisim_ctx* ctx, const prisim_obs* obs, const pri
   // chunks of snapshots whose geometry (44 bytes per catalogue source and snapshot) stays under 512 MiB
   const int64_t per_snap = 44 * std::max<int64_t>(C.n, 1);
   int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)512 << 20) / per_snap));
-  if (nsnap > 64 && wave_batch_eligible(ctx, obs, precision, want_grad, nsnap)) {
+  if (nsnap > 64 && wave_batch_eligible(ctx, obs, chunk_plan(ctx, precision, want_grad, nsnap))) {
     // small arrays whose snapshots share one launch: up to 256 snapshots per chunk (a 64-snapshot launch of HERA-19 lasts 1.7 ms and
     // starts from the idle clock; 256 snapshots fill the grid without source splits -- no partial cubes, no reduction pass) while the
     // chunk's beam x flux and packed rows (2 x 8 B per catalogue source and channel, at most) stay under 4 GiB
@@ -916,8 +869,9 @@ int prisim_hip_observe_catalog(prisim_ctx* ctx, const prisim_obs* obs, const pri
     const int64_t kc = std::min(chunk, nsnap - c0);
     const int b = C.next;
     ctx->sky_set = false;
-    if (C.n > 0 && wave_batch_eligible(ctx, obs, precision, want_grad, kc)) {
-      if ((rc = run_wave_batch(ctx, obs, snaps + c0, b, kc, slot0 + c0, nsrc_roi ? nsrc_roi + c0 : nullptr, want_keys, want_grad != 0))) return rc;
+    const BatchPlan bp = chunk_plan(ctx, precision, want_grad, kc);
+    if (C.n > 0 && wave_batch_eligible(ctx, obs, bp)) {
+      if ((rc = run_wave_batch(ctx, bp, obs, snaps + c0, b, kc, slot0 + c0, nsrc_roi ? nsrc_roi + c0 : nullptr, want_keys, want_grad != 0))) return rc;
       for (int64_t t = 0; t < kc; ++t)
         if ((rc = post_snapshot(ctx, post, slot0 + c0 + t))) return rc;
       C.next = b ^ 1;

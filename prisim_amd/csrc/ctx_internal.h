@@ -21,6 +21,7 @@
 #include "baseline_fold.h"
 #include "step_bound.h"
 #include "split_plan.h"
+#include "skyvis_plan.h"
 
 using namespace prisim;
 
@@ -130,6 +131,7 @@ struct prisim_ctx {
   int64_t last_sum_baselines = 0, last_terms_evaluated = 0, last_sum_lift_groups = 0;      // of the last compute() (prisim_hip_get_fold_info)
   std::vector<double> row_grp_maxlen; // max |b| per group of kBlockThreads CUBE rows: the units last_lift_groups is reported in
   std::vector<double> grp_maxlen;    // max |b| per group of kBlockThreads baselines (lifting-rotation guarantee)
+  double grp_lmax = 0.0;              // the largest of them (set_array)
   std::vector<double> grp_maxh, grp_maxz;   // max horizontal length / max |b_z| per group (bound of the split taper's parabola)
   std::vector<double> grp_minh;             // min horizontal length per group (taper culling)
   // Taper culling: cull_first[prec][run][group] = first source of the run that group still has to sum (device, int32); the sources before
@@ -141,7 +143,7 @@ struct prisim_ctx {
   int cull_nruns = 0;
   // runs of consecutive sources with one source size kappa (HEALPix skies: one run; point sources + diffuse: two): the packed fp32
   // taper kernel walks such skies run by run in its split form.  Empty: sizes vary from source to source (or no taper).
-  struct KappaRun { int64_t lo, hi; double kappa; int tab_row; };      // tab_row: this run's row of the cull table
+  using KappaRun = SkyRun;             // (skyvis_plan.h; tab_row: this run's row of the cull table)
   std::vector<KappaRun> kappa_runs;
   DevBuf grp_hz;      // grp_hz: [4][groups] (max horizontal length, max |b_z|, max length, min horizontal length) on the device
   int32_t* h_split_count = nullptr;                      // pinned: uncorrected-group counts of the last split launch, per run (read after a sync)
@@ -386,7 +388,6 @@ inline void release(DevBuf& b) {
   b.bytes = 0;
 }
 
-inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 // Uploads above this size go straight from the caller's (pageable) memory and are waited for; smaller ones are staged.
 constexpr size_t kStageMaxBytes = (size_t)64 << 20;
@@ -526,36 +527,39 @@ inline int ensure_copy_stream(prisim_ctx* ctx) {
   return PRISIM_OK;
 }
 
-constexpr int kMaxRunSets = 8;       // runs of one source size a split sky may have and still be summed run by run (partial-cube sets)
+static_assert(kPlanBlock == kBlockThreads, "skyvis_plan.h plans for the kernels' baseline groups");
 
-struct Plan {
-  int kernel;      // PRISIM_KERNEL_*
-  bool f32;
-  int ct;
-  int chunk;
-  int nsplit;
-  int64_t src_per_split;
-  int64_t nsrc_pad;
-  int ntiles;
-  int nbgroups;
-  bool pk;         // packed-fp32 kernel (k_skyvis_rec_f32pk) with interleaved pbflux pairs
-};
-
-// wave items (arrays of at most 256 baselines, grouped fp64 taper kernel): sources per split when nsrc sources are cut into s_want pieces
-inline int64_t wave_split_sources(int64_t nsrc, int64_t s_want) {
-  return round_up((std::max<int64_t>(nsrc, 1) + s_want - 1) / std::max<int64_t>(s_want, 1), 4);
+// what skyvis_plan.h reads of the context (t: this compute's hooks)
+inline SkyShape sky_shape(const prisim_ctx* ctx, const SkyToggles& t) {
+  SkyShape s{};
+  s.nbl = ctx->nbl; s.nbl_sum = ctx->nbl_sum; s.nchan = ctx->nchan; s.nsrc = ctx->nsrc;
+  s.f0 = ctx->f0; s.df = ctx->df;
+  s.uniform = ctx->uniform; s.taper = ctx->taper; s.folded = ctx->folded;
+  s.cu_count = ctx->cu_count;
+  s.tune_ct = ctx->tune_ct; s.tune_chunk = ctx->tune_chunk; s.tune_nsplit = ctx->tune_nsplit;
+  s.nruns = (int)std::min<size_t>(ctx->kappa_runs.size(), (size_t)kMaxRuns);
+  for (int r = 0; r < s.nruns; ++r) s.runs[r] = ctx->kappa_runs[(size_t)r];
+  s.ngroups = (int64_t)ctx->grp_maxlen.size();
+  s.lmax = ctx->grp_lmax;
+  s.cull_any[0] = ctx->cull_any[0]; s.cull_any[1] = ctx->cull_any[1];
+  s.cull_staged = ctx->sk->cull_first.p && ctx->cull_nruns > 0;
+  s.have_lift_flags = ctx->sk->lift_flags.p != nullptr;
+  s.flush_src = flush_sources(t);
+  return s;
 }
 
-// PRISIM_HIP_TAPER_F64_GROUP=0 (A/B hook): fp64 taper requests run the exact second-order kernel instead of the grouped one
-inline bool taper_f64_grouped_enabled() {
-  const char* env = getenv("PRISIM_HIP_TAPER_F64_GROUP");
-  return !(env && atoi(env) == 0);
-}
-
-// PRISIM_HIP_GRAD_TAPER_GROUP=0 (A/B hook): fp64 gradients of a tapered sky run round 3's exact form on 16-channel tiles
-inline bool grad_taper_grouped() {
-  const char* env = getenv("PRISIM_HIP_GRAD_TAPER_GROUP");
-  return !(env && atoi(env) == 0);
+// the kernel parameters that are pointers or constants of the resident array and the current sky-buffer set
+inline void fill_params(const prisim_ctx* ctx, SkyvisParams& p) {
+  if (ctx->folded) { p.bl_x = (const double*)ctx->ublx.p; p.bl_y = (const double*)ctx->ubly.p; p.bl_z = (const double*)ctx->ublz.p; }
+  else { p.bl_x = (const double*)ctx->blx.p; p.bl_y = (const double*)ctx->bly.p; p.bl_z = (const double*)ctx->blz.p; }
+  p.nbl = ctx->nbl_sum; p.nchan = ctx->nchan;
+  p.f0 = ctx->f0; p.df = ctx->df; p.inv_c = 1.0 / kC;
+  p.dirs_prep = (const double*)ctx->sk->dirs_prep.p;
+  p.pb_packed = ctx->sk->packed.p;
+  p.fsq = (const float*)ctx->fsq.p;
+  p.fsq_scale = 1e16;
+  p.flush_src = kFlushSrc;
+  p.scale_comp = -1;
 }
 
 // the stream a sky is prepared on: the preparation stream when the current sky came from the resident catalogue, else the compute stream
@@ -570,7 +574,6 @@ inline int join_prep(prisim_ctx* ctx) {
 }
 
 // capi.cpp
-Plan make_plan(const prisim_ctx* ctx, int precision, int kernel);
 int upload_common(prisim_ctx* ctx, int64_t nsrc, const double* dircos, const double* pc_dircos, const double* fwhm_deg, size_t extra_stage_bytes);
 int upload_any(prisim_ctx* ctx, void* dst, const void* src, size_t bytes, bool* synced);
 int check_beam_spec(prisim_ctx* ctx, int beam_kind, double diameter_m, const double* beam_pc_dircos, const prisim_beam_ext* ext);

@@ -1161,7 +1161,7 @@ __device__ __forceinline__ float exp2m1_small(float D) {
 //   channel), and exp(+kappa0 (b.s)^2 f^2/c^2), carried by the recurrence.  For a sky seen through a beam the second exponent is
 //   small wherever the flux is ((b.s)^2 <= |b|^2 sin^2 theta), so the parabola the grouped form leaves inside a group --
 //   16 kappa (b.s)^2 df^2/c^2 at most, relative to the term -- can be BOUNDED from beam-weighted moments of the sky (the host does,
-//   per baseline group, capi.cpp:taper_split_plan) and, where that bound is below 2e-7 of sum|pbflux|, not corrected at all:
+//   per baseline group, capi.cpp:split_flags_prepare) and, where that bound is below 2e-7 of sum|pbflux|, not corrected at all:
 //   3 = no parabola correction (6.375 packed instructions per pair of terms instead of 7.25), 2 = corrected (groups that fail the bound),
 //   4 = no correction and groups of 16 steps (the parabola is 4x larger: groups whose bound passes with that factor; 6.25 per pair).
 //   GPK (GRAD bodies without the taper): the rows arrive PRE-MULTIPLIED by the gradient coefficients -- k_pack_grad writes, per source and
@@ -2191,11 +2191,16 @@ __global__ void k_fsq(const double* __restrict__ freqs, float* __restrict__ fsq,
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
+// the grid of a launch over `items` block items (see block_item()): whole octets of blocks; 0: no such launch
+static unsigned item_grid(int64_t items) {
+  if (items <= 0 || items > 0x3fffffffLL) return 0;
+  return 8u * (unsigned)((items + 7) / 8);
+}
+
 template <typename T, int CT>
 static hipError_t launch_rec_ct(const SkyvisParams& p, hipStream_t stream) {
-  const int64_t items = (int64_t)p.ntiles * p.nsplit * p.nbgroups;          // see block_item()
-  if (items <= 0 || items > 0x3fffffffLL) return hipErrorInvalidValue;
-  const unsigned grid = 8u * (unsigned)((items + 7) / 8);
+  const unsigned grid = item_grid((int64_t)p.ntiles * p.nsplit * p.nbgroups);          // see block_item()
+  if (!grid) return hipErrorInvalidValue;
   if (p.taper)
     hipLaunchKernelGGL((k_skyvis_rec<T, CT, true>), dim3(grid), dim3(kBlockThreads), 0, stream, p);
   else
@@ -2205,9 +2210,8 @@ static hipError_t launch_rec_ct(const SkyvisParams& p, hipStream_t stream) {
 
 template <int CT>
 static hipError_t launch_rec_pk_ct(const SkyvisParams& p, hipStream_t stream) {
-  const int64_t items = (int64_t)p.ntiles * p.nsplit * p.nbgroups;          // see block_item()
-  if (items <= 0 || items > 0x3fffffffLL) return hipErrorInvalidValue;
-  const unsigned grid = 8u * (unsigned)((items + 7) / 8);
+  const unsigned grid = item_grid((int64_t)p.ntiles * p.nsplit * p.nbgroups);          // see block_item()
+  if (!grid) return hipErrorInvalidValue;
   if (p.taper)
     hipLaunchKernelGGL((k_skyvis_rec_f32pk<CT, true>), dim3(grid), dim3(kBlockThreads), 0, stream, p);
   else
@@ -2224,9 +2228,8 @@ hipError_t launch_skyvis_rec_f32pk(const SkyvisParams& p, int ct, hipStream_t st
 }
 
 hipError_t launch_skyvis_rec_f32pk_split(const SkyvisParams& p, int ct, hipStream_t stream) {
-  const int64_t items = (int64_t)p.ntiles * p.nsplit * p.nbgroups;
-  if (items <= 0 || items > 0x3fffffffLL || !p.split_flags || ct != 64) return hipErrorInvalidValue;
-  const unsigned grid = 8u * (unsigned)((items + 7) / 8);
+  const unsigned grid = item_grid((int64_t)p.ntiles * p.nsplit * p.nbgroups);
+  if (!grid || !p.split_flags || ct != 64) return hipErrorInvalidValue;
   hipLaunchKernelGGL((k_skyvis_rec_f32pk_split<64>), dim3(grid), dim3(kBlockThreads), 0, stream, p);
   return hipGetLastError();
 }
@@ -2268,9 +2271,8 @@ hipError_t launch_skyvis_rec(const SkyvisParams& p, bool f32, int ct, hipStream_
 }
 
 hipError_t launch_skyvis_taper_f64(const SkyvisParams& p, int ct, hipStream_t stream) {
-  const int64_t items = (int64_t)p.ntiles * p.nsplit * p.nbgroups;          // see block_item()
-  if (items <= 0 || items > 0x3fffffffLL || !p.taper) return hipErrorInvalidValue;
-  const unsigned grid = 8u * (unsigned)((items + 7) / 8);
+  const unsigned grid = item_grid((int64_t)p.ntiles * p.nsplit * p.nbgroups);          // see block_item()
+  if (!grid || !p.taper) return hipErrorInvalidValue;
   if (p.wave_nbw > 0) {
     // wave items: one baseline group, p.nbgroups quads of (baseline wave, split) items
     if (p.nsplit != 1 || p.wave_nsplit < 1 || p.nbl > kBlockThreads || (int64_t)p.wave_nbw * 64 < p.nbl ||
@@ -2293,11 +2295,10 @@ hipError_t launch_skyvis_taper_f64(const SkyvisParams& p, int ct, hipStream_t st
 
 // many snapshots in one launch: p.wave_snaps / p.wave_nsnap set, p.nbgroups = ceil(nsnap nbw wave_nsplit / 4), p.nsplit = 1
 hipError_t launch_skyvis_taper_f64_wave_batch(const SkyvisParams& p, int ct, hipStream_t stream) {
-  const int64_t items = (int64_t)p.ntiles * p.nbgroups;
-  if (items <= 0 || items > 0x3fffffffLL || !p.taper || p.nsplit != 1 || p.wave_nsplit < 1 || p.wave_nsnap < 1 || !p.wave_snaps || p.nbl > kBlockThreads ||
+  const unsigned grid = item_grid((int64_t)p.ntiles * p.nbgroups);
+  if (!grid || !p.taper || p.nsplit != 1 || p.wave_nsplit < 1 || p.wave_nsnap < 1 || !p.wave_snaps || p.nbl > kBlockThreads ||
       (int64_t)p.wave_nbw * 64 < p.nbl || (int64_t)p.nbgroups * (kBlockThreads / 64) < (int64_t)p.wave_nsnap * p.wave_nbw * p.wave_nsplit)
     return hipErrorInvalidValue;
-  const unsigned grid = 8u * (unsigned)((items + 7) / 8);
   switch (ct) {
     case 16: hipLaunchKernelGGL((k_skyvis_taper_f64_wave_batch<16>), dim3(grid), dim3(kBlockThreads), 0, stream, p); break;
     case 32: hipLaunchKernelGGL((k_skyvis_taper_f64_wave_batch<32>), dim3(grid), dim3(kBlockThreads), 0, stream, p); break;
@@ -2308,11 +2309,10 @@ hipError_t launch_skyvis_taper_f64_wave_batch(const SkyvisParams& p, int ct, hip
 
 // V + gradient of many snapshots in one launch: p.wave_nbw = waves of 16 baselines, p.nbgroups = ceil(nsnap wave_nbw wave_nsplit / 4), 32-channel tiles
 hipError_t launch_skyvis_grad_taper_f64_batch(const SkyvisParams& p, hipStream_t stream) {
-  const int64_t items = (int64_t)p.ntiles * p.nbgroups;
-  if (items <= 0 || items > 0x3fffffffLL || !p.taper || p.nsplit != 1 || p.wave_nsplit < 1 || p.wave_nsnap < 1 || !p.wave_snaps || p.nbl > kBlockThreads ||
+  const unsigned grid = item_grid((int64_t)p.ntiles * p.nbgroups);
+  if (!grid || !p.taper || p.nsplit != 1 || p.wave_nsplit < 1 || p.wave_nsnap < 1 || !p.wave_snaps || p.nbl > kBlockThreads ||
       (int64_t)p.wave_nbw * 16 < p.nbl || (int64_t)p.nbgroups * (kBlockThreads / 64) < (int64_t)p.wave_nsnap * p.wave_nbw * p.wave_nsplit)
     return hipErrorInvalidValue;
-  const unsigned grid = 8u * (unsigned)((items + 7) / 8);
   hipLaunchKernelGGL(k_skyvis_grad_taper_f64_batch, dim3(grid), dim3(kBlockThreads), 0, stream, p);
   return hipGetLastError();
 }
@@ -2338,9 +2338,8 @@ hipError_t launch_reduce_partials_batch(const double* part, double* out, int64_t
 
 hipError_t launch_skyvis_grad_f32(const SkyvisParams& p, hipStream_t stream) {
   // p.nbgroups = groups of 256 baselines, p.nsplit = 1, 16-channel tiles, p.dirs_c32 and p.grad_out set
-  const int64_t items = (int64_t)p.ntiles * p.nbgroups;
-  if (items <= 0 || items > 0x3fffffffLL || p.nsplit != 1 || (p.taper && !p.dirs_c32) || !p.grad_out) return hipErrorInvalidValue;
-  const unsigned grid = 8u * (unsigned)((items + 7) / 8);
+  const unsigned grid = item_grid((int64_t)p.ntiles * p.nbgroups);
+  if (!grid || p.nsplit != 1 || (p.taper && !p.dirs_c32) || !p.grad_out) return hipErrorInvalidValue;
   if (p.taper) hipLaunchKernelGGL((k_skyvis_grad_f32pk<true>), dim3(grid), dim3(kBlockThreads), 0, stream, p);
   else hipLaunchKernelGGL((k_skyvis_grad_f32pk<false>), dim3(grid), dim3(kBlockThreads), 0, stream, p);
   return hipGetLastError();
@@ -2348,9 +2347,8 @@ hipError_t launch_skyvis_grad_f32(const SkyvisParams& p, hipStream_t stream) {
 
 hipError_t launch_skyvis_grad_f64(const SkyvisParams& p, int ct, hipStream_t stream) {
   // p.nbgroups = groups of 64 baselines, p.nsplit = 1
-  const int64_t items = (int64_t)p.ntiles * p.nbgroups;
-  if (items <= 0 || items > 0x3fffffffLL || p.nsplit != 1) return hipErrorInvalidValue;
-  const unsigned grid = 8u * (unsigned)((items + 7) / 8);
+  const unsigned grid = item_grid((int64_t)p.ntiles * p.nbgroups);
+  if (!grid || p.nsplit != 1) return hipErrorInvalidValue;
   if (ct == 32 && p.taper) {            // grouped single-chain form, rows in natural channel order (launch_pack interleave = 0)
     hipLaunchKernelGGL(k_skyvis_grad_taper_f64, dim3(grid), dim3(kBlockThreads), 0, stream, p);
   } else if (ct == 32) {                // (the exact taper recurrence's per-lane state does not fit beside 128 accumulator VGPRs at 32 channels)

@@ -15,7 +15,7 @@
 //          optimum sits, a grid of ~1.5 rounds -- the second, half-empty round runs one block per CU, and a lone wave per SIMD issues
 //          packed FMAs at 3/4 of the full rate -- 2.53 ms at 16 splits against 3.28 at 19 and 2.75 at 10 or 24 on the config-4 share;
 //   bounds: 1 <= nsplit <= 64.
-// make_plan (capi.cpp) then realises the count in whole source chunks.
+// make_plan (skyvis_plan.h) then realises the count in whole source chunks.
 #pragma once
 #include <algorithm>
 #include <cstdint>
