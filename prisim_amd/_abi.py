@@ -98,6 +98,10 @@ PRISIM_IMAGE_W_NONE, PRISIM_IMAGE_W_BASELINE, PRISIM_IMAGE_W_FULL = 0, 1, 2
 IMAGING_ROUTES = {PRISIM_IMAGE_DIRECT: 'direct', PRISIM_IMAGE_STEPPED: 'stepped'}
 IMAGING_KINDS = {'dirty': PRISIM_IMAGE_DIRTY, 'psf': PRISIM_IMAGE_PSF}
 
+# Hogbom CLEAN of dirty images with the exact beam (include/prisim_imclean.h, prisim_amd/csrc_imaging/imclean.hip)
+PRISIM_IMCLEAN_THRESHOLD, PRISIM_IMCLEAN_MAXITER, PRISIM_IMCLEAN_DEAD = 1, 2, 4
+PRISIM_IMCLEAN_POLL_DEFAULT, PRISIM_IMCLEAN_POLL_MAX = 32, 1024
+
 # instrument gain tables (include/prisim_gains.h, prisim_amd/csrc_gains/)
 PRISIM_GAINS_MAX_DEGREE = 5
 PRISIM_GAINS_ANTENNA, PRISIM_GAINS_BASELINE = 0, 1
@@ -313,6 +317,25 @@ class _PrisimImagingArgs(C.Structure):
                 ('budget_bytes', C.c_int64)]
 
 
+class _PrisimImcleanStats(C.Structure):
+    """prisim_imclean_stats of include/prisim_imclean.h, public as Context.PrisimImcleanStats (see _PrisimCpxpsStats)."""
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('dirty_ms', C.c_double), ('peak_ms', C.c_double),
+                ('update_ms', C.c_double), ('restore_ms', C.c_double), ('terms', C.c_int64), ('iterations', C.c_int64),
+                ('components', C.c_int64), ('polls', C.c_int64), ('chunks', C.c_int64), ('chunk_pixels', C.c_int64),
+                ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64), ('device_bytes', C.c_int64),
+                ('route', C.c_int32), ('streams', C.c_int32), ('chan_tile', C.c_int32), ('reseed', C.c_int32), ('lds_bytes', C.c_int32),
+                ('block_pixels', C.c_int32)]
+
+
+class _PrisimImcleanArgs(C.Structure):
+    """prisim_imclean_args of include/prisim_imclean.h, public as Context.PrisimImcleanArgs."""
+    _fields_ = [('npix', C.c_int64), ('nbl', C.c_int64), ('nchan', C.c_int64), ('nt', C.c_int64), ('unitvec', C.c_void_p), ('rot', C.c_void_p),
+                ('aberr_beta', C.c_void_p), ('pc_dircos', C.c_void_p), ('baselines', C.c_void_p), ('freqs_hz', C.c_void_p), ('cube', C.c_void_p),
+                ('weights', C.c_void_p), ('window', C.c_void_p), ('fwhm_rad', C.c_void_p), ('gain', C.c_double), ('threshold', C.c_double),
+                ('maxiter', C.c_int64), ('budget_bytes', C.c_int64), ('weight_form', C.c_int32), ('chan_avg', C.c_int32), ('route', C.c_int32),
+                ('threshold_relative', C.c_int32), ('poll_every', C.c_int32), ('reserved_', C.c_int32)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -394,6 +417,7 @@ STRUCTS = {
     'prisim_cpxps_stats': _PrisimCpxpsStats, 'prisim_cpavg_stats': _PrisimCpavgStats, 'prisim_cpreal_stats': _PrisimCprealStats,
     'prisim_antpower_stats': _PrisimAntpowerStats, 'prisim_antpower_args': _PrisimAntpowerArgs,
     'prisim_imaging_stats': _PrisimImagingStats, 'prisim_imaging_args': _PrisimImagingArgs, 'prisim_gains_stats': PrisimGainsStats,
+    'prisim_imclean_stats': _PrisimImcleanStats, 'prisim_imclean_args': _PrisimImcleanArgs,
 }
 
 # The C ABI, declared once: per header of include/, its functions in the header's order, each as
@@ -521,6 +545,10 @@ _PROTOTYPES = {
     'prisim_imaging.h': '''
         int prisim_dirty_image(p ctx, *prisim_imaging_args a, p out_image, p out_wsum, *prisim_imaging_stats stats);
     ''',
+    'prisim_imclean.h': '''
+        int prisim_clean_image(p ctx, *prisim_imclean_args a, p out_residual, p out_restored, p out_comp_pixel, p out_comp_flux, p out_ncomp,
+            p out_status, p out_peak0, p out_wsum, *prisim_imclean_stats stats);
+    ''',
     'prisim_gains.h': '''
         int prisim_gains_eval_spline(p ctx, q nrows, i kx, i ky, p nx, p ny, p kx_off, p ky_off, p c_off, q nknots, p knots, q ncoefs, p coefs,
             q nt, p times, q nchan, p freqs, *p out, *prisim_gains_stats stats);
@@ -558,9 +586,9 @@ def _parse_prototypes(table):
 FUNCTIONS, HEADER_EXPORTS = _parse_prototypes(_PROTOTYPES)
 # the functions of each header (tests and tools import these names)
 (EXPORTS, CLEAN_EXPORTS, SUBBAND_EXPORTS, RUNS_EXPORTS, CLOSURE_EXPORTS, CPDELAY_EXPORTS, CPBINS_EXPORTS, CPDIFF_EXPORTS, CPFT_EXPORTS,
- CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, GAINS_EXPORTS) = (
+ CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMCLEAN_EXPORTS, GAINS_EXPORTS) = (
     HEADER_EXPORTS['prisim_%s.h' % h] for h in ('hip', 'clean', 'subband', 'runs', 'closure', 'cpdelay', 'cpbins', 'cpdiff', 'cpft', 'cpxps',
-                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'gains'))
+                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imclean', 'gains'))
 
 
 class PrisimHipError(RuntimeError):
@@ -1469,6 +1497,87 @@ class Context(object):
         st = self.PrisimImagingStats()
         self._call('prisim_dirty_image', a=a, out_image=image, out_wsum=wsum, stats=st)
         return image, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=x is None and kind == 'dirty')
+
+    # ---- Hogbom CLEAN of dirty images with the exact beam (include/prisim_imclean.h) ----
+    PrisimImcleanStats = _PrisimImcleanStats
+    PrisimImcleanArgs = _PrisimImcleanArgs
+
+    def clean_image(self, unitvec, rot, pc_dircos, baselines, freqs_hz, cube=None, weights=None, chan_avg=False, aberr_beta=None,
+                    gain=0.1, maxiter=10000, threshold=5e-3, threshold_relative=True, window=None, fwhm_rad=None, route='auto',
+                    budget_bytes=0, poll_every=0):
+        """Hogbom CLEAN of the dirty image of dirty_image(kind='dirty') with the exact beam on the device (prisim_clean_image): per
+        image channel (one for the band with chan_avg) and iteration, the largest |residual| inside the window becomes a component of
+        gain times its value, and the dirty image of that component's own visibilities is subtracted from every pixel.  The
+        geometry, cube and weights as dirty_image takes them.  gain in (0, 1]; maxiter >= 0 components per channel at most; threshold
+        finite and >= 0, a fraction (< 1) of the first peak with threshold_relative; window: (npix,) of pixels that may hold
+        components, or None for all; fwhm_rad: a scalar or (nc,) restoring beam in radians, or None for no restoration; budget_bytes:
+        device bytes the resident image may take (0: 1 GiB); poll_every: iterations between two reads of the active count (0: 32),
+        which no result depends on.  Returns a dict: 'residual' and 'restored' (or None) (npix, nchan) or (npix,); 'comp_pixel' int32
+        and 'comp_flux' (nc, longest list), the unused tail of a row -1 and 0; 'ncomp', 'status' (PRISIM_IMCLEAN_* bits) int32 and
+        'peak0', 'wsum' (nc,); and the stats dict."""
+        uv = NP.ascontiguousarray(unitvec, dtype=NP.float64).reshape(-1, 3)
+        rt = NP.ascontiguousarray(rot, dtype=NP.float64).reshape(-1, 9)
+        pc = NP.ascontiguousarray(pc_dircos, dtype=NP.float64).reshape(-1, 3)
+        bl = NP.ascontiguousarray(baselines, dtype=NP.float64).reshape(-1, 3)
+        fq = NP.ascontiguousarray(freqs_hz, dtype=NP.float64).ravel()
+        npix, nt, nbl, nchan = uv.shape[0], rt.shape[0], bl.shape[0], fq.size
+        nc = 1 if chan_avg else nchan
+        if pc.shape[0] != nt:
+            raise ValueError('pc_dircos must have one row per snapshot')
+        ab = None
+        if aberr_beta is not None:
+            ab = NP.ascontiguousarray(aberr_beta, dtype=NP.float64).reshape(-1, 3)
+            if ab.shape[0] != nt:
+                raise ValueError('aberr_beta must have one row per snapshot')
+        if route != 'auto' and route not in IMAGING_ROUTES.values():
+            raise ValueError("route must be 'auto', 'direct' or 'stepped'")
+        x = None
+        if cube is not None:
+            x = NP.ascontiguousarray(cube, dtype=NP.complex128)
+            if x.shape != (nt, nbl, nchan):
+                raise ValueError('cube must be (nt, nbl, nchan)')
+        w, form = None, PRISIM_IMAGE_W_NONE
+        if weights is not None:
+            w = NP.ascontiguousarray(weights, dtype=NP.float64)
+            if w.shape == (nbl,):
+                form = PRISIM_IMAGE_W_BASELINE
+            elif w.shape == (nt, nbl, nchan):
+                form = PRISIM_IMAGE_W_FULL
+            else:
+                raise ValueError('weights must be None, (nbl,) or (nt, nbl, nchan)')
+        win = None
+        if window is not None:
+            win = NP.ascontiguousarray(NP.asarray(window) != 0, dtype=NP.uint8)
+            if win.shape != (npix,):
+                raise ValueError('window must be (npix,)')
+        fw = None
+        if fwhm_rad is not None:
+            fw = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(fwhm_rad, dtype=NP.float64), (nc,)))
+        maxiter = int(maxiter)
+        a = self.PrisimImcleanArgs()
+        a.npix, a.nbl, a.nchan, a.nt = npix, nbl, nchan, nt
+        a.unitvec, a.rot, a.aberr_beta, a.pc_dircos = _ptr(uv), _ptr(rt), _ptr(ab), _ptr(pc)
+        a.baselines, a.freqs_hz, a.cube, a.weights = _ptr(bl), _ptr(fq), _ptr(x), _ptr(w)
+        a.window, a.fwhm_rad = _ptr(win), _ptr(fw)
+        a.gain, a.threshold, a.maxiter = float(gain), float(threshold), maxiter
+        a.budget_bytes = int(budget_bytes or 0)
+        a.weight_form, a.chan_avg, a.route = form, 1 if chan_avg else 0, _route_code(route, IMAGING_ROUTES)
+        a.threshold_relative, a.poll_every = 1 if threshold_relative else 0, int(poll_every or 0)
+        shape = (npix,) if chan_avg else (npix, nchan)
+        rows = max(maxiter, 0)
+        residual = NP.empty(shape, dtype=NP.float64)
+        restored = NP.empty(shape, dtype=NP.float64) if fw is not None else None
+        pixel = NP.full((nc, rows), -1, dtype=NP.int32)
+        flux = NP.zeros((nc, rows), dtype=NP.float64)
+        ncomp, status = NP.empty(nc, dtype=NP.int32), NP.empty(nc, dtype=NP.int32)
+        peak0, wsum = NP.empty(nc, dtype=NP.float64), NP.empty(nc, dtype=NP.float64)
+        st = self.PrisimImcleanStats()
+        self._call('prisim_clean_image', a=a, out_residual=residual, out_restored=restored, out_comp_pixel=pixel, out_comp_flux=flux,
+                   out_ncomp=ncomp, out_status=status, out_peak0=peak0, out_wsum=wsum, stats=st)
+        longest = int(ncomp.max()) if nc else 0
+        return {'residual': residual, 'restored': restored, 'comp_pixel': NP.ascontiguousarray(pixel[:, :longest]),
+                'comp_flux': NP.ascontiguousarray(flux[:, :longest]), 'ncomp': ncomp, 'status': status, 'peak0': peak0, 'wsum': wsum,
+                'stats': dict(_stats_dict(st, route=IMAGING_ROUTES), resident=x is None)}
 
     # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
     def closure_delay_spectra(self, wts, m, df, phases=None, cube=None, legs=None, conj=None, bpwts=None, freq_wts=None, masks=None,

@@ -2773,12 +2773,13 @@ class ApertureSynthesis(object):
 
     Attributes as in the reference (:9136-9163): ia, f, df, n_acc, lst, phase_center, phase_center_coords, pointing_center,
     pointing_coords, baselines, timestamp, latitude, blxyz, uvw_lambda, uvw, blc, trc, grid_blc, grid_trc, gridu, gridv, gridw,
-    grid_ready; and image_stats, the statistics of the last image() or psf().
+    grid_ready; and image_stats, the statistics of the last image(), psf() or clean().
 
     Departures from the reference: setUVWgrid is not ported -- its grid comes from GRD.grid_3d, whose source is not part of the
     reference tree, and the direct transform needs no grid; grid_ready stays False.  genUVW with a 'radec' phase centre takes
     HA = LST - RA and the centre's declination, as _pc_dircos and project_baselines do (the reference puts HA = LST and Dec = 0, :9180).
-    image(), psf() and dircos_grid() are additions.  There is no CPU path."""
+    image(), psf(), clean() (Hogbom's CLEAN of image() with the exact beam, include/prisim_imclean.h) and dircos_grid() are additions.
+    There is no CPU path."""
 
     def __init__(self, interferometer_array=None):
         if interferometer_array is None:
@@ -2879,7 +2880,9 @@ class ApertureSynthesis(object):
             beta.append(NP.asarray(b, dtype=NP.float64).reshape(3))
         return uv, NP.stack(rot), NP.stack(beta)
 
-    def _synthesize(self, kind, directions, coords, datakey, weights, chan_avg, epoch, route, budget_bytes):
+    def _prepare(self, kind, directions, coords, datakey, weights, epoch, route):
+        """What image(), psf() and clean() hand to the context: (unit vectors, rotations, aberration or None, phase centres, weights
+        snapshot-major or None, cube snapshot-major or None for the resident one -- and for the beam, which reads none)."""
         ia = self.ia
         nt = len(ia.lst)
         if nt < 1:
@@ -2913,6 +2916,11 @@ class ApertureSynthesis(object):
                     raise ValueError('{0} must have shape (nbl, nchan, n_acc)'.format(names[datakey]))
                 cube = NP.ascontiguousarray(NP.transpose(vis, (2, 0, 1)), dtype=NP.complex128)
         pc = ia._pc_dircos(ia.phase_center, ia.phase_center_coords)
+        return uv, rot, beta, pc, w, cube
+
+    def _synthesize(self, kind, directions, coords, datakey, weights, chan_avg, epoch, route, budget_bytes):
+        ia = self.ia
+        uv, rot, beta, pc, w, cube = self._prepare(kind, directions, coords, datakey, weights, epoch, route)
         image, wsum, st = ia._ctx.dirty_image(uv, rot, pc, ia._baselines_local(), ia.channels, cube=cube, weights=w, kind=kind,
                                               chan_avg=bool(chan_avg), aberr_beta=beta, route=route, budget_bytes=int(budget_bytes or 0))
         self.image_stats = dict(st, wsum=wsum)
@@ -2939,3 +2947,69 @@ class ApertureSynthesis(object):
     def psf(self, directions, coords='dircos', weights=None, chan_avg=False, epoch=None, route='auto', budget_bytes=None):
         """The synthesized beam at the given directions: image() of V = 1, centred on every snapshot's phase centre, where it is 1."""
         return self._synthesize('psf', directions, coords, None, weights, chan_avg, epoch, route, budget_bytes)
+
+    def clean(self, directions, coords='dircos', datakey='noiseless', weights=None, chan_avg=False, epoch=None, gain=0.1, maxiter=10000,
+              threshold=5e-3, threshold_type='relative', window=None, fwhm=None, restore=True, route='auto', budget_bytes=None):
+        """Hogbom CLEAN of image() with the exact beam, on the GPU (include/prisim_imclean.h): per channel (or for the band's image with
+        chan_avg) and iteration, the pixel of the largest |residual| inside the window becomes a component of gain times its value,
+        and the dirty image of that component's own visibilities -- the synthesized beam at that very place, w-term and frames
+        included, no shift invariance assumed -- is subtracted from every pixel.  The residual therefore always is the dirty image
+        of the visibilities less those of the components.  A channel ends when its peak is at or below the threshold or when it
+        holds maxiter components; a channel whose weights are all zero is NaN and holds none.
+
+        directions, coords, datakey, weights, chan_avg, epoch, route as image() takes them; the noiseless cube is read where it lies
+        on the device under the same condition.
+        gain, maxiter, threshold, threshold_type   as complex1dClean takes them, with its checks and exceptions: gain a float in
+                     (0, 1), maxiter a positive int, threshold a positive scalar, below 1 when threshold_type is 'relative' (a
+                     fraction of the channel's first peak) rather than 'absolute'.
+        window       None, or (npix,) booleans: the pixels that may hold components.  Every pixel is updated all the same.
+        fwhm         the restoring beam in degrees, a scalar or (nc,).  None: c / (f max|b|) radians per channel, at the mean frequency
+                     with chan_avg -- a convention (the diffraction scale of the longest baseline), not a fit to the synthesized beam.
+        restore      False: no restored image.
+        budget_bytes device bytes the resident image may take (None: 1 GiB); an image that does not fit is refused, not streamed.
+        Returns a dict: 'residual' and 'restored' (None without restore) (npix, nchan) or (npix,); 'model', of the same shape, the
+        component fluxes summed per pixel; 'components' {'pixel' int32, 'flux' (nc, longest list; -1 and 0 past a channel's own),
+        'count' (nc,)}; 'status' (nc,) of _abi.PRISIM_IMCLEAN_THRESHOLD, _MAXITER or _DEAD; 'peak0' and 'threshold' (nc,) the first peak
+        and the level the channel was cleaned to; 'fwhm' (nc,) degrees.  The entry's statistics, and 'wsum', are left in image_stats."""
+        from . import delay_spectrum as DS                            # (imports this module)
+        threshold = DS._check_clean_args(threshold_type, threshold, gain, maxiter)
+        DS._check_gain_maxiter(gain, maxiter)
+        ia = self.ia
+        uv, rot, beta, pc, w, cube = self._prepare('dirty', directions, coords, datakey, weights, epoch, route)
+        npix, nchan = uv.shape[0], ia.channels.size
+        nc = 1 if chan_avg else nchan
+        win = None
+        if window is not None:
+            win = NP.asarray(window)
+            if win.shape != (npix,):
+                raise ValueError('window must be None or (npix,)')
+            win = win != 0
+            if not win.any():
+                raise ValueError('window holds no pixel')
+        bl = ia._baselines_local()
+        if fwhm is None:
+            f = NP.asarray(ia.channels, dtype=NP.float64)
+            longest = float(NP.sqrt(NP.max(NP.sum(NP.asarray(bl, dtype=NP.float64) ** 2, axis=1))))
+            if not longest > 0.0:
+                raise ValueError('the default fwhm needs a baseline of non-zero length')
+            fwhm_rad = C_LIGHT / ((NP.array([f.mean()]) if chan_avg else f) * longest)
+        else:
+            fwhm_rad = NP.radians(NP.asarray(fwhm, dtype=NP.float64))
+            if fwhm_rad.ndim == 0:
+                fwhm_rad = NP.full(nc, float(fwhm_rad))
+            if fwhm_rad.shape != (nc,):
+                raise ValueError('fwhm must be None, a scalar or ({0},)'.format(nc))
+            if not NP.all(NP.isfinite(fwhm_rad) & (fwhm_rad > 0.0)):
+                raise ValueError('fwhm must be positive and finite')
+        r = ia._ctx.clean_image(uv, rot, pc, bl, ia.channels, cube=cube, weights=w, chan_avg=bool(chan_avg), aberr_beta=beta,
+                                gain=gain, maxiter=maxiter, threshold=threshold, threshold_relative=threshold_type == 'relative',
+                                window=win, fwhm_rad=fwhm_rad if restore else None, route=route, budget_bytes=int(budget_bytes or 0))
+        self.image_stats = dict(r['stats'], wsum=r['wsum'])
+        count = NP.asarray(r['ncomp'])
+        model = NP.zeros((npix, nc), dtype=NP.float64)
+        for k in range(nc):
+            NP.add.at(model[:, k], r['comp_pixel'][k, :count[k]], r['comp_flux'][k, :count[k]])
+        peak0 = NP.asarray(r['peak0'])
+        return {'residual': r['residual'], 'restored': r['restored'] if restore else None, 'model': model[:, 0] if chan_avg else model,
+                'components': {'pixel': r['comp_pixel'], 'flux': r['comp_flux'], 'count': count}, 'status': r['status'], 'peak0': peak0,
+                'threshold': threshold * peak0 if threshold_type == 'relative' else NP.full(nc, threshold), 'fwhm': NP.degrees(fwhm_rad)}
