@@ -336,6 +336,23 @@ class _PrisimImcleanArgs(C.Structure):
                 ('threshold_relative', C.c_int32), ('poll_every', C.c_int32), ('reserved_', C.c_int32)]
 
 
+class _PrisimMosaicStats(C.Structure):
+    """prisim_mosaic_stats of include/prisim_mosaic.h, public as Context.PrisimMosaicStats (see _PrisimCpxpsStats)."""
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('terms', C.c_int64), ('beam_values', C.c_int64), ('chunks', C.c_int64),
+                ('chunk_pixels', C.c_int64), ('pixel_bytes', C.c_int64), ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64),
+                ('download_bytes', C.c_int64), ('route', C.c_int32), ('streams', C.c_int32), ('chan_tile', C.c_int32), ('reseed', C.c_int32),
+                ('lds_bytes', C.c_int32), ('block_pixels', C.c_int32)]
+
+
+class _PrisimMosaicArgs(C.Structure):
+    """prisim_mosaic_args of include/prisim_mosaic.h, public as Context.PrisimMosaicArgs."""
+    _fields_ = [('npix', C.c_int64), ('nbl', C.c_int64), ('nchan', C.c_int64), ('nt', C.c_int64), ('unitvec', C.c_void_p), ('rot', C.c_void_p),
+                ('aberr_beta', C.c_void_p), ('pc_dircos', C.c_void_p), ('baselines', C.c_void_p), ('freqs_hz', C.c_void_p), ('cube', C.c_void_p),
+                ('weights', C.c_void_p), ('weight_form', C.c_int32), ('chan_avg', C.c_int32), ('route', C.c_int32), ('beam_kind', C.c_int32),
+                ('diameter_m', C.c_double), ('beam_pc_dircos', C.c_double * 3), ('beam_pc_snap', C.c_void_p), ('ext', C.c_void_p),
+                ('n_ext', C.c_int64), ('pbmin', C.c_double), ('budget_bytes', C.c_int64)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -402,6 +419,20 @@ def _want_bits(want, bits):
     return flag
 
 
+def _beam_ext_array(ext):
+    """The beam extensions of a call as the library takes them: ext is None, a dict (make_beam_ext) or a sequence of one dict per
+    snapshot.  Returns (the dicts, a contiguous PrisimBeamExt array of at least one element, the structs that keep the beamformer
+    arrays alive while the array is in use)."""
+    exts = [] if ext is None else ([ext] if isinstance(ext, dict) else list(ext))
+    xs = (PrisimBeamExt * max(len(exts), 1))()
+    keep = []
+    for i, e in enumerate(exts):
+        x = make_beam_ext(e)
+        keep.append(x)
+        C.memmove(C.byref(xs, i * C.sizeof(PrisimBeamExt)), C.byref(x), C.sizeof(PrisimBeamExt))
+    return exts, xs, keep
+
+
 def _route_code(name, routes):
     """The library's code of a route: 'auto' (-1 in every header) or a name of the table routes (code: name); KeyError on another."""
     return -1 if name == 'auto' else {v: k for k, v in routes.items()}[name]
@@ -418,6 +449,7 @@ STRUCTS = {
     'prisim_antpower_stats': _PrisimAntpowerStats, 'prisim_antpower_args': _PrisimAntpowerArgs,
     'prisim_imaging_stats': _PrisimImagingStats, 'prisim_imaging_args': _PrisimImagingArgs, 'prisim_gains_stats': PrisimGainsStats,
     'prisim_imclean_stats': _PrisimImcleanStats, 'prisim_imclean_args': _PrisimImcleanArgs,
+    'prisim_mosaic_stats': _PrisimMosaicStats, 'prisim_mosaic_args': _PrisimMosaicArgs,
 }
 
 # The C ABI, declared once: per header of include/, its functions in the header's order, each as
@@ -549,6 +581,10 @@ _PROTOTYPES = {
         int prisim_clean_image(p ctx, *prisim_imclean_args a, p out_residual, p out_restored, p out_comp_pixel, p out_comp_flux, p out_ncomp,
             p out_status, p out_peak0, p out_wsum, *prisim_imclean_stats stats);
     ''',
+    'prisim_mosaic.h': '''
+        int prisim_mosaic_image(p ctx, *prisim_mosaic_args a, p out_mosaic, p out_pb_eff, p out_num, p out_den, p out_wsum,
+            *prisim_mosaic_stats stats);
+    ''',
     'prisim_gains.h': '''
         int prisim_gains_eval_spline(p ctx, q nrows, i kx, i ky, p nx, p ny, p kx_off, p ky_off, p c_off, q nknots, p knots, q ncoefs, p coefs,
             q nt, p times, q nchan, p freqs, *p out, *prisim_gains_stats stats);
@@ -586,9 +622,9 @@ def _parse_prototypes(table):
 FUNCTIONS, HEADER_EXPORTS = _parse_prototypes(_PROTOTYPES)
 # the functions of each header (tests and tools import these names)
 (EXPORTS, CLEAN_EXPORTS, SUBBAND_EXPORTS, RUNS_EXPORTS, CLOSURE_EXPORTS, CPDELAY_EXPORTS, CPBINS_EXPORTS, CPDIFF_EXPORTS, CPFT_EXPORTS,
- CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMCLEAN_EXPORTS, GAINS_EXPORTS) = (
+ CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMCLEAN_EXPORTS, MOSAIC_EXPORTS, GAINS_EXPORTS) = (
     HEADER_EXPORTS['prisim_%s.h' % h] for h in ('hip', 'clean', 'subband', 'runs', 'closure', 'cpdelay', 'cpbins', 'cpdiff', 'cpft', 'cpxps',
-                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imclean', 'gains'))
+                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imclean', 'mosaic', 'gains'))
 
 
 class PrisimHipError(RuntimeError):
@@ -1411,13 +1447,7 @@ class Context(object):
             sp = NP.ascontiguousarray(spindex, dtype=NP.float64).ravel()
             if fr.size != nsrc or sp.size != nsrc:
                 raise ValueError('flux_ref and spindex must have nsrc elements')
-        exts = [] if ext is None else ([ext] if isinstance(ext, dict) else list(ext))
-        xs = (PrisimBeamExt * max(len(exts), 1))()
-        keep = []
-        for i, e in enumerate(exts):
-            x = make_beam_ext(e)
-            keep.append(x)
-            C.memmove(C.byref(xs, i * C.sizeof(PrisimBeamExt)), C.byref(x), C.sizeof(PrisimBeamExt))
+        exts, xs, keep = _beam_ext_array(ext)
         a = self.PrisimAntpowerArgs()
         a.nsrc, a.nchan, a.nsnap = nsrc, nchan, nsnap
         a.unitvec, a.flux_ref, a.spindex, a.flux_spectrum = _ptr(uv), _ptr(fr), _ptr(sp), _ptr(fs)
@@ -1497,6 +1527,76 @@ class Context(object):
         st = self.PrisimImagingStats()
         self._call('prisim_dirty_image', a=a, out_image=image, out_wsum=wsum, stats=st)
         return image, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=x is None and kind == 'dirty')
+
+    # ---- beam-weighted mosaics of the snapshots (include/prisim_mosaic.h) ----
+    PrisimMosaicStats = _PrisimMosaicStats
+    PrisimMosaicArgs = _PrisimMosaicArgs
+
+    def mosaic_image(self, unitvec, rot, pc_dircos, baselines, freqs_hz, beam_kind, diameter_m, beam_pc_dircos=(0.0, 0.0, 1.0), ext=None,
+                     cube=None, weights=None, chan_avg=False, aberr_beta=None, pbmin=0.1, route='auto', budget_bytes=0, want_sums=True):
+        """The beam-weighted linear mosaic of the snapshots at the given directions on the device (prisim_mosaic_image):
+        sum_t A_t D_t / sum_t A_t^2 W_t with D_t the direct Fourier sum of snapshot t (dirty_image), W_t its weight sum and A_t the
+        power pattern of the primary beam at the direction in that snapshot, 0 below the horizon.  The geometry, cube, weights,
+        chan_avg, route and budget_bytes as dirty_image takes them; the beam as antenna_power takes it: beam_kind, diameter_m,
+        beam_pc_dircos -- (3,), or (nt, 3) for an element pointing that moves from snapshot to snapshot -- and ext, a dict
+        (make_beam_ext), None, or a sequence of one dict per snapshot.  pbmin in [0, 1): a pixel whose
+        effective beam sqrt(Q / Wtot) is below it is NaN; 0 masks only Q == 0.  Returns (mosaic (npix, nchan) or (npix,), num, den
+        (npix, nchan) -- None without want_sums --, wsum (nchan,), stats); stats['pb_eff'] is the effective beam in the shape of the
+        mosaic and stats['resident'] whether the resident cube was read."""
+        uv = NP.ascontiguousarray(unitvec, dtype=NP.float64).reshape(-1, 3)
+        rt = NP.ascontiguousarray(rot, dtype=NP.float64).reshape(-1, 9)
+        pc = NP.ascontiguousarray(pc_dircos, dtype=NP.float64).reshape(-1, 3)
+        bl = NP.ascontiguousarray(baselines, dtype=NP.float64).reshape(-1, 3)
+        fq = NP.ascontiguousarray(freqs_hz, dtype=NP.float64).ravel()
+        npix, nt, nbl, nchan = uv.shape[0], rt.shape[0], bl.shape[0], fq.size
+        if pc.shape[0] != nt:
+            raise ValueError('pc_dircos must have one row per snapshot')
+        ab = None
+        if aberr_beta is not None:
+            ab = NP.ascontiguousarray(aberr_beta, dtype=NP.float64).reshape(-1, 3)
+            if ab.shape[0] != nt:
+                raise ValueError('aberr_beta must have one row per snapshot')
+        if route != 'auto' and route not in IMAGING_ROUTES.values():
+            raise ValueError("route must be 'auto', 'direct' or 'stepped'")
+        x = None
+        if cube is not None:
+            x = NP.ascontiguousarray(cube, dtype=NP.complex128)
+            if x.shape != (nt, nbl, nchan):
+                raise ValueError('cube must be (nt, nbl, nchan)')
+        w, form = None, PRISIM_IMAGE_W_NONE
+        if weights is not None:
+            w = NP.ascontiguousarray(weights, dtype=NP.float64)
+            if w.shape == (nbl,):
+                form = PRISIM_IMAGE_W_BASELINE
+            elif w.shape == (nt, nbl, nchan):
+                form = PRISIM_IMAGE_W_FULL
+            else:
+                raise ValueError('weights must be None, (nbl,) or (nt, nbl, nchan)')
+        bpc = NP.ascontiguousarray(beam_pc_dircos, dtype=NP.float64)
+        if bpc.shape not in ((3,), (nt, 3)):
+            raise ValueError('beam_pc_dircos must be (3,) or one row per snapshot (nt, 3)')
+        exts, xs, keep = _beam_ext_array(ext)
+        a = self.PrisimMosaicArgs()
+        a.npix, a.nbl, a.nchan, a.nt = npix, nbl, nchan, nt
+        a.unitvec, a.rot, a.aberr_beta, a.pc_dircos = _ptr(uv), _ptr(rt), _ptr(ab), _ptr(pc)
+        a.baselines, a.freqs_hz, a.cube, a.weights = _ptr(bl), _ptr(fq), _ptr(x), _ptr(w)
+        a.weight_form, a.chan_avg, a.route = form, 1 if chan_avg else 0, _route_code(route, IMAGING_ROUTES)
+        a.beam_kind, a.diameter_m = int(beam_kind), float(diameter_m)
+        a.beam_pc_dircos[:] = bpc.reshape(-1, 3)[0].tolist()
+        a.beam_pc_snap = _ptr(bpc) if bpc.ndim == 2 else None
+        a.ext = C.cast(xs, C.c_void_p) if exts else None
+        a.n_ext = len(exts)
+        a.pbmin = float(pbmin)
+        a.budget_bytes = int(budget_bytes or 0)
+        shape = (npix,) if chan_avg else (npix, nchan)
+        mosaic, pb_eff = NP.empty(shape, dtype=NP.float64), NP.empty(shape, dtype=NP.float64)
+        num = NP.empty((npix, nchan), dtype=NP.float64) if want_sums else None
+        den = NP.empty((npix, nchan), dtype=NP.float64) if want_sums else None
+        wsum = NP.empty(nchan, dtype=NP.float64)
+        st = self.PrisimMosaicStats()
+        self._call('prisim_mosaic_image', a=a, out_mosaic=mosaic, out_pb_eff=pb_eff, out_num=num, out_den=den, out_wsum=wsum, stats=st)
+        del keep
+        return mosaic, num, den, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=x is None, pb_eff=pb_eff)
 
     # ---- Hogbom CLEAN of dirty images with the exact beam (include/prisim_imclean.h) ----
     PrisimImcleanStats = _PrisimImcleanStats

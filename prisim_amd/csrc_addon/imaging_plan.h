@@ -48,15 +48,16 @@ struct ImagingPlan {
   Chunks chunks;
   const char* refusal;
 };
-inline ImagingPlan imaging_plan(int64_t npix, int64_t nbl, int64_t nchan, int64_t nt, int weight_form, bool chan_avg, int64_t budget_bytes,
-                                int64_t lds_max, int asked, bool uniform, int max_streams) {
+// ... of an entry whose chunk buffers take pixel_bytes a pixel (prisim_mosaic_image plans with this too, mosaic_plan.h)
+inline ImagingPlan pixel_plan(int64_t npix, int64_t nbl, int64_t nchan, int64_t nt, int weight_form, int64_t pixel_bytes, int64_t budget_bytes,
+                              int64_t lds_max, int asked, bool uniform, int max_streams) {
   ImagingPlan p{};
   p.tile = kImagingTile;
   p.ntiles = (nchan + p.tile - 1) / p.tile;
   p.block = kImagingBlock;
   p.nblocks = (npix + p.block - 1) / p.block;
   p.lds = kImagingLds;
-  p.pixel_bytes = imaging_pixel_bytes(nchan, nt, chan_avg);
+  p.pixel_bytes = pixel_bytes;
   p.route = asked == kImagingDirect ? kImagingDirect : asked == kImagingStepped ? kImagingStepped : uniform ? kImagingStepped : kImagingDirect;
   p.reseed = p.route == kImagingStepped ? kImagingReseed : 1;
   p.chunks = chunks_of(npix, p.block, 1);
@@ -78,6 +79,11 @@ inline ImagingPlan imaging_plan(int64_t npix, int64_t nbl, int64_t nchan, int64_
   p.chunks = chunks_of(npix, chunk, ns);
   p.buffer_bytes = p.chunks.nstreams * chunk * p.pixel_bytes;
   return p;
+}
+inline ImagingPlan imaging_plan(int64_t npix, int64_t nbl, int64_t nchan, int64_t nt, int weight_form, bool chan_avg, int64_t budget_bytes,
+                                int64_t lds_max, int asked, bool uniform, int max_streams) {
+  return pixel_plan(npix, nbl, nchan, nt, weight_form, imaging_pixel_bytes(nchan, nt, chan_avg), budget_bytes, lds_max, asked, uniform,
+                    max_streams);
 }
 
 }  // namespace pint

@@ -35,6 +35,7 @@
 #include "../../include/prisim_antpower.h"
 #include "../csrc_addon/addon_internal.h"
 #include "../csrc_addon/antpower_plan.h"
+#include "../csrc_addon/beam_setup.h"
 
 namespace {
 
@@ -154,32 +155,6 @@ __global__ void __launch_bounds__(kThreads) k_ap_finish(const double* __restrict
   if (threadIdx.x == 0) *up_total = cnt[0];
 }
 
-// the prisim_beam_ext -> BeamParams mapping of sky_beam_flux (../csrc/capi.cpp), restated; bf: the device copy of the beamformer's
-// element arrays (positions, delays, gains, in that order) or null
-void fill_beam(BeamParams& bp, const prisim_antpower_args& a, const prisim_beam_ext* x, const double* bf) {
-  bp.beam_kind = a.beam_kind;
-  bp.diameter = a.diameter_m;
-  bp.bpc_x = a.beam_pc_dircos[0]; bp.bpc_y = a.beam_pc_dircos[1]; bp.bpc_z = a.beam_pc_dircos[2];
-  if (x) {
-    const int bf_n = x->bf_nelem, bf_r = bf_n > 0 ? x->bf_nrand : 0;
-    bp.dip_x = x->dipole_dircos[0]; bp.dip_y = x->dipole_dircos[1]; bp.dip_z = x->dipole_dircos[2];
-    bp.dipole_mode = x->dipole_mode;
-    bp.nax1 = x->array_nax1; bp.nax2 = x->array_nax2; bp.sep1 = x->array_sep1; bp.sep2 = x->array_sep2;
-    const double ang = x->array_east2ax1_deg * M_PI / 180.0;
-    bp.rot_c = std::cos(ang); bp.rot_s = std::sin(ang);
-    bp.apc_x = x->array_pc_dircos[0]; bp.apc_y = x->array_pc_dircos[1]; bp.apc_z = x->array_pc_dircos[2];
-    bp.gp_height = x->ground_height; bp.gp_modify = x->ground_modify; bp.gp_scale = x->ground_scale; bp.gp_max = x->ground_max;
-    if (bf_n > 0) {
-      bp.bf_nelem = bf_n; bp.bf_nrand = bf_r;
-      bp.bf_pos = bf;
-      bp.bf_delays = bp.bf_pos + (size_t)bf_n * 3;
-      bp.bf_gains = bp.bf_delays + (size_t)bf_n * bf_r;
-    }
-    if (a.beam_kind == PRISIM_BEAM_POLY)
-      for (int i = 0; i < 4; ++i) bp.poly[i] = x->poly_coef[i];
-  }
-}
-
 int check_args(prisim_ctx* ctx, const prisim_antpower_args* a, const double* out_power) {
   if (!a) return fail(ctx, PRISIM_EINVAL, "the argument struct is NULL");
   if (!out_power) return fail(ctx, PRISIM_EINVAL, "out_power is NULL");
@@ -217,12 +192,7 @@ int check_args(prisim_ctx* ctx, const prisim_antpower_args* a, const double* out
         return fail(ctx, PRISIM_EINVAL, "aberr_beta of snapshot " + std::to_string(t) + " must be a velocity / c with |beta| < 0.01");
     }
   }
-  if (a->n_ext != 0 && a->n_ext != 1 && a->n_ext != a->nsnap) return fail(ctx, PRISIM_EINVAL, "n_ext must be 0, 1 or nsnap");
-  if (a->n_ext > 0 && !a->ext) return fail(ctx, PRISIM_EINVAL, "ext is NULL with n_ext > 0");
-  if (a->n_ext == 0) return check_beam_spec(ctx, a->beam_kind, a->diameter_m, a->beam_pc_dircos, nullptr);
-  for (int64_t e = 0; e < a->n_ext; ++e)
-    if (int rc = check_beam_spec(ctx, a->beam_kind, a->diameter_m, a->beam_pc_dircos, a->ext + e)) return rc;
-  return PRISIM_OK;
+  return check_beams(ctx, a->beam_kind, a->diameter_m, a->beam_pc_dircos, a->ext, a->n_ext, a->nsnap, "nsnap");
 }
 
 int antenna_power(prisim_ctx* ctx, const prisim_antpower_args* a, double* out_power, double* out_num, double* out_den,
@@ -273,19 +243,8 @@ int antenna_power(prisim_ctx* ctx, const prisim_antpower_args* a, double* out_po
   DEV_UPLOAD(ctx, wk.dev, d_ones, ones, s0);
   DEV_ALLOC(ctx, wk.dev, d_zeros, span * 8);
   HIPCHK(ctx, hipMemsetAsync(d_zeros, 0, (size_t)span * 8, s0));
-  std::vector<const double*> d_bf((size_t)std::max<int64_t>(a->n_ext, 1), nullptr);
-  for (int64_t e = 0; e < a->n_ext; ++e) {
-    const prisim_beam_ext* x = a->ext + e;
-    if (x->bf_nelem <= 0) continue;
-    const size_t np = (size_t)x->bf_nelem * 3, nd = (size_t)x->bf_nelem * x->bf_nrand;
-    double* b = nullptr;
-    DEV_ALLOC(ctx, wk.dev, b, beamformer_doubles(x) * sizeof(double));
-    HIPCHK(ctx, hipMemcpyAsync(b, x->bf_pos, np * 8, hipMemcpyHostToDevice, s0));
-    HIPCHK(ctx, hipMemcpyAsync(b + np, x->bf_delays, nd * 8, hipMemcpyHostToDevice, s0));
-    HIPCHK(ctx, hipMemcpyAsync(b + np + nd, x->bf_gains, nd * 8, hipMemcpyHostToDevice, s0));
-    d_bf[(size_t)e] = b;
-    upload += (int64_t)(np + 2 * nd) * 8;
-  }
+  std::vector<const double*> d_bf;
+  if (int rc = upload_beamformers(ctx, wk.dev, a->ext, a->n_ext, s0, d_bf, upload)) return rc;
   int32_t* d_flag = nullptr;
   DEV_ALLOC(ctx, wk.dev, d_flag, sizeof(int32_t));
   HIPCHK(ctx, hipMemsetAsync(d_flag, 0, sizeof(int32_t), s0));
@@ -314,7 +273,7 @@ int antenna_power(prisim_ctx* ctx, const prisim_antpower_args* a, double* out_po
     for (int k = 0; k < 3; ++k) fr.beta[k] = a->aberr_beta ? a->aberr_beta[t * 3 + k] : 0.0;
     const int64_t e = a->n_ext == nsnap ? t : 0;
     BeamParams bp{};
-    fill_beam(bp, *a, a->n_ext > 0 ? a->ext + e : nullptr, d_bf[(size_t)e]);
+    fill_beam(bp, a->beam_kind, a->diameter_m, a->beam_pc_dircos, a->n_ext > 0 ? a->ext + e : nullptr, d_bf[(size_t)e]);
     bp.dirs = (const double*)d_dirs[i];
     bp.flux_ref = d_ones;
     bp.spindex = d_zeros;
@@ -344,14 +303,7 @@ int antenna_power(prisim_ctx* ctx, const prisim_antpower_args* a, double* out_po
   };
   if (int rc = chunk_loop(ctx, st, chunks_of(nsnap, 1, nstreams), nsnap, no_step, kernels, no_step)) return rc;
 
-  if (a->beam_kind == PRISIM_BEAM_POLY) {             // the reference's validity checks (primary_beams.py:510-512, :802-807)
-    int32_t hflag = 0;
-    HIPCHK(ctx, hipMemcpy(&hflag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (hflag & 2)
-      return fail(ctx, PRISIM_EINVAL, "Primary beam values were found to be NaN in some case(s). Check if the polynomial equations are valid for the frequencies specified.");
-    if (hflag & 1)
-      return fail(ctx, PRISIM_EINVAL, "Primary beam exceeds unity by a significant amount. Check the validity of the Primary beam equation for the angles specified.");
-  }
+  if (int rc = poly_beam_verdict(ctx, a->beam_kind, d_flag)) return rc;
   std::vector<int64_t> uptot((size_t)nsnap, 0);
   HIPCHK(ctx, hipMemcpy(uptot.data(), d_uptot, (size_t)nsnap * 8, hipMemcpyDeviceToHost));
   HIPCHK(ctx, hipMemcpy(out_power, d_out, (size_t)nout * 8, hipMemcpyDeviceToHost));

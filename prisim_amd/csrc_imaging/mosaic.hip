@@ -1,0 +1,383 @@
+// mosaic.hip -- the beam-weighted linear mosaic of the snapshots of a visibility cube for gfx950 (include/prisim_mosaic.h):
+// mosaic[p][k] = sum_t A_t D_t / sum_t A_t^2 W_t, with D_t[p][k] = sum_b w (Re V cos phi - Im V sin phi) the direct Fourier sum of
+// snapshot t alone (imaging.hip), W_t[k] = sum_b w, and A_t[p][k] the power pattern of the primary beam at the pixel's direction in
+// that snapshot, 0 below the horizon.  It joins two statements this library already has and restates neither: the fused analytic beam
+// (launch_beam_flux of ../csrc/aux_kernels.hip with unit flux, as antpower.hip calls it) and the rows of the direct Fourier sum
+// (img_rows of imaging_kernels.h, as it stands).
+//
+// Once per call:
+//   k_mos_wsum   W_t[k] = sum_b w[t][b][k] as [nt][nchan], b ascending as in k_img_wsum, and Wtot[k] = sum_t W_t[k], t ascending; one
+//                thread per channel.  k_img_wtot sums Wtot over k for chan_avg.
+// Per chunk of pixels (contiguous, a whole number of blocks of 256), on the chunk's stream:
+//   k_mos_dirs   s[t][pixel] = normalise(R_t (u + beta_t)) as (l, m, n, 0), the rows BeamParams.dirs reads, and dd = s - s0[t]: the
+//                operations of k_img_dirs and k_ap_dirs, one after the other.
+//   then for t = 0 .. nt - 1, in this order:
+//     launch_beam_flux with unit flux (flux_ref = 1, spindex = 0: pb exp2(0) = pb exactly) on the chunk's directions of snapshot t
+//                into pb_tile[count][nchan], the one tile of the stream: 8 nchan bytes a pixel, not 8 nt nchan.
+//     k_mos_sum  the hot path, one launch per snapshot.  The workgroup of k_img_sum: 256 pixels (one per thread) and a tile of 32
+//                channels, 32 baselines at a time staged in LDS as (w Re V, w Im V) with b / c, img_rows<STEPPED, false> on them, 32
+//                fp64 accumulators per thread.  The epilogue reads the thread's 32 beam values, puts 0 in their place where the
+//                direction is below the horizon, and writes N = fma(A, acc, N) and Q = fma(A A, W_t, Q); snapshot 0 starts from 0 and
+//                reads nothing.  The launch per snapshot is what fixes the order in t, keeps the register budget of k_img_sum (the
+//                beam values are read when the accumulators are done, one at a time) and lets one beam tile serve every snapshot; a
+//                t loop inside one launch would need the beam of all snapshots resident (8 nt nchan bytes a pixel) or a second set of
+//                32 accumulators for N beside D_t (64 more VGPRs: half the occupancy).  Its price is N and Q read and written once
+//                per snapshot, 32 B per (pixel, channel, snapshot) against the nbl rows the snapshot stages.
+//   k_mos_finish the division, the mask Q >= pbmin^2 Wtot (else NaN) and pb_eff = sqrt(Q / Wtot) per (pixel, channel); or, with
+//                chan_avg, k_mos_finish_band: the sums of N and Q over k ascending per pixel, then the same three.
+// No atomics, and neither the b sum nor the t sum is split: the bits do not depend on the chunks or the streams.  Built with
+// -ffp-contract=off like the other add-ons; the fused multiply-adds are written as fma().  The results are gathered in host buffers and
+// copied to the caller's arrays when every chunk is in, so that a failed call writes nothing.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/prisim_mosaic.h"
+#include "../csrc_addon/beam_setup.h"
+#include "../csrc_addon/mosaic_plan.h"
+// (img_rows, the frames, the weights and the argument checks are taken from here; the kernels of prisim_dirty_image itself are not launched)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"
+#include "imaging_kernels.h"
+#pragma clang diagnostic pop
+
+namespace {
+
+// grid-stride over nt * count: s4 and dd [nt][count] of pixels [p0, p0 + count)
+__global__ void __launch_bounds__(kThreads) k_mos_dirs(const double* __restrict__ uvec, const ImgFrame* __restrict__ frames, int64_t p0,
+                                                       int64_t count, int64_t nt, double4* __restrict__ s4, double4* __restrict__ dd) {
+  const int64_t total = nt * count;
+  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
+    const int64_t t = e / count, pl = e - t * count;
+    const ImgFrame& fr = frames[t];
+    const double* u = uvec + (p0 + pl) * 3;
+    const double t0 = u[0] + fr.beta[0], t1 = u[1] + fr.beta[1], t2 = u[2] + fr.beta[2];
+    const double v0 = (fr.rot[0] * t0 + fr.rot[1] * t1) + fr.rot[2] * t2;
+    const double v1 = (fr.rot[3] * t0 + fr.rot[4] * t1) + fr.rot[5] * t2;
+    const double v2 = (fr.rot[6] * t0 + fr.rot[7] * t1) + fr.rot[8] * t2;
+    const double nrm = sqrt((v0 * v0 + v1 * v1) + v2 * v2);
+    const double l = v0 / nrm, m = v1 / nrm, n = v2 / nrm;
+    s4[e] = make_double4(l, m, n, 0.0);
+    dd[e] = make_double4(l - fr.pc[0], m - fr.pc[1], n - fr.pc[2], 0.0);
+  }
+}
+
+// grid: x over the channels.  wt [nt][nchan], wtot [nchan]
+__global__ void __launch_bounds__(kThreads) k_mos_wsum(ImgWeights W, int64_t nt, int64_t nbl, int nchan, double* __restrict__ wt,
+                                                       double* __restrict__ wtot) {
+  const int k = (int)blockIdx.x * kThreads + threadIdx.x;
+  if (k >= nchan) return;
+  double tot = 0.0;
+  for (int64_t t = 0; t < nt; ++t) {
+    const double* row = W.w ? W.w + t * W.st + k * W.sk : nullptr;
+    double s = 0.0;
+#pragma unroll 8
+    for (int64_t b = 0; b < nbl; ++b) s += row ? row[b * W.sb] : 1.0;
+    wt[t * nchan + k] = s;
+    tot += s;
+  }
+  wtot[k] = tot;
+}
+
+struct MosParams {
+  const double2* cube;      // [nt][nbl][nchan]
+  ImgWeights W;
+  const double* bl;         // [nbl][3]
+  const double* freqs;      // [nchan]
+  const double4* dd;        // [count] of the chunk at snapshot t: s - s0
+  const double4* s4;        // [count] of the chunk at snapshot t: s, for the horizon
+  const double* pb;         // [count][nchan] the beam tile of snapshot t
+  const double* wt;         // [nchan] W_t
+  double df;                // the step of a uniform grid (STEPPED)
+  int64_t nbl, t, count;    // t: the snapshot of this launch; count: pixels of the chunk
+  int nchan;
+  double *N, *Q;            // [count][nchan] of the chunk: read unless t == 0, written
+};
+
+// grid: x = block of the chunk's pixels, y = channel tile.  LDS: kImagingLds
+template <bool STEPPED>
+__global__ void __launch_bounds__(kThreads) k_mos_sum(MosParams P) {
+  __shared__ double2 sh_v[NB * CT];     // (w Re V, w Im V)
+  __shared__ double sh_b[NB * 3];       // b / c
+  __shared__ double sh_f[CT];           // the tile's frequencies; past the band: the last channel's (their operand rows are 0)
+  const int tid = threadIdx.x;
+  const int k0 = (int)blockIdx.y * CT;
+  const int64_t pl_raw = (int64_t)blockIdx.x * kThreads + tid;
+  const bool p_valid = pl_raw < P.count;
+  const int64_t pl = p_valid ? pl_raw : P.count - 1;
+  const int64_t t = P.t;
+  if (tid < CT) sh_f[tid] = P.freqs[k0 + tid < P.nchan ? k0 + tid : P.nchan - 1];
+  double acc[CT];
+#pragma unroll
+  for (int k = 0; k < CT; ++k) acc[k] = 0.0;
+  const double f0 = P.freqs[k0];          // k0 < nchan: the grid has ceil(nchan / CT) tiles
+  const double4 d = P.dd[pl];
+  for (int64_t b0 = 0; b0 < P.nbl; b0 += NB) {
+    const int nb = P.nbl - b0 < NB ? (int)(P.nbl - b0) : NB;
+    __syncthreads();                      // the rows of the block before are read (and sh_f is written, the first time)
+#pragma unroll
+    for (int e = tid; e < NB * CT; e += kThreads) {
+      const int r = e / CT, c = e - r * CT, k = k0 + c;
+      double2 v = make_double2(0.0, 0.0);
+      if (r < nb && k < P.nchan) {
+        const int64_t b = b0 + r;
+        const double w = P.W.w ? P.W.w[t * P.W.st + b * P.W.sb + k * P.W.sk] : 1.0;
+        const double2 x = P.cube[(t * P.nbl + b) * P.nchan + k];
+        v = make_double2(w * x.x, w * x.y);
+      }
+      sh_v[e] = v;
+    }
+    if (tid < nb * 3) sh_b[tid] = P.bl[b0 * 3 + tid] * kInvC;
+    __syncthreads();
+    img_rows<STEPPED, false>(nb, sh_v, sh_b, sh_f, d, f0, P.df, acc);
+  }
+  if (!p_valid) return;
+  const bool up = P.s4[pl].z >= 0.0;
+  const int64_t at = pl * P.nchan + k0;
+#pragma unroll
+  for (int k = 0; k < CT; ++k)
+    if (k0 + k < P.nchan) {
+      const double A = up ? P.pb[at + k] : 0.0;
+      P.N[at + k] = fma(A, acc[k], t ? P.N[at + k] : 0.0);
+      P.Q[at + k] = fma(A * A, P.wt[k0 + k], t ? P.Q[at + k] : 0.0);
+    }
+}
+
+// grid-stride over count * nchan
+__global__ void __launch_bounds__(kThreads) k_mos_finish(const double* __restrict__ N, const double* __restrict__ Q, const double* __restrict__ wtot,
+                                                         int64_t count, int nchan, double pbmin, double* __restrict__ mosaic,
+                                                         double* __restrict__ pb_eff) {
+  const int64_t total = count * nchan;
+  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
+    const double w = wtot[e % nchan], q = Q[e];
+    mosaic[e] = q >= (pbmin * pbmin) * w ? N[e] / q : NAN;
+    pb_eff[e] = sqrt(q / w);
+  }
+}
+
+// grid: x over the chunk's pixels.  wband[0] = sum_k wtot[k]
+__global__ void __launch_bounds__(kThreads) k_mos_finish_band(const double* __restrict__ N, const double* __restrict__ Q,
+                                                              const double* __restrict__ wband, int64_t count, int nchan, double pbmin,
+                                                              double* __restrict__ mosaic, double* __restrict__ pb_eff) {
+  const int64_t pl = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (pl >= count) return;
+  double n = 0.0, q = 0.0;
+  for (int k = 0; k < nchan; ++k) {
+    n += N[pl * nchan + k];
+    q += Q[pl * nchan + k];
+  }
+  const double w = wband[0];
+  mosaic[pl] = q >= (pbmin * pbmin) * w ? n / q : NAN;
+  pb_eff[pl] = sqrt(q / w);
+}
+
+int mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosaic, double* out_pb_eff, double* out_num, double* out_den,
+                 double* out_wsum, prisim_mosaic_stats* stats) {
+  if (!ctx) return PRISIM_EINVAL;
+  const WallTime wall0 = wall_now();
+  if (!a) return fail(ctx, PRISIM_EINVAL, "the argument struct is NULL");
+  if (!out_mosaic) return fail(ctx, PRISIM_EINVAL, "out_mosaic is NULL");
+  // the fields shared with prisim_dirty_image, under its own checks
+  prisim_imaging_args ia{};
+  ia.npix = a->npix; ia.nbl = a->nbl; ia.nchan = a->nchan; ia.nt = a->nt;
+  ia.unitvec = a->unitvec; ia.rot = a->rot; ia.aberr_beta = a->aberr_beta; ia.pc_dircos = a->pc_dircos;
+  ia.baselines = a->baselines; ia.freqs_hz = a->freqs_hz; ia.cube = a->cube; ia.weights = a->weights;
+  ia.kind = PRISIM_IMAGE_DIRTY; ia.weight_form = a->weight_form; ia.chan_avg = a->chan_avg; ia.route = a->route;
+  ia.budget_bytes = a->budget_bytes;
+  if (int rc = check_args(ctx, &ia, out_mosaic)) return rc;
+  if (!(a->pbmin >= 0.0 && a->pbmin < 1.0)) return fail(ctx, PRISIM_EINVAL, "pbmin must lie in [0, 1)");
+  if (int rc = check_beams(ctx, a->beam_kind, a->diameter_m, a->beam_pc_dircos, a->ext, a->n_ext, a->nt, "nt")) return rc;
+  for (int64_t i = 0; a->beam_pc_snap && i < a->nt * 3; ++i)
+    if (!std::isfinite(a->beam_pc_snap[i])) return fail(ctx, PRISIM_EINVAL, "beam_pc_snap of snapshot " + std::to_string(i / 3) + " is not finite");
+  const int64_t npix = a->npix, nbl = a->nbl, nchan = a->nchan, nt = a->nt;
+  const bool avg = a->chan_avg != 0, resident = !a->cube;
+  if (resident) {
+    if (int rc = check_resident_cube(ctx, nbl, nchan, nt)) return rc;
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int lds_max = 0;
+  if (int rc = lds_limit(ctx, lds_max)) return rc;
+  double df = 0.0;
+  const bool uniform = imaging_grid_uniform(a->freqs_hz, nchan, df);
+  const MosaicPlan pl = mosaic_plan(npix, nbl, nchan, nt, a->weight_form, avg, a->budget_bytes, lds_max, a->route, uniform, kMaxStreams);
+  if (pl.refusal)
+    return fail(ctx, PRISIM_EINVAL, std::string(pl.refusal) + " (one block of " + std::to_string(pl.block) + " pixels takes " +
+                                        std::to_string(pl.block * pl.pixel_bytes) + " B, the workgroup " + std::to_string(pl.lds) + " B of LDS)");
+  const Chunks& ch = pl.chunks;
+  const int nstreams = ch.nstreams;
+  const bool stepped = pl.route == kImagingStepped;
+
+  // the results wait here until every chunk is in: nothing reaches the caller's arrays from a call that fails.  Declared before the
+  // streams, so that they outlive every copy in flight on any return path
+  const int64_t per_out = avg ? 1 : nchan;
+  std::vector<double> h_mos((size_t)(npix * per_out)), h_wsum((size_t)nchan);
+  std::vector<double> h_eff(out_pb_eff ? (size_t)(npix * per_out) : 0), h_num(out_num ? (size_t)(npix * nchan) : 0),
+      h_den(out_den ? (size_t)(npix * nchan) : 0);
+
+  Work wk;
+  Streams& st = wk.st;
+  if (int rc = st.create(ctx, nstreams, true)) return rc;
+  hipStream_t s0 = st.s[0];
+
+  // the tables go up once on stream 0, outside the budget
+  const std::vector<ImgFrame> frames = snapshot_frames(&ia);
+  double *d_uvec = nullptr, *d_frames = nullptr, *d_bl = nullptr, *d_freqs = nullptr, *d_w = nullptr, *d_wt = nullptr, *d_wtot = nullptr,
+         *d_wband = nullptr, *d_ones = nullptr, *d_zeros = nullptr;
+  double2* d_cube = nullptr;
+  int64_t upload = 0;
+  const int64_t ncube = nt * nbl * nchan;
+  DEV_UPLOAD(ctx, wk.dev, d_uvec, a->unitvec, (size_t)npix * 3, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_frames, reinterpret_cast<const double*>(frames.data()), (size_t)nt * 16, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_bl, a->baselines, (size_t)nbl * 3, s0);
+  DEV_UPLOAD(ctx, wk.dev, d_freqs, a->freqs_hz, (size_t)nchan, s0);
+  upload += npix * 24 + nt * 128 + nbl * 24 + nchan * 8;
+  if (a->cube) {
+    DEV_UPLOAD(ctx, wk.dev, d_cube, a->cube, (size_t)ncube * 2, s0);
+    upload += ncube * 16;
+  }
+  ImgWeights W{nullptr, 0, 0, 0};
+  if (a->weight_form == PRISIM_IMAGE_W_BASELINE) {
+    DEV_UPLOAD(ctx, wk.dev, d_w, a->weights, (size_t)nbl, s0);
+    W = ImgWeights{d_w, 0, 1, 0};
+    upload += nbl * 8;
+  } else if (a->weight_form == PRISIM_IMAGE_W_FULL) {
+    DEV_UPLOAD(ctx, wk.dev, d_w, a->weights, (size_t)ncube, s0);
+    W = ImgWeights{d_w, nbl * nchan, nchan, 1};
+    upload += ncube * 8;
+  }
+  // the unit flux of the beam statement: pb * 1 * exp2(0 * lg) = pb
+  const std::vector<double> ones((size_t)ch.size, 1.0);
+  DEV_UPLOAD(ctx, wk.dev, d_ones, ones, s0);
+  DEV_ALLOC(ctx, wk.dev, d_zeros, ch.size * 8);
+  HIPCHK(ctx, hipMemsetAsync(d_zeros, 0, (size_t)ch.size * 8, s0));
+  upload += ch.size * 8;
+  std::vector<const double*> d_bf;
+  if (int rc = upload_beamformers(ctx, wk.dev, a->ext, a->n_ext, s0, d_bf, upload)) return rc;
+  int32_t* d_flag = nullptr;
+  DEV_ALLOC(ctx, wk.dev, d_flag, sizeof(int32_t));
+  HIPCHK(ctx, hipMemsetAsync(d_flag, 0, sizeof(int32_t), s0));
+  DEV_ALLOC(ctx, wk.dev, d_wt, nt * nchan * 8);
+  DEV_ALLOC(ctx, wk.dev, d_wtot, nchan * 8);
+  DEV_ALLOC(ctx, wk.dev, d_wband, 8);
+  if (int rc = launch(ctx, k_mos_wsum, dim3((unsigned)((nchan + kThreads - 1) / kThreads)), 0, s0, W, nt, nbl, (int)nchan, d_wt, d_wtot)) return rc;
+  hipLaunchKernelGGL(k_img_wtot, dim3(1), dim3(64), 0, s0, (const double*)d_wtot, (int)nchan, d_wband);
+  HIPCHK(ctx, hipGetLastError());
+
+  // per stream: the buffers of one chunk
+  double4 *d_s4[kMaxStreams] = {}, *d_dd[kMaxStreams] = {};
+  double *d_pb[kMaxStreams] = {}, *d_N[kMaxStreams] = {}, *d_Q[kMaxStreams] = {}, *d_mos[kMaxStreams] = {}, *d_eff[kMaxStreams] = {};
+  for (int i = 0; i < nstreams; ++i) {
+    DEV_ALLOC(ctx, wk.dev, d_s4[i], ch.size * nt * 32);
+    DEV_ALLOC(ctx, wk.dev, d_dd[i], ch.size * nt * 32);
+    DEV_ALLOC(ctx, wk.dev, d_pb[i], ch.size * nchan * 8);
+    DEV_ALLOC(ctx, wk.dev, d_N[i], ch.size * nchan * 8);
+    DEV_ALLOC(ctx, wk.dev, d_Q[i], ch.size * nchan * 8);
+    DEV_ALLOC(ctx, wk.dev, d_mos[i], ch.size * per_out * 8);
+    DEV_ALLOC(ctx, wk.dev, d_eff[i], ch.size * per_out * 8);
+  }
+  // the kernels start behind whatever the context's stream still writes into the resident cube
+  if (resident) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(s0));              // stream 1 starts behind the uploads and the weight sums; the tables are caller memory
+
+  MosParams base{};
+  base.cube = resident ? (const double2*)ctx->cube.p : d_cube;
+  base.W = W;
+  base.bl = d_bl; base.freqs = d_freqs;
+  base.df = df;
+  base.nbl = nbl; base.nchan = (int)nchan;
+
+  auto kernels = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+    if (int rc = launch(ctx, k_mos_dirs, dim3((unsigned)grid_for(ctx, sp.count * nt)), 0, sc, (const double*)d_uvec,
+                        reinterpret_cast<const ImgFrame*>(d_frames), sp.first, sp.count, nt, d_s4[i], d_dd[i]))
+      return rc;
+    const dim3 grid((unsigned)((sp.count + pl.block - 1) / pl.block), (unsigned)pl.ntiles);
+    for (int64_t t = 0; t < nt; ++t) {
+      const int64_t e = a->n_ext == nt ? t : 0;
+      BeamParams bp{};
+      fill_beam(bp, a->beam_kind, a->diameter_m, a->beam_pc_snap ? a->beam_pc_snap + t * 3 : a->beam_pc_dircos,
+                a->n_ext > 0 ? a->ext + e : nullptr, d_bf[(size_t)e]);
+      bp.dirs = (const double*)(d_s4[i] + t * sp.count);
+      bp.flux_ref = d_ones;
+      bp.spindex = d_zeros;
+      bp.freqs = d_freqs;
+      bp.ref_freq = 1.0;
+      bp.flag = d_flag;
+      bp.nsrc = sp.count;
+      bp.nchan = nchan;
+      bp.pb_out = d_pb[i];
+      HIPCHK(ctx, launch_beam_flux(bp, sc));
+      MosParams P = base;
+      P.dd = d_dd[i] + t * sp.count; P.s4 = d_s4[i] + t * sp.count;
+      P.pb = d_pb[i]; P.wt = d_wt + t * nchan;
+      P.t = t; P.count = sp.count;
+      P.N = d_N[i]; P.Q = d_Q[i];
+      if (int rc = stepped ? launch(ctx, k_mos_sum<true>, grid, 0, sc, P) : launch(ctx, k_mos_sum<false>, grid, 0, sc, P)) return rc;
+    }
+    if (avg)
+      return launch(ctx, k_mos_finish_band, dim3((unsigned)((sp.count + kThreads - 1) / kThreads)), 0, sc, (const double*)d_N[i],
+                    (const double*)d_Q[i], (const double*)d_wband, sp.count, (int)nchan, a->pbmin, d_mos[i], d_eff[i]);
+    return launch(ctx, k_mos_finish, dim3((unsigned)grid_for(ctx, sp.count * nchan)), 0, sc, (const double*)d_N[i], (const double*)d_Q[i],
+                  (const double*)d_wtot, sp.count, (int)nchan, a->pbmin, d_mos[i], d_eff[i]);
+  };
+  auto download = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
+    const size_t out_bytes = (size_t)(sp.count * per_out) * 8, sum_bytes = (size_t)(sp.count * nchan) * 8;
+    HIPCHK(ctx, hipMemcpyAsync(h_mos.data() + (size_t)(sp.first * per_out), d_mos[i], out_bytes, hipMemcpyDeviceToHost, sc));
+    if (out_pb_eff) HIPCHK(ctx, hipMemcpyAsync(h_eff.data() + (size_t)(sp.first * per_out), d_eff[i], out_bytes, hipMemcpyDeviceToHost, sc));
+    if (out_num) HIPCHK(ctx, hipMemcpyAsync(h_num.data() + (size_t)(sp.first * nchan), d_N[i], sum_bytes, hipMemcpyDeviceToHost, sc));
+    if (out_den) HIPCHK(ctx, hipMemcpyAsync(h_den.data() + (size_t)(sp.first * nchan), d_Q[i], sum_bytes, hipMemcpyDeviceToHost, sc));
+    return PRISIM_OK;
+  };
+  if (int rc = chunk_loop(ctx, st, ch, npix, no_step, kernels, download)) return rc;
+  if (int rc = poly_beam_verdict(ctx, a->beam_kind, d_flag)) return rc;
+  HIPCHK(ctx, hipMemcpy(h_wsum.data(), d_wtot, h_wsum.size() * 8, hipMemcpyDeviceToHost));
+
+  std::memcpy(out_mosaic, h_mos.data(), h_mos.size() * 8);
+  if (out_pb_eff) std::memcpy(out_pb_eff, h_eff.data(), h_eff.size() * 8);
+  if (out_num) std::memcpy(out_num, h_num.data(), h_num.size() * 8);
+  if (out_den) std::memcpy(out_den, h_den.data(), h_den.size() * 8);
+  if (out_wsum) std::memcpy(out_wsum, h_wsum.data(), h_wsum.size() * 8);
+  if (stats) {
+    // per snapshot.  k_mos_sum, per workgroup (block of pixels, channel tile) and b: the tile's row of the cube (16 B a channel) and
+    // of the weights (8 B a channel when there are any), and the baseline (24 B); per pixel and tile its offset and its direction
+    // (32 B each); per (pixel, channel) the beam value read (8 B), N and Q written (16 B) and, past snapshot 0, read (16 B).  The
+    // beam: 32 B of direction read per pixel, 8 B written per (pixel, channel).  Once: k_mos_dirs, 24 B read and 64 B written per
+    // (pixel, snapshot); the finish, N and Q read and two outputs written, read once more per channel with chan_avg; k_mos_wsum, the
+    // weights once.
+    const int64_t wg = pl.nblocks * pl.ntiles;
+    const int64_t row = pl.tile * (16 + (W.w ? 8 : 0)) + 24;
+    stats->wall_ms = wall_ms_since(wall0);
+    stats->kernel_ms = st.kernel_ms;
+    stats->terms = npix * nbl * nchan * nt;
+    stats->beam_values = npix * nchan * nt;
+    stats->chunks = ch.count;
+    stats->chunk_pixels = ch.size;
+    stats->pixel_bytes = pl.pixel_bytes;
+    stats->kernel_bytes = wg * nt * nbl * row + npix * nt * (24 + 64 + 32 + 64 * pl.ntiles) + npix * nchan * (nt * (8 + 8 + 16) + (nt - 1) * 16) +
+                          npix * nchan * 16 + npix * per_out * 16 + (W.w ? ncube * 8 : 0) + (nt + 2) * nchan * 8;
+    stats->upload_bytes = upload;
+    stats->download_bytes = (npix * per_out * (out_pb_eff ? 2 : 1) + npix * nchan * ((out_num ? 1 : 0) + (out_den ? 1 : 0)) + nchan) * 8;
+    stats->route = pl.route;
+    stats->streams = nstreams;
+    stats->chan_tile = (int32_t)pl.tile;
+    stats->reseed = (int32_t)pl.reseed;
+    stats->lds_bytes = (int32_t)pl.lds;
+    stats->block_pixels = (int32_t)pl.block;
+  }
+  return PRISIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int prisim_mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosaic, double* out_pb_eff, double* out_num,
+                        double* out_den, double* out_wsum, prisim_mosaic_stats* stats) {
+  return guarded(ctx, [&]() -> int { return mosaic_image(ctx, a, out_mosaic, out_pb_eff, out_num, out_den, out_wsum, stats); });
+}
+
+}  // extern "C"

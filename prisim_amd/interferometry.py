@@ -2773,12 +2773,14 @@ class ApertureSynthesis(object):
 
     Attributes as in the reference (:9136-9163): ia, f, df, n_acc, lst, phase_center, phase_center_coords, pointing_center,
     pointing_coords, baselines, timestamp, latitude, blxyz, uvw_lambda, uvw, blc, trc, grid_blc, grid_trc, gridu, gridv, gridw,
-    grid_ready; and image_stats, the statistics of the last image(), psf() or clean().
+    grid_ready; and image_stats, the statistics of the last image(), psf(), clean() or mosaic().
 
     Departures from the reference: setUVWgrid is not ported -- its grid comes from GRD.grid_3d, whose source is not part of the
     reference tree, and the direct transform needs no grid; grid_ready stays False.  genUVW with a 'radec' phase centre takes
     HA = LST - RA and the centre's declination, as _pc_dircos and project_baselines do (the reference puts HA = LST and Dec = 0, :9180).
-    image(), psf(), clean() (Hogbom's CLEAN of image() with the exact beam, include/prisim_imclean.h) and dircos_grid() are additions.
+    image(), psf(), clean() (Hogbom's CLEAN of image() with the exact beam, include/prisim_imclean.h), mosaic() (the beam-weighted
+    mosaic of the snapshots, horizon mask included: true fluxes where image() gives apparent ones, include/prisim_mosaic.h) and
+    dircos_grid() are additions.
     There is no CPU path."""
 
     def __init__(self, interferometer_array=None):
@@ -2947,6 +2949,58 @@ class ApertureSynthesis(object):
     def psf(self, directions, coords='dircos', weights=None, chan_avg=False, epoch=None, route='auto', budget_bytes=None):
         """The synthesized beam at the given directions: image() of V = 1, centred on every snapshot's phase centre, where it is 1."""
         return self._synthesize('psf', directions, coords, None, weights, chan_avg, epoch, route, budget_bytes)
+
+    def mosaic(self, directions, coords='dircos', datakey='noiseless', weights=None, chan_avg=False, epoch=None, telescope=None,
+               pb_info=None, pbmin=0.1, route='auto', budget_bytes=None):
+        """The beam-weighted linear mosaic of the snapshots at the given directions, on the GPU (include/prisim_mosaic.h), (npix, nchan)
+        float64 or (npix,) with chan_avg: sum_t A_t D_t / sum_t A_t^2 W_t, with D_t the unnormalised image() of snapshot t alone, W_t
+        its weight sum and A_t the power pattern of the primary beam at the direction in that snapshot, 0 below the horizon.  Where
+        image() gives apparent fluxes, this gives true ones: a source of flux S simulated through the beam comes back as S at its own
+        direction for any number of snapshots, any drift of the beam across the sky and any chromaticity of the beam.
+
+        directions, coords, datakey, weights, chan_avg, epoch, route, budget_bytes as image() takes them; the noiseless cube is read
+        where it lies on the device under the same condition.
+        telescope    the dictionary of the beam; None: the array's own (ia.telescope), the beam the visibilities were simulated with.
+        pb_info      the pointing_info of a phased array's beamformer, as observe() takes it: None, one dictionary, or a sequence of one
+                     per snapshot (observe() takes one per call).  The beam of snapshot t is primary_beams.device_beam_spec at the
+                     pointing observe() used; what differs between the snapshots -- the element's pointing, the beamformer's delays --
+                     goes to the device per snapshot.
+        pbmin        in [0, 1): where the effective beam pb_eff = sqrt(sum_t A_t^2 W_t / sum_t W_t) is below it the mosaic is NaN (the
+                     usual 'pblimit'; 0.1 is a convention, not a measured value).  0 masks only what no snapshot saw at all.
+        The noise of the mosaic goes as 1 / pb_eff.  num, den (npix, nchan), wsum (nchan,), pb_eff (the mosaic's shape) and the entry's
+        statistics are left in image_stats.
+
+        Raises NotImplementedError for an array with an external beam (set_external_beam) and for the apertures device_beam_spec
+        does not carry (rect, square)."""
+        ia = self.ia
+        if getattr(ia, '_extbeam', None) is not None:
+            raise NotImplementedError('mosaic() evaluates the analytic beams; the array has an external beam (set_external_beam)')
+        pbmin = float(pbmin)
+        if not (0.0 <= pbmin < 1.0):
+            raise ValueError('pbmin must lie in [0, 1)')
+        uv, rot, beta, pc, w, cube = self._prepare('dirty', directions, coords, datakey, weights, epoch, route)
+        tel = ia.telescope if telescope is None else telescope
+        nt = len(ia.lst)
+        infos = list(pb_info) if isinstance(pb_info, (list, tuple)) else [pb_info] * nt
+        if len(infos) != nt:
+            raise ValueError('pb_info must be None, one dictionary or one per snapshot')
+        specs = []
+        for t in range(nt):
+            pc_altaz = ia._pointing(ia.pointing_center[t], ia.lst[t])[1]
+            specs.append(PB.device_beam_spec(tel, pointing_info=infos[t], pointing_center=pc_altaz, first_frequency_hz=float(ia.channels[0])))
+        # one shared description unless the pointing moves: then the element's pointing, a beamformer's delays, or both go per snapshot
+        kind, dia, bpc, ext = specs[0]
+        if not all(_same_beam_spec(specs[0][:2], sp[:2]) for sp in specs[1:]):
+            raise ValueError('the snapshots must share one kind and size of beam')
+        if not all(_same_beam_spec(bpc, sp[2]) for sp in specs[1:]):
+            bpc = NP.stack([NP.asarray(sp[2], dtype=NP.float64).ravel() for sp in specs])
+        if not all(_same_beam_spec(ext, sp[3]) for sp in specs[1:]):
+            ext = [sp[3] for sp in specs]
+        image, num, den, wsum, st = ia._ctx.mosaic_image(uv, rot, pc, ia._baselines_local(), ia.channels, kind, dia, beam_pc_dircos=bpc,
+                                                         ext=ext, cube=cube, weights=w, chan_avg=bool(chan_avg), aberr_beta=beta,
+                                                         pbmin=pbmin, route=route, budget_bytes=int(budget_bytes or 0))
+        self.image_stats = dict(st, num=num, den=den, wsum=wsum)
+        return image
 
     def clean(self, directions, coords='dircos', datakey='noiseless', weights=None, chan_avg=False, epoch=None, gain=0.1, maxiter=10000,
               threshold=5e-3, threshold_type='relative', window=None, fwhm=None, restore=True, route='auto', budget_bytes=None):
