@@ -478,6 +478,12 @@ int prisim_hip_get_timing(prisim_ctx* ctx, prisim_timing* out, int reset);
  * last_culled_fraction and last_split_uncorrected_groups refer to the summed rows.  Any pointer may be NULL.  (Kept out of
  * prisim_timing: its layout is frozen at 96 bytes.)  PRISIM_HIP_FOLD=0 in the environment turns folding off. */
 int prisim_hip_get_fold_info(prisim_ctx* ctx, int64_t* last_sum_baselines, int64_t* last_terms_evaluated, int64_t* last_sum_lift_groups);
+/* The second tier of the fp32 step flag (csrc/step_bound.h).  A group of 256 summed rows whose step bound exceeds the 1/8-cycle
+ * lifting limit but not the wide limit runs the leapfrog with a sine fitted for that range, in the packed fp32 kernel without the
+ * taper only (not the fused gradient, not fp64).  last_sum_wide_groups: those groups in the last compute(), counted beside -- not in --
+ * last_sum_lift_groups; wide_limit_cycles: the limit.  Either pointer may be NULL.  PRISIM_HIP_WIDE_LEAPFROG=0 in the environment
+ * (read by prisim_hip_set_array) sends those groups to the plain rotation again. */
+int prisim_hip_get_step_tiers(prisim_ctx* ctx, int64_t* last_sum_wide_groups, double* wide_limit_cycles);
 /* Device properties: CU count and clock (kHz) used to re-derive the VALU peak on the box. */
 int prisim_hip_device_info(prisim_ctx* ctx, int* cu_count, int* clock_khz, char name[64]);
 /* Tuning knobs (0 = library default): channels per thread, source padding / split granularity, source split factor. */

@@ -509,6 +509,7 @@ _PROTOTYPES = {
         int prisim_hip_sync(p ctx);
         int prisim_hip_get_timing(p ctx, *prisim_timing out, i reset);
         int prisim_hip_get_fold_info(p ctx, *q last_sum_baselines, *q last_terms_evaluated, *q last_sum_lift_groups);
+        int prisim_hip_get_step_tiers(p ctx, *q last_sum_wide_groups, *d wide_limit_cycles);
         int prisim_hip_device_info(p ctx, *i cu_count, *i clock_khz, s name);
         int prisim_hip_set_tuning(p ctx, i chan_tile, i src_chunk, i nsplit);
     ''',
@@ -2327,6 +2328,11 @@ class Context(object):
         out['last_sum_lift_groups'] = nlift.value
         out['last_sum_baselines'] = nsum.value
         out['last_terms_evaluated'] = nterms.value
+        # the second tier of the fp32 step flag: groups of 256 summed rows that ran the wide leapfrog body, and its limit in cycles
+        nwide, wlim = C.c_int64(), C.c_double()
+        self._check(self._lib.prisim_hip_get_step_tiers(self._h, C.byref(nwide), C.byref(wlim)), 'prisim_hip_get_step_tiers')
+        out['last_sum_wide_groups'] = nwide.value
+        out['wide_limit_cycles'] = wlim.value
         return out
 
     def device_info(self):

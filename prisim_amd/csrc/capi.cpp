@@ -146,7 +146,7 @@ void prisim_hip_destroy(prisim_ctx* ctx) {
                     &ctx->dl_stage, &ctx->grp_hz, &ctx->fft_work, &ctx->fft_buf, &ctx->dt_out, &ctx->dt_pow, &ctx->dt_wts, &ctx->dt_lag_all, &ctx->dt_pow_all, &ctx->dt_tw})
     release(*b);
   for (SkyBufs& k : ctx->skb) {
-    for (DevBuf* b : {&k.pb, &k.packed, &k.dirs_prep, &k.dirs_c32, &k.lift_flags, &k.split_flags, &k.moments, &k.moments_part, &k.split_count, &k.cull_first,
+    for (DevBuf* b : {&k.pb, &k.packed, &k.dirs_prep, &k.dirs_c32, &k.lift_flags, &k.wide_flags, &k.split_flags, &k.moments, &k.moments_part, &k.split_count, &k.cull_first,
                       &k.dirs_sorted, &k.idx_sorted, &k.batch_tab})
       release(*b);
     if (k.ev_prep) (void)hipEventDestroy(k.ev_prep);
@@ -201,6 +201,9 @@ int prisim_hip_set_array(prisim_ctx* ctx, const double* bl_enu, int64_t nbl, con
   const int64_t nbl_u = (int64_t)fold_rep.size();
   bool fold = nbl_u * 8 <= nbl * 7 && nbl_u > kBlockThreads;
   if (const char* env = getenv("PRISIM_HIP_FOLD")) fold = fold && atoi(env) != 0;
+  // PRISIM_HIP_WIDE_LEAPFROG=0: no group takes the wide tier of the fp32 leapfrog (step_bound.h); the A/B hook, bit-identical to the form without it
+  ctx->wide_leapfrog = true;
+  if (const char* env = getenv("PRISIM_HIP_WIDE_LEAPFROG")) ctx->wide_leapfrog = atoi(env) != 0;
   // PRISIM_HIP_DEFER_POST=0: reduce / expand stay on the compute stream behind their sky-sum (the A/B hook of the deferred post-pass)
   ctx->defer_post = true;
   if (const char* env = getenv("PRISIM_HIP_DEFER_POST")) ctx->defer_post = atoi(env) != 0;
@@ -781,6 +784,8 @@ static void sky_params(prisim_ctx* ctx, const SkyShape& s, const SkyRoute& rt, S
   p.dirs = ctx->dirs_p;
   p.fsq_pairs = (const float*)ctx->fsq_pairs.p;
   p.lift_flags = ctx->sk->lift_flags.p ? (const int32_t*)ctx->sk->lift_flags.p : nullptr;   // taper kernels: which groups need no re-anchoring
+  // the wide tier: fp32 skies without the taper (the table is formed with lift_flags for every fp32 plan; a tapered sky's point-source runs keep the plain body)
+  p.wide_flags = (pl.f32 && !ctx->taper && ctx->sk->wide_flags.p) ? (const int32_t*)ctx->sk->wide_flags.p : nullptr;
   p.nsrc = ctx->nsrc; p.nsrc_pad = pl.nsrc_pad;
   p.pc_x = ctx->pc[0]; p.pc_y = ctx->pc[1]; p.pc_z = ctx->pc[2];
   p.taper = ctx->taper ? 1 : 0;
@@ -1006,6 +1011,7 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
   const int post_set = defer ? ctx->part_next : -1;
   ctx->timing.last_lift_groups = 0;
   ctx->last_sum_lift_groups = 0;
+  ctx->last_sum_wide_groups = 0;
   ctx->timing.last_taper_group = 0;
   ctx->timing.last_taper_split = 0;
   ctx->timing.last_split_uncorrected_groups = 0;
@@ -1035,6 +1041,12 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
         if ((rc = ensure(ctx, ctx->sk->lift_flags, (size_t)pl.nbgroups * sizeof(int32_t)))) return rc;
         HIPCHK(ctx, launch_lift_flags((const double*)ctx->grp_hz.p, pl.nbgroups, ctx->dmax, ctx->hmax, ctx->zmax, adf, lift_limit,
                                       (int32_t*)ctx->sk->lift_flags.p, pstream(ctx)));
+        if (pl.f32) {
+          // the wide tier's table (fp32 only): the same kernel under the wide limit; the hook off = a limit no step meets = all zero
+          if ((rc = ensure(ctx, ctx->sk->wide_flags, (size_t)pl.nbgroups * sizeof(int32_t)))) return rc;
+          HIPCHK(ctx, launch_lift_flags((const double*)ctx->grp_hz.p, pl.nbgroups, ctx->dmax, ctx->hmax, ctx->zmax, adf,
+                                        ctx->wide_leapfrog ? prisim::step_wide_limit_cycles() : -1.0, (int32_t*)ctx->sk->wide_flags.p, pstream(ctx)));
+        }
         for (int i = 0; i < 3; ++i) ctx->sk->lift_key_k[i] = key[i];
         ctx->sk->lift_key_f32 = (int)pl.f32;
         ctx->sk->lift_groups = pl.nbgroups;
@@ -1044,12 +1056,18 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
       // last_lift_groups stays the length-rule count per group of 256 CUBE rows (the caller's units): the groups whose longest baseline
       // passes max|b| max_s|e| alone.  It is a lower bound of what lifts on an unfolded array; on a folded one a cube row within the
       // limit whose vector shares a summed group with a longer one runs the plain rotation, which is valid for every step angle.
-      int nlift = 0, nlift_sum = 0;
+      // last_sum_wide_groups (prisim_hip_get_step_tiers): the groups of tier 2, where the kernel that reads the wide table runs -- the
+      // packed fp32 kernel without the taper, not the fused gradient.
+      int nlift = 0, nlift_sum = 0, nwide_sum = 0;
       for (double len : ctx->row_grp_maxlen) nlift += (len * k <= lift_limit) ? 1 : 0;
-      for (size_t g = 0; g < ng; ++g)
-        nlift_sum += prisim::step_flag(ctx->grp_maxlen[g], ctx->grp_maxh[g], ctx->grp_maxz[g], ctx->dmax, ctx->hmax, ctx->zmax, ctx->df, pl.f32) ? 1 : 0;
+      for (size_t g = 0; g < ng; ++g) {
+        const int tier = prisim::step_tier(ctx->grp_maxlen[g], ctx->grp_maxh[g], ctx->grp_maxz[g], ctx->dmax, ctx->hmax, ctx->zmax, ctx->df, pl.f32);
+        nlift_sum += tier == 1 ? 1 : 0;
+        nwide_sum += tier == 2 ? 1 : 0;
+      }
       ctx->timing.last_lift_groups = rt.zero_lift_counts ? 0 : nlift;
       ctx->last_sum_lift_groups = rt.zero_lift_counts ? 0 : nlift_sum;
+      ctx->last_sum_wide_groups = (ctx->wide_leapfrog && rt.sum_family == kFamPackedF32 && !ctx->taper && !fused_grad) ? nwide_sum : 0;
       shape.have_lift_flags = ctx->sk->lift_flags.p != nullptr;      // (formed above, now or by an earlier compute() of this sky-buffer set)
     }
     if (pl.f32 && ctx->taper) {
@@ -1232,6 +1250,15 @@ int prisim_hip_get_fold_info(prisim_ctx* ctx, int64_t* last_sum_baselines, int64
   if (last_sum_baselines) *last_sum_baselines = ctx->last_sum_baselines;
   if (last_terms_evaluated) *last_terms_evaluated = ctx->last_terms_evaluated;
   if (last_sum_lift_groups) *last_sum_lift_groups = ctx->last_sum_lift_groups;
+  return PRISIM_OK;
+  });
+}
+
+int prisim_hip_get_step_tiers(prisim_ctx* ctx, int64_t* last_sum_wide_groups, double* wide_limit_cycles) {
+  return guarded(ctx, [&]() -> int {
+  if (!ctx) return PRISIM_EINVAL;
+  if (last_sum_wide_groups) *last_sum_wide_groups = ctx->last_sum_wide_groups;
+  if (wide_limit_cycles) *wide_limit_cycles = prisim::step_wide_limit_cycles();
   return PRISIM_OK;
   });
 }

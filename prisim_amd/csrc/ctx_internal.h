@@ -94,6 +94,7 @@ struct SkyBufs {
   double lift_key_k[3] = {-1.0, -1.0, -1.0};      // max_s |e|, |e_xy|, |e_z| (e = s - s_pc), each times |df|: all three enter the flags
   int lift_key_f32 = -1;
   int lift_groups = -1;
+  DevBuf wide_flags;         // [groups] the same flags under the wide fp32 limit (step_bound.h), formed with lift_flags under the same key; fp32 only
   DevBuf split_flags, moments, moments_part, split_count;      // split taper form: per-run moments and per-group flags
   // Taper culling: cull_first[prec][run][group] = first source of the run that group still has to sum (device, int32); the sources before
   // it contribute < exp(-18) (fp32) / exp(-28) (fp64) of sum|pbflux| to every baseline of the group.
@@ -129,6 +130,8 @@ struct prisim_ctx {
   int64_t nbl_sum = 0;                // rows the sky-sum computes: distinct vectors when folded, nbl otherwise
   DevBuf ublx, ubly, ublz, fold_map, fold_vis, fold_grad;
   int64_t last_sum_baselines = 0, last_terms_evaluated = 0, last_sum_lift_groups = 0;      // of the last compute() (prisim_hip_get_fold_info)
+  int64_t last_sum_wide_groups = 0;   // groups of the last compute() that ran the wide leapfrog body (prisim_hip_get_step_tiers)
+  bool wide_leapfrog = true;          // PRISIM_HIP_WIDE_LEAPFROG=0 (read by set_array): the wide table stays all zero
   std::vector<double> row_grp_maxlen; // max |b| per group of kBlockThreads CUBE rows: the units last_lift_groups is reported in
   std::vector<double> grp_maxlen;    // max |b| per group of kBlockThreads baselines (lifting-rotation guarantee)
   double grp_lmax = 0.0;              // the largest of them (set_array)

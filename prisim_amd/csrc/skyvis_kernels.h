@@ -76,6 +76,8 @@ struct SkyvisParams {
   const BatchSnap* wave_snaps;
   int32_t wave_nsnap;
   int32_t pad4_;
+  // packed fp32 kernel without the taper (k_skyvis_rec_f32pk<CT, false>) only: the second tier of the step flag (step_bound.h)
+  const int32_t* wide_flags; // [nbgroups] 1: |step phase| <= the wide limit for this baseline group (or nullptr); read where lift_flags is 0
 };
 
 hipError_t launch_skyvis_rec(const SkyvisParams& p, bool f32, int ct, hipStream_t stream);

@@ -116,6 +116,23 @@ __device__ __forceinline__ float sin_2pi_y(float y) {
   return __builtin_fmaf(y, q, y * 6.2831855f);
 }
 
+// sin(2 pi y) for |y| <= 3/16 cycle, rounded ONCE to fp32: y P(y^2) in fp64, P = degree-4 fit (3e-10 relative), so the result is within
+// half an ulp (6e-8 relative) where sin_2pi_y is within one (1.2e-7 up to 1/8 cycle; 5e-7 at 5/32).  The step of the WIDE leapfrog body
+// (step_bound.h: step_wide_limit_cycles): the angle error of a step is tan(alpha) times the relative error of its sine, repeated at
+// every step of the chain, and past 1/8 cycle tan(alpha) > 1 -- with the fp32 polynomial carried to one more term a single source
+// at 9/64 cycle ended its chains 4.1e-6 off (profiles/LOG.md 4.1.10).  Six v_*_f64 per source in the three or so groups of an array that
+// take this body.  Its cosine is cos_2pi_y unchanged: that polynomial holds 8e-8 absolute up to 3/16 cycle, and the leapfrog uses the
+// cosine once per source (the down chain's seed).
+__device__ __forceinline__ float sin_2pi_y_wide(double y) {
+  const double u = y * y;
+  double ps = 40.751603403474405;
+  ps = __builtin_fma(ps, u, -76.66585977884482);
+  ps = __builtin_fma(ps, u, 81.60474846816732);
+  ps = __builtin_fma(ps, u, -41.34170004400274);
+  ps = __builtin_fma(ps, u, 6.283185305638015);
+  return (float)(y * ps);
+}
+
 // tan(pi y) for |y| <= 1/8 cycle, ~1 ulp: y * (pi_hi + (pi_lo + y^2 P(y^2))), P = degree-3 fit of (tan(pi y)/y - pi)/y^2
 __device__ __forceinline__ float tan_pi_y(float y) {
   const float u = y * y;
@@ -335,12 +352,20 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // on one XCD walk the baseline groups of one slab before the next, so that slab's pbflux rows stay in the XCD's 4 MiB L2, and every
 // XCD gets the same number of blocks whatever the slab count (pinning whole slabs to XCDs left 2 of 8 XCDs with 2 instead of 3
 // tiles at 22 tiles: 9 % of the launch).  Returns false for the padding blocks past the last item.
+// LAST_FIRST (the packed fp32 kernel without the taper): within a slab the baseline groups are walked from the last to the first.
+// Arrays come sorted by length more often than not (a folded array lists its vectors by first appearance: short spacings first), and
+// the last groups are then the ones that take the slower bodies.  Walked in ascending order they were every XCD's last items
+// (headline: 516 = 12 x 43 items per XCD on 64 resident slots, 8.06 rounds) and the launch ended with a lone plain block that had
+// started last; measured on the headline step, parent and the two orders alternated: 10.48 -> 10.05 ms (profiles/LOG.md 4.1.10).
+// The other kernels keep the ascending order (and their code: one more SGPR put lane moves into k_skyvis_rec<double, 32, true>'s loop).
+template <bool LAST_FIRST = false>
 __device__ __forceinline__ bool block_item(const SkyvisParams& p, int& slab, int& bg) {
   const int total = p.ntiles * p.nsplit * p.nbgroups;
   const int per_xcd = (total + 7) >> 3;
   const int item = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
   slab = item / p.nbgroups;
   bg = item - slab * p.nbgroups;
+  if constexpr (LAST_FIRST) bg = p.nbgroups - 1 - bg;
   return (int)(blockIdx.x >> 3) < per_xcd && item < total;
 }
 
@@ -1169,9 +1194,12 @@ __device__ __forceinline__ float exp2m1_small(float D) {
 //   64-channel tile's -- so every accumulator set takes its own SGPR-pair operand straight into v_pk_fma_f32: 8 accumulate FMAs + the
 //   2-instruction leapfrog rotation (LIFT groups) = 10 packed instructions per pair of terms instead of 13 (term = p zeta first, then four adds / FMAs), and
 //   the per-source coefficient load disappears.
-template <int CT, bool TAPER, bool LIFT, int TGROUP = 0, int REANCHOR = 0, bool GRAD = false, bool GPK = false>
+//   WIDE (the LIFT body of the plain sky-sum only): the same leapfrog for baseline groups whose step is guaranteed within the WIDE limit
+//   but not within 1/8 cycle (step_bound.h: tier 2; p.wide_flags).  Only the step's sine differs: sin_2pi_y_wide, formed in fp64.
+template <int CT, bool TAPER, bool LIFT, int TGROUP = 0, int REANCHOR = 0, bool GRAD = false, bool GPK = false, bool WIDE = false>
 __device__ __forceinline__ void skyvis_rec_f32pk_body(const SkyvisParams& p, unsigned char* flush_lds) {
   static_assert(!GPK || (GRAD && !TAPER), "pre-multiplied rows: the gradient bodies without the taper");
+  static_assert(!WIDE || (LIFT && !TAPER && !GRAD), "the wide tier: the leapfrog body of the plain sky-sum");
   constexpr int NR = GRAD ? 4 : 1;                   // accumulator sets: V (+ G_l, G_m, G_n)
   constexpr bool SPLIT = TGROUP >= 2;
   constexpr bool PARABOLA = TGROUP == 1 || TGROUP == 2;
@@ -1188,7 +1216,7 @@ __device__ __forceinline__ void skyvis_rec_f32pk_body(const SkyvisParams& p, uns
   constexpr int NP = ROWF / NPART;                   // floats per piece
 
   int slab, bg;
-  if (!block_item(p, slab, bg)) return;
+  if (!block_item<!TAPER && !GRAD>(p, slab, bg)) return;      // (as the kernel that chose this body maps its blocks)
   const int tile = slab % p.ntiles;
   const int split = slab / p.ntiles;
 
@@ -1372,7 +1400,7 @@ __device__ __forceinline__ void skyvis_rec_f32pk_body(const SkyvisParams& p, uns
         // LIFT and the taper bodies of baseline groups whose |theta| <= 1/8 cycle is guaranteed (the host's lift flag): no quadrant logic
         const float yth = (float)(d * p.df);
         rr = cos_2pi_y(yth);
-        ri = -sin_2pi_y(yth);
+        ri = WIDE ? -sin_2pi_y_wide(d * p.df) : -sin_2pi_y(yth);
       } else {
         float rc, rs;
         sincos_qcycles(d * df4, rc, rs);
@@ -1777,11 +1805,20 @@ void k_skyvis_rec_f32pk(const SkyvisParams p) {
   if constexpr (!TAPER) {
     // block-uniform choice made by the host per baseline group; the two bodies share no live state
     int slab_, bg;
-    if (!block_item(p, slab_, bg)) return;
+    if (!block_item<true>(p, slab_, bg)) return;
     if (p.lift_flags != nullptr && p.lift_flags[bg] != 0) {
       skyvis_rec_f32pk_body<CT, false, true>(p, flush_lds);
       return;
     }
+    // Second tier (step_bound.h): the step is within the wide limit only -- the strict flag is looked at first, so the wide table may
+    // flag both tiers.  The plain body stands before the wide one: in this order the strict and the plain source loops come out as
+    // they did before the wide body existed (tools/kernel_meta.py --loops 1: 154 / 161 and 232 / 239 VALU instructions, one lane move).
+    if (p.wide_flags == nullptr || p.wide_flags[bg] == 0) {
+      skyvis_rec_f32pk_body<CT, false, false>(p, flush_lds);
+      return;
+    }
+    skyvis_rec_f32pk_body<CT, false, true, 0, 0, false, false, true>(p, flush_lds);
+    return;
   } else {
     // lift_flags[bg] = 1: |step angle| <= pi/4 for every source of this baseline group; 0: re-anchor the chains at their midpoint
     int slab_, bg;
