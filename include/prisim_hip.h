@@ -484,6 +484,13 @@ int prisim_hip_get_fold_info(prisim_ctx* ctx, int64_t* last_sum_baselines, int64
  * last_sum_lift_groups; wide_limit_cycles: the limit.  Either pointer may be NULL.  PRISIM_HIP_WIDE_LEAPFROG=0 in the environment
  * (read by prisim_hip_set_array) sends those groups to the plain rotation again. */
 int prisim_hip_get_step_tiers(prisim_ctx* ctx, int64_t* last_sum_wide_groups, double* wide_limit_cycles);
+/* Tail pieces (csrc/tail_plan.h).  The packed fp32 sky-sum without the taper and without a gradient, where the planner itself split
+ * the sources of a grid at least three rounds of resident blocks deep, cuts the last of its source pieces into a half and up to four
+ * eighths, so that small work items close the launch.  pieces: partial cubes the last compute() summed (1: no split; last_nsplit of
+ * prisim_timing stays the plan's count); tail_pieces: how many of them were made of the plan's last piece (0: the plan's pieces, as for
+ * every other kernel family and under set_tuning).  Either pointer may be NULL.  PRISIM_HIP_TAIL_PIECES=0 in the environment (read by
+ * prisim_hip_set_array) keeps the plan's pieces. */
+int prisim_hip_get_tail_pieces(prisim_ctx* ctx, int64_t* pieces, int64_t* tail_pieces);
 /* Device properties: CU count and clock (kHz) used to re-derive the VALU peak on the box. */
 int prisim_hip_device_info(prisim_ctx* ctx, int* cu_count, int* clock_khz, char name[64]);
 /* Tuning knobs (0 = library default): channels per thread, source padding / split granularity, source split factor. */

@@ -510,6 +510,7 @@ _PROTOTYPES = {
         int prisim_hip_get_timing(p ctx, *prisim_timing out, i reset);
         int prisim_hip_get_fold_info(p ctx, *q last_sum_baselines, *q last_terms_evaluated, *q last_sum_lift_groups);
         int prisim_hip_get_step_tiers(p ctx, *q last_sum_wide_groups, *d wide_limit_cycles);
+        int prisim_hip_get_tail_pieces(p ctx, *q pieces, *q tail_pieces);
         int prisim_hip_device_info(p ctx, *i cu_count, *i clock_khz, s name);
         int prisim_hip_set_tuning(p ctx, i chan_tile, i src_chunk, i nsplit);
     ''',
@@ -2333,6 +2334,12 @@ class Context(object):
         self._check(self._lib.prisim_hip_get_step_tiers(self._h, C.byref(nwide), C.byref(wlim)), 'prisim_hip_get_step_tiers')
         out['last_sum_wide_groups'] = nwide.value
         out['wide_limit_cycles'] = wlim.value
+        # tail pieces (csrc/tail_plan.h): partial cubes the last compute() summed, and how many of them the plan's last source piece was
+        # cut into (0: the plan's pieces; last_nsplit stays the plan's count either way)
+        npieces, ntail = C.c_int64(), C.c_int64()
+        self._check(self._lib.prisim_hip_get_tail_pieces(self._h, C.byref(npieces), C.byref(ntail)), 'prisim_hip_get_tail_pieces')
+        out['last_sum_pieces'] = npieces.value
+        out['last_tail_pieces'] = ntail.value
         return out
 
     def device_info(self):

@@ -141,7 +141,7 @@ void prisim_hip_destroy(prisim_ctx* ctx) {
   if (ctx->fft_plan && g_rocfft.plan_destroy) g_rocfft.plan_destroy(ctx->fft_plan);
   if (ctx->fft_info && g_rocfft.execution_info_destroy) g_rocfft.execution_info_destroy(ctx->fft_info);
   for (DevBuf* b : {&ctx->blx, &ctx->bly, &ctx->blz, &ctx->ublx, &ctx->ubly, &ctx->ublz, &ctx->fold_map, &ctx->fold_vis, &ctx->fold_grad, &ctx->freqs, &ctx->fsq, &ctx->fsq_pairs, &ctx->cube, &ctx->grad, &ctx->dirs,
-                    &ctx->partial, &ctx->partial_b, &ctx->scratch, &ctx->gathered, &ctx->sendbuf, &ctx->shard_map, &ctx->stage_main, &ctx->stage_comm, &ctx->ext_table,
+                    &ctx->partial, &ctx->partial_b, &ctx->tail_lo, &ctx->tail_tab, &ctx->scratch, &ctx->gathered, &ctx->sendbuf, &ctx->shard_map, &ctx->stage_main, &ctx->stage_comm, &ctx->ext_table,
                     &ctx->ext_work, &ctx->ext_colmax, &ctx->sky_flux, &ctx->sky_sp, &ctx->sky_bf, &ctx->sky_flag,
                     &ctx->dl_stage, &ctx->grp_hz, &ctx->fft_work, &ctx->fft_buf, &ctx->dt_out, &ctx->dt_pow, &ctx->dt_wts, &ctx->dt_lag_all, &ctx->dt_pow_all, &ctx->dt_tw})
     release(*b);
@@ -162,6 +162,8 @@ void prisim_hip_destroy(prisim_ctx* ctx) {
   if (ctx->ev_d1) (void)hipEventDestroy(ctx->ev_d1);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   if (ctx->h_split_count) (void)hipHostFree(ctx->h_split_count);
+  if (ctx->ev_tail) (void)hipEventDestroy(ctx->ev_tail);
+  if (ctx->h_tail) (void)hipHostFree(ctx->h_tail);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -207,6 +209,11 @@ int prisim_hip_set_array(prisim_ctx* ctx, const double* bl_enu, int64_t nbl, con
   // PRISIM_HIP_DEFER_POST=0: reduce / expand stay on the compute stream behind their sky-sum (the A/B hook of the deferred post-pass)
   ctx->defer_post = true;
   if (const char* env = getenv("PRISIM_HIP_DEFER_POST")) ctx->defer_post = atoi(env) != 0;
+  // PRISIM_HIP_TAIL_PIECES (tail_plan.h): 0 = the plan's equal source pieces (the A/B hook, the bits of the form without the rule),
+  // "force" = the rule without its depth condition and 64-source floor (the test mode for small shapes); unset: the rule
+  ctx->tail_mode = kTailRule;
+  if (const char* env = getenv("PRISIM_HIP_TAIL_PIECES")) ctx->tail_mode = strcmp(env, "force") == 0 ? kTailForce : (atoi(env) != 0 ? kTailRule : kTailOff);
+  ctx->tail_key[0] = -1;      // (the tables are formed again for this array)
   // Four workgroups per CU.  Measured on the headline step beside the next sky-sum (profiles/LOG.md 4.1.9): the kernels' own grids
   // (8192 workgroups) flood the CUs and the memory system while the next snapshot's pack / prep and first round of sky-sum blocks start,
   // one or two per CU keep the passes resident for a millisecond and cost the sky-sum more than they hide.
@@ -846,6 +853,54 @@ static hipError_t launch_family(const SkyvisParams& q, int family, const Plan& p
   return hipErrorInvalidValue;
 }
 
+// The source pieces of route rt's sky-sum (tail_plan.h).  Only one family cuts its last piece: packed fp32 without the taper and without
+// a gradient, one launch over one set of complex64 partial cubes; everything else keeps the plan's pieces (ntail = 0).
+static TailPieces route_tail(const prisim_ctx* ctx, const SkyShape& s, const SkyRoute& rt, int scale_comp) {
+  const Plan& pl = rt.pl;
+  const bool family = scale_comp < 0 && rt.family == kFamPackedF32 && !s.taper && rt.nlaunch == 1 && rt.launch[0].family == kFamPackedF32 &&
+                      rt.launch[0].taper == 0 && rt.nsets == 1 && rt.part_f32 && pl.nsplit > 1;
+  const SkyLaunch& l = rt.launch[0];
+  return tail_pieces(pl.nsplit, l.src_per_split, pl.chunk, l.src_lo, l.src_hi, pl.ntiles, pl.nbgroups, 2 * (int64_t)std::max(ctx->cu_count, 1),
+                     family ? ctx->tail_mode : kTailOff, s.tune_nsplit != 0 || s.tune_chunk != 0);
+}
+
+// The device tables of tail pieces tp: boundaries and per-XCD slab table, uploaded on the compute stream when the pieces or the grid
+// are not those of the last upload (ctx_internal.h).  The sky-sums that read the old tables are ahead of the copy on the same stream.
+static int tail_tables(prisim_ctx* ctx, const TailPieces& tp, const Plan& pl) {
+  const int64_t key[9] = {tp.n, tp.ntail, tp.lo[0], tp.lo[1], tp.lo[tp.n - tp.ntail], tp.lo[tp.n - tp.ntail + 1], tp.lo[tp.n], pl.ntiles, pl.chunk};
+  if (std::equal(key, key + 9, ctx->tail_key) && ctx->tail_lo.p && ctx->tail_tab.p) return PRISIM_OK;
+  std::vector<int32_t> tab;
+  const int per = tail_slab_table(tp.n, pl.ntiles, tab);
+  const size_t lo_bytes = (size_t)(tp.n + 1) * sizeof(int64_t), tab_bytes = tab.size() * sizeof(int32_t);
+  int rc;
+  if ((rc = ensure(ctx, ctx->tail_lo, (size_t)(kTailMaxPieces + 1) * sizeof(int64_t))) || (rc = ensure_grow(ctx, ctx->tail_tab, tab_bytes))) return rc;
+  if (!ctx->ev_tail) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_tail, hipEventDisableTiming));
+  if (ctx->tail_pending) {      // the pinned area is free once the previous upload has read it
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev_tail));
+    ctx->tail_pending = false;
+  }
+  const size_t need = 1024 + tab_bytes;      // boundaries in the first KiB, the table behind them
+  if (need > ctx->h_tail_bytes) {
+    if (ctx->h_tail) { (void)hipHostFree(ctx->h_tail); ctx->h_tail = nullptr; ctx->h_tail_bytes = 0; }
+    if (hipHostMalloc(&ctx->h_tail, need + need / 4, hipHostMallocDefault) != hipSuccess) {
+      ctx->h_tail = nullptr;
+      return fail(ctx, PRISIM_ENOMEM, "hipHostMalloc for the tail-piece tables failed");
+    }
+    ctx->h_tail_bytes = need + need / 4;
+  }
+  static_assert((kTailMaxPieces + 1) * sizeof(int64_t) <= 1024, "the boundaries fit the first KiB of the pinned area");
+  memcpy(ctx->h_tail, tp.lo, lo_bytes);
+  memcpy((char*)ctx->h_tail + 1024, tab.data(), tab_bytes);
+  ctx->tail_key[0] = -1;      // (a failed copy leaves no key behind)
+  HIPCHK(ctx, hipMemcpyAsync(ctx->tail_lo.p, ctx->h_tail, lo_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->tail_tab.p, (char*)ctx->h_tail + 1024, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipEventRecord(ctx->ev_tail, ctx->stream));
+  ctx->tail_pending = true;
+  ctx->tail_per_xcd = per;
+  std::copy(key, key + 9, ctx->tail_key);
+  return PRISIM_OK;
+}
+
 // One sky-sum pass into `dst` ([nbl_sum][nchan] complex128: the cube slot, or the compact buffer of a folded array) along route rt0
 // (skyvis_plan.h; formed without the split form): rows in the route's layout, the split form's flags where it is eligible, then the
 // route's launches.  scale_comp >= 0 multiplies pbflux rows by dircos[:,comp] (a gradient component: never the split form).
@@ -880,6 +935,19 @@ static int run_pass(prisim_ctx* ctx, const SkyShape& s, const SkyToggles& t, con
   const SkyRoute& rt = split ? rt_split : rt0;
   if (prep) { int rcj = join_prep(ctx); if (rcj) return rcj; }      // rows, directions, flags are ready: the sums run on the compute stream
   p.out_f32 = rt.part_f32 ? 1 : 0;
+  // tail pieces (tail_plan.h): the launch then writes tp.n partial cubes, piece by piece, and the reduction sums them in piece order
+  const TailPieces tp = route_tail(ctx, s, rt, scale_comp);
+  const int ncubes = tp.ntail > 0 ? tp.n : pl.nsplit * rt.nsets;
+  if (tp.ntail > 0) {
+    if (int rct = tail_tables(ctx, tp, pl)) return rct;
+    p.tail_lo = (const int64_t*)ctx->tail_lo.p;
+    p.tail_tab = (const int32_t*)ctx->tail_tab.p;
+    p.tail_per_xcd = ctx->tail_per_xcd;
+  }
+  if (scale_comp < 0) {
+    ctx->last_sum_pieces = pl.nsplit > 1 ? ncubes : 1;
+    ctx->last_tail_pieces = tp.ntail;
+  }
   const size_t set_reals = (size_t)pl.nsplit * (size_t)ctx->nbl_sum * (size_t)ctx->nchan * 2;       // reals of one run's partial cubes
   auto set_out = [&](int r) -> double* {
     if (pl.nsplit == 1) return dst;
@@ -917,7 +985,7 @@ static int run_pass(prisim_ctx* ctx, const SkyShape& s, const SkyToggles& t, con
     HIPCHK(ctx, hipStreamWaitEvent(rs, ctx->ev_k1[ctx->ring_head], 0));
   }
   if (pl.nsplit > 1)
-    HIPCHK(ctx, launch_reduce_partials(part.p, rt.part_f32, dst, ctx->nbl_sum * ctx->nchan * 2, pl.nsplit * rt.nsets, rs,
+    HIPCHK(ctx, launch_reduce_partials(part.p, rt.part_f32, dst, ctx->nbl_sum * ctx->nchan * 2, ncubes, rs,
                                        post_set >= 0 ? (unsigned)ctx->post_blocks : 0u));
   return PRISIM_OK;
 }
@@ -1017,11 +1085,15 @@ int prisim_hip_compute(prisim_ctx* ctx, int precision, int kernel, int want_grad
   ctx->timing.last_split_uncorrected_groups = 0;
   ctx->timing.last_culled_fraction = 0.0;
   ctx->timing.last_batch_snapshots = 1;
+  ctx->last_sum_pieces = 1;
+  ctx->last_tail_pieces = 0;
   if (pl.kernel == PRISIM_KERNEL_RECURRENCE) {
     const size_t pbytes = (size_t)pl.ntiles * pl.nsrc_pad * pl.ct * (pl.f32 ? 4 : 8);
     if ((rc = ensure(ctx, ctx->sk->packed, pbytes))) return rc;
     if ((rc = ensure(ctx, ctx->sk->dirs_prep, (size_t)pl.nsrc_pad * 4 * sizeof(double)))) return rc;
-    if (pl.nsplit > 1 && (rc = ensure(ctx, post_set == 1 ? ctx->partial_b : ctx->partial, (size_t)rt.alloc_sets * (size_t)pl.nsplit * sum_elems * sizeof(double))))
+    // (tail pieces: the one family that takes them writes tp.n complex64 cubes into one set)
+    const size_t part_cubes = std::max((size_t)rt.alloc_sets * (size_t)pl.nsplit, (size_t)route_tail(ctx, shape, rt, -1).n);
+    if (pl.nsplit > 1 && (rc = ensure(ctx, post_set == 1 ? ctx->partial_b : ctx->partial, part_cubes * sum_elems * sizeof(double))))
       return rc;
     {
       // lifting rotation is used for a baseline group only when |step phase| <= 1/8 cycle (fp32; 1/4 cycle in fp64, where the
@@ -1259,6 +1331,15 @@ int prisim_hip_get_step_tiers(prisim_ctx* ctx, int64_t* last_sum_wide_groups, do
   if (!ctx) return PRISIM_EINVAL;
   if (last_sum_wide_groups) *last_sum_wide_groups = ctx->last_sum_wide_groups;
   if (wide_limit_cycles) *wide_limit_cycles = prisim::step_wide_limit_cycles();
+  return PRISIM_OK;
+  });
+}
+
+int prisim_hip_get_tail_pieces(prisim_ctx* ctx, int64_t* pieces, int64_t* tail_pieces) {
+  return guarded(ctx, [&]() -> int {
+  if (!ctx) return PRISIM_EINVAL;
+  if (pieces) *pieces = ctx->last_sum_pieces;
+  if (tail_pieces) *tail_pieces = ctx->last_tail_pieces;
   return PRISIM_OK;
   });
 }

@@ -607,6 +607,8 @@ int run_wave_batch(prisim_ctx* ctx, const BatchPlan& bp, const prisim_obs* obs, 
   ctx->timing.last_lift_groups = 0;
   ctx->last_sum_lift_groups = 0;
   ctx->last_sum_wide_groups = 0;
+  ctx->last_sum_pieces = (int)nsplit;      // (the batched launch sums its own nsplit partial cubes per snapshot; no tail pieces)
+  ctx->last_tail_pieces = 0;
   ctx->timing.last_taper_group = 0;
   ctx->timing.last_taper_split = 0;
   ctx->timing.last_split_uncorrected_groups = 0;

@@ -21,6 +21,7 @@
 #include "baseline_fold.h"
 #include "step_bound.h"
 #include "split_plan.h"
+#include "tail_plan.h"
 #include "skyvis_plan.h"
 
 using namespace prisim;
@@ -178,6 +179,18 @@ struct prisim_ctx {
   int post_last = -1;
   bool defer_post = true;                 // PRISIM_HIP_DEFER_POST=0: the single-stream order (the A/B hook; read by set_array)
   int post_blocks = 0;                    // workgroups of a deferred reduce / expand launch (PRISIM_HIP_POST_BLOCKS; 0: the kernels' own grids)
+  // Tail pieces (tail_plan.h): the packed fp32 sky-sum without the taper cuts the last of the plan's source pieces into small ones.  The
+  // piece boundaries and the per-XCD slab table live on the device and are uploaded only when what they are formed from changes
+  // (tail_key: plan, source range, grid, mode) -- through a pinned area, on the compute stream; ev_tail: the last upload has read it.
+  int tail_mode = kTailRule;              // PRISIM_HIP_TAIL_PIECES (read by set_array): 0 = the plan's pieces, "force" = the test mode
+  DevBuf tail_lo, tail_tab;
+  void* h_tail = nullptr;
+  size_t h_tail_bytes = 0;
+  hipEvent_t ev_tail = nullptr;
+  bool tail_pending = false;
+  int64_t tail_key[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int tail_per_xcd = 0;
+  int last_sum_pieces = 0, last_tail_pieces = 0;      // of the last compute() (prisim_hip_get_tail_pieces)
   // per-snapshot sky inputs (flux_ref / spindex or a flux table, beamformer elements, validity flag): owned by the context so that
   // a set_sky_* call allocates nothing after the first snapshot
   DevBuf sky_flux, sky_sp, sky_bf, sky_flag;

@@ -78,6 +78,13 @@ struct SkyvisParams {
   int32_t pad4_;
   // packed fp32 kernel without the taper (k_skyvis_rec_f32pk<CT, false>) only: the second tier of the step flag (step_bound.h)
   const int32_t* wide_flags; // [nbgroups] 1: |step phase| <= the wide limit for this baseline group (or nullptr); read where lift_flags is 0
+  // ... and its tail pieces (tail_plan.h; both nullptr: the nsplit equal pieces above, mapped by block_item): the sources are cut into
+  // unequal pieces, piece i = [tail_lo[i], tail_lo[i + 1]) writing partial cube i, and block b runs group nbgroups - 1 - (b >> 3) % nbgroups
+  // of slab tail_tab[b & 7][(b >> 3) / nbgroups] on a grid of 8 * tail_per_xcd * nbgroups blocks
+  const int64_t* tail_lo;    // [pieces + 1]
+  const int32_t* tail_tab;   // [8][tail_per_xcd] pairs (piece, tile); -1: no slab
+  int32_t tail_per_xcd;
+  int32_t pad5_;
 };
 
 hipError_t launch_skyvis_rec(const SkyvisParams& p, bool f32, int ct, hipStream_t stream);

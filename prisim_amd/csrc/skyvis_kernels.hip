@@ -369,6 +369,23 @@ __device__ __forceinline__ bool block_item(const SkyvisParams& p, int& slab, int
   return (int)(blockIdx.x >> 3) < per_xcd && item < total;
 }
 
+// The map of the packed fp32 kernel without the taper under TAIL PIECES (tail_plan.h; p.tail_tab set): the source pieces are unequal --
+// the plan's last piece is cut into small ones that close the launch -- so a cut of the items by count would give the XCDs unequal
+// work.  The host deals the slabs (piece, tile) round-robin to the XCDs instead, big pieces first, and block b runs one baseline group
+// of slab tail_tab[b & 7][(b >> 3) / nbgroups]: a slab's groups stay on one XCD, walked last-first as above.  One scalar load per block;
+// false for an XCD's padding entries (-1).  Launched on exactly 8 * tail_per_xcd * nbgroups blocks (launch_rec_pk_ct).
+__device__ __forceinline__ bool tail_item(const SkyvisParams& p, int& piece, int& tile, int& bg) {
+  typedef const __attribute__((address_space(4))) int32_t* cint_p;
+  const int local = (int)(blockIdx.x >> 3);
+  const int j = local / p.nbgroups;
+  if (j >= p.tail_per_xcd) return false;
+  const cint_p e = (cint_p)(uintptr_t)(p.tail_tab + ((size_t)(blockIdx.x & 7) * (size_t)p.tail_per_xcd + (size_t)j) * 2);
+  piece = e[0];
+  tile = e[1];
+  bg = p.nbgroups - 1 - (local - j * p.nbgroups);
+  return piece >= 0;
+}
+
 // LIFT: lifting (three-shear) form of the step rotation, see skyvis_rec_f32pk_body below; chosen per baseline group by the host.
 // TAPER: 0 = none; 1 = exact second-order amplitude recurrence on the pbflux operand (8 instructions per term);
 //   2 (fp64 only, k_skyvis_taper_f64) = the GROUPED form of the packed fp32 kernels carried over to fp64, made exact: ONE chain from the
@@ -1215,15 +1232,30 @@ __device__ __forceinline__ void skyvis_rec_f32pk_body(const SkyvisParams& p, uns
   constexpr int ROWF = GPK ? 4 * CT : CT;            // floats per (source, tile) row
   constexpr int NP = ROWF / NPART;                   // floats per piece
 
-  int slab, bg;
-  if (!block_item<!TAPER && !GRAD>(p, slab, bg)) return;      // (as the kernel that chose this body maps its blocks)
-  const int tile = slab % p.ntiles;
-  const int split = slab / p.ntiles;
-
-  // sources [src_lo, src_hi) of the sky (the whole sky unless the host walks it in ranges of one source size), cut into nsplit pieces
-  int64_t s_begin = p.src_lo + (int64_t)split * p.src_per_split;
-  int64_t s_end = s_begin + p.src_per_split;
-  if (s_end > p.src_hi) s_end = p.src_hi;
+  int slab, bg = 0;
+  int tile = 0, split = 0;
+  int64_t s_begin = 0, s_end = 0;
+  bool tailed = false;
+  if constexpr (!TAPER && !GRAD) {
+    // tail pieces (tail_plan.h): `split` is the piece -- its sources come from the boundary table, its partial cube is cube `split`
+    if (p.tail_tab != nullptr) {
+      if (!tail_item(p, split, tile, bg)) return;
+      typedef const __attribute__((address_space(4))) int64_t* ci64_p;
+      const ci64_p lo = (ci64_p)(uintptr_t)p.tail_lo;
+      s_begin = lo[split];
+      s_end = lo[split + 1];
+      tailed = true;
+    }
+  }
+  if (!tailed) {
+    if (!block_item<!TAPER && !GRAD>(p, slab, bg)) return;      // (as the kernel that chose this body maps its blocks)
+    tile = slab % p.ntiles;
+    split = slab / p.ntiles;
+    // sources [src_lo, src_hi) of the sky (the whole sky unless the host walks it in ranges of one source size), cut into nsplit pieces
+    s_begin = p.src_lo + (int64_t)split * p.src_per_split;
+    s_end = s_begin + p.src_per_split;
+    if (s_end > p.src_hi) s_end = p.src_hi;
+  }
   if (TAPER && p.src_first != nullptr) {
     // taper culling: the group's leading sources are provably below the tolerance (capi.cpp).  What is left is cut into nsplit EQUAL
     // pieces again, so that every split of the group shrinks alike (the XCD map deals whole slabs to XCDs: skipping only the first
@@ -1805,7 +1837,12 @@ void k_skyvis_rec_f32pk(const SkyvisParams p) {
   if constexpr (!TAPER) {
     // block-uniform choice made by the host per baseline group; the two bodies share no live state
     int slab_, bg;
-    if (!block_item<true>(p, slab_, bg)) return;
+    if (p.tail_tab != nullptr) {
+      int tile_;
+      if (!tail_item(p, slab_, tile_, bg)) return;
+    } else if (!block_item<true>(p, slab_, bg)) {
+      return;
+    }
     if (p.lift_flags != nullptr && p.lift_flags[bg] != 0) {
       skyvis_rec_f32pk_body<CT, false, true>(p, flush_lds);
       return;
@@ -2247,7 +2284,12 @@ static hipError_t launch_rec_ct(const SkyvisParams& p, hipStream_t stream) {
 
 template <int CT>
 static hipError_t launch_rec_pk_ct(const SkyvisParams& p, hipStream_t stream) {
-  const unsigned grid = item_grid((int64_t)p.ntiles * p.nsplit * p.nbgroups);          // see block_item()
+  unsigned grid = item_grid((int64_t)p.ntiles * p.nsplit * p.nbgroups);          // see block_item()
+  if (p.tail_tab != nullptr || p.tail_lo != nullptr) {
+    // tail pieces: the kernel without the taper only, and exactly the blocks the table has entries for (see tail_item())
+    if (p.taper || !p.tail_tab || !p.tail_lo || p.tail_per_xcd < 1) return hipErrorInvalidValue;
+    grid = item_grid((int64_t)8 * p.tail_per_xcd * p.nbgroups);
+  }
   if (!grid) return hipErrorInvalidValue;
   if (p.taper)
     hipLaunchKernelGGL((k_skyvis_rec_f32pk<CT, true>), dim3(grid), dim3(kBlockThreads), 0, stream, p);
