@@ -478,7 +478,16 @@ int prisim_hip_get_timing(prisim_ctx* ctx, prisim_timing* out, int reset);
  * last_culled_fraction and last_split_uncorrected_groups refer to the summed rows.  Any pointer may be NULL.  (Kept out of
  * prisim_timing: its layout is frozen at 96 bytes.)  PRISIM_HIP_FOLD=0 in the environment turns folding off. */
 int prisim_hip_get_fold_info(prisim_ctx* ctx, int64_t* last_sum_baselines, int64_t* last_terms_evaluated, int64_t* last_sum_lift_groups);
-/* The second tier of the fp32 step flag (csrc/step_bound.h).  A group of 256 summed rows whose step bound exceeds the 1/8-cycle
+/* Vectors equal to rounding (csrc/baseline_fold.h).  A redundant layout built by floating-point arithmetic gives lattice-equal
+ * baselines vectors that differ in their last bits.  prisim_hip_set_array also clusters the rows within tol = 16 * 2^-52 * max|component|
+ * (per component) of a cluster's first row, and sums each cluster once with that row's vector when this leaves fewer rows than the
+ * exact fold, meets the exact fold's conditions (at most 7/8 of the rows, more than 256) and the phase it can cost,
+ * 2 pi max|f| / c * 2 * max_dev, is at most 1e-12 rad; otherwise the exact fold is tried as above.  exact_baselines / near_baselines:
+ * the rows either fold would sum; max_dev_m: the largest |b - b_rep| of a row from its cluster's first row; phase_bound_rad: the
+ * bound above; used: 1 when the kernels see the clusters.  The values are those of the last prisim_hip_set_array.  Any pointer may
+ * be NULL.  PRISIM_HIP_FOLD_NEAR=0 in the environment (read by prisim_hip_set_array) keeps the exact fold. */
+int prisim_hip_get_fold_near(prisim_ctx* ctx, int64_t* exact_baselines, int64_t* near_baselines, double* max_dev_m, double* phase_bound_rad, int* used);
+/* The second tier of the fp32 step flag (csrc/step_bound.h). A group of 256 summed rows whose step bound exceeds the 1/8-cycle
  * lifting limit but not the wide limit runs the leapfrog with a sine fitted for that range, in the packed fp32 kernel without the
  * taper only (not the fused gradient, not fp64).  last_sum_wide_groups: those groups in the last compute(), counted beside -- not in --
  * last_sum_lift_groups; wide_limit_cycles: the limit.  Either pointer may be NULL.  PRISIM_HIP_WIDE_LEAPFROG=0 in the environment

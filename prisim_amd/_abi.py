@@ -509,6 +509,7 @@ _PROTOTYPES = {
         int prisim_hip_sync(p ctx);
         int prisim_hip_get_timing(p ctx, *prisim_timing out, i reset);
         int prisim_hip_get_fold_info(p ctx, *q last_sum_baselines, *q last_terms_evaluated, *q last_sum_lift_groups);
+        int prisim_hip_get_fold_near(p ctx, *q exact_baselines, *q near_baselines, *d max_dev_m, *d phase_bound_rad, *i used);
         int prisim_hip_get_step_tiers(p ctx, *q last_sum_wide_groups, *d wide_limit_cycles);
         int prisim_hip_get_tail_pieces(p ctx, *q pieces, *q tail_pieces);
         int prisim_hip_device_info(p ctx, *i cu_count, *i clock_khz, s name);
@@ -2329,6 +2330,16 @@ class Context(object):
         out['last_sum_lift_groups'] = nlift.value
         out['last_sum_baselines'] = nsum.value
         out['last_terms_evaluated'] = nterms.value
+        # vectors equal to rounding (csrc/baseline_fold.h): the rows the exact and the merged fold of the last set_array() would sum, the
+        # largest |b - b_rep| of the merged one (m), the phase it bounds (rad), and whether the kernels see the merged clusters
+        nexact, nnear, dev, phase, used = C.c_int64(), C.c_int64(), C.c_double(), C.c_double(), C.c_int()
+        self._check(self._lib.prisim_hip_get_fold_near(self._h, C.byref(nexact), C.byref(nnear), C.byref(dev), C.byref(phase), C.byref(used)),
+                    'prisim_hip_get_fold_near')
+        out['fold_exact_baselines'] = nexact.value
+        out['fold_near_baselines'] = nnear.value
+        out['fold_near_max_dev_m'] = dev.value
+        out['fold_near_phase_bound'] = phase.value
+        out['fold_near_used'] = used.value
         # the second tier of the fp32 step flag: groups of 256 summed rows that ran the wide leapfrog body, and its limit in cycles
         nwide, wlim = C.c_int64(), C.c_double()
         self._check(self._lib.prisim_hip_get_step_tiers(self._h, C.byref(nwide), C.byref(wlim)), 'prisim_hip_get_step_tiers')

@@ -197,12 +197,32 @@ int prisim_hip_set_array(prisim_ctx* ctx, const double* bl_enu, int64_t nbl, con
   // Fold map: rows of equal vectors are summed once and expanded into the cube (baseline_fold.h).  On when it removes at least an
   // eighth of the rows and the folded array is still more than one baseline group, so that a folded context never enters the
   // wave-item or batched small-array paths (those are chosen by ctx->nbl <= kBlockThreads).  PRISIM_HIP_FOLD=0: off (the A/B hook).
+  // Vectors equal to rounding (within 16 ulp of the largest coordinate, per component) are merged onto the first of them when that
+  // leaves fewer rows and the phase it can cost, 2 pi f_max / c * 2 * max|b - b_rep|, is within 1e-12 rad (choose_fold): the kernels
+  // then see the representatives' vectors.  PRISIM_HIP_FOLD_NEAR=0: the exact fold only (the A/B hook, the bits of the form without it).
   std::vector<int64_t> fold_rep;
   std::vector<int32_t> fold_map;
   fold_baselines(bl_enu, nbl, fold_rep, fold_map);
+  {
+    std::vector<int64_t> near_rep;
+    std::vector<int32_t> near_map;
+    double max_dev = 0.0, fmax = 0.0;
+    fold_baselines_near(bl_enu, nbl, fold_near_tol(bl_enu, nbl), near_rep, near_map, max_dev);
+    for (int64_t i = 0; i < nchan; ++i) fmax = std::max(fmax, std::fabs(freqs_hz[i]));
+    bool allow_near = true, allow = true;
+    if (const char* env = getenv("PRISIM_HIP_FOLD_NEAR")) allow_near = atoi(env) != 0;
+    if (const char* env = getenv("PRISIM_HIP_FOLD")) allow = atoi(env) != 0;
+    ctx->fold_exact_nbl = (int64_t)fold_rep.size();
+    ctx->fold_near_nbl = (int64_t)near_rep.size();
+    ctx->fold_near_max_dev = max_dev;
+    ctx->fold_near_phase = fold_near_phase_bound(max_dev, fmax);
+    const FoldKind kind = !allow ? kFoldNone : choose_fold(nbl, ctx->fold_exact_nbl, ctx->fold_near_nbl, ctx->fold_near_phase, kBlockThreads, allow_near);
+    ctx->fold_near_used = kind == kFoldNear;
+    if (kind == kFoldNear) { fold_rep.swap(near_rep); fold_map.swap(near_map); }
+    else if (kind == kFoldNone) { fold_rep.clear(); }
+  }
   const int64_t nbl_u = (int64_t)fold_rep.size();
-  bool fold = nbl_u * 8 <= nbl * 7 && nbl_u > kBlockThreads;
-  if (const char* env = getenv("PRISIM_HIP_FOLD")) fold = fold && atoi(env) != 0;
+  const bool fold = nbl_u > 0;
   // PRISIM_HIP_WIDE_LEAPFROG=0: no group takes the wide tier of the fp32 leapfrog (step_bound.h); the A/B hook, bit-identical to the form without it
   ctx->wide_leapfrog = true;
   if (const char* env = getenv("PRISIM_HIP_WIDE_LEAPFROG")) ctx->wide_leapfrog = atoi(env) != 0;
@@ -1322,6 +1342,18 @@ int prisim_hip_get_fold_info(prisim_ctx* ctx, int64_t* last_sum_baselines, int64
   if (last_sum_baselines) *last_sum_baselines = ctx->last_sum_baselines;
   if (last_terms_evaluated) *last_terms_evaluated = ctx->last_terms_evaluated;
   if (last_sum_lift_groups) *last_sum_lift_groups = ctx->last_sum_lift_groups;
+  return PRISIM_OK;
+  });
+}
+
+int prisim_hip_get_fold_near(prisim_ctx* ctx, int64_t* exact_baselines, int64_t* near_baselines, double* max_dev_m, double* phase_bound_rad, int* used) {
+  return guarded(ctx, [&]() -> int {
+  if (!ctx) return PRISIM_EINVAL;
+  if (exact_baselines) *exact_baselines = ctx->fold_exact_nbl;
+  if (near_baselines) *near_baselines = ctx->fold_near_nbl;
+  if (max_dev_m) *max_dev_m = ctx->fold_near_max_dev;
+  if (phase_bound_rad) *phase_bound_rad = ctx->fold_near_phase;
+  if (used) *used = ctx->fold_near_used ? 1 : 0;
   return PRISIM_OK;
   });
 }

@@ -130,6 +130,11 @@ struct prisim_ctx {
   bool folded = false;
   int64_t nbl_sum = 0;                // rows the sky-sum computes: distinct vectors when folded, nbl otherwise
   DevBuf ublx, ubly, ublz, fold_map, fold_vis, fold_grad;
+  // The two folds set_array chose between (prisim_hip_get_fold_near): distinct vectors by IEEE value, clusters of vectors equal to
+  // rounding, the largest |b - b_rep| of the latter and the phase it bounds, and whether the kernels see the clusters' representatives.
+  int64_t fold_exact_nbl = 0, fold_near_nbl = 0;
+  double fold_near_max_dev = 0.0, fold_near_phase = 0.0;
+  bool fold_near_used = false;
   int64_t last_sum_baselines = 0, last_terms_evaluated = 0, last_sum_lift_groups = 0;      // of the last compute() (prisim_hip_get_fold_info)
   int64_t last_sum_wide_groups = 0;   // groups of the last compute() that ran the wide leapfrog body (prisim_hip_get_step_tiers)
   bool wide_leapfrog = true;          // PRISIM_HIP_WIDE_LEAPFROG=0 (read by set_array): the wide table stays all zero
