@@ -411,6 +411,49 @@ def _closure_inputs(legs, conj, bpwts, freq_wts, masks, mask_index, nbl, nchan, 
     return lg, cj, bw, fw, mk, mi
 
 
+def _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube, weights, chan_avg, aberr_beta, route, budget_bytes):
+    """The inputs dirty_image, mosaic_image and clean_image take alike, checked and put into the fields that their argument structs
+    have under the same names: unitvec (npix, 3), rot (nt, 3, 3), pc_dircos (nt, 3), baselines (nbl, 3), freqs_hz (nchan,), aberr_beta
+    (nt, 3) or None: float64; cube (nt, nbl, nchan) complex128 or None; weights None, (nbl,) or (nt, nbl, nchan), which decides
+    weight_form; chan_avg, route and budget_bytes.  Returns (npix, nbl, nchan, nt, resident, keep): resident, the cube is None; keep,
+    the arrays the struct points into, to be held until the call is over."""
+    uv = NP.ascontiguousarray(unitvec, dtype=NP.float64).reshape(-1, 3)
+    rt = NP.ascontiguousarray(rot, dtype=NP.float64).reshape(-1, 9)
+    pc = NP.ascontiguousarray(pc_dircos, dtype=NP.float64).reshape(-1, 3)
+    bl = NP.ascontiguousarray(baselines, dtype=NP.float64).reshape(-1, 3)
+    fq = NP.ascontiguousarray(freqs_hz, dtype=NP.float64).ravel()
+    npix, nt, nbl, nchan = uv.shape[0], rt.shape[0], bl.shape[0], fq.size
+    if pc.shape[0] != nt:
+        raise ValueError('pc_dircos must have one row per snapshot')
+    ab = None
+    if aberr_beta is not None:
+        ab = NP.ascontiguousarray(aberr_beta, dtype=NP.float64).reshape(-1, 3)
+        if ab.shape[0] != nt:
+            raise ValueError('aberr_beta must have one row per snapshot')
+    if route != 'auto' and route not in IMAGING_ROUTES.values():
+        raise ValueError("route must be 'auto', 'direct' or 'stepped'")
+    x = None
+    if cube is not None:
+        x = NP.ascontiguousarray(cube, dtype=NP.complex128)
+        if x.shape != (nt, nbl, nchan):
+            raise ValueError('cube must be (nt, nbl, nchan)')
+    w, form = None, PRISIM_IMAGE_W_NONE
+    if weights is not None:
+        w = NP.ascontiguousarray(weights, dtype=NP.float64)
+        if w.shape == (nbl,):
+            form = PRISIM_IMAGE_W_BASELINE
+        elif w.shape == (nt, nbl, nchan):
+            form = PRISIM_IMAGE_W_FULL
+        else:
+            raise ValueError('weights must be None, (nbl,) or (nt, nbl, nchan)')
+    a.npix, a.nbl, a.nchan, a.nt = npix, nbl, nchan, nt
+    a.unitvec, a.rot, a.aberr_beta, a.pc_dircos = _ptr(uv), _ptr(rt), _ptr(ab), _ptr(pc)
+    a.baselines, a.freqs_hz, a.cube, a.weights = _ptr(bl), _ptr(fq), _ptr(x), _ptr(w)
+    a.weight_form, a.chan_avg, a.route = form, 1 if chan_avg else 0, _route_code(route, IMAGING_ROUTES)
+    a.budget_bytes = int(budget_bytes or 0)
+    return npix, nbl, nchan, nt, x is None, (uv, rt, pc, bl, fq, ab, x, w)
+
+
 def _want_bits(want, bits):
     """The OR of bits[name] over the names of want; KeyError on an unknown name."""
     flag = 0
@@ -1487,49 +1530,18 @@ class Context(object):
         or 'stepped'; budget_bytes: device bytes of the streamed buffers (0: 1 GiB), which the result does not depend on.  Returns
         (image (npix, nchan) or (npix,), wsum (nchan,) or (1,), stats); a zero weight sum is NaN in the image; stats['resident']: the
         resident cube was read."""
-        uv = NP.ascontiguousarray(unitvec, dtype=NP.float64).reshape(-1, 3)
-        rt = NP.ascontiguousarray(rot, dtype=NP.float64).reshape(-1, 9)
-        pc = NP.ascontiguousarray(pc_dircos, dtype=NP.float64).reshape(-1, 3)
-        bl = NP.ascontiguousarray(baselines, dtype=NP.float64).reshape(-1, 3)
-        fq = NP.ascontiguousarray(freqs_hz, dtype=NP.float64).ravel()
-        npix, nt, nbl, nchan = uv.shape[0], rt.shape[0], bl.shape[0], fq.size
-        if pc.shape[0] != nt:
-            raise ValueError('pc_dircos must have one row per snapshot')
-        ab = None
-        if aberr_beta is not None:
-            ab = NP.ascontiguousarray(aberr_beta, dtype=NP.float64).reshape(-1, 3)
-            if ab.shape[0] != nt:
-                raise ValueError('aberr_beta must have one row per snapshot')
         if kind not in IMAGING_KINDS:
             raise ValueError("kind must be 'dirty' or 'psf'")
-        if route != 'auto' and route not in IMAGING_ROUTES.values():
-            raise ValueError("route must be 'auto', 'direct' or 'stepped'")
-        x = None
-        if cube is not None and kind == 'dirty':
-            x = NP.ascontiguousarray(cube, dtype=NP.complex128)
-            if x.shape != (nt, nbl, nchan):
-                raise ValueError('cube must be (nt, nbl, nchan)')
-        w, form = None, PRISIM_IMAGE_W_NONE
-        if weights is not None:
-            w = NP.ascontiguousarray(weights, dtype=NP.float64)
-            if w.shape == (nbl,):
-                form = PRISIM_IMAGE_W_BASELINE
-            elif w.shape == (nt, nbl, nchan):
-                form = PRISIM_IMAGE_W_FULL
-            else:
-                raise ValueError('weights must be None, (nbl,) or (nt, nbl, nchan)')
         a = self.PrisimImagingArgs()
-        a.npix, a.nbl, a.nchan, a.nt = npix, nbl, nchan, nt
-        a.unitvec, a.rot, a.aberr_beta, a.pc_dircos = _ptr(uv), _ptr(rt), _ptr(ab), _ptr(pc)
-        a.baselines, a.freqs_hz, a.cube, a.weights = _ptr(bl), _ptr(fq), _ptr(x), _ptr(w)
-        a.kind, a.weight_form, a.chan_avg = IMAGING_KINDS[kind], form, 1 if chan_avg else 0
-        a.route = _route_code(route, IMAGING_ROUTES)
-        a.budget_bytes = int(budget_bytes or 0)
+        npix, _, nchan, _, resident, keep = _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube if kind == 'dirty' else None,
+                                                            weights, chan_avg, aberr_beta, route, budget_bytes)
+        a.kind = IMAGING_KINDS[kind]
         image = NP.empty((npix,) if chan_avg else (npix, nchan), dtype=NP.float64)
         wsum = NP.empty(1 if chan_avg else nchan, dtype=NP.float64)
         st = self.PrisimImagingStats()
         self._call('prisim_dirty_image', a=a, out_image=image, out_wsum=wsum, stats=st)
-        return image, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=x is None and kind == 'dirty')
+        del keep
+        return image, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident and kind == 'dirty')
 
     # ---- beam-weighted mosaics of the snapshots (include/prisim_mosaic.h) ----
     PrisimMosaicStats = _PrisimMosaicStats
@@ -1546,51 +1558,19 @@ class Context(object):
         effective beam sqrt(Q / Wtot) is below it is NaN; 0 masks only Q == 0.  Returns (mosaic (npix, nchan) or (npix,), num, den
         (npix, nchan) -- None without want_sums --, wsum (nchan,), stats); stats['pb_eff'] is the effective beam in the shape of the
         mosaic and stats['resident'] whether the resident cube was read."""
-        uv = NP.ascontiguousarray(unitvec, dtype=NP.float64).reshape(-1, 3)
-        rt = NP.ascontiguousarray(rot, dtype=NP.float64).reshape(-1, 9)
-        pc = NP.ascontiguousarray(pc_dircos, dtype=NP.float64).reshape(-1, 3)
-        bl = NP.ascontiguousarray(baselines, dtype=NP.float64).reshape(-1, 3)
-        fq = NP.ascontiguousarray(freqs_hz, dtype=NP.float64).ravel()
-        npix, nt, nbl, nchan = uv.shape[0], rt.shape[0], bl.shape[0], fq.size
-        if pc.shape[0] != nt:
-            raise ValueError('pc_dircos must have one row per snapshot')
-        ab = None
-        if aberr_beta is not None:
-            ab = NP.ascontiguousarray(aberr_beta, dtype=NP.float64).reshape(-1, 3)
-            if ab.shape[0] != nt:
-                raise ValueError('aberr_beta must have one row per snapshot')
-        if route != 'auto' and route not in IMAGING_ROUTES.values():
-            raise ValueError("route must be 'auto', 'direct' or 'stepped'")
-        x = None
-        if cube is not None:
-            x = NP.ascontiguousarray(cube, dtype=NP.complex128)
-            if x.shape != (nt, nbl, nchan):
-                raise ValueError('cube must be (nt, nbl, nchan)')
-        w, form = None, PRISIM_IMAGE_W_NONE
-        if weights is not None:
-            w = NP.ascontiguousarray(weights, dtype=NP.float64)
-            if w.shape == (nbl,):
-                form = PRISIM_IMAGE_W_BASELINE
-            elif w.shape == (nt, nbl, nchan):
-                form = PRISIM_IMAGE_W_FULL
-            else:
-                raise ValueError('weights must be None, (nbl,) or (nt, nbl, nchan)')
+        a = self.PrisimMosaicArgs()
+        npix, _, nchan, nt, resident, keep = _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube, weights, chan_avg, aberr_beta,
+                                                             route, budget_bytes)
         bpc = NP.ascontiguousarray(beam_pc_dircos, dtype=NP.float64)
         if bpc.shape not in ((3,), (nt, 3)):
             raise ValueError('beam_pc_dircos must be (3,) or one row per snapshot (nt, 3)')
-        exts, xs, keep = _beam_ext_array(ext)
-        a = self.PrisimMosaicArgs()
-        a.npix, a.nbl, a.nchan, a.nt = npix, nbl, nchan, nt
-        a.unitvec, a.rot, a.aberr_beta, a.pc_dircos = _ptr(uv), _ptr(rt), _ptr(ab), _ptr(pc)
-        a.baselines, a.freqs_hz, a.cube, a.weights = _ptr(bl), _ptr(fq), _ptr(x), _ptr(w)
-        a.weight_form, a.chan_avg, a.route = form, 1 if chan_avg else 0, _route_code(route, IMAGING_ROUTES)
+        exts, xs, keep_ext = _beam_ext_array(ext)
         a.beam_kind, a.diameter_m = int(beam_kind), float(diameter_m)
         a.beam_pc_dircos[:] = bpc.reshape(-1, 3)[0].tolist()
         a.beam_pc_snap = _ptr(bpc) if bpc.ndim == 2 else None
         a.ext = C.cast(xs, C.c_void_p) if exts else None
         a.n_ext = len(exts)
         a.pbmin = float(pbmin)
-        a.budget_bytes = int(budget_bytes or 0)
         shape = (npix,) if chan_avg else (npix, nchan)
         mosaic, pb_eff = NP.empty(shape, dtype=NP.float64), NP.empty(shape, dtype=NP.float64)
         num = NP.empty((npix, nchan), dtype=NP.float64) if want_sums else None
@@ -1598,8 +1578,8 @@ class Context(object):
         wsum = NP.empty(nchan, dtype=NP.float64)
         st = self.PrisimMosaicStats()
         self._call('prisim_mosaic_image', a=a, out_mosaic=mosaic, out_pb_eff=pb_eff, out_num=num, out_den=den, out_wsum=wsum, stats=st)
-        del keep
-        return mosaic, num, den, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=x is None, pb_eff=pb_eff)
+        del keep, keep_ext
+        return mosaic, num, den, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident, pb_eff=pb_eff)
 
     # ---- Hogbom CLEAN of dirty images with the exact beam (include/prisim_imclean.h) ----
     PrisimImcleanStats = _PrisimImcleanStats
@@ -1618,36 +1598,10 @@ class Context(object):
         which no result depends on.  Returns a dict: 'residual' and 'restored' (or None) (npix, nchan) or (npix,); 'comp_pixel' int32
         and 'comp_flux' (nc, longest list), the unused tail of a row -1 and 0; 'ncomp', 'status' (PRISIM_IMCLEAN_* bits) int32 and
         'peak0', 'wsum' (nc,); and the stats dict."""
-        uv = NP.ascontiguousarray(unitvec, dtype=NP.float64).reshape(-1, 3)
-        rt = NP.ascontiguousarray(rot, dtype=NP.float64).reshape(-1, 9)
-        pc = NP.ascontiguousarray(pc_dircos, dtype=NP.float64).reshape(-1, 3)
-        bl = NP.ascontiguousarray(baselines, dtype=NP.float64).reshape(-1, 3)
-        fq = NP.ascontiguousarray(freqs_hz, dtype=NP.float64).ravel()
-        npix, nt, nbl, nchan = uv.shape[0], rt.shape[0], bl.shape[0], fq.size
+        a = self.PrisimImcleanArgs()
+        npix, _, nchan, _, resident, keep = _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube, weights, chan_avg, aberr_beta,
+                                                            route, budget_bytes)
         nc = 1 if chan_avg else nchan
-        if pc.shape[0] != nt:
-            raise ValueError('pc_dircos must have one row per snapshot')
-        ab = None
-        if aberr_beta is not None:
-            ab = NP.ascontiguousarray(aberr_beta, dtype=NP.float64).reshape(-1, 3)
-            if ab.shape[0] != nt:
-                raise ValueError('aberr_beta must have one row per snapshot')
-        if route != 'auto' and route not in IMAGING_ROUTES.values():
-            raise ValueError("route must be 'auto', 'direct' or 'stepped'")
-        x = None
-        if cube is not None:
-            x = NP.ascontiguousarray(cube, dtype=NP.complex128)
-            if x.shape != (nt, nbl, nchan):
-                raise ValueError('cube must be (nt, nbl, nchan)')
-        w, form = None, PRISIM_IMAGE_W_NONE
-        if weights is not None:
-            w = NP.ascontiguousarray(weights, dtype=NP.float64)
-            if w.shape == (nbl,):
-                form = PRISIM_IMAGE_W_BASELINE
-            elif w.shape == (nt, nbl, nchan):
-                form = PRISIM_IMAGE_W_FULL
-            else:
-                raise ValueError('weights must be None, (nbl,) or (nt, nbl, nchan)')
         win = None
         if window is not None:
             win = NP.ascontiguousarray(NP.asarray(window) != 0, dtype=NP.uint8)
@@ -1657,14 +1611,8 @@ class Context(object):
         if fwhm_rad is not None:
             fw = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(fwhm_rad, dtype=NP.float64), (nc,)))
         maxiter = int(maxiter)
-        a = self.PrisimImcleanArgs()
-        a.npix, a.nbl, a.nchan, a.nt = npix, nbl, nchan, nt
-        a.unitvec, a.rot, a.aberr_beta, a.pc_dircos = _ptr(uv), _ptr(rt), _ptr(ab), _ptr(pc)
-        a.baselines, a.freqs_hz, a.cube, a.weights = _ptr(bl), _ptr(fq), _ptr(x), _ptr(w)
         a.window, a.fwhm_rad = _ptr(win), _ptr(fw)
         a.gain, a.threshold, a.maxiter = float(gain), float(threshold), maxiter
-        a.budget_bytes = int(budget_bytes or 0)
-        a.weight_form, a.chan_avg, a.route = form, 1 if chan_avg else 0, _route_code(route, IMAGING_ROUTES)
         a.threshold_relative, a.poll_every = 1 if threshold_relative else 0, int(poll_every or 0)
         shape = (npix,) if chan_avg else (npix, nchan)
         rows = max(maxiter, 0)
@@ -1677,10 +1625,11 @@ class Context(object):
         st = self.PrisimImcleanStats()
         self._call('prisim_clean_image', a=a, out_residual=residual, out_restored=restored, out_comp_pixel=pixel, out_comp_flux=flux,
                    out_ncomp=ncomp, out_status=status, out_peak0=peak0, out_wsum=wsum, stats=st)
+        del keep
         longest = int(ncomp.max()) if nc else 0
         return {'residual': residual, 'restored': restored, 'comp_pixel': NP.ascontiguousarray(pixel[:, :longest]),
                 'comp_flux': NP.ascontiguousarray(flux[:, :longest]), 'ncomp': ncomp, 'status': status, 'peak0': peak0, 'wsum': wsum,
-                'stats': dict(_stats_dict(st, route=IMAGING_ROUTES), resident=x is None)}
+                'stats': dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident)}
 
     # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
     def closure_delay_spectra(self, wts, m, df, phases=None, cube=None, legs=None, conj=None, bpwts=None, freq_wts=None, masks=None,

@@ -1,14 +1,14 @@
 // imclean.hip -- Hogbom CLEAN of a dirty image with the exact beam for gfx950 (include/prisim_imclean.h).  The first residual is the
-// dirty image by the kernels of prisim_dirty_image (imaging_kernels.h), over all pixels at once; then, per iteration, three launches
-// that never wait for the host:
+// dirty image as prisim_dirty_image enqueues it (dirty_image.h), over all pixels at once; then, per iteration, three launches that
+// never wait for the host:
 //   k_imclean_peak1   reads the residual channel-fastest.  A workgroup is cx channels by 256 / cx pixel lanes and owns a slab of pixels;
 //                     a lane keeps the largest |R| of its pixels (by >, ascending pixels, so the lowest index wins a tie and a NaN never
 //                     wins), the lanes are reduced in LDS under the associative rule "larger |value|, then lower index", and the
 //                     partial (|value|, index) of (slab, channel) is written.  Channels that have ended are not read.
 //   k_imclean_peak2   one workgroup, a thread per image channel: reduces the partials, applies the stop rule, appends the component and
 //                     publishes (q_k, a_k) -- a_k = 0 once the channel has ended -- and the count of active channels.
-//   k_imclean_update  the hot path, the shape of k_img_sum: 256 pixels per workgroup, a tile of 32 channels, 32 baselines per pass, the same
-//                     row loop (img_rows) and summation order.  The staged operand is computed, not loaded: element (r, c) is
+//   k_imclean_update  the hot path: the tile pass of k_img_sum (img_tile_pass of imaging_kernels.h, where it is described), so the same
+//                     summation order.  The staged operand is computed, not loaded: element (r, c) is
 //                     w a_k (cos phi_q, -sin phi_q), phi_q = 2 pi f_k b_r . dd[t][q_k] / c from the channel's true frequency (cycles_phasor),
 //                     four phasors per thread and pass.  The epilogue subtracts acc / W[k] from R in place, only where a_k != 0; a tile
 //                     whose a_k are all 0 returns at once, so an ended channel keeps its bits.  With chan_avg every channel shares (q, a),
@@ -26,7 +26,7 @@
 
 #include "../../include/prisim_imclean.h"
 #include "../csrc_addon/imclean_plan.h"
-#include "imaging_kernels.h"
+#include "dirty_image.h"
 
 namespace {
 
@@ -176,35 +176,23 @@ __global__ void __launch_bounds__(kThreads) k_imclean_update(UpdParams P) {
   for (int k = 0; k < CT; ++k) acc[k] = 0.0;
   const double f0 = P.freqs[k0];
 
-  for (int64_t t = 0; t < P.nt; ++t) {
-    const double4 d = P.dd[t * P.npix + pl];
-    for (int64_t b0 = 0; b0 < P.nbl; b0 += NB) {
-      const int nb = P.nbl - b0 < NB ? (int)(P.nbl - b0) : NB;
-      __syncthreads();                    // the rows of the block before are read (and sh_f, sh_a, sh_q are written, the first time)
-#pragma unroll
-      for (int e = tid; e < NB * CT; e += kThreads) {
-        const int r = e / CT, c = e - r * CT;
-        double2 v = make_double2(0.0, 0.0);
-        const double ak = sh_a[c];
-        if (r < nb && ak != 0.0) {        // ak != 0 only inside the band
-          const int64_t b = b0 + r;
-          const int k = k0 + c;
-          const double w = P.W.w ? P.W.w[t * P.W.st + b * P.W.sb + k * P.W.sk] : 1.0;
-          const double4 dq = P.dd[t * P.npix + sh_q[c]];
-          const double* bl = P.bl + b * 3;
-          const double tau = ((bl[0] * kInvC) * dq.x + (bl[1] * kInvC) * dq.y) + (bl[2] * kInvC) * dq.z;
-          double cq, sq;
-          cycles_phasor(sh_f[c] * tau, cq, sq);
-          const double wa = w * ak;
-          v = make_double2(wa * cq, -(wa * sq));
-        }
-        sh_v[e] = v;
-      }
-      if (tid < nb * 3) sh_b[tid] = P.bl[b0 * 3 + tid] * kInvC;
-      __syncthreads();
-      img_rows<STEPPED, false>(nb, sh_v, sh_b, sh_f, d, f0, P.df, acc);
+  auto stage = [&P](bool live, int64_t t, int64_t b, int c, int k) {
+    double2 v = make_double2(0.0, 0.0);
+    const double ak = sh_a[c];
+    if (live && ak != 0.0) {                      // ak != 0 only inside the band
+      const double w = P.W.at(t, b, k);
+      const double4 dq = P.dd[t * P.npix + sh_q[c]];
+      const double* bl = P.bl + b * 3;
+      const double tau = ((bl[0] * kInvC) * dq.x + (bl[1] * kInvC) * dq.y) + (bl[2] * kInvC) * dq.z;
+      double cq, sq;
+      cycles_phasor(sh_f[c] * tau, cq, sq);
+      const double wa = w * ak;
+      v = make_double2(wa * cq, -(wa * sq));
     }
-  }
+    return v;
+  };
+  for (int64_t t = 0; t < P.nt; ++t)
+    img_tile_pass<STEPPED, false>(t, P.dd[t * P.npix + pl], P.bl, P.nbl, k0, f0, P.df, sh_v, sh_b, sh_f, acc, stage);
   if (!p_valid) return;
   double* out = P.out + pl * P.nchan + k0;
   if (P.avg) {
@@ -274,16 +262,10 @@ int clean_image(prisim_ctx* ctx, const prisim_imclean_args* a, double* out_resid
   if (!out_residual) return fail(ctx, PRISIM_EINVAL, "out_residual is NULL");
   if (!out_comp_pixel || !out_comp_flux || !out_ncomp || !out_status || !out_peak0)
     return fail(ctx, PRISIM_EINVAL, "out_comp_pixel, out_comp_flux, out_ncomp, out_status or out_peak0 is NULL");
-  // what prisim_dirty_image checks of the same arguments, by its own function
-  prisim_imaging_args ia{};
-  ia.npix = a->npix; ia.nbl = a->nbl; ia.nchan = a->nchan; ia.nt = a->nt;
-  ia.unitvec = a->unitvec; ia.rot = a->rot; ia.aberr_beta = a->aberr_beta; ia.pc_dircos = a->pc_dircos;
-  ia.baselines = a->baselines; ia.freqs_hz = a->freqs_hz; ia.cube = a->cube; ia.weights = a->weights;
-  ia.kind = PRISIM_IMAGE_DIRTY; ia.weight_form = a->weight_form; ia.chan_avg = a->chan_avg; ia.route = a->route;
-  ia.budget_bytes = a->budget_bytes;
-  if (int rc = check_args(ctx, &ia, out_residual)) return rc;
+  const ImgView v = imaging_view(*a);
+  if (int rc = check_args(ctx, v)) return rc;
   const int64_t npix = a->npix, nbl = a->nbl, nchan = a->nchan, nt = a->nt, maxiter = a->maxiter;
-  const bool avg = a->chan_avg != 0, resident = !a->cube, restore = out_restored != nullptr;
+  const bool avg = a->chan_avg != 0, restore = out_restored != nullptr;
   const int64_t nc = avg ? 1 : nchan;
   if (!(a->gain > 0.0 && a->gain <= 1.0)) return fail(ctx, PRISIM_EINVAL, "gain must lie in (0, 1]");
   if (!(a->threshold >= 0.0) || !std::isfinite(a->threshold)) return fail(ctx, PRISIM_EINVAL, "threshold must be finite and non-negative");
@@ -295,14 +277,9 @@ int clean_image(prisim_ctx* ctx, const prisim_imclean_args* a, double* out_resid
   for (int64_t k = 0; restore && k < nc; ++k)
     if (!(a->fwhm_rad[k] > 0.0) || !std::isfinite(a->fwhm_rad[k]))
       return fail(ctx, PRISIM_EINVAL, "fwhm_rad[" + std::to_string(k) + "] is not positive and finite");
-  if (resident)
-    if (int rc = check_resident_cube(ctx, nbl, nchan, nt)) return rc;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int lds_max = 0;
-  if (int rc = lds_limit(ctx, lds_max)) return rc;
-  double df = 0.0;
-  const bool uniform = imaging_grid_uniform(a->freqs_hz, nchan, df);
-  const ImcleanPlan pl = imclean_plan(npix, nbl, nchan, nt, avg, maxiter, a->budget_bytes, lds_max, a->route, uniform);
+  ImgSetup su{};
+  if (int rc = imaging_preamble(ctx, v, su)) return rc;
+  const ImcleanPlan pl = imclean_plan(npix, nbl, nchan, nt, avg, maxiter, a->budget_bytes, su.lds_max, a->route, su.uniform);
   if (pl.refusal)
     return fail(ctx, PRISIM_EINVAL, std::string(pl.refusal) + " (the resident buffers take " + std::to_string(pl.total) + " B, the workgroup " +
                                         std::to_string(pl.lds) + " B of LDS)");
@@ -316,6 +293,7 @@ int clean_image(prisim_ctx* ctx, const prisim_imclean_args* a, double* out_resid
   std::vector<int32_t> h_pix;
   std::vector<double> h_flux;
   int64_t h_counts[2] = {1, 0};                         // what the polls read: channels active, iterations in which any was
+  ImgTables T;
 
   Work wk;
   BatchEvents be;
@@ -325,31 +303,11 @@ int clean_image(prisim_ctx* ctx, const prisim_imclean_args* a, double* out_resid
   if (timed)
     if (int rc = be.create(ctx, 2 * batch + 1)) return rc;
 
-  // the tables, outside the budget
-  const std::vector<ImgFrame> frames = snapshot_frames(&ia);
-  double *d_uvec = nullptr, *d_frames = nullptr, *d_bl = nullptr, *d_freqs = nullptr, *d_w = nullptr, *d_fwhm = nullptr;
-  double2* d_cube = nullptr;
+  if (int rc = upload_tables(ctx, wk.dev, v, s0, T)) return rc;
+  const ImgWeights& W = T.W;
+  int64_t upload = T.bytes;
+  double* d_fwhm = nullptr;
   uint8_t* d_window = nullptr;
-  const int64_t ncube = nt * nbl * nchan;
-  int64_t upload = npix * 24 + nt * 128 + nbl * 24 + nchan * 8;
-  DEV_UPLOAD(ctx, wk.dev, d_uvec, a->unitvec, (size_t)npix * 3, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_frames, reinterpret_cast<const double*>(frames.data()), (size_t)nt * 16, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_bl, a->baselines, (size_t)nbl * 3, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_freqs, a->freqs_hz, (size_t)nchan, s0);
-  if (!resident) {
-    DEV_UPLOAD(ctx, wk.dev, d_cube, a->cube, (size_t)ncube * 2, s0);
-    upload += ncube * 16;
-  }
-  ImgWeights W{nullptr, 0, 0, 0};
-  if (a->weight_form == PRISIM_IMAGE_W_BASELINE) {
-    DEV_UPLOAD(ctx, wk.dev, d_w, a->weights, (size_t)nbl, s0);
-    W = ImgWeights{d_w, 0, 1, 0};
-    upload += nbl * 8;
-  } else if (a->weight_form == PRISIM_IMAGE_W_FULL) {
-    DEV_UPLOAD(ctx, wk.dev, d_w, a->weights, (size_t)ncube, s0);
-    W = ImgWeights{d_w, nbl * nchan, nchan, 1};
-    upload += ncube * 8;
-  }
   if (a->window) {
     DEV_UPLOAD(ctx, wk.dev, d_window, a->window, (size_t)npix, s0);
     upload += npix;
@@ -384,28 +342,14 @@ int clean_image(prisim_ctx* ctx, const prisim_imclean_args* a, double* out_resid
   if (timed)
     if (int rc = tev.create(ctx)) return rc;
   // the kernels start behind whatever the context's stream still writes into the resident cube, which is read where it lies
-  if (resident) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (v.resident()) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 
-  // ---- the dirty image of all pixels: the kernels and the order of prisim_dirty_image
+  // ---- the dirty image of all pixels
   if (timed) HIPCHK(ctx, hipEventRecord(tev.e[0], s0));
-  if (int rc = launch(ctx, k_img_wsum, dim3((unsigned)((nchan + kThreads - 1) / kThreads)), 0, s0, W, nt, nbl, (int)nchan, d_wsum)) return rc;
-  hipLaunchKernelGGL(k_img_wtot, dim3(1), dim3(64), 0, s0, (const double*)d_wsum, (int)nchan, d_wtot);
-  HIPCHK(ctx, hipGetLastError());
-  if (int rc = launch(ctx, k_img_dirs, dim3((unsigned)grid_for(ctx, npix * nt)), 0, s0, (const double*)d_uvec,
-                      reinterpret_cast<const ImgFrame*>(d_frames), (int64_t)0, npix, nt, d_dd))
-    return rc;
+  const DirtyImage job = dirty_image_of(v, T, su.df, pl, d_wsum, d_wtot);
+  if (int rc = enqueue_weight_sums(ctx, job, s0)) return rc;
+  if (int rc = enqueue_dirty(ctx, job, Span{0, npix}, d_dd, avg ? d_D : d_R, d_R, s0)) return rc;
   const dim3 grid((unsigned)pl.nblocks, (unsigned)pl.ntiles), pixgrid((unsigned)((npix + kThreads - 1) / kThreads));
-  ImgParams P;
-  P.cube = resident ? (const double2*)ctx->cube.p : d_cube;
-  P.W = W;
-  P.bl = d_bl; P.freqs = d_freqs; P.dd = d_dd; P.wsum = d_wsum;
-  P.df = df;
-  P.nbl = nbl; P.nt = nt; P.count = npix;
-  P.nchan = (int)nchan; P.divide = avg ? 0 : 1;
-  P.out = avg ? d_D : d_R;
-  if (int rc = stepped ? launch_sum<true>(ctx, false, grid, s0, P) : launch_sum<false>(ctx, false, grid, s0, P)) return rc;
-  if (avg)
-    if (int rc = launch(ctx, k_img_avg, pixgrid, 0, s0, (const double*)d_D, npix, (int)nchan, (const double*)d_wtot, d_R)) return rc;
   if (int rc = launch(ctx, k_imclean_init, dim3((unsigned)((nc + kThreads - 1) / kThreads)), 0, s0, S, (const double*)(avg ? d_wtot : d_wsum), (int)nc))
     return rc;
   if (timed) HIPCHK(ctx, hipEventRecord(tev.e[1], s0));
@@ -413,9 +357,9 @@ int clean_image(prisim_ctx* ctx, const prisim_imclean_args* a, double* out_resid
   // ---- the iterations: maxiter + 1 at most end every channel, since an active channel gains a component in each
   UpdParams U;
   U.W = W;
-  U.bl = d_bl; U.freqs = d_freqs; U.dd = d_dd; U.wsum = d_wsum;
+  U.bl = T.bl; U.freqs = T.freqs; U.dd = d_dd; U.wsum = d_wsum;
   U.q = S.q; U.a = S.a;
-  U.df = df;
+  U.df = su.df;
   U.nbl = nbl; U.nt = nt; U.npix = npix;
   U.nchan = (int)nchan; U.avg = avg ? 1 : 0;
   U.out = avg ? d_D : d_R;
@@ -459,7 +403,7 @@ int clean_image(prisim_ctx* ctx, const prisim_imclean_args* a, double* out_resid
   HIPCHK(ctx, hipMemcpyAsync(h_wsum.data(), avg ? d_wtot : d_wsum, (size_t)nc * 8, hipMemcpyDeviceToHost, s0));
   if (restore) {
     if (timed) HIPCHK(ctx, hipEventRecord(tev.e[2], s0));
-    if (int rc = launch(ctx, k_imclean_restore, dim3((unsigned)grid_for(ctx, npix * nc)), 0, s0, d_R, (const double*)d_uvec, S,
+    if (int rc = launch(ctx, k_imclean_restore, dim3((unsigned)grid_for(ctx, npix * nc)), 0, s0, d_R, T.uvec, S,
                         (const double*)d_fwhm, npix, (int)nc, maxiter))
       return rc;
     if (timed) HIPCHK(ctx, hipEventRecord(tev.e[3], s0));
@@ -495,14 +439,13 @@ int clean_image(prisim_ctx* ctx, const prisim_imclean_args* a, double* out_resid
   std::memcpy(out_peak0, h_peak0.data(), (size_t)nc * 8);
   if (out_wsum) std::memcpy(out_wsum, h_wsum.data(), (size_t)nc * 8);
   if (stats) {
-    // the dirty image as prisim_dirty_image counts it in one chunk.  An iteration, counted with every channel active: the update reads
+    // the dirty image as dirty_kernel_bytes counts it.  An iteration, counted with every channel active: the update reads
     // per workgroup and (t, b) the tile's weights (8 B a channel when there are any), the pick's offsets (32 B a channel) and the
     // baseline twice (24 B), per pixel and snapshot its offsets (32 B per tile), and reads and writes the residual (16 B; with
     // chan_avg the scratch rows written and read, and 16 B a pixel); the peak search reads the residual and the window and writes and
     // reads the partials.
     const int64_t wg = pl.nblocks * pl.ntiles;
-    const int64_t dirty_bytes = wg * nt * nbl * (pl.tile * (16 + (W.w ? 8 : 0)) + 24) + npix * nt * (24 + 32 + 32 * pl.ntiles) +
-                                npix * nchan * 8 * (avg ? 2 : 1) + (avg ? npix * 8 : 0) + (W.w ? ncube * 8 : 0) + nchan * 16;
+    const int64_t dirty_bytes = dirty_kernel_bytes(v, pl, W.w != nullptr);
     const int64_t iter_bytes = wg * nt * nbl * (pl.tile * (32 + (W.w ? 8 : 0)) + 48) + npix * nt * 32 * pl.ntiles + npix * nchan * 16 +
                                (avg ? npix * 16 : 0) + npix * nc * 8 + (a->window ? npix : 0) + pl.nslabs * nc * 32;
     const double dirty_ms = elapsed_ms(tev.e[0], tev.e[1]), restore_ms = restore ? elapsed_ms(tev.e[2], tev.e[3]) : 0.0;
@@ -512,7 +455,6 @@ int clean_image(prisim_ctx* ctx, const prisim_imclean_args* a, double* out_resid
     stats->peak_ms = peak_ms;
     stats->update_ms = update_ms;
     stats->restore_ms = restore_ms;
-    stats->terms = npix * nbl * nchan * nt;
     stats->iterations = h_counts[1];
     stats->components = components;
     stats->polls = polls;
@@ -522,12 +464,7 @@ int clean_image(prisim_ctx* ctx, const prisim_imclean_args* a, double* out_resid
     stats->upload_bytes = upload;
     stats->download_bytes = npix * nc * 8 * (restore ? 2 : 1) + nc * 32 + nc * longest * 12 + polls * 16;
     stats->device_bytes = pl.total;
-    stats->route = pl.route;
-    stats->streams = 1;
-    stats->chan_tile = (int32_t)pl.tile;
-    stats->reseed = (int32_t)pl.reseed;
-    stats->lds_bytes = (int32_t)pl.lds;
-    stats->block_pixels = (int32_t)pl.block;
+    plan_stats(stats, v, pl, 1);
   }
   return PRISIM_OK;
 }

@@ -2,27 +2,26 @@
 // mosaic[p][k] = sum_t A_t D_t / sum_t A_t^2 W_t, with D_t[p][k] = sum_b w (Re V cos phi - Im V sin phi) the direct Fourier sum of
 // snapshot t alone (imaging.hip), W_t[k] = sum_b w, and A_t[p][k] the power pattern of the primary beam at the pixel's direction in
 // that snapshot, 0 below the horizon.  It joins two statements this library already has and restates neither: the fused analytic beam
-// (launch_beam_flux of ../csrc/aux_kernels.hip with unit flux, as antpower.hip calls it) and the rows of the direct Fourier sum
-// (img_rows of imaging_kernels.h, as it stands).
+// (launch_beam_flux of ../csrc/aux_kernels.hip with unit flux, as antpower.hip calls it) and the tile pass of the direct Fourier sum
+// (img_tile_pass of imaging_kernels.h, as it stands, where the hot loop is described).
 //
 // Once per call:
-//   k_mos_wsum   W_t[k] = sum_b w[t][b][k] as [nt][nchan], b ascending as in k_img_wsum, and Wtot[k] = sum_t W_t[k], t ascending; one
-//                thread per channel.  k_img_wtot sums Wtot over k for chan_avg.
+//   k_mos_wsum   W_t[k] = sum_b w[t][b][k] as [nt][nchan], b ascending, and Wtot[k] = sum_t W_t[k], t ascending; one thread per
+//                channel.  k_img_wtot sums Wtot over k for chan_avg.
 // Per chunk of pixels (contiguous, a whole number of blocks of 256), on the chunk's stream:
-//   k_mos_dirs   s[t][pixel] = normalise(R_t (u + beta_t)) as (l, m, n, 0), the rows BeamParams.dirs reads, and dd = s - s0[t]: the
-//                operations of k_img_dirs and k_ap_dirs, one after the other.
+//   k_img_dirs   with both outputs: s[t][pixel] = normalise(R_t (u + beta_t)) as (l, m, n, 0), the rows BeamParams.dirs reads, and
+//                dd = s - s0[t].
 //   then for t = 0 .. nt - 1, in this order:
 //     launch_beam_flux with unit flux (flux_ref = 1, spindex = 0: pb exp2(0) = pb exactly) on the chunk's directions of snapshot t
 //                into pb_tile[count][nchan], the one tile of the stream: 8 nchan bytes a pixel, not 8 nt nchan.
-//     k_mos_sum  the hot path, one launch per snapshot.  The workgroup of k_img_sum: 256 pixels (one per thread) and a tile of 32
-//                channels, 32 baselines at a time staged in LDS as (w Re V, w Im V) with b / c, img_rows<STEPPED, false> on them, 32
-//                fp64 accumulators per thread.  The epilogue reads the thread's 32 beam values, puts 0 in their place where the
-//                direction is below the horizon, and writes N = fma(A, acc, N) and Q = fma(A A, W_t, Q); snapshot 0 starts from 0 and
-//                reads nothing.  The launch per snapshot is what fixes the order in t, keeps the register budget of k_img_sum (the
-//                beam values are read when the accumulators are done, one at a time) and lets one beam tile serve every snapshot; a
-//                t loop inside one launch would need the beam of all snapshots resident (8 nt nchan bytes a pixel) or a second set of
-//                32 accumulators for N beside D_t (64 more VGPRs: half the occupancy).  Its price is N and Q read and written once
-//                per snapshot, 32 B per (pixel, channel, snapshot) against the nbl rows the snapshot stages.
+//     k_mos_sum  the hot path, one launch per snapshot: the tile pass of that snapshot on (w Re V, w Im V), the operand of the dirty
+//                image.  The epilogue reads the thread's 32 beam values, puts 0 in their place where the direction is below the
+//                horizon, and writes N = fma(A, acc, N) and Q = fma(A A, W_t, Q); snapshot 0 starts from 0 and reads nothing.
+//                The launch per snapshot is what fixes the order in t, keeps the register budget of k_img_sum (the beam values are
+//                read when the accumulators are done, one at a time) and lets one beam tile serve every snapshot; a t loop inside one
+//                launch would need the beam of all snapshots resident (8 nt nchan bytes a pixel) or a second set of 32 accumulators
+//                for N beside D_t (64 more VGPRs: half the occupancy).  Its price is N and Q read and written once per snapshot,
+//                32 B per (pixel, channel, snapshot) against the nbl rows the snapshot stages.
 //   k_mos_finish the division, the mask Q >= pbmin^2 Wtot (else NaN) and pb_eff = sqrt(Q / Wtot) per (pixel, channel); or, with
 //                chan_avg, k_mos_finish_band: the sums of N and Q over k ascending per pixel, then the same three.
 // No atomics, and neither the b sum nor the t sum is split: the bits do not depend on the chunks or the streams.  Built with
@@ -30,7 +29,6 @@
 // copied to the caller's arrays when every chunk is in, so that a failed call writes nothing.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -40,34 +38,11 @@
 #include "../../include/prisim_mosaic.h"
 #include "../csrc_addon/beam_setup.h"
 #include "../csrc_addon/mosaic_plan.h"
-// (img_rows, the frames, the weights and the argument checks are taken from here; the kernels of prisim_dirty_image itself are not launched)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"
 #include "imaging_kernels.h"
-#pragma clang diagnostic pop
 
 namespace {
 
-// grid-stride over nt * count: s4 and dd [nt][count] of pixels [p0, p0 + count)
-__global__ void __launch_bounds__(kThreads) k_mos_dirs(const double* __restrict__ uvec, const ImgFrame* __restrict__ frames, int64_t p0,
-                                                       int64_t count, int64_t nt, double4* __restrict__ s4, double4* __restrict__ dd) {
-  const int64_t total = nt * count;
-  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
-    const int64_t t = e / count, pl = e - t * count;
-    const ImgFrame& fr = frames[t];
-    const double* u = uvec + (p0 + pl) * 3;
-    const double t0 = u[0] + fr.beta[0], t1 = u[1] + fr.beta[1], t2 = u[2] + fr.beta[2];
-    const double v0 = (fr.rot[0] * t0 + fr.rot[1] * t1) + fr.rot[2] * t2;
-    const double v1 = (fr.rot[3] * t0 + fr.rot[4] * t1) + fr.rot[5] * t2;
-    const double v2 = (fr.rot[6] * t0 + fr.rot[7] * t1) + fr.rot[8] * t2;
-    const double nrm = sqrt((v0 * v0 + v1 * v1) + v2 * v2);
-    const double l = v0 / nrm, m = v1 / nrm, n = v2 / nrm;
-    s4[e] = make_double4(l, m, n, 0.0);
-    dd[e] = make_double4(l - fr.pc[0], m - fr.pc[1], n - fr.pc[2], 0.0);
-  }
-}
-
-// grid: x over the channels.  wt [nt][nchan], wtot [nchan]
+// grid: x over the channels.  wt [nt][nchan], wtot [nchan].  Why this is not k_img_wsum: see there (dirty_image.h)
 __global__ void __launch_bounds__(kThreads) k_mos_wsum(ImgWeights W, int64_t nt, int64_t nbl, int nchan, double* __restrict__ wt,
                                                        double* __restrict__ wtot) {
   const int k = (int)blockIdx.x * kThreads + threadIdx.x;
@@ -116,26 +91,12 @@ __global__ void __launch_bounds__(kThreads) k_mos_sum(MosParams P) {
 #pragma unroll
   for (int k = 0; k < CT; ++k) acc[k] = 0.0;
   const double f0 = P.freqs[k0];          // k0 < nchan: the grid has ceil(nchan / CT) tiles
-  const double4 d = P.dd[pl];
-  for (int64_t b0 = 0; b0 < P.nbl; b0 += NB) {
-    const int nb = P.nbl - b0 < NB ? (int)(P.nbl - b0) : NB;
-    __syncthreads();                      // the rows of the block before are read (and sh_f is written, the first time)
-#pragma unroll
-    for (int e = tid; e < NB * CT; e += kThreads) {
-      const int r = e / CT, c = e - r * CT, k = k0 + c;
-      double2 v = make_double2(0.0, 0.0);
-      if (r < nb && k < P.nchan) {
-        const int64_t b = b0 + r;
-        const double w = P.W.w ? P.W.w[t * P.W.st + b * P.W.sb + k * P.W.sk] : 1.0;
-        const double2 x = P.cube[(t * P.nbl + b) * P.nchan + k];
-        v = make_double2(w * x.x, w * x.y);
-      }
-      sh_v[e] = v;
-    }
-    if (tid < nb * 3) sh_b[tid] = P.bl[b0 * 3 + tid] * kInvC;
-    __syncthreads();
-    img_rows<STEPPED, false>(nb, sh_v, sh_b, sh_f, d, f0, P.df, acc);
-  }
+  img_tile_pass<STEPPED, false>(t, P.dd[pl], P.bl, P.nbl, k0, f0, P.df, sh_v, sh_b, sh_f, acc, [&P](bool live, int64_t t, int64_t b, int, int k) {
+    if (!live || k >= P.nchan) return make_double2(0.0, 0.0);
+    const double w = P.W.at(t, b, k);
+    const double2 x = P.cube[(t * P.nbl + b) * P.nchan + k];
+    return make_double2(w * x.x, w * x.y);
+  });
   if (!p_valid) return;
   const bool up = P.s4[pl].z >= 0.0;
   const int64_t at = pl * P.nchan + k0;
@@ -182,32 +143,18 @@ int mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosai
   const WallTime wall0 = wall_now();
   if (!a) return fail(ctx, PRISIM_EINVAL, "the argument struct is NULL");
   if (!out_mosaic) return fail(ctx, PRISIM_EINVAL, "out_mosaic is NULL");
-  // the fields shared with prisim_dirty_image, under its own checks
-  prisim_imaging_args ia{};
-  ia.npix = a->npix; ia.nbl = a->nbl; ia.nchan = a->nchan; ia.nt = a->nt;
-  ia.unitvec = a->unitvec; ia.rot = a->rot; ia.aberr_beta = a->aberr_beta; ia.pc_dircos = a->pc_dircos;
-  ia.baselines = a->baselines; ia.freqs_hz = a->freqs_hz; ia.cube = a->cube; ia.weights = a->weights;
-  ia.kind = PRISIM_IMAGE_DIRTY; ia.weight_form = a->weight_form; ia.chan_avg = a->chan_avg; ia.route = a->route;
-  ia.budget_bytes = a->budget_bytes;
-  if (int rc = check_args(ctx, &ia, out_mosaic)) return rc;
+  const ImgView v = imaging_view(*a);
+  if (int rc = check_args(ctx, v)) return rc;
   if (!(a->pbmin >= 0.0 && a->pbmin < 1.0)) return fail(ctx, PRISIM_EINVAL, "pbmin must lie in [0, 1)");
   if (int rc = check_beams(ctx, a->beam_kind, a->diameter_m, a->beam_pc_dircos, a->ext, a->n_ext, a->nt, "nt")) return rc;
   for (int64_t i = 0; a->beam_pc_snap && i < a->nt * 3; ++i)
     if (!std::isfinite(a->beam_pc_snap[i])) return fail(ctx, PRISIM_EINVAL, "beam_pc_snap of snapshot " + std::to_string(i / 3) + " is not finite");
   const int64_t npix = a->npix, nbl = a->nbl, nchan = a->nchan, nt = a->nt;
-  const bool avg = a->chan_avg != 0, resident = !a->cube;
-  if (resident) {
-    if (int rc = check_resident_cube(ctx, nbl, nchan, nt)) return rc;
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int lds_max = 0;
-  if (int rc = lds_limit(ctx, lds_max)) return rc;
-  double df = 0.0;
-  const bool uniform = imaging_grid_uniform(a->freqs_hz, nchan, df);
-  const MosaicPlan pl = mosaic_plan(npix, nbl, nchan, nt, a->weight_form, avg, a->budget_bytes, lds_max, a->route, uniform, kMaxStreams);
-  if (pl.refusal)
-    return fail(ctx, PRISIM_EINVAL, std::string(pl.refusal) + " (one block of " + std::to_string(pl.block) + " pixels takes " +
-                                        std::to_string(pl.block * pl.pixel_bytes) + " B, the workgroup " + std::to_string(pl.lds) + " B of LDS)");
+  const bool avg = a->chan_avg != 0;
+  ImgSetup su{};
+  if (int rc = imaging_preamble(ctx, v, su)) return rc;
+  const MosaicPlan pl = mosaic_plan(npix, nbl, nchan, nt, a->weight_form, avg, a->budget_bytes, su.lds_max, a->route, su.uniform, kMaxStreams);
+  if (pl.refusal) return fail(ctx, PRISIM_EINVAL, plan_refusal(pl));
   const Chunks& ch = pl.chunks;
   const int nstreams = ch.nstreams;
   const bool stepped = pl.route == kImagingStepped;
@@ -218,38 +165,17 @@ int mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosai
   std::vector<double> h_mos((size_t)(npix * per_out)), h_wsum((size_t)nchan);
   std::vector<double> h_eff(out_pb_eff ? (size_t)(npix * per_out) : 0), h_num(out_num ? (size_t)(npix * nchan) : 0),
       h_den(out_den ? (size_t)(npix * nchan) : 0);
+  ImgTables T;
 
   Work wk;
   Streams& st = wk.st;
   if (int rc = st.create(ctx, nstreams, true)) return rc;
   hipStream_t s0 = st.s[0];
 
-  // the tables go up once on stream 0, outside the budget
-  const std::vector<ImgFrame> frames = snapshot_frames(&ia);
-  double *d_uvec = nullptr, *d_frames = nullptr, *d_bl = nullptr, *d_freqs = nullptr, *d_w = nullptr, *d_wt = nullptr, *d_wtot = nullptr,
-         *d_wband = nullptr, *d_ones = nullptr, *d_zeros = nullptr;
-  double2* d_cube = nullptr;
-  int64_t upload = 0;
-  const int64_t ncube = nt * nbl * nchan;
-  DEV_UPLOAD(ctx, wk.dev, d_uvec, a->unitvec, (size_t)npix * 3, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_frames, reinterpret_cast<const double*>(frames.data()), (size_t)nt * 16, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_bl, a->baselines, (size_t)nbl * 3, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_freqs, a->freqs_hz, (size_t)nchan, s0);
-  upload += npix * 24 + nt * 128 + nbl * 24 + nchan * 8;
-  if (a->cube) {
-    DEV_UPLOAD(ctx, wk.dev, d_cube, a->cube, (size_t)ncube * 2, s0);
-    upload += ncube * 16;
-  }
-  ImgWeights W{nullptr, 0, 0, 0};
-  if (a->weight_form == PRISIM_IMAGE_W_BASELINE) {
-    DEV_UPLOAD(ctx, wk.dev, d_w, a->weights, (size_t)nbl, s0);
-    W = ImgWeights{d_w, 0, 1, 0};
-    upload += nbl * 8;
-  } else if (a->weight_form == PRISIM_IMAGE_W_FULL) {
-    DEV_UPLOAD(ctx, wk.dev, d_w, a->weights, (size_t)ncube, s0);
-    W = ImgWeights{d_w, nbl * nchan, nchan, 1};
-    upload += ncube * 8;
-  }
+  if (int rc = upload_tables(ctx, wk.dev, v, s0, T)) return rc;
+  const ImgWeights& W = T.W;
+  int64_t upload = T.bytes;
+  double *d_wt = nullptr, *d_wtot = nullptr, *d_wband = nullptr, *d_ones = nullptr, *d_zeros = nullptr;
   // the unit flux of the beam statement: pb * 1 * exp2(0 * lg) = pb
   const std::vector<double> ones((size_t)ch.size, 1.0);
   DEV_UPLOAD(ctx, wk.dev, d_ones, ones, s0);
@@ -281,19 +207,19 @@ int mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosai
     DEV_ALLOC(ctx, wk.dev, d_eff[i], ch.size * per_out * 8);
   }
   // the kernels start behind whatever the context's stream still writes into the resident cube
-  if (resident) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (v.resident()) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(s0));              // stream 1 starts behind the uploads and the weight sums; the tables are caller memory
 
   MosParams base{};
-  base.cube = resident ? (const double2*)ctx->cube.p : d_cube;
+  base.cube = T.cube;
   base.W = W;
-  base.bl = d_bl; base.freqs = d_freqs;
-  base.df = df;
+  base.bl = T.bl; base.freqs = T.freqs;
+  base.df = su.df;
   base.nbl = nbl; base.nchan = (int)nchan;
 
   auto kernels = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
-    if (int rc = launch(ctx, k_mos_dirs, dim3((unsigned)grid_for(ctx, sp.count * nt)), 0, sc, (const double*)d_uvec,
-                        reinterpret_cast<const ImgFrame*>(d_frames), sp.first, sp.count, nt, d_s4[i], d_dd[i]))
+    if (int rc = launch(ctx, k_img_dirs, dim3((unsigned)grid_for(ctx, sp.count * nt)), 0, sc, T.uvec, T.frames, sp.first, sp.count, nt, d_s4[i],
+                        d_dd[i]))
       return rc;
     const dim3 grid((unsigned)((sp.count + pl.block - 1) / pl.block), (unsigned)pl.ntiles);
     for (int64_t t = 0; t < nt; ++t) {
@@ -304,7 +230,7 @@ int mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosai
       bp.dirs = (const double*)(d_s4[i] + t * sp.count);
       bp.flux_ref = d_ones;
       bp.spindex = d_zeros;
-      bp.freqs = d_freqs;
+      bp.freqs = T.freqs;
       bp.ref_freq = 1.0;
       bp.flag = d_flag;
       bp.nsrc = sp.count;
@@ -345,28 +271,22 @@ int mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosai
     // per snapshot.  k_mos_sum, per workgroup (block of pixels, channel tile) and b: the tile's row of the cube (16 B a channel) and
     // of the weights (8 B a channel when there are any), and the baseline (24 B); per pixel and tile its offset and its direction
     // (32 B each); per (pixel, channel) the beam value read (8 B), N and Q written (16 B) and, past snapshot 0, read (16 B).  The
-    // beam: 32 B of direction read per pixel, 8 B written per (pixel, channel).  Once: k_mos_dirs, 24 B read and 64 B written per
+    // beam: 32 B of direction read per pixel, 8 B written per (pixel, channel).  Once: k_img_dirs, 24 B read and 64 B written per
     // (pixel, snapshot); the finish, N and Q read and two outputs written, read once more per channel with chan_avg; k_mos_wsum, the
     // weights once.
     const int64_t wg = pl.nblocks * pl.ntiles;
     const int64_t row = pl.tile * (16 + (W.w ? 8 : 0)) + 24;
     stats->wall_ms = wall_ms_since(wall0);
     stats->kernel_ms = st.kernel_ms;
-    stats->terms = npix * nbl * nchan * nt;
     stats->beam_values = npix * nchan * nt;
     stats->chunks = ch.count;
     stats->chunk_pixels = ch.size;
     stats->pixel_bytes = pl.pixel_bytes;
     stats->kernel_bytes = wg * nt * nbl * row + npix * nt * (24 + 64 + 32 + 64 * pl.ntiles) + npix * nchan * (nt * (8 + 8 + 16) + (nt - 1) * 16) +
-                          npix * nchan * 16 + npix * per_out * 16 + (W.w ? ncube * 8 : 0) + (nt + 2) * nchan * 8;
+                          npix * nchan * 16 + npix * per_out * 16 + (W.w ? nt * nbl * nchan * 8 : 0) + (nt + 2) * nchan * 8;
     stats->upload_bytes = upload;
     stats->download_bytes = (npix * per_out * (out_pb_eff ? 2 : 1) + npix * nchan * ((out_num ? 1 : 0) + (out_den ? 1 : 0)) + nchan) * 8;
-    stats->route = pl.route;
-    stats->streams = nstreams;
-    stats->chan_tile = (int32_t)pl.tile;
-    stats->reseed = (int32_t)pl.reseed;
-    stats->lds_bytes = (int32_t)pl.lds;
-    stats->block_pixels = (int32_t)pl.block;
+    plan_stats(stats, v, pl, nstreams);
   }
   return PRISIM_OK;
 }

@@ -150,6 +150,59 @@ def test_g1_resident_cube_and_refusals(ctx):
     assert NP.array_equal(out, call(ctx, c, weights=c['w_full'])[0])
 
 
+def test_g1_the_three_entries_refuse_a_shared_argument_alike(ctx):
+    """prisim_dirty_image, prisim_mosaic_image and prisim_clean_image check the arguments they have in common by one function: a faulty
+    one gets the same code and the same sentence from each, on the host and before any launch, and no output is written."""
+    c = IC.case(37, K + 1, 65, 3)
+    p, lib, h, byref = _abi._ptr, ctx._lib, ctx._h, _abi.C.byref
+    npix, nchan, maxiter = 65, K + 1, 5
+    rot = NP.ascontiguousarray(c['rot'].reshape(-1, 9))
+    image = [NP.full((npix, nchan), -7.0) for _ in range(6)] + [NP.full(nchan, -7.0) for _ in range(4)]
+    lists = [NP.full((nchan, maxiter), -7, dtype=NP.int32), NP.full((nchan, maxiter), -7.0), NP.full(nchan, -7, dtype=NP.int32),
+             NP.full(nchan, -7, dtype=NP.int32)]
+    shared = dict(npix=npix, nbl=37, nchan=nchan, nt=3, unitvec=c['unitvec'], rot=rot, aberr_beta=c['beta'], pc_dircos=c['pc'],
+                  baselines=c['baselines'], freqs_hz=c['freqs'], cube=c['cube'], weights=c['w_full'], weight_form=2, chan_avg=0, route=-1,
+                  budget_bytes=0)
+    own = {'prisim_dirty_image': (ctx.PrisimImagingArgs, dict(kind=0)),
+           'prisim_mosaic_image': (ctx.PrisimMosaicArgs, dict(beam_kind=_abi.PRISIM_BEAM_AIRY, diameter_m=2.0, pbmin=0.1)),
+           'prisim_clean_image': (ctx.PrisimImcleanArgs, dict(gain=0.3, threshold=0.1, maxiter=maxiter, threshold_relative=1, poll_every=0))}
+
+    def entry(name, **kw):
+        a, keep = own[name][0](), []
+        for field, val in dict(shared, **own[name][1], **kw).items():
+            if isinstance(val, NP.ndarray):
+                val = NP.ascontiguousarray(val)
+                keep.append(val)
+                val = p(val)
+            setattr(a, field, val)
+        if name == 'prisim_dirty_image':
+            rc = lib.prisim_dirty_image(h, byref(a), p(image[0]), p(image[6]), None)
+        elif name == 'prisim_mosaic_image':
+            a.beam_pc_dircos[:] = [0.0, 0.0, 1.0]
+            rc = lib.prisim_mosaic_image(h, byref(a), p(image[1]), p(image[2]), p(image[3]), p(image[4]), p(image[7]), None)
+        else:
+            rc = lib.prisim_clean_image(h, byref(a), p(image[5]), None, p(lists[0]), p(lists[1]), p(lists[2]), p(lists[3]), p(image[8]),
+                                        p(image[9]), None)
+        return rc, lib.prisim_hip_last_error(h).decode()
+
+    def changed(name, index, value):
+        x = NP.array(rot if name == 'rot' else c[name], dtype=NP.float64)
+        x[index] = value
+        return x
+
+    faults = [({'unitvec': changed('unitvec', (3, 0), 1.5)}, 'unitvec[3]'), ({'rot': changed('rot', (1, 4), 0.5)}, 'rot of snapshot 1'),
+              ({'aberr_beta': changed('beta', (2, 1), 0.02)}, 'aberr_beta of snapshot 2'),
+              ({'weights': changed('w_full', (1, 2, 3), -1.0)}, 'finite and non-negative'), ({'nchan': 0}, '>= 1'),
+              ({'route': 2}, 'unknown route')]
+    for kw, msg in faults:
+        answers = {name: entry(name, **kw) for name in own}
+        assert len(set(answers.values())) == 1, (list(kw), answers)
+        rc, err = answers['prisim_dirty_image']
+        assert rc == _abi.PRISIM_EINVAL and msg in err, (list(kw), rc, err)
+        assert all(NP.all(o == -7) for o in image + lists), list(kw)  # nothing is written unless the call succeeds
+    assert all(entry(name)[0] == _abi.PRISIM_OK for name in own)      # and the unchanged arguments are taken by all three
+
+
 def test_g2_a_channel_without_weight_is_nan_and_nothing_else_is(ctx):
     c = IC.case(37, 70, 65, 3)
     w = c['w_full'].copy()

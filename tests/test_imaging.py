@@ -40,8 +40,13 @@ def test_export_is_in_the_library_and_outside_the_core_abi():
     assert set(_abi._stats_dict(_abi.Context.PrisimImagingStats())) == {
         'wall_ms', 'kernel_ms', 'terms', 'chunks', 'chunk_pixels', 'kernel_bytes', 'upload_bytes', 'download_bytes', 'route', 'streams',
         'chan_tile', 'reseed', 'lds_bytes', 'block_pixels'}
-    src = open(os.path.join(ROOT, 'prisim_amd', 'csrc_imaging', 'imaging.hip')).read()
-    assert 'atomic' not in src.replace('no atomics', '')
+    folder = os.path.join(ROOT, 'prisim_amd', 'csrc_imaging')
+    srcs = {name: open(os.path.join(folder, name)).read() for name in os.listdir(folder)}
+    assert all('atomic' not in txt.lower().replace('no atomics', '') for txt in srcs.values())
+    # the hot loop of the three entries is stated once: the two barriers of the staging loop are in one file, which the others call
+    assert [name for name, txt in srcs.items() if '__syncthreads();' in txt and 'sh_b[tid] =' in txt] == ['imaging_kernels.h']
+    assert srcs['imaging_kernels.h'].count('__syncthreads();') == 2 and srcs['dirty_image.h'].count('img_tile_pass<STEPPED, PSF>(') == 1
+    assert '#include "dirty_image.h"' in srcs['imaging.hip'] and 'enqueue_dirty(' in srcs['imaging.hip'] and '<<<' not in srcs['imaging.hip']
     header = open(os.path.join(ROOT, 'include', 'prisim_imaging.h')).read()
     for name in ('prisim_hip.h', 'prisim_hip_last_error', 'prisim_hip_set_array'):
         header = header.replace(name, '')

@@ -40,9 +40,11 @@ def test_export_is_in_the_library_and_outside_the_core_abi():
         'lds_bytes', 'block_pixels'}
     assert (_abi.PRISIM_IMCLEAN_THRESHOLD, _abi.PRISIM_IMCLEAN_MAXITER, _abi.PRISIM_IMCLEAN_DEAD) == (CK.THRESHOLD, CK.MAXITER, CK.DEAD) == (1, 2, 4)
     src = open(os.path.join(ROOT, 'prisim_amd', 'csrc_imaging', 'imclean.hip')).read()
-    assert 'atomic' not in src.replace('No atomics', '') and '#include "imaging_kernels.h"' in src
-    # the dirty image of both entries is one set of kernels
-    assert '#include "imaging_kernels.h"' in open(os.path.join(ROOT, 'prisim_amd', 'csrc_imaging', 'imaging.hip')).read()
+    assert 'atomic' not in src.replace('No atomics', '') and '#include "dirty_image.h"' in src
+    # the dirty image of both entries is one set of kernels, enqueued by one function; the update's hot loop is that of the dirty image
+    assert '#include "dirty_image.h"' in open(os.path.join(ROOT, 'prisim_amd', 'csrc_imaging', 'imaging.hip')).read()
+    assert 'enqueue_dirty(' in src and 'k_img_sum<' not in src and 'prisim_imaging_args ia' not in src
+    assert 'img_tile_pass<STEPPED, false>(' in src and 'img_rows' not in src and 'sh_b[tid] =' not in src
 
 
 def test_plan_header_under_the_sanitizers(tmp_path):

@@ -44,7 +44,9 @@ def test_export_is_in_the_library_and_outside_the_core_abi():
         'download_bytes', 'route', 'streams', 'chan_tile', 'reseed', 'lds_bytes', 'block_pixels'}
     src = open(os.path.join(ROOT, 'prisim_amd', 'csrc_imaging', 'mosaic.hip')).read()
     assert 'atomic' not in src.replace('No atomics', '') and 'fma(' in src
-    assert 'img_rows<STEPPED, false>' in src and 'launch_beam_flux(' in src and 'beam_flux_body' not in src      # called, not restated
+    assert 'img_tile_pass<STEPPED, false>(' in src and 'launch_beam_flux(' in src and 'beam_flux_body' not in src      # called, not restated
+    assert 'img_rows' not in src and 'sh_b[tid] =' not in src and 'prisim_imaging_args ia' not in src and 'k_mos_dirs' not in src
+    assert '#include "imaging_kernels.h"' in src and 'dirty_image.h"' not in src and 'Wunused' not in src      # it compiles what it launches
     ant = open(os.path.join(ROOT, 'prisim_amd', 'csrc_antpower', 'antpower.hip')).read()
     assert 'beam_setup.h' in ant and 'beam_setup.h' in src and 'void fill_beam' not in ant + src       # one statement of the beam's set-up
     header = open(os.path.join(ROOT, 'include', 'prisim_mosaic.h')).read()
