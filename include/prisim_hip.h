@@ -339,8 +339,12 @@ int prisim_hip_phase_rotate(prisim_ctx* ctx, int64_t nt, const double* diff_dirc
 /* ---- thermal noise (interferometry.py:6661-6693) ----------------------------------- */
 
 /* noise[t][b][f] = rms[t][b][f] / sqrt(2) * (n1 + i n2), n1, n2 ~ N(0,1) (interferometry.py:6692).  The normals come from
- * a counter-based generator (Philox-4x32-10 keyed by `seed`, counter = (t, bl_offset + b, f)), so a baseline-sharded run
- * draws exactly the numbers of the unsharded run.  rms: host [nt][nbl][nchan] float64 (vis_rms_freq, :6685-6689);
+ * a counter-based generator, so a baseline-sharded run draws exactly the numbers of the unsharded run, and a stored seed
+ * has a meaning: with g = bl_offset + b the GLOBAL baseline, r[0..3] = Philox-4x32-10 (Salmon et al. 2011) of the counter
+ * words (f, g mod 2^32, t, g div 2^32) under the key words (seed mod 2^32, seed div 2^32);
+ * u1 = ((r0 << 20 | r1 >> 12) + 1) / 2^52 in (0, 1], u2 = (r2 << 20 | r3 >> 12) / 2^52 in [0, 1);
+ * noise = rms * 0.70710678118654752440 * sqrt(-2 ln u1) * (cospi(2 u2) + i sinpi(2 u2)), in fp64.  tests/test_gpu_noise.py
+ * holds this to the published Philox known-answer vectors.  rms: host [nt][nbl][nchan] float64 (vis_rms_freq, :6685-6689);
  * out: host complex128 [nt][nbl][nchan]. */
 int prisim_hip_noise(prisim_ctx* ctx, int64_t nt, const double* rms, uint64_t seed, int64_t bl_offset, double* out);
 /* The same for a shard whose baselines are not one contiguous range of the whole array (shards dealt round-robin in groups,
