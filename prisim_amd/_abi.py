@@ -353,6 +353,24 @@ class _PrisimMosaicArgs(C.Structure):
                 ('n_ext', C.c_int64), ('pbmin', C.c_double), ('budget_bytes', C.c_int64)]
 
 
+class _PrisimMoscleanStats(C.Structure):
+    """prisim_mosclean_stats of include/prisim_mosclean.h, public as Context.PrisimMoscleanStats (see _PrisimCpxpsStats)."""
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('mosaic_ms', C.c_double), ('peak_ms', C.c_double),
+                ('update_ms', C.c_double), ('restore_ms', C.c_double), ('terms', C.c_int64), ('beam_values', C.c_int64),
+                ('iterations', C.c_int64), ('components', C.c_int64), ('polls', C.c_int64), ('chunks', C.c_int64),
+                ('chunk_pixels', C.c_int64), ('kernel_bytes', C.c_int64), ('upload_bytes', C.c_int64), ('download_bytes', C.c_int64),
+                ('device_bytes', C.c_int64), ('route', C.c_int32), ('streams', C.c_int32), ('chan_tile', C.c_int32), ('reseed', C.c_int32),
+                ('lds_bytes', C.c_int32), ('block_pixels', C.c_int32)]
+
+
+class _PrisimMoscleanArgs(C.Structure):
+    """prisim_mosclean_args of include/prisim_mosclean.h, public as Context.PrisimMoscleanArgs: the fields of prisim_mosaic_args in their
+    order, then those of the CLEAN."""
+    _fields_ = _PrisimMosaicArgs._fields_ + [('gain', C.c_double), ('maxiter', C.c_int64), ('threshold', C.c_double),
+                                             ('threshold_relative', C.c_int32), ('window', C.c_void_p), ('fwhm_rad', C.c_void_p),
+                                             ('poll_every', C.c_int32)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -454,6 +472,40 @@ def _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube, weigh
     return npix, nbl, nchan, nt, x is None, (uv, rt, pc, bl, fq, ab, x, w)
 
 
+def _mosaic_beam_fields(a, nt, beam_kind, diameter_m, beam_pc_dircos, ext, pbmin):
+    """The beam of mosaic_image and clean_mosaic put into the fields their argument structs have alike: beam_pc_dircos (3,) or (nt, 3);
+    ext None, a dict or one dict per snapshot; pbmin.  Returns what the struct points into, to be held until the call is over."""
+    bpc = NP.ascontiguousarray(beam_pc_dircos, dtype=NP.float64)
+    if bpc.shape not in ((3,), (nt, 3)):
+        raise ValueError('beam_pc_dircos must be (3,) or one row per snapshot (nt, 3)')
+    exts, xs, keep_ext = _beam_ext_array(ext)
+    a.beam_kind, a.diameter_m = int(beam_kind), float(diameter_m)
+    a.beam_pc_dircos[:] = bpc.reshape(-1, 3)[0].tolist()
+    a.beam_pc_snap = _ptr(bpc) if bpc.ndim == 2 else None
+    a.ext = C.cast(xs, C.c_void_p) if exts else None
+    a.n_ext = len(exts)
+    a.pbmin = float(pbmin)
+    return bpc, xs, keep_ext
+
+
+def _clean_fields(a, npix, nc, gain, maxiter, threshold, threshold_relative, window, fwhm_rad, poll_every):
+    """The CLEAN arguments of clean_image and clean_mosaic put into the fields their argument structs have alike.  Returns (maxiter,
+    the window as uint8 or None, fwhm_rad (nc,) or None): the arrays the struct points into."""
+    win = None
+    if window is not None:
+        win = NP.ascontiguousarray(NP.asarray(window) != 0, dtype=NP.uint8)
+        if win.shape != (npix,):
+            raise ValueError('window must be (npix,)')
+    fw = None
+    if fwhm_rad is not None:
+        fw = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(fwhm_rad, dtype=NP.float64), (nc,)))
+    maxiter = int(maxiter)
+    a.window, a.fwhm_rad = _ptr(win), _ptr(fw)
+    a.gain, a.threshold, a.maxiter = float(gain), float(threshold), maxiter
+    a.threshold_relative, a.poll_every = 1 if threshold_relative else 0, int(poll_every or 0)
+    return maxiter, win, fw
+
+
 def _want_bits(want, bits):
     """The OR of bits[name] over the names of want; KeyError on an unknown name."""
     flag = 0
@@ -493,6 +545,7 @@ STRUCTS = {
     'prisim_imaging_stats': _PrisimImagingStats, 'prisim_imaging_args': _PrisimImagingArgs, 'prisim_gains_stats': PrisimGainsStats,
     'prisim_imclean_stats': _PrisimImcleanStats, 'prisim_imclean_args': _PrisimImcleanArgs,
     'prisim_mosaic_stats': _PrisimMosaicStats, 'prisim_mosaic_args': _PrisimMosaicArgs,
+    'prisim_mosclean_stats': _PrisimMoscleanStats, 'prisim_mosclean_args': _PrisimMoscleanArgs,
 }
 
 # The C ABI, declared once: per header of include/, its functions in the header's order, each as
@@ -631,6 +684,10 @@ _PROTOTYPES = {
         int prisim_mosaic_image(p ctx, *prisim_mosaic_args a, p out_mosaic, p out_pb_eff, p out_num, p out_den, p out_wsum,
             *prisim_mosaic_stats stats);
     ''',
+    'prisim_mosclean.h': '''
+        int prisim_clean_mosaic(p ctx, *prisim_mosclean_args a, p out_residual, p out_restored, p out_residual_flat, p out_pb_eff, p out_num,
+            p out_den, p out_wsum, p out_comp_pixel, p out_comp_flux, p out_ncomp, p out_status, p out_peak0, *prisim_mosclean_stats stats);
+    ''',
     'prisim_gains.h': '''
         int prisim_gains_eval_spline(p ctx, q nrows, i kx, i ky, p nx, p ny, p kx_off, p ky_off, p c_off, q nknots, p knots, q ncoefs, p coefs,
             q nt, p times, q nchan, p freqs, *p out, *prisim_gains_stats stats);
@@ -668,9 +725,9 @@ def _parse_prototypes(table):
 FUNCTIONS, HEADER_EXPORTS = _parse_prototypes(_PROTOTYPES)
 # the functions of each header (tests and tools import these names)
 (EXPORTS, CLEAN_EXPORTS, SUBBAND_EXPORTS, RUNS_EXPORTS, CLOSURE_EXPORTS, CPDELAY_EXPORTS, CPBINS_EXPORTS, CPDIFF_EXPORTS, CPFT_EXPORTS,
- CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMCLEAN_EXPORTS, MOSAIC_EXPORTS, GAINS_EXPORTS) = (
+ CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMCLEAN_EXPORTS, MOSAIC_EXPORTS, MOSCLEAN_EXPORTS, GAINS_EXPORTS) = (
     HEADER_EXPORTS['prisim_%s.h' % h] for h in ('hip', 'clean', 'subband', 'runs', 'closure', 'cpdelay', 'cpbins', 'cpdiff', 'cpft', 'cpxps',
-                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imclean', 'mosaic', 'gains'))
+                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imclean', 'mosaic', 'mosclean', 'gains'))
 
 
 class PrisimHipError(RuntimeError):
@@ -1561,16 +1618,7 @@ class Context(object):
         a = self.PrisimMosaicArgs()
         npix, _, nchan, nt, resident, keep = _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube, weights, chan_avg, aberr_beta,
                                                              route, budget_bytes)
-        bpc = NP.ascontiguousarray(beam_pc_dircos, dtype=NP.float64)
-        if bpc.shape not in ((3,), (nt, 3)):
-            raise ValueError('beam_pc_dircos must be (3,) or one row per snapshot (nt, 3)')
-        exts, xs, keep_ext = _beam_ext_array(ext)
-        a.beam_kind, a.diameter_m = int(beam_kind), float(diameter_m)
-        a.beam_pc_dircos[:] = bpc.reshape(-1, 3)[0].tolist()
-        a.beam_pc_snap = _ptr(bpc) if bpc.ndim == 2 else None
-        a.ext = C.cast(xs, C.c_void_p) if exts else None
-        a.n_ext = len(exts)
-        a.pbmin = float(pbmin)
+        keep_ext = _mosaic_beam_fields(a, nt, beam_kind, diameter_m, beam_pc_dircos, ext, pbmin)
         shape = (npix,) if chan_avg else (npix, nchan)
         mosaic, pb_eff = NP.empty(shape, dtype=NP.float64), NP.empty(shape, dtype=NP.float64)
         num = NP.empty((npix, nchan), dtype=NP.float64) if want_sums else None
@@ -1602,18 +1650,7 @@ class Context(object):
         npix, _, nchan, _, resident, keep = _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube, weights, chan_avg, aberr_beta,
                                                             route, budget_bytes)
         nc = 1 if chan_avg else nchan
-        win = None
-        if window is not None:
-            win = NP.ascontiguousarray(NP.asarray(window) != 0, dtype=NP.uint8)
-            if win.shape != (npix,):
-                raise ValueError('window must be (npix,)')
-        fw = None
-        if fwhm_rad is not None:
-            fw = NP.ascontiguousarray(NP.broadcast_to(NP.asarray(fwhm_rad, dtype=NP.float64), (nc,)))
-        maxiter = int(maxiter)
-        a.window, a.fwhm_rad = _ptr(win), _ptr(fw)
-        a.gain, a.threshold, a.maxiter = float(gain), float(threshold), maxiter
-        a.threshold_relative, a.poll_every = 1 if threshold_relative else 0, int(poll_every or 0)
+        maxiter, win, fw = _clean_fields(a, npix, nc, gain, maxiter, threshold, threshold_relative, window, fwhm_rad, poll_every)
         shape = (npix,) if chan_avg else (npix, nchan)
         rows = max(maxiter, 0)
         residual = NP.empty(shape, dtype=NP.float64)
@@ -1625,11 +1662,52 @@ class Context(object):
         st = self.PrisimImcleanStats()
         self._call('prisim_clean_image', a=a, out_residual=residual, out_restored=restored, out_comp_pixel=pixel, out_comp_flux=flux,
                    out_ncomp=ncomp, out_status=status, out_peak0=peak0, out_wsum=wsum, stats=st)
-        del keep
+        del keep, win, fw
         longest = int(ncomp.max()) if nc else 0
         return {'residual': residual, 'restored': restored, 'comp_pixel': NP.ascontiguousarray(pixel[:, :longest]),
                 'comp_flux': NP.ascontiguousarray(flux[:, :longest]), 'ncomp': ncomp, 'status': status, 'peak0': peak0, 'wsum': wsum,
                 'stats': dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident)}
+
+    # ---- CLEAN of the beam-weighted mosaic (include/prisim_mosclean.h) ----
+    PrisimMoscleanStats = _PrisimMoscleanStats
+    PrisimMoscleanArgs = _PrisimMoscleanArgs
+
+    def clean_mosaic(self, unitvec, rot, pc_dircos, baselines, freqs_hz, beam_kind, diameter_m, beam_pc_dircos=(0.0, 0.0, 1.0), ext=None,
+                     cube=None, weights=None, chan_avg=False, aberr_beta=None, pbmin=0.1, gain=0.1, maxiter=10000, threshold=5e-3,
+                     threshold_relative=True, window=None, fwhm_rad=None, route='auto', budget_bytes=0, poll_every=0):
+        """CLEAN of the beam-weighted mosaic of mosaic_image on the device (prisim_clean_mosaic): per image channel (one for the band
+        with chan_avg) and iteration, the pixel of the largest |F| inside the window and the mask, F = R_N / sqrt(Q Wtot) the flat-noise
+        image, becomes a component of the true flux gain * R_N / Q there, and what the beam-weighted snapshots show of that component's
+        own visibilities is subtracted from the numerator R_N of every pixel.  The geometry, cube, weights and the beam as mosaic_image
+        takes them; gain, maxiter, threshold (in the units of F), threshold_relative, window, fwhm_rad, budget_bytes and poll_every as
+        clean_image takes them.  Returns a dict: 'residual' (R_N / Q under the mask, true fluxes), 'restored' (or None),
+        'residual_flat' (F) and 'pb_eff', (npix, nchan) or (npix,); 'num' (the final R_N) and 'den' (Q) (npix, nchan); 'wsum'
+        (nchan,); 'comp_pixel' int32 and 'comp_flux' (nc, longest list), the unused tail of a row -1 and 0; 'ncomp', 'status'
+        (PRISIM_IMCLEAN_* bits) int32 and 'peak0' (nc,); and the stats dict."""
+        a = self.PrisimMoscleanArgs()
+        npix, _, nchan, nt, resident, keep = _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube, weights, chan_avg, aberr_beta,
+                                                             route, budget_bytes)
+        keep_ext = _mosaic_beam_fields(a, nt, beam_kind, diameter_m, beam_pc_dircos, ext, pbmin)
+        nc = 1 if chan_avg else nchan
+        maxiter, win, fw = _clean_fields(a, npix, nc, gain, maxiter, threshold, threshold_relative, window, fwhm_rad, poll_every)
+        shape = (npix,) if chan_avg else (npix, nchan)
+        rows = max(maxiter, 0)
+        residual, flat, pb_eff = (NP.empty(shape, dtype=NP.float64) for _ in range(3))
+        restored = NP.empty(shape, dtype=NP.float64) if fw is not None else None
+        num, den = NP.empty((npix, nchan), dtype=NP.float64), NP.empty((npix, nchan), dtype=NP.float64)
+        wsum = NP.empty(nchan, dtype=NP.float64)
+        pixel = NP.full((nc, rows), -1, dtype=NP.int32)
+        flux = NP.zeros((nc, rows), dtype=NP.float64)
+        ncomp, status, peak0 = NP.empty(nc, dtype=NP.int32), NP.empty(nc, dtype=NP.int32), NP.empty(nc, dtype=NP.float64)
+        st = self.PrisimMoscleanStats()
+        self._call('prisim_clean_mosaic', a=a, out_residual=residual, out_restored=restored, out_residual_flat=flat, out_pb_eff=pb_eff,
+                   out_num=num, out_den=den, out_wsum=wsum, out_comp_pixel=pixel, out_comp_flux=flux, out_ncomp=ncomp, out_status=status,
+                   out_peak0=peak0, stats=st)
+        del keep, keep_ext, win, fw
+        longest = int(ncomp.max()) if nc else 0
+        return {'residual': residual, 'restored': restored, 'residual_flat': flat, 'pb_eff': pb_eff, 'num': num, 'den': den, 'wsum': wsum,
+                'comp_pixel': NP.ascontiguousarray(pixel[:, :longest]), 'comp_flux': NP.ascontiguousarray(flux[:, :longest]), 'ncomp': ncomp,
+                'status': status, 'peak0': peak0, 'stats': dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident)}
 
     # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
     def closure_delay_spectra(self, wts, m, df, phases=None, cube=None, legs=None, conj=None, bpwts=None, freq_wts=None, masks=None,

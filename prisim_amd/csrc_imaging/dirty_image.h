@@ -15,7 +15,7 @@
 
 namespace {
 
-// grid: x over the channels.  wsum [nchan].  Not one kernel with k_mos_wsum (mosaic.hip): this one carries one running sum over
+// grid: x over the channels.  wsum [nchan].  Not one kernel with k_mos_wsum (mosaic_kernels.h): this one carries one running sum over
 // (t, b), that one sums over b within each snapshot and then over t; for weights that are not integers the two orders give different
 // bits, and each is pinned by its own checker.
 __global__ void __launch_bounds__(kThreads) k_img_wsum(ImgWeights W, int64_t nt, int64_t nbl, int nchan, double* __restrict__ wsum) {

@@ -5,14 +5,15 @@
 // (launch_beam_flux of ../csrc/aux_kernels.hip with unit flux, as antpower.hip calls it) and the tile pass of the direct Fourier sum
 // (img_tile_pass of imaging_kernels.h, as it stands, where the hot loop is described).
 //
-// Once per call:
+// The kernels and the functions that enqueue them are in mosaic_kernels.h, which prisim_clean_mosaic (mosclean.hip) shares: k_mos_sum<STEPPED>
+// is img_tile_pass<STEPPED, false>(...) with the epilogue below.  Once per call:
 //   k_mos_wsum   W_t[k] = sum_b w[t][b][k] as [nt][nchan], b ascending, and Wtot[k] = sum_t W_t[k], t ascending; one thread per
 //                channel.  k_img_wtot sums Wtot over k for chan_avg.
 // Per chunk of pixels (contiguous, a whole number of blocks of 256), on the chunk's stream:
 //   k_img_dirs   with both outputs: s[t][pixel] = normalise(R_t (u + beta_t)) as (l, m, n, 0), the rows BeamParams.dirs reads, and
 //                dd = s - s0[t].
 //   then for t = 0 .. nt - 1, in this order:
-//     launch_beam_flux with unit flux (flux_ref = 1, spindex = 0: pb exp2(0) = pb exactly) on the chunk's directions of snapshot t
+//     launch_beam_flux(bp, stream) by enqueue_mos_beam, with unit flux (flux_ref = 1, spindex = 0: pb exp2(0) = pb exactly) on the chunk's directions of snapshot t
 //                into pb_tile[count][nchan], the one tile of the stream: 8 nchan bytes a pixel, not 8 nt nchan.
 //     k_mos_sum  the hot path, one launch per snapshot: the tile pass of that snapshot on (w Re V, w Im V), the operand of the dirty
 //                image.  The epilogue reads the thread's 32 beam values, puts 0 in their place where the direction is below the
@@ -39,103 +40,9 @@
 #include "../csrc_addon/beam_setup.h"
 #include "../csrc_addon/mosaic_plan.h"
 #include "imaging_kernels.h"
+#include "mosaic_kernels.h"
 
 namespace {
-
-// grid: x over the channels.  wt [nt][nchan], wtot [nchan].  Why this is not k_img_wsum: see there (dirty_image.h)
-__global__ void __launch_bounds__(kThreads) k_mos_wsum(ImgWeights W, int64_t nt, int64_t nbl, int nchan, double* __restrict__ wt,
-                                                       double* __restrict__ wtot) {
-  const int k = (int)blockIdx.x * kThreads + threadIdx.x;
-  if (k >= nchan) return;
-  double tot = 0.0;
-  for (int64_t t = 0; t < nt; ++t) {
-    const double* row = W.w ? W.w + t * W.st + k * W.sk : nullptr;
-    double s = 0.0;
-#pragma unroll 8
-    for (int64_t b = 0; b < nbl; ++b) s += row ? row[b * W.sb] : 1.0;
-    wt[t * nchan + k] = s;
-    tot += s;
-  }
-  wtot[k] = tot;
-}
-
-struct MosParams {
-  const double2* cube;      // [nt][nbl][nchan]
-  ImgWeights W;
-  const double* bl;         // [nbl][3]
-  const double* freqs;      // [nchan]
-  const double4* dd;        // [count] of the chunk at snapshot t: s - s0
-  const double4* s4;        // [count] of the chunk at snapshot t: s, for the horizon
-  const double* pb;         // [count][nchan] the beam tile of snapshot t
-  const double* wt;         // [nchan] W_t
-  double df;                // the step of a uniform grid (STEPPED)
-  int64_t nbl, t, count;    // t: the snapshot of this launch; count: pixels of the chunk
-  int nchan;
-  double *N, *Q;            // [count][nchan] of the chunk: read unless t == 0, written
-};
-
-// grid: x = block of the chunk's pixels, y = channel tile.  LDS: kImagingLds
-template <bool STEPPED>
-__global__ void __launch_bounds__(kThreads) k_mos_sum(MosParams P) {
-  __shared__ double2 sh_v[NB * CT];     // (w Re V, w Im V)
-  __shared__ double sh_b[NB * 3];       // b / c
-  __shared__ double sh_f[CT];           // the tile's frequencies; past the band: the last channel's (their operand rows are 0)
-  const int tid = threadIdx.x;
-  const int k0 = (int)blockIdx.y * CT;
-  const int64_t pl_raw = (int64_t)blockIdx.x * kThreads + tid;
-  const bool p_valid = pl_raw < P.count;
-  const int64_t pl = p_valid ? pl_raw : P.count - 1;
-  const int64_t t = P.t;
-  if (tid < CT) sh_f[tid] = P.freqs[k0 + tid < P.nchan ? k0 + tid : P.nchan - 1];
-  double acc[CT];
-#pragma unroll
-  for (int k = 0; k < CT; ++k) acc[k] = 0.0;
-  const double f0 = P.freqs[k0];          // k0 < nchan: the grid has ceil(nchan / CT) tiles
-  img_tile_pass<STEPPED, false>(t, P.dd[pl], P.bl, P.nbl, k0, f0, P.df, sh_v, sh_b, sh_f, acc, [&P](bool live, int64_t t, int64_t b, int, int k) {
-    if (!live || k >= P.nchan) return make_double2(0.0, 0.0);
-    const double w = P.W.at(t, b, k);
-    const double2 x = P.cube[(t * P.nbl + b) * P.nchan + k];
-    return make_double2(w * x.x, w * x.y);
-  });
-  if (!p_valid) return;
-  const bool up = P.s4[pl].z >= 0.0;
-  const int64_t at = pl * P.nchan + k0;
-#pragma unroll
-  for (int k = 0; k < CT; ++k)
-    if (k0 + k < P.nchan) {
-      const double A = up ? P.pb[at + k] : 0.0;
-      P.N[at + k] = fma(A, acc[k], t ? P.N[at + k] : 0.0);
-      P.Q[at + k] = fma(A * A, P.wt[k0 + k], t ? P.Q[at + k] : 0.0);
-    }
-}
-
-// grid-stride over count * nchan
-__global__ void __launch_bounds__(kThreads) k_mos_finish(const double* __restrict__ N, const double* __restrict__ Q, const double* __restrict__ wtot,
-                                                         int64_t count, int nchan, double pbmin, double* __restrict__ mosaic,
-                                                         double* __restrict__ pb_eff) {
-  const int64_t total = count * nchan;
-  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
-    const double w = wtot[e % nchan], q = Q[e];
-    mosaic[e] = q >= (pbmin * pbmin) * w ? N[e] / q : NAN;
-    pb_eff[e] = sqrt(q / w);
-  }
-}
-
-// grid: x over the chunk's pixels.  wband[0] = sum_k wtot[k]
-__global__ void __launch_bounds__(kThreads) k_mos_finish_band(const double* __restrict__ N, const double* __restrict__ Q,
-                                                              const double* __restrict__ wband, int64_t count, int nchan, double pbmin,
-                                                              double* __restrict__ mosaic, double* __restrict__ pb_eff) {
-  const int64_t pl = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (pl >= count) return;
-  double n = 0.0, q = 0.0;
-  for (int k = 0; k < nchan; ++k) {
-    n += N[pl * nchan + k];
-    q += Q[pl * nchan + k];
-  }
-  const double w = wband[0];
-  mosaic[pl] = q >= (pbmin * pbmin) * w ? n / q : NAN;
-  pb_eff[pl] = sqrt(q / w);
-}
 
 int mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosaic, double* out_pb_eff, double* out_num, double* out_den,
                  double* out_wsum, prisim_mosaic_stats* stats) {
@@ -145,10 +52,7 @@ int mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosai
   if (!out_mosaic) return fail(ctx, PRISIM_EINVAL, "out_mosaic is NULL");
   const ImgView v = imaging_view(*a);
   if (int rc = check_args(ctx, v)) return rc;
-  if (!(a->pbmin >= 0.0 && a->pbmin < 1.0)) return fail(ctx, PRISIM_EINVAL, "pbmin must lie in [0, 1)");
-  if (int rc = check_beams(ctx, a->beam_kind, a->diameter_m, a->beam_pc_dircos, a->ext, a->n_ext, a->nt, "nt")) return rc;
-  for (int64_t i = 0; a->beam_pc_snap && i < a->nt * 3; ++i)
-    if (!std::isfinite(a->beam_pc_snap[i])) return fail(ctx, PRISIM_EINVAL, "beam_pc_snap of snapshot " + std::to_string(i / 3) + " is not finite");
+  if (int rc = check_mosaic_beam(ctx, *a)) return rc;
   const int64_t npix = a->npix, nbl = a->nbl, nchan = a->nchan, nt = a->nt;
   const bool avg = a->chan_avg != 0;
   ImgSetup su{};
@@ -190,9 +94,7 @@ int mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosai
   DEV_ALLOC(ctx, wk.dev, d_wt, nt * nchan * 8);
   DEV_ALLOC(ctx, wk.dev, d_wtot, nchan * 8);
   DEV_ALLOC(ctx, wk.dev, d_wband, 8);
-  if (int rc = launch(ctx, k_mos_wsum, dim3((unsigned)((nchan + kThreads - 1) / kThreads)), 0, s0, W, nt, nbl, (int)nchan, d_wt, d_wtot)) return rc;
-  hipLaunchKernelGGL(k_img_wtot, dim3(1), dim3(64), 0, s0, (const double*)d_wtot, (int)nchan, d_wband);
-  HIPCHK(ctx, hipGetLastError());
+  if (int rc = enqueue_mos_wsum(ctx, W, nt, nbl, nchan, d_wt, d_wtot, d_wband, s0)) return rc;
 
   // per stream: the buffers of one chunk
   double4 *d_s4[kMaxStreams] = {}, *d_dd[kMaxStreams] = {};
@@ -221,34 +123,16 @@ int mosaic_image(prisim_ctx* ctx, const prisim_mosaic_args* a, double* out_mosai
     if (int rc = launch(ctx, k_img_dirs, dim3((unsigned)grid_for(ctx, sp.count * nt)), 0, sc, T.uvec, T.frames, sp.first, sp.count, nt, d_s4[i],
                         d_dd[i]))
       return rc;
-    const dim3 grid((unsigned)((sp.count + pl.block - 1) / pl.block), (unsigned)pl.ntiles);
     for (int64_t t = 0; t < nt; ++t) {
-      const int64_t e = a->n_ext == nt ? t : 0;
-      BeamParams bp{};
-      fill_beam(bp, a->beam_kind, a->diameter_m, a->beam_pc_snap ? a->beam_pc_snap + t * 3 : a->beam_pc_dircos,
-                a->n_ext > 0 ? a->ext + e : nullptr, d_bf[(size_t)e]);
-      bp.dirs = (const double*)(d_s4[i] + t * sp.count);
-      bp.flux_ref = d_ones;
-      bp.spindex = d_zeros;
-      bp.freqs = T.freqs;
-      bp.ref_freq = 1.0;
-      bp.flag = d_flag;
-      bp.nsrc = sp.count;
-      bp.nchan = nchan;
-      bp.pb_out = d_pb[i];
-      HIPCHK(ctx, launch_beam_flux(bp, sc));
+      if (int rc = enqueue_mos_beam(ctx, *a, t, d_bf, d_s4[i] + t * sp.count, sp.count, T.freqs, d_ones, d_zeros, d_flag, d_pb[i], sc)) return rc;
       MosParams P = base;
       P.dd = d_dd[i] + t * sp.count; P.s4 = d_s4[i] + t * sp.count;
       P.pb = d_pb[i]; P.wt = d_wt + t * nchan;
       P.t = t; P.count = sp.count;
       P.N = d_N[i]; P.Q = d_Q[i];
-      if (int rc = stepped ? launch(ctx, k_mos_sum<true>, grid, 0, sc, P) : launch(ctx, k_mos_sum<false>, grid, 0, sc, P)) return rc;
+      if (int rc = enqueue_mos_sum(ctx, P, pl.block, pl.ntiles, stepped, sc)) return rc;
     }
-    if (avg)
-      return launch(ctx, k_mos_finish_band, dim3((unsigned)((sp.count + kThreads - 1) / kThreads)), 0, sc, (const double*)d_N[i],
-                    (const double*)d_Q[i], (const double*)d_wband, sp.count, (int)nchan, a->pbmin, d_mos[i], d_eff[i]);
-    return launch(ctx, k_mos_finish, dim3((unsigned)grid_for(ctx, sp.count * nchan)), 0, sc, (const double*)d_N[i], (const double*)d_Q[i],
-                  (const double*)d_wtot, sp.count, (int)nchan, a->pbmin, d_mos[i], d_eff[i]);
+    return enqueue_mos_finish(ctx, avg, d_N[i], d_Q[i], d_wtot, d_wband, sp.count, nchan, a->pbmin, d_mos[i], d_eff[i], sc);
   };
   auto download = [&](int64_t, Span sp, int i, hipStream_t sc) -> int {
     const size_t out_bytes = (size_t)(sp.count * per_out) * 8, sum_bytes = (size_t)(sp.count * nchan) * 8;

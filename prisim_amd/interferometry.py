@@ -2773,14 +2773,14 @@ class ApertureSynthesis(object):
 
     Attributes as in the reference (:9136-9163): ia, f, df, n_acc, lst, phase_center, phase_center_coords, pointing_center,
     pointing_coords, baselines, timestamp, latitude, blxyz, uvw_lambda, uvw, blc, trc, grid_blc, grid_trc, gridu, gridv, gridw,
-    grid_ready; and image_stats, the statistics of the last image(), psf(), clean() or mosaic().
+    grid_ready; and image_stats, the statistics of the last image(), psf(), clean(), mosaic() or clean_mosaic().
 
     Departures from the reference: setUVWgrid is not ported -- its grid comes from GRD.grid_3d, whose source is not part of the
     reference tree, and the direct transform needs no grid; grid_ready stays False.  genUVW with a 'radec' phase centre takes
     HA = LST - RA and the centre's declination, as _pc_dircos and project_baselines do (the reference puts HA = LST and Dec = 0, :9180).
     image(), psf(), clean() (Hogbom's CLEAN of image() with the exact beam, include/prisim_imclean.h), mosaic() (the beam-weighted
-    mosaic of the snapshots, horizon mask included: true fluxes where image() gives apparent ones, include/prisim_mosaic.h) and
-    dircos_grid() are additions.
+    mosaic of the snapshots, horizon mask included: true fluxes where image() gives apparent ones, include/prisim_mosaic.h),
+    clean_mosaic() (CLEAN of that mosaic, include/prisim_mosclean.h) and dircos_grid() are additions.
     There is no CPU path."""
 
     def __init__(self, interferometer_array=None):
@@ -2979,6 +2979,17 @@ class ApertureSynthesis(object):
         if not (0.0 <= pbmin < 1.0):
             raise ValueError('pbmin must lie in [0, 1)')
         uv, rot, beta, pc, w, cube = self._prepare('dirty', directions, coords, datakey, weights, epoch, route)
+        kind, dia, bpc, ext = self._beam_specs(telescope, pb_info)
+        image, num, den, wsum, st = ia._ctx.mosaic_image(uv, rot, pc, ia._baselines_local(), ia.channels, kind, dia, beam_pc_dircos=bpc,
+                                                         ext=ext, cube=cube, weights=w, chan_avg=bool(chan_avg), aberr_beta=beta,
+                                                         pbmin=pbmin, route=route, budget_bytes=int(budget_bytes or 0))
+        self.image_stats = dict(st, num=num, den=den, wsum=wsum)
+        return image
+
+    def _beam_specs(self, telescope, pb_info):
+        """The beam of the snapshots as mosaic_image and clean_mosaic take it: (kind, size, beam_pc_dircos (3,) or (nt, 3), ext None, a
+        dict or one dict per snapshot), from primary_beams.device_beam_spec at the pointing observe() used in every snapshot."""
+        ia = self.ia
         tel = ia.telescope if telescope is None else telescope
         nt = len(ia.lst)
         infos = list(pb_info) if isinstance(pb_info, (list, tuple)) else [pb_info] * nt
@@ -2996,11 +3007,7 @@ class ApertureSynthesis(object):
             bpc = NP.stack([NP.asarray(sp[2], dtype=NP.float64).ravel() for sp in specs])
         if not all(_same_beam_spec(ext, sp[3]) for sp in specs[1:]):
             ext = [sp[3] for sp in specs]
-        image, num, den, wsum, st = ia._ctx.mosaic_image(uv, rot, pc, ia._baselines_local(), ia.channels, kind, dia, beam_pc_dircos=bpc,
-                                                         ext=ext, cube=cube, weights=w, chan_avg=bool(chan_avg), aberr_beta=beta,
-                                                         pbmin=pbmin, route=route, budget_bytes=int(budget_bytes or 0))
-        self.image_stats = dict(st, num=num, den=den, wsum=wsum)
-        return image
+        return kind, dia, bpc, ext
 
     def clean(self, directions, coords='dircos', datakey='noiseless', weights=None, chan_avg=False, epoch=None, gain=0.1, maxiter=10000,
               threshold=5e-3, threshold_type='relative', window=None, fwhm=None, restore=True, route='auto', budget_bytes=None):
@@ -3032,6 +3039,16 @@ class ApertureSynthesis(object):
         uv, rot, beta, pc, w, cube = self._prepare('dirty', directions, coords, datakey, weights, epoch, route)
         npix, nchan = uv.shape[0], ia.channels.size
         nc = 1 if chan_avg else nchan
+        bl = ia._baselines_local()
+        win, fwhm_rad = self._window_and_fwhm(window, fwhm, npix, nc, chan_avg, bl)
+        r = ia._ctx.clean_image(uv, rot, pc, bl, ia.channels, cube=cube, weights=w, chan_avg=bool(chan_avg), aberr_beta=beta,
+                                gain=gain, maxiter=maxiter, threshold=threshold, threshold_relative=threshold_type == 'relative',
+                                window=win, fwhm_rad=fwhm_rad if restore else None, route=route, budget_bytes=int(budget_bytes or 0))
+        self.image_stats = dict(r['stats'], wsum=r['wsum'])
+        return self._clean_dict(r, npix, nc, chan_avg, restore, threshold, threshold_type, fwhm_rad)
+
+    def _window_and_fwhm(self, window, fwhm, npix, nc, chan_avg, bl):
+        """(the window as booleans or None, the restoring beam (nc,) in radians) of clean() and clean_mosaic(), with their checks"""
         win = None
         if window is not None:
             win = NP.asarray(window)
@@ -3040,9 +3057,8 @@ class ApertureSynthesis(object):
             win = win != 0
             if not win.any():
                 raise ValueError('window holds no pixel')
-        bl = ia._baselines_local()
         if fwhm is None:
-            f = NP.asarray(ia.channels, dtype=NP.float64)
+            f = NP.asarray(self.ia.channels, dtype=NP.float64)
             longest = float(NP.sqrt(NP.max(NP.sum(NP.asarray(bl, dtype=NP.float64) ** 2, axis=1))))
             if not longest > 0.0:
                 raise ValueError('the default fwhm needs a baseline of non-zero length')
@@ -3055,10 +3071,11 @@ class ApertureSynthesis(object):
                 raise ValueError('fwhm must be None, a scalar or ({0},)'.format(nc))
             if not NP.all(NP.isfinite(fwhm_rad) & (fwhm_rad > 0.0)):
                 raise ValueError('fwhm must be positive and finite')
-        r = ia._ctx.clean_image(uv, rot, pc, bl, ia.channels, cube=cube, weights=w, chan_avg=bool(chan_avg), aberr_beta=beta,
-                                gain=gain, maxiter=maxiter, threshold=threshold, threshold_relative=threshold_type == 'relative',
-                                window=win, fwhm_rad=fwhm_rad if restore else None, route=route, budget_bytes=int(budget_bytes or 0))
-        self.image_stats = dict(r['stats'], wsum=r['wsum'])
+        return win, fwhm_rad
+
+    @staticmethod
+    def _clean_dict(r, npix, nc, chan_avg, restore, threshold, threshold_type, fwhm_rad):
+        """What clean() and clean_mosaic() return alike, from the context's dict r"""
         count = NP.asarray(r['ncomp'])
         model = NP.zeros((npix, nc), dtype=NP.float64)
         for k in range(nc):
@@ -3067,3 +3084,45 @@ class ApertureSynthesis(object):
         return {'residual': r['residual'], 'restored': r['restored'] if restore else None, 'model': model[:, 0] if chan_avg else model,
                 'components': {'pixel': r['comp_pixel'], 'flux': r['comp_flux'], 'count': count}, 'status': r['status'], 'peak0': peak0,
                 'threshold': threshold * peak0 if threshold_type == 'relative' else NP.full(nc, threshold), 'fwhm': NP.degrees(fwhm_rad)}
+
+    def clean_mosaic(self, directions, coords='dircos', datakey='noiseless', weights=None, chan_avg=False, epoch=None, telescope=None,
+                     pb_info=None, pbmin=0.1, gain=0.1, maxiter=10000, threshold=5e-3, threshold_type='relative', window=None, fwhm=None,
+                     restore=True, route='auto', budget_bytes=None):
+        """CLEAN of mosaic(), on the GPU (include/prisim_mosclean.h): a deconvolved sky in true fluxes for a drift scan through a
+        chromatic beam, where clean() returns apparent fluxes and mosaic() leaves every source the sidelobes of every other one.  Per
+        channel (or for the band with chan_avg) and iteration, the pixel of the largest |F| inside the window and the pbmin mask
+        becomes a component of gain times the mosaic's value there -- F = num / sqrt(den wsum) is the flat-noise image, in the units
+        and at the noise level of image(), so the search does not run to the rim of the beam --, and what the beam-weighted snapshots
+        show of that component's own visibilities, as observe() would simulate them, is subtracted from the numerator of every pixel.
+        The mosaic's value is the least-squares flux of a component at that pixel, so a step is one of matching pursuit: the weighted
+        sum of |V - model|^2 cannot grow.
+
+        directions, coords, datakey, weights, chan_avg, epoch, telescope, pb_info, pbmin, route as mosaic() takes them; gain, maxiter,
+        threshold, threshold_type, window, fwhm, restore, budget_bytes as clean() takes them, the threshold in the units of F.
+        Returns the dict of clean() -- 'residual' and 'restored' in true fluxes, NaN where the mosaic is masked; 'model' and the
+        components' fluxes true fluxes; 'peak0' and 'threshold' in the units of F -- and 'residual_flat', F of the final residual.
+        num (the final numerator), den, wsum, pb_eff and the entry's statistics are left in image_stats.
+
+        Raises NotImplementedError for an array with an external beam (set_external_beam) and for the apertures device_beam_spec
+        does not carry (rect, square)."""
+        from . import delay_spectrum as DS                            # (imports this module)
+        ia = self.ia
+        if getattr(ia, '_extbeam', None) is not None:
+            raise NotImplementedError('clean_mosaic() evaluates the analytic beams; the array has an external beam (set_external_beam)')
+        threshold = DS._check_clean_args(threshold_type, threshold, gain, maxiter)
+        DS._check_gain_maxiter(gain, maxiter)
+        pbmin = float(pbmin)
+        if not (0.0 <= pbmin < 1.0):
+            raise ValueError('pbmin must lie in [0, 1)')
+        uv, rot, beta, pc, w, cube = self._prepare('dirty', directions, coords, datakey, weights, epoch, route)
+        kind, dia, bpc, ext = self._beam_specs(telescope, pb_info)
+        npix, nchan = uv.shape[0], ia.channels.size
+        nc = 1 if chan_avg else nchan
+        bl = ia._baselines_local()
+        win, fwhm_rad = self._window_and_fwhm(window, fwhm, npix, nc, chan_avg, bl)
+        r = ia._ctx.clean_mosaic(uv, rot, pc, bl, ia.channels, kind, dia, beam_pc_dircos=bpc, ext=ext, cube=cube, weights=w,
+                                 chan_avg=bool(chan_avg), aberr_beta=beta, pbmin=pbmin, gain=gain, maxiter=maxiter, threshold=threshold,
+                                 threshold_relative=threshold_type == 'relative', window=win, fwhm_rad=fwhm_rad if restore else None,
+                                 route=route, budget_bytes=int(budget_bytes or 0))
+        self.image_stats = dict(r['stats'], num=r['num'], den=r['den'], wsum=r['wsum'], pb_eff=r['pb_eff'])
+        return dict(self._clean_dict(r, npix, nc, chan_avg, restore, threshold, threshold_type, fwhm_rad), residual_flat=r['residual_flat'])
