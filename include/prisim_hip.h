@@ -309,6 +309,9 @@ int prisim_hip_observe_catalog(prisim_ctx* ctx, const prisim_obs* obs, const pri
 /* For slots [0, nt): x = V * bpwts (bpwts: [nbl][nchan] real weights = bp*bp_wts, or NULL = 1),
  * zero-pad by npad = int(nchan*pad) at the high-frequency end (:8123-8125), inverse FFT along
  * frequency (rocFFT), fftshift, scale by (nchan+npad)*df (:8125), keep every (1+pad)-th lag (:8132).
+ * nchan_out = ceil((nchan + npad) / (1 + pad) - 1e-12) (delay_geom in capi.cpp), the exact count of j >= 0 with j (1 + pad) < nchan + npad;
+ * numpy's len(arange(0, nchan + npad, 1 + pad)) is one more where the quotient rounds up past an integer (1400 / 1.4).  The binding
+ * sizes its arrays by the same rule, delay_nout in prisim_amd/_abi.py: change both together.
  * out: host complex128 [nt][nbl][nchan_out]; lags_out: [nchan_out] seconds (may be NULL).
  * power != 0 writes |.|^2 * power_scale into out_power [nt][nbl][nchan_out] float64
  * (delay_spectrum.py:3992-3993) instead of / in addition to out (either may be NULL). */

@@ -4,6 +4,7 @@ The product path FAILS LOUDLY when the HIP library or a GPU is missing: there is
 fallback anywhere in ``prisim_amd``.
 """
 import ctypes as C
+import math
 import os
 import re
 
@@ -399,6 +400,19 @@ def _stats_dict(st, rename=None, **maps):
             v = f.get(v, v) if isinstance(f, dict) else f(v)
         out[(rename or {}).get(name, name)] = v
     return out
+
+
+def delay_nout(nchan, pad):
+    """Lags per row of the delay transform of nchan channels padded by the fraction pad: the library's rule, delay_geom in
+    csrc/capi.cpp (stated for callers in include/prisim_hip.h), restated so that the host sizes its arrays as the library fills them:
+    change both together, tests/test_gpu_delay_sweeps.py holds one against the other.  It is the exact count of positions
+    j (1 + pad) < nfft, j >= 0.  len(arange(0, nfft, 1 + pad)) is NOT: where nfft / (1 + pad) rounds up past an integer (1400 / 1.4 =
+    1000.0000000000001) arange has one position more, and that position is nfft itself."""
+    pad = max(float(pad), 0.0)
+    nchan = int(nchan)
+    npad = int(nchan * pad)
+    nfft = nchan + npad
+    return int(math.ceil(nfft / (1.0 + pad) - 1e-12))
 
 
 def _resample_map(wanted, m, nout):
@@ -1173,8 +1187,7 @@ class Context(object):
     def delay_transform(self, nt, bpwts=None, pad=1.0, want_power=False, power_scale=1.0, want_lag=True):
         pad = max(float(pad), 0.0)
         nchan = self.nchan
-        nfft = nchan + int(nchan * pad)
-        nout = int(NP.arange(0, nfft, 1.0 + pad).size)
+        nout = delay_nout(nchan, pad)                     # the library writes nt * nbl rows of exactly this many lags back to back
         w = None
         if bpwts is not None:
             w = NP.ascontiguousarray(bpwts, dtype=NP.float64).reshape(self.nbl, nchan)

@@ -473,7 +473,8 @@ class DelaySpectrum(object):
         if decimate and pad > 0.0:
             result['lags'] = result['lags'][NP.arange(0, nfft, 1 + pad).astype(int)] if float(1 + pad).is_integer() else \
                 NP.interp(NP.arange(0, nfft, 1 + pad), NP.arange(nfft), result['lags'])    # DSP.downsampler(lags, 1 + pad), :1329
-            result['lags'] = result['lags'].flatten()
+            # as many as the spectra have (arange has one position more, nfft itself, where nfft / (1 + pad) rounds up past an integer)
+            result['lags'] = result['lags'].flatten()[:_abi.delay_nout(nchan, pad)]
             if verbose:
                 print('\tDelay transform products downsampled by factor of {0:.1f}'.format(1 + pad))
                 print('delay_transform() completed successfully.')

@@ -213,6 +213,34 @@ def test_context_call_fills_in_the_context_and_checks_the_code():
     ctx._h = None                                                             # (nothing for __del__ to destroy)
 
 
+DELAY_PADS = ('0', '0.05', '0.1', '0.2', '0.25', '0.3', '0.33', '0.4', '0.5', '0.6', '0.7', '0.75', '0.8', '0.9', '1', '1.1', '1.25', '1.5',
+              '2', '2.5', '3')
+
+
+def test_delay_nout_is_the_exact_count_and_arange_is_not():
+    """delay_nout (the library's rule, delay_geom in csrc/capi.cpp) against the exact count of j >= 0 with j (1 + pad) < nfft, the pad
+    taken as the decimal written, for 2 <= nchan < 2100 and 21 pads.  numpy's len(arange(0, nfft, 1 + pad)), which sized the host
+    arrays before, is one more at pad 0.4 (1400 / 1.4 evaluates to 1000.0000000000001) and nowhere less; its extra position is >= nfft,
+    so no sample of the spectrum is lost by following the library."""
+    from fractions import Fraction
+    longer = []
+    for ps in DELAY_PADS:
+        pad, fpad = float(ps), Fraction(ps)
+        for nchan in range(2, 2100):
+            nfft = nchan + int(nchan * pad)
+            q = Fraction(nfft) / (1 + fpad)
+            exact = -((-q.numerator) // q.denominator)                     # ceil
+            assert A.delay_nout(nchan, pad) == exact, (nchan, ps)
+            pos = NP.arange(0, nfft, 1.0 + pad)
+            if pos.size != exact:
+                assert pos.size == exact + 1 and pos[-1] >= nfft, (nchan, ps, pos.size, exact)
+                longer.append((nchan, ps))
+    assert NP.arange(0, 1400, 1.4).size == 1001 and A.delay_nout(1000, 0.4) == 1000
+    assert len(longer) == 102 and {ps for _, ps in longer} == {'0.4'}
+    assert {15, 30, 60, 115, 120, 125, 225, 230, 235, 240, 245, 250, 255, 1000} <= {n for n, _ in longer}
+    assert A.delay_nout(64, -1.0) == 64                                   # a negative pad is no pad, as in the library
+
+
 def test_resample_map_helper():
     assert A._resample_map(False, 16, 8) == (0, None, None, None)
     assert A._resample_map(0, 16, 8) == (0, None, None, None)
