@@ -103,6 +103,12 @@ IMAGING_KINDS = {'dirty': PRISIM_IMAGE_DIRTY, 'psf': PRISIM_IMAGE_PSF}
 PRISIM_IMCLEAN_THRESHOLD, PRISIM_IMCLEAN_MAXITER, PRISIM_IMCLEAN_DEAD = 1, 2, 4
 PRISIM_IMCLEAN_POLL_DEFAULT, PRISIM_IMCLEAN_POLL_MAX = 32, 1024
 
+# Cotton-Schwab CLEAN of dirty images (include/prisim_csclean.h, prisim_amd/csrc_imaging/csclean.hip)
+PRISIM_CSCLEAN_MAJOR, PRISIM_CSCLEAN_DIVERGED = 8, 16
+PRISIM_CSCLEAN_AUTO, PRISIM_CSCLEAN_LDS, PRISIM_CSCLEAN_GLOBAL = -1, 0, 1
+PRISIM_CSCLEAN_MAX_MAJOR = 65536
+CSCLEAN_ROUTES = {PRISIM_CSCLEAN_LDS: 'lds', PRISIM_CSCLEAN_GLOBAL: 'global'}
+
 # instrument gain tables (include/prisim_gains.h, prisim_amd/csrc_gains/)
 PRISIM_GAINS_MAX_DEGREE = 5
 PRISIM_GAINS_ANTENNA, PRISIM_GAINS_BASELINE = 0, 1
@@ -337,6 +343,24 @@ class _PrisimImcleanArgs(C.Structure):
                 ('threshold_relative', C.c_int32), ('poll_every', C.c_int32), ('reserved_', C.c_int32)]
 
 
+class _PrisimCscleanStats(C.Structure):
+    """prisim_csclean_stats of include/prisim_csclean.h, public as Context.PrisimCscleanStats (see _PrisimCpxpsStats)."""
+    _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('psf_ms', C.c_double), ('dirty_ms', C.c_double), ('peak_ms', C.c_double),
+                ('minor_ms', C.c_double), ('model_ms', C.c_double), ('restore_ms', C.c_double), ('terms', C.c_int64), ('cycles', C.c_int64),
+                ('components', C.c_int64), ('polls', C.c_int64), ('psf_offsets', C.c_int64), ('upload_bytes', C.c_int64),
+                ('download_bytes', C.c_int64), ('device_bytes', C.c_int64), ('route', C.c_int32), ('minor_route', C.c_int32),
+                ('streams', C.c_int32), ('chan_tile', C.c_int32), ('reseed', C.c_int32), ('lds_bytes', C.c_int32),
+                ('minor_lds_bytes', C.c_int32), ('block_pixels', C.c_int32)]
+
+
+class _PrisimCscleanArgs(C.Structure):
+    """prisim_csclean_args of include/prisim_csclean.h, public as Context.PrisimCscleanArgs: the fields of prisim_imclean_args less its
+    polling, then those of the cycles."""
+    _fields_ = [f for f in _PrisimImcleanArgs._fields_ if f[0] not in ('poll_every', 'reserved_')] + [
+        ('ny', C.c_int64), ('nx', C.c_int64), ('cycle_depth', C.c_double), ('cycle_niter', C.c_int64), ('max_major', C.c_int32),
+        ('minor_route', C.c_int32)]
+
+
 class _PrisimMosaicStats(C.Structure):
     """prisim_mosaic_stats of include/prisim_mosaic.h, public as Context.PrisimMosaicStats (see _PrisimCpxpsStats)."""
     _fields_ = [('wall_ms', C.c_double), ('kernel_ms', C.c_double), ('terms', C.c_int64), ('beam_values', C.c_int64), ('chunks', C.c_int64),
@@ -560,6 +584,7 @@ STRUCTS = {
     'prisim_imclean_stats': _PrisimImcleanStats, 'prisim_imclean_args': _PrisimImcleanArgs,
     'prisim_mosaic_stats': _PrisimMosaicStats, 'prisim_mosaic_args': _PrisimMosaicArgs,
     'prisim_mosclean_stats': _PrisimMoscleanStats, 'prisim_mosclean_args': _PrisimMoscleanArgs,
+    'prisim_csclean_stats': _PrisimCscleanStats, 'prisim_csclean_args': _PrisimCscleanArgs,
 }
 
 # The C ABI, declared once: per header of include/, its functions in the header's order, each as
@@ -702,6 +727,11 @@ _PROTOTYPES = {
         int prisim_clean_mosaic(p ctx, *prisim_mosclean_args a, p out_residual, p out_restored, p out_residual_flat, p out_pb_eff, p out_num,
             p out_den, p out_wsum, p out_comp_pixel, p out_comp_flux, p out_ncomp, p out_status, p out_peak0, *prisim_mosclean_stats stats);
     ''',
+    'prisim_csclean.h': '''
+        int prisim_clean_image_cs(p ctx, *prisim_csclean_args a, p out_residual, p out_restored, p out_comp_pixel, p out_comp_flux,
+            p out_ncomp, p out_status, p out_peak0, p out_wsum, p out_ncycles, p out_cycle_ncomp, p out_cycle_peak, p out_psf, p out_vres,
+            *prisim_csclean_stats stats);
+    ''',
     'prisim_gains.h': '''
         int prisim_gains_eval_spline(p ctx, q nrows, i kx, i ky, p nx, p ny, p kx_off, p ky_off, p c_off, q nknots, p knots, q ncoefs, p coefs,
             q nt, p times, q nchan, p freqs, *p out, *prisim_gains_stats stats);
@@ -739,9 +769,10 @@ def _parse_prototypes(table):
 FUNCTIONS, HEADER_EXPORTS = _parse_prototypes(_PROTOTYPES)
 # the functions of each header (tests and tools import these names)
 (EXPORTS, CLEAN_EXPORTS, SUBBAND_EXPORTS, RUNS_EXPORTS, CLOSURE_EXPORTS, CPDELAY_EXPORTS, CPBINS_EXPORTS, CPDIFF_EXPORTS, CPFT_EXPORTS,
- CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMCLEAN_EXPORTS, MOSAIC_EXPORTS, MOSCLEAN_EXPORTS, GAINS_EXPORTS) = (
+ CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMCLEAN_EXPORTS, MOSAIC_EXPORTS, MOSCLEAN_EXPORTS, CSCLEAN_EXPORTS,
+ GAINS_EXPORTS) = (
     HEADER_EXPORTS['prisim_%s.h' % h] for h in ('hip', 'clean', 'subband', 'runs', 'closure', 'cpdelay', 'cpbins', 'cpdiff', 'cpft', 'cpxps',
-                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imclean', 'mosaic', 'mosclean', 'gains'))
+                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imclean', 'mosaic', 'mosclean', 'csclean', 'gains'))
 
 
 class PrisimHipError(RuntimeError):
@@ -1680,6 +1711,54 @@ class Context(object):
         return {'residual': residual, 'restored': restored, 'comp_pixel': NP.ascontiguousarray(pixel[:, :longest]),
                 'comp_flux': NP.ascontiguousarray(flux[:, :longest]), 'ncomp': ncomp, 'status': status, 'peak0': peak0, 'wsum': wsum,
                 'stats': dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident)}
+
+    # ---- Cotton-Schwab CLEAN of dirty images (include/prisim_csclean.h) ----
+    PrisimCscleanStats = _PrisimCscleanStats
+    PrisimCscleanArgs = _PrisimCscleanArgs
+
+    def clean_image_cs(self, unitvec, grid_shape, rot, pc_dircos, baselines, freqs_hz, cube=None, weights=None, chan_avg=False, aberr_beta=None,
+                       gain=0.1, maxiter=10000, threshold=5e-3, threshold_relative=True, cycle_depth=0.3, cycle_niter=0, max_major=32,
+                       window=None, fwhm_rad=None, route='auto', minor_route='auto', budget_bytes=0, want_psf=False, want_vis=False):
+        """Cotton-Schwab CLEAN of the dirty image of dirty_image(kind='dirty') on the device (prisim_clean_image_cs): minor cycles on
+        one image channel with the shift-invariant beam P of the lattice grid_shape = (ny, nx) (ny * nx = npix, nx fastest), each
+        down to cycle_depth of its first peak or cycle_niter components (0: no cap), and after each a major cycle that takes the new
+        components out of the residual visibilities and images those again, max_major at most.  The geometry, cube, weights, gain,
+        maxiter, threshold, threshold_relative, window, fwhm_rad, route and budget_bytes as clean_image takes them; minor_route:
+        'auto', 'lds' or 'global', where the working image of a minor cycle lives, which no result depends on.  Returns the dict of
+        clean_image -- 'status' may also hold PRISIM_CSCLEAN_MAJOR or _DIVERGED -- with 'ncycles' (nc,) int32, 'cycle_ncomp' int32
+        (nc, most cycles; -1 past a channel's own), 'cycle_peak' (nc, most cycles + 1; NaN past a channel's own), 'psf' (nc, 2 ny - 1,
+        2 nx - 1) with want_psf and 'vres' (nt, nbl, nchan) complex128 with want_vis, else None."""
+        a = self.PrisimCscleanArgs()
+        npix, nbl, nchan, nt, resident, keep = _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube, weights, chan_avg,
+                                                               aberr_beta, route, budget_bytes)
+        nc = 1 if chan_avg else nchan
+        maxiter, win, fw = _clean_fields(a, npix, nc, gain, maxiter, threshold, threshold_relative, window, fwhm_rad, None)
+        ny, nx = (int(n) for n in grid_shape)
+        a.ny, a.nx, a.cycle_depth, a.cycle_niter, a.max_major = ny, nx, float(cycle_depth), int(cycle_niter or 0), int(max_major)
+        a.minor_route = _route_code(minor_route, CSCLEAN_ROUTES)
+        shape = (npix,) if chan_avg else (npix, nchan)
+        rows, cyc = max(maxiter, 0), max(int(max_major), 0)
+        residual = NP.empty(shape, dtype=NP.float64)
+        restored = NP.empty(shape, dtype=NP.float64) if fw is not None else None
+        pixel = NP.full((nc, rows), -1, dtype=NP.int32)
+        flux = NP.zeros((nc, rows), dtype=NP.float64)
+        ncomp, status, ncycles = (NP.empty(nc, dtype=NP.int32) for _ in range(3))
+        peak0, wsum = NP.empty(nc, dtype=NP.float64), NP.empty(nc, dtype=NP.float64)
+        cycle_ncomp = NP.full((nc, cyc), -1, dtype=NP.int32)
+        cycle_peak = NP.full((nc, cyc + 1), NP.nan, dtype=NP.float64)
+        psf = NP.empty((nc, max(2 * ny - 1, 0), max(2 * nx - 1, 0)), dtype=NP.float64) if want_psf else None
+        vres = NP.empty((nt, nbl, nchan), dtype=NP.complex128) if want_vis else None
+        st = self.PrisimCscleanStats()
+        self._call('prisim_clean_image_cs', a=a, out_residual=residual, out_restored=restored, out_comp_pixel=pixel, out_comp_flux=flux,
+                   out_ncomp=ncomp, out_status=status, out_peak0=peak0, out_wsum=wsum, out_ncycles=ncycles, out_cycle_ncomp=cycle_ncomp,
+                   out_cycle_peak=cycle_peak, out_psf=psf, out_vres=vres, stats=st)
+        del keep, win, fw
+        longest, most = (int(ncomp.max()), int(ncycles.max())) if nc else (0, 0)
+        return {'residual': residual, 'restored': restored, 'comp_pixel': NP.ascontiguousarray(pixel[:, :longest]),
+                'comp_flux': NP.ascontiguousarray(flux[:, :longest]), 'ncomp': ncomp, 'status': status, 'peak0': peak0, 'wsum': wsum,
+                'ncycles': ncycles, 'cycle_ncomp': NP.ascontiguousarray(cycle_ncomp[:, :most]),
+                'cycle_peak': NP.ascontiguousarray(cycle_peak[:, :most + 1]), 'psf': psf, 'vres': vres,
+                'stats': dict(_stats_dict(st, route=IMAGING_ROUTES, minor_route=CSCLEAN_ROUTES), resident=resident)}
 
     # ---- CLEAN of the beam-weighted mosaic (include/prisim_mosclean.h) ----
     PrisimMoscleanStats = _PrisimMoscleanStats

@@ -1,6 +1,7 @@
 // dirty_image.h -- the dirty image and the synthesized beam by the direct Fourier sum, as prisim_dirty_image (imaging.hip) runs it chunk
-// by chunk and prisim_clean_image (imclean.hip) once over all pixels for its first residual: the kernels, the one function that
-// enqueues them and the one count of their bytes.  Once per call:
+// by chunk, prisim_clean_image (imclean.hip) once over all pixels for its first residual and prisim_clean_image_cs (csclean.hip) once
+// per major cycle, and over offsets of its own for its minor-cycle beam: the kernels, the one function that enqueues them and the one
+// count of their bytes.  Once per call:
 //   k_img_wsum   W[k] = sum_t sum_b w[t][b][k], one thread per channel, t ascending and b ascending inside t, and k_img_wtot their sum.
 // Per chunk of pixels:
 //   k_img_dirs   dd[t][pixel] = normalise(R_t (u + beta_t)) - s0[t] (imaging_kernels.h).
@@ -113,21 +114,27 @@ inline int enqueue_weight_sums(prisim_ctx* ctx, const DirtyImage& J, hipStream_t
   return PRISIM_OK;
 }
 
-// The pixels of sp behind the weight sums: directions -> sum -> band average.  dd [nt][count]; rows [count][nchan], the image or, with
-// chan_avg, D; avg [count], the band's image (chan_avg only).
-inline int enqueue_dirty(prisim_ctx* ctx, const DirtyImage& J, Span sp, double4* dd, double* rows, double* avg, hipStream_t s) {
-  if (int rc = launch(ctx, k_img_dirs, dim3((unsigned)grid_for(ctx, sp.count * J.nt)), 0, s, J.T->uvec, J.T->frames, sp.first, sp.count, J.nt,
-                      (double4*)nullptr, dd))
-    return rc;
-  const ImgParams P{J.T->cube, J.T->W, J.T->bl, J.T->freqs, dd, J.wsum, J.df, J.nbl, J.nt, sp.count, (int)J.nchan, J.avg ? 0 : 1, rows};
-  const dim3 grid((unsigned)((sp.count + J.block - 1) / J.block), (unsigned)J.ntiles);
+// `count` pixels whose offsets dd [nt][count] are there, behind the weight sums: sum -> band average.  rows [count][nchan], the image or,
+// with chan_avg, D; avg [count], the band's image (chan_avg only).
+inline int enqueue_dirty_sums(prisim_ctx* ctx, const DirtyImage& J, int64_t count, const double4* dd, double* rows, double* avg, hipStream_t s) {
+  const ImgParams P{J.T->cube, J.T->W, J.T->bl, J.T->freqs, dd, J.wsum, J.df, J.nbl, J.nt, count, (int)J.nchan, J.avg ? 0 : 1, rows};
+  const dim3 grid((unsigned)((count + J.block - 1) / J.block), (unsigned)J.ntiles);
   if (int rc = J.stepped ? (J.psf ? launch(ctx, k_img_sum<true, true>, grid, 0, s, P) : launch(ctx, k_img_sum<true, false>, grid, 0, s, P))
                          : (J.psf ? launch(ctx, k_img_sum<false, true>, grid, 0, s, P) : launch(ctx, k_img_sum<false, false>, grid, 0, s, P)))
     return rc;
   if (J.avg)
-    return launch(ctx, k_img_avg, dim3((unsigned)((sp.count + kThreads - 1) / kThreads)), 0, s, (const double*)rows, sp.count, (int)J.nchan,
+    return launch(ctx, k_img_avg, dim3((unsigned)((count + kThreads - 1) / kThreads)), 0, s, (const double*)rows, count, (int)J.nchan,
                   (const double*)J.wtot, avg);
   return PRISIM_OK;
+}
+
+// The pixels of sp behind the weight sums: directions -> sum -> band average.  dd [nt][count]; rows and avg as enqueue_dirty_sums
+// takes them.
+inline int enqueue_dirty(prisim_ctx* ctx, const DirtyImage& J, Span sp, double4* dd, double* rows, double* avg, hipStream_t s) {
+  if (int rc = launch(ctx, k_img_dirs, dim3((unsigned)grid_for(ctx, sp.count * J.nt)), 0, s, J.T->uvec, J.T->frames, sp.first, sp.count, J.nt,
+                      (double4*)nullptr, dd))
+    return rc;
+  return enqueue_dirty_sums(ctx, J, sp.count, dd, rows, avg, s);
 }
 
 // The bytes the kernels of one dirty image of all pixels read and write.  k_img_sum, per workgroup (block of pixels, channel tile) and

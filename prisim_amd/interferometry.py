@@ -2773,14 +2773,16 @@ class ApertureSynthesis(object):
 
     Attributes as in the reference (:9136-9163): ia, f, df, n_acc, lst, phase_center, phase_center_coords, pointing_center,
     pointing_coords, baselines, timestamp, latitude, blxyz, uvw_lambda, uvw, blc, trc, grid_blc, grid_trc, gridu, gridv, gridw,
-    grid_ready; and image_stats, the statistics of the last image(), psf(), clean(), mosaic() or clean_mosaic().
+    grid_ready; and image_stats, the statistics of the last image(), psf(), clean(), mosaic(), clean_mosaic() or
+    clean_cotton_schwab().
 
     Departures from the reference: setUVWgrid is not ported -- its grid comes from GRD.grid_3d, whose source is not part of the
     reference tree, and the direct transform needs no grid; grid_ready stays False.  genUVW with a 'radec' phase centre takes
     HA = LST - RA and the centre's declination, as _pc_dircos and project_baselines do (the reference puts HA = LST and Dec = 0, :9180).
     image(), psf(), clean() (Hogbom's CLEAN of image() with the exact beam, include/prisim_imclean.h), mosaic() (the beam-weighted
     mosaic of the snapshots, horizon mask included: true fluxes where image() gives apparent ones, include/prisim_mosaic.h),
-    clean_mosaic() (CLEAN of that mosaic, include/prisim_mosclean.h) and dircos_grid() are additions.
+    clean_mosaic() (CLEAN of that mosaic, include/prisim_mosclean.h), clean_cotton_schwab() (clean() in major and minor cycles,
+    include/prisim_csclean.h) and dircos_grid() are additions.
     There is no CPU path."""
 
     def __init__(self, interferometer_array=None):
@@ -3046,6 +3048,67 @@ class ApertureSynthesis(object):
                                 window=win, fwhm_rad=fwhm_rad if restore else None, route=route, budget_bytes=int(budget_bytes or 0))
         self.image_stats = dict(r['stats'], wsum=r['wsum'])
         return self._clean_dict(r, npix, nc, chan_avg, restore, threshold, threshold_type, fwhm_rad)
+
+    def clean_cotton_schwab(self, directions, grid_shape, coords='dircos', datakey='noiseless', weights=None, chan_avg=False, epoch=None,
+                            gain=0.1, maxiter=10000, threshold=5e-3, threshold_type='relative', cycle_depth=0.3, cycle_niter=None,
+                            max_major=32, window=None, fwhm=None, restore=True, return_vis=False, route='auto', minor_route='auto',
+                            budget_bytes=None):
+        """Cotton-Schwab CLEAN of image(), on the GPU (include/prisim_csclean.h): clean() pays a full direct Fourier pass for every
+        component; this pays one per major cycle.  A minor cycle cleans one channel's residual in image space with a shift-invariant
+        beam -- the synthesized beam at the offsets of the lattice grid_shape, without the curvature of the grid or aberration -- down
+        to cycle_depth of the cycle's first peak; the major cycle then takes the new components out of the residual visibilities
+        with their exact phases and images those again.  So after every major cycle, and at the end, the residual is the dirty image
+        of the visibilities less those of the components, as clean()'s is.
+
+        directions, coords, datakey, weights, chan_avg, epoch, gain, maxiter, threshold, threshold_type, window, fwhm, restore, route
+        and budget_bytes as clean() takes them.
+        grid_shape   (ny, nx) with ny * nx = npix: the directions as ny rows of nx, nx fastest, as dircos_grid(n, hw) lays them out
+                     with ny = nx = n.  Any list of directions is accepted, because the major cycle is exact for all of them; only
+                     the speed of convergence depends on the list being a lattice, for which the minor cycle's beam is a good one.
+        cycle_depth  in (0, 1): 0.3 is a convention.  A deeper cycle (a smaller value) saves major cycles and trusts the approximate
+                     beam further; with a beam that is several per cent off, 0.1 picks stray pixels where 0.3 does not.
+        cycle_niter  None, or components per channel and minor cycle at most (a positive int).
+        max_major    major cycles at most, 0 .. 65536.  A channel that wants more ends with _abi.PRISIM_CSCLEAN_MAJOR; one whose peak
+                     grew from one cycle to the next with PRISIM_CSCLEAN_DIVERGED, its components kept and its residual still exact.
+        return_vis   True: the residual visibilities are returned.
+        minor_route  'auto', 'lds' or 'global': where the working image of a minor cycle lives; no result depends on it.
+        Returns the dict of clean() and 'cycles': {'count' (nc,) the minor cycles a channel ran, 'ncomp' (nc, most cycles; -1 past a
+        channel's own) the components it held at the end of each, 'peak' (nc, most cycles + 1; NaN past a channel's own) its peak at the
+        start of each and at the test that ended it}, and 'residual_vis' (nbl, nchan, n_acc) complex128 or None.  The entry's
+        statistics, and 'wsum', are left in image_stats."""
+        from . import delay_spectrum as DS                            # (imports this module)
+        threshold = DS._check_clean_args(threshold_type, threshold, gain, maxiter)
+        DS._check_gain_maxiter(gain, maxiter)
+        if not isinstance(cycle_depth, float) or not (0.0 < cycle_depth < 1.0):
+            raise ValueError('cycle_depth must be a float in (0, 1)')
+        if cycle_niter is not None and (not isinstance(cycle_niter, (int, NP.integer)) or isinstance(cycle_niter, bool) or cycle_niter < 1):
+            raise ValueError('cycle_niter must be None or a positive int')
+        if not isinstance(max_major, (int, NP.integer)) or isinstance(max_major, bool) or not (0 <= max_major <= 65536):
+            raise ValueError('max_major must be an int in [0, 65536]')
+        if minor_route not in ('auto', 'lds', 'global'):
+            raise ValueError("minor_route must be 'auto', 'lds' or 'global'")
+        ia = self.ia
+        uv, rot, beta, pc, w, cube = self._prepare('dirty', directions, coords, datakey, weights, epoch, route)
+        npix, nchan = uv.shape[0], ia.channels.size
+        try:
+            ny, nx = (int(n) for n in grid_shape)
+        except (TypeError, ValueError):
+            raise ValueError('grid_shape must be (ny, nx)')
+        if ny < 1 or nx < 1 or ny * nx != npix:
+            raise ValueError('grid_shape must be (ny, nx) with ny * nx the number of directions')
+        nc = 1 if chan_avg else nchan
+        bl = ia._baselines_local()
+        win, fwhm_rad = self._window_and_fwhm(window, fwhm, npix, nc, chan_avg, bl)
+        r = ia._ctx.clean_image_cs(uv, (ny, nx), rot, pc, bl, ia.channels, cube=cube, weights=w, chan_avg=bool(chan_avg), aberr_beta=beta,
+                                   gain=gain, maxiter=maxiter, threshold=threshold, threshold_relative=threshold_type == 'relative',
+                                   cycle_depth=cycle_depth, cycle_niter=int(cycle_niter or 0), max_major=int(max_major), window=win,
+                                   fwhm_rad=fwhm_rad if restore else None, route=route, minor_route=minor_route,
+                                   budget_bytes=int(budget_bytes or 0), want_vis=bool(return_vis))
+        self.image_stats = dict(r['stats'], wsum=r['wsum'])
+        out = self._clean_dict(r, npix, nc, chan_avg, restore, threshold, threshold_type, fwhm_rad)
+        out['cycles'] = {'count': NP.asarray(r['ncycles']), 'ncomp': r['cycle_ncomp'], 'peak': r['cycle_peak']}
+        out['residual_vis'] = NP.ascontiguousarray(NP.transpose(r['vres'], (1, 2, 0))) if return_vis else None
+        return out
 
     def _window_and_fwhm(self, window, fwhm, npix, nc, chan_avg, bl):
         """(the window as booleans or None, the restoring beam (nc,) in radians) of clean() and clean_mosaic(), with their checks"""
