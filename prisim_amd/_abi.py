@@ -544,6 +544,25 @@ def _clean_fields(a, npix, nc, gain, maxiter, threshold, threshold_relative, win
     return maxiter, win, fw
 
 
+def _clean_outputs(npix, nchan, nc, maxiter, chan_avg, restore):
+    """The arrays every CLEAN entry fills, under the names of its out_* arguments: the residual and (with restore) the restored image,
+    (npix,) with chan_avg else (npix, nchan); the lists (nc, maxiter), their unused tail -1 and 0; ncomp, status and peak0 (nc,)."""
+    shape = (npix,) if chan_avg else (npix, nchan)
+    rows = max(maxiter, 0)
+    return {'out_residual': NP.empty(shape, dtype=NP.float64), 'out_restored': NP.empty(shape, dtype=NP.float64) if restore else None,
+            'out_comp_pixel': NP.full((nc, rows), -1, dtype=NP.int32), 'out_comp_flux': NP.zeros((nc, rows), dtype=NP.float64),
+            'out_ncomp': NP.empty(nc, dtype=NP.int32), 'out_status': NP.empty(nc, dtype=NP.int32), 'out_peak0': NP.empty(nc, dtype=NP.float64)}
+
+
+def _clean_result(out):
+    """What every CLEAN entry returns of _clean_outputs: the lists trimmed to the longest."""
+    longest = int(out['out_ncomp'].max()) if out['out_ncomp'].size else 0
+    return {'residual': out['out_residual'], 'restored': out['out_restored'],
+            'comp_pixel': NP.ascontiguousarray(out['out_comp_pixel'][:, :longest]),
+            'comp_flux': NP.ascontiguousarray(out['out_comp_flux'][:, :longest]), 'ncomp': out['out_ncomp'], 'status': out['out_status'],
+            'peak0': out['out_peak0']}
+
+
 def _want_bits(want, bits):
     """The OR of bits[name] over the names of want; KeyError on an unknown name."""
     flag = 0
@@ -1695,22 +1714,12 @@ class Context(object):
                                                             route, budget_bytes)
         nc = 1 if chan_avg else nchan
         maxiter, win, fw = _clean_fields(a, npix, nc, gain, maxiter, threshold, threshold_relative, window, fwhm_rad, poll_every)
-        shape = (npix,) if chan_avg else (npix, nchan)
-        rows = max(maxiter, 0)
-        residual = NP.empty(shape, dtype=NP.float64)
-        restored = NP.empty(shape, dtype=NP.float64) if fw is not None else None
-        pixel = NP.full((nc, rows), -1, dtype=NP.int32)
-        flux = NP.zeros((nc, rows), dtype=NP.float64)
-        ncomp, status = NP.empty(nc, dtype=NP.int32), NP.empty(nc, dtype=NP.int32)
-        peak0, wsum = NP.empty(nc, dtype=NP.float64), NP.empty(nc, dtype=NP.float64)
+        out = _clean_outputs(npix, nchan, nc, maxiter, chan_avg, fw is not None)
+        wsum = NP.empty(nc, dtype=NP.float64)
         st = self.PrisimImcleanStats()
-        self._call('prisim_clean_image', a=a, out_residual=residual, out_restored=restored, out_comp_pixel=pixel, out_comp_flux=flux,
-                   out_ncomp=ncomp, out_status=status, out_peak0=peak0, out_wsum=wsum, stats=st)
+        self._call('prisim_clean_image', a=a, out_wsum=wsum, stats=st, **out)
         del keep, win, fw
-        longest = int(ncomp.max()) if nc else 0
-        return {'residual': residual, 'restored': restored, 'comp_pixel': NP.ascontiguousarray(pixel[:, :longest]),
-                'comp_flux': NP.ascontiguousarray(flux[:, :longest]), 'ncomp': ncomp, 'status': status, 'peak0': peak0, 'wsum': wsum,
-                'stats': dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident)}
+        return dict(_clean_result(out), wsum=wsum, stats=dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident))
 
     # ---- Cotton-Schwab CLEAN of dirty images (include/prisim_csclean.h) ----
     PrisimCscleanStats = _PrisimCscleanStats
@@ -1736,29 +1745,21 @@ class Context(object):
         ny, nx = (int(n) for n in grid_shape)
         a.ny, a.nx, a.cycle_depth, a.cycle_niter, a.max_major = ny, nx, float(cycle_depth), int(cycle_niter or 0), int(max_major)
         a.minor_route = _route_code(minor_route, CSCLEAN_ROUTES)
-        shape = (npix,) if chan_avg else (npix, nchan)
-        rows, cyc = max(maxiter, 0), max(int(max_major), 0)
-        residual = NP.empty(shape, dtype=NP.float64)
-        restored = NP.empty(shape, dtype=NP.float64) if fw is not None else None
-        pixel = NP.full((nc, rows), -1, dtype=NP.int32)
-        flux = NP.zeros((nc, rows), dtype=NP.float64)
-        ncomp, status, ncycles = (NP.empty(nc, dtype=NP.int32) for _ in range(3))
-        peak0, wsum = NP.empty(nc, dtype=NP.float64), NP.empty(nc, dtype=NP.float64)
+        out = _clean_outputs(npix, nchan, nc, maxiter, chan_avg, fw is not None)
+        cyc = max(int(max_major), 0)
+        ncycles, wsum = NP.empty(nc, dtype=NP.int32), NP.empty(nc, dtype=NP.float64)
         cycle_ncomp = NP.full((nc, cyc), -1, dtype=NP.int32)
         cycle_peak = NP.full((nc, cyc + 1), NP.nan, dtype=NP.float64)
         psf = NP.empty((nc, max(2 * ny - 1, 0), max(2 * nx - 1, 0)), dtype=NP.float64) if want_psf else None
         vres = NP.empty((nt, nbl, nchan), dtype=NP.complex128) if want_vis else None
         st = self.PrisimCscleanStats()
-        self._call('prisim_clean_image_cs', a=a, out_residual=residual, out_restored=restored, out_comp_pixel=pixel, out_comp_flux=flux,
-                   out_ncomp=ncomp, out_status=status, out_peak0=peak0, out_wsum=wsum, out_ncycles=ncycles, out_cycle_ncomp=cycle_ncomp,
-                   out_cycle_peak=cycle_peak, out_psf=psf, out_vres=vres, stats=st)
+        self._call('prisim_clean_image_cs', a=a, out_wsum=wsum, out_ncycles=ncycles, out_cycle_ncomp=cycle_ncomp, out_cycle_peak=cycle_peak,
+                   out_psf=psf, out_vres=vres, stats=st, **out)
         del keep, win, fw
-        longest, most = (int(ncomp.max()), int(ncycles.max())) if nc else (0, 0)
-        return {'residual': residual, 'restored': restored, 'comp_pixel': NP.ascontiguousarray(pixel[:, :longest]),
-                'comp_flux': NP.ascontiguousarray(flux[:, :longest]), 'ncomp': ncomp, 'status': status, 'peak0': peak0, 'wsum': wsum,
-                'ncycles': ncycles, 'cycle_ncomp': NP.ascontiguousarray(cycle_ncomp[:, :most]),
-                'cycle_peak': NP.ascontiguousarray(cycle_peak[:, :most + 1]), 'psf': psf, 'vres': vres,
-                'stats': dict(_stats_dict(st, route=IMAGING_ROUTES, minor_route=CSCLEAN_ROUTES), resident=resident)}
+        most = int(ncycles.max()) if nc else 0
+        return dict(_clean_result(out), wsum=wsum, ncycles=ncycles, cycle_ncomp=NP.ascontiguousarray(cycle_ncomp[:, :most]),
+                    cycle_peak=NP.ascontiguousarray(cycle_peak[:, :most + 1]), psf=psf, vres=vres,
+                    stats=dict(_stats_dict(st, route=IMAGING_ROUTES, minor_route=CSCLEAN_ROUTES), resident=resident))
 
     # ---- CLEAN of the beam-weighted mosaic (include/prisim_mosclean.h) ----
     PrisimMoscleanStats = _PrisimMoscleanStats
@@ -1782,24 +1783,15 @@ class Context(object):
         keep_ext = _mosaic_beam_fields(a, nt, beam_kind, diameter_m, beam_pc_dircos, ext, pbmin)
         nc = 1 if chan_avg else nchan
         maxiter, win, fw = _clean_fields(a, npix, nc, gain, maxiter, threshold, threshold_relative, window, fwhm_rad, poll_every)
-        shape = (npix,) if chan_avg else (npix, nchan)
-        rows = max(maxiter, 0)
-        residual, flat, pb_eff = (NP.empty(shape, dtype=NP.float64) for _ in range(3))
-        restored = NP.empty(shape, dtype=NP.float64) if fw is not None else None
+        out = _clean_outputs(npix, nchan, nc, maxiter, chan_avg, fw is not None)
+        flat, pb_eff = NP.empty_like(out['out_residual']), NP.empty_like(out['out_residual'])
         num, den = NP.empty((npix, nchan), dtype=NP.float64), NP.empty((npix, nchan), dtype=NP.float64)
         wsum = NP.empty(nchan, dtype=NP.float64)
-        pixel = NP.full((nc, rows), -1, dtype=NP.int32)
-        flux = NP.zeros((nc, rows), dtype=NP.float64)
-        ncomp, status, peak0 = NP.empty(nc, dtype=NP.int32), NP.empty(nc, dtype=NP.int32), NP.empty(nc, dtype=NP.float64)
         st = self.PrisimMoscleanStats()
-        self._call('prisim_clean_mosaic', a=a, out_residual=residual, out_restored=restored, out_residual_flat=flat, out_pb_eff=pb_eff,
-                   out_num=num, out_den=den, out_wsum=wsum, out_comp_pixel=pixel, out_comp_flux=flux, out_ncomp=ncomp, out_status=status,
-                   out_peak0=peak0, stats=st)
+        self._call('prisim_clean_mosaic', a=a, out_residual_flat=flat, out_pb_eff=pb_eff, out_num=num, out_den=den, out_wsum=wsum, stats=st, **out)
         del keep, keep_ext, win, fw
-        longest = int(ncomp.max()) if nc else 0
-        return {'residual': residual, 'restored': restored, 'residual_flat': flat, 'pb_eff': pb_eff, 'num': num, 'den': den, 'wsum': wsum,
-                'comp_pixel': NP.ascontiguousarray(pixel[:, :longest]), 'comp_flux': NP.ascontiguousarray(flux[:, :longest]), 'ncomp': ncomp,
-                'status': status, 'peak0': peak0, 'stats': dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident)}
+        return dict(_clean_result(out), residual_flat=flat, pb_eff=pb_eff, num=num, den=den, wsum=wsum,
+                    stats=dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident))
 
     # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
     def closure_delay_spectra(self, wts, m, df, phases=None, cube=None, legs=None, conj=None, bpwts=None, freq_wts=None, masks=None,

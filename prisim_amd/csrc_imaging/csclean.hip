@@ -4,9 +4,10 @@
 // kind PSF over the offsets rot_t (di rho + dj kappa) of the half-plane.  What is new here:
 //   k_csclean_offsets the offsets of the half-plane, per snapshot, in the layout k_img_sum reads.
 //   k_csclean_mirror  P [nc][2 ny - 1][2 nx - 1] from the rows of the half-plane: a transposition and the mirror, copies only.
-//   k_csclean_decide  the start of a cycle, one thread per image channel: reduces the partials of k_imclean_peak1 (clean_kernels.h),
-//                     sets P0 and the threshold in cycle 0, records the peak, ends the channel in the order of the header or sets the
-//                     cycle's limit, and counts the channels that go on.
+//   k_csclean_decide  the start of a cycle, one thread per image channel: reduces the partials of k_imclean_peak1, sets P0 and the
+//                     threshold in cycle 0 and counts the channels that go on, each by the piece k_imclean_peak2 calls too
+//                     (clean_kernels.h); between them, its own: it records the peak, ends the channel in the order of the header or
+//                     sets the cycle's limit.
 //   k_csclean_minor   the minor cycle: ONE workgroup per image channel for the whole cycle, which never waits for another (no flags,
 //                     no spinning; its loop is bounded by min(cycle_niter, maxiter - ncomp) on the host's word).  The working image
 //                     lives in LDS (8 B a pixel; gfx950 lets a workgroup hold 160 KiB, 128 x 128 pixels) or in a device scratch row;
@@ -17,7 +18,8 @@
 //                     waves through LDS: two barriers per component.
 //   k_csclean_model   Vres -= the cycle's new components: one thread per (t, b, k), components in list order, every phasor from the
 //                     channel's true frequency (cycles_phasor).  Channels that did not run a cycle are not touched.
-// The peak search before a cycle, the state of the channels, the lists and the restoration are those of clean_kernels.h.
+// The frame of the call (CleanCall), the peak search before a cycle, the state of the channels, the lists and the restoration are those
+// of clean_kernels.h, and so are the buffers of the dirty-image residual (DirtyResidual), as prisim_clean_image (imclean.hip) has them.
 // No atomics, no floating-point reduction whose order depends on the launch.
 #include <hip/hip_runtime.h>
 
@@ -93,20 +95,12 @@ __global__ void __launch_bounds__(kThreads) k_csclean_mirror(const double* __res
 __global__ void __launch_bounds__(kThreads) k_csclean_decide(CleanState S, CycleState X, const Peak* __restrict__ partial, int nc, int64_t nslabs,
                                                              int64_t maxiter, double threshold, int relative, double depth, int cycle,
                                                              int max_major) {
-  __shared__ int sh_n[kThreads];
   int active = 0;
   for (int k = threadIdx.x; k < nc; k += kThreads) {
     X.go[k] = 0;
     if (S.status[k] != 0) continue;
-    Peak m{-1.0, -1, 0};
-    for (int64_t s = 0; s < nslabs; ++s) {
-      const Peak o = partial[s * nc + k];
-      if (peak_beats(o, m)) m = o;
-    }
-    if (cycle == 0) {
-      if (m.p >= 0) S.peak0[k] = m.v;
-      S.thr[k] = relative ? threshold * m.v : threshold;
-    }
+    const Peak m = best_partial(partial, nc, nslabs, k);
+    if (cycle == 0) set_first_peak(S, k, m, threshold, relative);
     X.cycle_peak[(int64_t)k * (max_major + 1) + cycle] = m.p >= 0 ? m.v : __longlong_as_double(0x7ff8000000000000LL);
     const double thr = S.thr[k];
     if (m.p < 0 || !(m.v > thr)) {
@@ -125,16 +119,7 @@ __global__ void __launch_bounds__(kThreads) k_csclean_decide(CleanState S, Cycle
       ++active;
     }
   }
-  sh_n[threadIdx.x] = active;
-  __syncthreads();
-  for (int h = kThreads / 2; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) sh_n[threadIdx.x] += sh_n[threadIdx.x + h];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    S.counts[0] = sh_n[0];
-    if (sh_n[0] > 0) S.counts[1] += 1;
-  }
+  publish_active(S, active);
 }
 
 struct MinorParams {
@@ -287,43 +272,35 @@ int clean_image_cs(prisim_ctx* ctx, const prisim_csclean_args* a, double* out_re
                    double* out_comp_flux, int32_t* out_ncomp, int32_t* out_status, double* out_peak0, double* out_wsum, int32_t* out_ncycles,
                    int32_t* out_cycle_ncomp, double* out_cycle_peak, double* out_psf, double* out_vres, prisim_csclean_stats* stats) {
   if (!ctx) return PRISIM_EINVAL;
-  const WallTime wall0 = wall_now();
-  if (!a) return fail(ctx, PRISIM_EINVAL, "the argument struct is NULL");
-  if (!out_residual) return fail(ctx, PRISIM_EINVAL, "out_residual is NULL");
-  if (!out_comp_pixel || !out_comp_flux || !out_ncomp || !out_status || !out_peak0)
-    return fail(ctx, PRISIM_EINVAL, "out_comp_pixel, out_comp_flux, out_ncomp, out_status or out_peak0 is NULL");
+  // the entry's own host buffers: declared before the frame, whose stream drains before they go.  The results wait in them until the
+  // call is through, as the frame's do
+  std::vector<double> h_psf, h_cyc_peak;
+  std::vector<int32_t> h_ncycles, h_cyc_ncomp;
+  DirtyResidual dr;
+  CleanCall call(ctx, {out_residual, out_restored, out_comp_pixel, out_comp_flux, out_ncomp, out_status, out_peak0}, stats != nullptr);
+  if (int rc = call.check_outputs(a)) return rc;
   if (!out_ncycles || !out_cycle_ncomp || !out_cycle_peak) return fail(ctx, PRISIM_EINVAL, "out_ncycles, out_cycle_ncomp or out_cycle_peak is NULL");
-  const ImgView v = imaging_view(*a);
-  if (int rc = check_args(ctx, v)) return rc;
-  const int64_t npix = a->npix, nbl = a->nbl, nchan = a->nchan, nt = a->nt, maxiter = a->maxiter, ny = a->ny, nx = a->nx;
-  const bool avg = a->chan_avg != 0, restore = out_restored != nullptr;
-  const int64_t nc = avg ? 1 : nchan;
-  if (int rc = check_clean_args(ctx, *a, nc, restore)) return rc;
-  ImgSetup su{};
-  if (int rc = imaging_preamble(ctx, v, su)) return rc;
-  const CscleanPlan cp = csclean_plan(npix, ny, nx, nbl, nchan, nt, avg, maxiter, a->cycle_depth, a->max_major, a->budget_bytes, su.lds_max,
-                                      a->route, su.uniform, a->minor_route);
+  if (int rc = call.check_inputs(*a)) return rc;
+  const ImgView& v = call.v;
+  const int64_t npix = a->npix, nbl = a->nbl, nchan = a->nchan, nt = a->nt, maxiter = a->maxiter, ny = a->ny, nx = a->nx, nc = call.nc;
+  const bool avg = call.avg, restore = call.restore, timed = call.timed;
+  const CscleanPlan cp = csclean_plan(npix, ny, nx, nbl, nchan, nt, avg, maxiter, a->cycle_depth, a->max_major, a->budget_bytes, call.su.lds_max,
+                                      a->route, call.su.uniform, a->minor_route);
   const ImcleanPlan& pl = cp.base;
-  if (cp.refusal)
-    return fail(ctx, PRISIM_EINVAL, std::string(cp.refusal) + " (the resident buffers take " + std::to_string(cp.total) + " B, the workgroup of a minor cycle " +
-                                        std::to_string(cp.minor_lds) + " B of LDS)");
+  if (cp.refusal) return fail(ctx, PRISIM_EINVAL, clean_refusal(cp.refusal, cp.total, "the workgroup of a minor cycle", cp.minor_lds));
   const int max_major = a->max_major;
-  const bool in_lds = cp.minor_route == kCscleanLds, timed = stats != nullptr;
+  const bool in_lds = cp.minor_route == kCscleanLds;
   const int64_t half = cp.psf_half, full = cp.psf_full, ncube = nt * nbl * nchan;
   const Lattice lat = lattice_of(a->unitvec, ny, nx);
 
-  // the results wait here until the call is through: nothing reaches the caller's arrays from a call that fails
-  std::vector<double> h_res((size_t)(npix * nc)), h_rest(restore ? (size_t)(npix * nc) : 0), h_wsum((size_t)nc), h_psf(out_psf ? (size_t)(nc * full) : 0);
-  std::vector<int32_t> h_ncycles((size_t)nc), h_cyc_ncomp;
-  std::vector<double> h_cyc_peak;
-  CleanLists lists;
-  ImgTables T;
-
-  Work wk;
+  h_psf.resize(out_psf ? (size_t)(nc * full) : 0);
+  h_ncycles.resize((size_t)nc);
+  if (int rc = call.open(pl)) return rc;
+  hipStream_t s0 = call.s0;
+  Dev& dev = call.wk.dev;
+  ImgTables& T = call.T;
+  const CleanState& S = call.S;
   BatchEvents be;
-  Streams& st = wk.st;
-  if (int rc = st.create(ctx, 1, false)) return rc;
-  hipStream_t s0 = st.s[0];
   if (timed)
     if (int rc = be.create(ctx, 12)) return rc;
   auto mark = [&](int i) -> int {
@@ -332,50 +309,28 @@ int clean_image_cs(prisim_ctx* ctx, const prisim_csclean_args* a, double* out_re
   };
   auto span_ms = [&](int i, int j) { return timed ? elapsed_ms(be.ev[(size_t)i], be.ev[(size_t)j]) : 0.0; };
 
-  if (int rc = upload_tables(ctx, wk.dev, v, s0, T)) return rc;
-  int64_t upload = T.bytes;
-  double* d_fwhm = nullptr;
-  uint8_t* d_window = nullptr;
-  if (a->window) {
-    DEV_UPLOAD(ctx, wk.dev, d_window, a->window, (size_t)npix, s0);
-    upload += npix;
-  }
-  if (restore) {
-    DEV_UPLOAD(ctx, wk.dev, d_fwhm, a->fwhm_rad, (size_t)nc, s0);
-    upload += nc * 8;
-  }
-
   // the resident buffers of the plan
-  double4 *d_dd = nullptr, *d_pdd = nullptr;
-  double *d_R = nullptr, *d_D = nullptr, *d_wsum = nullptr, *d_wtot = nullptr, *d_P = nullptr, *d_prow = nullptr, *d_pavg = nullptr, *d_minor = nullptr;
+  if (int rc = dr.alloc(call)) return rc;
+  double4* d_pdd = nullptr;
+  double *d_P = nullptr, *d_prow = nullptr, *d_pavg = nullptr, *d_minor = nullptr;
   double2* d_vres = nullptr;
-  Peak* d_partial = nullptr;
-  CleanState S{};
   CycleState X{};
-  DEV_ALLOC(ctx, wk.dev, d_dd, pl.dd_bytes);
-  DEV_ALLOC(ctx, wk.dev, d_R, pl.resid_bytes);
-  if (avg) DEV_ALLOC(ctx, wk.dev, d_D, pl.scratch_bytes);
-  DEV_ALLOC(ctx, wk.dev, d_partial, pl.partial_bytes);
-  DEV_ALLOC(ctx, wk.dev, d_wsum, nchan * 8);
-  DEV_ALLOC(ctx, wk.dev, d_wtot, 8);
-  if (int rc = alloc_clean_state(ctx, wk.dev, S, nc, maxiter)) return rc;
-  DEV_ALLOC(ctx, wk.dev, X.go, nc * 4);
-  DEV_ALLOC(ctx, wk.dev, X.first, nc * 4);
-  DEV_ALLOC(ctx, wk.dev, X.ncycles, nc * 4);
-  DEV_ALLOC(ctx, wk.dev, X.prev, nc * 8);
-  DEV_ALLOC(ctx, wk.dev, X.limit, nc * 8);
-  DEV_ALLOC(ctx, wk.dev, X.cycle_ncomp, nc * max_major * 4);
-  DEV_ALLOC(ctx, wk.dev, X.cycle_peak, nc * (max_major + 1) * 8);
-  DEV_ALLOC(ctx, wk.dev, d_P, cp.psf_bytes);
-  DEV_ALLOC(ctx, wk.dev, d_pdd, nt * half * 32);
-  DEV_ALLOC(ctx, wk.dev, d_prow, half * nchan * 8);
-  if (avg) DEV_ALLOC(ctx, wk.dev, d_pavg, half * 8);
-  if (!in_lds) DEV_ALLOC(ctx, wk.dev, d_minor, cp.minor_bytes);
+  DEV_ALLOC(ctx, dev, X.go, nc * 4);
+  DEV_ALLOC(ctx, dev, X.first, nc * 4);
+  DEV_ALLOC(ctx, dev, X.ncycles, nc * 4);
+  DEV_ALLOC(ctx, dev, X.prev, nc * 8);
+  DEV_ALLOC(ctx, dev, X.limit, nc * 8);
+  DEV_ALLOC(ctx, dev, X.cycle_ncomp, nc * max_major * 4);
+  DEV_ALLOC(ctx, dev, X.cycle_peak, nc * (max_major + 1) * 8);
+  DEV_ALLOC(ctx, dev, d_P, cp.psf_bytes);
+  DEV_ALLOC(ctx, dev, d_pdd, nt * half * 32);
+  DEV_ALLOC(ctx, dev, d_prow, half * nchan * 8);
+  if (avg) DEV_ALLOC(ctx, dev, d_pavg, half * 8);
+  if (!in_lds) DEV_ALLOC(ctx, dev, d_minor, cp.minor_bytes);
 
-  // Vres: the uploaded cube is the call's own; the resident one is copied behind whatever the context's stream still writes into it
+  // Vres: the uploaded cube is the call's own; the resident one is copied, behind what the context's stream wrote into it (open)
   if (v.resident()) {
-    DEV_ALLOC(ctx, wk.dev, d_vres, cp.vres_bytes);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    DEV_ALLOC(ctx, dev, d_vres, cp.vres_bytes);
     HIPCHK(ctx, hipMemcpyAsync(d_vres, ctx->cube.p, (size_t)ncube * 16, hipMemcpyDeviceToDevice, s0));
     T.cube = d_vres;
   } else {
@@ -385,10 +340,10 @@ int clean_image_cs(prisim_ctx* ctx, const prisim_csclean_args* a, double* out_re
     if (int rc = allow_lds(ctx, k_csclean_minor<true>, npix * 8)) return rc;
 
   // ---- the weight sums, P, the first dirty image.  Events: [0] sums [1] P [2] dirty image [3]
-  const DirtyImage job = dirty_image_of(v, T, su.df, pl, d_wsum, d_wtot);
+  const DirtyImage job = dirty_image_of(v, T, call.su.df, pl, dr.wsum, dr.wtot);
   ImgView vp = v;
   vp.kind = PRISIM_IMAGE_PSF;
-  const DirtyImage beam = dirty_image_of(vp, T, su.df, pl, d_wsum, d_wtot);
+  const DirtyImage beam = dirty_image_of(vp, T, call.su.df, pl, dr.wsum, dr.wtot);
   if (int rc = mark(0)) return rc;
   if (int rc = enqueue_weight_sums(ctx, job, s0)) return rc;
   if (int rc = mark(1)) return rc;
@@ -398,35 +353,31 @@ int clean_image_cs(prisim_ctx* ctx, const prisim_csclean_args* a, double* out_re
                       avg ? (int64_t)0 : nchan, (int)nc, full, full - half, d_P))
     return rc;
   if (int rc = mark(2)) return rc;
-  if (int rc = enqueue_dirty(ctx, job, Span{0, npix}, d_dd, avg ? d_D : d_R, d_R, s0)) return rc;
-  const dim3 chgrid((unsigned)((nc + kThreads - 1) / kThreads));
-  if (int rc = launch(ctx, k_imclean_init, chgrid, 0, s0, S, (const double*)(avg ? d_wtot : d_wsum), (int)nc)) return rc;
-  if (int rc = launch(ctx, k_csclean_init, chgrid, 0, s0, X, (int)nc)) return rc;
+  if (int rc = enqueue_dirty(ctx, job, Span{0, npix}, dr.dd, dr.rows(), dr.R, s0)) return rc;
+  if (int rc = call.init(dr.norm())) return rc;
+  if (int rc = launch(ctx, k_csclean_init, dim3((unsigned)((nc + kThreads - 1) / kThreads)), 0, s0, X, (int)nc)) return rc;
   if (int rc = mark(3)) return rc;
 
   // ---- the cycles: max_major + 1 starts at most, whatever the device says.  Events of a cycle: [4] search and decision [5], then
   // behind the host's read [6] minor [7] model [8] dirty image [9]
   MinorParams MP{};
-  MP.R = d_R; MP.P = d_P; MP.window = d_window; MP.scratch = d_minor;
+  MP.R = dr.R; MP.P = d_P; MP.window = call.d_window; MP.scratch = d_minor;
   MP.S = S; MP.X = X;
   MP.maxiter = maxiter; MP.cycle_niter = a->cycle_niter; MP.gain = a->gain;
   MP.npix = (int)npix; MP.nc = (int)nc; MP.ny = (int)ny; MP.nx = (int)nx; MP.max_major = max_major;
   ModelParams MM{};
-  MM.V = d_vres; MM.bl = T.bl; MM.freqs = T.freqs; MM.dd = d_dd;
+  MM.V = d_vres; MM.bl = T.bl; MM.freqs = T.freqs; MM.dd = dr.dd;
   MM.S = S; MM.X = X;
   MM.nt = nt; MM.nbl = nbl; MM.npix = npix; MM.maxiter = maxiter;
   MM.nchan = (int)nchan; MM.avg = avg ? 1 : 0;
-  const dim3 peakgrid((unsigned)pl.nslabs, (unsigned)pl.peak_cgroups);
   double dirty_ms = 0.0, peak_ms = 0.0, minor_ms = 0.0, model_ms = 0.0;
   int64_t active[2] = {0, 0}, polls = 0, cycles = 0;   // what a poll reads: the channels that go on, the cycles in which any did
   for (int c = 0; c <= max_major; ++c) {
     if (int rc = mark(4)) return rc;
-    if (int rc = launch(ctx, k_imclean_peak1, peakgrid, 0, s0, (const double*)d_R, (const uint8_t*)d_window, (const int32_t*)S.status, npix, (int)nc,
-                        pl.slab, (int)pl.peak_cx, d_partial))
+    if (int rc = call.search(dr.R)) return rc;
+    if (int rc = launch(ctx, k_csclean_decide, dim3(1), 0, s0, S, X, (const Peak*)call.d_partial, (int)nc, pl.nslabs, maxiter, a->threshold,
+                        (int)a->threshold_relative, a->cycle_depth, c, max_major))
       return rc;
-    hipLaunchKernelGGL(k_csclean_decide, dim3(1), dim3(kThreads), 0, s0, S, X, (const Peak*)d_partial, (int)nc, pl.nslabs, maxiter, a->threshold,
-                       (int)a->threshold_relative, a->cycle_depth, c, max_major);
-    HIPCHK(ctx, hipGetLastError());
     if (int rc = mark(5)) return rc;
     HIPCHK(ctx, hipMemcpyAsync(active, S.counts, 16, hipMemcpyDeviceToHost, s0));
     HIPCHK(ctx, hipStreamSynchronize(s0));
@@ -447,14 +398,12 @@ int clean_image_cs(prisim_ctx* ctx, const prisim_csclean_args* a, double* out_re
     if (int rc = mark(7)) return rc;
     if (int rc = launch(ctx, k_csclean_model, dim3((unsigned)grid_for(ctx, ncube)), 0, s0, MM)) return rc;
     if (int rc = mark(8)) return rc;
-    if (int rc = enqueue_dirty(ctx, job, Span{0, npix}, d_dd, avg ? d_D : d_R, d_R, s0)) return rc;
+    if (int rc = enqueue_dirty(ctx, job, Span{0, npix}, dr.dd, dr.rows(), dr.R, s0)) return rc;
     if (int rc = mark(9)) return rc;
   }
 
   // ---- the results
-  HIPCHK(ctx, hipMemcpyAsync(h_res.data(), d_R, h_res.size() * 8, hipMemcpyDeviceToHost, s0));
-  if (int rc = lists.enqueue(ctx, S, nc, maxiter, s0)) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(h_wsum.data(), avg ? d_wtot : d_wsum, (size_t)nc * 8, hipMemcpyDeviceToHost, s0));
+  if (int rc = dr.download_norm(call)) return rc;
   HIPCHK(ctx, hipMemcpyAsync(h_ncycles.data(), X.ncycles, (size_t)nc * 4, hipMemcpyDeviceToHost, s0));
   // of the cycle tables, the columns that any channel filled
   h_cyc_ncomp.resize((size_t)(nc * cycles));
@@ -465,16 +414,9 @@ int clean_image_cs(prisim_ctx* ctx, const prisim_csclean_args* a, double* out_re
   HIPCHK(ctx, copy_rows(h_cyc_peak.data(), (size_t)(cycles + 1) * 8, X.cycle_peak, (size_t)(max_major + 1) * 8, (size_t)(cycles + 1) * 8, (size_t)nc,
                         hipMemcpyDeviceToHost, s0));
   if (out_psf) HIPCHK(ctx, hipMemcpyAsync(h_psf.data(), d_P, h_psf.size() * 8, hipMemcpyDeviceToHost, s0));
-  if (restore) {
-    if (int rc = mark(10)) return rc;
-    if (int rc = launch(ctx, k_imclean_restore, dim3((unsigned)grid_for(ctx, npix * nc)), 0, s0, d_R, T.uvec, S, (const double*)d_fwhm, npix, (int)nc,
-                        maxiter))
-      return rc;
-    if (int rc = mark(11)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(h_rest.data(), d_R, h_rest.size() * 8, hipMemcpyDeviceToHost, s0));
-  }
-  HIPCHK(ctx, hipStreamSynchronize(s0));
-  if (int rc = lists.lists(ctx, S, s0)) return rc;
+  if (int rc = call.close(dr.R, timed ? be.ev[10] : nullptr, timed ? be.ev[11] : nullptr)) return rc;
+  if (int rc = call.gather()) return rc;
+  const CleanLists& lists = call.lists;
   for (int64_t k = 0; k < nc; ++k)
     if (h_ncycles[(size_t)k] < 0 || h_ncycles[(size_t)k] > cycles) return fail(ctx, PRISIM_EINTERNAL, "a cycle count beyond the cycles run");
   // the residual visibilities go straight to the caller, as the last thing that can fail
@@ -483,10 +425,8 @@ int clean_image_cs(prisim_ctx* ctx, const prisim_csclean_args* a, double* out_re
     HIPCHK(ctx, hipStreamSynchronize(s0));
   }
 
-  std::memcpy(out_residual, h_res.data(), h_res.size() * 8);
-  if (restore) std::memcpy(out_restored, h_rest.data(), h_rest.size() * 8);
-  lists.write(out_comp_pixel, out_comp_flux, out_ncomp, out_status, out_peak0);
-  if (out_wsum) std::memcpy(out_wsum, h_wsum.data(), (size_t)nc * 8);
+  call.write();
+  dr.write_norm(out_wsum);
   std::memcpy(out_ncycles, h_ncycles.data(), (size_t)nc * 4);
   for (int64_t k = 0; k < nc; ++k) {
     const size_t n = (size_t)h_ncycles[(size_t)k];
@@ -497,7 +437,7 @@ int clean_image_cs(prisim_ctx* ctx, const prisim_csclean_args* a, double* out_re
   if (stats) {
     const double psf_ms = span_ms(1, 2), restore_ms = restore ? span_ms(10, 11) : 0.0;
     dirty_ms += span_ms(0, 1) + span_ms(2, 3);
-    stats->wall_ms = wall_ms_since(wall0);
+    call.common_stats(stats, cp.total);
     stats->kernel_ms = psf_ms + dirty_ms + peak_ms + minor_ms + model_ms + restore_ms;
     stats->psf_ms = psf_ms;
     stats->dirty_ms = dirty_ms;
@@ -506,16 +446,12 @@ int clean_image_cs(prisim_ctx* ctx, const prisim_csclean_args* a, double* out_re
     stats->model_ms = model_ms;
     stats->restore_ms = restore_ms;
     stats->cycles = cycles;
-    stats->components = lists.components;
     stats->polls = polls;
     stats->psf_offsets = half;
-    stats->upload_bytes = upload;
     stats->download_bytes = npix * nc * 8 * (restore ? 2 : 1) + nc * 36 + nc * lists.longest * 12 + nc * (2 * cycles + 1) * 12 + polls * 16 +
                             (out_psf ? nc * full * 8 : 0) + (out_vres ? ncube * 16 : 0);
-    stats->device_bytes = cp.total;
     stats->minor_route = cp.minor_route;
     stats->minor_lds_bytes = (int32_t)cp.minor_lds;
-    plan_stats(stats, v, pl, 1);
   }
   return PRISIM_OK;
 }

@@ -108,7 +108,7 @@ __device__ __forceinline__ void img_rows(int nb, const double2* sh_v, const doub
   }
 }
 
-// The tile pass: the hot loop of k_img_sum (dirty_image.h), k_mos_sum (mosaic.hip) and k_imclean_update (imclean.hip), whose bits
+// The tile pass: the hot loop of k_img_sum (dirty_image.h), k_mos_sum (mosaic_kernels.h) and k_clean_update (clean_update.h), whose bits
 // agree because this is the one statement of it.  A workgroup owns 256 pixels (one per thread) and a tile of CT = 32 channels from k0
 // on; a thread keeps 32 fp64 accumulators and the phasor, nothing else per lane.  For snapshot t, NB = 32 baselines at a time, the
 // workgroup stages the operand of the tile in sh_v and b / c in sh_b; every lane then reads the same LDS address in img_rows (a
@@ -120,7 +120,7 @@ __device__ __forceinline__ void img_rows(int nb, const double2* sh_v, const doub
 // stage(live, t, b, c, k) gives the staged element of baseline b and channel k = k0 + c: the (w Re V, w Im V) of the dirty image, (w, 0)
 // of the beam, or what CLEAN subtracts, and zero where it has nothing to add: past the band, and wherever the row is not live, that is
 // past the pass's last baseline, where it must not read anything by b.  (It is told so and not skipped, so that what it reads of its
-// channel alone is read once per thread and pass, ahead of the test, as CLEAN's flux is: skipping costs k_imclean_update<STEPPED> half
+// channel alone is read once per thread and pass, ahead of the test, as CLEAN's flux is: skipping costs k_clean_update<STEPPED, false> half
 // a percent.)  The caller writes sh_f (and whatever else its stage reads from LDS) before the first pass without a barrier
 // of its own: the first barrier here covers it.  The terms of a (pixel, channel) are added by one thread, b ascending, and the caller
 // passes its snapshots ascending: no atomics, no split of the sum over workgroups, so the bits do not depend on chunks or streams.  The

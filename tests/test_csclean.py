@@ -46,7 +46,16 @@ def test_export_is_in_the_library_and_outside_the_core_abi():
     src = open(os.path.join(ROOT, 'prisim_amd', 'csrc_imaging', 'csclean.hip')).read()
     # the dirty images and the beam are those of prisim_dirty_image, called and not restated; the restoration and the peak search are shared
     assert '#include "dirty_image.h"' in src and '#include "clean_kernels.h"' in src and 'k_img_sum<' not in src and 'img_tile_pass' not in src
-    assert src.count('enqueue_dirty(') == 2 and src.count('enqueue_dirty_sums(') == 1 and 'k_imclean_restore' in src and 'k_imclean_peak1' in src
+    assert src.count('enqueue_dirty(') == 2 and src.count('enqueue_dirty_sums(') == 1 and '.search(' in src and '.close(' in src
+    # ... through the frame of clean_kernels.h: their launches are written there alone, and the decision kernel calls the pieces of its own
+    folder = os.path.join(ROOT, 'prisim_amd', 'csrc_imaging')
+    for name in ('k_imclean_peak1', 'k_imclean_restore', 'k_imclean_init'):
+        assert [f for f in sorted(os.listdir(folder)) if 'launch(ctx, ' + name in open(os.path.join(folder, f)).read()] == ['clean_kernels.h'], name
+        assert 'hipLaunchKernelGGL(' + name not in src
+    shared = open(os.path.join(folder, 'clean_kernels.h')).read()
+    for name in ('Peak best_partial(', 'void set_first_peak(', 'void publish_active('):
+        assert shared.count('__device__ __forceinline__ ' + name) == 1 and src.count(name.split()[1]) == 1 and shared.count(name.split()[1]) == 2, name
+    assert 'sh_n' not in src and 'S.counts[0] =' not in src and 'partial[s * nc + k]' not in src and 'DirtyResidual ' in src
     # a minor cycle waits for nobody: no flags, no spinning
     assert 'while' not in src and 'volatile' not in src
 

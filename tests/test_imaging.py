@@ -46,6 +46,10 @@ def test_export_is_in_the_library_and_outside_the_core_abi():
     # the hot loop of the three entries is stated once: the two barriers of the staging loop are in one file, which the others call
     assert [name for name, txt in srcs.items() if '__syncthreads();' in txt and 'sh_b[tid] =' in txt] == ['imaging_kernels.h']
     assert srcs['imaging_kernels.h'].count('__syncthreads();') == 2 and srcs['dirty_image.h'].count('img_tile_pass<STEPPED, PSF>(') == 1
+    # ... and it has three callers, each with one set of accumulators: the dirty image, the mosaic's sum and the one update of the CLEANs
+    assert sorted(name for name, txt in srcs.items() if 'double acc[CT];' in txt) == ['clean_update.h', 'dirty_image.h', 'mosaic_kernels.h']
+    assert all(srcs[name].count('double acc[CT];') == 1 and srcs[name].count('img_tile_pass<STEPPED, ') == 1
+               for name in ('clean_update.h', 'dirty_image.h', 'mosaic_kernels.h'))
     assert '#include "dirty_image.h"' in srcs['imaging.hip'] and 'enqueue_dirty(' in srcs['imaging.hip'] and '<<<' not in srcs['imaging.hip']
     header = open(os.path.join(ROOT, 'include', 'prisim_imaging.h')).read()
     for name in ('prisim_hip.h', 'prisim_hip_last_error', 'prisim_hip_set_array'):

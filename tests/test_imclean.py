@@ -44,7 +44,11 @@ def test_export_is_in_the_library_and_outside_the_core_abi():
     # the dirty image of both entries is one set of kernels, enqueued by one function; the update's hot loop is that of the dirty image
     assert '#include "dirty_image.h"' in open(os.path.join(ROOT, 'prisim_amd', 'csrc_imaging', 'imaging.hip')).read()
     assert 'enqueue_dirty(' in src and 'k_img_sum<' not in src and 'prisim_imaging_args ia' not in src
-    assert 'img_tile_pass<STEPPED, false>(' in src and 'img_rows' not in src and 'sh_b[tid] =' not in src
+    # ... in the one update kernel that this entry and the mosaic's CLEAN launch, which is not restated here
+    upd = open(os.path.join(ROOT, 'prisim_amd', 'csrc_imaging', 'clean_update.h')).read()
+    assert 'img_tile_pass<STEPPED, false>(' in upd and 'img_rows' not in upd and 'sh_b[tid] =' not in upd and 'atomic' not in upd.replace('No atomics', '')
+    assert '#include "clean_update.h"' in src and 'enqueue_clean_update<false>(' in src and 'k_imclean_avg_sub(' in src
+    assert 'img_tile_pass' not in src and 'img_rows' not in src and 'sh_b[tid] =' not in src and 'double acc' not in src
 
 
 def test_plan_header_under_the_sanitizers(tmp_path):

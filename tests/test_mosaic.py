@@ -45,6 +45,10 @@ def test_export_is_in_the_library_and_outside_the_core_abi():
     src = open(os.path.join(ROOT, 'prisim_amd', 'csrc_imaging', 'mosaic.hip')).read()
     assert 'atomic' not in src.replace('No atomics', '') and 'fma(' in src
     assert 'img_tile_pass<STEPPED, false>(' in src and 'launch_beam_flux(' in src and 'beam_flux_body' not in src      # called, not restated
+    # ... by k_mos_sum, once, in the header that this entry and the mosaic's CLEAN include; the CLEAN's own call of it is the shared update's
+    folder = os.path.join(ROOT, 'prisim_amd', 'csrc_imaging')
+    assert open(os.path.join(folder, 'mosaic_kernels.h')).read().count('img_tile_pass<STEPPED, false>(') == 1 and '#include "mosaic_kernels.h"' in src
+    assert 'img_tile_pass' not in open(os.path.join(folder, 'mosclean.hip')).read()
     assert 'img_rows' not in src and 'sh_b[tid] =' not in src and 'prisim_imaging_args ia' not in src and 'k_mos_dirs' not in src
     assert '#include "imaging_kernels.h"' in src and 'dirty_image.h"' not in src and 'Wunused' not in src      # it compiles what it launches
     ant = open(os.path.join(ROOT, 'prisim_amd', 'csrc_antpower', 'antpower.hip')).read()

@@ -59,10 +59,37 @@ def test_export_is_in_the_library_and_outside_the_core_abi():
                  'void __launch_bounds__(kThreads) k_imclean_peak1(', 'void __launch_bounds__(kThreads) k_imclean_peak2(',
                  'void __launch_bounds__(kThreads) k_imclean_restore(', 'hipMemcpyAsync(counts, S.counts'):
         assert [f for f, txt in src.items() if name in txt] == ['clean_kernels.h'], name
-    assert 'img_tile_pass<STEPPED, false>(' in new and 'img_rows' not in new and 'cycles_phasor(' in new and 'enqueue_mos_sum(' in new
-    assert 'enqueue_mos_beam(' in new and 'fill_beam(' not in new and 'check_mosaic_beam(' in new and 'check_clean_args(' in new
-    assert 'k_imclean_peak2<MosaicFlux>' in new and 'k_imclean_peak2<ResidualFlux>' in src['imclean.hip']
-    assert new.count('double acc[CT];') == 1                          # one set of accumulators
+    # the update is one kernel for this entry and prisim_clean_image: its accumulators, its tile pass and its operand's phasor are
+    # written in one file of the directory, besides the dirty image, the mosaic's sum and the model of the Cotton-Schwab cycles
+    upd = src['clean_update.h']
+    assert upd.count('double acc[CT];') == 1 and upd.count('img_tile_pass<STEPPED, false>(') == 1 and upd.count('cycles_phasor(') == 1       # one set of accumulators
+    assert sorted(f for f, txt in src.items() if 'double acc[CT];' in txt) == ['clean_update.h', 'dirty_image.h', 'mosaic_kernels.h']
+    assert sorted(f for f, txt in src.items() if 'img_tile_pass<STEPPED, false>(' in txt.replace('img_tile_pass<STEPPED, false>(...)', '')) == [
+        'clean_update.h', 'mosaic_kernels.h']
+    assert sorted(f for f, txt in src.items() if 'cycles_phasor(' in txt) == ['clean_update.h', 'csclean.hip', 'imaging_kernels.h']
+    assert 'template <bool STEPPED, bool MOSAIC>' in upd and 'img_rows' not in upd
+    for entry in (new, src['imclean.hip']):
+        assert 'img_tile_pass' not in entry and 'sh_b[tid] =' not in entry and 'img_rows' not in entry and 'double acc' not in entry
+    assert 'enqueue_clean_update<true>(' in new and 'enqueue_clean_update<false>(' in src['imclean.hip'] and 'enqueue_mos_sum(' in new
+    # the frame of a call is one: its checks, the launches of the peak search, of the decision and of the restoration are written once
+    assert 'enqueue_mos_beam(' in new and 'fill_beam(' not in new and 'check_mosaic_beam(' in new
+    for name in ('check_clean_args(ctx', 'launch(ctx, k_imclean_init', 'launch(ctx, k_imclean_peak1', 'launch(ctx, k_imclean_peak2<', 'launch(ctx, k_imclean_restore',
+                 'alloc_clean_state(ctx', 'DEV_UPLOAD(ctx, wk.dev, d_fwhm', 'lists.enqueue(', 'lists.write(', 'out_status or out_peak0 is NULL'):
+        assert [f for f, txt in src.items() if name in txt.replace('inline int ' + name, '')] == ['clean_kernels.h'], name
+    assert not [f for f, txt in src.items() if 'hipLaunchKernelGGL(k_imclean' in txt]
+    shared = src['clean_kernels.h']
+    for entry in (new, src['imclean.hip'], src['csclean.hip']):
+        for step in ('.check_outputs(', '.check_inputs(', '.open(', '.search(', '.close(', '.gather(', '.write(', '.common_stats(', 'clean_refusal('):
+            assert step in entry, step
+        # the stream drains when the frame goes: the host buffers a copy may still be filling are declared before it, so they go after it
+        body = entry[entry.index('  CleanCall '):entry.index('extern "C"')]
+        for kind in ('std::vector<double>', 'std::vector<int32_t>', 'DirtyResidual ', 'CleanLoop '):
+            assert kind not in body, kind
+    frame = shared[shared.index('struct CleanCall {'):shared.index('  CleanCall(prisim_ctx*')]
+    assert all(frame.index(member) < frame.index('Work wk;') for member in ('ImgTables T;', 'CleanLists lists;', 'h_res, h_rest;'))
+    assert frame.rstrip().splitlines()[-1].lstrip().startswith('Work wk;')          # the last member
+    assert 'struct MosaicFlux' in new and 'MosaicFlux' not in src['imclean.hip'] and 'ResidualFlux' in src['imclean.hip']
+    assert '.decide(' in new and '.decide(' in src['imclean.hip'] and '.decide(' not in src['csclean.hip']
     assert (_abi.PRISIM_IMCLEAN_THRESHOLD, _abi.PRISIM_IMCLEAN_MAXITER, _abi.PRISIM_IMCLEAN_DEAD) == (QK.THRESHOLD, QK.MAXITER, QK.DEAD)
     # an add-on: one name in the Makefile, nothing under csrc/
     mk = open(os.path.join(ROOT, 'prisim_amd', 'csrc', 'Makefile')).read()

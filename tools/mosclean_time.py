@@ -4,9 +4,11 @@ seeded cube held in the context's resident slots, dircos_grid(64, 0.5) turning b
 14 m beam at the zenith, no weights, the stepped route, gain 0.1, maxiter 10, absolute threshold 0; one small warm-up call each, then
 --calls calls each, alternated; minimum, median and maximum.
 
-With --entries the process runs Context.mosaic_image and Context.clean_image alone, once each behind a warm-up, and prints their
-kernel_ms and a SHA-1 of their outputs: run from two trees (--root), it shows that the entries whose kernels moved into shared headers
-give the same bits and take the same time.  Prints one JSON line and, with --out, writes it there."""
+With --entries the process runs Context.mosaic_image, clean_image (one snapshot, maxiter 3, restored), clean_mosaic (maxiter 3, restored,
+every optional output) and clean_image_cs (one snapshot, cycle_niter 2, max_major 2, with the beam and the residual visibilities)
+alone, once each behind a warm-up, and prints their kernel_ms, the phase times of the CLEANs and a SHA-1 over every array each
+returns: run from two trees (--root), it shows that the entries whose kernels moved into shared headers give the same bits and take
+the same time.  Prints one JSON line and, with --out, writes it there."""
 import argparse
 import hashlib
 import json
@@ -26,7 +28,7 @@ def main():
     ap.add_argument('--calls', type=int, default=3)
     ap.add_argument('--maxiter', type=int, default=10)
     ap.add_argument('--budget', type=int, default=2 << 30, help='budget_bytes: enough for one resident image')
-    ap.add_argument('--entries', action='store_true', help='mosaic_image and clean_image alone: kernel_ms and a hash of the outputs')
+    ap.add_argument('--entries', action='store_true', help='mosaic_image and the three CLEAN entries alone: their times and a hash of the outputs')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
@@ -55,6 +57,12 @@ def main():
             h.update(NP.ascontiguousarray(x).tobytes())
         return h.hexdigest()
 
+    def entry(r):
+        """Of a CLEAN entry's dict: kernel_ms with the phase times, and the hash over every array it returned, by name"""
+        row = {k: v for k, v in r['stats'].items() if k.endswith('_ms') and k != 'wall_ms'}
+        row['sha1'] = digest(*[r[k] for k in sorted(r) if isinstance(r[k], NP.ndarray)])
+        return row
+
     with _abi.Context(0) as ctx:
         out['device'] = ctx.device_info()
         ctx.set_array(bl, freqs, nt_max=nt)
@@ -72,8 +80,16 @@ def main():
             out['mosaic_image'] = {'kernel_ms': st['kernel_ms'], 'sha1': digest(mosaic, num, den, wsum, st['pb_eff'])}
             img(small)
             r = img(grid)
-            out['clean_image'] = {'kernel_ms': r['stats']['kernel_ms'], 'update_ms': r['stats']['update_ms'], 'dirty_ms': r['stats']['dirty_ms'],
-                                  'sha1': digest(r['residual'], r['restored'], r['comp_pixel'], r['comp_flux'], r['ncomp'], r['status'], r['peak0'])}
+            out['clean_image'] = entry(r)
+            cln = lambda g: ctx.clean_mosaic(g, rot, pc, bl, freqs, _abi.PRISIM_BEAM_AIRY, 14.0, route='stepped', gain=0.1, maxiter=3, threshold=0.0,
+                                             threshold_relative=False, fwhm_rad=0.01, budget_bytes=a.budget)      # noqa: E731
+            cln(small)
+            out['clean_mosaic'] = entry(cln(grid))
+            ccs = lambda g, n: ctx.clean_image_cs(g, (n, n), rot[:1], pc[:1], bl, freqs, route='stepped', gain=0.1, maxiter=10, threshold=0.0,
+                                                  threshold_relative=False, cycle_niter=2, max_major=2, fwhm_rad=0.01, budget_bytes=a.budget,
+                                                  want_psf=True, want_vis=True)      # noqa: E731
+            ccs(small, 16)
+            out['clean_image_cs'] = entry(ccs(grid, a.n))
         else:
             cln = lambda g: ctx.clean_mosaic(g, rot, pc, bl, freqs, _abi.PRISIM_BEAM_AIRY, 14.0, route='stepped', gain=0.1, maxiter=a.maxiter,
                                              threshold=0.0, threshold_relative=False, budget_bytes=a.budget)      # noqa: E731
