@@ -66,6 +66,7 @@ def get_interp_weights(nside, theta, phi):
         w1 = (phi - (i1 + 0.5 * shift) * dphi) / dphi
         i2 = i1 + 1
         i1 = NP.where(i1 < 0, i1 + nr, i1)
+        i1 = NP.where(i1 >= nr, i1 - nr, i1)                    # (phi one ulp below 2 pi: phi / dphi can round up to nr itself)
         i2 = NP.where(i2 >= nr, i2 - nr, i2)
         pix[2 * k] = NP.where(ok, sp + i1, 0)
         pix[2 * k + 1] = NP.where(ok, sp + i2, 0)

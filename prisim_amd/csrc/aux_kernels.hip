@@ -291,7 +291,7 @@ void k_extbeam_gather(const double* __restrict__ table, int nside_i, const doubl
       const double4 d = reinterpret_cast<const double4*>(dirs)[s];
       double z = d.z;                                   // cos(theta), theta = zenith angle
       z = z > 1.0 ? 1.0 : (z < -1.0 ? -1.0 : z);
-      const double theta = acos(z);
+      const double theta = atan2(sqrt(d.x * d.x + d.y * d.y), z);      // (acos(z) is 0 or coarse within ~1e-7 rad of a pole)
       double phi = atan2(d.x, d.y);                     // azimuth from North through East
       if (phi < 0.0) phi += 2.0 * kPi;
       if (phi >= 2.0 * kPi) phi -= 2.0 * kPi;           // (-1e-17 + 2 pi rounds to 2 pi: a source due North to the last bit belongs to phi = 0,
@@ -313,6 +313,7 @@ void k_extbeam_gather(const double* __restrict__ table, int nside_i, const doubl
         const double w1 = (phi - ((double)i1 + 0.5 * r.shift) * dphi) / dphi;
         int64_t i2 = i1 + 1;
         if (i1 < 0) i1 += r.nr;
+        if (i1 >= r.nr) i1 -= r.nr;                     // (phi one ulp below 2 pi: phi / dphi can round up to nr itself)
         if (i2 >= r.nr) i2 -= r.nr;
         pix[0] = r.start + i1; pix[1] = r.start + i2; wgt[0] = 1.0 - w1; wgt[1] = w1; theta1 = r.theta;
       }
@@ -324,6 +325,7 @@ void k_extbeam_gather(const double* __restrict__ table, int nside_i, const doubl
         const double w1 = (phi - ((double)i1 + 0.5 * r.shift) * dphi) / dphi;
         int64_t i2 = i1 + 1;
         if (i1 < 0) i1 += r.nr;
+        if (i1 >= r.nr) i1 -= r.nr;                     // (phi one ulp below 2 pi: phi / dphi can round up to nr itself)
         if (i2 >= r.nr) i2 -= r.nr;
         pix[2] = r.start + i1; pix[3] = r.start + i2; wgt[2] = 1.0 - w1; wgt[3] = w1; theta2 = r.theta;
       }
