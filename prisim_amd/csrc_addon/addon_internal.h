@@ -1,6 +1,6 @@
 // addon_internal.h -- what the add-on entries share (csrc_clean, csrc_subband, csrc_gains, csrc_runs, csrc_closure): the per-call
-// device buffers, streams, events and rocFFT plans of their chunk loops on the host, and the complex helpers and the in-LDS radix-2
-// inverse transform of their fused kernels on the device.  Not part of the public ABI.
+// device buffers, streams, events and rocFFT plans of their chunk loops on the host, and the complex helpers and the in-LDS radix-2 inverse
+// transform of their fused kernels on the device (delay_lines.h has the delay add-ons' arithmetic around it).  Not part of the public ABI.
 #ifndef PRISIM_ADDON_INTERNAL_H
 #define PRISIM_ADDON_INTERNAL_H
 

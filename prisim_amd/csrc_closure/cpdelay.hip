@@ -5,17 +5,15 @@
 // The phases of a chunk of rows lie on the device as [row][nchan][nt], snapshot-fastest: uploaded by this file's loop, or left there by
 // closure.hip's loop (closure_internal.h), which then calls this file's kernels as its sink -- no triplet and no phase crosses the
 // host link on that path.  The outputs are snapshot-fastest too, [row][window][lag][nt], while the transform runs along the lags.
-//   k_cpd_fused (m a power of two): one workgroup per (row, window, tile of snapshots).  x = (cos phi, -sin phi) wts, times
-//     df (-1)^ch (with even m, m df fftshift(ifft(x))[j] = df sum_n x[n] (-1)^n e^{+2 pi i j n / m}), is loaded along the snapshots
-//     and stored bit-reversed into rows of m + 1 double2 (16 (m + 1) bytes: lane k of a snapshot-fastest access starts at bank
-//     4 k mod 64, so the 16 lanes a 128-bit access serves together touch 16 different 16-byte slots); a radix-2 decimation-in-time
-//     transform with an LDS twiddle table leaves the shifted spectrum in natural order; it is written along the snapshots.
+// The transform, the shift, the resampled bins, their direct sum and the power are csrc_addon/delay_lines.h's.  Particular to this file:
+//   k_cpd_fused (m a power of two): one workgroup per (row, window, tile of snapshots).  x = (cos phi, -sin phi) wts is read, and the
+//     spectrum written, along the snapshots; the LDS rows are m + 1 double2 (16 (m + 1) bytes: lane k of a snapshot-fastest access starts
+//     at bank 4 k mod 64, so the 16 lanes a 128-bit access serves together touch 16 different 16-byte slots).
 //   rocFFT route (any other m): k_cpd_prepare turns [ch][t] into the padded rows [line][t][m] through a [32][33] double2 LDS tile
 //     (closure.hip's k_cl_tiled pattern) -> batched inverse rocFFT in place -> k_cpd_finish shifts, scales by df and turns back.
-//   k_cpd_resample (both routes): the FFT of the oversampled series is m df e^{-2 pi i k floor(m/2) / m} x[k], so scipy.signal.resample's
-//     spectrum Y[k_out] is a sum of at most two weighted channels.  The host folds wts, df and the map's weights into one coefficient
-//     per (window, kept bin, term) and drops the bins whose channels the window zeroes; one workgroup per (row, window, tile of
-//     snapshots) forms the kept Y in LDS and sums y[q] = sum_k Y[k] e^{+2 pi i k q / nres} directly.
+//   k_cpd_resample (both routes): the host folds wts, df and the map's weights into one coefficient per (window, kept bin, term) and
+//     drops the bins whose channels the window zeroes; one workgroup per (row, window, tile of snapshots)
+//     forms the kept Y in LDS and sums them.
 //   k_cpp_accumulate / k_cpp_finish: the power spectra; every thread owns points of the contiguous trailing axes, loops over the
 //     chunk's entries of axis 0 and keeps sum |x|^2 and sum x in device arrays between chunks.  No atomics.
 // Chunks of rows alternate between two streams with their own buffers, as in closure.hip.
@@ -29,6 +27,7 @@
 #include <vector>
 
 #include "closure_internal.h"
+#include "../csrc_addon/delay_lines.h"
 #include "../../include/prisim_cpdelay.h"
 
 namespace {
@@ -79,13 +78,12 @@ __global__ void __launch_bounds__(kThreads) k_cpd_fused(CdParams P, int64_t line
   lds_twiddles(tw, m);
   for (int e = threadIdx.x; e < m * tile; e += kThreads) {             // lanes along the snapshots
     const int n = e / tile, tt = e - n * tile;
-    const int j = bitrev(n, P.logm);
-    double2 v = make_double2(0.0, 0.0);
+    LdsOperand x = shifted_zero(n, P.logm);
     if (n < P.nchan && tt < tcount) {
       const double wv = wt[n];
-      if (wv != 0.0) v = rmul(rmul(phasor(ph[(int64_t)n * P.nt + tt]), wv), (m > 1 && (n & 1)) ? -P.df : P.df);
+      if (wv != 0.0) x = shifted_operand(rmul(phasor(ph[(int64_t)n * P.nt + tt]), wv), n, m, P.logm, P.df);
     }
-    buf[tt * ld + j] = v;
+    buf[tt * ld + x.slot] = x.v;
   }
   __syncthreads();
   lds_ifft_dit(buf, ld, tile, m, tw);
@@ -96,7 +94,7 @@ __global__ void __launch_bounds__(kThreads) k_cpd_fused(CdParams P, int64_t line
     if (tt < tcount) {
       const double2 v = buf[tt * ld + j];
       if (P.over) P.over[o + (int64_t)j * P.nt + tt] = v;
-      if (P.over_pow) P.over_pow[o + (int64_t)j * P.nt + tt] = (v.x * v.x + v.y * v.y) * ps;
+      if (P.over_pow) P.over_pow[o + (int64_t)j * P.nt + tt] = power_of(v, ps);
     }
   }
 }
@@ -130,7 +128,7 @@ __global__ void __launch_bounds__(kThreads) k_cpd_prepare(CdParams P, int64_t li
   }
 }
 
-// rocFFT route, after the unnormalised inverse transform F: oversampled[(jf + floor(m/2)) mod m] = df F[jf].  grid as k_cpd_prepare
+// rocFFT route, after the unnormalised inverse transform: transform bin jf scatters to its lag.  grid as k_cpd_prepare
 __global__ void __launch_bounds__(kThreads) k_cpd_finish(CdParams P, int64_t line0, int nct, int ntt) {
   __shared__ double2 tile[kTile][kTile + 1];
   const int64_t line = line0 + blockIdx.x / ((int64_t)nct * ntt);
@@ -150,10 +148,9 @@ __global__ void __launch_bounds__(kThreads) k_cpd_finish(CdParams P, int64_t lin
     const int cc = ly + 8 * i, jf = c0 + cc, t = t0 + lx;
     if (jf < P.m && t < P.nt) {
       const double2 v = rmul(tile[lx][cc], P.df);
-      const int j = (jf + P.m / 2) % P.m;
-      const int64_t o = (line * P.m + j) * P.nt + t;
+      const int64_t o = (line * P.m + shift_target(jf, P.m)) * P.nt + t;
       if (P.over) P.over[o] = v;
-      if (P.over_pow) P.over_pow[o] = (v.x * v.x + v.y * v.y) * ps;
+      if (P.over_pow) P.over_pow[o] = power_of(v, ps);
     }
   }
 }
@@ -176,13 +173,8 @@ __global__ void __launch_bounds__(kThreads) k_cpd_resample(CdParams P, int64_t l
   for (int e = threadIdx.x; e < nz * tile; e += kThreads) {            // lanes along the snapshots
     const int i = e / tile, tt = e - i * tile;
     double2 v = make_double2(0.0, 0.0);
-    if (tt < tcount) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int ch = kin[s * nres + i];
-        if (ch >= 0) v = cadd(v, cmul(phasor(ph[(int64_t)ch * P.nt + tt]), coef[s * nres + i]));
-      }
-    }
+    if (tt < tcount)                                                   // the window's own tables, by kept bin
+      v = resampled_bin([&](int ch) { return phasor(ph[(int64_t)ch * P.nt + tt]); }, kin, coef, nres, i);
     Y[i * tile + tt] = v;
   }
   __syncthreads();
@@ -191,10 +183,9 @@ __global__ void __launch_bounds__(kThreads) k_cpd_resample(CdParams P, int64_t l
   for (int e = threadIdx.x; e < nres * tile; e += kThreads) {
     const int q = e / tile, tt = e - q * tile;
     if (tt >= tcount) continue;
-    double2 acc = make_double2(0.0, 0.0);
-    for (int i = 0; i < nz; ++i) acc = cadd(acc, cmul(Y[i * tile + tt], P.rtw[(kout[i] * q) % nres]));   // k q < 2^24
+    const double2 acc = direct_sum<true>(Y + tt, tile, kout, nz, q, nres, P.rtw);
     if (P.res) P.res[o + (int64_t)q * P.nt + tt] = acc;
-    if (P.res_pow) P.res_pow[o + (int64_t)q * P.nt + tt] = (acc.x * acc.x + acc.y * acc.y) * ps;
+    if (P.res_pow) P.res_pow[o + (int64_t)q * P.nt + tt] = power_of(acc, ps);
   }
 }
 
@@ -266,16 +257,11 @@ struct Transform {
   int prepare(int64_t tc, int64_t last, int nstreams, const hipStream_t* streams) {
     const int64_t lines = tc * nwin * nt;
     double *d_wts, *d_ps = nullptr;
-    int32_t *d_rso, *d_rsk, *d_rsin;
-    double2 *d_rsc, *d_rtw;
+    ResampleDev rd;
     hipStream_t s0 = streams[0];
     DEV_UPLOAD(ctx, wk.dev, d_wts, wts, (size_t)nwin * nchan, s0);
     if (pscale) DEV_UPLOAD(ctx, wk.dev, d_ps, pscale, (size_t)nwin, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_rso, rs_o, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_rsk, rs_k, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_rsin, rs_in, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_rsc, rs_c, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_rtw, rtw, s0);
+    if (int rc = upload_resample(ctx, wk.dev, rd, rs_in, rs_c, rtw, rs_o, rs_k, s0)) return rc;
     for (int i = 0; i < nstreams; ++i) {
       if (w_over) DEV_ALLOC(ctx, wk.dev, d_over[i], (size_t)lines * m * 16);
       if (w_opow) DEV_ALLOC(ctx, wk.dev, d_opow[i], (size_t)lines * m * 8);
@@ -293,7 +279,7 @@ struct Transform {
     base.nwin = nwin; base.nchan = (int)nchan; base.nt = (int)nt; base.m = (int)m; base.logm = logm; base.nres = (int)std::max<int64_t>(nres, 1);
     base.tile = (int)tile; base.ntiles = (int)ntiles; base.rtile = (int)rtile; base.rntiles = (int)rntiles;
     base.df = df;
-    base.rs_o = d_rso; base.rs_k = d_rsk; base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw;
+    base.rs_o = rd.ofs; base.rs_k = rd.list; base.rs_in = rd.in; base.rs_c = rd.c; base.rtw = rd.rtw;
     base.over = nullptr; base.over_pow = nullptr; base.res = nullptr; base.res_pow = nullptr; base.fbuf = nullptr;
     if (fused && want_over())
       if (int rc = allow_lds(ctx, k_cpd_fused, lds)) return rc;

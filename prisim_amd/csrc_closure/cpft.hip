@@ -5,17 +5,14 @@
 // wavefront reads and writes consecutive pieces of a row and nothing is transposed.
 //   k_cpft_rows<true> (fused, m a power of two): one workgroup per group of R consecutive rows (R = 1 from m = 2048 on, more for
 //     small m).  It reads the group's weights once into LDS, reduces their means there and turns them into fw = w / mean (0 for a row
-//     of mean 0).  Then, for every input and the lag kernel (a "pass") and every window, it stores x = in fw wts vscale, times
-//     df (-1)^ch (with even m, m df fftshift(ifft(x))[j] = df sum_n x[n] (-1)^n e^{+2 pi i j n / m}), bit-reversed into LDS rows of m
-//     double2, runs the radix-2 decimation-in-time transform of addon_internal.h with an LDS twiddle table and writes the rows out.
+//     of mean 0).  Then, for every input and the lag kernel (a "pass") and every window, it transforms x = in fw wts vscale in LDS
+//     rows of m double2 (csrc_addon/delay_lines.h, as the shift, the resampled bins and their direct sum) and writes the rows out.
 //     LDS: 16 R m (rows) + 8 m (twiddles) + 8 R nchan + 2 KiB (weights and their reduction) + 68 R; at m = 4096 and nchan = 2048 that
 //     is 64 + 32 + 16 + 2 KiB of the 160 KiB of a CU, one workgroup per CU; from m = 1024 down, two or more.
 //   rocFFT route (any other m): k_cpft_rows<false>, the same kernel without the transform, writes the padded rows x -> batched
 //     inverse rocFFT in place -> k_cpft_finish shifts and scales by df.
-//   k_cpft_resample (both routes): the FFT of the oversampled series is m df e^{-2 pi i k floor(m/2) / m} x[k], so
-//     scipy.signal.resample's spectrum Y[k_out] is a sum of at most two channels of x (build_resample_tables).  One workgroup per
-//     group of rows forms, per pass and window, the Y of the bins that the window feeds in LDS and sums
-//     y[q] = sum_k Y[k] e^{+2 pi i k q / nres} directly.
+//   k_cpft_resample (both routes): one workgroup per group of rows forms, per pass and window, the Y of the bins that the window
+//     feeds (Feeds::kNonzero) in LDS and sums them.
 // An input with a leading extent of 1 is uploaded once and read with stride 0; the others are streamed with the rows.  Chunks of
 // rows alternate between two streams with their own buffers, so that the upload of one chunk, the kernels of the other and the
 // downloads overlap.  No atomics, no scratch.  fp64 throughout, built with -ffp-contract=off.
@@ -27,7 +24,7 @@
 #include <string>
 #include <vector>
 
-#include "../csrc_addon/addon_internal.h"
+#include "../csrc_addon/delay_lines.h"
 #include "../../include/prisim_cpft.h"
 
 using namespace pint;
@@ -152,8 +149,9 @@ __global__ void __launch_bounds__(kThreads) k_cpft_rows(const FtParams P) {
         const int rr = FUSED ? e >> P.logm : e / m, n = e - rr * m;
         double2 v = make_double2(0.0, 0.0);
         if (n < nchan) v = x_value(P, g, p, k, rr, n);
-        if (FUSED) buf[rr * m + bitrev(n, P.logm)] = rmul(v, (m > 1 && (n & 1)) ? -P.df : P.df);
-        else orow[e] = v;
+        if (!FUSED) { orow[e] = v; continue; }
+        const LdsOperand x = shifted_operand(v, n, m, P.logm, P.df);    // the padding too: its odd samples are 0 * -df
+        buf[rr * m + x.slot] = x.v;
       }
       if (FUSED) {
         __syncthreads();
@@ -165,7 +163,7 @@ __global__ void __launch_bounds__(kThreads) k_cpft_rows(const FtParams P) {
   }
 }
 
-// rocFFT route, after the unnormalised inverse transform F: over[(jf + floor(m/2)) mod m] = df F[jf].  Grid-stride over the lines.
+// rocFFT route, after the unnormalised inverse transform: transform bin jf scatters to its lag.  Grid-stride over the lines.
 __global__ void __launch_bounds__(kThreads) k_cpft_finish(const FtParams P) {
   const int m = P.m, npass = P.nin + P.lagk;
   const int64_t per = (int64_t)P.nwin * P.rn * m;
@@ -176,7 +174,7 @@ __global__ void __launch_bounds__(kThreads) k_cpft_finish(const FtParams P) {
     for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < per; e += (int64_t)gridDim.x * kThreads) {
       const int64_t line = e / m;
       const int jf = (int)(e - line * m);
-      dst[line * m + (jf + m / 2) % m] = rmul(src[e], P.df);
+      dst[line * m + shift_target(jf, m)] = rmul(src[e], P.df);
     }
   }
 }
@@ -196,21 +194,13 @@ __global__ void __launch_bounds__(kThreads) k_cpft_resample(const FtParams P) {
       const int32_t* kout = P.rs_k + P.rs_o[k];
       for (int e = threadIdx.x; e < g.rc * nz; e += kThreads) {
         const int rr = e / nz, i = e - rr * nz, kk = kout[i];
-        double2 v = make_double2(0.0, 0.0);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const int ch = P.rs_in[s * nres + kk];
-          if (ch >= 0) v = cadd(v, cmul(x_value(P, g, p, k, rr, ch), P.rs_c[s * nres + kk]));
-        }
-        Y[rr * nres + i] = v;
+        Y[rr * nres + i] = resampled_bin([&](int ch) { return x_value(P, g, p, k, rr, ch); }, P.rs_in, P.rs_c, nres, kk);
       }
       __syncthreads();
       double2* orow = P.res[p] + ((int64_t)k * P.rn + g.l0) * nres;
       for (int e = threadIdx.x; e < g.rc * nres; e += kThreads) {
         const int rr = e / nres, q = e - rr * nres;
-        double2 acc = make_double2(0.0, 0.0);
-        for (int i = 0; i < nz; ++i) acc = cadd(acc, cmul(Y[rr * nres + i], P.rtw[(kout[i] * q) % nres]));   // k q < 2^24
-        orow[e] = acc;
+        orow[e] = direct_sum<true>(Y + rr * nres, 1, kout, nz, q, nres, P.rtw);
       }
       __syncthreads();
     }
@@ -330,15 +320,10 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
   if (int rc = st.create(ctx, nstreams, true)) return rc;
   hipStream_t s0 = st.s[0];
   double *d_wts, *d_vs = nullptr;
-  int32_t *d_rso, *d_rsk, *d_rsin;
-  double2 *d_rsc, *d_rtw;
+  ResampleDev rd;
   DEV_UPLOAD(ctx, wk.dev, d_wts, wts, (size_t)nwin * nchan, s0);
   if (vscale) DEV_UPLOAD(ctx, wk.dev, d_vs, vscale, (size_t)nwin * n0, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_rso, rs_o, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_rsk, rs_k, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_rsin, rs.in, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_rsc, rs_c, s0);
-  DEV_UPLOAD(ctx, wk.dev, d_rtw, rs.rtw, s0);
+  if (int rc = upload_resample(ctx, wk.dev, rd, rs.in, rs_c, rs.rtw, rs_o, rs_k, s0)) return rc;
   double2* d_bcast[kMaxIn] = {};
   for (int i = 0; i < nin; ++i)
     if (!chunked[i]) DEV_UPLOAD(ctx, wk.dev, d_bcast[i], inputs[i], (size_t)in_rows[i] * nchan * 2, s0);
@@ -393,7 +378,7 @@ int prisim_cphase_ft(prisim_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
   base.nwin = nwin; base.nchan = (int)nchan; base.m = (int)m; base.logm = logm; base.nres = (int)nr;
   base.df = df;
   base.fpass0 = fpass0;
-  base.rs_o = d_rso; base.rs_k = d_rsk; base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw;
+  base.rs_o = rd.ofs; base.rs_k = rd.list; base.rs_in = rd.in; base.rs_c = rd.c; base.rtw = rd.rtw;
   const size_t lds_rows = rows_lds(R), lds_res = res_lds(Rr);
   if (any_over)
     if (int rc = fused ? allow_lds(ctx, k_cpft_rows<true>, lds_rows) : allow_lds(ctx, k_cpft_rows<false>, lds_rows)) return rc;

@@ -6,15 +6,12 @@
 // kernel maps consecutive lanes to consecutive snapshots of one channel, so that the [nchan][nt] block of a pair is read, and the
 // [nout][nt] block of the spectra written, in contiguous runs of nt elements.
 //
-// Fused route (m a power of two): one workgroup per (pair, window, tile of TT snapshots).  The tile's windowed rows x[n] times
-// (scale / m) (-1)^n are loaded bit-reversed into LDS (with even m, scale fftshift(ifft(x))[j] = (scale / m) sum_n x[n] (-1)^n
-// e^{+2 pi i j n / m}), a radix-2 in-place transform with an LDS twiddle table gives the shifted spectra in natural order, and the
-// selected lags are written.
+// The transform, the shift, the resampled bins and their direct sum are csrc_addon/delay_lines.h's, with the scale s = scale / m.
+// Fused route (m a power of two): one workgroup per (pair, window, tile of TT snapshots); the selected lags are written.
 // rocFFT route (any other m): k_runs_prepare writes the windowed padded rows [w][pair][t][m] -> batched inverse rocFFT in place ->
 // k_runs_finish shifts, scales, selects and writes [w][pair][j][t].
-// Resampling (out_mode PRISIM_RUNS_RESAMPLE, any m): k_runs_resample forms scipy.signal.resample's spectrum Y[k] (at most two weighted
-// bins of x per output bin) in LDS and sums y[q] = sum_k Y[k] e^{+2 pi i k q / nout} over the bins that the window can make nonzero;
-// the m-lag spectra never exist.
+// Resampling (out_mode PRISIM_RUNS_RESAMPLE, any m): k_runs_resample forms every bin Y[k] in LDS and sums over the bins inside the
+// span of the window's nonzero channels (Feeds::kSpan); the m-lag spectra never exist.
 // The power kernel forms Re(v1 conj(v2)) * factor (* 2) as numpy rounds it.
 // Chunks of pairs are spread over two streams with their own buffers: the copies of one chunk overlap the kernels of the other.
 // fp64 throughout (complex64 input is widened on load), built with -ffp-contract=off; the one fused product is an explicit fma().
@@ -26,7 +23,7 @@
 #include <string>
 #include <vector>
 
-#include "../csrc_addon/addon_internal.h"
+#include "../csrc_addon/delay_lines.h"
 #include "../../include/prisim_runs.h"
 
 namespace {
@@ -97,10 +94,9 @@ __global__ void __launch_bounds__(kThreads) k_runs_fused(RunParams P) {
   lds_twiddles(tw, m);
   for (int e = threadIdx.x; e < m * tile; e += kThreads) {
     const int n = e / tile, tt = e - n * tile;
-    const int j = bitrev(n, P.logm);
-    double2 v = make_double2(0.0, 0.0);
-    if (n < P.nchan && tt < tcount) v = rmul(row_value(P, pl, n, t0 + tt, w), (m > 1 && (n & 1)) ? -P.s : P.s);
-    buf[tt * m + j] = v;
+    LdsOperand x = shifted_zero(n, P.logm);
+    if (n < P.nchan && tt < tcount) x = shifted_operand(row_value(P, pl, n, t0 + tt, w), n, m, P.logm, P.s);
+    buf[tt * m + x.slot] = x.v;
   }
   __syncthreads();
   lds_ifft_dit(buf, m, tile, m, tw);
@@ -127,9 +123,9 @@ __global__ void __launch_bounds__(kThreads) k_runs_prepare(RunParams P) {
   }
 }
 
-// rocFFT route, after the unnormalised inverse transform F: spectrum[i] = (scale / m) F[(i - floor(m/2)) mod m], then the selection
+// rocFFT route, after the unnormalised inverse transform: every selected lag gathers its transform bins
 __global__ void __launch_bounds__(kThreads) k_runs_finish(RunParams P) {
-  const int m = P.m, half = m / 2;
+  const int m = P.m;
   const int64_t total = (int64_t)P.nwin * P.pc * P.nout * P.nt;
   for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
     const int t = (int)(e % P.nt);
@@ -137,7 +133,7 @@ __global__ void __launch_bounds__(kThreads) k_runs_finish(RunParams P) {
     const int j = (int)(r % P.nout);
     const int64_t wp = r / P.nout;
     const double2* row = P.fbuf + (wp * P.nt + t) * m;
-    P.out[e] = select_lag(P, j, [&](int i) { return rmul(row[(i + m - half) % m], P.s); });
+    P.out[e] = select_lag(P, j, [&](int i) { return rmul(row[shift_source(i, m)], P.s); });
   }
 }
 
@@ -153,13 +149,8 @@ __global__ void __launch_bounds__(kThreads) k_runs_resample(RunParams P) {
   for (int e = threadIdx.x; e < nout * tile; e += kThreads) {
     const int k = e / tile, tt = e - k * tile;
     double2 v = make_double2(0.0, 0.0);
-    if (tt < tcount) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int i = P.rs_in[s * nout + k];
-        if (i >= 0) v = cadd(v, cmul(row_value(P, pl, i, t0 + tt, w), P.rs_c[s * nout + k]));
-      }
-    }
+    if (tt < tcount)
+      v = resampled_bin([&](int i) { return row_value(P, pl, i, t0 + tt, w); }, P.rs_in, P.rs_c, nout, k);
     z[e] = v;
   }
   __syncthreads();
@@ -168,11 +159,7 @@ __global__ void __launch_bounds__(kThreads) k_runs_resample(RunParams P) {
   double2* dst = P.out + ((int64_t)w * P.pc + pl) * nout * P.nt + t0;
   for (int e = threadIdx.x; e < nout * tile; e += kThreads) {
     const int q = e / tile, tt = e - q * tile;
-    double2 acc = make_double2(0.0, 0.0);
-    for (int i = 0; i < nk; ++i) {
-      const int k = kl[i];
-      acc = cadd(acc, cmul(z[k * tile + tt], P.rtw[(int)(((int64_t)k * q) % nout)]));
-    }
+    const double2 acc = direct_sum<false>(z + tt, tile, kl, nk, q, nout, P.rtw);
     if (tt < tcount) dst[(int64_t)q * P.nt + tt] = acc;
   }
 }
@@ -279,18 +266,12 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
   hipStream_t s0 = st.s[0];
   const int64_t bp_n = bp ? span_of(bp_strides, nbl, nchan, nt) : 0, wts_n = wts ? span_of(wts_strides, nbl, nchan, nt) : 0;
   double *d_bp = nullptr, *d_wts = nullptr, *d_win = nullptr;
-  int32_t *d_rsin = nullptr, *d_klist = nullptr, *d_kofs = nullptr;
-  double2 *d_rsc = nullptr, *d_rtw = nullptr;
+  ResampleDev rd;
   if (bp) DEV_UPLOAD(ctx, wk.dev, d_bp, bp, (size_t)bp_n, s0);
   if (wts) DEV_UPLOAD(ctx, wk.dev, d_wts, wts, (size_t)wts_n, s0);
   if (win) DEV_UPLOAD(ctx, wk.dev, d_win, win, (size_t)nwin * nchan, s0);
-  if (resample) {
-    DEV_UPLOAD(ctx, wk.dev, d_rsin, rs.in, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_rsc, rs_c, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_rtw, rs.rtw, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_klist, klist, s0);
-    DEV_UPLOAD(ctx, wk.dev, d_kofs, kofs, s0);
-  }
+  if (resample)
+    if (int rc = upload_resample(ctx, wk.dev, rd, rs.in, rs_c, rs.rtw, kofs, klist, s0)) return rc;
   void* d_in[kMaxStreams] = {};
   double2* d_out[kMaxStreams] = {};
   double2* d_fbuf[kMaxStreams] = {};
@@ -313,7 +294,7 @@ int prisim_runs_transform(prisim_ctx* ctx, int64_t R, int64_t nbl, int64_t nchan
   base.nwin = nwin; base.nchan = (int)nchan; base.nt = (int)nt; base.m = (int)m; base.logm = logm; base.nout = (int)nout;
   base.mode = out_mode; base.tile = (int)tile; base.ntiles = (int)ntiles;
   base.nbl = nbl; base.p0 = 0; base.pc = 0; base.s = s; base.factor = factor;
-  base.rs_in = d_rsin; base.rs_c = d_rsc; base.rtw = d_rtw; base.klist = d_klist; base.kofs = d_kofs;
+  base.rs_in = rd.in; base.rs_c = rd.c; base.rtw = rd.rtw; base.klist = rd.list; base.kofs = rd.ofs;
   base.out = nullptr; base.fbuf = nullptr;
   if (rt == PRISIM_RUNS_FUSED)
     if (int rc = allow_lds(ctx, k_runs_fused, lds)) return rc;

@@ -1,16 +1,12 @@
 // subband.hip -- sub-band delay spectra for gfx950 (include/prisim_subband.h): prisim/delay_spectrum.py:subband_delay_transform
 // (:2196-2236) for every (snapshot, baseline) row of one or more cubes, every frequency window, and the FFT resampling of the spectra.
 //
+// The transform, the shift, the resampled bins, their direct sum and the power are csrc_addon/delay_lines.h's.  Particular to this file:
 // Fused route (m a power of two, LDS permitting): one workgroup per row.  Per cube the row times its bandpass is read once into LDS;
 // then for every window w
-//   oversampled: x[n] = row[n] bp[n] wts[w][n] on the window's nonzero channel span [lo, hi), zero elsewhere up to m.  With even m,
-//     m df fftshift(ifft(x))[j] = df sum_n x[n] (-1)^n e^{+2 pi i j n / m}: the sign and df are folded into the load (bit-reversed
-//     into LDS) and a radix-2 in-place transform with an LDS twiddle table gives the shifted spectrum in natural order;
-//   resampled: the FFT of the oversampled series is m df e^{-2 pi i k floor(m/2) / m} x[k], so scipy.signal.resample's spectrum
-//     Y[k_out] = sum of at most two weighted bins x[k_in] (the caller's selection map, prisim_amd/dsp_readings.py:resample_map)
-//     follows from the row in LDS without the m lags: the nonzero Y[k_out] are compacted and
-//     y[q] = (1 / m) sum_k_out Y[k_out] e^{+2 pi i k_out q / nres} is summed directly (the kept bins are the lowest and highest
-//     ~nres/2 channels, so a window away from channel 0 has none and writes zeros).
+//   oversampled: x[n] = row[n] bp[n] wts[w][n] on the window's nonzero channel span [lo, hi), zero elsewhere up to m;
+//   resampled: from the row in LDS, without the m lags.  Only the terms inside [lo, hi) count; wave 0 compacts the nonzero Y[k_out] on
+//     the device (the kept bins are the lowest and highest ~nres/2 channels, so a window away from channel 0 has none and writes zeros).
 // Each output element is written once.
 // rocFFT route (any other m): k_sb_prepare writes the windowed padded rows [cube][row][window][m] (and the resampled spectra, as above)
 // -> batched inverse rocFFT in place -> k_sb_finish shifts, scales by df and forms the power.
@@ -23,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../csrc_addon/addon_internal.h"
+#include "../csrc_addon/delay_lines.h"
 #include "../../include/prisim_subband.h"
 
 namespace {
@@ -69,13 +65,7 @@ __device__ void resample_window(const SbParams& P, const double2* xs, int c, int
   const double* wt = P.wts + (int64_t)w * P.nchan;
   const int nres = P.nres;
   for (int k = threadIdx.x; k < nres; k += kThreads) {
-    double2 v = make_double2(0.0, 0.0);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int i = P.rs_in[s * nres + k];
-      if (i >= lo && i < hi) v = cadd(v, cmul(rmul(xs[i], wt[i]), P.rs_c[s * nres + k]));
-    }
-    z[k] = v;
+    z[k] = resampled_bin([&](int i) { return rmul(xs[i], wt[i]); }, P.rs_in, P.rs_c, nres, k, lo, hi);   // the window's span alone
   }
   __syncthreads();
   if (threadIdx.x < 64) {                       // wave 0 compacts the nonzero bins in increasing order
@@ -95,13 +85,9 @@ __device__ void resample_window(const SbParams& P, const double2* xs, int c, int
   const int64_t o = (((int64_t)c * P.nrows + r) * P.nwin + w) * nres;
   const double ps = P.pscale ? P.pscale[w] : 0.0;
   for (int q = threadIdx.x; q < nres; q += kThreads) {
-    double2 acc = make_double2(0.0, 0.0);
-    for (int i = 0; i < nz; ++i) {
-      const int k = zi[i];
-      acc = cadd(acc, cmul(z[k], P.rtw[(int)(((int64_t)k * q) % nres)]));
-    }
+    const double2 acc = direct_sum<false>(z, 1, zi, nz, q, nres, P.rtw);
     if (P.res) P.res[o + q] = acc;
-    if (P.res_pow) P.res_pow[o + q] = (acc.x * acc.x + acc.y * acc.y) * ps;
+    if (P.res_pow) P.res_pow[o + q] = power_of(acc, ps);
   }
   __syncthreads();
 }
@@ -127,10 +113,9 @@ __global__ void __launch_bounds__(kThreads) k_sb_fused(SbParams P) {
       if (want_over) {
         const double* wt = P.wts + (int64_t)w * nchan;
         for (int n = threadIdx.x; n < m; n += kThreads) {
-          const int j = bitrev(n, P.logm);
-          double2 v = make_double2(0.0, 0.0);
-          if (n >= lo && n < hi) v = rmul(rmul(xs[n], wt[n]), (m > 1 && (n & 1)) ? -P.df : P.df);
-          buf[j] = v;
+          LdsOperand x = shifted_zero(n, P.logm);
+          if (n >= lo && n < hi) x = shifted_operand(rmul(xs[n], wt[n]), n, m, P.logm, P.df);
+          buf[x.slot] = x.v;
         }
         __syncthreads();
         lds_ifft_dit(buf, m, 1, m, tw);
@@ -139,7 +124,7 @@ __global__ void __launch_bounds__(kThreads) k_sb_fused(SbParams P) {
         for (int j = threadIdx.x; j < m; j += kThreads) {
           const double2 v = buf[j];
           if (P.over) P.over[o + j] = v;
-          if (P.over_pow) P.over_pow[o + j] = (v.x * v.x + v.y * v.y) * ps;
+          if (P.over_pow) P.over_pow[o + j] = power_of(v, ps);
         }
         __syncthreads();
       }
@@ -175,16 +160,16 @@ __global__ void __launch_bounds__(kThreads) k_sb_prepare(SbParams P) {
   }
 }
 
-// rocFFT route, after the unnormalised inverse transform F: oversampled[j] = df F[(j - floor(m/2)) mod m]
+// rocFFT route, after the unnormalised inverse transform: lag j gathers its transform bin
 __global__ void __launch_bounds__(kThreads) k_sb_finish(SbParams P, int64_t nlines) {
-  const int m = P.m, half = m / 2;
+  const int m = P.m;
   const int64_t total = nlines * m;
   for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
     const int64_t line = e / m;
     const int j = (int)(e - line * m);
-    const double2 v = rmul(P.fbuf[line * m + (j + m - half) % m], P.df);
+    const double2 v = rmul(P.fbuf[line * m + shift_source(j, m)], P.df);
     if (P.over) P.over[e] = v;
-    if (P.over_pow) P.over_pow[e] = (v.x * v.x + v.y * v.y) * P.pscale[line % P.nwin];
+    if (P.over_pow) P.over_pow[e] = power_of(v, P.pscale[line % P.nwin]);
   }
 }
 

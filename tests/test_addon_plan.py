@@ -455,3 +455,21 @@ def test_resample_plan_and_snapshot_tile_match_the_handwritten_loops(tmp_path):
         err = NP.abs(got - want).max() / (DF * NP.abs(x).sum())
         print('resample (%d, %d, %d): %.3g of df sum |x|' % (m, nout, nchan, err))
         assert err <= 1e-12
+
+
+# ---- the delay add-ons state their transform and resampling arithmetic once ----------------------------------------------------------
+
+DELAY_ADDONS = ['csrc_subband/subband.hip', 'csrc_runs/runs.hip', 'csrc_closure/cpdelay.hip', 'csrc_closure/cpft.hip']
+
+
+def test_delay_addons_take_their_arithmetic_from_delay_lines():
+    """The sign of the shifted transform's operand and the direct sum's twiddle index are written in csrc_addon/delay_lines.h alone."""
+    for rel in DELAY_ADDONS:
+        with open(os.path.join(ROOT, 'prisim_amd', rel)) as f:
+            txt = f.read()
+        assert 'delay_lines.h"' in [ln.split('/')[-1] for ln in txt.splitlines() if ln.startswith('#include "')], rel
+        assert 'rtw[' not in txt, rel
+        assert '& 1)) ?' not in txt, rel
+    with open(os.path.join(ROOT, 'prisim_amd', 'csrc_addon', 'delay_lines.h')) as f:
+        txt = f.read()
+    assert txt.count('rtw[') == 1 and txt.count('& 1)) ?') == 1
