@@ -11,7 +11,9 @@
 //   order-preserving 64-bit keys, counted with ballots (at most 32 passes per 64-bit key, fewer once one candidate is left).  The complex median is numpy's: lexicographic
 //   (real, then imaginary; the imaginary keys are only consulted on ties of the real part), mean of the two middle elements when the
 //   count is even.
-// fp64 throughout, built with -ffp-contract=off: the AXPY, the medians' means and x - median round as numpy's separate operations.
+// fp64 throughout, built with -ffp-contract=off: the medians' means and x - median round as numpy's separate operations, and the
+// AXPY's complex product as numpy's vector loop rounds it where the processor fuses (fma(ar, br, -(ai bi)), fma(ar, bi, ai br)), so
+// residuals, and with them the two rms, follow the reference's fixtures to the last bits.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -289,6 +291,7 @@ __device__ void clean_row(const CleanParams& P, const RowLds& L, const double2* 
       const double nan = __longlong_as_double(0x7ff8000000000000ll);
       P.rms[row] = make_double2(nan, nan);
     }
+    wave_sync();           // as the other exit: lane 0's stores above and the next hand-out's lane-0 atomic must not merge into one branch
     return;
   }
   const double bound = lolim * mx;
@@ -331,8 +334,8 @@ __device__ void clean_row(const CleanParams& P, const RowLds& L, const double2* 
       kj = kj < 0 ? kj + m : (kj >= m ? kj - m : kj);
       const double2 k = kg[kj];
       const double2 v = L.r[p];
-      const double tr = cv.x * k.x - cv.y * k.y;
-      const double ti = cv.x * k.y + cv.y * k.x;
+      const double tr = fma(cv.x, k.x, -(cv.y * k.y));                  // numpy's complex product on a processor with fused
+      const double ti = fma(cv.x, k.y, cv.y * k.x);                     // multiply-add: one product rounded, the other fused into the sum
       L.r[p] = make_double2(v.x - tr, v.y - ti);
     }
     wave_sync();
@@ -376,6 +379,10 @@ __global__ void __launch_bounds__(kWave * kMaxWaves) k_clean_rows(CleanParams P)
   L.sk = reinterpret_cast<uint64_t*>(w + (size_t)m * 16);
   L.perm = reinterpret_cast<uint16_t*>(w + (size_t)m * 24);
   for (;;) {
+    // The whole wave meets here before lane 0 draws a row: the shuffle below reads lane 0.  Without a convergent operation between a
+    // lane-0-only tail of clean_row and this lane-0-only atomic the compiler threads lane 0 from one to the other and sends the other
+    // lanes straight back to the shuffle, where they read row 0 for ever (a row rejected for its threshold hung the wave).
+    wave_sync();
     unsigned long long row = 0;
     if (lane == 0) row = atomicAdd(P.counter, 1ull);
     row = ((unsigned long long)(unsigned)__shfl((int)(row >> 32), 0) << 32) | (unsigned)__shfl((int)(row & 0xffffffffu), 0);
@@ -384,13 +391,29 @@ __global__ void __launch_bounds__(kWave * kMaxWaves) k_clean_rows(CleanParams P)
   }
 }
 
+// |z| rounded correctly (but for a true value within 2^-100 of a midpoint): hypot is within an ulp, and the residual x^2 + y^2 - h^2,
+// formed without rounding error by fused products, says which neighbour is nearer.  Every normalised tap inherits the peak's modulus,
+// so its last bit is worth this once per kernel; values whose squares leave the double range keep hypot's answer.
+__device__ __forceinline__ double modulus_rounded(double x, double y) {
+  const double h = hypot(x, y);
+  const double xx = x * x, yy = y * y, hh = h * h;
+  if (!(h > 0x1p-500 && h < 0x1p500)) return h;
+  const double ex = fma(x, x, -xx), ey = fma(y, y, -yy), eh = fma(h, h, -hh);
+  const double big = fmax(xx, yy), small = fmin(xx, yy);
+  const double d = big - hh;                       // exact: hh is within a factor 2 of big
+  const double t = d + small;
+  const double et = (d - (t - (t - d))) + (small - (t - d));   // two-sum error of d + small
+  const double r = t + (et + ((ex + ey) - eh));
+  return h + r / (2.0 * h);
+}
+
 // kernel /= max|kernel| as numpy divides a complex array by a float (Smith's branch with a zero imaginary part), then the first argmax
 __global__ void __launch_bounds__(kWave) k_clean_norm(const double2* kin, double2* kout, int* kmax, int m) {
   const int lane = threadIdx.x;
   const double2* k = kin + (int64_t)blockIdx.x * m;
   double2* o = kout + (int64_t)blockIdx.x * m;
   double mx = 0.0;
-  for (int j = lane; j < m; j += kWave) mx = fmax(mx, hypot(k[j].x, k[j].y));
+  for (int j = lane; j < m; j += kWave) mx = fmax(mx, modulus_rounded(k[j].x, k[j].y));
   for (int s = 32; s >= 1; s >>= 1) mx = fmax(mx, shfl_xor_f64(mx, s));
   const double rat = 0.0 / mx;
   const double scl = 1.0 / (mx + 0.0 * rat);

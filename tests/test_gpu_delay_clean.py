@@ -22,6 +22,12 @@ def _flags(c1, c2, c3, no_out=False):
         int(no_out) * _abi.PRISIM_CLEAN_NO_OUTRMS
 
 
+def _rms_agrees(got, want):
+    """(inrms, outrms) NaN where wanted, else within 4 ulp: two hypots within an ulp each, and the rounding of the mean of two."""
+    nan = NP.isnan(want)
+    return NP.array_equal(NP.isnan(got), nan) and bool(NP.all(NP.abs(got[~nan] - want[~nan]) <= 4 * CK.ULP * NP.abs(want[~nan])))
+
+
 def test_fixtures_through_the_device():
     g = NP.load(GOLD)
     with _abi.Context(0) as ctx:
@@ -35,6 +41,10 @@ def test_fixtures_through_the_device():
             scale = max(NP.abs(inp).max(), 1e-300)
             assert NP.max(NP.abs(cc[0] - g['cc_%d' % i])) <= 1e-12 * scale, i
             assert NP.max(NP.abs(res[0] - g['res_%d' % i])) <= 1e-12 * scale, i
+            want = NP.array(g['rms_%d' % i], dtype=float)
+            if inp.size - int(NP.count_nonzero(box)) <= 2:
+                want[1] = NP.nan                            # the departure: no outrms with <= 2 lags outside the box
+            assert _rms_agrees(rms[0], want), (i, rms[0], want)
             assert st['rows'] == 1 and st['sum_iter'] == it[0]
 
 
@@ -89,6 +99,8 @@ def test_seeded_sweep_against_the_checker():
                 scale = NP.abs(lag[r]).max()
                 assert NP.max(NP.abs(cc[r] - o['cc'])) <= 1e-12 * scale, (m, r)
                 assert NP.max(NP.abs(res[r] - o['res'])) <= 1e-12 * scale, (m, r)
+                want = NP.array([o['inrms'], NP.nan if o['outrms'] is None else o['outrms']], dtype=float)
+                assert _rms_agrees(rms[r], want), (m, r, rms[r], want)
             assert st['sum_iter'] == int(it.sum())
             total += nrows
     assert total >= 2000 and tolerated <= total // 100
