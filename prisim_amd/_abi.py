@@ -396,6 +396,20 @@ class _PrisimMoscleanArgs(C.Structure):
                                              ('poll_every', C.c_int32)]
 
 
+class _PrisimMoscsStats(C.Structure):
+    """prisim_moscs_stats of include/prisim_moscs.h, public as Context.PrisimMoscsStats (see _PrisimCpxpsStats): prisim_csclean_stats
+    with mosaic_ms for dirty_ms, then beam_ms."""
+    _fields_ = [(('mosaic_ms' if n == 'dirty_ms' else n), t) for n, t in _PrisimCscleanStats._fields_] + [('beam_ms', C.c_double)]
+
+
+class _PrisimMoscsArgs(C.Structure):
+    """prisim_moscs_args of include/prisim_moscs.h, public as Context.PrisimMoscsArgs: the fields of prisim_mosclean_args less its
+    polling, then those of the cycles."""
+    _fields_ = [f for f in _PrisimMoscleanArgs._fields_ if f[0] != 'poll_every'] + [
+        ('ny', C.c_int64), ('nx', C.c_int64), ('cycle_depth', C.c_double), ('cycle_niter', C.c_int64), ('max_major', C.c_int32),
+        ('minor_route', C.c_int32)]
+
+
 def numpy_fuses_complex_product(dtype):
     """Whether numpy rounds the real part of a * conj(b) as fma(ar, br, ai bi) (its SIMD complex loop on FMA hardware) rather than
     ar br + ai bi, for complex128 or complex64: probed on a product whose two readings differ (ar br is a tie -- (1 + 2^-26)(1 + 2^-27)
@@ -604,6 +618,7 @@ STRUCTS = {
     'prisim_mosaic_stats': _PrisimMosaicStats, 'prisim_mosaic_args': _PrisimMosaicArgs,
     'prisim_mosclean_stats': _PrisimMoscleanStats, 'prisim_mosclean_args': _PrisimMoscleanArgs,
     'prisim_csclean_stats': _PrisimCscleanStats, 'prisim_csclean_args': _PrisimCscleanArgs,
+    'prisim_moscs_stats': _PrisimMoscsStats, 'prisim_moscs_args': _PrisimMoscsArgs,
 }
 
 # The C ABI, declared once: per header of include/, its functions in the header's order, each as
@@ -751,6 +766,11 @@ _PROTOTYPES = {
             p out_ncomp, p out_status, p out_peak0, p out_wsum, p out_ncycles, p out_cycle_ncomp, p out_cycle_peak, p out_psf, p out_vres,
             *prisim_csclean_stats stats);
     ''',
+    'prisim_moscs.h': '''
+        int prisim_clean_mosaic_cs(p ctx, *prisim_moscs_args a, p out_residual, p out_restored, p out_residual_flat, p out_pb_eff, p out_num,
+            p out_den, p out_wsum, p out_comp_pixel, p out_comp_flux, p out_ncomp, p out_status, p out_peak0, p out_ncycles,
+            p out_cycle_ncomp, p out_cycle_peak, p out_psf, p out_vres, *prisim_moscs_stats stats);
+    ''',
     'prisim_gains.h': '''
         int prisim_gains_eval_spline(p ctx, q nrows, i kx, i ky, p nx, p ny, p kx_off, p ky_off, p c_off, q nknots, p knots, q ncoefs, p coefs,
             q nt, p times, q nchan, p freqs, *p out, *prisim_gains_stats stats);
@@ -789,9 +809,9 @@ FUNCTIONS, HEADER_EXPORTS = _parse_prototypes(_PROTOTYPES)
 # the functions of each header (tests and tools import these names)
 (EXPORTS, CLEAN_EXPORTS, SUBBAND_EXPORTS, RUNS_EXPORTS, CLOSURE_EXPORTS, CPDELAY_EXPORTS, CPBINS_EXPORTS, CPDIFF_EXPORTS, CPFT_EXPORTS,
  CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMCLEAN_EXPORTS, MOSAIC_EXPORTS, MOSCLEAN_EXPORTS, CSCLEAN_EXPORTS,
- GAINS_EXPORTS) = (
+ MOSCS_EXPORTS, GAINS_EXPORTS) = (
     HEADER_EXPORTS['prisim_%s.h' % h] for h in ('hip', 'clean', 'subband', 'runs', 'closure', 'cpdelay', 'cpbins', 'cpdiff', 'cpft', 'cpxps',
-                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imclean', 'mosaic', 'mosclean', 'csclean', 'gains'))
+                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imclean', 'mosaic', 'mosclean', 'csclean', 'moscs', 'gains'))
 
 
 class PrisimHipError(RuntimeError):
@@ -1792,6 +1812,53 @@ class Context(object):
         del keep, keep_ext, win, fw
         return dict(_clean_result(out), residual_flat=flat, pb_eff=pb_eff, num=num, den=den, wsum=wsum,
                     stats=dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident))
+
+    # ---- Cotton-Schwab CLEAN of the beam-weighted mosaic (include/prisim_moscs.h) ----
+    PrisimMoscsStats = _PrisimMoscsStats
+    PrisimMoscsArgs = _PrisimMoscsArgs
+
+    def clean_mosaic_cs(self, unitvec, grid_shape, rot, pc_dircos, baselines, freqs_hz, beam_kind, diameter_m, beam_pc_dircos=(0.0, 0.0, 1.0),
+                        ext=None, cube=None, weights=None, chan_avg=False, aberr_beta=None, pbmin=0.1, gain=0.1, maxiter=10000, threshold=5e-3,
+                        threshold_relative=True, cycle_depth=0.3, cycle_niter=0, max_major=32, window=None, fwhm_rad=None, route='auto',
+                        minor_route='auto', budget_bytes=0, want_psf=False, want_vis=False):
+        """Cotton-Schwab CLEAN of the beam-weighted mosaic of mosaic_image on the device (prisim_clean_mosaic_cs): where clean_mosaic
+        pays a mosaic pass per component, this pays one per major cycle.  A minor cycle cleans the flat-noise image F of one image
+        channel with the shift-invariant beam P of the lattice grid_shape = (ny, nx) (ny * nx = npix, nx fastest), down to cycle_depth
+        of its first peak or cycle_niter components (0: no cap), each component listed with its true flux; the major cycle then takes
+        the new components out of the residual visibilities through the beam of every snapshot and forms the mosaic's numerator of
+        those again, max_major times at most.  The geometry, cube, weights and the beam as mosaic_image takes them; pbmin, gain,
+        maxiter, threshold (in the units of F), threshold_relative, window, fwhm_rad, route and budget_bytes as clean_mosaic takes
+        them; cycle_depth, cycle_niter, max_major and minor_route as clean_image_cs takes them.  Returns the dict of clean_mosaic --
+        'status' may also hold PRISIM_CSCLEAN_MAJOR or _DIVERGED -- with 'ncycles' (nc,) int32, 'cycle_ncomp' int32 (nc, most cycles;
+        -1 past a channel's own), 'cycle_peak' (nc, most cycles + 1; NaN past a channel's own), 'psf' (nc, 2 ny - 1, 2 nx - 1) with
+        want_psf and 'vres' (nt, nbl, nchan) complex128 with want_vis, else None; 'num' is the mosaic's numerator of 'vres'."""
+        a = self.PrisimMoscsArgs()
+        npix, nbl, nchan, nt, resident, keep = _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube, weights, chan_avg,
+                                                               aberr_beta, route, budget_bytes)
+        keep_ext = _mosaic_beam_fields(a, nt, beam_kind, diameter_m, beam_pc_dircos, ext, pbmin)
+        nc = 1 if chan_avg else nchan
+        maxiter, win, fw = _clean_fields(a, npix, nc, gain, maxiter, threshold, threshold_relative, window, fwhm_rad, None)
+        ny, nx = (int(n) for n in grid_shape)
+        a.ny, a.nx, a.cycle_depth, a.cycle_niter, a.max_major = ny, nx, float(cycle_depth), int(cycle_niter or 0), int(max_major)
+        a.minor_route = _route_code(minor_route, CSCLEAN_ROUTES)
+        out = _clean_outputs(npix, nchan, nc, maxiter, chan_avg, fw is not None)
+        flat, pb_eff = NP.empty_like(out['out_residual']), NP.empty_like(out['out_residual'])
+        num, den = NP.empty((npix, nchan), dtype=NP.float64), NP.empty((npix, nchan), dtype=NP.float64)
+        wsum = NP.empty(nchan, dtype=NP.float64)
+        cyc = max(int(max_major), 0)
+        ncycles = NP.empty(nc, dtype=NP.int32)
+        cycle_ncomp = NP.full((nc, cyc), -1, dtype=NP.int32)
+        cycle_peak = NP.full((nc, cyc + 1), NP.nan, dtype=NP.float64)
+        psf = NP.empty((nc, max(2 * ny - 1, 0), max(2 * nx - 1, 0)), dtype=NP.float64) if want_psf else None
+        vres = NP.empty((nt, nbl, nchan), dtype=NP.complex128) if want_vis else None
+        st = self.PrisimMoscsStats()
+        self._call('prisim_clean_mosaic_cs', a=a, out_residual_flat=flat, out_pb_eff=pb_eff, out_num=num, out_den=den, out_wsum=wsum,
+                   out_ncycles=ncycles, out_cycle_ncomp=cycle_ncomp, out_cycle_peak=cycle_peak, out_psf=psf, out_vres=vres, stats=st, **out)
+        del keep, keep_ext, win, fw
+        most = int(ncycles.max()) if nc else 0
+        return dict(_clean_result(out), residual_flat=flat, pb_eff=pb_eff, num=num, den=den, wsum=wsum, ncycles=ncycles,
+                    cycle_ncomp=NP.ascontiguousarray(cycle_ncomp[:, :most]), cycle_peak=NP.ascontiguousarray(cycle_peak[:, :most + 1]),
+                    psf=psf, vres=vres, stats=dict(_stats_dict(st, route=IMAGING_ROUTES, minor_route=CSCLEAN_ROUTES), resident=resident))
 
     # ---- delay spectra of closure phases and their power spectra (include/prisim_cpdelay.h) ----
     def closure_delay_spectra(self, wts, m, df, phases=None, cube=None, legs=None, conj=None, bpwts=None, freq_wts=None, masks=None,

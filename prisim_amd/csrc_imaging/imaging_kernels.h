@@ -73,6 +73,12 @@ __device__ __forceinline__ void cycles_phasor(double x, double& c, double& s) {
   sincospi(2.0 * r, &s, &c);
 }
 
+// the phasor of a point at the offset d from the phase centre on the baseline (b0, b1, b2) = b / c, at the true frequency f
+__device__ __forceinline__ void point_phasor(double b0, double b1, double b2, double4 d, double f, double& c, double& s) {
+  const double tau = (b0 * d.x + b1 * d.y) + b2 * d.z;
+  cycles_phasor(f * tau, c, s);
+}
+
 // The rows of one pass into the accumulators of a pixel: for each of the nb staged baselines, tau = b . d / c and, per channel of the
 // tile, acc[k] += row[k].x cos phi - row[k].y sin phi (PSF: the first product alone), phi = 2 pi f_k tau.  STEPPED seeds the phasor at
 // f0, the tile's first frequency, and steps it by df; DIRECT takes every channel's own frequency from sh_f.

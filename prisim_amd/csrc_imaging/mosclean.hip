@@ -1,7 +1,8 @@
 // mosclean.hip -- CLEAN of the beam-weighted mosaic of the snapshots for gfx950 (include/prisim_mosclean.h, where the mathematics is).
 // It joins what this directory already states and restates none of it: the mosaic's sums (mosaic_kernels.h), the bookkeeping of an
 // image-space CLEAN with the frame of its call (clean_kernels.h), its update by the tile pass of the direct Fourier sum
-// (clean_update.h) and the fused analytic beam (launch_beam_flux by enqueue_mos_beam).  All pixels are resident; one stream.
+// (clean_update.h) and the fused analytic beam (launch_beam_flux by enqueue_mos_beam).  The horizon pass of the beam table and the
+// search image are in mosclean_kernels.h, which prisim_clean_mosaic_cs (moscs.hip) runs too.  All pixels are resident; one stream.
 //
 // Once per call:
 //   k_img_dirs, k_mos_wsum   the directions with their offsets, and the weight sums, as prisim_mosaic_image runs them.
@@ -35,41 +36,9 @@
 #include "../csrc_addon/beam_setup.h"
 #include "../csrc_addon/mosclean_plan.h"
 #include "clean_update.h"
-#include "mosaic_kernels.h"
+#include "mosclean_kernels.h"
 
 namespace {
-
-// grid-stride over count * nchan: the beam is 0 below the horizon
-__global__ void __launch_bounds__(kThreads) k_mosclean_horizon(const double4* __restrict__ s4, int64_t count, int nchan, double* __restrict__ pb) {
-  const int64_t total = count * nchan;
-  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads)
-    if (s4[e / nchan].z < 0.0) pb[e] = 0.0;
-}
-
-// grid-stride over npix * nchan: F = R_N / sqrt(Q Wtot) where Q >= pbmin^2 Wtot, else NaN
-__global__ void __launch_bounds__(kThreads) k_mosclean_flat(const double* __restrict__ N, const double* __restrict__ Q, const double* __restrict__ wtot,
-                                                            int64_t npix, int nchan, double pbmin, double* __restrict__ F) {
-  const int64_t total = npix * nchan;
-  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
-    const double w = wtot[e % nchan], q = Q[e];
-    F[e] = q >= (pbmin * pbmin) * w ? N[e] / sqrt(q * w) : NAN;
-  }
-}
-
-// grid: x over the pixels.  The band: the sums of k_mos_finish_band, k ascending; wband[0] = sum_k wtot[k]
-__global__ void __launch_bounds__(kThreads) k_mosclean_flat_band(const double* __restrict__ N, const double* __restrict__ Q,
-                                                                 const double* __restrict__ wband, int64_t npix, int nchan, double pbmin,
-                                                                 double* __restrict__ F) {
-  const int64_t pl = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (pl >= npix) return;
-  double n = 0.0, q = 0.0;
-  for (int k = 0; k < nchan; ++k) {
-    n += N[pl * nchan + k];
-    q += Q[pl * nchan + k];
-  }
-  const double w = wband[0];
-  F[pl] = q >= (pbmin * pbmin) * w ? n / sqrt(q * w) : NAN;
-}
 
 // the flux of prisim_clean_mosaic: the mosaic value at the pick, from R_N and Q themselves
 struct MosaicFlux {
@@ -162,9 +131,7 @@ int clean_mosaic(prisim_ctx* ctx, const prisim_mosclean_args* a, double* out_res
   for (int64_t t = 0; t < nt; ++t) {
     double* At = d_A + t * npix * nchan;
     if (int rc = enqueue_mos_beam(ctx, *a, t, d_bf, d_s4 + t * npix, npix, T.freqs, d_ones, d_zeros, d_flag, At, s0)) return rc;
-    if (int rc = launch(ctx, k_mosclean_horizon, dim3((unsigned)grid_for(ctx, npix * nchan)), 0, s0, (const double4*)(d_s4 + t * npix), npix,
-                        (int)nchan, At))
-      return rc;
+    if (int rc = enqueue_mosclean_horizon(ctx, d_s4 + t * npix, npix, nchan, At, s0)) return rc;
     M.dd = d_dd + t * npix; M.s4 = d_s4 + t * npix;
     M.pb = At; M.wt = d_wt + t * nchan;
     M.t = t;
@@ -174,15 +141,8 @@ int clean_mosaic(prisim_ctx* ctx, const prisim_mosclean_args* a, double* out_res
   if (call.timed) HIPCHK(ctx, hipEventRecord(tev.e[1], s0));
 
   // ---- the iterations
-  const dim3 pixgrid((unsigned)((npix + kThreads - 1) / kThreads));
   const MosaicFlux flux{d_N, d_Q, (int)nchan, avg ? 1 : 0};
-  auto flat = [&]() -> int {
-    if (avg)
-      return launch(ctx, k_mosclean_flat_band, pixgrid, 0, s0, (const double*)d_N, (const double*)d_Q, (const double*)d_wband, npix, (int)nchan,
-                    a->pbmin, d_F);
-    return launch(ctx, k_mosclean_flat, dim3((unsigned)grid_for(ctx, npix * nchan)), 0, s0, (const double*)d_N, (const double*)d_Q,
-                  (const double*)d_wtot, npix, (int)nchan, a->pbmin, d_F);
-  };
+  auto flat = [&]() -> int { return enqueue_mosclean_flat(ctx, avg, d_N, d_Q, d_wtot, d_wband, npix, nchan, a->pbmin, d_F, s0); };
   auto search = [&](bool first) -> int {
     if (int rc = flat()) return rc;
     if (int rc = call.search(d_F)) return rc;

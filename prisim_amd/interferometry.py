@@ -3189,3 +3189,69 @@ class ApertureSynthesis(object):
                                  route=route, budget_bytes=int(budget_bytes or 0))
         self.image_stats = dict(r['stats'], num=r['num'], den=r['den'], wsum=r['wsum'], pb_eff=r['pb_eff'])
         return dict(self._clean_dict(r, npix, nc, chan_avg, restore, threshold, threshold_type, fwhm_rad), residual_flat=r['residual_flat'])
+
+    def clean_mosaic_cotton_schwab(self, directions, grid_shape, coords='dircos', datakey='noiseless', weights=None, chan_avg=False, epoch=None,
+                                   telescope=None, pb_info=None, pbmin=0.1, gain=0.1, maxiter=10000, threshold=5e-3, threshold_type='relative',
+                                   window=None, fwhm=None, restore=True, cycle_depth=0.3, cycle_niter=None, max_major=32, return_vis=False,
+                                   route='auto', minor_route='auto', budget_bytes=None):
+        """Cotton-Schwab CLEAN of mosaic(), on the GPU (include/prisim_moscs.h): clean_mosaic() pays a full mosaic pass over all
+        snapshots for every component; this pays one per major cycle, as clean_cotton_schwab() does for clean().  A minor cycle cleans
+        the flat-noise image F = num / sqrt(den wsum) of one channel with the shift-invariant beam of the lattice grid_shape: in F a
+        component answers with at most its own amplitude anywhere, and near its pixel with the synthesized beam, so the step of
+        clean_cotton_schwab() serves; each component is listed with its true flux.  The major cycle then takes the new components out
+        of the residual visibilities through the beam of every snapshot, as observe() would simulate them, and forms the mosaic's
+        numerator of those again: what the minor cycle's beam leaves out -- the drift and chromaticity of the beam, the curvature of
+        the grid, aberration, the w-term -- is corrected there, and after every major cycle, and at the end, the residual is the
+        mosaic of the visibilities less those of the components, as clean_mosaic()'s is.
+
+        directions, coords, datakey, weights, chan_avg, epoch, telescope, pb_info, pbmin, gain, maxiter, threshold, threshold_type,
+        window, fwhm, restore, route and budget_bytes as clean_mosaic() takes them; grid_shape, cycle_depth, cycle_niter, max_major,
+        return_vis and minor_route as clean_cotton_schwab() takes them.
+        Returns the dict of clean_mosaic() -- 'status' may also hold _abi.PRISIM_CSCLEAN_MAJOR or _DIVERGED -- and 'cycles': {'count'
+        (nc,), 'ncomp' (nc, most cycles; -1 past a channel's own), 'peak' (nc, most cycles + 1; NaN past a channel's own, in the units
+        of F)}, and 'residual_vis' (nbl, nchan, n_acc) complex128 or None.  num (the mosaic's numerator of the residual visibilities),
+        den, wsum, pb_eff and the entry's statistics are left in image_stats.
+
+        Raises NotImplementedError for an array with an external beam (set_external_beam) and for the apertures device_beam_spec
+        does not carry (rect, square)."""
+        from . import delay_spectrum as DS                            # (imports this module)
+        ia = self.ia
+        if getattr(ia, '_extbeam', None) is not None:
+            raise NotImplementedError('clean_mosaic_cotton_schwab() evaluates the analytic beams; the array has an external beam '
+                                      '(set_external_beam)')
+        threshold = DS._check_clean_args(threshold_type, threshold, gain, maxiter)
+        DS._check_gain_maxiter(gain, maxiter)
+        pbmin = float(pbmin)
+        if not (0.0 <= pbmin < 1.0):
+            raise ValueError('pbmin must lie in [0, 1)')
+        if not isinstance(cycle_depth, float) or not (0.0 < cycle_depth < 1.0):
+            raise ValueError('cycle_depth must be a float in (0, 1)')
+        if cycle_niter is not None and (not isinstance(cycle_niter, (int, NP.integer)) or isinstance(cycle_niter, bool) or cycle_niter < 1):
+            raise ValueError('cycle_niter must be None or a positive int')
+        if not isinstance(max_major, (int, NP.integer)) or isinstance(max_major, bool) or not (0 <= max_major <= 65536):
+            raise ValueError('max_major must be an int in [0, 65536]')
+        if minor_route not in ('auto', 'lds', 'global'):
+            raise ValueError("minor_route must be 'auto', 'lds' or 'global'")
+        uv, rot, beta, pc, w, cube = self._prepare('dirty', directions, coords, datakey, weights, epoch, route)
+        kind, dia, bpc, ext = self._beam_specs(telescope, pb_info)
+        npix, nchan = uv.shape[0], ia.channels.size
+        try:
+            ny, nx = (int(n) for n in grid_shape)
+        except (TypeError, ValueError):
+            raise ValueError('grid_shape must be (ny, nx)')
+        if ny < 1 or nx < 1 or ny * nx != npix:
+            raise ValueError('grid_shape must be (ny, nx) with ny * nx the number of directions')
+        nc = 1 if chan_avg else nchan
+        bl = ia._baselines_local()
+        win, fwhm_rad = self._window_and_fwhm(window, fwhm, npix, nc, chan_avg, bl)
+        r = ia._ctx.clean_mosaic_cs(uv, (ny, nx), rot, pc, bl, ia.channels, kind, dia, beam_pc_dircos=bpc, ext=ext, cube=cube, weights=w,
+                                    chan_avg=bool(chan_avg), aberr_beta=beta, pbmin=pbmin, gain=gain, maxiter=maxiter, threshold=threshold,
+                                    threshold_relative=threshold_type == 'relative', cycle_depth=cycle_depth,
+                                    cycle_niter=int(cycle_niter or 0), max_major=int(max_major), window=win,
+                                    fwhm_rad=fwhm_rad if restore else None, route=route, minor_route=minor_route,
+                                    budget_bytes=int(budget_bytes or 0), want_vis=bool(return_vis))
+        self.image_stats = dict(r['stats'], num=r['num'], den=r['den'], wsum=r['wsum'], pb_eff=r['pb_eff'])
+        out = dict(self._clean_dict(r, npix, nc, chan_avg, restore, threshold, threshold_type, fwhm_rad), residual_flat=r['residual_flat'])
+        out['cycles'] = {'count': NP.asarray(r['ncycles']), 'ncomp': r['cycle_ncomp'], 'peak': r['cycle_peak']}
+        out['residual_vis'] = NP.ascontiguousarray(NP.transpose(r['vres'], (1, 2, 0))) if return_vis else None
+        return out
