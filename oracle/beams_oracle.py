@@ -25,8 +25,11 @@ def _angles(skypos_altaz, pointing_altaz):
         pc = NP.asarray(pointing_altaz, dtype=NP.float64).ravel()
         a1, z1 = NP.radians(skypos[:, 0]), NP.radians(skypos[:, 1])
         a0, z0 = NP.radians(pc[0]), NP.radians(pc[1])
-        cosx = NP.sin(a1) * NP.sin(a0) + NP.cos(a1) * NP.cos(a0) * NP.cos(z1 - z0)
-        x = NP.arccos(NP.clip(cosx, -1.0, 1.0))                           # GEOM.sphdist, :605 / :712
+        # GEOM.sphdist, :605 / :712 -- the angle as atan2(|s x p|, s . p): arccos of the dot product loses the angle below 1.5e-8 rad
+        # of the pointing centre (1.4e-11 of the D = 300 m Airy power there, tests/test_beam_reference.py)
+        s = NP.stack((NP.cos(a1) * NP.sin(z1), NP.cos(a1) * NP.cos(z1), NP.sin(a1)), axis=1)
+        p = NP.array([NP.cos(a0) * NP.sin(z0), NP.cos(a0) * NP.cos(z0), NP.sin(a0)])
+        x = NP.arctan2(NP.linalg.norm(NP.cross(s, p), axis=1), s @ p)
         zero_ind = NP.logical_or(x >= NP.pi / 2, skypos[:, 0] <= 0.0)     # :607 / :714
     return x, zero_ind
 

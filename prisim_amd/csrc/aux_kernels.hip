@@ -19,6 +19,21 @@ namespace prisim {
 static constexpr double kC = 299792458.0;
 static constexpr double kPi = 3.14159265358979323846;
 
+// One axis of the isotropic-radiator array factor, sin(n phi/2) / (n sin(phi/2)) with phi = 2 pi c (primary_beams.py:1465-1471), from
+// the phase in CYCLES reduced to [-1/2, 1/2] first, as the beamformer branch below reduces its own.  The literal statement is noise at a
+// grating lobe (c an integer to rounding) unless n is a power of two: 0.5 n phi rounds while sin(phi/2) is about 1e-16 -- order one at
+// the lobe, 1e-9 at a relative distance of 1e-7 (tests/test_beam_reference.py keeps that on record).  Taking m = rint(c)
+// out turns the quotient by (-1)^((n - 1) m), put back here: the power does not see it, the field does.  The reference's
+// |phi| < 1e-10 branch is kept as it is.
+__device__ __forceinline__ double array_term(int n, double phi, double c) {
+  const double dn = (double)n;
+  if (fabs(phi) < 1e-10) return cos(0.5 * dn * phi) / cos(0.5 * phi);                     // :1466-1467 / :1470-1471
+  const double m = rint(c);
+  c -= m;
+  const double t = c == 0.0 ? 1.0 : sinpi(dn * c) / sinpi(c) / dn;                        // :1465 / :1469
+  return (((n - 1) & 1) && ((long long)m & 1)) ? -t : t;
+}
+
 // thread per (source, channel); channel fastest (coalesced store of pb_out[s][f]).  The launchers make the total thread count a
 // multiple of nchan, so a thread keeps ONE channel over its whole grid-stride loop and everything that depends on the frequency alone
 // -- the wavenumber, the on-axis normalisation 2 J1(x0) / x0 of the Airy pattern (a second Bessel function per element otherwise), the
@@ -104,10 +119,7 @@ __device__ __forceinline__ void beam_flux_body(BeamParams p) {
       const double ry = (-p.rot_s * d.x + p.rot_c * d.y) - (-p.rot_s * p.apc_x + p.rot_c * p.apc_y);
       const double phi = 2.0 * kPi * p.sep1 * rx / lam;                                   // :1458
       const double psi = 2.0 * kPi * p.sep2 * ry / lam;                                   // :1459
-      const double n1 = (double)p.nax1, n2 = (double)p.nax2;
-      const double t1 = fabs(phi) < 1e-10 ? cos(0.5 * n1 * phi) / cos(0.5 * phi) : sin(0.5 * n1 * phi) / sin(0.5 * phi) / n1;   // :1465-1467
-      const double t2 = fabs(psi) < 1e-10 ? cos(0.5 * n2 * psi) / cos(0.5 * psi) : sin(0.5 * n2 * psi) / sin(0.5 * psi) / n2;   // :1469-1471 (nax2)
-      af = t1 * t2;
+      af = array_term(p.nax1, phi, p.sep1 * rx / lam) * array_term(p.nax2, psi, p.sep2 * ry / lam);       // :1465-1471 (nax2)
     }
     double pb = (ep * af) * (ep * af);                                                    // :317 / :349 / :416
     if (EXTRAS && p.bf_nelem > 0) {
