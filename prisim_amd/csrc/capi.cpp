@@ -177,6 +177,24 @@ int prisim_hip_set_array(prisim_ctx* ctx, const double* bl_enu, int64_t nbl, con
   if (nbl > (int64_t)1 << 30 || nchan > (int64_t)1 << 24) return fail(ctx, PRISIM_EINVAL, "nbl or nchan too large");
   for (int64_t i = 0; i < nchan; ++i)
     if (!std::isfinite(freqs_hz[i])) return fail(ctx, PRISIM_EINVAL, "non-finite channel frequency");
+  {
+    // The phase range of the kernels (prisim_hip.h): they take the quadrant of 4 x phase with (int)q, so |4 phase| < 2^31 must hold for
+    // every term; |s - s_pc| <= 2 for unit vectors, so max|b| 2 max|f| / c < 2^29 cycles guarantees it.  Refused here, on the host,
+    // before any state changes: no kernel ever runs past the range.  (A non-finite length is left to the per-component
+    // check below.)
+    double lmax = 0.0, fmax = 0.0;
+    for (int64_t b = 0; b < nbl; ++b) {
+      const double len = std::sqrt(bl_enu[3 * b] * bl_enu[3 * b] + bl_enu[3 * b + 1] * bl_enu[3 * b + 1] + bl_enu[3 * b + 2] * bl_enu[3 * b + 2]);
+      if (std::isfinite(len)) lmax = std::max(lmax, len);
+    }
+    for (int64_t i = 0; i < nchan; ++i) fmax = std::max(fmax, std::fabs(freqs_hz[i]));
+    const double cycles = lmax * 2.0 * fmax / kC;
+    if (cycles >= 536870912.0) {
+      char msg[200];
+      snprintf(msg, sizeof msg, "phase range: max|b| * 2 * max|f| / c = %.6g cycles, the limit is below 2^29 = 536870912 cycles", cycles);
+      return fail(ctx, PRISIM_EINVAL, msg);
+    }
+  }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->array_set = false;

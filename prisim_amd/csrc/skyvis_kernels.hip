@@ -1476,6 +1476,13 @@ __device__ __forceinline__ void skyvis_rec_f32pk_body(const SkyvisParams& p, uns
         const float gqf = (float)gq;
         tB = gqf * kBf;
         tC = gqf * kCf;
+        if constexpr (!SPLIT) {
+          // A source this tile resolves out altogether: L(j) <= A + |B| HC (C <= 0) is below the smallest fp32 denormal on every channel,
+          // so the chain is zero from its seed (exp2(A) = 0) whatever the ratios -- which must then not be formed from B and C: at
+          // thousands of octaves exp2(-B + ...) is inf and 0 * inf = NaN (the exact form), exp2(2 C) - 1 leaves its series.  Found by
+          // tests/test_gpu_skyvis_reference.py (30-degree sources on 1.2 km, 0.02-degree sources on 2400 km baselines).
+          if (tA + __builtin_fabsf(tB) * (float)HC < -150.f) { tB = 0.f; tC = 0.f; }
+        }
         tA_keep = tA;
         float w_u0, w_d0;
         if constexpr (SPLIT) {
