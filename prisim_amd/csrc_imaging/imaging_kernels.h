@@ -11,6 +11,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -192,6 +193,24 @@ inline int check_args(prisim_ctx* ctx, const ImgView& a) {
       return fail(ctx, PRISIM_EINVAL, "unitvec[" + std::to_string(p) + "] does not have unit length (to 1e-6)");
   for (int64_t i = 0; i < a.nbl * 3; ++i)
     if (!std::isfinite(a.baselines[i])) return fail(ctx, PRISIM_EINVAL, "baseline " + std::to_string(i / 3) + " is not finite");
+  {
+    // The phase range, by the rule and in the sentence of prisim_hip_set_array (../csrc/capi.cpp): |s - s0| <= 2 for unit vectors, so
+    // below max|b| 2 max|f| / c = 2^29 cycles a phase keeps 2^-23 of a cycle and more in cycles_phasor's x - rint(x); past 2^52 cycles
+    // that fraction would be 0 and every phasor 1.  Refused here, on the host and before any launch.
+    double lmax = 0.0, fmax = 0.0;
+    for (int64_t b = 0; b < a.nbl; ++b) {
+      const double* v = a.baselines + b * 3;
+      const double len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+      if (std::isfinite(len)) lmax = std::fmax(lmax, len); else lmax = INFINITY;   // finite components whose square overflows
+    }
+    for (int64_t f = 0; f < a.nchan; ++f) fmax = std::fmax(fmax, a.freqs_hz[f]);
+    const double cycles = lmax * 2.0 * fmax / 299792458.0;
+    if (!(cycles < 536870912.0)) {
+      char msg[200];
+      snprintf(msg, sizeof msg, "phase range: max|b| * 2 * max|f| / c = %.6g cycles, the limit is below 2^29 = 536870912 cycles", cycles);
+      return fail(ctx, PRISIM_EINVAL, msg);
+    }
+  }
   for (int64_t t = 0; t < a.nt; ++t) {
     const double* R = a.rot + t * 9;
     for (int r = 0; r < 3; ++r)

@@ -94,7 +94,7 @@ def f64_bound(r, scale):
 
 
 # ---- doubles as integers -------------------------------------------------------------------------------------------------------------
-def _ints(a):
+def ints(a):
     """(object array of Python ints n, k) with a == n * 2**-k exactly, element by element."""
     a = NP.asarray(a, dtype=NP.float64)
     m, e = NP.frexp(a)
@@ -121,12 +121,12 @@ def _int_to_ld(n, k):
     return sign * NP.ldexp(v, sh - k)
 
 
-def _to_ld(v):
+def to_ld(v):
     hi = float(v)
     return LD(hi) + LD(float(v - hi))
 
 
-def _ld_to_mp(v):
+def ld_to_mp(v):
     hi = float(v)
     return MP.mpf(hi) + MP.mpf(float(v - LD(hi)))
 
@@ -138,7 +138,7 @@ def _kappa_mp(fwhm_deg):
 
 
 # ---- the fast route ------------------------------------------------------------------------------------------------------------------
-def _frac_cycles(num, k):
+def frac_cycles(num, k):
     """num * 2**-k / c modulo one cycle, in [-1/2, 1/2), as longdouble; num an object array of ints."""
     if k < 0:
         num, k = num * (1 << -k), 0
@@ -163,17 +163,17 @@ def reference(bl, ch, dc, pb, pc, fwhm_deg=None, diff=None):
     pb = NP.ascontiguousarray(pb, dtype=NP.float64).reshape(dc.shape[0], ch.size)
     pc = NP.ascontiguousarray(pc, dtype=NP.float64).ravel()
     nbl, nchan, nsrc = bl.shape[0], ch.size, dc.shape[0]
-    B, kb = _ints(bl)
-    F, kf = _ints(ch)
-    SP, kd = _ints(NP.vstack((dc, pc[None, :], (NP.zeros(3) if diff is None else NP.asarray(diff, dtype=NP.float64))[None, :])))
+    B, kb = ints(bl)
+    F, kf = ints(ch)
+    SP, kd = ints(NP.vstack((dc, pc[None, :], (NP.zeros(3) if diff is None else NP.asarray(diff, dtype=NP.float64))[None, :])))
     S, P, DV = SP[:nsrc], SP[nsrc], SP[nsrc + 1]
     D = NP.empty((nsrc, 3), dtype=object)
     for s in range(nsrc):
         for i in range(3):
             D[s, i] = DV[i] if diff is not None else S[s, i] - P[i]
     M = D[:, None, 0] * B[None, :, 0] + D[:, None, 1] * B[None, :, 1] + D[:, None, 2] * B[None, :, 2]          # [s][b], 2^-(kb + kd)
-    frac = _frac_cycles(M[:, :, None] * F[None, None, :], kb + kd + kf)                                        # [s][b][f]
-    ang = frac * (LD(2) * _to_ld(MP.pi))
+    frac = frac_cycles(M[:, :, None] * F[None, None, :], kb + kd + kf)                                        # [s][b][f]
+    ang = frac * (LD(2) * to_ld(MP.pi))
     amp = pb.astype(LD)[:, None, :] * NP.ones((1, nbl, 1), dtype=LD)
     if fwhm_deg is not None:
         fw = NP.ascontiguousarray(fwhm_deg, dtype=NP.float64).ravel()
@@ -184,7 +184,7 @@ def reference(bl, ch, dc, pb, pc, fwhm_deg=None, diff=None):
             kap = _kappa_mp(fw[s])
             if kap is None:
                 continue
-            kap = _to_ld(kap)
+            kap = to_ld(kap)
             for b in range(nbl):
                 p2 = B2[b] * (1 << (2 * kd)) - BS[s, b] * BS[s, b] if kd >= 0 else B2[b] - BS[s, b] * BS[s, b] * (1 << (-2 * kd))
                 perp2 = _int_to_ld(max(p2, 0), 2 * kb + (2 * kd if kd >= 0 else 0))
@@ -242,7 +242,7 @@ def route_gap(case, ref, nsample=24, seed=0):
     worst = 0.0
     for (b, k), want in zip(outs, reference_mp(case.bl, case.ch, case.dc, case.pb, case.pc, case.fw, outs)):
         for (re, im), w in zip((ref.v_ld,) + tuple(ref.g_ld), want):
-            gap = abs(MP.mpc(_ld_to_mp(re[b, k]), _ld_to_mp(im[b, k])) - w)
+            gap = abs(MP.mpc(ld_to_mp(re[b, k]), ld_to_mp(im[b, k])) - w)
             if ref.S[k] == 0.0:                                          # the zero-flux row alone: both routes give 0 exactly
                 assert gap == 0
                 continue

@@ -79,23 +79,25 @@ def same_bits(a, b):
 def test_g1_no_cycle_and_no_component_leave_the_dirty_image_bit_for_bit(ctx, form):
     c, _ = case(SHAPES[2])
     w = weights_of(c, form)
-    for chan_avg in (False, True):
-        for route in ('direct', 'stepped'):
-            want, wsum, _ = ctx.dirty_image(c['unitvec'], c['rot'], c['pc'], c['baselines'], c['freqs'], cube=c['cube'], weights=w,
-                                            aberr_beta=c['beta'], chan_avg=chan_avg, route=route)
-            nc = 1 if chan_avg else K + 1
-            for kw, status in ((dict(max_major=0, maxiter=25), MAJOR), (dict(max_major=4, maxiter=0), MAXITER), (dict(max_major=0, maxiter=0), MAXITER)):
-                got = run(ctx, c, weights=w, chan_avg=chan_avg, route=route, threshold=0.0, threshold_relative=False, want_vis=True, **kw)
-                assert got['residual'].shape == want.shape and NP.array_equal(got['residual'], want), (form, chan_avg, route, kw)
-                assert NP.array_equal(got['wsum'], wsum) and got['restored'] is None and NP.array_equal(got['vres'], c['cube'])
-                assert got['comp_pixel'].shape == (nc, 0) and NP.all(got['ncomp'] == 0) and NP.all(got['ncycles'] == 0)
-                assert NP.all(got['status'] == status) and got['cycle_ncomp'].shape == (nc, 0)
-                peak = NP.abs(want).reshape(want.shape[0], nc).max(axis=0)
-                assert NP.array_equal(got['peak0'], peak) and NP.array_equal(got['cycle_peak'], peak[:, None])
-                st = got['stats']
-                assert st['route'] == route and st['cycles'] == 0 and st['components'] == 0 and st['polls'] == 1 and st['resident'] is False
-                assert st['terms'] == 1000 * 37 * (K + 1) * 3 and st['minor_route'] == 'lds' and st['minor_lds_bytes'] == 8064
-                assert st['psf_offsets'] == 25 * 79 - 40 + 1
+    for scale in (1.0, 1000.0):                                       # to 300 m, and to 300 km where tests/imaging_reference.py holds the image
+        c = dict(c, baselines=c['baselines'] * scale)
+        for chan_avg in (False, True):
+            for route in ('direct', 'stepped'):
+                want, wsum, _ = ctx.dirty_image(c['unitvec'], c['rot'], c['pc'], c['baselines'], c['freqs'], cube=c['cube'], weights=w,
+                                                aberr_beta=c['beta'], chan_avg=chan_avg, route=route)
+                nc = 1 if chan_avg else K + 1
+                for kw, status in ((dict(max_major=0, maxiter=25), MAJOR), (dict(max_major=4, maxiter=0), MAXITER), (dict(max_major=0, maxiter=0), MAXITER)):
+                    got = run(ctx, c, weights=w, chan_avg=chan_avg, route=route, threshold=0.0, threshold_relative=False, want_vis=True, **kw)
+                    assert got['residual'].shape == want.shape and NP.array_equal(got['residual'], want), (form, scale, chan_avg, route, kw)
+                    assert NP.array_equal(got['wsum'], wsum) and got['restored'] is None and NP.array_equal(got['vres'], c['cube'])
+                    assert got['comp_pixel'].shape == (nc, 0) and NP.all(got['ncomp'] == 0) and NP.all(got['ncycles'] == 0)
+                    assert NP.all(got['status'] == status) and got['cycle_ncomp'].shape == (nc, 0)
+                    peak = NP.abs(want).reshape(want.shape[0], nc).max(axis=0)
+                    assert NP.array_equal(got['peak0'], peak) and NP.array_equal(got['cycle_peak'], peak[:, None])
+                    st = got['stats']
+                    assert st['route'] == route and st['cycles'] == 0 and st['components'] == 0 and st['polls'] == 1 and st['resident'] is False
+                    assert st['terms'] == 1000 * 37 * (K + 1) * 3 and st['minor_route'] == 'lds' and st['minor_lds_bytes'] == 8064
+                    assert st['psf_offsets'] == 25 * 79 - 40 + 1
 
 
 @pytest.mark.parametrize('form', FORMS)

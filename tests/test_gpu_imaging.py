@@ -3,9 +3,11 @@ against the numpy checker (tests/imaging_checker.py), the NaN of a channel witho
 through prisim_amd.interferometry.ApertureSynthesis against the project's own sky-sum (the dot-product identity) and a point source.
 
 Bounds.  The project's tolerance for the fp64 sky-sum, 1e-11 of the natural scale (README), here sum_{t,b} w|V| / sum w per channel
-(per image with chan_avg; 1 for the synthesized beam): every element of every image is held to it against the checker, which itself
-agrees with an extended-precision evaluation to 1e-14 of that scale on these shapes (tests/test_imaging.py).  The two routes are
-within twice that of each other.  The dot-product identity carries the bound once for the sky-sum and once for the image:
+(per image with chan_avg; 1 for the synthesized beam): every element of every image is held to it against the checker.  That checker
+agrees to 1e-14 of the scale with its own phase and sum arithmetic redone in longdouble (tests/test_imaging.py) -- from float64
+directions in both arms, on these baselines of 300 m at most: no independent check of the directions, and none of long baselines.
+Both are in tests/test_gpu_imaging_reference.py, against the 40-digit reference of tests/imaging_reference.py out to 2400 km, where
+this checker itself is past 1e-11 from 300 km on.  The two routes are within twice the bound of each other.  The dot-product identity carries the bound once for the sky-sum and once for the image:
 2e-11 sum|x| sum w|V|.  No element is left out of any comparison."""
 import os
 import sys
@@ -193,7 +195,10 @@ def test_g1_the_three_entries_refuse_a_shared_argument_alike(ctx):
     faults = [({'unitvec': changed('unitvec', (3, 0), 1.5)}, 'unitvec[3]'), ({'rot': changed('rot', (1, 4), 0.5)}, 'rot of snapshot 1'),
               ({'aberr_beta': changed('beta', (2, 1), 0.02)}, 'aberr_beta of snapshot 2'),
               ({'weights': changed('w_full', (1, 2, 3), -1.0)}, 'finite and non-negative'), ({'nchan': 0}, '>= 1'),
-              ({'route': 2}, 'unknown route')]
+              ({'route': 2}, 'unknown route'),
+              # the phase range, in the sentence of prisim_hip_set_array: 2^29 cycles of max|b| 2 max|f| / c and beyond
+              ({'baselines': changed('baselines', (4, 1), 6e8)}, 'phase range: max|b| * 2 * max|f| / c = '),
+              ({'baselines': changed('baselines', (4, 1), 1e200)}, 'the limit is below 2^29 = 536870912 cycles')]
     for kw, msg in faults:
         answers = {name: entry(name, **kw) for name in own}
         assert len(set(answers.values())) == 1, (list(kw), answers)

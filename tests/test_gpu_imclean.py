@@ -63,20 +63,22 @@ def same_bits(a, b):
 def test_g1_no_iterations_leave_the_dirty_image_bit_for_bit(ctx, form):
     c, _ = case(SHAPES[2])
     w = weights_of(c, form)
-    for chan_avg in (False, True):
-        for route in ('direct', 'stepped'):
-            want, wsum, _ = ctx.dirty_image(c['unitvec'], c['rot'], c['pc'], c['baselines'], c['freqs'], cube=c['cube'], weights=w,
-                                            aberr_beta=c['beta'], chan_avg=chan_avg, route=route)
-            got = run(ctx, c, weights=w, chan_avg=chan_avg, route=route, maxiter=0, threshold=0.0, threshold_relative=False)
-            nc = 1 if chan_avg else K + 1
-            assert got['residual'].shape == want.shape and NP.array_equal(got['residual'], want), (form, chan_avg, route)
-            assert NP.array_equal(got['wsum'], wsum) and got['restored'] is None
-            assert got['comp_pixel'].shape == (nc, 0) and got['comp_flux'].shape == (nc, 0) and NP.all(got['ncomp'] == 0)
-            assert NP.all(got['status'] == MAXITER)                   # a peak above the threshold and no component allowed
-            assert NP.array_equal(got['peak0'], NP.abs(want).reshape(want.shape[0], nc).max(axis=0))
-            st = got['stats']
-            assert st['route'] == route and st['iterations'] == 0 and st['components'] == 0 and st['polls'] == 1 and st['resident'] is False
-            assert st['terms'] == 1000 * 37 * (K + 1) * 3 and st['chan_tile'] == K and st['block_pixels'] == 256 and st['lds_bytes'] == 17792
+    for scale in (1.0, 1000.0):                                       # to 300 m, and to 300 km where tests/imaging_reference.py holds the image
+        c = dict(c, baselines=c['baselines'] * scale)
+        for chan_avg in (False, True):
+            for route in ('direct', 'stepped'):
+                want, wsum, _ = ctx.dirty_image(c['unitvec'], c['rot'], c['pc'], c['baselines'], c['freqs'], cube=c['cube'], weights=w,
+                                                aberr_beta=c['beta'], chan_avg=chan_avg, route=route)
+                got = run(ctx, c, weights=w, chan_avg=chan_avg, route=route, maxiter=0, threshold=0.0, threshold_relative=False)
+                nc = 1 if chan_avg else K + 1
+                assert got['residual'].shape == want.shape and NP.array_equal(got['residual'], want), (form, scale, chan_avg, route)
+                assert NP.array_equal(got['wsum'], wsum) and got['restored'] is None
+                assert got['comp_pixel'].shape == (nc, 0) and got['comp_flux'].shape == (nc, 0) and NP.all(got['ncomp'] == 0)
+                assert NP.all(got['status'] == MAXITER)                   # a peak above the threshold and no component allowed
+                assert NP.array_equal(got['peak0'], NP.abs(want).reshape(want.shape[0], nc).max(axis=0))
+                st = got['stats']
+                assert st['route'] == route and st['iterations'] == 0 and st['components'] == 0 and st['polls'] == 1 and st['resident'] is False
+                assert st['terms'] == 1000 * 37 * (K + 1) * 3 and st['chan_tile'] == K and st['block_pixels'] == 256 and st['lds_bytes'] == 17792
 
 
 @pytest.mark.parametrize('form', FORMS)

@@ -104,16 +104,18 @@ def test_m2_delta_beam_on_one_snapshot_has_the_bits_of_the_dirty_image(ctx):
     c = MC.up_case(37, K + 1, 300, 1)
     assert NP.min(IK.directions(c['unitvec'], c['rot'], c['beta'])[..., 2]) > 0.04
     delta = MC.beam_setups(1)['delta']
-    for weights in (None, c['w_bl'], c['w_full']):
-        for route in ('direct', 'stepped'):
-            for chan_avg in (False, True):
-                mosaic, num, den, wsum, st = call(ctx, c, delta, weights=weights, route=route, chan_avg=chan_avg)
-                img, wimg, _ = ctx.dirty_image(c['unitvec'], c['rot'], c['pc'], c['baselines'], c['freqs'], cube=c['cube'], weights=weights,
-                                               aberr_beta=c['beta'], route=route, chan_avg=chan_avg)
-                assert NP.all(NP.isfinite(img)) and NP.array_equal(mosaic, img), (route, chan_avg)
-                assert NP.array_equal(den, NP.broadcast_to(wsum, den.shape))
-                assert chan_avg or NP.array_equal(wsum, wimg)
-                assert NP.array_equal(st['pb_eff'], NP.ones_like(mosaic))
+    for scale in (1.0, 1000.0):                                       # to 300 m, and to 300 km where tests/imaging_reference.py holds the image
+        c = dict(c, baselines=c['baselines'] * scale)
+        for weights in (None, c['w_bl'], c['w_full']):
+            for route in ('direct', 'stepped'):
+                for chan_avg in (False, True):
+                    mosaic, num, den, wsum, st = call(ctx, c, delta, weights=weights, route=route, chan_avg=chan_avg)
+                    img, wimg, _ = ctx.dirty_image(c['unitvec'], c['rot'], c['pc'], c['baselines'], c['freqs'], cube=c['cube'], weights=weights,
+                                                   aberr_beta=c['beta'], route=route, chan_avg=chan_avg)
+                    assert NP.all(NP.isfinite(img)) and NP.array_equal(mosaic, img), (scale, route, chan_avg)
+                    assert NP.array_equal(den, NP.broadcast_to(wsum, den.shape))
+                    assert chan_avg or NP.array_equal(wsum, wimg)
+                    assert NP.array_equal(st['pb_eff'], NP.ones_like(mosaic))
 
 
 # ---- M3: the horizon and the mask -----------------------------------------------------------------------------------------------------------

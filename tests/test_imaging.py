@@ -1,7 +1,14 @@
 """CPU: dirty images and synthesized beams by the direct Fourier sum (include/prisim_imaging.h) -- the export (tests/test_abi_headers.py holds
 the ctypes mirrors, the constants and the prototype to the header), the planning header compiled alone, the class
 prisim_amd.interferometry.ApertureSynthesis against a stand-in context that answers dirty_image with the numpy checker
-(tests/imaging_checker.py), and the checker itself against an extended-precision evaluation, a stepped phasor and two closed forms.
+(tests/imaging_checker.py), and the checker itself against its own arithmetic in longdouble, a stepped phasor and two closed forms.
+
+What the longdouble comparison covers.  It evaluates the phases and the sums of the checker in longdouble, from directions
+normalise(R (u + beta)) that BOTH arms form in float64, on baselines to 300 m (250 cycles): it holds the checker's phase and sum
+arithmetic at that length and nothing else.  It is not independent of the directions, whose rounding acts on the whole baseline in
+wavelengths, and it says nothing beyond 300 m: tests/imaging_reference.py is the independent reference (directions at 60 digits,
+phases reduced exactly), and tests/test_imaging_reference.py measures this checker against it per decade -- inside 1e-11 of the scale
+up to 30 km, outside from 300 km on.
 
 Bounds of the checker's self-tests.  A term of the sum carries the rounding of its phase: up to 1.3e3 rad here, formed by a handful
 of fp64 operations of 1.1e-16 each, so at most some 1e-12 of the term and far less of the sum, where the roundings average out.
