@@ -98,6 +98,8 @@ PRISIM_IMAGE_AUTO, PRISIM_IMAGE_DIRECT, PRISIM_IMAGE_STEPPED = -1, 0, 1
 PRISIM_IMAGE_W_NONE, PRISIM_IMAGE_W_BASELINE, PRISIM_IMAGE_W_FULL = 0, 1, 2
 IMAGING_ROUTES = {PRISIM_IMAGE_DIRECT: 'direct', PRISIM_IMAGE_STEPPED: 'stepped'}
 IMAGING_KINDS = {'dirty': PRISIM_IMAGE_DIRTY, 'psf': PRISIM_IMAGE_PSF}
+# ... and their fp32 route (include/prisim_imaging32.h, prisim_amd/csrc_imaging/imaging32.hip): the entry of each precision
+IMAGING_PRECISIONS = {'double': 'prisim_dirty_image', 'single': 'prisim_dirty_image_f32'}
 
 # Hogbom CLEAN of dirty images with the exact beam (include/prisim_imclean.h, prisim_amd/csrc_imaging/imclean.hip)
 PRISIM_IMCLEAN_THRESHOLD, PRISIM_IMCLEAN_MAXITER, PRISIM_IMCLEAN_DEAD = 1, 2, 4
@@ -749,6 +751,9 @@ _PROTOTYPES = {
     'prisim_imaging.h': '''
         int prisim_dirty_image(p ctx, *prisim_imaging_args a, p out_image, p out_wsum, *prisim_imaging_stats stats);
     ''',
+    'prisim_imaging32.h': '''
+        int prisim_dirty_image_f32(p ctx, *prisim_imaging_args a, p out_image, p out_wsum, *prisim_imaging_stats stats);
+    ''',
     'prisim_imclean.h': '''
         int prisim_clean_image(p ctx, *prisim_imclean_args a, p out_residual, p out_restored, p out_comp_pixel, p out_comp_flux, p out_ncomp,
             p out_status, p out_peak0, p out_wsum, *prisim_imclean_stats stats);
@@ -808,10 +813,10 @@ def _parse_prototypes(table):
 FUNCTIONS, HEADER_EXPORTS = _parse_prototypes(_PROTOTYPES)
 # the functions of each header (tests and tools import these names)
 (EXPORTS, CLEAN_EXPORTS, SUBBAND_EXPORTS, RUNS_EXPORTS, CLOSURE_EXPORTS, CPDELAY_EXPORTS, CPBINS_EXPORTS, CPDIFF_EXPORTS, CPFT_EXPORTS,
- CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMCLEAN_EXPORTS, MOSAIC_EXPORTS, MOSCLEAN_EXPORTS, CSCLEAN_EXPORTS,
- MOSCS_EXPORTS, GAINS_EXPORTS) = (
+ CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMAGING32_EXPORTS, IMCLEAN_EXPORTS, MOSAIC_EXPORTS, MOSCLEAN_EXPORTS,
+ CSCLEAN_EXPORTS, MOSCS_EXPORTS, GAINS_EXPORTS) = (
     HEADER_EXPORTS['prisim_%s.h' % h] for h in ('hip', 'clean', 'subband', 'runs', 'closure', 'cpdelay', 'cpbins', 'cpdiff', 'cpft', 'cpxps',
-                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imclean', 'mosaic', 'mosclean', 'csclean', 'moscs', 'gains'))
+                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imaging32', 'imclean', 'mosaic', 'mosclean', 'csclean', 'moscs', 'gains'))
 
 
 class PrisimHipError(RuntimeError):
@@ -1659,7 +1664,7 @@ class Context(object):
     PrisimImagingArgs = _PrisimImagingArgs
 
     def dirty_image(self, unitvec, rot, pc_dircos, baselines, freqs_hz, cube=None, weights=None, kind='dirty', chan_avg=False,
-                    aberr_beta=None, route='auto', budget_bytes=0):
+                    aberr_beta=None, route='auto', budget_bytes=0, precision='double'):
         """The dirty image (kind 'dirty') or the synthesized beam ('psf') at the given directions by the direct Fourier sum on the
         device (prisim_dirty_image): D[p][k] = sum_t sum_b w Re(V e^{+i phi}), phi = 2 pi f_k b . (s - s0) / c, over W[k] = sum w.
         unitvec: (npix, 3) unit vectors of the directions in their own frame (geometry.catalog_unitvec); rot: (nt, 3, 3) rotations of
@@ -1669,9 +1674,13 @@ class Context(object):
         nbl, nchan), finite and non-negative.  chan_avg: one image of the band instead of one per channel.  route: 'auto', 'direct'
         or 'stepped'; budget_bytes: device bytes of the streamed buffers (0: 1 GiB), which the result does not depend on.  Returns
         (image (npix, nchan) or (npix,), wsum (nchan,) or (1,), stats); a zero weight sum is NaN in the image; stats['resident']: the
-        resident cube was read."""
+        resident cube was read.  precision: 'double', or 'single' for the fp32 route (prisim_dirty_image_f32,
+        include/prisim_imaging32.h): the phases fp64, the phasors and partial sums fp32, within 5e-6 of the scale; it takes a uniform
+        grid and route 'auto' or 'stepped'.  stats['precision'] says which ran."""
         if kind not in IMAGING_KINDS:
             raise ValueError("kind must be 'dirty' or 'psf'")
+        if precision not in IMAGING_PRECISIONS:
+            raise ValueError("precision must be 'double' or 'single'")
         a = self.PrisimImagingArgs()
         npix, _, nchan, _, resident, keep = _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube if kind == 'dirty' else None,
                                                             weights, chan_avg, aberr_beta, route, budget_bytes)
@@ -1679,9 +1688,9 @@ class Context(object):
         image = NP.empty((npix,) if chan_avg else (npix, nchan), dtype=NP.float64)
         wsum = NP.empty(1 if chan_avg else nchan, dtype=NP.float64)
         st = self.PrisimImagingStats()
-        self._call('prisim_dirty_image', a=a, out_image=image, out_wsum=wsum, stats=st)
+        self._call(IMAGING_PRECISIONS[precision], a=a, out_image=image, out_wsum=wsum, stats=st)
         del keep
-        return image, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident and kind == 'dirty')
+        return image, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident and kind == 'dirty', precision=precision)
 
     # ---- beam-weighted mosaics of the snapshots (include/prisim_mosaic.h) ----
     PrisimMosaicStats = _PrisimMosaicStats

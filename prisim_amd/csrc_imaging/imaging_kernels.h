@@ -259,7 +259,7 @@ inline int imaging_preamble(prisim_ctx* ctx, const ImgView& v, ImgSetup& su) {
 }
 
 // why an ImagingPlan (that of prisim_mosaic_image too) cannot run, in full
-inline std::string plan_refusal(const ImagingPlan& pl) {
+template <typename Plan> inline std::string plan_refusal(const Plan& pl) {
   return std::string(pl.refusal) + " (one block of " + std::to_string(pl.block) + " pixels takes " + std::to_string(pl.block * pl.pixel_bytes) +
          " B, the workgroup " + std::to_string(pl.lds) + " B of LDS)";
 }

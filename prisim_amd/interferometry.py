@@ -2774,7 +2774,7 @@ class ApertureSynthesis(object):
     Attributes as in the reference (:9136-9163): ia, f, df, n_acc, lst, phase_center, phase_center_coords, pointing_center,
     pointing_coords, baselines, timestamp, latitude, blxyz, uvw_lambda, uvw, blc, trc, grid_blc, grid_trc, gridu, gridv, gridw,
     grid_ready; and image_stats, the statistics of the last image(), psf(), clean(), mosaic(), clean_mosaic() or
-    clean_cotton_schwab().
+    clean_cotton_schwab(); and precision, 'double' or 'single', the arithmetic of image() and psf() (see image()).
 
     Departures from the reference: setUVWgrid is not ported -- its grid comes from GRD.grid_3d, whose source is not part of the
     reference tree, and the direct transform needs no grid; grid_ready stays False.  genUVW with a 'radec' phase centre takes
@@ -2810,6 +2810,7 @@ class ApertureSynthesis(object):
         self.gridu, self.gridv, self.gridw = None, None, None
         self.grid_ready = False
         self.image_stats = None
+        self.precision = 'double'                                     # of image() and psf(): 'double', or 'single' for the fp32 route
 
     def genUVW(self):
         """(u, v, w) of every baseline phased to the phase centre of every snapshot: uvw_lambda (nbl, 3, n_acc) in metres and uvw
@@ -2924,10 +2925,23 @@ class ApertureSynthesis(object):
 
     def _synthesize(self, kind, directions, coords, datakey, weights, chan_avg, epoch, route, budget_bytes):
         ia = self.ia
+        precision = self.precision
+        if precision not in ('double', 'single'):
+            raise ValueError("precision must be 'double' or 'single'")
         uv, rot, beta, pc, w, cube = self._prepare(kind, directions, coords, datakey, weights, epoch, route)
+        single = {}
+        if precision == 'single':                                     # refused here, before any device work; 'double' calls as ever
+            if route == 'direct':
+                raise ValueError("precision='single' has no direct route: use route='auto' or 'stepped', or precision='double'")
+            f = NP.asarray(ia.channels, dtype=NP.float64).ravel()
+            line = f[0] + NP.arange(f.size) * ((f[-1] - f[0]) / (f.size - 1) if f.size > 1 else 0.0)
+            if not NP.all(NP.abs(f - line) <= 1e-7):                  # the uniform-grid rule of include/prisim_imaging.h
+                raise ValueError("precision='single' needs a uniform channel grid: use precision='double'")
+            single = {'precision': 'single'}
         image, wsum, st = ia._ctx.dirty_image(uv, rot, pc, ia._baselines_local(), ia.channels, cube=cube, weights=w, kind=kind,
-                                              chan_avg=bool(chan_avg), aberr_beta=beta, route=route, budget_bytes=int(budget_bytes or 0))
-        self.image_stats = dict(st, wsum=wsum)
+                                              chan_avg=bool(chan_avg), aberr_beta=beta, route=route, budget_bytes=int(budget_bytes or 0),
+                                              **single)
+        self.image_stats = dict(st, wsum=wsum, precision=precision)
         return image
 
     def image(self, directions, coords='dircos', datakey='noiseless', weights=None, chan_avg=False, epoch=None, route='auto',
@@ -2945,11 +2959,16 @@ class ApertureSynthesis(object):
                      lies on the device when the device slots are in step with skyvis_freq (reserve()); otherwise the cube is handed over.
         weights      None, (nbl,) or (nbl, nchan, n_acc): finite and non-negative.
         route        'auto', 'direct' or 'stepped' (include/prisim_imaging.h); budget_bytes: device bytes of the streamed buffers.
-        The entry's statistics, and 'wsum', are left in image_stats."""
+        The attribute `precision` of the object, 'double' by default, selects the arithmetic of image() and psf(): set to 'single' they
+        take the fp32 route (include/prisim_imaging32.h): every element within 5e-6 of sum w|V| / sum w of the fp64 image, the phases
+        still fp64 so that long baselines cost nothing.  It takes a uniform channel grid and route 'auto' or 'stepped'; anything else
+        is a ValueError before any device work.  It is an attribute and no keyword: the parameter lists of these methods are pinned.
+        The entry's statistics, 'wsum' and 'precision' are left in image_stats."""
         return self._synthesize('dirty', directions, coords, datakey, weights, chan_avg, epoch, route, budget_bytes)
 
     def psf(self, directions, coords='dircos', weights=None, chan_avg=False, epoch=None, route='auto', budget_bytes=None):
-        """The synthesized beam at the given directions: image() of V = 1, centred on every snapshot's phase centre, where it is 1."""
+        """The synthesized beam at the given directions: image() of V = 1, centred on every snapshot's phase centre, where it is 1.
+        The attribute `precision` selects the arithmetic as it does for image()."""
         return self._synthesize('psf', directions, coords, None, weights, chan_avg, epoch, route, budget_bytes)
 
     def mosaic(self, directions, coords='dircos', datakey='noiseless', weights=None, chan_avg=False, epoch=None, telescope=None,
