@@ -100,6 +100,8 @@ IMAGING_ROUTES = {PRISIM_IMAGE_DIRECT: 'direct', PRISIM_IMAGE_STEPPED: 'stepped'
 IMAGING_KINDS = {'dirty': PRISIM_IMAGE_DIRTY, 'psf': PRISIM_IMAGE_PSF}
 # ... and their fp32 route (include/prisim_imaging32.h, prisim_amd/csrc_imaging/imaging32.hip): the entry of each precision
 IMAGING_PRECISIONS = {'double': 'prisim_dirty_image', 'single': 'prisim_dirty_image_f32'}
+# ... and the two entries of the beam-weighted mosaic (include/prisim_mosaic.h, include/prisim_mosaic32.h)
+MOSAIC_PRECISIONS = {'double': 'prisim_mosaic_image', 'single': 'prisim_mosaic_image_f32'}
 
 # Hogbom CLEAN of dirty images with the exact beam (include/prisim_imclean.h, prisim_amd/csrc_imaging/imclean.hip)
 PRISIM_IMCLEAN_THRESHOLD, PRISIM_IMCLEAN_MAXITER, PRISIM_IMCLEAN_DEAD = 1, 2, 4
@@ -762,6 +764,10 @@ _PROTOTYPES = {
         int prisim_mosaic_image(p ctx, *prisim_mosaic_args a, p out_mosaic, p out_pb_eff, p out_num, p out_den, p out_wsum,
             *prisim_mosaic_stats stats);
     ''',
+    'prisim_mosaic32.h': '''
+        int prisim_mosaic_image_f32(p ctx, *prisim_mosaic_args a, p out_mosaic, p out_pb_eff, p out_num, p out_den, p out_wsum,
+            *prisim_mosaic_stats stats);
+    ''',
     'prisim_mosclean.h': '''
         int prisim_clean_mosaic(p ctx, *prisim_mosclean_args a, p out_residual, p out_restored, p out_residual_flat, p out_pb_eff, p out_num,
             p out_den, p out_wsum, p out_comp_pixel, p out_comp_flux, p out_ncomp, p out_status, p out_peak0, *prisim_mosclean_stats stats);
@@ -813,10 +819,11 @@ def _parse_prototypes(table):
 FUNCTIONS, HEADER_EXPORTS = _parse_prototypes(_PROTOTYPES)
 # the functions of each header (tests and tools import these names)
 (EXPORTS, CLEAN_EXPORTS, SUBBAND_EXPORTS, RUNS_EXPORTS, CLOSURE_EXPORTS, CPDELAY_EXPORTS, CPBINS_EXPORTS, CPDIFF_EXPORTS, CPFT_EXPORTS,
- CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMAGING32_EXPORTS, IMCLEAN_EXPORTS, MOSAIC_EXPORTS, MOSCLEAN_EXPORTS,
- CSCLEAN_EXPORTS, MOSCS_EXPORTS, GAINS_EXPORTS) = (
+ CPXPS_EXPORTS, CPAVG_EXPORTS, CPREAL_EXPORTS, ANTPOWER_EXPORTS, IMAGING_EXPORTS, IMAGING32_EXPORTS, IMCLEAN_EXPORTS, MOSAIC_EXPORTS, MOSAIC32_EXPORTS,
+ MOSCLEAN_EXPORTS, CSCLEAN_EXPORTS, MOSCS_EXPORTS, GAINS_EXPORTS) = (
     HEADER_EXPORTS['prisim_%s.h' % h] for h in ('hip', 'clean', 'subband', 'runs', 'closure', 'cpdelay', 'cpbins', 'cpdiff', 'cpft', 'cpxps',
-                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imaging32', 'imclean', 'mosaic', 'mosclean', 'csclean', 'moscs', 'gains'))
+                                                'cpavg', 'cpreal', 'antpower', 'imaging', 'imaging32', 'imclean', 'mosaic', 'mosaic32', 'mosclean',
+                                                'csclean', 'moscs', 'gains'))
 
 
 class PrisimHipError(RuntimeError):
@@ -1697,7 +1704,8 @@ class Context(object):
     PrisimMosaicArgs = _PrisimMosaicArgs
 
     def mosaic_image(self, unitvec, rot, pc_dircos, baselines, freqs_hz, beam_kind, diameter_m, beam_pc_dircos=(0.0, 0.0, 1.0), ext=None,
-                     cube=None, weights=None, chan_avg=False, aberr_beta=None, pbmin=0.1, route='auto', budget_bytes=0, want_sums=True):
+                     cube=None, weights=None, chan_avg=False, aberr_beta=None, pbmin=0.1, route='auto', budget_bytes=0, want_sums=True,
+                     precision='double'):
         """The beam-weighted linear mosaic of the snapshots at the given directions on the device (prisim_mosaic_image):
         sum_t A_t D_t / sum_t A_t^2 W_t with D_t the direct Fourier sum of snapshot t (dirty_image), W_t its weight sum and A_t the
         power pattern of the primary beam at the direction in that snapshot, 0 below the horizon.  The geometry, cube, weights,
@@ -1706,7 +1714,13 @@ class Context(object):
         (make_beam_ext), None, or a sequence of one dict per snapshot.  pbmin in [0, 1): a pixel whose
         effective beam sqrt(Q / Wtot) is below it is NaN; 0 masks only Q == 0.  Returns (mosaic (npix, nchan) or (npix,), num, den
         (npix, nchan) -- None without want_sums --, wsum (nchan,), stats); stats['pb_eff'] is the effective beam in the shape of the
-        mosaic and stats['resident'] whether the resident cube was read."""
+        mosaic and stats['resident'] whether the resident cube was read.  precision: 'double', or 'single' for the fp32 route
+        (prisim_mosaic_image_f32, include/prisim_mosaic32.h): every D_t formed as dirty_image forms it with precision='single', the
+        beam, the weight sums and the sums over t still fp64, so that den, wsum, pb_eff and the NaN positions have the bits of
+        'double' and num is within 5e-6 sum_t A_t sum_b w|V| of it; it takes a uniform grid and route 'auto' or 'stepped'.
+        stats['precision'] says which ran."""
+        if precision not in MOSAIC_PRECISIONS:
+            raise ValueError("precision must be 'double' or 'single'")
         a = self.PrisimMosaicArgs()
         npix, _, nchan, nt, resident, keep = _imaging_inputs(a, unitvec, rot, pc_dircos, baselines, freqs_hz, cube, weights, chan_avg, aberr_beta,
                                                              route, budget_bytes)
@@ -1717,9 +1731,9 @@ class Context(object):
         den = NP.empty((npix, nchan), dtype=NP.float64) if want_sums else None
         wsum = NP.empty(nchan, dtype=NP.float64)
         st = self.PrisimMosaicStats()
-        self._call('prisim_mosaic_image', a=a, out_mosaic=mosaic, out_pb_eff=pb_eff, out_num=num, out_den=den, out_wsum=wsum, stats=st)
+        self._call(MOSAIC_PRECISIONS[precision], a=a, out_mosaic=mosaic, out_pb_eff=pb_eff, out_num=num, out_den=den, out_wsum=wsum, stats=st)
         del keep, keep_ext
-        return mosaic, num, den, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident, pb_eff=pb_eff)
+        return mosaic, num, den, wsum, dict(_stats_dict(st, route=IMAGING_ROUTES), resident=resident, pb_eff=pb_eff, precision=precision)
 
     # ---- Hogbom CLEAN of dirty images with the exact beam (include/prisim_imclean.h) ----
     PrisimImcleanStats = _PrisimImcleanStats

@@ -2774,7 +2774,8 @@ class ApertureSynthesis(object):
     Attributes as in the reference (:9136-9163): ia, f, df, n_acc, lst, phase_center, phase_center_coords, pointing_center,
     pointing_coords, baselines, timestamp, latitude, blxyz, uvw_lambda, uvw, blc, trc, grid_blc, grid_trc, gridu, gridv, gridw,
     grid_ready; and image_stats, the statistics of the last image(), psf(), clean(), mosaic(), clean_mosaic() or
-    clean_cotton_schwab(); and precision, 'double' or 'single', the arithmetic of image() and psf() (see image()).
+    clean_cotton_schwab(); and precision, 'double' or 'single', the arithmetic of image(), psf() and mosaic() (see image()); the
+    clean*() methods do not read it and stay fp64.
 
     Departures from the reference: setUVWgrid is not ported -- its grid comes from GRD.grid_3d, whose source is not part of the
     reference tree, and the direct transform needs no grid; grid_ready stays False.  genUVW with a 'radec' phase centre takes
@@ -2810,7 +2811,7 @@ class ApertureSynthesis(object):
         self.gridu, self.gridv, self.gridw = None, None, None
         self.grid_ready = False
         self.image_stats = None
-        self.precision = 'double'                                     # of image() and psf(): 'double', or 'single' for the fp32 route
+        self.precision = 'double'                                     # of image(), psf() and mosaic(): 'double', or 'single' for the fp32 routes
 
     def genUVW(self):
         """(u, v, w) of every baseline phased to the phase centre of every snapshot: uvw_lambda (nbl, 3, n_acc) in metres and uvw
@@ -2923,21 +2924,26 @@ class ApertureSynthesis(object):
         pc = ia._pc_dircos(ia.phase_center, ia.phase_center_coords)
         return uv, rot, beta, pc, w, cube
 
-    def _synthesize(self, kind, directions, coords, datakey, weights, chan_avg, epoch, route, budget_bytes):
-        ia = self.ia
+    def _precision_keyword(self, route):
+        """(the attribute `precision`, the keyword that selects it at the context) for image(), psf() and mosaic(): {} for 'double',
+        which calls the context as ever; for 'single' what the fp32 entries refuse is refused here, before any device work."""
         precision = self.precision
         if precision not in ('double', 'single'):
             raise ValueError("precision must be 'double' or 'single'")
+        if precision == 'double':
+            return precision, {}
+        if route == 'direct':
+            raise ValueError("precision='single' has no direct route: use route='auto' or 'stepped', or precision='double'")
+        f = NP.asarray(self.ia.channels, dtype=NP.float64).ravel()
+        line = f[0] + NP.arange(f.size) * ((f[-1] - f[0]) / (f.size - 1) if f.size > 1 else 0.0)
+        if not NP.all(NP.abs(f - line) <= 1e-7):                      # the uniform-grid rule of include/prisim_imaging.h
+            raise ValueError("precision='single' needs a uniform channel grid: use precision='double'")
+        return precision, {'precision': 'single'}
+
+    def _synthesize(self, kind, directions, coords, datakey, weights, chan_avg, epoch, route, budget_bytes):
+        ia = self.ia
         uv, rot, beta, pc, w, cube = self._prepare(kind, directions, coords, datakey, weights, epoch, route)
-        single = {}
-        if precision == 'single':                                     # refused here, before any device work; 'double' calls as ever
-            if route == 'direct':
-                raise ValueError("precision='single' has no direct route: use route='auto' or 'stepped', or precision='double'")
-            f = NP.asarray(ia.channels, dtype=NP.float64).ravel()
-            line = f[0] + NP.arange(f.size) * ((f[-1] - f[0]) / (f.size - 1) if f.size > 1 else 0.0)
-            if not NP.all(NP.abs(f - line) <= 1e-7):                  # the uniform-grid rule of include/prisim_imaging.h
-                raise ValueError("precision='single' needs a uniform channel grid: use precision='double'")
-            single = {'precision': 'single'}
+        precision, single = self._precision_keyword(route)
         image, wsum, st = ia._ctx.dirty_image(uv, rot, pc, ia._baselines_local(), ia.channels, cube=cube, weights=w, kind=kind,
                                               chan_avg=bool(chan_avg), aberr_beta=beta, route=route, budget_bytes=int(budget_bytes or 0),
                                               **single)
@@ -2988,8 +2994,12 @@ class ApertureSynthesis(object):
                      goes to the device per snapshot.
         pbmin        in [0, 1): where the effective beam pb_eff = sqrt(sum_t A_t^2 W_t / sum_t W_t) is below it the mosaic is NaN (the
                      usual 'pblimit'; 0.1 is a convention, not a measured value).  0 masks only what no snapshot saw at all.
-        The noise of the mosaic goes as 1 / pb_eff.  num, den (npix, nchan), wsum (nchan,), pb_eff (the mosaic's shape) and the entry's
-        statistics are left in image_stats.
+        The noise of the mosaic goes as 1 / pb_eff.  num, den (npix, nchan), wsum (nchan,), pb_eff (the mosaic's shape), 'precision'
+        and the entry's statistics are left in image_stats.
+        The attribute `precision` of the object selects the arithmetic as it does for image(): set to 'single', every snapshot's sum
+        D_t takes the fp32 route (include/prisim_mosaic32.h) while the beam, the weight sums and the sums over t stay fp64, so den,
+        wsum, pb_eff and the mask have the bits of 'double' and num is within 5e-6 sum_t A_t sum_b w|V| of it.  It takes a uniform
+        channel grid and route 'auto' or 'stepped'; anything else is a ValueError before any device work.
 
         Raises NotImplementedError for an array with an external beam (set_external_beam) and for the apertures device_beam_spec
         does not carry (rect, square)."""
@@ -3000,11 +3010,12 @@ class ApertureSynthesis(object):
         if not (0.0 <= pbmin < 1.0):
             raise ValueError('pbmin must lie in [0, 1)')
         uv, rot, beta, pc, w, cube = self._prepare('dirty', directions, coords, datakey, weights, epoch, route)
+        precision, single = self._precision_keyword(route)
         kind, dia, bpc, ext = self._beam_specs(telescope, pb_info)
         image, num, den, wsum, st = ia._ctx.mosaic_image(uv, rot, pc, ia._baselines_local(), ia.channels, kind, dia, beam_pc_dircos=bpc,
                                                          ext=ext, cube=cube, weights=w, chan_avg=bool(chan_avg), aberr_beta=beta,
-                                                         pbmin=pbmin, route=route, budget_bytes=int(budget_bytes or 0))
-        self.image_stats = dict(st, num=num, den=den, wsum=wsum)
+                                                         pbmin=pbmin, route=route, budget_bytes=int(budget_bytes or 0), **single)
+        self.image_stats = dict(st, num=num, den=den, wsum=wsum, precision=precision)
         return image
 
     def _beam_specs(self, telescope, pb_info):
