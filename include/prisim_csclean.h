@@ -40,6 +40,17 @@
  * dd, the residual, Vres, P with the buffers of its half-plane, the lists, the cycle tables, the window and the scratch are resident
  * within `budget_bytes`; a call that does not fit is refused with the bytes it needs.
  *
+ * Accuracy of P.  With u = 2^-53 and N_delta = max|f| max_{t,b,di,dj} sum_i |b_i| sum_j |rot_t,ij| (|di rho_j| + |dj kappa_j|) / c, the
+ * largest phase of the lattice in cycles, every element of P is within
+ *     1e-12 + 2 pi u 13 N_delta            (14 for STEPPED, plus 2 pi N_delta / f times what the grid is off its line)
+ * of the exact sum.  It is N_delta that counts and NOT the baseline in wavelengths, unlike the dirty image: rho and kappa are differences
+ * of the given unit vectors, formed first and rounded relative to the difference, and every later operation (the two products, their
+ * sum, the rotation, b . delta / c, f tau) rounds relative to an offset, never to a vector of length 1.  A lattice that shrinks as
+ * the baselines grow keeps the P of short baselines: with N_delta = 88 cycles the deviation is below 1e-14 at 300 m, at 300 km and
+ * at 2400 km alike (N_b = 2e2, 2e5, 2e6), and on a fixed lattice it grows with N_delta, 9e-12 at N_delta = 9e4; some 0.15 * 2 pi u N_delta.
+ * The count is that of tests/mosaic_reference.py, which holds the device to it against a 40-digit reference.  The dirty images of the
+ * major cycles and the model visibilities (phi_j from the directions of the pixels) carry the law of prisim_imaging.h.
+ *
  * Deterministic: the sums of the dirty image and of P as prisim_dirty_image orders them; the peak searches are trees of
  * (|value|, index) pairs under an associative rule; a visibility is updated by one thread, components in list order.  No atomics.
  */

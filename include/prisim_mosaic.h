@@ -14,6 +14,15 @@
  * prisim_antpower.h, whose beam description (the fused analytic beam of prisim_hip_set_sky_analytic, with unit flux) it takes.  The sum
  * is deterministic: every (pixel, channel) adds its b terms in one thread, b ascending, and its snapshots in that same thread, t
  * ascending.  No atomic is used and no sum is split over workgroups: the outputs are bit-identical for any budget and stream count.
+ *
+ * Accuracy.  D_t is the sum of prisim_dirty_image and carries its law (prisim_imaging.h: 1e-11 + 2 pi u (13 N_b + 7 N') of the natural
+ * scale, N_b the longest baseline in wavelengths), the beam is within 1e-12 of the exact pattern, W_t has no phase in it.  So per element
+ *     |N - N_exact| <= sum_t (1e-11 + 2 pi u (13 N_b + 7 N'_t)) A_t sum_b w|V| + 1e-12 sum_{t,b} w|V|
+ *     |Q - Q_exact| <= 1e-11 sum_t A_t^2 W_t + 2e-12 sum_t A_t W_t
+ * and like the image the mosaic keeps 1e-11 of its scale to baselines of some 1e5 wavelengths as measured (7e2 by the bound), however
+ * narrow the field.  tests/mosaic_reference.py counts this and holds the device to it against a 40-digit reference from 300 m to
+ * 2400 km; measured, N is at most 0.09 of the bound and Q at 1e-3 of its own.  The horizon test and the mask compare rounded numbers:
+ * a direction within some 1e-15 of the horizon, or a Q within rounding of pbmin^2 Wtot, may fall on either side.
  */
 #ifndef PRISIM_MOSAIC_H
 #define PRISIM_MOSAIC_H

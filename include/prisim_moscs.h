@@ -46,6 +46,11 @@
  * prisim_clean_mosaic holds, and Vres, P with the buffers of its half-plane and its weight sums, the cycle state and tables, the
  * scale and the scratch of the GLOBAL route; a call that does not fit is refused with the bytes it needs.
  *
+ * Accuracy.  P is that of prisim_csclean.h and carries its law: 1e-12 + 2 pi u 13 N_delta, on the phase of the lattice and not on the
+ * baseline in wavelengths.  The numerator of every major cycle carries the law of prisim_mosaic.h, and a component's visibilities
+ * A[t][q] a e^{-i phi_q} the chain of its pixel's direction (prisim_imaging.h) and 1e-12 |a| of the beam.  tests/mosaic_reference.py
+ * holds all three to a 40-digit reference from 300 m to 2400 km.
+ *
  * Deterministic: one GPU, one stream, no atomics; every sum in the order of the entries it is taken from.
  */
 #ifndef PRISIM_MOSCS_H

@@ -115,9 +115,12 @@ def clean(pb, P, ny, nx, gain, maxiter, threshold, relative, depth, cycle_niter,
             'ncycles': ncycles, 'cycle_ncomp': cn, 'cycle_peak': cpk, 'vres': pb.v - vm}
 
 
-def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_niter, max_major):
+def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_niter, max_major, bound=None):
     """Follows the lists and cycle tables of `got` (the dict of Context.clean_image_cs, or of clean()) and asserts every decision and
-    the results.  Returns the largest deviation met, as a fraction of its tolerance."""
+    the results.  Returns the largest deviation met, as a fraction of its tolerance.  bound: None for BOUND, or a pair of (nc,) arrays,
+    the factor of the scale and that of the sum of |a| in the tolerance, as imclean_checker.replay takes them (tests/mosaic_reference.py
+    says which they are at long baselines); the second also holds the residual visibilities."""
+    b_scale, b_spent = (BOUND, BOUND) if bound is None else bound
     nc, npix = pb.nc, pb.npix
     cap = cycle_niter if cycle_niter and cycle_niter > 0 else None
     cp, cf, count, status, ncyc, cn, cpk = (NP.asarray(got[n]) for n in ('comp_pixel', 'comp_flux', 'ncomp', 'status', 'ncycles', 'cycle_ncomp',
@@ -134,7 +137,7 @@ def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_
     worst = 0.0
 
     def tol():
-        return BOUND * (scale + spent)
+        return BOUND * (scale + spent) if bound is None else b_scale * scale + b_spent * spent
 
     def note(dev, t):
         nonlocal worst
@@ -174,7 +177,7 @@ def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_
             L = max(thr[k], depth * pc)
             r = R[:, k].copy()
             for j in range(held, n1):
-                tk = BOUND * (scale[k] + spent[k])
+                tk = tol()[k]
                 v, _ = _peak1(pb, r)
                 q, a = int(cp[k, j]), cf[k, j]
                 assert 0 <= q < npix and pb.window[q], ('a pick outside the window', k, j)
@@ -187,7 +190,7 @@ def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_
                 vm += pb.component_vis(k, q, a)
                 spent[k] += abs(a)
             if not ((cap is not None and n1 - held == cap) or n1 == maxiter):
-                tk = BOUND * (scale[k] + spent[k])
+                tk = tol()[k]
                 v, _ = _peak1(pb, r)
                 assert v <= L + 2 * tk, ('a cycle ended early', k, c, v, L)
                 note(max(v - L, 0.0), 2 * tk)
@@ -201,7 +204,7 @@ def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_
     if got.get('vres') is not None:
         vres = NP.asarray(got['vres'])
         assert vres.shape == pb.v.shape
-        bound = BOUND * (NP.abs(pb.v).max(axis=(0, 1)) + (spent[0] if pb.chan_avg else spent))
+        bound = NP.max(b_spent) * (NP.abs(pb.v).max(axis=(0, 1)) + spent[0]) if pb.chan_avg else b_spent * (NP.abs(pb.v).max(axis=(0, 1)) + spent)
         dev = NP.abs(vres - (pb.v - vm)).max(axis=(0, 1))
         assert NP.all(dev <= bound), ('the residual visibilities against V - model', float(NP.max(dev / bound)))
         note(dev, bound)

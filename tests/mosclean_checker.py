@@ -132,11 +132,14 @@ class Problem(object):
         c = NP.einsum('tbk->k', self.w * NP.abs(self.v - vm) ** 2)
         return NP.array([c.sum()]) if self.chan_avg else c
 
-    def tolerances(self, RN, spent_q, spent):
+    def tolerances(self, RN, spent_q, spent, bound=None):
         """(tol_N (npix, nchan), tol_F (npix, nc), the largest tol_F over the searched pixels (nc,)).  spent_q (nt, nchan): the sum over
-        the components so far of |a_c| A[t][q_c][k]; spent (nchan,): of |a_c|."""
+        the components so far of |a_c| A[t][q_c][k]; spent (nchan,): of |a_c|.  bound: None for BOUND, or a pair of (nt, nchan) arrays
+        in its place, the factor of sum_b w|V| and that of the model's scale (tests/mosaic_reference.py derives them)."""
         scale = self.absV + self.Wt * spent_q                                          # (nt, nchan)
-        tol_N = BOUND * NP.einsum('tpk,tk->pk', self.A, scale) + \
+        sums = BOUND * NP.einsum('tpk,tk->pk', self.A, scale) if bound is None else \
+            NP.einsum('tpk,tk->pk', self.A, bound[0] * self.absV + bound[1] * (self.Wt * spent_q))
+        tol_N = sums + \
             BEAM_BOUND * (scale.sum(axis=0)[NP.newaxis, :] + NP.einsum('tpk,tk->pk', self.A, self.Wt * spent[NP.newaxis, :]))
         with NP.errstate(invalid='ignore', divide='ignore'):
             F = self.flat(RN)
@@ -200,9 +203,9 @@ def clean(pb, gain, maxiter, threshold, relative, costs=None):
     return pb.outputs(RN, cp, cf, count, status, peak0)
 
 
-def replay(pb, got, gain, maxiter, threshold, relative):
+def replay(pb, got, gain, maxiter, threshold, relative, bound=None):
     """Follows the lists of `got` (the dict of Context.clean_mosaic, or of clean()) and asserts every decision and the results.
-    Returns the largest deviation met, as a fraction of its tolerance."""
+    Returns the largest deviation met, as a fraction of its tolerance.  bound: what Problem.tolerances takes."""
     nc, npix = pb.nc, pb.npix
     cp, cf, count, status = (NP.asarray(got[n]) for n in ('comp_pixel', 'comp_flux', 'ncomp', 'status'))
     assert cp.shape == cf.shape and cp.shape[0] == nc and count.shape == (nc,) and status.shape == (nc,)
@@ -222,7 +225,7 @@ def replay(pb, got, gain, maxiter, threshold, relative):
             with NP.errstate(invalid='ignore', divide='ignore'):
                 worst = max(worst, float(NP.max(NP.where(t > 0.0, dev / t, NP.where(dev > 0.0, NP.inf, 0.0)))))
 
-    tol_N, tol_F, tmax = pb.tolerances(RN, spent_q, spent)
+    tol_N, tol_F, tmax = pb.tolerances(RN, spent_q, spent, bound)
     peak0, _ = pb.peak(pb.flat(RN))
     got0 = NP.asarray(got['peak0'], dtype=NP.float64)
     seen = live & ~empty
@@ -235,7 +238,7 @@ def replay(pb, got, gain, maxiter, threshold, relative):
     for i in range(cp.shape[1] + 1):
         F = pb.flat(RN)
         peak, _ = pb.peak(F)
-        tol_N, tol_F, tmax = pb.tolerances(RN, spent_q, spent)
+        tol_N, tol_F, tmax = pb.tolerances(RN, spent_q, spent, bound)
         going = NP.flatnonzero(seen & (count > i))
         for k in NP.flatnonzero(seen & (count == i)):
             if status[k] == THRESHOLD:
@@ -266,7 +269,7 @@ def replay(pb, got, gain, maxiter, threshold, relative):
             ks = slice(None) if pb.chan_avg else slice(k, k + 1)
             spent_q[:, ks] += abs(a) * pb.A[:, q, ks]
             spent[ks] += abs(a)
-    tol_N, _, _ = pb.tolerances(RN, spent_q, spent)
+    tol_N, _, _ = pb.tolerances(RN, spent_q, spent, bound)
     num, den, wsum = (NP.asarray(got[n], dtype=NP.float64) for n in ('num', 'den', 'wsum'))
     assert num.shape == den.shape == (npix, pb.nchan) and wsum.shape == (pb.nchan,)
     dev = NP.abs(num - RN)

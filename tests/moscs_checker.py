@@ -65,15 +65,16 @@ def _spend(pb, spent_q, spent, k, q, a):
     spent[ks] += abs(a)
 
 
-def channel_tolerance(pb, RN, k):
+def channel_tolerance(pb, RN, k, bound=None):
     """Problem.tolerances(RN, spent_q, spent) for image channel k alone, as a function of (spent_q, spent): (tol_F[:, k], tmax[k]).
     The same expressions on the channel's own columns, so that a minor cycle of many components does not form the bounds of every
     other channel once per component (tests/test_moscs.py holds the two against each other)."""
     if pb.chan_avg:
         def whole(spent_q, spent):
-            _, tol_F, tmax = pb.tolerances(RN, spent_q, spent)
+            _, tol_F, tmax = pb.tolerances(RN, spent_q, spent, bound)
             return tol_F[:, 0], tmax[0]
         return whole
+    b_scale, b_spent = (b * NP.ones((pb.nt, pb.nchan)) for b in ((BOUND, BOUND) if bound is None else bound))
     Ak = NP.ascontiguousarray(pb.A[:, :, k])                                        # (nt, npix)
     AW = pb.Wt[:, k].dot(Ak)
     srch = pb.search[:, k]
@@ -83,7 +84,8 @@ def channel_tolerance(pb, RN, k):
 
     def own(spent_q, spent):
         scale = pb.absV[:, k] + pb.Wt[:, k] * spent_q[:, k]
-        tol_N = BOUND * scale.dot(Ak) + BEAM_BOUND * (scale.sum() + AW * spent[k])
+        sums = BOUND * scale.dot(Ak) if bound is None else (b_scale[:, k] * pb.absV[:, k] + b_spent[:, k] * (pb.Wt[:, k] * spent_q[:, k])).dot(Ak)
+        tol_N = sums + BEAM_BOUND * (scale.sum() + AW * spent[k])
         with NP.errstate(invalid='ignore'):
             tol_F = tol_N * inv + fterm
         return tol_F, (float(NP.max(tol_F[srch])) if srch.any() else 0.0)
@@ -153,9 +155,11 @@ def clean(pb, P, ny, nx, gain, maxiter, threshold, relative, depth, cycle_niter,
     return out
 
 
-def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_niter, max_major):
+def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_niter, max_major, bound=None, psf_bound=None):
     """Follows the lists and cycle tables of `got` (the dict of Context.clean_mosaic_cs, or of clean()) and asserts every decision
-    and the results.  Returns the largest deviation met, as a fraction of its tolerance."""
+    and the results.  Returns the largest deviation met, as a fraction of its tolerance.  bound: what mosclean_checker's
+    Problem.tolerances takes, its second factor (the largest over the snapshots) also for the residual visibilities; psf_bound: (nc,)
+    in place of PSF_BOUND (tests/mosaic_reference.py derives both)."""
     nc, npix = pb.nc, pb.npix
     cap = cycle_niter if cycle_niter and cycle_niter > 0 else None
     cp, cf, count, status, ncyc, cn, cpk = (NP.asarray(got[n]) for n in ('comp_pixel', 'comp_flux', 'ncomp', 'status', 'ncycles', 'cycle_ncomp',
@@ -192,7 +196,7 @@ def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_
     for c in range(most + 1):
         F = pb.flat(RN)
         peak, _ = pb.peak(F)
-        _, _, tmax = pb.tolerances(RN, spent_q, spent)
+        _, _, tmax = pb.tolerances(RN, spent_q, spent, bound)
         # the components of this cycle are added to these as they are appended; a channel's own columns alone bear on its tolerance
         run_q, run = spent_q.copy(), spent.copy()
         for k in NP.flatnonzero(seen & (ncyc >= c)):
@@ -220,7 +224,7 @@ def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_
             assert held < n1 <= min(maxiter, count[k]) and (cap is None or n1 - held <= cap), ('the components of a cycle', k, c, held, n1)
             L = max(thr[k], depth * pc)
             r = F[:, k].copy()
-            tolerance = channel_tolerance(pb, RN, k)
+            tolerance = channel_tolerance(pb, RN, k, bound)
             for j in range(held, n1):
                 tF, tm = tolerance(run_q, run)
                 v, _ = _peak1(pb, r, k)
@@ -244,7 +248,7 @@ def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_
                 note(max(v - L, 0.0), 2 * tm)
         spent_q, spent = run_q, run
         RN = pb.numerator(pb.v - vm)
-    tol_N, _, _ = pb.tolerances(RN, spent_q, spent)
+    tol_N, _, _ = pb.tolerances(RN, spent_q, spent, bound)
     num, den, wsum = (NP.asarray(got[n], dtype=NP.float64) for n in ('num', 'den', 'wsum'))
     assert num.shape == den.shape == (npix, pb.nchan) and wsum.shape == (pb.nchan,)
     dev = NP.abs(num - RN)
@@ -271,14 +275,16 @@ def replay(pb, P, ny, nx, got, gain, maxiter, threshold, relative, depth, cycle_
     if got.get('vres') is not None:
         vres = NP.asarray(got['vres'])
         assert vres.shape == pb.v.shape
-        bound = BOUND * (NP.abs(pb.v).max(axis=(0, 1)) + spent) + BEAM_BOUND * spent
+        b_vis = BOUND if bound is None else NP.max(bound[1] * NP.ones((pb.nt, pb.nchan)), axis=0)
+        vbound = b_vis * (NP.abs(pb.v).max(axis=(0, 1)) + spent) + BEAM_BOUND * spent
         dev = NP.abs(vres - (pb.v - vm)).max(axis=(0, 1))
-        assert NP.all(dev <= bound), ('the residual visibilities against V - model', float(NP.max(dev / bound)))
-        note(dev, bound)
+        assert NP.all(dev <= vbound), ('the residual visibilities against V - model', float(NP.max(dev / vbound)))
+        note(dev, vbound)
     if got.get('psf') is not None:
         psf = NP.asarray(got['psf'], dtype=NP.float64)
         assert psf.shape == P.shape
+        pbound = NP.full(nc, PSF_BOUND) if psf_bound is None else NP.asarray(psf_bound, dtype=NP.float64) * NP.ones(nc)
         dev = NP.abs(psf - P)[live]
-        assert NP.all(dev <= PSF_BOUND), ('P against the checker\'s', float(NP.max(dev)))
-        note(dev, PSF_BOUND)
+        assert NP.all(dev <= pbound[live, None, None]), ('P against the checker\'s', float(NP.max(dev / pbound[live, None, None])))
+        note(dev, pbound[live, None, None])
     return worst

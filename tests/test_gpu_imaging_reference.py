@@ -9,7 +9,8 @@ of one row, a second tile of one channel and a ragged block; three tiles and a s
 entries (tests/test_gpu_mosaic.py, test_gpu_imclean.py, test_gpu_csclean.py) carry what is held here over to the mosaic and the CLEANs
 at the 300 km decade as well.
 
-Out of scope: prisim_clean_mosaic and the Cotton-Schwab replays against this reference (their lattice beam needs one of its own)."""
+The mosaic with a beam that is not 1, its fp32 route, prisim_clean_mosaic and the Cotton-Schwab entries with their lattice beam P are
+held at the same baselines by tests/test_gpu_mosaic_reference.py against tests/mosaic_reference.py, which builds on this reference."""
 import os
 import sys
 
